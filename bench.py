@@ -6,11 +6,17 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `value` is the whole-job images/sec with inputs resident in HBM.
-Beside it: `roofline` for the dominant kernel class (the MFMA forward/data-gradient GEMM),
-measured live with HIP events on the launch stream in extra, untimed steps; and
-`cpu_baseline`, the CPU oracle (oracle/, a port of the reference's arithmetic) timed on this
-host's cores on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  `value` is the whole-job images/sec with inputs resident in HBM,
+`ms_per_step` the time of one timed step.  A plain run sets up, warms up, times the K steps and
+prints the line; `--dump-outputs DIR` also writes, after the timed steps, what one step of the timed path
+(AdamW update included) computes from the seeded weights and inputs (.npy files, the same every run up
+to rounding).
+`--full` adds everything else, in extra untimed work after the timed steps: the second leg
+(`config3_n1` at N = 1, `weak256` at N > 1), the data-parallel no_sync leg and reducer telemetry,
+`roofline` for the dominant kernel class (the MFMA forward/data-gradient GEMM), measured live with
+HIP events on the launch stream; and `cpu_baseline`, the CPU oracle (oracle/, a port of the
+reference's arithmetic) timed on this host's cores on a bounded sample of the same workload, with
+its loss check against the timed model.
 """
 import argparse
 import ctypes as C
@@ -59,7 +65,7 @@ def host_cores():
     return max(1, min(n, int(os.environ.get("LNX_CPU_CORES", "16"))))
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -99,7 +105,18 @@ def parse():
                     help="skip the warm-up comparison of the two backward schedules (weight-gradient stream on / off) and keep the library default (on)")
     ap.add_argument("--cpu-batch", type=int, default=16)
     ap.add_argument("--profile-steps", type=int, default=3)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg: the second leg, the data-parallel no_sync leg and telemetry, the live per-kernel profile "
+                         "(roofline, kernels, rope_blocks) and the CPU oracle baseline with its loss check.  Off: only what `value` needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more from the seeded initial weights (fresh optimizer state, the "
+                         "leg's seeded resident inputs, also with --host-input / --flat-file) and write what it computed to DIR/<name>.npy "
+                         "(float32): the loss, the logits of every task, and fixed, seeded samples of the gradients the optimizer was given and "
+                         "of the parameters after its update; the timed run's own state is restored afterwards")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.eval_iters < 1:
+        ap.error("--steps and --eval-iters must be at least 1: the result line is a rate over the timed steps")
+    return args
 
 
 def make_model(args):
@@ -133,6 +150,37 @@ def committed_traffic():
         return json.load(fh)["bytes_per_launch"], "profiles/" + best[1]
 
 
+DUMP_SAMPLE = 1 << 20  # elements of the gradient and parameter samples: 4 MB each in float32
+
+
+def dump_outputs(out_dir, out, loss=None, params=(), grads=None):
+    """`--dump-outputs DIR`: what a step computed, as float32 .npy files -- `loss`, `logits_<task>` and, for a training step,
+    `grads_sample` (the gradients the optimizer was given; `grads`, default the parameters' .grad) and `params_sample` (the
+    parameters after the optimizer's update): the same DUMP_SAMPLE positions (seeded, sorted) of all parameters flattened in model
+    order.  Run to run, the gradients differ only in the float atomics' summation order.  A parameter's first AdamW update is
+    lr * g / (|g| + eps): rounding-level too, except where that noise flips the sign of a gradient |g| >~ eps, which moves the
+    parameter by at most 2 lr."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if loss is not None:
+        arrays["loss"] = loss.detach().float().reshape(1)
+    for t, v in out.items():
+        arrays[f"logits_{t}"] = v.detach().float()
+    if params:
+        n = sum(p_.numel() for p_ in params)
+        idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(0)).sort().values
+        idx = idx.to(params[0].device)
+        grads = [p_.grad for p_ in params] if grads is None else grads
+        if any(g_ is not None for g_ in grads):  # (a parameter without a gradient counts as zeros)
+            arrays["grads_sample"] = torch.cat([(g_ if g_ is not None else torch.zeros_like(p_)).detach().float().reshape(-1) for p_, g_ in zip(params, grads)])[idx]
+        arrays["params_sample"] = torch.cat([p_.detach().float().reshape(-1) for p_ in params])[idx]
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.cpu().numpy().astype(np.float32))
+    log(f"outputs written to {out_dir}: {', '.join(sorted(arrays))}")
+
+
 def eval_throughput(args):
     """`--eval`: inference images/sec measured the way the reference's own tool measures it (evaluation/throughput_tester.py:56-90,
     inputs as evaluation/synthetic_data.py:6-22): model in eval mode under no_grad, uniform-random images and metadata resident on
@@ -141,27 +189,31 @@ def eval_throughput(args):
     reference is importable; this is the same protocol for the GPU box, where it is not.)  One JSON line; `value` = best batch."""
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
+    torch.manual_seed(42)
     _, model = make_model(args)
     model = model.to(dev).eval()
     model.set_compute_dtype(args.dtype)
     meta_width = sum(model.meta_dims)
     rows = []
+    g = torch.Generator(device=dev).manual_seed(42)
     with torch.no_grad():
         for bs in (int(b) for b in args.eval_batches.split(",")):
-            x = torch.rand(bs, 3, args.img, args.img, device=dev)
-            meta = torch.rand(bs, meta_width, device=dev) if meta_width else None
+            x = torch.rand(bs, 3, args.img, args.img, device=dev, generator=g)
+            meta = torch.rand(bs, meta_width, device=dev, generator=g) if meta_width else None
             for _ in range(args.eval_warmup):
                 model(x, meta)
             torch.cuda.reset_peak_memory_stats(dev)
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
             for _ in range(args.eval_iters):
-                model(x, meta)
+                out = model(x, meta)
             torch.cuda.synchronize(dev)
             sec = time.perf_counter() - t0
             rows.append({"batch_size": bs, "imgs_per_sec": round(bs * args.eval_iters / sec, 3), "ms_per_call": round(sec / args.eval_iters * 1e3, 3),
                          "torch_peak_alloc_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 3)})
             log(f"eval batch {bs}: {rows[-1]['imgs_per_sec']:.0f} img/s")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)  # the last timed call: the last batch size's logits
     best = max(rows, key=lambda r: r["imgs_per_sec"])
     print(json.dumps({
         "metric": f"images/sec (eval forward, no_grad) mFormerV1_{args.arch} 3x{args.img}x{args.img}", "value": best["imgs_per_sec"],
@@ -379,6 +431,16 @@ def legs_for(n_gpus, batch):
     return [("config2", 256), ("config3_n1", 128)] if n_gpus == 1 else [("config3", 128), ("weak256", 256)]
 
 
+def legs_to_time(args, world):
+    """The legs this run times: the first is `value`; the others only with --full."""
+    legs = legs_for(2 if (args.force_dp and world == 1) else world, args.batch)  # --force-dp: the N > 1 legs rehearsed on one GPU
+    if world == 1 and not args.force_dp and len(legs) > 1 and (args.arch != "sm" or args.img != 224 or args.host_input or args.flat_file or args.drop_in or args.recompute):
+        legs = legs[:1]  # config3_n1 belongs to the headline workload only
+    if not args.full:
+        legs = legs[:1]  # a plain run times the leg of `value` and nothing else
+    return legs
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -390,9 +452,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one process per GPU (python bench.py --gpus N starts them itself)")
     if args.eval:
         return eval_throughput(args)
-    legs = legs_for(2 if (args.force_dp and world == 1) else world, args.batch)  # --force-dp: the N > 1 legs rehearsed on one GPU
-    if world == 1 and not args.force_dp and len(legs) > 1 and (args.arch != "sm" or args.img != 224 or args.host_input or args.flat_file or args.drop_in or args.recompute):
-        legs = legs[:1]  # config3_n1 belongs to the headline workload only
+    legs = legs_to_time(args, world)
     rehearsal = bool(args.rehearse_one_gpu and world > 1)
     if rehearsal:
         local = 0  # every rank on the one card
@@ -458,12 +518,53 @@ def main():
 
     params = [p_ for p_ in model.parameters() if p_.requires_grad]
     cleanup = []
+    keep_out = bool(args.dump_outputs) and rank == 0
+    init = None
+    if args.dump_outputs:
+        # where the --dump-outputs step starts: the seeded weights (after DataParallel's broadcast) and this point's RNG state
+        init = {"params": [p_.detach().clone() for p_ in params], "rng": torch.cuda.get_rng_state(dev)}
+
+    def replay_and_dump(step, state):
+        """--dump-outputs: the timed step (forward, loss, backward, optimizer update) once more, from `init` with an empty optimizer
+        state, on the leg's seeded batch -- every rank (the collectives need them all), rank 0 writes.  Why not the last timed step: the
+        weight-gradient kernels sum with float atomics, and every AdamW step turns that last-bit noise into moves of up to 2 lr for
+        parameters with near-zero gradients; compounded over W + K steps (and the calibration's), two runs' last-step logits differ
+        by up to ~0.4 and their losses by ~1e-3 relative -- not a comparison of two builds output for output.  From a fixed state one
+        step reproduces to rounding.  The timed run's parameters, optimizer state, RNG state and batch are put back afterwards."""
+        import collections
+
+        keep = [p_.detach().clone() for p_ in params]
+        rng = torch.cuda.get_rng_state(dev)
+        batch = (state["x"], state["meta"], state["tg"])
+        with torch.no_grad():
+            for p_, v in zip(params, init["params"]):
+                p_.copy_(v)
+        if opt is not None:
+            opt_state, opt.state = opt.state, collections.defaultdict(dict)
+        torch.cuda.set_rng_state(init["rng"], dev)
+        state["x"], state["meta"], state["tg"] = state["inputs0"]
+        if rank == 0 and (args.host_input or args.flat_file):
+            log("--dump-outputs: the replayed step reads the leg's seeded batch resident in HBM, not a batch from the host feed")
+        loss = step(replay=True)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, state["out"], loss, params, state.pop("grads", None))
+        with torch.no_grad():
+            for p_, v in zip(params, keep):
+                p_.copy_(v)
+        if opt is not None:
+            opt.state = opt_state
+        torch.cuda.set_rng_state(rng, dev)
+        state["x"], state["meta"], state["tg"] = batch
+        torch.cuda.synchronize()
 
     def make_step(B):
         """Inputs of one leg (resident in HBM unless --host-input / --flat-file) and the step function over them."""
         g = torch.Generator(device=dev).manual_seed(42 + rank)
         state = {"x": torch.rand(B, 3, args.img, args.img, device=dev, generator=g), "meta": torch.rand(B, 5, device=dev, generator=g),
                  "tg": {t: torch.randint(1, c, (B,), device=dev, generator=g) for t, c in TASKS}}
+        if args.dump_outputs:
+            state["inputs0"] = (state["x"], state["meta"], state["tg"])  # the seeded batch the --dump-outputs step replays
         feed = None
         if args.flat_file:
             import queue
@@ -528,22 +629,28 @@ def main():
 
             feed = iter(DevicePrefetcher(cycle(), dev))
 
-        def step():
-            if feed is not None:
+        def step(replay=False):
+            if feed is not None and not replay:
                 state["x"], state["meta"], state["tg"] = next(feed)
             x, meta, tg = state["x"], state["meta"], state["tg"]
             if args.drop_in:
                 # the reference's step glue (train.py:147-176,279-316) around the drop-in model, torch ops only
                 out = net(x, meta)
+                if keep_out:
+                    state["out"] = {t: v.detach() for t, v in out.items()}
                 loss = sum(F.cross_entropy(out[t].float(), tg[t]) for t, _ in TASKS)
                 loss.backward()
                 torch.nn.utils.clip_grad_norm_(params, 1.0)
+                if replay:  # (--dump-outputs) the gradients the optimizer is given: zero_grad below sets them to None
+                    state["grads"] = [p_.grad.detach().clone() if p_.grad is not None else None for p_ in params]
                 if opt is not None:
                     opt.step()
                     opt.zero_grad(set_to_none=True)
                 return loss
             model.zero_grad(set_to_none=True)
             out = net(x, meta)
+            if keep_out:
+                state["out"] = {t: v.detach() for t, v in out.items()}  # (--dump-outputs only: the graph is not kept alive)
             loss = multitask_cross_entropy(out, tg)  # sum over the 4 tasks of the batch-mean CE: one HIP launch for all tasks
             loss.backward()
             if opt is not None:
@@ -624,10 +731,12 @@ def main():
                "images_per_sec": round(world * B * args.steps / dt, 2), "host_enqueue_ms_per_step": round(host_dt / args.steps * 1e3, 3),
                "loss": round(float(loss.item()), 4), "step": step, "state": state, "backward_schedule": sched}
         log(f"leg {name}: timed {args.steps} steps: {res['ms_per_step']:.2f} ms/step, {res['images_per_sec']:.0f} img/s")
+        if args.dump_outputs and name == legs[0][0]:
+            replay_and_dump(step, state)
         # ---- data parallel only: n1_equiv = what ONE GPU does alone at this per-GPU batch (the same steps under no_sync: no
         # gradient collective is issued), exposed_allreduce_ms = step time with collectives - without, and
         # scaling_efficiency = images/sec / (n_gpus * n1_equiv): all three from this one run, at this leg's batch
-        if dist and hasattr(net, "no_sync"):
+        if args.full and dist and hasattr(net, "no_sync"):
             k = max(3, min(args.steps, 10))
             with net.no_sync():
                 for _ in range(2):
@@ -665,7 +774,7 @@ def main():
 
     # ---- data parallel: stream budget and per-bucket issue -> done times (3 untimed steps with the reducer's telemetry on, all ranks) ----
     dp_diag = None
-    if dist and hasattr(net, "bucket_report"):
+    if args.full and dist and hasattr(net, "bucket_report"):
         net.telemetry = True
         for _ in range(3):
             step()
@@ -682,7 +791,7 @@ def main():
     roofline, kernels, rope = None, {}, None
     if head["backward_schedule"]:  # (a later leg's calibration may have left the other schedule set)
         model.set_wgrad_stream(head["backward_schedule"]["weight_gradient_stream"] == "on")
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         roofline, kernels, rope = live_profile(args, model, state, multitask_cross_entropy, ips / world)
 
     if dist:
@@ -696,7 +805,7 @@ def main():
             dist.destroy_process_group()
         return
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         log("kernel profile done; timing the CPU oracle")
 
         def gpu_loss(sd, x, meta, tg):

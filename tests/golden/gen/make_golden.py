@@ -23,6 +23,8 @@ plus per-op known answers (cos table, LN variants, dwconv, softmax-attention, ag
   soft_ce     the reference's TaxonomyAwareLabelSmoothingCE (per-sample losses + logits gradient)
   train_step  two optimizer steps of tiny_a (CE loss, clip_grad_norm_, AdamW): losses, grad norms, deltas.
   hier_loss   weighted_hierarchical_loss (null masking, class weights, task weights) + build_taxonomy_smoothing_matrix.
+  aug_policies  the AutoAugment policy tables of get_policy, entry by entry (JSON).
+  registry      state_dict / parameter layout and metadata of the reference-built mFormerV1_sm with ConditionalClassifier heads (JSON).
 """
 import os
 import sys
@@ -699,6 +701,44 @@ def per_op_known_answers():
     print("[per_op] written")
 
 
+def aug_policy_tables():
+    """aug_policies.json: the reference's AutoAugment policy tables (aug/policies.py get_policy), entry by entry, for every
+    policy name linnaeus_amd.aug.get_policy knows."""
+    import json
+
+    from linnaeus.aug.policies import get_policy
+
+    tables = {n: [[list(op) for op in sub] for sub in get_policy(n, {})] for n in ("original", "originalr", "v0r", "3a", "hybrid_v0")}
+    with open(os.path.join(OUT, "aug_policies.json"), "w") as f:
+        json.dump(tables, f, indent=0)
+    print(f"[aug_policies] {', '.join(f'{n}: {len(t)}' for n, t in tables.items())}")
+
+
+def registry_facts():
+    """registry_sm.json: what the reference's build_model() builds for mFormerV1_sm @224 with three ConditionalClassifier heads on a
+    real TaxonomyTree -- state_dict names, shapes and dtypes in order, parameter names, the two metadata dicts and the head keys:
+    the layout a model registered in its place must reproduce."""
+    import json
+
+    from linnaeus.utils.taxonomy.taxonomy_tree import TaxonomyTree
+
+    c = base_cfg(224)
+    tasks = ["taxa_L10", "taxa_L20", "taxa_L30"]
+    c.DATA.TASK_KEYS_H5 = tasks
+    c.MODEL.CLASSIFICATION.HEADS = CN({t: {"TYPE": "ConditionalClassifier", "ROUTING_STRATEGY": "soft", "TEMPERATURE": 1.0, "USE_BIAS": True} for t in tasks})
+    nc = {"taxa_L10": 6, "taxa_L20": 3, "taxa_L30": 2}
+    tree = TaxonomyTree({"taxa_L10": {0: 0, 1: 0, 2: 1, 3: 1, 4: 2, 5: 2}, "taxa_L20": {0: 0, 1: 0, 2: 1}}, tasks, nc)
+    ref = build_model(c, num_classes=nc, taxonomy_tree=tree)
+    rec = {"state_dict": [[k, list(v.shape), str(v.dtype)] for k, v in ref.state_dict().items()],
+           "parameters": [n for n, _ in ref.named_parameters()],
+           "parameter_groups_metadata": ref.parameter_groups_metadata,
+           "pretrained_ckpt_handling_metadata": ref.pretrained_ckpt_handling_metadata,
+           "heads": sorted(ref.head.keys())}
+    with open(os.path.join(OUT, "registry_sm.json"), "w") as f:
+        json.dump(rec, f, indent=0)
+    print(f"[registry] {len(rec['state_dict'])} state_dict entries, {len(rec['parameters'])} parameters")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -746,6 +786,10 @@ def main():
         collate_known_answers()
     if want("aug"):
         aug_known_answers()
+    if want("aug_policies"):
+        aug_policy_tables()
+    if want("registry"):
+        registry_facts()
 
 
 if __name__ == "__main__":

@@ -133,7 +133,7 @@ def test_bench_line_loss_is_pinned_and_checked_against_the_oracle():
     with open(os.path.join(repo, "tests", "golden", "bench_loss.json")) as fh:
         pin = json.load(fh)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-batch", "8", "--profile-steps", "0", "--no-sched-calibration"],
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-batch", "8", "--profile-steps", "0", "--no-sched-calibration"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -158,7 +158,7 @@ def test_bench_n2_path_with_two_real_ranks_on_one_gpu():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--batch", "8", "--steps", "2", "--warmup", "1",
-                        "--profile-steps", "0", "--no-sched-calibration"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--profile-steps", "0", "--no-sched-calibration"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and "rehearsal" in line and line["scaling"] == "weak"
@@ -168,3 +168,58 @@ def test_bench_n2_path_with_two_real_ranks_on_one_gpu():
     assert line["rccl"]["stream_budget"]["count"] <= 4
     dp = line["data_parallel"]
     assert dp["ms_per_step_no_sync"] > 0 and dp["n1_equiv_images_per_sec"] > 0 and line["value"] > 0
+
+
+def test_bench_plain_run_times_only_its_leg_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no `--full`) runs no live profile and no CPU baseline (which legs it times is checked on the host:
+    tests/test_host_logic.py::test_bench_plain_run_times_only_the_value_leg).  `--dump-outputs DIR` replays the timed step once from
+    the seeded weights and inputs and writes what it computed (float32 .npy: loss, every task's logits, the seeded samples of the
+    gradients and of the parameters after the AdamW update): two runs with the same arguments write the same arrays up to the rounding
+    of the float atomics' summation order -- and, for a parameter whose near-zero gradient that noise flips in sign, a move of at most
+    2 lr.  The update is really applied: the parameters differ from the seeded ones by about lr."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--batch", "16", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert "timed 3 steps" in r.stderr
+        return json.loads(r.stdout.strip().splitlines()[-1]), {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+    (line, a), (_, b) = run(tmp_path / "a"), run(tmp_path / "b")
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert abs(line["value"] - 16 * 1e3 / line["ms_per_step"]) <= 0.01 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["kernels"] == {}
+    names = {"loss", "grads_sample", "params_sample"} | {f"logits_{t}" for t in ("taxa_L10", "taxa_L20", "taxa_L30", "taxa_L40")}
+    assert set(a) == set(b) == names
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["logits_taxa_L10"].shape == (16, 1000) and a["grads_sample"].shape == (1 << 20,) and np.abs(a["grads_sample"]).max() > 0
+    assert a["params_sample"].shape == (1 << 20,)
+    for k in names:
+        scale = max(1.0, float(np.abs(a[k]).max()))
+        d = np.abs(a[k] - b[k])
+        if k == "params_sample":  # lr = 1e-4
+            assert d.max() <= 2e-4 + 1e-5 * scale and int((d > 1e-5 * scale).sum()) <= 16, (k, float(d.max()), int((d > 1e-5 * scale).sum()))
+        else:
+            assert d.max() <= 1e-5 * scale, (k, float(d.max()))
+
+    # the dumped parameters are the seeded ones moved by one AdamW step: a bench run that skipped the update would write them unmoved
+    import torch
+
+    sys.path.insert(0, repo)
+    import bench
+
+    torch.manual_seed(42)
+    _, model = bench.make_model(bench.parse([]))
+    p0 = torch.cat([p_.detach().float().reshape(-1) for p_ in model.parameters() if p_.requires_grad])
+    idx = torch.randint(0, p0.numel(), (min(bench.DUMP_SAMPLE, p0.numel()),), generator=torch.Generator().manual_seed(0)).sort().values
+    moved = np.abs(a["params_sample"] - p0[idx].numpy())
+    assert 0.5e-4 <= float(np.median(moved[a["grads_sample"] != 0])) <= 1.5e-4 and float(moved.max()) <= 2e-4

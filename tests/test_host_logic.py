@@ -145,67 +145,53 @@ def test_build_model_loads_local_pretrained(tmp_path):
             build_model(cfg2, num_classes=nc)
 
 
-_REF = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(_REF), reason="build-container only: the reference is not on the GPU box")
-def test_install_into_linnaeus_swaps_the_reference_registry():
-    """the reference-side binding.  In a child process (so that nothing of `linnaeus` stays imported
-    here): import linnaeus.models, build mFormerV1 through the REFERENCE's build_model with its yacs CfgNode and a real
-    TaxonomyTree -> the reference class; call install_into_linnaeus(); build again through the same reference entry point ->
-    the HIP-backed class, whose state_dict has exactly the reference model's keys, shapes and order."""
-    import subprocess
+def test_install_into_linnaeus_swaps_the_reference_registry(monkeypatch, golden_dir):
+    """the reference-side binding.  install_into_linnaeus() registers the HIP-backed class under the registry of
+    `linnaeus.models.model_factory` (here a stand-in module with the registry's two names: `_model_registry` and the overwriting
+    `register_model` decorator); the class it registers, built for mFormerV1_sm @224 with three ConditionalClassifier heads on a
+    taxonomy tree, has exactly the state_dict keys, shapes, dtypes and order, parameter names, metadata and heads that the
+    reference's own build_model() gives that configuration (tests/golden/registry_sm.json, recorded from the reference)."""
+    import json
     import sys
-    import textwrap
+    import types
 
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = textwrap.dedent("""
-        import logging, sys, warnings
-        warnings.filterwarnings("ignore"); logging.disable(logging.CRITICAL)
-        import torch
-        from yacs.config import CfgNode as CN
-        from linnaeus.config import get_default_config
-        from linnaeus.models import build_model
-        from linnaeus.models import model_factory as mf
-        from linnaeus.utils.config_utils import load_config, merge_configs
-        from linnaeus.utils.taxonomy.taxonomy_tree import TaxonomyTree
+    from linnaeus_amd.registry import install_into_linnaeus
 
-        def cfg():
-            c = get_default_config()
-            arch = load_config("/root/reference/configs/model/archs/mFormerV1/mFormerV1_sm.yaml")
-            c.MODEL = merge_configs(c.MODEL, arch.MODEL)
-            c.MODEL.IMG_SIZE = 224
-            tasks = ["taxa_L10", "taxa_L20", "taxa_L30"]
-            c.DATA.TASK_KEYS_H5 = tasks
-            c.MODEL.CLASSIFICATION.HEADS = CN({t: {"TYPE": "ConditionalClassifier", "ROUTING_STRATEGY": "soft", "TEMPERATURE": 1.0, "USE_BIAS": True} for t in tasks})
-            return c, tasks
+    mf = types.ModuleType("linnaeus.models.model_factory")
+    mf._model_registry = {"mFormerV1": object}
 
-        c, tasks = cfg()
-        nc = {"taxa_L10": 6, "taxa_L20": 3, "taxa_L30": 2}
-        tree = TaxonomyTree({"taxa_L10": {0: 0, 1: 0, 2: 1, 3: 1, 4: 2, 5: 2}, "taxa_L20": {0: 0, 1: 0, 2: 1}}, tasks, nc)
-        ref = build_model(c, num_classes=nc, taxonomy_tree=tree)
-        assert type(ref).__module__.startswith("linnaeus."), type(ref)
-        import linnaeus_amd
-        from linnaeus_amd.registry import install_into_linnaeus
-        assert install_into_linnaeus()
-        ours = build_model(c, num_classes=nc, taxonomy_tree=tree)
-        assert type(ours) is linnaeus_amd.model.mFormerV1 and mf._model_registry["mFormerV1"] is linnaeus_amd.model.mFormerV1, type(ours)
-        a, b = ref.state_dict(), ours.state_dict()
-        assert list(a.keys()) == list(b.keys()), [k for k in a if k not in b][:5] + [k for k in b if k not in a][:5]
-        for k in a:
-            assert a[k].shape == b[k].shape and a[k].dtype == b[k].dtype, k
-        assert [n for n, _ in ref.named_parameters()] == [n for n, _ in ours.named_parameters()]
-        ours.load_state_dict(a, strict=True)
-        assert ref.parameter_groups_metadata == ours.parameter_groups_metadata
-        assert ref.pretrained_ckpt_handling_metadata == ours.pretrained_ckpt_handling_metadata
-        assert set(ours.head.keys()) == set(ref.head.keys()) and all(hasattr(h, "set_gradnorm_mode") for h in ours.head.values())
-        print("OK", len(a))
-    """)
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(repo, "tests", "golden", "gen", "_stubs"), _REF, repo]))
-    r = subprocess.run([sys.executable, "-c", code], cwd="/tmp", env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    def register_model(name):
+        def deco(cls):
+            mf._model_registry[name] = cls
+            return cls
 
+        return deco
+
+    mf.register_model = register_model
+    pkg, models = types.ModuleType("linnaeus"), types.ModuleType("linnaeus.models")
+    pkg.models, models.model_factory = models, mf
+    for name, mod in (("linnaeus", pkg), ("linnaeus.models", models), ("linnaeus.models.model_factory", mf)):
+        monkeypatch.setitem(sys.modules, name, mod)
+    assert install_into_linnaeus()
+    assert mf._model_registry["mFormerV1"] is linnaeus_amd.model.mFormerV1
+
+    with open(os.path.join(golden_dir, "registry_sm.json")) as fh:
+        ref = json.load(fh)
+    tasks = ["taxa_L10", "taxa_L20", "taxa_L30"]
+    nc = {"taxa_L10": 6, "taxa_L20": 3, "taxa_L30": 2}
+    cfg = arch_config("sm", 224)
+    cfg.DATA.TASK_KEYS_H5 = tasks
+    cfg.MODEL.CLASSIFICATION.HEADS = {t: {"TYPE": "ConditionalClassifier", "ROUTING_STRATEGY": "soft", "TEMPERATURE": 1.0, "USE_BIAS": True} for t in tasks}
+    tree = TinyTree({"taxa_L10": {0: 0, 1: 0, 2: 1, 3: 1, 4: 2, 5: 2}, "taxa_L20": {0: 0, 1: 0, 2: 1}}, tasks, nc)
+    ours = mf._model_registry[cfg.MODEL.TYPE](cfg, num_classes=nc, taxonomy_tree=tree)
+    got = [[k, list(v.shape), str(v.dtype)] for k, v in ours.state_dict().items()]
+    want = ref["state_dict"]
+    assert [k for k, _, _ in got] == [k for k, _, _ in want], [k for k, _, _ in want if k not in ours.state_dict()][:5]
+    assert got == want, [(g, w) for g, w in zip(got, want) if g != w][:5]
+    assert [n for n, _ in ours.named_parameters()] == ref["parameters"]
+    assert json.loads(json.dumps(ours.parameter_groups_metadata)) == ref["parameter_groups_metadata"]
+    assert json.loads(json.dumps(ours.pretrained_ckpt_handling_metadata)) == ref["pretrained_ckpt_handling_metadata"]
+    assert sorted(ours.head.keys()) == ref["heads"] and all(hasattr(h, "set_gradnorm_mode") for h in ours.head.values())
 
 def test_plan_footprint_counts_dropout_masks_and_logits():
     """AutoBatch's predicted bytes include what lives outside the plan workspace -- the per-forward dropout
@@ -266,6 +252,28 @@ def test_bench_legs():
         legs = bench.legs_for(n, None)
         assert legs[0] == ("config3", 128) and legs[0][1] * 8 == 1024 and ("weak256", 256) in legs
     assert bench.legs_for(8, 64) == [("batch", 64)]
+
+
+def test_bench_plain_run_times_only_the_value_leg():
+    """A plain `bench.py` run times the one leg of `value`; config 3's 128-image leg at N = 1 and the weak 256-image leg at N > 1
+    are timed only under --full (and config3_n1 only for the headline workload)."""
+    import importlib.util
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    legs = bench.legs_to_time
+    assert legs(bench.parse([]), 1) == [("config2", 256)]
+    assert legs(bench.parse(["--full"]), 1) == [("config2", 256), ("config3_n1", 128)]
+    assert legs(bench.parse(["--full", "--arch", "lg"]), 1) == [("config2", 256)]
+    assert legs(bench.parse(["--gpus", "8"]), 8) == [("config3", 128)]
+    assert legs(bench.parse(["--gpus", "8", "--full"]), 8) == [("config3", 128), ("weak256", 256)]
+    assert legs(bench.parse(["--force-dp"]), 1) == [("config3", 128)]
+    assert legs(bench.parse(["--batch", "64", "--full"]), 1) == [("batch", 64)]
+    for bad in (["--steps", "0"], ["--eval", "--eval-iters", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
 
 
 @pytest.mark.skipif(not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")), reason="needs hipcc (cross-compiles without a GPU)")

@@ -4,7 +4,7 @@
 T=${1:-rXX}
 O=gpurun_out/bench_round
 mkdir -p $O
-run() { n=$1; shift; echo "== $n: bench.py $*"; timeout -k 10 400 python bench.py "$@" > $O/${T}_bench_$n.log 2>&1 || { echo "FAILED $n"; tail -5 $O/${T}_bench_$n.log; return 1; }; tail -1 $O/${T}_bench_$n.log | cut -c1-230; }
+run() { n=$1; shift; echo "== $n: bench.py $*"; timeout -k 10 400 python bench.py --full "$@" > $O/${T}_bench_$n.log 2>&1 || { echo "FAILED $n"; tail -5 $O/${T}_bench_$n.log; return 1; }; tail -1 $O/${T}_bench_$n.log | cut -c1-230; }
 run b256 &&
 run dropin --drop-in --no-cpu-baseline &&
 run hostinput --host-input --no-cpu-baseline &&
