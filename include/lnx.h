@@ -637,6 +637,24 @@ int lnx_grad_sumsq(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks,
 int lnx_adamw_step(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_adamw_hyper* hyper, const float* sumsq, float max_norm,
                    void* stream);
 
+/* AdEMAMix (linnaeus/optimizers/ademamix.py:119-175, built by optimizers/build.py:105-113 for OPTIMIZER.NAME = ademamix) over
+ * the AdamW descriptor table, with the same clip: slow_dev is a DEVICE array parallel to descs_dev, slow_dev[i] = exp_avg_slow
+ * of tensor i.  Per slot (one per (parameter group, step count) pair), with alpha_t / beta3_t the T_alpha_beta3 schedule of
+ * ademamix.py:146-161 at that step (host, double, rounded once):
+ *   p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  s = beta3_t s + (1-beta3_t) g
+ *   p -= lr/bias_c1 * (m + alpha_t s) / (sqrt(v)/sqrt(bias_c2) + eps)
+ * The slow EMA is divided by bias_c1 too (as the reference does; the paper does not).  sumsq == NULL or max_norm <= 0: no clip. */
+typedef struct lnx_ademamix_hyper {
+    int ngroups;
+    float lr[LNX_ADAMW_MAX_GROUPS], beta1[LNX_ADAMW_MAX_GROUPS], beta2[LNX_ADAMW_MAX_GROUPS], eps[LNX_ADAMW_MAX_GROUPS],
+        weight_decay[LNX_ADAMW_MAX_GROUPS];
+    float bias_c1[LNX_ADAMW_MAX_GROUPS], bias_c2[LNX_ADAMW_MAX_GROUPS]; /* 1 - beta^step of the step being taken */
+    float omb1[LNX_ADAMW_MAX_GROUPS], omb2[LNX_ADAMW_MAX_GROUPS];       /* 1 - beta, rounded from double */
+    float alpha_t[LNX_ADAMW_MAX_GROUPS], beta3_t[LNX_ADAMW_MAX_GROUPS], omb3[LNX_ADAMW_MAX_GROUPS]; /* scheduled; omb3 = 1 - beta3_t */
+} lnx_ademamix_hyper;
+int lnx_ademamix_step(const lnx_adamw_desc* descs_dev, float* const* slow_dev, int ndesc, int total_blocks, const lnx_ademamix_hyper* hyper,
+                      const float* sumsq, float max_norm, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP branch (bf16 storage, C in {32,64,96,128,192}):
  *   out = x + rowscale * gamma * (GELU(ln . W1^T + b1) . W2^T + b2)

@@ -1,4 +1,4 @@
-// Multi-tensor AdamW with a fused global-norm clip for gfx950 ("optimizer + step glue").
+// Multi-tensor AdamW and AdEMAMix with a fused global-norm clip for gfx950 ("optimizer + step glue").
 // Replaces, for the model's parameters: torch.optim.AdamW.step (decoupled weight decay, bias correction) as built
 // by linnaeus/optimizers/build.py, and the gradient-norm / clip passes of train.py:282-308
 // (clip_grad_norm_: coef = min(1, max_norm / (total_norm + 1e-6)), gradients scaled by coef).
@@ -12,14 +12,19 @@ namespace {
 
 constexpr int OPT_ELEMS = 4096;  // elements per workgroup
 
-__device__ __forceinline__ const lnx_adamw_desc& find_desc(const lnx_adamw_desc* __restrict__ descs, int ndesc, int block) {
+// index of the tensor that owns workgroup `block` (descriptors sorted by block_start)
+__device__ __forceinline__ int find_desc_index(const lnx_adamw_desc* __restrict__ descs, int ndesc, int block) {
     int lo = 0, hi = ndesc - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (descs[mid].block_start <= block) lo = mid;
         else hi = mid - 1;
     }
-    return descs[lo];
+    return lo;
+}
+
+__device__ __forceinline__ const lnx_adamw_desc& find_desc(const lnx_adamw_desc* __restrict__ descs, int ndesc, int block) {
+    return descs[find_desc_index(descs, ndesc, block)];
 }
 
 // one partial per workgroup, folded in a fixed order by grad_sumsq_fold_kernel: the same gradients give the same bits on every
@@ -136,6 +141,90 @@ __global__ __launch_bounds__(256) void adamw_kernel(const lnx_adamw_desc* __rest
     }
 }
 
+// AdEMAMix (linnaeus/optimizers/ademamix.py:119-175) over the same descriptor table; slow[i] is exp_avg_slow (m3) of
+// descs[i].  Per element, in the reference's order and with its quirks:
+//   g *= coef                                   (clip coefficient, as adamw_kernel)
+//   p *= 1 - lr*wd                              decoupled weight decay; the reference applies it after the moments and
+//                                               before the update, which touches p only, so applying it first is the same
+//   m1 = b1 m1 + (1-b1) g;  v = b2 v + (1-b2) g^2;  m3 = b3_t m3 + (1-b3_t) g
+//   denom = sqrt(v) / sqrt(bc2) + eps
+//   p -= (lr / bc1) * (m1 + alpha_t m3) / denom
+// Quirk: the slow EMA m3 is divided by bc1 as well (it sits inside the addcdiv numerator of :175); the paper leaves m3
+// uncorrected.  linnaeus trains with this form, so it is kept.  alpha_t, b3_t and 1-b3_t are per slot (they depend on
+// the parameter's own step through the T_alpha_beta3 schedule) and come from the host, computed in double.
+// Weight decay is written p + (-lr*wd) p, one fma, as the reference's p.add_(p, alpha=-wd*lr).
+// 36 bytes per parameter: read p, g, m1, v, m3; write p, m1, v, m3.
+__global__ __launch_bounds__(256) void ademamix_kernel(const lnx_adamw_desc* __restrict__ descs, float* const* __restrict__ slow, int ndesc,
+                                                       const lnx_ademamix_hyper h, const float* __restrict__ sumsq, float max_norm) {
+    const int di = find_desc_index(descs, ndesc, blockIdx.x);
+    const lnx_adamw_desc& d = descs[di];
+    float* const m3p = slow[di];
+    const int gi = d.group;
+    const float lr = h.lr[gi], b1 = h.beta1[gi], b2 = h.beta2[gi], eps = h.eps[gi], nlrwd = -(lr * h.weight_decay[gi]);
+    const float omb1 = h.omb1[gi], omb2 = h.omb2[gi], b3 = h.beta3_t[gi], omb3 = h.omb3[gi], alpha = h.alpha_t[gi];
+    const float step_size = lr / h.bias_c1[gi], sqrt_bc2 = sqrtf(h.bias_c2[gi]);
+    float coef = 1.0f;
+    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+    const int64_t base = (int64_t)(blockIdx.x - d.block_start) * OPT_ELEMS;
+    const int64_t end = min(d.n, base + OPT_ELEMS);
+    auto upd = [&](float g, float& p, float& m, float& v, float& s) __attribute__((always_inline)) {
+        g *= coef;
+        p = fmaf(nlrwd, p, p);
+        m = fmaf(b1, m, omb1 * g);
+        v = fmaf(b2, v, omb2 * g * g);
+        s = fmaf(b3, s, omb3 * g);
+        const float denom = sqrtf(v) / sqrt_bc2 + eps;
+        p -= step_size * (fmaf(alpha, s, m) / denom);
+    };
+    // same access shape as adamw_kernel: 16-byte accesses, all four rounds of loads in flight before the first use; the
+    // scalar loop takes tails and tensors any of whose five pointers is not 16-byte aligned (arena views at odd offsets)
+    const bool vec = ((reinterpret_cast<uintptr_t>(d.p) | reinterpret_cast<uintptr_t>(d.g) | reinterpret_cast<uintptr_t>(d.m) | reinterpret_cast<uintptr_t>(d.v) |
+                       reinterpret_cast<uintptr_t>(m3p)) & 15) == 0;
+    int64_t done = base;
+    if (vec) {
+        constexpr int R = OPT_ELEMS / 1024;
+        float4 g4[R], p4[R], m4[R], v4[R], s4[R];
+        const int64_t full = base + ((end - base) & ~(int64_t)3);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t i = base + 1024 * r + 4 * threadIdx.x;
+            const int64_t ic = i + 3 < full ? i : base;  // unconditional loads (a workgroup's first four elements always exist when full > base)
+            if (full > base) {
+                g4[r] = *reinterpret_cast<const float4*>(d.g + ic);
+                p4[r] = *reinterpret_cast<const float4*>(d.p + ic);
+                m4[r] = *reinterpret_cast<const float4*>(d.m + ic);
+                v4[r] = *reinterpret_cast<const float4*>(d.v + ic);
+                s4[r] = *reinterpret_cast<const float4*>(m3p + ic);
+            }
+        }
+        if (full > base) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int64_t i = base + 1024 * r + 4 * threadIdx.x;
+                if (i + 3 < full) {
+                    upd(g4[r].x, p4[r].x, m4[r].x, v4[r].x, s4[r].x);
+                    upd(g4[r].y, p4[r].y, m4[r].y, v4[r].y, s4[r].y);
+                    upd(g4[r].z, p4[r].z, m4[r].z, v4[r].z, s4[r].z);
+                    upd(g4[r].w, p4[r].w, m4[r].w, v4[r].w, s4[r].w);
+                    *reinterpret_cast<float4*>(d.p + i) = p4[r];
+                    *reinterpret_cast<float4*>(d.m + i) = m4[r];
+                    *reinterpret_cast<float4*>(d.v + i) = v4[r];
+                    *reinterpret_cast<float4*>(m3p + i) = s4[r];
+                }
+            }
+        }
+        done = full;
+    }
+    for (int64_t i = done + threadIdx.x; i < end; i += 256) {
+        float p = d.p[i], m = d.m[i], v = d.v[i], s = m3p[i];
+        upd(d.g[i], p, m, v, s);
+        d.p[i] = p;
+        d.m[i] = m;
+        d.v[i] = v;
+        m3p[i] = s;
+    }
+}
+
 }  // namespace
 
 extern "C" int lnx_adamw_blocks(int64_t numel) { return (int)((numel + OPT_ELEMS - 1) / OPT_ELEMS); }
@@ -156,6 +245,17 @@ extern "C" int lnx_adamw_step(const lnx_adamw_desc* descs_dev, int ndesc, int to
     for (int i = 0; i < hyper->ngroups; ++i)
         LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_adamw_step: bias corrections of group %d must be positive (step >= 1)", i);
     hipLaunchKernelGGL(adamw_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, ndesc, *hyper, sumsq, max_norm);
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_ademamix_step(const lnx_adamw_desc* descs_dev, float* const* slow_dev, int ndesc, int total_blocks, const lnx_ademamix_hyper* hyper,
+                                 const float* sumsq, float max_norm, void* stream) {
+    LNX_CHECK(descs_dev && slow_dev && ndesc > 0 && total_blocks > 0 && hyper, "lnx_ademamix_step: bad arguments");
+    LNX_CHECK(hyper->ngroups > 0 && hyper->ngroups <= LNX_ADAMW_MAX_GROUPS, "lnx_ademamix_step: ngroups=%d (max %d)", hyper->ngroups, LNX_ADAMW_MAX_GROUPS);
+    for (int i = 0; i < hyper->ngroups; ++i)
+        LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_ademamix_step: bias corrections of slot %d must be positive (step >= 1)", i);
+    hipLaunchKernelGGL(ademamix_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, slow_dev, ndesc, *hyper, sumsq, max_norm);
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -7,14 +7,41 @@ gradient passes with host syncs, train.py:282-308) followed by `torch.optim.Adam
 Same update rule and `param_groups` / `state_dict` layout as `torch.optim.AdamW` (per-group `lr`, `betas`, `eps`,
 `weight_decay`; per-parameter `step`, `exp_avg`, `exp_avg_sq`), so LR schedulers and the reference's parameter-group
 builder (optimizers/build.py) work unchanged.  GPU fp32 parameters only.
+
+`FusedAdEMAMix` is the same machinery for the reference's AdEMAMix (optimizers/ademamix.py): one launch per step over the
+same descriptor table plus a parallel table of slow-EMA pointers, three with the clip.
 """
 import ctypes as C
+import math
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib as L
+
+
+def _slot_items(state, items, name):
+    """[(param group, p)] -> ({(group, step): slot}, [(slot, p)]): one hyper-parameter slot per distinct (group, step count)"""
+    slots = {}
+    for gi, p in items:
+        slots.setdefault((gi, int(state[p]["step"])), len(slots))
+    if len(slots) > L.ADAMW_MAX_GROUPS:
+        raise L.LnxError(f"{name}: {len(slots)} distinct (parameter group, step count) combinations, at most {L.ADAMW_MAX_GROUPS} are supported")
+    return slots, [(slots[(gi, int(state[p]["step"]))], p) for gi, p in items]
+
+
+def _adamw_descs(state, items):
+    """host lnx_adamw_desc table of [(slot, p)] and its total workgroup count"""
+    lib = L.lib()
+    arr = (L.AdamWDesc * len(items))()
+    blk = 0
+    for i, (gi, p) in enumerate(items):  # gi: hyper-parameter slot = (param group, step count) combination
+        st = state[p]
+        arr[i].p, arr[i].m, arr[i].v, arr[i].g = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.grad.data_ptr()
+        arr[i].n, arr[i].group, arr[i].block_start = p.numel(), gi, blk
+        blk += lib.lnx_adamw_blocks(C.c_int64(p.numel()))
+    return arr, blk
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -33,14 +60,7 @@ class FusedAdamW(torch.optim.Optimizer):
     # ------------------------------------------------------------------ descriptor table
     def _build(self, items):
         dev = items[0][1].device
-        lib = L.lib()
-        arr = (L.AdamWDesc * len(items))()
-        blk = 0
-        for i, (gi, p) in enumerate(items):  # gi: hyper-parameter slot = (param group, step count) combination
-            st = self.state[p]
-            arr[i].p, arr[i].m, arr[i].v, arr[i].g = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.grad.data_ptr()
-            arr[i].n, arr[i].group, arr[i].block_start = p.numel(), gi, blk
-            blk += lib.lnx_adamw_blocks(C.c_int64(p.numel()))
+        arr, blk = _adamw_descs(self.state, items)
         host = torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy())
         self._table = (host.to(dev), len(items), blk)
         if self._sumsq is None or self._sumsq.device != dev:
@@ -73,12 +93,7 @@ class FusedAdamW(torch.optim.Optimizer):
         # torch.optim.AdamW bias-corrects PER PARAMETER (its own step count).  Parameters of one group normally share a
         # step count, but one that was frozen for a while, had no gradient on some steps or came from a checkpoint with
         # mixed steps does not: every distinct (group, step) pair gets its own hyper-parameter slot.
-        slots = {}
-        for gi, p in items:
-            slots.setdefault((gi, int(self.state[p]["step"])), len(slots))
-        if len(slots) > L.ADAMW_MAX_GROUPS:
-            raise L.LnxError(f"FusedAdamW: {len(slots)} distinct (parameter group, step count) combinations, at most {L.ADAMW_MAX_GROUPS} are supported")
-        items = [(slots[(gi, int(self.state[p]["step"]))], p) for gi, p in items]
+        slots, items = _slot_items(self.state, items, "FusedAdamW")
         key = tuple((si, p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for si, p in items)
         if key != self._key:
             self._build(items)
@@ -100,6 +115,137 @@ class FusedAdamW(torch.optim.Optimizer):
                     "lnx_grad_sumsq")
         L.check(lib.lnx_adamw_step(C.c_void_p(table.data_ptr()), n, blocks, C.byref(h), C.c_void_p(self._sumsq.data_ptr()) if clip else None,
                                    C.c_float(self.max_grad_norm if clip else 0.0), stream), "lnx_adamw_step")
+        return loss
+
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """total L2 norm of the gradients seen by the last clipped step (device scalar, no sync); None without clipping"""
+        if self._sumsq is None or self.max_grad_norm is None:
+            return None
+        return self._sumsq.sqrt()[0]
+
+
+def ademamix_schedule(step: int, alpha: float, beta1: float, beta3: float, T_alpha_beta3: Optional[float]):
+    """(alpha_t, beta3_t) of AdEMAMix at a parameter's step (1-based), in double: alpha warms up linearly over T steps,
+    beta3 follows the log-interpolation from beta1 (Pagliardini et al. 2024), both capped at their final values.  Without T
+    they are constant."""
+    if T_alpha_beta3 is None:
+        return float(alpha), float(beta3)
+    f = step / T_alpha_beta3
+    lb1, lb3 = math.log(beta1), math.log(beta3)
+    return min(step * alpha / T_alpha_beta3, alpha), min(math.exp(lb1 * lb3 / ((1.0 - f) * lb3 + f * lb1)), beta3)
+
+
+def _check_ademamix_group(lr, betas, eps, weight_decay, T_alpha_beta3):
+    if not 0.0 <= lr:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    if len(betas) != 3 or not all(0.0 <= b < 1.0 for b in betas):
+        raise ValueError(f"Invalid beta parameters: {betas}, expected three in [0, 1)")
+    if not 0.0 <= weight_decay:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+    if T_alpha_beta3 is not None:
+        # the reference only fails on these at its first step (a division by zero, or log(0) in the beta3 schedule)
+        if not T_alpha_beta3 > 0:
+            raise ValueError(f"Invalid T_alpha_beta3 value: {T_alpha_beta3} (must be > 0, or None)")
+        if betas[0] == 0.0 or betas[2] == 0.0:
+            raise ValueError(f"Invalid beta parameters: {betas}: the T_alpha_beta3 schedule needs beta1 > 0 and beta3 > 0")
+
+
+class FusedAdEMAMix(torch.optim.Optimizer):
+    """AdEMAMix (linnaeus/optimizers/ademamix.py, chosen by OPTIMIZER.NAME = ademamix in optimizers/build.py) as one
+    multi-tensor HIP launch per step, three with clipping (lnx_grad_sumsq, then lnx_ademamix_step with the clip folded in),
+    instead of the reference's ~13 tensor ops per parameter.
+
+    Same constructor defaults, `param_groups` keys (lr, betas, eps, weight_decay, alpha, T_alpha_beta3) and per-parameter
+    state (step, exp_avg, exp_avg_sq, exp_avg_slow) as the reference, so its checkpoints load with `load_state_dict` and
+    the other way round, and LR schedulers and build.py's parameter groups work unchanged.  The update is the reference's,
+    including its quirk of dividing the slow EMA by the first bias correction as well (csrc/optim.hip).
+
+    `max_grad_norm` clips over THIS optimizer's parameters.  When linnaeus builds one optimizer per parameter group
+    (PARAMETER_GROUPS.ENABLED), leave it None and clip once, over all parameters, before the steps.  GPU fp32 only.
+    """
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999, 0.9999), eps: float = 1e-8, weight_decay: float = 0, alpha: float = 5.0,
+                 T_alpha_beta3: Optional[float] = None, max_grad_norm: Optional[float] = None):
+        _check_ademamix_group(lr, betas, eps, weight_decay, T_alpha_beta3)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, alpha=alpha, T_alpha_beta3=T_alpha_beta3))
+        for g in self.param_groups:  # groups may carry their own values
+            _check_ademamix_group(g["lr"], g["betas"], g["eps"], g["weight_decay"], g["T_alpha_beta3"])
+        if len(self.param_groups) > L.ADAMW_MAX_GROUPS:
+            raise ValueError(f"at most {L.ADAMW_MAX_GROUPS} parameter groups")
+        self.max_grad_norm = max_grad_norm
+        self._table = None
+        self._key = None
+        self._sumsq = None
+        self._sumsq_ws = None
+
+    def _build(self, items):
+        dev = items[0][1].device
+        for _, p in items:  # the kernel indexes every state tensor with the parameter's offsets
+            for k in ("exp_avg", "exp_avg_sq", "exp_avg_slow"):
+                t = self.state[p][k]
+                if t.device != dev or t.dtype != torch.float32 or t.shape != p.shape or not t.is_contiguous():
+                    raise L.LnxError(f"FusedAdEMAMix: state '{k}' must be a contiguous fp32 tensor of the parameter's shape on its device")
+        arr, blk = _adamw_descs(self.state, items)
+        slow = (C.c_uint64 * len(items))(*(self.state[p]["exp_avg_slow"].data_ptr() for _, p in items))
+        descs = np.frombuffer(arr, dtype=np.uint8)
+        host = torch.from_numpy(np.concatenate([descs, np.frombuffer(slow, dtype=np.uint8)]))  # one copy: descriptors, then slow pointers
+        self._table = (host.to(dev), len(descs), len(items), blk)
+        if self._sumsq is None or self._sumsq.device != dev:
+            self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
+        if self._sumsq_ws is None or self._sumsq_ws.device != dev or self._sumsq_ws.numel() < blk:
+            self._sumsq_ws = torch.empty(blk, device=dev, dtype=torch.float32)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        items = []
+        for gi, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
+                    raise L.LnxError("FusedAdEMAMix needs contiguous fp32 parameters and gradients on the GPU")
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_slow"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] = int(st["step"]) + 1  # int() also accepts a tensor step
+                items.append((gi, p))
+        if not items:
+            return loss
+        # bias corrections, alpha_t and beta3_t all follow each parameter's own step count (as in the reference)
+        slots, items = _slot_items(self.state, items, "FusedAdEMAMix")
+        key = tuple((si, p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
+                     self.state[p]["exp_avg_slow"].data_ptr()) for si, p in items)
+        if key != self._key:
+            self._build(items)
+            self._key = key
+        h = L.AdEMAMixHyper()
+        h.ngroups = len(slots)
+        for (gi, t), si in slots.items():
+            group = self.param_groups[gi]
+            b1, b2, b3 = group["betas"]
+            alpha_t, beta3_t = ademamix_schedule(t, group["alpha"], b1, b3, group["T_alpha_beta3"])
+            h.lr[si], h.beta1[si], h.beta2[si], h.eps[si], h.weight_decay[si] = group["lr"], b1, b2, group["eps"], group["weight_decay"]
+            h.bias_c1[si], h.bias_c2[si] = 1.0 - b1 ** float(t), 1.0 - b2 ** float(t)
+            h.omb1[si], h.omb2[si] = 1.0 - b1, 1.0 - b2
+            h.alpha_t[si], h.beta3_t[si], h.omb3[si] = alpha_t, beta3_t, 1.0 - beta3_t
+        table, nbytes, n, blocks = self._table
+        lib = L.lib()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        clip = self.max_grad_norm is not None and self.max_grad_norm > 0
+        if clip:
+            L.check(lib.lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self._sumsq.data_ptr()), C.c_void_p(self._sumsq_ws.data_ptr()), stream),
+                    "lnx_grad_sumsq")
+        L.check(lib.lnx_ademamix_step(table.data_ptr(), table.data_ptr() + nbytes, n, blocks, C.byref(h), self._sumsq.data_ptr() if clip else None,
+                                      self.max_grad_norm if clip else 0.0, stream), "lnx_ademamix_step")
         return loss
 
     def grad_norm(self) -> Optional[torch.Tensor]:
