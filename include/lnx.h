@@ -656,6 +656,37 @@ int lnx_ademamix_step(const lnx_adamw_desc* descs_dev, float* const* slow_dev, i
                       const float* sumsq, float max_norm, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * GradNorm task weighting (LOSS.GRAD_WEIGHTING.TASK.TYPE = gradnorm): loss/gradnorm.py GradNormModule.measure_and_update on the
+ * device, behind one forward and one lnx_plan_backward_into per task (linnaeus_amd.loss.GradientWeighting).
+ * lnx_gradnorm_sumsq: for task t < ntasks, sum of squares of the tensors of the AdamW-style descriptor table (only .g and .n are
+ * read: the backbone slices of one gradient arena), with task t's gradients at .g + t * task_stride floats.  Same workgroup shape
+ * and fixed-order two-pass fold as lnx_grad_sumsq (bit-identical to it per task).  Writes sumsq[t] (sumsq may be NULL) and
+ * norm[t] = sqrt(sumsq[t]).  ws: ntasks * total_blocks floats.  ntasks <= LNX_MAX_TASKS.
+ * -----------------------------------------------------------------------------------*/
+int lnx_gradnorm_sumsq(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, int ntasks, int64_t task_stride, float* sumsq, float* norm,
+                       float* ws, void* stream);
+/* lnx_gradnorm_update: one workgroup; every [T] array in sorted-task-key order (the order measure_and_update indexes task_weights in):
+ *   loss_i = loss_sum_i / max(count_i, 1)
+ *   first call with alpha > 0 (*initted == 0): initial_losses = init_loss (the all-reduced mean under data parallelism) or loss; *initted = 1
+ *   g_avg = mean(norm);  alpha > 0: r_i = loss_i / max(L0_i, 1e-8), r_i *= T / max(sum r, 1e-8), target_i = g_avg r_i^alpha;
+ *   alpha = 0: target_i = g_avg (r_i reported as 1)
+ *   w_i *= norm_i / target_i unless target_i < 1e-8;  w *= T / max(sum w, 1e-8)
+ * metrics (NULL or [1 + 5T]): g_avg, loss[T], norm[T], target[T], weight[T] (the new ones), ratio[T] (normalised). */
+typedef struct lnx_gradnorm_args {
+    int T;
+    float alpha;
+    const float* norm;      /* [T] backbone gradient norms */
+    const float* loss_sum;  /* [T] sum of the per-sample losses over the valid rows */
+    const float* count;     /* [T] valid rows */
+    const float* init_loss; /* [T] or NULL */
+    float* weights;         /* [T] task weights, updated in place */
+    float* initial_losses;  /* [T] */
+    int* initted;           /* device flag, 0 until initial_losses are set */
+    float* metrics;
+} lnx_gradnorm_args;
+int lnx_gradnorm_update(const lnx_gradnorm_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP branch (bf16 storage, C in {32,64,96,128,192}):
  *   out = x + rowscale * gamma * (GELU(ln . W1^T + b1) . W2^T + b2)
  * = pwconv1 -> GELU -> pwconv2 -> LayerScale -> DropPath -> residual (blocks/convnext.py:79-86)
@@ -809,6 +840,12 @@ int lnx_plan_set_attn_dropout(lnx_plan* p, const unsigned char* masks, float dro
  * stage 2, ConvNeXt stage 1 + stem}, to be called in that order (lets the caller start the
  * gradient all-reduce of a finished segment while the next one runs). */
 int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float* dfeats, int segment, void* stream);
+/* lnx_plan_backward(segment = -1) with the parameter gradients ACCUMULATED into grads[lnx_plan_num_params] (fp32, 4-byte aligned)
+ * instead of the bound ones, which stay untouched and are bound again when the call returns, whatever it returns.  No rebind:
+ * the forward stays valid, and any number of these (and lnx_plan_backward) may follow one forward, each giving what a fresh
+ * forward + backward would (recompute plans re-run every block, the last ones included).  GradNorm runs one forward and one
+ * of these per task, seeded by that task's dlogits alone, into scratch gradient arenas. */
+int lnx_plan_backward_into(lnx_plan* p, const float* dlogits, const float* dfeats, float* const* grads, void* stream);
 /* Live per-kernel-class timing with HIP events on the launch stream (used by bench.py for the
  * roofline line; adds event records around the timed launches, so never leave it on in a timed
  * region).  Classes: 0 gemm_nt, 1 gemm_tn, 2 attention fwd, 3 attention bwd (both kernels),

@@ -90,6 +90,11 @@ class AdEMAMixHyper(C.Structure):  # == lnx_ademamix_hyper
                                                                                   "alpha_t", "beta3_t", "omb3")]
 
 
+class GradNormArgs(C.Structure):  # == lnx_gradnorm_args
+    _fields_ = [("T", C.c_int), ("alpha", C.c_float), ("norm", C.c_void_p), ("loss_sum", C.c_void_p), ("count", C.c_void_p), ("init_loss", C.c_void_p),
+                ("weights", C.c_void_p), ("initial_losses", C.c_void_p), ("initted", C.c_void_p), ("metrics", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -109,6 +114,8 @@ def lib() -> C.CDLL:
         _lib.lnx_meta_heads_bwd_part_floats.restype = C.c_int64
         if hasattr(_lib, "lnx_ademamix_step"):
             _lib.lnx_ademamix_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(AdEMAMixHyper), C.c_void_p, C.c_float, C.c_void_p]
+        if hasattr(_lib, "lnx_gradnorm_sumsq"):
+            _lib.lnx_gradnorm_sumsq.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         # A/B runs against an OLDER build (LNX_LIB_PATH=... LNX_LIB_OLDER=1): entry points added since are allowed to be missing; calling
         # one then fails with ctypes' AttributeError
         older = bool(os.environ.get("LNX_LIB_PATH")) and os.environ.get("LNX_LIB_OLDER") == "1"
@@ -137,13 +144,13 @@ EXPORTS = [
     "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
-    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step",
+    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_mix_rows", "lnx_mix_meta",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",
     "lnx_plan_create", "lnx_plan_destroy", "lnx_plan_workspace_bytes", "lnx_plan_num_params", "lnx_plan_param_name",
     "lnx_plan_param_numel", "lnx_plan_num_drop_calls", "lnx_plan_logits_numel", "lnx_plan_logits_offset", "lnx_plan_logits_ld",
-    "lnx_plan_bind", "lnx_plan_forward", "lnx_plan_backward", "lnx_plan_segment_params", "lnx_plan_profile_begin", "lnx_plan_profile_end", "lnx_plan_profile_begin_spans", "lnx_plan_profile_end_ex", "lnx_plan_set_wgrad_stream", "lnx_plan_set_meta_stream",
+    "lnx_plan_bind", "lnx_plan_forward", "lnx_plan_backward", "lnx_plan_backward_into", "lnx_plan_segment_params", "lnx_plan_profile_begin", "lnx_plan_profile_end", "lnx_plan_profile_begin_spans", "lnx_plan_profile_end_ex", "lnx_plan_set_wgrad_stream", "lnx_plan_set_meta_stream",
 ]
 
 

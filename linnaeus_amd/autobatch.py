@@ -26,17 +26,19 @@ except Exception:  # pragma: no cover
     dist = None
 
 
-def predicted_bytes(model, batch: int, img_size: Optional[int] = None, *, mode: str = "train", optimizer_state_per_param: int = 2) -> int:
+def predicted_bytes(model, batch: int, img_size: Optional[int] = None, *, mode: str = "train", optimizer_state_per_param: int = 2,
+                    gradnorm_arenas: int = 0) -> int:
     """Device bytes one step at this per-GPU batch holds: plan workspace + fp32 master weights + fp32 gradient arena +
-    `optimizer_state_per_param` fp32 copies (AdamW: 2) + the input batch + logits."""
+    `optimizer_state_per_param` fp32 copies (AdamW: 2) + the input batch + logits (+ a GradNorm update's scratch arenas:
+    `gradnorm_arenas` = GradientWeighting.scratch_arenas())."""
     m = getattr(model, "module", model)
     n_param = sum(p.numel() for p in m.parameters())
     train = mode == "train"
     H = img_size or m.img_size[0]
-    fp = m.plan_footprint(batch, H, H, train=train)
+    fp = m.plan_footprint(batch, H, H, train=train, gradnorm_arenas=gradnorm_arenas if train else 0)
     fixed = 4 * n_param * (1 + ((1 + optimizer_state_per_param) if train else 0))
     io = batch * (m._in_chans * H * H + sum(m.meta_dims)) * 4
-    return fp["workspace"] + fp["dropout"] + fp["attn_dropout"] + fp["logits"] + fixed + io
+    return fp["workspace"] + fp["dropout"] + fp["attn_dropout"] + fp["logits"] + fp.get("gradnorm", 0) + fixed + io
 
 
 def foreign_bytes(model) -> int:

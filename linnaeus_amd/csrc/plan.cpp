@@ -2086,6 +2086,25 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
     return 0;
 }
 
+// The gradient pointers are read only while launches are built: every postponed LayerNorm / split-K / freqs reduction holding
+// one is flushed before lnx_plan_backward returns, and the weight-gradient stream's kernels captured theirs at enqueue time.
+// So swapping the pointer set for the call is all it takes; no rebind (which would sync and clear the forward).
+extern "C" int lnx_plan_backward_into(lnx_plan* p, const float* dlogits, const float* dfeats, float* const* grads, void* stream) {
+    if (!p || !grads) FAIL("lnx_plan_backward_into: null %s", !p ? "plan" : "gradient pointer set");
+    if (!p->bound || !p->has_grads) FAIL("lnx_plan_backward_into: plan is not bound with gradient buffers");
+    const size_t n = p->names.size();
+    for (size_t i = 0; i < n; ++i)
+        if (grads[i] == nullptr || (((uintptr_t)grads[i]) & 3) != 0) FAIL("lnx_plan_backward_into: gradient of %s is null or misaligned", p->names[i].c_str());
+    std::vector<float*> into(grads, grads + n);
+    struct Swap {
+        lnx_plan* p;
+        std::vector<float*>& v;
+        Swap(lnx_plan* p_, std::vector<float*>& v_) : p(p_), v(v_) { p->G.swap(v); }
+        ~Swap() { p->G.swap(v); }  // the bound set is back on every exit path
+    } swap{p, into};
+    return lnx_plan_backward(p, dlogits, dfeats, -1, stream);
+}
+
 extern "C" int lnx_plan_segment_params(const lnx_plan* p, int segment, int* idx_out, int max_out) {
     if (!p || segment < 0 || segment > 3) return -1;
     // a parameter's gradient is final after the segment that owns it

@@ -10,9 +10,12 @@ of the train step as single HIP launches (`lnx_softce`, csrc/loss.hip) behind th
 There is no CPU path: tensors must be on the GPU (LnxError otherwise), like the model itself.
 """
 import ctypes as C
-from typing import Any, Dict, Optional
+import math
+import re
+from typing import Any, Callable, Dict, Optional
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib as L
@@ -190,7 +193,7 @@ def multitask_cross_entropy(outputs: Dict[str, torch.Tensor], targets: Dict[str,
 #   build_taxonomy_smoothing_matrix <- loss/taxonomy_label_smoothing.py:30-130
 #   compute_core_loss               <- loss/core_loss.py:19-100
 #   apply_null_masking / apply_class_weighting / apply_loss_masking <- loss/masking.py:19-465, 469-518, 521-700
-#   GradientWeighting (static mode) <- loss/gradient_weighting.py:178-365
+#   GradientWeighting               <- loss/gradient_weighting.py:178-880 (static and GradNorm), loss/gradnorm.py
 #   weighted_hierarchical_loss      <- loss/hierarchical_loss.py:24-406
 # The per-sample criterion runs in the HIP kernel (lnx_softce); everything after it is arithmetic on [B]-sized device
 # vectors.  What changes against the reference is HOW, not WHAT: its per-sample Python loops with .item() (a host sync
@@ -314,32 +317,302 @@ def apply_loss_masking(per_task_losses, targets, ops_schedule, current_step, cla
     return masked, stats
 
 
+def _cfg_get(node, path, default):
+    for k in path.split("."):
+        if node is None:
+            return default
+        node = node.get(k, None) if isinstance(node, dict) else getattr(node, k, None)
+    return default if node is None else node
+
+
+DEFAULT_EXCLUDE_CONFIG = {"TYPE": "or", "FILTERS": [{"TYPE": "name", "PATTERNS": ["head"]}, {"TYPE": "name", "PATTERNS": ["meta_"]}]}
+
+
+def param_filter(spec) -> Callable[[str, torch.Tensor], bool]:
+    """matches(name, param) of the reference's parameter filter config (utils/param_filters.py create_filter_from_config, as
+    UnifiedParamFilter applies it: a leading 'module.' is stripped).  Types: name (contains / startswith / endswith / regex),
+    dimension, and / or / not / all_except."""
+    kind = str(_cfg_get(spec, "TYPE", "")).lower()
+    if kind == "name":
+        pats, how = list(_cfg_get(spec, "PATTERNS", [])), str(_cfg_get(spec, "MATCH_TYPE", "contains"))
+        if how == "regex":
+            rx = [re.compile(q) for q in pats]
+            f = lambda n, p: any(r.search(n) for r in rx)  # noqa: E731
+        elif how in ("contains", "startswith", "endswith"):
+            f = {"contains": lambda n, p: any(q in n for q in pats), "startswith": lambda n, p: any(n.startswith(q) for q in pats),
+                 "endswith": lambda n, p: any(n.endswith(q) for q in pats)}[how]
+        else:
+            raise ValueError(f"Unknown match_type: {how}")
+    elif kind == "dimension":
+        dims = list(_cfg_get(spec, "DIMENSIONS", []))
+        f = lambda n, p: p.dim() in dims  # noqa: E731
+    elif kind in ("and", "or"):
+        subs = [param_filter(x) for x in _cfg_get(spec, "FILTERS", [])]
+        f = (lambda n, p: all(g(n, p) for g in subs)) if kind == "and" else (lambda n, p: any(g(n, p) for g in subs))
+    elif kind in ("not", "all_except"):
+        sub = param_filter(_cfg_get(spec, "FILTER" if kind == "not" else "EXCEPT", {}))
+        f = lambda n, p: not sub(n, p)  # noqa: E731
+    else:
+        raise ValueError(f"Unsupported filter type for the GradNorm backbone: {kind!r}")
+    return lambda n, p: f(n[7:] if n.startswith("module.") else n, p)
+
+
+class GradNormModule(nn.Module):
+    """State of GradNorm (loss/gradnorm.py:31-140): buffers `task_weights` and `initial_losses` (same names as the reference, so
+    state dicts load both ways), indexed by SORTED task key as measure_and_update does.  The update itself is lnx_gradnorm_update."""
+
+    def __init__(self, task_keys, alpha: float = 1.5, init_weights: Optional[torch.Tensor] = None, label_densities=None, num_classes=None,
+                 init_strategy: str = "inverse_density", config: Any = None):
+        super().__init__()
+        self.num_tasks = len(task_keys)
+        self.task_keys = list(task_keys)
+        self.alpha = float(alpha)
+        self.config = config
+        if init_weights is None:
+            init_weights = self._compute_init_weights(self.task_keys, label_densities, num_classes, init_strategy)
+        self.register_buffer("task_weights", torch.as_tensor(init_weights, dtype=torch.float32).clone())
+        self.register_buffer("initial_losses", torch.zeros(self.num_tasks))
+        self.register_buffer("_initted", torch.zeros(1, dtype=torch.int32), persistent=False)  # device twin of has_initted
+        self.has_initted = False
+
+    def _compute_init_weights(self, task_keys, label_densities=None, num_classes=None, strategy: str = "inverse_density") -> torch.Tensor:
+        if not label_densities:
+            return torch.ones(len(task_keys), dtype=torch.float32)
+        dens = [label_densities.get(k, 1.0) for k in task_keys]
+        if strategy == "inverse_density" or (strategy == "class_complexity" and num_classes is None):
+            w = [1.0 / max(d, 0.001) for d in dens]
+        elif strategy == "class_complexity":
+            counts = [num_classes.get(k, 1) for k in task_keys]
+            mx = max(counts)
+            w = [1.0 / max(d, 0.001) * (math.log(c) / math.log(mx)) for d, c in zip(dens, counts)]
+        else:
+            w = [1.0] * len(task_keys)
+        tot = sum(w)
+        return torch.tensor([x * len(task_keys) / tot for x in w], dtype=torch.float32)
+
+    def forward(self, losses):
+        return (torch.stack([losses[k] for k in sorted(losses.keys())]) * self.task_weights).sum()
+
+    def get_task_weights(self) -> Dict[str, float]:
+        return {t: float(w) for t, w in zip(sorted(self.task_keys), self.task_weights.tolist())}
+
+
+def backbone_slices(layout, backbone) -> list:
+    """(offset, numel) in floats of every backbone parameter's slice of the gradient arena (`mFormerV1.grad_arena_layout()`), in
+    arena order; `backbone` = the parameters (identity).  Parameters the plan does not differentiate are absent (zero gradient)."""
+    ids = {id(p) for p in backbone}
+    out = [(o, n) for o, n, p in zip(layout["offsets"], layout["numels"], layout["params"]) if id(p) in ids]
+    return sorted(out)
+
+
+def gradnorm_desc_table(slices, base_ptr: int):
+    """lnx_adamw_desc table (only .g / .n / .block_start are read by lnx_gradnorm_sumsq) of arena slices at `base_ptr`, and its
+    total workgroup count"""
+    arr = (L.AdamWDesc * len(slices))()
+    blk = 0
+    for d, (off, n) in zip(arr, slices):
+        d.g, d.n, d.group, d.block_start = base_ptr + 4 * off, n, 0, blk
+        blk += (n + 4095) // 4096  # == lnx_adamw_blocks
+    return arr, blk
+
+
 class GradientWeighting(nn.Module):
-    """Task weighting of the multi-task loss, static mode (the reference's default for fixed weights).  GradNorm (a
-    second backward through the backbone per task) is outside the hot path and not provided."""
+    """Task weighting of the multi-task loss (loss/gradient_weighting.py:178-880): "static" (fixed weights) or "gradnorm".
+
+    GradNorm: `set_model(model)` picks the shared backbone with LOSS.GRAD_WEIGHTING.TASK.EXCLUDE_CONFIG, and
+    `update_gradnorm_weights_reforward` measures each task's backbone gradient norm and updates the weights.  Where the reference
+    re-runs forward + autograd.grad per task, here ONE forward of the native plan feeds T backward passes into scratch gradient
+    arenas (mFormerV1._task_backbone_grads); the norms (lnx_gradnorm_sumsq) and the update (lnx_gradnorm_update) stay on the
+    device.  Reproduced from the reference: backbone .grad are set to None (opt out: keep_step_grads=True), weights indexed by
+    sorted task key in the update but read in task_keys order by forward, initial weights from init_weights or ones."""
 
     def __init__(self, task_keys, config=None, task_weighting_type: str = "static", init_weights=None, class_weights=None,
-                 use_subset_weights: bool = False, **kwargs):
+                 use_subset_weights: bool = False, alpha: float = 1.5, label_densities=None, num_classes=None, init_strategy: str = "inverse_density",
+                 update_interval: int = 100, exclude_patterns=None, zero_aux_info: bool = True, keep_step_grads: bool = False, **kwargs):
         super().__init__()
-        if task_weighting_type != "static":
-            raise NotImplementedError("linnaeus_amd.loss.GradientWeighting implements static task weights; GradNorm is out of scope")
+        if task_weighting_type not in ("static", "gradnorm"):
+            raise NotImplementedError(f"task weighting type {task_weighting_type!r}: 'static' or 'gradnorm'")
         self.task_keys = list(task_keys)
         self.config = config
         self.task_weighting_type = task_weighting_type
         if isinstance(init_weights, dict):
             init_weights = [init_weights.get(k, 1.0) for k in self.task_keys]
-        self.task_weights = torch.tensor(init_weights or [1.0] * len(self.task_keys), dtype=torch.float32)
+        init_weights = list(init_weights or [1.0] * len(self.task_keys))
+        self.task_weights = torch.tensor(init_weights, dtype=torch.float32)
         self.gradnorm = None
+        self.update_interval, self.exclude_patterns = 0, []
+        self.backbone_params = None
+        self.model = None
+        if task_weighting_type == "gradnorm":
+            # the reference always hands GradNormModule a tensor: INIT_STRATEGY / label_densities never take effect
+            self.gradnorm = GradNormModule(self.task_keys, alpha=alpha, init_weights=torch.tensor(init_weights, dtype=torch.float32),
+                                           label_densities=label_densities, num_classes=num_classes, init_strategy=init_strategy, config=config)
+            self.update_interval = update_interval
+            self.exclude_patterns = exclude_patterns or ["head", "meta_"]
+            self.zero_aux_info = bool(_cfg_get(config, "LOSS.GRAD_WEIGHTING.TASK.ZERO_AUX_INFO", zero_aux_info))
+            self.keep_step_grads = bool(keep_step_grads)
         self.class_weights = class_weights
         self.use_subset_weights = use_subset_weights
         self._cache: dict = {}
+        self._gn: dict = {}
 
     def _normalize_weights(self, w):
         return w
 
+    # ------------------------------------------------------------------ GradNorm
+    def set_model(self, model: nn.Module) -> None:
+        if self.task_weighting_type != "gradnorm":
+            return
+        self.model = model
+        net = model
+        while hasattr(net, "module") and isinstance(net.module, nn.Module):  # torch DDP, linnaeus_amd.ddp.DataParallel
+            net = net.module
+        self._net = net
+        spec = _cfg_get(self.config, "LOSS.GRAD_WEIGHTING.TASK.EXCLUDE_CONFIG", None) or DEFAULT_EXCLUDE_CONFIG
+        f = param_filter(spec)
+        self.backbone_names = [n for n, p in net.named_parameters() if p.requires_grad and not f(n, p)]
+        self.backbone_params = [net.get_parameter(n) for n in self.backbone_names]
+        self._gn = {}
+
+    def scratch_arenas(self) -> int:
+        """scratch gradient arenas one update holds (mFormerV1.plan_footprint(gradnorm_arenas=...))"""
+        if self.gradnorm is None:
+            return 0
+        return 1 if int(_cfg_get(self.config, "LOSS.GRAD_WEIGHTING.TASK.GRADNORM_ACCUM_STEPS", 1)) <= 1 else len(self.task_keys)
+
+    def _descs(self, arenas: torch.Tensor):
+        """device descriptor table of the backbone slices of arena row 0, built once per arena layout"""
+        net = self._net
+        key = (arenas.data_ptr(), tuple(arenas.shape), net._arena_layout)
+        if self._gn.get("key") != key:
+            layout = net.grad_arena_layout()
+            if layout["total"] != arenas.shape[1]:
+                raise L.LnxError(f"gradient arena layout mismatch: {layout['total']} floats, scratch rows hold {arenas.shape[1]}")
+            slices = backbone_slices(layout, self.backbone_params)
+            if not slices:
+                raise L.LnxError("GradNorm: no backbone parameter is differentiated by the model's plan")
+            arr, blk = gradnorm_desc_table(slices, arenas.data_ptr())
+            table = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(arenas.device)
+            self._gn = {"key": key, "table": table, "ndesc": len(slices), "blocks": blk,
+                        "ws": torch.empty(len(self.task_keys) * blk, device=arenas.device, dtype=torch.float32)}
+        return self._gn
+
+    def _sumsq(self, arenas, first: int, ntasks: int, norm: torch.Tensor, stream) -> None:
+        g = self._descs(arenas)
+        L.check(L.lib().lnx_gradnorm_sumsq(C.c_void_p(g["table"].data_ptr()), g["ndesc"], g["blocks"], ntasks, arenas.stride(0), None,
+                                           C.c_void_p(norm.data_ptr() + 4 * first), C.c_void_p(g["ws"].data_ptr()), stream), "lnx_gradnorm_sumsq")
+
+    def update_gradnorm_weights_reforward(self, data_batch, criteria, amp_enabled: bool = True, ops_schedule=None, current_step=None, *,
+                                          sync: bool = True, keep_step_grads: Optional[bool] = None) -> Dict[str, Any]:
+        """One GradNorm update (gradient_weighting.py:367-880) on `data_batch` = (images, {task: targets}, aux_info, ...).  The step's
+        own gradients are not touched except that backbone .grad are set to None as in the reference (keep_step_grads=True: left
+        alone).  Returns the reference's metrics: floats, or with sync=False device scalars (no host sync in the whole update)."""
+        if self.task_weighting_type != "gradnorm" or self.gradnorm is None:
+            return {}
+        if self.model is None or not self.backbone_params:
+            raise RuntimeError("GradientWeighting.set_model(model) must be called before a GradNorm update")
+        net = self._net
+        keep = self.keep_step_grads if keep_step_grads is None else bool(keep_step_grads)
+        images, targets, aux = data_batch[0], data_batch[1], data_batch[2]
+        dev = images.device
+        aux_g = torch.zeros_like(aux) if (self.zero_aux_info and aux is not None) else aux
+        S = max(1, int(_cfg_get(self.config, "LOSS.GRAD_WEIGHTING.TASK.GRADNORM_ACCUM_STEPS", 1)))
+        ckpt = bool(_cfg_get(self.config, "TRAIN.GRADIENT_CHECKPOINTING.ENABLED_GRADNORM_STEPS", False))
+        T = len(self.task_keys)
+        plan_tasks = net._task_list()
+        order = sorted(self.task_keys)  # measure_and_update's indexing
+        if sorted(plan_tasks) != order:
+            raise ValueError(f"GradNorm tasks {self.task_keys} differ from the model's heads {plan_tasks}")
+        gn = self.gradnorm.to(dev)
+        stats = torch.zeros(2, T, device=dev, dtype=torch.float32)  # loss_sum, valid count per plan task
+        norm_plan = torch.zeros(T, device=dev, dtype=torch.float32)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        was_training = net.training
+        net.train()
+        try:
+            B = images.shape[0]
+            for s in range(S):
+                lo = s * (B // S)
+                hi = B if s == S - 1 else (s + 1) * (B // S)
+                sb_t = {k: v[lo:hi].to(dev) for k, v in targets.items()}
+
+                def seed(t, logits_t, dl_t, sb_t=sb_t):
+                    name = plan_tasks[t]
+                    y = sb_t[name]
+                    valid = (y != 0) if y.dim() == 1 else (y[:, 0] <= 0.5)
+                    cnt = valid.sum().float()
+                    crit = criteria[name]
+                    if isinstance(crit, TaxonomyAwareLabelSmoothingCE):
+                        tgt = (y.argmax(dim=1) if y.dim() == 2 else y).to(torch.long).contiguous()
+                        cw = crit.weight.to(dev) if (crit.apply_class_weights and crit.weight is not None) else None
+                        rs = valid.float() / cnt.clamp_min(1.0)
+                        per = torch.empty(y.shape[0], device=dev, dtype=torch.float32)
+                        _launch(_as_rows(logits_t), tgt, crit.soft_labels.to(dev), 0.0, cw, crit.ignore_index, rs, 1.0, per, None, dl_t)
+                        lsum = torch.where(valid, per, torch.zeros((), device=dev)).sum()
+                    else:  # any other criterion: autograd on a detached [B, C] leaf, never on the model
+                        leaf = logits_t.detach().clone().requires_grad_(True)
+                        with torch.enable_grad():
+                            vec = crit(leaf, y)
+                            lsum = vec[valid].sum()
+                            g, = torch.autograd.grad(lsum / cnt.clamp_min(1.0), leaf, allow_unused=True)
+                        if g is not None:
+                            dl_t.copy_(g)
+                        lsum = lsum.detach().float()
+                    stats[0, t] += lsum
+                    stats[1, t] += cnt
+
+                after = None
+                if S == 1:
+                    after = lambda t: self._sumsq(net._gn_scratch, t, 1, norm_plan, stream)  # noqa: E731  (the one arena is reused)
+                with torch.no_grad():
+                    net._task_backbone_grads(images[lo:hi], aux_g[lo:hi] if aux_g is not None else None, seed, 1 if S == 1 else T, ckpt,
+                                             accumulate=s > 0, after_task=after)
+            if S > 1:
+                self._sumsq(net._gn_scratch, 0, T, norm_plan, stream)
+        finally:
+            net.train(was_training)
+        if self._gn.get("perm") is None or self._gn["perm"].device != dev:
+            self._gn["perm"] = torch.tensor([plan_tasks.index(k) for k in order], device=dev)
+        perm = self._gn["perm"]
+        norm = norm_plan[perm]
+        loss_sum, count = stats[0][perm].contiguous(), stats[1][perm].contiguous()
+        init_loss = None
+        distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if distributed:  # the reference all-reduces each norm (and, once, each loss) and divides by the world size
+            ws = dist.get_world_size()
+            dist.all_reduce(norm)
+            norm = norm / ws
+            if gn.alpha > 0 and not gn.has_initted:
+                init_loss = loss_sum / count.clamp_min(1.0)
+                dist.all_reduce(init_loss)
+                init_loss = init_loss / ws
+        metrics = torch.empty(1 + 5 * T, device=dev, dtype=torch.float32)
+        a = L.GradNormArgs()
+        a.T, a.alpha = T, gn.alpha
+        a.norm, a.loss_sum, a.count = norm.data_ptr(), loss_sum.data_ptr(), count.data_ptr()
+        a.init_loss = init_loss.data_ptr() if init_loss is not None else None
+        a.weights, a.initial_losses, a.initted, a.metrics = gn.task_weights.data_ptr(), gn.initial_losses.data_ptr(), gn._initted.data_ptr(), metrics.data_ptr()
+        L.check(L.lib().lnx_gradnorm_update(C.byref(a), stream), "lnx_gradnorm_update")
+        if gn.alpha > 0:
+            gn.has_initted = True
+        self._gn_keepalive = (norm, loss_sum, count, init_loss, stats, norm_plan)  # (the launches above read them)
+        if not keep:
+            for p_ in self.backbone_params:
+                p_.grad = None
+        vals = metrics.tolist() if sync else metrics
+        out = {"gradnorm/avg_norm": vals[0]}
+        kinds = ("loss", "norm", "target", "weight") + (("ratio",) if gn.alpha > 0 else ())
+        for j, kind in enumerate(kinds):
+            for i, k in enumerate(order):
+                out[f"gradnorm/{kind}/{k}"] = vals[1 + j * T + i]
+        return out
+
     def forward(self, per_task_losses, targets, subset_ids=None, mixed_subset_ids=None, num_valid_samples_per_task=None):
         first = next(iter(per_task_losses.values()))
-        norm_w = self._normalize_weights(self.task_weights)
+        if self.gradnorm is not None:
+            norm_w = self.gradnorm.task_weights.to(device=first.device, dtype=first.dtype)  # task_keys order, as the reference reads it
+        else:
+            norm_w = self._normalize_weights(self.task_weights)
         weighted = {}
         for i, t in enumerate(self.task_keys):
             vec = per_task_losses[t]
@@ -349,7 +622,9 @@ class GradientWeighting(nn.Module):
             if self.class_weights and t in self.class_weights:
                 vec = vec * _sample_weights(self.class_weights[t], targets[t], self._cache, t).to(vec.dtype)
             denom = nv.to(vec.dtype).clamp_min(1e-6) if isinstance(nv, torch.Tensor) else max(float(nv), 1e-6)
-            weighted[t] = vec.sum() / denom * float(norm_w[i])
+            weighted[t] = vec.sum() / denom * (norm_w[i] if self.gradnorm is not None else float(norm_w[i]))
+        if self.gradnorm is not None:  # device scalars: no host sync in the step
+            return weighted, {t: norm_w[i] for i, t in enumerate(self.task_keys)}
         return weighted, dict(zip(self.task_keys, norm_w.tolist()))
 
 

@@ -446,11 +446,17 @@ class mFormerV1(nn.Module):
         return self.plan_footprint(batch, H, W, train, recompute)["workspace"]
 
     def plan_footprint(self, batch: int, img_h: Optional[int] = None, img_w: Optional[int] = None, train: bool = True,
-                       recompute: Optional[bool] = None) -> Dict[str, int]:
+                       recompute: Optional[bool] = None, gradnorm_arenas: int = 0) -> Dict[str, int]:
         """Everything a plan of this shape holds on the device, computed by the native planner without allocating: the
         workspace, the per-forward dropout keep masks that live OUTSIDE it (`lnx_plan_dropout_bytes` /
         `lnx_plan_attn_dropout_bytes`; only when MODEL.DROP_RATE / ATTN_DROP_RATE > 0 and in training) and the fp32 logits
-        buffer (the forward's output and, in training, the persistent dlogits buffer of the same size)."""
+        buffer (the forward's output and, in training, the persistent dlogits buffer of the same size).  With
+        `gradnorm_arenas` > 0 the dict also holds "gradnorm": the scratch gradient arenas of a GradNorm update
+        (`loss.GradientWeighting.scratch_arenas()`: 1, or T with GRADNORM_ACCUM_STEPS > 1) and its dlogits buffer."""
+        if gradnorm_arenas:
+            fp = self.plan_footprint(batch, img_h, img_w, train, recompute)
+            fp["gradnorm"] = int(gradnorm_arenas) * 4 * self.grad_arena_layout()["total"] + fp["logits"] // 2
+            return fp
         lib = L.lib()
         for fn in (lib.lnx_plan_workspace_bytes, lib.lnx_plan_dropout_bytes, lib.lnx_plan_attn_dropout_bytes, lib.lnx_plan_logits_numel):
             fn.restype = C.c_int64
@@ -723,6 +729,62 @@ class mFormerV1(nn.Module):
         snap = self._grad_arena.clone()
         base = self._grad_arena.data_ptr()
         return [snap[(v.data_ptr() - base) // 4: (v.data_ptr() - base) // 4 + v.numel()].view(v.shape) for v in views]
+
+    # ------------------------------------------------------------------ GradNorm
+    def _gradnorm_arenas(self, n: int) -> torch.Tensor:
+        """[n, arena floats] fp32 scratch with the gradient arena's layout (one row per task when GradNorm accumulates sub-batches),
+        allocated once per (n, layout).  Allocation failure raises: the reference silently skips a task under memory pressure."""
+        total = self._grad_arena.numel()
+        cur = getattr(self, "_gn_scratch", None)
+        if cur is None or cur.shape != (n, total) or cur.device != self._grad_arena.device:
+            self._gn_scratch = None
+            try:
+                self._gn_scratch = torch.empty(n, total, dtype=torch.float32, device=self._grad_arena.device)
+            except torch.cuda.OutOfMemoryError as e:
+                raise L.LnxError(f"GradNorm needs {n} scratch gradient arena(s) of {4 * total / 2**20:.1f} MiB each: {e}") from e
+        return self._gn_scratch
+
+    def _task_backbone_grads(self, x: torch.Tensor, meta: Optional[torch.Tensor], seeds, n_arenas: int = 1, force_checkpointing: Optional[bool] = None,
+                             accumulate: bool = False, after_task=None) -> torch.Tensor:
+        """GradNorm's per-task gradients without an autograd graph: ONE training forward of the plan (one DropPath / dropout draw),
+        then per task t one lnx_plan_backward_into seeded by task t's dlogits alone, into row t of the returned [n_arenas, arena floats]
+        scratch (`_gradnorm_arenas`; row 0 for every task when n_arenas = 1, zeroed before each task).  `seeds(t, logits_t, dl_t)` writes task t's dlogits into dl_t ([B, classes]
+        view of a zeroed buffer in the plan's layout); `after_task(t)` runs once task t's backward is enqueued.  `accumulate`: add
+        into the rows (sub-batches 2.. of GRADNORM_ACCUM_STEPS).  The hierarchical refinement is not applied
+        (USE_LINEAR_HEADS_FOR_GRADNORM_REFORWARD), and the bound gradient arena / every .grad stay untouched."""
+        if not x.is_cuda:
+            raise L.LnxError("mFormerV1 (linnaeus_amd) has no CPU path: inputs must be on the GPU")
+        x = x.float().contiguous()
+        B, _, H, W = x.shape
+        meta = meta.float().contiguous() if (self.use_meta and self.meta_dims) else None
+        st = self._get_plan(B, H, W, True, self._wants_recompute(force_checkpointing))
+        self._active = st
+        drop = self._draw_drop_scales(st, B, x.device)
+        self._set_dropout(st, True, x.device)
+        _, logits = self._plan_forward(x, meta, drop)
+        views = self._task_views(st, logits, B)
+        dl = torch.zeros(max(st["logits_numel"], 1), device=x.device, dtype=torch.float32)
+        dl_views = self._task_views(st, dl, B)
+        n, T = st["n"], len(st["tasks"])
+        if n_arenas not in (1, T):
+            raise L.LnxError(f"GradNorm uses 1 or {T} scratch gradient arenas, not {n_arenas}")
+        arenas = self._gradnorm_arenas(n_arenas)
+        base = self._grad_arena.data_ptr()
+        offs = [v.data_ptr() - base for v in self._grad_views]
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        lib = L.lib()
+        for t in range(T):
+            row = arenas[t if arenas.shape[0] > 1 else 0]
+            if not accumulate or arenas.shape[0] == 1:
+                row.zero_()
+            seeds(t, views[t], dl_views[t])
+            ptrs = (C.c_void_p * n)(*[row.data_ptr() + o for o in offs])
+            L.check(lib.lnx_plan_backward_into(st["handle"], C.c_void_p(dl.data_ptr()) if st["logits_numel"] else None, None, ptrs, stream),
+                    "lnx_plan_backward_into")
+            dl_views[t].zero_()
+            if after_task is not None:
+                after_task(t)
+        return arenas
 
     # ------------------------------------------------------------------ public forward
     def _run(self, x: torch.Tensor, meta: Optional[torch.Tensor], force_checkpointing: Optional[bool] = None):
