@@ -296,40 +296,51 @@ int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* args, void* stream);
 /* ------------------------------------------------------------------------------------
  * Attention with the reference's cos-only "2D RoPE" (SURVEY F1), global over N tokens.
  *   cos table: rope_2d_mhsa.py:56-73,114-155,397-408; q,k scaling :176-218,440-456;
- *   scores/softmax/AV :495-501.  head_dim is 64 for every shipped config.
- * qkv is the raw output of the qkv Linear, [B*N, 3*C] with column = which*C + head*64 + d
- * (:432-437); o is [B*N, C] with column = head*64 + d (:501).  The first E tokens of each
+ *   scores/softmax/AV :495-501.  head_dim D = C / heads is 32, 64 or 128 (64 in every shipped
+ * config; the reference takes any, rope_2d_mhsa.py:76-111, scale D^-0.5).  Every struct and call
+ * below that carries a head_dim takes 0 for 64, so callers written for head_dim 64 are unchanged.
+ * head_dim 64 runs the resident kernels (bf16, N <= 256) or the tiled ones; 32 and 128 the tiled ones.
+ * qkv is the raw output of the qkv Linear, [B*N, 3*C] with column = which*C + head*D + d
+ * (:432-437); o is [B*N, C] with column = head*D + d (:501).  The first E tokens of each
  * sample are extra (CLS/meta) tokens and are not scaled by cos.
  * -----------------------------------------------------------------------------------*/
+/* head_dim 64 */
 int lnx_rope_cos_table(const float* freqs /* [2,heads,32] */, int heads, int H, int W, float* cos_out /* [H*W,heads,32] */,
                        float* dsin_out /* optional [2][H*W,heads,32]: -t_x sin(theta), -t_y sin(theta) = d cos(theta) / d freqs[a] (what
                                           lnx_attn_bwd weights its pair gradients with) */,
                        void* stream);
+/* any supported head_dim D: freqs [2,heads,D/2], cos_out [H*W,heads,D/2], dsin_out optional [2][H*W,heads,D/2] */
+int lnx_rope_cos_table_hd(const float* freqs, int heads, int head_dim, int H, int W, float* cos_out, float* dsin_out, void* stream);
 /* The same tables for several blocks in one launch (each RoPE block owns its freqs, rope_2d_mhsa.py:397-408; a plan fills the
- * tables of all its blocks once per forward, off the main stream).  Entries as lnx_rope_cos_table's arguments. */
+ * tables of all its blocks once per forward, off the main stream).  Entries as lnx_rope_cos_table_hd's arguments; one launch per
+ * head_dim present. */
 #define LNX_ROPE_TABLES_MAX 24
 typedef struct {
-    const float* freqs; /* [2,heads,32] */
-    float* cos_out;     /* [H*W,heads,32] */
-    float* dsin_out;    /* optional [2][H*W,heads,32] */
-    int heads, H, W, pad_;
+    const float* freqs; /* [2,heads,D/2] */
+    float* cos_out;     /* [H*W,heads,D/2] */
+    float* dsin_out;    /* optional [2][H*W,heads,D/2] */
+    int heads, H, W;
+    int head_dim;       /* D; 0 = 64 */
 } lnx_rope_table;
 int lnx_rope_cos_tables(const lnx_rope_table* tables, int n, void* stream);
-/* floats of lnx_attn_bwd's freqs-gradient workspace (one [2][32] partial per workgroup of its finest tiling) */
+/* floats of lnx_attn_bwd's freqs-gradient workspace (one [2][D/2] partial per workgroup of its finest tiling): head_dim 64, and any
+ * supported head_dim (0 for an unsupported one) */
 int64_t lnx_attn_bwd_ws_floats(int B, int N, int heads);
+int64_t lnx_attn_bwd_ws_floats_hd(int B, int N, int heads, int head_dim);
 
 typedef struct lnx_attn_args {
     int dtype;
     int B, N, E, heads;
-    const void* qkv;     /* [B*N, 3*heads*64] */
-    const float* cos_tab;/* [(N-E), heads, 32] */
-    void* o;             /* [B*N, heads*64] */
+    const void* qkv;     /* [B*N, 3*heads*D] */
+    const float* cos_tab;/* [(N-E), heads, D/2] */
+    void* o;             /* [B*N, heads*D] */
     float* lse;          /* [B, heads, N] log-sum-exp of the scaled scores */
     const unsigned char* drop_mask; /* optional (training with MODEL.ATTN_DROP_RATE, rope_2d_mhsa.py:497): keep mask of the attention
                                        probabilities, one byte per (b, head, query, key), [B, heads, N, Np] with Np = N rounded up to
                                        a multiple of 64; P is multiplied by mask * drop_inv_keep AFTER the softmax normalisation.
                                        Runs the 64-row tiled kernels (the dropout-free path keeps its own instantiations). */
     float drop_inv_keep; /* 1 / (1 - ATTN_DROP_RATE) */
+    int head_dim;        /* D: 32, 64 or 128; 0 = 64 */
 } lnx_attn_args;
 int lnx_attn_fwd(const lnx_attn_args* args, void* stream);
 
@@ -340,20 +351,21 @@ typedef struct lnx_attn_bwd_args {
     const float* cos_tab;
     const void* o;
     const float* lse;
-    const void* d_o;     /* [B*N, heads*64] */
-    void* dqkv;          /* [B*N, 3*heads*64] */
-    float* freq_ws;      /* workspace, lnx_attn_bwd_ws_floats(B, N, heads) floats (overwritten): round 3 -- the gradient of the learnable
+    const void* d_o;     /* [B*N, heads*D] */
+    void* dqkv;          /* [B*N, 3*heads*D] */
+    float* freq_ws;      /* workspace, lnx_attn_bwd_ws_floats_hd(B, N, heads, D) floats (overwritten): round 3 -- the gradient of the learnable
                             frequencies (autograd of compute_mixed_cis / apply_rotary_emb through the real part only, finding F1) is
-                            reduced inside the two backward kernels to one [2][32] partial per workgroup; it used to be a
-                            [2][B, N-E, heads, 32] tensor read back by a separate lnx_rope_freqs_bwd */
+                            reduced inside the two backward kernels to one [2][D/2] partial per workgroup; it used to be a
+                            [2][B, N-E, heads, D/2] tensor read back by a separate lnx_rope_freqs_bwd */
     float* delta;        /* workspace [B, heads, N] */
     const unsigned char* drop_mask; /* the forward's keep mask (see lnx_attn_args), or NULL */
     float drop_inv_keep;
-    const float* dsin_tab; /* [2][(N-E), heads, 32] from lnx_rope_cos_table */
-    float* dfreqs;         /* [2, heads, 32] fp32, accumulated into (dfreqs += ...) */
+    const float* dsin_tab; /* [2][(N-E), heads, D/2] from lnx_rope_cos_table(_hd) */
+    float* dfreqs;         /* [2, heads, D/2] fp32, accumulated into (dfreqs += ...) */
     int defer_freqs;       /* 1: leave the fold of freq_ws into dfreqs to lnx_attn_bwd_flush (one launch for up to LNX_ATTN_DEFER_MAX calls of
                               this thread on this stream; freq_ws and dfreqs must stay untouched and alive until then -- a plan gives every
                               pending call its own freq_ws region and flushes at the end of each backward segment) */
+    int head_dim;          /* D: 32, 64 or 128; 0 = 64 */
 } lnx_attn_bwd_args;
 #define LNX_ATTN_DEFER_MAX 16
 int lnx_attn_bwd_flush(void* stream); /* folds every postponed call of this thread; refuses a stream other than theirs */
@@ -778,7 +790,7 @@ typedef struct lnx_mformer_cfg {
     int dims[4];               /* CONVNEXT_STAGES.DIMS (dims[2:] are the RoPE dims) */
     int conv_depths[2];        /* CONVNEXT_STAGES.DEPTHS[0:2] */
     int rope_depths[2];
-    int rope_heads[2];
+    int rope_heads[2];         /* dims[2+s] / rope_heads[s] = head_dim: 32, 64 or 128 */
     int mlp_hidden[2];         /* int(dim * MLP_RATIO) */
     int n_meta;                /* enabled metadata components, 0 = metadata inactive */
     int meta_dims[LNX_MAX_META];

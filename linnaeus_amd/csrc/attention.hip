@@ -3,8 +3,9 @@
 // Reference: RoPE2DAttention.forward, standard path (blocks/rope_2d_mhsa.py:422-505):
 //   q,k image tokens scaled pairwise by cos(theta) (:176-218, finding F1), q *= d^-0.5
 //   (:456), S = q k^T in fp32 (:495), softmax (:496), O = P v (:498), O laid out [B,N,h*d].
-// head_dim is 64 in every shipped config.  N is small (52..580), so the whole problem of a
-// (batch, head) pair is a few 64-key tiles; parallelism comes from batch x heads x q-tiles.
+// head_dim (HD) is 32, 64 or 128: 64 in every shipped config, and the only one the resident kernels take (the tiled kernels,
+// the tables and the freqs fold are templated on it).  N is small (52..580), so the whole problem of a (batch, head) pair is a
+// few 64-key tiles; parallelism comes from batch x heads x q-tiles.
 //
 // Layout trick used everywhere below: score tiles are computed TRANSPOSED (keys in the
 // accumulator registers, the query -- or in the dK/dV kernel the key -- on the lane), so
@@ -17,25 +18,31 @@
 //           attn_bwd_dkv  (per 64 keys:    dk, dv, cos-gradient part of k)
 #include <stdlib.h>
 
+#include <vector>
+
 #include "common.hpp"
 #include "../../include/lnx.h"
 
 namespace {
 
-constexpr int HD = 64;   // head dim
 constexpr int BT = 64;   // rows per tile (queries or keys)
 
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 
-template <typename T> struct AT {
+template <typename T, int HD = 64> struct AT {
+    static_assert(HD == 32 || HD == 64 || HD == 128, "head_dim 32, 64 or 128");
     static constexpr int EPV = TT<T>::EPV;
-    static constexpr int NKK = sizeof(T);               // 64-byte k-chunks per head row (2 bf16 / 4 fp32)
-    static constexpr int ROWB = HD * sizeof(T);         // bytes per row in the row image
-    static constexpr int NCH = ROWB / 16;               // 16-byte chunks per row
-    static constexpr int TRB = sizeof(T) == 2 ? 160 : 272;  // padded row bytes of the transposed-read image
+    static constexpr int NKK = HD * (int)sizeof(T) / 64;  // 64-byte k-chunks per head row (HD 64: 2 bf16 / 4 fp32)
+    static constexpr int ND = HD / 16;                    // 16-channel groups of an output row (accumulators per lane)
+    static constexpr int ROWB = HD * sizeof(T);           // bytes per row in the row image
+    static constexpr int NCH = ROWB / 16;                 // 16-byte chunks per row
+    static constexpr int SWZ = (NCH < 8 ? NCH : 8) - 1;   // row-image swizzle mask (r & 7; r & 3 for the 4-chunk bf16 HD 32 row)
+    static constexpr int TRB = ROWB + (sizeof(T) == 2 ? 32 : 16);  // padded row bytes of the transposed-read image (HD 64: 160 / 272)
     static constexpr int ROW_IMG = BT * ROWB;
     static constexpr int TR_IMG = BT * TRB;
 };
+// HD^-0.5 as the reference's fp32 product q * head_dim**-0.5 rounds it
+template <int HD> constexpr float attn_scale() { return HD == 32 ? 0.17677669529663688f : HD == 64 ? 0.125f : 0.08838834764831845f; }
 
 __device__ __forceinline__ void mfma_bf16(f32x4_t& acc, const uint4& a, const uint4& b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
@@ -63,14 +70,14 @@ __device__ __forceinline__ uint2 tr_read(const unsigned char* p) {
 // batch before the first use: fetch() is unconditional (a row beyond N reads row N - 1, a class token reads the first
 // cos row) -- a load under `if (n < N)` whose result is merged with a zero is waited for on the spot, which turns a
 // staging loop into one memory round trip per chunk.
-template <typename T, bool COS> struct Chunk {
+template <typename T, bool COS, int HD = 64> struct Chunk {
     uint4 raw;
     float cf[COS ? TT<T>::EPV / 2 : 1];
     __device__ __forceinline__ void fetch(const T* __restrict__ base, int64_t ld, int n, int N, int E, int d0, const float* __restrict__ cos_tab, int heads, int head) {
         const int nc = min(n, N - 1);
         raw = ld16(base + (int64_t)nc * ld + d0);
         if constexpr (COS) {
-            const float* cp = cos_tab + ((int64_t)max(nc - E, 0) * heads + head) * 32 + (d0 >> 1);
+            const float* cp = cos_tab + ((int64_t)max(nc - E, 0) * heads + head) * (HD / 2) + (d0 >> 1);
             if constexpr (TT<T>::EPV == 8) {
                 const float4 c4 = *reinterpret_cast<const float4*>(cp);
                 cf[0] = c4.x; cf[1] = c4.y; cf[2] = c4.z; cf[3] = c4.w;
@@ -115,7 +122,7 @@ __device__ __forceinline__ void stage_tile(unsigned char* rowimg, unsigned char*
     for (int i = threadIdx.x; i < BT * NCH; i += NT) {
         const int r = i / NCH, c = i % NCH;
         const uint4 v = load_chunk<T, COS>(base, ld, n0 + r, N, E, c * EPV, cos_tab, heads, head, scale);
-        if constexpr (ROWIMG) st16(rowimg + r * AT<T>::ROWB + ((c ^ (r & 7)) << 4), v);
+        if constexpr (ROWIMG) st16(rowimg + r * AT<T>::ROWB + ((c ^ (r & AT<T>::SWZ)) << 4), v);
         if constexpr (TRIMG) st16(trimg + r * AT<T>::TRB + c * 16, v);
     }
 }
@@ -123,10 +130,12 @@ __device__ __forceinline__ void stage_tile(unsigned char* rowimg, unsigned char*
 // The same staging split in two, for the tiled kernels' software pipeline: fetch() requests a 64-row tile into registers
 // (unconditional, clamped rows -- call it for min(next, last) rather than under `if (more)`), commit() writes it to the LDS
 // images one loop trip later, after the products of the current tile have been issued in between.
-template <typename T, bool COS, int NT>
+template <typename T, bool COS, int NT, int HD = 64>
 struct TileFetch {
-    static constexpr int NCH = AT<T>::NCH, EPV = AT<T>::EPV, PER = BT * NCH / NT;
-    Chunk<T, COS> ch[PER];
+    using A = AT<T, HD>;
+    static constexpr int NCH = A::NCH, EPV = A::EPV, PER = BT * NCH / NT;
+    static_assert(PER > 0 && PER * NT == BT * NCH, "a tile's chunks split evenly over the workgroup");
+    Chunk<T, COS, HD> ch[PER];
     __device__ __forceinline__ void fetch(const T* __restrict__ base, int64_t ld, int n0, int N, int E, const float* __restrict__ cos_tab, int heads, int head) {
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
@@ -141,21 +150,21 @@ struct TileFetch {
             const int i = threadIdx.x + u * NT;
             const int r = i / NCH, c = i % NCH;
             const uint4 v = ch[u].value(n0 + r, N, E, scale);
-            if constexpr (ROWIMG) st16(rowimg + r * AT<T>::ROWB + ((c ^ (r & 7)) << 4), v);
-            if constexpr (TRIMG) st16(trimg + r * AT<T>::TRB + c * 16, v);
+            if constexpr (ROWIMG) st16(rowimg + r * A::ROWB + ((c ^ (r & A::SWZ)) << 4), v);
+            if constexpr (TRIMG) st16(trimg + r * A::TRB + c * 16, v);
         }
     }
 };
 
 // fragment of a row operand held in registers: lane (s, g) <- token row, chunks kk*4 + g
-template <typename T, bool COS>
-__device__ __forceinline__ void load_row_frag(uint4 (&f)[AT<T>::NKK], const T* __restrict__ base, int64_t ld, int n, int N, int E, int g,
+template <typename T, bool COS, int HD = 64>
+__device__ __forceinline__ void load_row_frag(uint4 (&f)[(AT<T, HD>::NKK)], const T* __restrict__ base, int64_t ld, int n, int N, int E, int g,
                                               const float* __restrict__ cos_tab, int heads, int head, float scale) {
-    Chunk<T, COS> c[AT<T>::NKK];
+    Chunk<T, COS, HD> c[(AT<T, HD>::NKK)];
 #pragma unroll
-    for (int kk = 0; kk < AT<T>::NKK; ++kk) c[kk].fetch(base, ld, n, N, E, (kk * 4 + g) * AT<T>::EPV, cos_tab, heads, head);
+    for (int kk = 0; kk < AT<T, HD>::NKK; ++kk) c[kk].fetch(base, ld, n, N, E, (kk * 4 + g) * AT<T, HD>::EPV, cos_tab, heads, head);
 #pragma unroll
-    for (int kk = 0; kk < AT<T>::NKK; ++kk) f[kk] = c[kk].value(n, N, E, scale);
+    for (int kk = 0; kk < AT<T, HD>::NKK; ++kk) f[kk] = c[kk].value(n, N, E, scale);
 }
 
 // acc[t] (t = 0..3, 16 rows each) = Rows(img, row0 + 16 t + s) . frag^T over the 64 channels
@@ -169,7 +178,7 @@ __device__ __forceinline__ void rows_times_frag(f32x4_t (&acc)[4], const unsigne
         const int row = t * 16 + s;
 #pragma unroll
         for (int kk = 0; kk < AT<T>::NKK; ++kk) {
-            const uint4 a = ld16(rowimg + row * AT<T>::ROWB + (((kk * 4 + g) ^ (row & 7)) << 4));
+            const uint4 a = ld16(rowimg + row * AT<T>::ROWB + (((kk * 4 + g) ^ (row & AT<T>::SWZ)) << 4));
             mfma_chunk<T>(acc[t], a, frag[kk]);
         }
     }
@@ -260,23 +269,25 @@ __device__ __forceinline__ void rows_times_frag_pad_n(f32x4_t (&acc)[4], const u
 #pragma unroll
         for (int kk = 0; kk < AT<T>::NKK; ++kk) mfma_chunk<T>(acc[t], a[t][kk], frag[kk]);
 }
-template <typename T, int NT>
-__device__ __forceinline__ void rows_times_frag_n(f32x4_t (&acc)[4], const unsigned char* rowimg, int s, int g, const uint4 (&frag)[AT<T>::NKK]) {
-    uint4 a[NT][AT<T>::NKK];
+template <typename T, int NT, int HD = 64>
+__device__ __forceinline__ void rows_times_frag_n(f32x4_t (&acc)[4], const unsigned char* rowimg, int s, int g, const uint4 (&frag)[(AT<T, HD>::NKK)]) {
+    using A = AT<T, HD>;
+    uint4 a[NT][A::NKK];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int kk = 0; kk < AT<T>::NKK; ++kk) a[t][kk] = ld16(rowimg + (t * 16 + s) * AT<T>::ROWB + (((kk * 4 + g) ^ ((t * 16 + s) & 7)) << 4));
+        for (int kk = 0; kk < A::NKK; ++kk) a[t][kk] = ld16(rowimg + (t * 16 + s) * A::ROWB + (((kk * 4 + g) ^ ((t * 16 + s) & A::SWZ)) << 4));
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int kk = 0; kk < AT<T>::NKK; ++kk) mfma_chunk<T>(acc[t], a[t][kk], frag[kk]);
+        for (int kk = 0; kk < A::NKK; ++kk) mfma_chunk<T>(acc[t], a[t][kk], frag[kk]);
 }
 // p[t] of the groups t >= NT must be zero (the image rows behind them may lie beyond the staged part only for t >= 2 ceil(NT / 2))
-template <typename T, int NT>
-__device__ __forceinline__ void imgT_times_regs_n(f32x4_t (&out)[4], const unsigned char* trimg, int s, int g, const float (&p)[4][4]) {
+template <typename T, int NT, int HD = 64>
+__device__ __forceinline__ void imgT_times_regs_n(f32x4_t (&out)[HD / 16], const unsigned char* trimg, int s, int g, const float (&p)[4][4]) {
+    using A = AT<T, HD>;
     if constexpr (sizeof(T) == 2) {
         constexpr int NKS = (NT + 1) / 2;
         uint4 pf[NKS];
@@ -287,21 +298,21 @@ __device__ __forceinline__ void imgT_times_regs_n(f32x4_t (&out)[4], const unsig
             for (int j = 0; j < 8; ++j) v.set(j, p[2 * ks + (j >> 2)][j & 3]);
             pf[ks] = v.raw;
         }
-        uint2 a0[NKS][4], a1[NKS][4];
+        uint2 a0[NKS][A::ND], a1[NKS][A::ND];
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             const int r0 = ks * 32 + 4 * g + (s >> 2);
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
+            for (int dt = 0; dt < A::ND; ++dt) {
                 const int col = (dt * 16 + 4 * (s & 3)) * 2;
-                a0[ks][dt] = tr_read(trimg + r0 * AT<T>::TRB + col);
-                a1[ks][dt] = tr_read(trimg + (r0 + 16) * AT<T>::TRB + col);
+                a0[ks][dt] = tr_read(trimg + r0 * A::TRB + col);
+                a1[ks][dt] = tr_read(trimg + (r0 + 16) * A::TRB + col);
             }
         }
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) mfma_bf16(out[dt], make_uint4(a0[ks][dt].x, a0[ks][dt].y, a1[ks][dt].x, a1[ks][dt].y), pf[ks]);
+            for (int dt = 0; dt < A::ND; ++dt) mfma_bf16(out[dt], make_uint4(a0[ks][dt].x, a0[ks][dt].y, a1[ks][dt].x, a1[ks][dt].y), pf[ks]);
     } else {
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -309,8 +320,8 @@ __device__ __forceinline__ void imgT_times_regs_n(f32x4_t (&out)[4], const unsig
             for (int r = 0; r < 4; ++r) {
                 const int row = t * 16 + 4 * g + r;
 #pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const float a = *reinterpret_cast<const float*>(trimg + row * AT<T>::TRB + (dt * 16 + s) * 4);
+                for (int dt = 0; dt < A::ND; ++dt) {
+                    const float a = *reinterpret_cast<const float*>(trimg + row * A::TRB + (dt * 16 + s) * 4);
                     mfma_f32(out[dt], a, p[t][r]);
                 }
             }
@@ -332,37 +343,54 @@ template <typename T> __device__ __forceinline__ void store4(T* p, float a, floa
     }
 }
 
-// One 64-element head row held as v[dt][0..3] = elements 16 dt + 4 g .. + 3 by the four lanes g of a row (the layout every
-// kernel here ends with).  fp32: four 16-byte stores.  bf16: lanes g and g ^ 1 swap halves first, so that the even one writes
-// elements 16 dt + 4 g .. + 7 of dt = 0, 2 and the odd one those of dt = 1, 3 -- two 16-byte stores a lane instead of four 8-byte
-// ones (whose half-filled 32-byte sectors made the key-side backward write 1.4x its output).  EVERY lane of the wave must call
+// One HD-element head row held as v[dt][0..3] = elements 16 dt + 4 g .. + 3 by the four lanes g of a row (the layout every
+// kernel here ends with).  fp32: HD / 16 16-byte stores.  bf16: lanes g and g ^ 1 swap halves first, so that the even one writes
+// elements 16 dt + 4 g .. + 7 of the even dt and the odd one those of the odd dt -- HD / 32 16-byte stores a lane instead of HD / 16
+// 8-byte ones (whose half-filled 32-byte sectors made the key-side backward write 1.4x its output).  EVERY lane of the wave must call
 // (the exchange is a cross-lane operation); `live` gates the stores only.
-template <typename T> __device__ __forceinline__ void store_row64(T* rowp, const float (&v)[4][4], int g, bool live) {
+template <typename T, int HD = 64> __device__ __forceinline__ void store_row(T* rowp, const float (&v)[HD / 16][4], int g, bool live) {
+    constexpr int ND = HD / 16;
     if constexpr (sizeof(T) == 4) {
         if (live) {
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<float4*>(rowp + dt * 16 + 4 * g) = make_float4(v[dt][0], v[dt][1], v[dt][2], v[dt][3]);
+            for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<float4*>(rowp + dt * 16 + 4 * g) = make_float4(v[dt][0], v[dt][1], v[dt][2], v[dt][3]);
         }
     } else {
-        uint2 pk[4];
+        uint2 pk[ND];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
+        for (int dt = 0; dt < ND; ++dt) {
             T* h = reinterpret_cast<T*>(&pk[dt]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) h[j] = from_f<T>(v[dt][j]);
         }
         const bool even = (g & 1) == 0;
-        const uint2 s0 = even ? pk[1] : pk[0], s1 = even ? pk[3] : pk[2];
-        uint2 r0, r1;
-        r0.x = (uint32_t)__shfl_xor((int)s0.x, 16, 64); r0.y = (uint32_t)__shfl_xor((int)s0.y, 16, 64);
-        r1.x = (uint32_t)__shfl_xor((int)s1.x, 16, 64); r1.y = (uint32_t)__shfl_xor((int)s1.y, 16, 64);
-        if (live) {
-            if (even) {
-                st16(rowp + 4 * g, make_uint4(pk[0].x, pk[0].y, r0.x, r0.y));
-                st16(rowp + 32 + 4 * g, make_uint4(pk[2].x, pk[2].y, r1.x, r1.y));
-            } else {
-                st16(rowp + 16 + 4 * (g - 1), make_uint4(r0.x, r0.y, pk[1].x, pk[1].y));
-                st16(rowp + 48 + 4 * (g - 1), make_uint4(r1.x, r1.y, pk[3].x, pk[3].y));
+        if constexpr (ND == 4) {  // head_dim 64: spelled out (the loop form below compiles to a differently scheduled kernel)
+            const uint2 s0 = even ? pk[1] : pk[0], s1 = even ? pk[3] : pk[2];
+            uint2 r0, r1;
+            r0.x = (uint32_t)__shfl_xor((int)s0.x, 16, 64); r0.y = (uint32_t)__shfl_xor((int)s0.y, 16, 64);
+            r1.x = (uint32_t)__shfl_xor((int)s1.x, 16, 64); r1.y = (uint32_t)__shfl_xor((int)s1.y, 16, 64);
+            if (live) {
+                if (even) {
+                    st16(rowp + 4 * g, make_uint4(pk[0].x, pk[0].y, r0.x, r0.y));
+                    st16(rowp + 32 + 4 * g, make_uint4(pk[2].x, pk[2].y, r1.x, r1.y));
+                } else {
+                    st16(rowp + 16 + 4 * (g - 1), make_uint4(r0.x, r0.y, pk[1].x, pk[1].y));
+                    st16(rowp + 48 + 4 * (g - 1), make_uint4(r1.x, r1.y, pk[3].x, pk[3].y));
+                }
+            }
+        } else {
+            uint2 rr[ND / 2];
+#pragma unroll
+            for (int pp = 0; pp < ND / 2; ++pp) {
+                const uint2 sv = even ? pk[2 * pp + 1] : pk[2 * pp];
+                rr[pp].x = (uint32_t)__shfl_xor((int)sv.x, 16, 64); rr[pp].y = (uint32_t)__shfl_xor((int)sv.y, 16, 64);
+            }
+            if (live) {
+#pragma unroll
+                for (int pp = 0; pp < ND / 2; ++pp) {
+                    if (even) st16(rowp + 32 * pp + 4 * g, make_uint4(pk[2 * pp].x, pk[2 * pp].y, rr[pp].x, rr[pp].y));
+                    else st16(rowp + 32 * pp + 16 + 4 * (g - 1), make_uint4(rr[pp].x, rr[pp].y, pk[2 * pp + 1].x, pk[2 * pp + 1].y));
+                }
             }
         }
     }
@@ -392,10 +420,11 @@ __device__ __forceinline__ float row16_sum(float v) {
 //   dfreqs[a, h, j] = sum_{b, n} (d cos(theta[n,h,j]) / d freqs[a,h,j]) * gpair[b, n, h, j],   gpair = dQ~[2j] q[2j] + dQ~[2j+1] q[2j+1] (+ the k term)
 // This lane holds the 8 pair gradients gp[dt][pr] (j = 8 dt + 2 g + pr) of ONE row and the matching table entries
 // dx / dy = -t_x sin(theta), -t_y sin(theta); rows are summed over the 16 lanes of the DPP row, then added to the
-// workgroup's 64 LDS accumulators [a][j] (order of the LDS float adds is not fixed: last-bit differences from run to run).
-__device__ __forceinline__ void freq_accum(float* fl, const float (&gp)[4][2], const float (&dx)[4][2], const float (&dy)[4][2], int s, int g) {
+// workgroup's HD LDS accumulators [a][j] (order of the LDS float adds is not fixed: last-bit differences from run to run).
+template <int HD = 64>
+__device__ __forceinline__ void freq_accum(float* fl, const float (&gp)[HD / 16][2], const float (&dx)[HD / 16][2], const float (&dy)[HD / 16][2], int s, int g) {
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < HD / 16; ++dt)
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
             const float tx = row16_sum(gp[dt][pr] * dx[dt][pr]);
@@ -403,15 +432,15 @@ __device__ __forceinline__ void freq_accum(float* fl, const float (&gp)[4][2], c
             if (s == 0) {
                 const int j = 8 * dt + 2 * g + pr;
                 atomicAdd(fl + j, tx);
-                atomicAdd(fl + 32 + j, ty);
+                atomicAdd(fl + HD / 2 + j, ty);
             }
         }
 }
 // after the workgroup's last freq_accum: publish (dq kernel) or add to (dk/dv kernel, same grid, launched after it) the partial
-template <bool ADD> __device__ __forceinline__ void freq_flush(const float* fl, float* fpart) {
+template <bool ADD, int HD = 64> __device__ __forceinline__ void freq_flush(const float* fl, float* fpart) {
     __syncthreads();
-    if (threadIdx.x < 64) {
-        float* dst = fpart + (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (threadIdx.x < HD) {
+        float* dst = fpart + (int64_t)blockIdx.x * HD + threadIdx.x;
         *dst = ADD ? *dst + fl[threadIdx.x] : fl[threadIdx.x];
     }
 }
@@ -447,8 +476,8 @@ struct AttnP {
     float* lse;
     const void* d_o;
     void* dqkv;
-    float* fpart;        // [workgroups][2][32]: per-workgroup partial sums of the freqs gradient (dq kernel writes, dk/dv kernel adds)
-    const float* dsin;   // [2][N-E, heads, 32]: -t_x sin(theta), -t_y sin(theta) = d cos(theta) / d freqs[a]
+    float* fpart;        // [workgroups][2][HD/2]: per-workgroup partial sums of the freqs gradient (dq kernel writes, dk/dv kernel adds)
+    const float* dsin;   // [2][N-E, heads, HD/2]: -t_x sin(theta), -t_y sin(theta) = d cos(theta) / d freqs[a]
     float* delta;
     int B, N, E, heads;
     int qtiles;
@@ -459,18 +488,19 @@ struct AttnP {
 
 // dk / dv epilogue of one 16-key wave tile: every load in one batch (clamped rows, unconditional), 8-/16-byte stores, the k part
 // of the freqs gradient.  Shared by the resident and the tiled kernel.
-template <typename T>
-__device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)[4], const f32x4_t (&dv)[4], const T* __restrict__ kb, int64_t ld, int C,
+template <typename T, int HD = 64>
+__device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)[HD / 16], const f32x4_t (&dv)[HD / 16], const T* __restrict__ kb, int64_t ld, int C,
                                              int b, int head, int key, int s, int g, float* fl) {
     const int kc = min(key, p.N - 1);
     const T* kraw = kb + (int64_t)kc * ld;
-    const float* cpr = p.cos_tab + ((int64_t)max(kc - p.E, 0) * p.heads + head) * 32;
-    const float* sxp = p.dsin + ((int64_t)max(kc - p.E, 0) * p.heads + head) * 32;
-    const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * 32;
-    float kr[4][4], cr[4][2], gp[4][2], dx[4][2], dy[4][2];
+    const float* cpr = p.cos_tab + ((int64_t)max(kc - p.E, 0) * p.heads + head) * (HD / 2);
+    const float* sxp = p.dsin + ((int64_t)max(kc - p.E, 0) * p.heads + head) * (HD / 2);
+    const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * (HD / 2);
+    constexpr int ND = HD / 16;
+    float kr[ND][4], cr[ND][2], gp[ND][2], dx[ND][2], dy[ND][2];
     const bool rope = p.E < p.N;  // uniform: without image tokens there are no tables
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < ND; ++dt) {
         const int d0 = dt * 16 + 4 * g;
         if constexpr (sizeof(T) == 2) {
             const uint2 r = *reinterpret_cast<const uint2*>(kraw + d0);
@@ -495,39 +525,40 @@ __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)
     const bool row = key < p.N, img = row && key >= p.E;
     T* dkp = reinterpret_cast<T*>(p.dqkv) + ((int64_t)b * p.N + kc) * ld + C + head * HD;
     {
-        float ok[4][4];
+        float ok[ND][4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
+        for (int dt = 0; dt < ND; ++dt) {
             const float c0 = img ? cr[dt][0] : 1.0f, c1 = img ? cr[dt][1] : 1.0f;
             ok[dt][0] = dk[dt][0] * c0; ok[dt][1] = dk[dt][1] * c0; ok[dt][2] = dk[dt][2] * c1; ok[dt][3] = dk[dt][3] * c1;
             gp[dt][0] = img ? dk[dt][0] * kr[dt][0] + dk[dt][1] * kr[dt][1] : 0.f;
             gp[dt][1] = img ? dk[dt][2] * kr[dt][2] + dk[dt][3] * kr[dt][3] : 0.f;
         }
-        store_row64<T>(dkp, ok, g, row);
+        store_row<T, HD>(dkp, ok, g, row);
     }
     {
-        float ov[4][4];
+        float ov[ND][4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
+        for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
             for (int j = 0; j < 4; ++j) ov[dt][j] = dv[dt][j];
-        store_row64<T>(dkp + C, ov, g, row);
+        store_row<T, HD>(dkp + C, ov, g, row);
     }
-    if (rope) freq_accum(fl, gp, dx, dy, s, g);
+    if (rope) freq_accum<HD>(fl, gp, dx, dy, s, g);
 }
 // dq epilogue of one 16-query wave tile (the tiled kernel; the resident one fetches its operands ahead of the key loop)
-template <typename T>
-__device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[4], const T* __restrict__ qb, int64_t ld, int b, int head, int q, int s, int g,
+template <typename T, int HD = 64>
+__device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[HD / 16], const T* __restrict__ qb, int64_t ld, int b, int head, int q, int s, int g,
                                             float scale, float* fl) {
     const int qc = min(q, p.N - 1);
     const T* qraw = qb + (int64_t)qc * ld;
-    const float* cpr = p.cos_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
-    const float* sxp = p.dsin + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
-    const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * 32;
-    float qr[4][4], cr[4][2], gp[4][2], dx[4][2], dy[4][2];
+    const float* cpr = p.cos_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * (HD / 2);
+    const float* sxp = p.dsin + ((int64_t)max(qc - p.E, 0) * p.heads + head) * (HD / 2);
+    const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * (HD / 2);
+    constexpr int ND = HD / 16;
+    float qr[ND][4], cr[ND][2], gp[ND][2], dx[ND][2], dy[ND][2];
     const bool rope = p.E < p.N;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < ND; ++dt) {
         const int d0 = dt * 16 + 4 * g;
         if constexpr (sizeof(T) == 2) {
             const uint2 r = *reinterpret_cast<const uint2*>(qraw + d0);
@@ -551,16 +582,16 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
     }
     const bool row = q < p.N, img = row && q >= p.E;
     T* dqp = reinterpret_cast<T*>(p.dqkv) + ((int64_t)b * p.N + qc) * ld + head * HD;
-    float oq[4][4];
+    float oq[ND][4];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < ND; ++dt) {
         const float c0 = img ? cr[dt][0] * scale : scale, c1 = img ? cr[dt][1] * scale : scale;
         oq[dt][0] = dq[dt][0] * c0; oq[dt][1] = dq[dt][1] * c0; oq[dt][2] = dq[dt][2] * c1; oq[dt][3] = dq[dt][3] * c1;
         gp[dt][0] = img ? scale * (dq[dt][0] * qr[dt][0] + dq[dt][1] * qr[dt][1]) : 0.f;
         gp[dt][1] = img ? scale * (dq[dt][2] * qr[dt][2] + dq[dt][3] * qr[dt][3]) : 0.f;
     }
-    store_row64<T>(dqp, oq, g, row);
-    if (rope) freq_accum(fl, gp, dx, dy, s, g);
+    store_row<T, HD>(dqp, oq, g, row);
+    if (rope) freq_accum<HD>(fl, gp, dx, dy, s, g);
 }
 
 // ---------------------------------------------------------------------------------
@@ -570,11 +601,11 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
 // ---------------------------------------------------------------------------------
 // DROP: dropout on the attention probabilities (rope_2d_mhsa.py:497), applied after the normalisation: the running sum
 // takes the undropped exponentials, P . V the dropped ones
-template <typename T, int NW = 4, bool DROP = false>
+template <typename T, int NW = 4, bool DROP = false, int HD = 64>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* kimg = smem;                       // K~ row image
-    unsigned char* vimg = smem + AT<T>::ROW_IMG;      // V transposed-read image
+    unsigned char* vimg = smem + AT<T, HD>::ROW_IMG;      // V transposed-read image
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
     const int qt = blockIdx.x % p.qtiles;
@@ -585,22 +616,22 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
     const T* kb = qb + C;
     const T* vb = qb + 2 * C;
-    const float scale = 0.125f;  // 64^-0.5
+    const float scale = attn_scale<HD>();  // HD^-0.5
 
     const int q = qt * (16 * NW) + wave * 16 + s;
-    uint4 qf[AT<T>::NKK];
-    load_row_frag<T, true>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale);
+    uint4 qf[(AT<T, HD>::NKK)];
+    load_row_frag<T, true, HD>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale);
 
-    f32x4_t oacc[4];
+    f32x4_t oacc[HD / 16];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) oacc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < HD / 16; ++i) oacc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
     const unsigned char* mrow = nullptr;
     if constexpr (DROP) mrow = p.amask + (((int64_t)b * p.heads + head) * p.N + min(q, p.N - 1)) * p.Np + 4 * g;
 
     const int nkt = (p.N + BT - 1) / BT;
-    TileFetch<T, true, 64 * NW> fk;   // the next key tile travels in registers while this one is multiplied
-    TileFetch<T, false, 64 * NW> fv;
+    TileFetch<T, true, 64 * NW, HD> fk;   // the next key tile travels in registers while this one is multiplied
+    TileFetch<T, false, 64 * NW, HD> fv;
     fk.fetch(kb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head);
     fv.fetch(vb, ld, 0, p.N, p.E, nullptr, p.heads, head);
     for (int kt = 0; kt < nkt; ++kt) {
@@ -617,7 +648,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
         fv.fetch(vb, ld, nxt, p.N, p.E, nullptr, p.heads, head);
         __syncthreads();
         f32x4_t sacc[4];
-        rows_times_frag_n<T, 4>(sacc, kimg, s, g, qf);  // S^T[key = 16t + 4g + r][query = s]
+        rows_times_frag_n<T, 4, HD>(sacc, kimg, s, g, qf);  // S^T[key = 16t + 4g + r][query = s]
         float pv[4][4];
         float mx = -INFINITY;
         if (kt * BT + BT <= p.N) {  // uniform: only the last tile of a sequence can hold padding keys
@@ -655,20 +686,20 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
         l_run = l_run * alpha + psum;
         m_run = m_new;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
+        for (int dt = 0; dt < HD / 16; ++dt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) oacc[dt][r] *= alpha;
-        imgT_times_regs_n<T, 4>(oacc, vimg, s, g, pv);  // O^T[d = 16dt + 4g + r][query = s]
+        imgT_times_regs_n<T, 4, HD>(oacc, vimg, s, g, pv);  // O^T[d = 16dt + 4g + r][query = s]
     }
     const float l_tot = group_sum(l_run);
     const float inv = 1.0f / l_tot;
     {
-        float ov[4][4];
+        float ov[HD / 16][4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
+        for (int dt = 0; dt < HD / 16; ++dt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) ov[dt][r] = oacc[dt][r] * inv;
-        store_row64<T>(reinterpret_cast<T*>(p.o) + ((int64_t)b * p.N + min(q, p.N - 1)) * C + head * HD, ov, g, q < p.N);
+        store_row<T, HD>(reinterpret_cast<T*>(p.o) + ((int64_t)b * p.N + min(q, p.N - 1)) * C + head * HD, ov, g, q < p.N);
         if (q < p.N && g == 0 && p.lse) p.lse[((int64_t)b * p.heads + head) * p.N + q] = m_run + logf(l_tot);
     }
 }
@@ -676,12 +707,12 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
 // ---------------------------------------------------------------------------------
 // backward, query side: delta, dq (and the q part of the cos gradient)
 // ---------------------------------------------------------------------------------
-template <typename T, int NW = 4, bool DROP = false>
+template <typename T, int NW = 4, bool DROP = false, int HD = 64>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* kimg = smem;                                        // K~ rows
-    unsigned char* vimg = smem + AT<T>::ROW_IMG;                       // V rows
-    unsigned char* ktr = smem + 2 * AT<T>::ROW_IMG;                    // K~ transposed-read image
+    unsigned char* vimg = smem + AT<T, HD>::ROW_IMG;                       // V rows
+    unsigned char* ktr = smem + 2 * AT<T, HD>::ROW_IMG;                    // K~ transposed-read image
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
     const int qt = blockIdx.x % p.qtiles;
@@ -694,26 +725,26 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     const T* vb = qb + 2 * C;
     const T* dob = reinterpret_cast<const T*>(p.d_o) + (int64_t)b * p.N * C + head * HD;
     const T* ob = reinterpret_cast<const T*>(p.o) + (int64_t)b * p.N * C + head * HD;
-    const float scale = 0.125f;
+    const float scale = attn_scale<HD>();
 
-    __shared__ float fl[64];  // this workgroup's freqs-gradient partial [a][j]; zeroed here, published behind the loop's barriers
-    if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
+    __shared__ float fl[HD];  // this workgroup's freqs-gradient partial [a][j]; zeroed here, published behind the loop's barriers
+    if (threadIdx.x < HD) fl[threadIdx.x] = 0.f;
     const int q = qt * (16 * NW) + wave * 16 + s;
-    uint4 qf[AT<T>::NKK], dof[AT<T>::NKK];
-    load_row_frag<T, true>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale);
-    load_row_frag<T, false>(dof, dob, C, q, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
+    uint4 qf[(AT<T, HD>::NKK)], dof[(AT<T, HD>::NKK)];
+    load_row_frag<T, true, HD>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale);
+    load_row_frag<T, false, HD>(dof, dob, C, q, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
     // delta = sum_d dO * O  (each lane holds 1/4 of the row)
     float dl = 0.f;
     {
-        uint4 of[AT<T>::NKK];
-        load_row_frag<T, false>(of, ob, C, q, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
+        uint4 of[(AT<T, HD>::NKK)];
+        load_row_frag<T, false, HD>(of, ob, C, q, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
 #pragma unroll
-        for (int kk = 0; kk < AT<T>::NKK; ++kk) {
+        for (int kk = 0; kk < AT<T, HD>::NKK; ++kk) {
             Vec16<T> a, bb;
             a.raw = dof[kk];
             bb.raw = of[kk];
 #pragma unroll
-            for (int j = 0; j < AT<T>::EPV; ++j) dl += a.get(j) * bb.get(j);
+            for (int j = 0; j < AT<T, HD>::EPV; ++j) dl += a.get(j) * bb.get(j);
         }
     }
     const float delta = group_sum(dl);
@@ -721,15 +752,15 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     const float lse = RowExp<T>::prep(q < p.N ? lse_raw : 0.f);
     if (q < p.N && g == 0) p.delta[((int64_t)b * p.heads + head) * p.N + q] = delta;
 
-    f32x4_t dq[4];
+    f32x4_t dq[HD / 16];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) dq[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < HD / 16; ++i) dq[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const unsigned char* mrow = nullptr;
     if constexpr (DROP) mrow = p.amask + (((int64_t)b * p.heads + head) * p.N + min(q, p.N - 1)) * p.Np + 4 * g;
 
     const int nkt = (p.N + BT - 1) / BT;
-    TileFetch<T, true, 64 * NW> fk;   // the next key tile travels in registers while this one is multiplied
-    TileFetch<T, false, 64 * NW> fv;
+    TileFetch<T, true, 64 * NW, HD> fk;   // the next key tile travels in registers while this one is multiplied
+    TileFetch<T, false, 64 * NW, HD> fv;
     fk.fetch(kb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head);
     fv.fetch(vb, ld, 0, p.N, p.E, nullptr, p.heads, head);
     for (int kt = 0; kt < nkt; ++kt) {
@@ -751,9 +782,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             f32x4_t sacc[4], dpacc[4];
-            rows_times_frag_n<T, 2>(sacc, kimg + h * 32 * AT<T>::ROWB, s, g, qf);    // S^T[key][q]
+            rows_times_frag_n<T, 2, HD>(sacc, kimg + h * 32 * AT<T, HD>::ROWB, s, g, qf);    // S^T[key][q]
             PHASE_FENCE();
-            rows_times_frag_n<T, 2>(dpacc, vimg + h * 32 * AT<T>::ROWB, s, g, dof);  // dP^T[key][q] = V[key] . dO[q]
+            rows_times_frag_n<T, 2, HD>(dpacc, vimg + h * 32 * AT<T, HD>::ROWB, s, g, dof);  // dP^T[key][q] = V[key] . dO[q]
             PHASE_FENCE();
             float ds[4][4];
 #pragma unroll
@@ -769,12 +800,12 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
                     }
                 }
             PHASE_FENCE();
-            imgT_times_regs_n<T, 2>(dq, ktr + h * 32 * AT<T>::TRB, s, g, ds);  // dQ~^T[d][q] += K~^T . dS^T
+            imgT_times_regs_n<T, 2, HD>(dq, ktr + h * 32 * AT<T, HD>::TRB, s, g, ds);  // dQ~^T[d][q] += K~^T . dS^T
             PHASE_FENCE();
         }
     }
-    dq_epilogue<T>(p, dq, qb, ld, b, head, q, s, g, scale, fl);
-    if (p.E < p.N) freq_flush<false>(fl, p.fpart);
+    dq_epilogue<T, HD>(p, dq, qb, ld, b, head, q, s, g, scale, fl);
+    if (p.E < p.N) freq_flush<false, HD>(fl, p.fpart);
 }
 
 // ---------------------------------------------------------------------------------
@@ -783,14 +814,14 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
 // ---------------------------------------------------------------------------------
 // NW = 8: at least 4 waves per SIMD (two 8-wave workgroups per CU) -- left to itself the compiler takes 130 registers and
 // only one workgroup fits
-template <typename T, int NW = 4, bool DROP = false>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void attn_bwd_dkv_kernel(const AttnP p) {
+template <typename T, int NW = 4, bool DROP = false, int HD = 64>
+__global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd_dkv_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* qimg = smem;                                   // Q~ rows
-    unsigned char* doimg = smem + AT<T>::ROW_IMG;                 // dO rows
-    unsigned char* qtr = smem + 2 * AT<T>::ROW_IMG;               // Q~ transposed-read image
-    unsigned char* dotr = qtr + AT<T>::TR_IMG;                    // dO transposed-read image
-    float* lse_s = reinterpret_cast<float*>(dotr + AT<T>::TR_IMG);
+    unsigned char* doimg = smem + AT<T, HD>::ROW_IMG;                 // dO rows
+    unsigned char* qtr = smem + 2 * AT<T, HD>::ROW_IMG;               // Q~ transposed-read image
+    unsigned char* dotr = qtr + AT<T, HD>::TR_IMG;                    // dO transposed-read image
+    float* lse_s = reinterpret_cast<float*>(dotr + AT<T, HD>::TR_IMG);
     float* del_s = lse_s + BT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -803,25 +834,25 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void attn_bwd_dkv_kernel(
     const T* kb = qb + C;
     const T* vb = qb + 2 * C;
     const T* dob = reinterpret_cast<const T*>(p.d_o) + (int64_t)b * p.N * C + head * HD;
-    const float scale = 0.125f;
+    const float scale = attn_scale<HD>();
     const int64_t statbase = ((int64_t)b * p.heads + head) * p.N;
 
-    __shared__ float fl[64];
-    if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
+    __shared__ float fl[HD];
+    if (threadIdx.x < HD) fl[threadIdx.x] = 0.f;
     const int key = ktile * (16 * NW) + wave * 16 + s;
-    uint4 kf[AT<T>::NKK], vf[AT<T>::NKK];
-    load_row_frag<T, true>(kf, kb, ld, key, p.N, p.E, g, p.cos_tab, p.heads, head, 1.0f);
-    load_row_frag<T, false>(vf, vb, ld, key, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
+    uint4 kf[(AT<T, HD>::NKK)], vf[(AT<T, HD>::NKK)];
+    load_row_frag<T, true, HD>(kf, kb, ld, key, p.N, p.E, g, p.cos_tab, p.heads, head, 1.0f);
+    load_row_frag<T, false, HD>(vf, vb, ld, key, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
 
-    f32x4_t dk[4], dv[4];
+    f32x4_t dk[HD / 16], dv[HD / 16];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < HD / 16; ++i) {
         dk[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         dv[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
     const int nqt = (p.N + BT - 1) / BT;
-    TileFetch<T, true, 64 * NW> fq;   // the next query tile (and its statistics) travel in registers while this one is multiplied
-    TileFetch<T, false, 64 * NW> fdo;
+    TileFetch<T, true, 64 * NW, HD> fq;   // the next query tile (and its statistics) travel in registers while this one is multiplied
+    TileFetch<T, false, 64 * NW, HD> fdo;
     const int stl = threadIdx.x & (BT - 1);  // every thread fetches a statistic (unconditional load); the first 64 commit
     float l_n, d_n;
     fq.fetch(qb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head);
@@ -847,9 +878,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void attn_bwd_dkv_kernel(
 #pragma unroll
         for (int h = 0; h < 2; ++h) {  // half steps of 32 queries
             f32x4_t sacc[4], dpacc[4];
-            rows_times_frag_n<T, 2>(sacc, qimg + h * 32 * AT<T>::ROWB, s, g, kf);     // S[q = 16t + 4g + r][key = s]
+            rows_times_frag_n<T, 2, HD>(sacc, qimg + h * 32 * AT<T, HD>::ROWB, s, g, kf);     // S[q = 16t + 4g + r][key = s]
             PHASE_FENCE();
-            rows_times_frag_n<T, 2>(dpacc, doimg + h * 32 * AT<T>::ROWB, s, g, vf);   // dP[q][key]
+            rows_times_frag_n<T, 2, HD>(dpacc, doimg + h * 32 * AT<T, HD>::ROWB, s, g, vf);   // dP[q][key]
             PHASE_FENCE();
             float pr[4][4], ds[4][4];
 #pragma unroll
@@ -875,14 +906,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 1) void attn_bwd_dkv_kernel(
                 }
             }
             PHASE_FENCE();
-            imgT_times_regs_n<T, 2>(dv, dotr + h * 32 * AT<T>::TRB, s, g, pr);  // dV^T[d][key] += dO^T . P
+            imgT_times_regs_n<T, 2, HD>(dv, dotr + h * 32 * AT<T, HD>::TRB, s, g, pr);  // dV^T[d][key] += dO^T . P
             PHASE_FENCE();
-            imgT_times_regs_n<T, 2>(dk, qtr + h * 32 * AT<T>::TRB, s, g, ds);   // dK~^T[d][key] += Q~^T . dS
+            imgT_times_regs_n<T, 2, HD>(dk, qtr + h * 32 * AT<T, HD>::TRB, s, g, ds);   // dK~^T[d][key] += Q~^T . dS
             PHASE_FENCE();
         }
     }
-    dkv_epilogue<T>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
-    if (p.E < p.N) freq_flush<true>(fl, p.fpart);
+    dkv_epilogue<T, HD>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
+    if (p.E < p.N) freq_flush<true, HD>(fl, p.fpart);
 }
 
 // ---------------------------------------------------------------------------------
@@ -911,7 +942,7 @@ __device__ __forceinline__ void stage_all(unsigned char* rowimg, unsigned char* 
             if (i < total) {
                 const int r = i / NCH, c = i % NCH;
                 const uint4 v = ch[u].value(r, N, E, scale);
-                if constexpr (ROWIMG) st16(rowimg + r * AT<T>::ROWB + ((c ^ (r & 7)) << 4), v);
+                if constexpr (ROWIMG) st16(rowimg + r * AT<T>::ROWB + ((c ^ (r & AT<T>::SWZ)) << 4), v);
                 if constexpr (TRIMG) st16(trimg + r * AT<T>::TRB + c * 16, v);
             }
         }
@@ -921,6 +952,7 @@ __device__ __forceinline__ void stage_all(unsigned char* rowimg, unsigned char* 
 template <typename T, int NW = 8>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_res_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
     const int nkt = (p.N + BT - 1) / BT;
     const int npad = nkt * BT;
     unsigned char* kimg = smem;
@@ -998,7 +1030,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
             for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ov[dt][r] = oacc[dt][r] * inv;
-            store_row64<T>(reinterpret_cast<T*>(p.o) + ((int64_t)b * p.N + min(q, p.N - 1)) * C + head * HD, ov, g, q < p.N);
+            store_row<T>(reinterpret_cast<T*>(p.o) + ((int64_t)b * p.N + min(q, p.N - 1)) * C + head * HD, ov, g, q < p.N);
             if (q < p.N && g == 0 && p.lse) p.lse[((int64_t)b * p.heads + head) * p.N + q] = m_run + logf(l_tot);
         }
     }
@@ -1007,6 +1039,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
 template <typename T, int NW = 8>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dq_res_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
     const int nkt = (p.N + BT - 1) / BT;
     const int npad = (p.N + 31) & ~31;  // image rows: padding groups beyond it are never read (nt below)
     unsigned char* kimg = smem;         // padded-pitch images: row fragments AND transposed reads
@@ -1127,7 +1160,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 gp[dt][0] = img ? scale * (dq[dt][0] * qr[dt][0] + dq[dt][1] * qr[dt][1]) : 0.f;
                 gp[dt][1] = img ? scale * (dq[dt][2] * qr[dt][2] + dq[dt][3] * qr[dt][3]) : 0.f;
             }
-            store_row64<T>(dqp, oq, g, row);
+            store_row<T>(dqp, oq, g, row);
             if (p.E < p.N) freq_accum(fl, gp, dx, dy, s, g);
         }
     }
@@ -1146,6 +1179,7 @@ __device__ unsigned long long g_att_stamp[8];
 template <typename T, int NW = 8>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dkv_res_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
 #ifdef ATT_STAMP
     unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
@@ -1255,17 +1289,20 @@ extern "C" int lnx_dbg_attn_stamps(unsigned long long* out8) { return (int)hipMe
 // ---------------------------------------------------------------------------------
 // cos table and its backward to the learnable freqs
 // ---------------------------------------------------------------------------------
+// HD / 2 frequencies per head: entry i = (n * heads + h) * HD / 2 + j
+template <int HD = 64>
 __device__ __forceinline__ void rope_cos_entry(const float* __restrict__ freqs, int heads, int H, int W, float* __restrict__ out, float* __restrict__ dsin, int i) {
-    const int total = H * W * heads * 32;
+    constexpr int HH = HD / 2, SH = HD == 32 ? 4 : HD == 64 ? 5 : 6;
+    const int total = H * W * heads * HH;
     if (i >= total) return;
-    const int j = i & 31;
-    const int h = (i >> 5) % heads;
-    const int n = (i >> 5) / heads;
+    const int j = i & (HH - 1);
+    const int h = (i >> SH) % heads;
+    const int n = (i >> SH) / heads;
     const float tx = (float)(n % W), ty = (float)(n / W);
     // theta = t_x * f_x + t_y * f_y in fp32, two rounded products then a rounded sum (einsum + add,
     // rope_2d_mhsa.py:136-142) -- keep them un-fused so the angle matches the reference bit for bit
-    const float ax = __fmul_rn(tx, freqs[h * 32 + j]);
-    const float ay = __fmul_rn(ty, freqs[(heads + h) * 32 + j]);
+    const float ax = __fmul_rn(tx, freqs[h * HH + j]);
+    const float ay = __fmul_rn(ty, freqs[(heads + h) * HH + j]);
     const float th = __fadd_rn(ax, ay);
     out[i] = cosf(th);
     if (dsin) {  // d cos(theta) / d freqs[a, h, j] = -t_a sin(theta): what the attention backward weights its pair gradients with
@@ -1275,87 +1312,96 @@ __device__ __forceinline__ void rope_cos_entry(const float* __restrict__ freqs, 
     }
 }
 
+template <int HD = 64>
 __global__ __launch_bounds__(256) void rope_cos_kernel(const float* __restrict__ freqs, int heads, int H, int W, float* __restrict__ out,
                                                        float* __restrict__ dsin) {
-    rope_cos_entry(freqs, heads, H, W, out, dsin, blockIdx.x * 256 + threadIdx.x);
+    rope_cos_entry<HD>(freqs, heads, H, W, out, dsin, blockIdx.x * 256 + threadIdx.x);
 }
 
-// the tables of several blocks in one launch (every RoPE block of a plan has its own freqs): blockIdx.y picks the table
+// the tables of several blocks in one launch (every RoPE block of a plan has its own freqs): blockIdx.y picks the table.  One launch
+// covers tables of one head_dim (the host groups them)
 struct RopeTabBatch {
     lnx_rope_table t[LNX_ROPE_TABLES_MAX];
 };
+template <int HD = 64>
 __global__ __launch_bounds__(256) void rope_cos_batch_kernel(const RopeTabBatch b) {
     const lnx_rope_table& t = b.t[blockIdx.y];
-    rope_cos_entry(t.freqs, t.heads, t.H, t.W, t.cos_out, t.dsin_out, blockIdx.x * 256 + threadIdx.x);
+    rope_cos_entry<HD>(t.freqs, t.heads, t.H, t.W, t.cos_out, t.dsin_out, blockIdx.x * 256 + threadIdx.x);
 }
 
 // dfreqs[a, h, j] += sum over the workgroups of head h of their partial [a][j]   (fixed order: deterministic given the partials)
-// one 1024-thread workgroup per head: 16 slices of the partial list x 64 entries, four loads in flight per thread, LDS tree
+// one 1024-thread workgroup per head: SL = 1024 / HD slices of the partial list x HD entries (16 x 64 at head_dim 64), four loads in
+// flight per thread, LDS tree
+template <int HD = 64>
 __global__ __launch_bounds__(1024) void rope_freqs_reduce_kernel(const float* __restrict__ fpart, int B, int heads, int per_bh, float* __restrict__ dfreqs) {
-    __shared__ float red[16][64];
-    const int h = blockIdx.x, t = threadIdx.x & 63, sl = threadIdx.x >> 6;  // t = a * 32 + j
+    constexpr int SL = 1024 / HD, HH = HD / 2;
+    __shared__ float red[SL][HD];
+    const int h = blockIdx.x, t = threadIdx.x & (HD - 1), sl = threadIdx.x / HD;  // t = a * HD / 2 + j
     const int n = B * per_bh;  // partials of this head: (b, k) -> ((b * heads + h) * per_bh + k)
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     auto at = [&](int i) -> float {
         const int ii = min(i, n - 1);
         const int b = ii / per_bh, k = ii - b * per_bh;
-        const float v = fpart[(((int64_t)b * heads + h) * per_bh + k) * 64 + t];
+        const float v = fpart[(((int64_t)b * heads + h) * per_bh + k) * HD + t];
         return i < n ? v : 0.f;
     };
-    for (int i = sl; i < n; i += 64) {
+    for (int i = sl; i < n; i += 4 * SL) {
         a0 += at(i);
-        a1 += at(i + 16);
-        a2 += at(i + 32);
-        a3 += at(i + 48);
+        a1 += at(i + SL);
+        a2 += at(i + 2 * SL);
+        a3 += at(i + 3 * SL);
     }
     red[sl][t] = (a0 + a1) + (a2 + a3);
     __syncthreads();
     if (sl == 0) {
         float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) acc += red[k][t];
-        dfreqs[((t >> 5) * heads + h) * 32 + (t & 31)] += acc;
+        for (int k = 0; k < SL; ++k) acc += red[k][t];
+        dfreqs[((t / HH) * heads + h) * HH + (t & (HH - 1))] += acc;
     }
 }
 
 // the same fold for several attention backward calls in ONE launch (lnx_attn_bwd_args.defer_freqs + lnx_attn_bwd_flush): blockIdx.y picks
-// the call.  Every RoPE block owns its freqs, so a backward segment of a plan has one of these small folds per block.
+// the call.  Every RoPE block owns its freqs, so a backward segment of a plan has one of these small folds per block.  One launch folds
+// the calls of one head_dim (freq_flush groups them).
 struct FreqEntry {
     const float* fpart;
     float* dfreqs;
-    int B, heads, per_bh, pad_;
+    int B, heads, per_bh, hd;
 };
 struct FreqBatch {
     FreqEntry e[LNX_ATTN_DEFER_MAX];
 };
+template <int HD = 64>
 __global__ __launch_bounds__(1024) void rope_freqs_reduce_batch_kernel(const FreqBatch fb) {
-    __shared__ float red[16][64];
+    constexpr int SL = 1024 / HD, HH = HD / 2;
+    __shared__ float red[SL][HD];
     const FreqEntry& q = fb.e[blockIdx.y];
     if ((int)blockIdx.x >= q.heads) return;  // (uniform per workgroup: the grid's width is the largest head count of the batch)
     const float* __restrict__ fpart = q.fpart;
     const int heads = q.heads, per_bh = q.per_bh;
-    const int h = blockIdx.x, t = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int h = blockIdx.x, t = threadIdx.x & (HD - 1), sl = threadIdx.x / HD;
     const int n = q.B * per_bh;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     auto at = [&](int i) -> float {
         const int ii = min(i, n - 1);
         const int b = ii / per_bh, k = ii - b * per_bh;
-        const float v = fpart[(((int64_t)b * heads + h) * per_bh + k) * 64 + t];
+        const float v = fpart[(((int64_t)b * heads + h) * per_bh + k) * HD + t];
         return i < n ? v : 0.f;
     };
-    for (int i = sl; i < n; i += 64) {  // (the order of rope_freqs_reduce_kernel: same bits)
+    for (int i = sl; i < n; i += 4 * SL) {  // (the order of rope_freqs_reduce_kernel: same bits)
         a0 += at(i);
-        a1 += at(i + 16);
-        a2 += at(i + 32);
-        a3 += at(i + 48);
+        a1 += at(i + SL);
+        a2 += at(i + 2 * SL);
+        a3 += at(i + 3 * SL);
     }
     red[sl][t] = (a0 + a1) + (a2 + a3);
     __syncthreads();
     if (sl == 0) {
         float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) acc += red[k][t];
-        q.dfreqs[((t >> 5) * heads + h) * 32 + (t & 31)] += acc;
+        for (int k = 0; k < SL; ++k) acc += red[k][t];
+        q.dfreqs[((t / HH) * heads + h) * HH + (t & (HH - 1))] += acc;
     }
 }
 
@@ -1367,13 +1413,20 @@ thread_local hipStream_t g_freq_stream = nullptr;
 int freq_flush(hipStream_t st) {
     if (g_freq_n == 0) return 0;
     LNX_CHECK(st == g_freq_stream, "lnx_attn_bwd_flush: the postponed folds belong to another stream");
-    FreqBatch fb{};
-    int most = 0;
-    for (int i = 0; i < g_freq_n; ++i) {
-        fb.e[i] = g_freq_pending[i];
-        if (fb.e[i].heads > most) most = fb.e[i].heads;
+    for (const int hd : {64, 32, 128}) {  // one launch per head_dim present (a plan of head_dim 64 only: the one launch it always made)
+        FreqBatch fb{};
+        int most = 0, m = 0;
+        for (int i = 0; i < g_freq_n; ++i) {
+            if (g_freq_pending[i].hd != hd) continue;
+            fb.e[m] = g_freq_pending[i];
+            if (fb.e[m].heads > most) most = fb.e[m].heads;
+            ++m;
+        }
+        if (m == 0) continue;
+        if (hd == 64) hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel<64>, dim3(most, m), dim3(1024), 0, st, fb);
+        else if (hd == 32) hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel<32>, dim3(most, m), dim3(1024), 0, st, fb);
+        else hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel<128>, dim3(most, m), dim3(1024), 0, st, fb);
     }
-    hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel, dim3(most, g_freq_n), dim3(1024), 0, st, fb);
     g_freq_n = 0;
     LNX_LAUNCH_CHECK();
     return 0;
@@ -1383,42 +1436,18 @@ template <typename K> void set_lds(K kernel, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-int check_attn(int dtype, int B, int N, int E, int heads, const char* who) {
+bool hd_ok(int hd) { return hd == 32 || hd == 64 || hd == 128; }
+
+// Without image tokens (E == N) a caller may pass no tables, yet the kernels fetch one entry of row 0 unconditionally (clamped
+// rows, never used: only image tokens are scaled).  qkv (3 C elements per token) covers the C / 2 floats of such a fetch.
+const float* cos_or_stub(const float* tab, const void* qkv) { return tab ? tab : reinterpret_cast<const float*>(qkv); }
+
+int check_attn(int dtype, int B, int N, int E, int heads, int hd, const char* who) {
     LNX_CHECK(dtype == LNX_F32 || dtype == LNX_BF16, "%s: bad dtype %d", who, dtype);
     LNX_CHECK(B > 0 && N > 0 && heads > 0 && E >= 0 && E <= N, "%s: bad shape B=%d N=%d E=%d heads=%d", who, B, N, E, heads);
+    LNX_CHECK(hd_ok(hd), "%s: head_dim %d is not supported (32, 64 or 128)", who, hd);
     return 0;
 }
-
-}  // namespace
-
-extern "C" int lnx_rope_cos_table(const float* freqs, int heads, int H, int W, float* cos_out, float* dsin_out, void* stream) {
-    LNX_CHECK(freqs && cos_out && heads > 0 && H > 0 && W > 0, "lnx_rope_cos_table: bad arguments");
-    const int total = H * W * heads * 32;
-    hipLaunchKernelGGL(rope_cos_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, freqs, heads, H, W, cos_out, dsin_out);
-    LNX_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int lnx_rope_cos_tables(const lnx_rope_table* t, int n, void* stream) {
-    LNX_CHECK(t && n > 0, "lnx_rope_cos_tables: bad arguments");
-    for (int i = 0; i < n; ++i) LNX_CHECK(t[i].freqs && t[i].cos_out && t[i].heads > 0 && t[i].H > 0 && t[i].W > 0, "lnx_rope_cos_tables: bad table");
-    for (int i0 = 0; i0 < n; i0 += LNX_ROPE_TABLES_MAX) {
-        RopeTabBatch b{};
-        const int m = n - i0 < LNX_ROPE_TABLES_MAX ? n - i0 : LNX_ROPE_TABLES_MAX;
-        int most = 0;
-        for (int i = 0; i < m; ++i) {
-            b.t[i] = t[i0 + i];
-            const int total = t[i0 + i].H * t[i0 + i].W * t[i0 + i].heads * 32;
-            if (total > most) most = total;
-        }
-        hipLaunchKernelGGL(rope_cos_batch_kernel, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
-        LNX_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-// floats of lnx_attn_bwd's freqs-gradient workspace: one [2][32] partial per workgroup of its finest tiling
-extern "C" int64_t lnx_attn_bwd_ws_floats(int B, int N, int heads) { return (int64_t)B * heads * cdiv(N, BT) * 64; }
 
 // tiled bf16 kernels: 8 waves (128 rows) per workgroup for sequences beyond the resident kernels' reach, where every staged
 // tile is then shared by twice the rows; 4 waves for short ones (more workgroups) and with LNX_ATTN_NW=4 (A/B switch)
@@ -1427,16 +1456,155 @@ static bool tiled_nw8(int N) {
     return !force4 && N > 128;
 }
 
+// ---- head_dim 32 / 128: the tiled kernels, NW = 4 (fp32, dropout, bf16 at N <= 128) or NW = 8 (bf16 beyond).  The resident kernels
+// carry head_dim 64 only.  bf16 head_dim 32 keeps NW = 4 throughout: a 64-row tile is 256 16-byte chunks, one per thread of 4 waves.
+template <typename T, int HD> constexpr bool hd_nw8() { return sizeof(T) == 2 && HD > 32; }
+
+template <typename T, int HD>
+void attn_fwd_tiled(AttnP& p, bool drop, hipStream_t st) {
+    using A = AT<T, HD>;
+    const size_t lds = A::ROW_IMG + A::TR_IMG;  // fp32 head_dim 128: 65 KiB
+    static bool once = false;
+    if (!once) {
+        set_lds(attn_fwd_kernel<T, 4, false, HD>, lds);
+        set_lds(attn_fwd_kernel<T, 4, true, HD>, lds);
+        if constexpr (hd_nw8<T, HD>()) set_lds(attn_fwd_kernel<T, 8, false, HD>, lds);
+        once = true;
+    }
+    const int bh = p.B * p.heads;
+    if (drop) {
+        hipLaunchKernelGGL((attn_fwd_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
+        return;
+    }
+    if constexpr (hd_nw8<T, HD>()) {
+        if (tiled_nw8(p.N)) {
+            p.qtiles = cdiv(p.N, 128);
+            hipLaunchKernelGGL((attn_fwd_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds, st, p);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((attn_fwd_kernel<T, 4, false, HD>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
+}
+
+// returns the workgroups per (sample, head) of the launch (the fold's per_bh)
+template <typename T, int HD>
+int attn_bwd_tiled(AttnP& p, bool drop, hipStream_t st) {
+    using A = AT<T, HD>;
+    const size_t lds_q = 2 * A::ROW_IMG + A::TR_IMG;
+    const size_t lds_k = 2 * A::ROW_IMG + 2 * A::TR_IMG + 2 * BT * sizeof(float);  // fp32 head_dim 128: 130.5 KiB
+    static bool once = false;
+    if (!once) {
+        set_lds(attn_bwd_dq_kernel<T, 4, false, HD>, lds_q);
+        set_lds(attn_bwd_dq_kernel<T, 4, true, HD>, lds_q);
+        set_lds(attn_bwd_dkv_kernel<T, 4, false, HD>, lds_k);
+        set_lds(attn_bwd_dkv_kernel<T, 4, true, HD>, lds_k);
+        if constexpr (hd_nw8<T, HD>()) {
+            set_lds(attn_bwd_dq_kernel<T, 8, false, HD>, lds_q);
+            set_lds(attn_bwd_dkv_kernel<T, 8, false, HD>, lds_k);
+        }
+        once = true;
+    }
+    const int bh = p.B * p.heads;
+    if (drop) {
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
+        return p.qtiles;
+    }
+    if constexpr (hd_nw8<T, HD>()) {
+        if (tiled_nw8(p.N)) {
+            p.qtiles = cdiv(p.N, 128);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds_q, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds_k, st, p);
+            return p.qtiles;
+        }
+    }
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, HD>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, HD>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
+    return p.qtiles;
+}
+
+int rope_table_hd(const float* freqs, int heads, int hd, int H, int W, float* cos_out, float* dsin_out, hipStream_t st, const char* who) {
+    LNX_CHECK(freqs && cos_out && heads > 0 && H > 0 && W > 0, "%s: bad arguments", who);
+    LNX_CHECK(hd_ok(hd), "%s: head_dim %d is not supported (32, 64 or 128)", who, hd);
+    const int total = H * W * heads * (hd / 2);
+    if (hd == 64) hipLaunchKernelGGL(rope_cos_kernel<64>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out);
+    else if (hd == 32) hipLaunchKernelGGL(rope_cos_kernel<32>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out);
+    else hipLaunchKernelGGL(rope_cos_kernel<128>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out);
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int lnx_rope_cos_table(const float* freqs, int heads, int H, int W, float* cos_out, float* dsin_out, void* stream) {
+    return rope_table_hd(freqs, heads, 64, H, W, cos_out, dsin_out, (hipStream_t)stream, "lnx_rope_cos_table");
+}
+
+extern "C" int lnx_rope_cos_table_hd(const float* freqs, int heads, int head_dim, int H, int W, float* cos_out, float* dsin_out, void* stream) {
+    return rope_table_hd(freqs, heads, head_dim, H, W, cos_out, dsin_out, (hipStream_t)stream, "lnx_rope_cos_table_hd");
+}
+
+extern "C" int lnx_rope_cos_tables(const lnx_rope_table* t, int n, void* stream) {
+    LNX_CHECK(t && n > 0, "lnx_rope_cos_tables: bad arguments");
+    for (int i = 0; i < n; ++i) LNX_CHECK(t[i].freqs && t[i].cos_out && t[i].heads > 0 && t[i].H > 0 && t[i].W > 0, "lnx_rope_cos_tables: bad table");
+    for (int i = 0; i < n; ++i)
+        LNX_CHECK(t[i].head_dim == 0 || hd_ok(t[i].head_dim), "lnx_rope_cos_tables: head_dim %d is not supported (32, 64 or 128)", t[i].head_dim);
+    for (const int hd : {64, 32, 128}) {  // one launch (per LNX_ROPE_TABLES_MAX tables) per head_dim present, tables in their order
+        std::vector<lnx_rope_table> g;
+        for (int i = 0; i < n; ++i)
+            if ((t[i].head_dim ? t[i].head_dim : 64) == hd) g.push_back(t[i]);
+        const int ng = (int)g.size();
+        for (int i0 = 0; i0 < ng; i0 += LNX_ROPE_TABLES_MAX) {
+            RopeTabBatch b{};
+            const int m = ng - i0 < LNX_ROPE_TABLES_MAX ? ng - i0 : LNX_ROPE_TABLES_MAX;
+            int most = 0;
+            for (int i = 0; i < m; ++i) {
+                b.t[i] = g[i0 + i];
+                const int total = g[i0 + i].H * g[i0 + i].W * g[i0 + i].heads * (hd / 2);
+                if (total > most) most = total;
+            }
+            if (hd == 64) hipLaunchKernelGGL(rope_cos_batch_kernel<64>, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
+            else if (hd == 32) hipLaunchKernelGGL(rope_cos_batch_kernel<32>, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
+            else hipLaunchKernelGGL(rope_cos_batch_kernel<128>, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
+            LNX_LAUNCH_CHECK();
+        }
+    }
+    return 0;
+}
+
+// floats of lnx_attn_bwd's freqs-gradient workspace: one [2][head_dim / 2] partial per workgroup of its finest tiling
+extern "C" int64_t lnx_attn_bwd_ws_floats(int B, int N, int heads) { return (int64_t)B * heads * cdiv(N, BT) * 64; }
+extern "C" int64_t lnx_attn_bwd_ws_floats_hd(int B, int N, int heads, int head_dim) {
+    return hd_ok(head_dim) ? (int64_t)B * heads * cdiv(N, BT) * head_dim : 0;
+}
+
 extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
     LNX_CHECK(a && a->qkv && a->o, "lnx_attn_fwd: null operand");
-    if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, "lnx_attn_fwd")) return 1;
+    const int hd = a->head_dim ? a->head_dim : 64;
+    if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, hd, "lnx_attn_fwd")) return 1;
     LNX_CHECK(a->E == a->N || a->cos_tab, "lnx_attn_fwd: cos table missing");
     AttnP p{};
-    p.qkv = a->qkv; p.cos_tab = a->cos_tab; p.o = a->o; p.lse = a->lse;
+    p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = a->o; p.lse = a->lse;
     p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
     p.qtiles = cdiv(a->N, BT);
     const int grid = a->B * a->heads * p.qtiles;
     hipStream_t st = (hipStream_t)stream;
+    if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
+        if (a->drop_mask) {
+            LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_fwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
+            p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
+        }
+        const bool drop = a->drop_mask != nullptr;
+        if (a->dtype == LNX_BF16) {
+            if (hd == 32) attn_fwd_tiled<bf16_t, 32>(p, drop, st);
+            else attn_fwd_tiled<bf16_t, 128>(p, drop, st);
+        } else {
+            if (hd == 32) attn_fwd_tiled<float, 32>(p, drop, st);
+            else attn_fwd_tiled<float, 128>(p, drop, st);
+        }
+        LNX_LAUNCH_CHECK();
+        return 0;
+    }
     if (a->drop_mask) {  // attention-probability dropout: the 64-row tiled kernels with the DROP code
         LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_fwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
         p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
@@ -1477,11 +1645,12 @@ extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
 
 extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
     LNX_CHECK(a && a->qkv && a->o && a->lse && a->d_o && a->dqkv && a->delta, "lnx_attn_bwd: null operand");
-    if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, "lnx_attn_bwd")) return 1;
+    const int hd = a->head_dim ? a->head_dim : 64;
+    if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, hd, "lnx_attn_bwd")) return 1;
     LNX_CHECK(a->E == a->N || (a->cos_tab && a->dsin_tab && a->freq_ws && a->dfreqs), "lnx_attn_bwd: cos / d-cos tables, freqs-gradient workspace or dfreqs missing");
     AttnP p{};
-    p.qkv = a->qkv; p.cos_tab = a->cos_tab; p.o = const_cast<void*>(a->o); p.lse = const_cast<float*>(a->lse);
-    p.d_o = a->d_o; p.dqkv = a->dqkv; p.fpart = a->freq_ws; p.dsin = a->dsin_tab; p.delta = a->delta;
+    p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = const_cast<void*>(a->o); p.lse = const_cast<float*>(a->lse);
+    p.d_o = a->d_o; p.dqkv = a->dqkv; p.fpart = a->freq_ws; p.dsin = cos_or_stub(a->dsin_tab, a->qkv); p.delta = a->delta;
     p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
     p.qtiles = cdiv(a->N, BT);
     const int grid = a->B * a->heads * p.qtiles;
@@ -1494,12 +1663,27 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
     auto reduce_freqs = [&](int per_bh) {
         if (a->E >= a->N) return;
         if (a->defer_freqs) {
-            g_freq_pending[g_freq_n++] = FreqEntry{p.fpart, a->dfreqs, a->B, a->heads, per_bh, 0};
+            g_freq_pending[g_freq_n++] = FreqEntry{p.fpart, a->dfreqs, a->B, a->heads, per_bh, hd};
             g_freq_stream = st;
             return;
         }
-        hipLaunchKernelGGL(rope_freqs_reduce_kernel, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
+        if (hd == 64) hipLaunchKernelGGL(rope_freqs_reduce_kernel<64>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
+        else if (hd == 32) hipLaunchKernelGGL(rope_freqs_reduce_kernel<32>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
+        else hipLaunchKernelGGL(rope_freqs_reduce_kernel<128>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
     };
+    if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
+        if (a->drop_mask) {
+            LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_bwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
+            p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
+        }
+        const bool drop = a->drop_mask != nullptr;
+        int per_bh;
+        if (a->dtype == LNX_BF16) per_bh = hd == 32 ? attn_bwd_tiled<bf16_t, 32>(p, drop, st) : attn_bwd_tiled<bf16_t, 128>(p, drop, st);
+        else per_bh = hd == 32 ? attn_bwd_tiled<float, 32>(p, drop, st) : attn_bwd_tiled<float, 128>(p, drop, st);
+        reduce_freqs(per_bh);
+        LNX_LAUNCH_CHECK();
+        return 0;
+    }
     if (a->drop_mask) {
         LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_bwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
         p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;

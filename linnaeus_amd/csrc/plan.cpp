@@ -250,7 +250,7 @@ void build_inventory(lnx_plan* p) {
             add_param(p, pre + "norm1.bias", C);
             add_param(p, pre + "norm2.weight", C);
             add_param(p, pre + "norm2.bias", C);
-            add_param(p, pre + "attn.freqs", 2 * c.rope_heads[s] * 32);
+            add_param(p, pre + "attn.freqs", C);  // [2, heads, head_dim / 2]: 2 * heads * head_dim / 2 = C
             add_param(p, pre + "attn.qkv.weight", 3 * C * C);
             add_param(p, pre + "attn.qkv.bias", 3 * C);
             add_param(p, pre + "attn.proj.weight", C * C);
@@ -337,7 +337,9 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         if (c.dims[i] <= 0 || c.dims[i] % 32 != 0 || c.dims[i] > 2048) FAIL("lnx_plan_create: dims[%d]=%d must be a multiple of 32 in (0, 2048]", i, c.dims[i]);
     for (int s = 0; s < 2; ++s) {
         if (c.conv_depths[s] < 0 || c.rope_depths[s] <= 0) FAIL("lnx_plan_create: bad depths");
-        if (c.rope_heads[s] <= 0 || c.dims[2 + s] != c.rope_heads[s] * 64) FAIL("lnx_plan_create: head_dim must be 64 (dim %d, heads %d)", c.dims[2 + s], c.rope_heads[s]);
+        const int hd = c.rope_heads[s] > 0 && c.dims[2 + s] % c.rope_heads[s] == 0 ? c.dims[2 + s] / c.rope_heads[s] : 0;
+        if (hd != 32 && hd != 64 && hd != 128)
+            FAIL("lnx_plan_create: head_dim = dim / heads must be 32, 64 or 128 (dim %d, heads %d)", c.dims[2 + s], c.rope_heads[s]);
         if (c.mlp_hidden[s] <= 0 || c.mlp_hidden[s] % 16 != 0) FAIL("lnx_plan_create: mlp_hidden must be a multiple of 16");
     }
     if (c.n_meta < 0 || c.n_meta > LNX_MAX_META || c.n_tasks < 0 || c.n_tasks > LNX_MAX_TASKS) FAIL("lnx_plan_create: too many meta components / tasks");
@@ -626,8 +628,8 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
             k.mean1 = share ? f.mean1 : cv.take(M * 4);
             k.rstd1 = share ? f.rstd1 : cv.take(M * 4);
             k.qkvbuf = share ? f.qkvbuf : cv.take(M * 3 * C * esz);
-            k.cos = cv.take((int64_t)p->HW[2 + s] * heads * 32 * 4);
-            k.dsin = inf ? 0 : cv.take((int64_t)2 * p->HW[2 + s] * heads * 32 * 4);  // d cos / d freqs, for the attention backward
+            k.cos = cv.take((int64_t)p->HW[2 + s] * C / 2 * 4);  // [HW, heads, head_dim / 2]
+            k.dsin = inf ? 0 : cv.take((int64_t)2 * p->HW[2 + s] * C / 2 * 4);  // d cos / d freqs, for the attention backward
             k.o = share ? f.o : cv.take(M * C * esz);
             k.lse = share ? f.lse : cv.take((int64_t)B * heads * N * 4);
             k.xmid = share ? f.xmid : cv.take(M * C * 4);
@@ -739,7 +741,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         int64_t gmax = 0, dmax = 0;
         for (int s = 0; s < 2; ++s) {
             const int N = s == 0 ? p->N2 : p->N3;
-            const int64_t gsz = lnx_attn_bwd_ws_floats(B, N, c.rope_heads[s]) * 4;  // per-workgroup partials of the freqs gradient
+            const int64_t gsz = lnx_attn_bwd_ws_floats_hd(B, N, c.rope_heads[s], D[2 + s] / c.rope_heads[s]) * 4;  // per-workgroup partials of the freqs gradient
             const int64_t dsz = (int64_t)B * c.rope_heads[s] * N * 4;
             if (gsz > gmax) gmax = gsz;
             if (dsz > dmax) dmax = dsz;
@@ -1340,10 +1342,11 @@ int meta_chain_bwd(const Ctx& c, int s, const float* g) {
     return p->c.n_meta ? lnx_meta_heads_bwd(a, p->c.n_meta, c.st) : 0;
 }
 
-// forward FLOPs of one RoPE2DMHSABlock: qkv + proj + fc1 + fc2 products and the two attention products (SURVEY 8d's count)
-double rope_block_flops(int B, int N, int C, int hid, int heads) {
+// forward FLOPs of one RoPE2DMHSABlock: qkv + proj + fc1 + fc2 products and the two attention products (SURVEY 8d's count;
+// heads * head_dim = C)
+double rope_block_flops(int B, int N, int C, int hid) {
     const double M = (double)B * N;
-    return 2.0 * M * C * (3.0 * C + C + 2.0 * hid) + 4.0 * B * heads * (double)N * N * 64.0;
+    return 2.0 * M * C * (3.0 * C + C + 2.0 * hid) + 4.0 * B * (double)N * N * C;
 }
 
 int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
@@ -1353,7 +1356,7 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     const int N = s == 0 ? p->N2 : p->N3, M = B * N, E = p->E;
     const float* xin = c.at<float>(k.xin);
     p->resident[2 + s] = i;
-    Timed span(c, 8, rope_block_flops(B, N, C, hid, heads));
+    Timed span(c, 8, rope_block_flops(B, N, C, hid));
     const bool f8 = fp8_rows(p, M, C);
     void* a8 = f8 ? c.at<void>(p->o_a8) : nullptr;
     void* a8s = f8 ? c.at<void>(p->o_a8s) : nullptr;
@@ -1363,13 +1366,13 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     RUN(linear_fwd(c, g, k.qkv, p->o_a8, p->o_a8s));
     lnx_attn_args a;
     memset(&a, 0, sizeof a);
-    a.dtype = c.dt; a.B = B; a.N = N; a.E = E; a.heads = heads;
+    a.dtype = c.dt; a.B = B; a.N = N; a.E = E; a.heads = heads; a.head_dim = C / heads;
     a.qkv = c.at<void>(k.qkvbuf); a.cos_tab = c.at<float>(k.cos); a.o = c.at<void>(k.o); a.lse = c.at<float>(k.lse);
     if (p->amask) {
         a.drop_mask = p->amask + k.dm_attn; a.drop_inv_keep = p->a_inv_keep;
     }
     {
-        Timed t(c, 2, 4.0 * B * heads * (double)N * N * 64);
+        Timed t(c, 2, 4.0 * B * (double)N * N * C);
         RUN(lnx_attn_fwd(&a, c.st));
     }
     if (p->dmask) {
@@ -1467,7 +1470,7 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
             for (auto& k : p->rope[s]) {
                 lnx_rope_table t;
                 memset(&t, 0, sizeof t);
-                t.freqs = p->P[k.freqs]; t.heads = cf.rope_heads[s]; t.H = p->H[2 + s]; t.W = p->W[2 + s];
+                t.freqs = p->P[k.freqs]; t.heads = cf.rope_heads[s]; t.H = p->H[2 + s]; t.W = p->W[2 + s]; t.head_dim = cf.dims[2 + s] / cf.rope_heads[s];
                 t.cos_out = c.at<float>(k.cos); t.dsin_out = cf.inference ? nullptr : c.at<float>(k.dsin);
                 tabs.push_back(t);
             }
@@ -1624,7 +1627,7 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     void* sA = c.at<void>(p->o_sA);
     void* sC = c.at<void>(p->o_sC);
     void* sD = c.at<void>(p->o_sD);
-    Timed span(c, 8, 2.0 * rope_block_flops(B, N, C, hid, heads));
+    Timed span(c, 8, 2.0 * rope_block_flops(B, N, C, hid));
     const Ctx cw = wg_ctx(c);
     auto wfork = [&](int j) { return wg_fork(c, j); };
     auto wdone = [&](int j) { return wg_done(c, j); };
@@ -1667,7 +1670,7 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     RUN(wjoin(1));  // the attention backward overwrites sA
     lnx_attn_bwd_args ab;
     memset(&ab, 0, sizeof ab);
-    ab.dtype = c.dt; ab.B = B; ab.N = N; ab.E = E; ab.heads = heads;
+    ab.dtype = c.dt; ab.B = B; ab.N = N; ab.E = E; ab.heads = heads; ab.head_dim = C / heads;
     ab.qkv = c.at<void>(k.qkvbuf); ab.cos_tab = c.at<float>(k.cos); ab.o = c.at<void>(k.o); ab.lse = c.at<float>(k.lse);
     ab.d_o = sD; ab.dqkv = sA; ab.freq_ws = c.at<float>(p->o_gcos); ab.delta = c.at<float>(p->o_delta);
     if (p->freq_defer && E < N) {  // the fold into dfreqs: one launch per backward segment (ln_flush)
@@ -1684,7 +1687,7 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
         ab.drop_mask = p->amask + k.dm_attn; ab.drop_inv_keep = p->a_inv_keep;
     }
     {
-        Timed t(c, 3, 14.0 * B * heads * (double)N * N * 64);
+        Timed t(c, 3, 14.0 * B * (double)N * N * C);
         RUN(lnx_attn_bwd(&ab, c.st));
     }
     RUN(wfork(3));

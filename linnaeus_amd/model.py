@@ -202,8 +202,8 @@ class mFormerV1(nn.Module):
         if rdims[1] != dims[3]:
             raise ValueError(f"ConvNeXt dim[3] ({dims[3]}) must match RoPE dim[1] ({rdims[1]})")
         for d_, h_ in zip(rdims, rheads):
-            if d_ % h_ != 0 or d_ // h_ != 64:
-                raise NotImplementedError(f"HIP attention kernels are built for head_dim 64 (got dim {d_}, heads {h_})")
+            if h_ <= 0 or d_ % h_ != 0 or d_ // h_ not in (32, 64, 128):
+                raise NotImplementedError(f"HIP attention kernels are built for head_dim 32, 64 or 128 (got dim {d_}, heads {h_})")
         self.use_flash_attn = M.get("USE_FLASH_ATTN", False)  # accepted and ignored: attention is always the fused HIP kernel
 
         # metadata components in IDX order (mFormerV1.py:94-130)

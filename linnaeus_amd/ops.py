@@ -239,46 +239,58 @@ def dwconv7_wgrad(x, dy, dw, db):
 
 
 def rope_cos_table(freqs, H, W, out=None, dsin=None):
-    """cos(theta) table [H*W, heads, 32]; `dsin` (optional, [2, H*W, heads, 32]) receives -t_x sin(theta), -t_y sin(theta)."""
-    heads = freqs.shape[1]
+    """cos(theta) table [H*W, heads, head_dim/2] of freqs [2, heads, head_dim/2]; `dsin` (optional, [2, H*W, heads, head_dim/2])
+    receives -t_x sin(theta), -t_y sin(theta)."""
+    heads, half = freqs.shape[1], freqs.shape[2]
     if out is None:
-        out = torch.empty(H * W, heads, 32, device=freqs.device, dtype=torch.float32)
-    L.check(L.lib().lnx_rope_cos_table(_p(freqs), heads, H, W, _p(out), _p(dsin) if dsin is not None else None, _stream()), "lnx_rope_cos_table")
+        out = torch.empty(H * W, heads, half, device=freqs.device, dtype=torch.float32)
+    L.check(L.lib().lnx_rope_cos_table_hd(_p(freqs), heads, 2 * half, H, W, _p(out), _p(dsin) if dsin is not None else None, _stream()),
+            "lnx_rope_cos_table_hd")
     return out
 
 
 def rope_cos_tables(entries):
-    """The tables of several blocks in one launch: entries = [(freqs [2,heads,32], H, W, cos_out, dsin_out or None), ...]."""
+    """The tables of several blocks in one launch per head_dim: entries = [(freqs [2,heads,head_dim/2], H, W, cos_out, dsin_out or None), ...]."""
     arr = (L.RopeTable * len(entries))()
     for t, (freqs, H, W, out, dsin) in zip(arr, entries):
         t.freqs, t.cos_out, t.dsin_out = _p(freqs), _p(out), _p(dsin) if dsin is not None else None
-        t.heads, t.H, t.W = freqs.shape[1], H, W
+        t.heads, t.H, t.W, t.head_dim = freqs.shape[1], H, W, 2 * freqs.shape[2]
     L.check(L.lib().lnx_rope_cos_tables(arr, len(entries), _stream()), "lnx_rope_cos_tables")
 
 
-def attn_bwd_ws_floats(B, N, heads):
-    fn = L.lib().lnx_attn_bwd_ws_floats
+def attn_bwd_ws_floats(B, N, heads, head_dim=64):
+    fn = L.lib().lnx_attn_bwd_ws_floats_hd
     fn.restype = C.c_int64
-    return int(fn(B, N, heads))
+    return int(fn(B, N, heads, head_dim))
 
 
-def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=0.0):
+def _head_dim(qkv, heads, head_dim):
+    """head_dim from qkv [..., 3*heads*head_dim] unless given (64 for a flat qkv, as before head_dim was an argument)"""
+    if head_dim is not None:
+        return int(head_dim)
+    return qkv.shape[-1] // (3 * heads) if qkv.dim() >= 2 and qkv.shape[-1] % (3 * heads) == 0 else 64
+
+
+def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=0.0, head_dim=None):
     a = L.AttnArgs()
     a.dtype, a.B, a.N, a.E, a.heads = code_of(qkv), B, N, E, heads
+    a.head_dim = _head_dim(qkv, heads, head_dim)
     a.qkv, a.cos_tab, a.o, a.lse = _p(qkv), _p(cos_tab), _p(o), _p(lse)
     if drop_mask is not None:
         a.drop_mask, a.drop_inv_keep = _p(drop_mask), 1.0 / (1.0 - drop_rate)
     L.check(L.lib().lnx_attn_fwd(C.byref(a), _stream()), "lnx_attn_fwd")
 
 
-def attn_bwd(qkv, cos_tab, o, lse, d_o, dqkv, delta, B, N, E, heads, *, dsin=None, dfreqs=None, drop_mask=None, drop_rate=0.0, defer_freqs=False):
-    """dq/dk/dv into dqkv; with image tokens (E < N) also dfreqs [2, heads, 32] += the gradient of the RoPE frequencies
-    (`dsin` = the second table of rope_cos_table).  defer_freqs: the fold into dfreqs waits for attn_bwd_flush(); the returned
-    workspace (and dfreqs) must be kept alive until then."""
+def attn_bwd(qkv, cos_tab, o, lse, d_o, dqkv, delta, B, N, E, heads, *, dsin=None, dfreqs=None, drop_mask=None, drop_rate=0.0, defer_freqs=False,
+             head_dim=None):
+    """dq/dk/dv into dqkv; with image tokens (E < N) also dfreqs [2, heads, head_dim/2] += the gradient of the RoPE frequencies
+    (`dsin` = the second table of rope_cos_table).  head_dim: from qkv's width unless given.  defer_freqs: the fold into dfreqs
+    waits for attn_bwd_flush(); the returned workspace (and dfreqs) must be kept alive until then."""
     a = L.AttnBwdArgs()
     a.dtype, a.B, a.N, a.E, a.heads = code_of(qkv), B, N, E, heads
+    a.head_dim = _head_dim(qkv, heads, head_dim)
     a.qkv, a.cos_tab, a.o, a.lse = _p(qkv), _p(cos_tab), _p(o), _p(lse)
-    ws = torch.empty(max(attn_bwd_ws_floats(B, N, heads), 1), device=qkv.device, dtype=torch.float32)
+    ws = torch.empty(max(attn_bwd_ws_floats(B, N, heads, a.head_dim), 1), device=qkv.device, dtype=torch.float32)
     a.d_o, a.dqkv, a.freq_ws, a.delta = _p(d_o), _p(dqkv), _p(ws), _p(delta)
     if dsin is not None:
         a.dsin_tab, a.dfreqs = _p(dsin), _p(dfreqs)
