@@ -18,6 +18,7 @@
 //           attn_bwd_dkv  (per 64 keys:    dk, dv, cos-gradient part of k)
 #include <stdlib.h>
 
+#include <atomic>
 #include <vector>
 
 #include "common.hpp"
@@ -1460,8 +1461,18 @@ static bool tiled_nw8(int N) {
 // carry head_dim 64 only.  bf16 head_dim 32 keeps NW = 4 throughout: a 64-row tile is 256 16-byte chunks, one per thread of 4 waves.
 template <typename T, int HD> constexpr bool hd_nw8() { return sizeof(T) == 2 && HD > 32; }
 
+// The kernel family of a forward / backward launch (include/lnx.h: lnx_attn_dispatch answers with this, lnx_attn_fwd / lnx_attn_bwd
+// launch by it).  Arguments already passed check_attn.
+int attn_family(int dtype, int N, int hd, bool drop) {
+    if (dtype != LNX_BF16 || drop || hd == 32) return LNX_ATTN_KERNEL_TILED4;
+    if (hd == 64 && N <= 256 && getenv("LNX_ATTN_TILED") == nullptr) return N <= 64 ? LNX_ATTN_KERNEL_RES4 : LNX_ATTN_KERNEL_RES8;
+    return tiled_nw8(N) ? LNX_ATTN_KERNEL_TILED8 : LNX_ATTN_KERNEL_TILED4;
+}
+
+std::atomic<int> g_last_attn{LNX_ATTN_KERNEL_NONE};
+
 template <typename T, int HD>
-void attn_fwd_tiled(AttnP& p, bool drop, hipStream_t st) {
+void attn_fwd_tiled(AttnP& p, int family, hipStream_t st) {
     using A = AT<T, HD>;
     const size_t lds = A::ROW_IMG + A::TR_IMG;  // fp32 head_dim 128: 65 KiB
     static bool once = false;
@@ -1472,12 +1483,12 @@ void attn_fwd_tiled(AttnP& p, bool drop, hipStream_t st) {
         once = true;
     }
     const int bh = p.B * p.heads;
-    if (drop) {
+    if (p.amask) {
         hipLaunchKernelGGL((attn_fwd_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
         return;
     }
     if constexpr (hd_nw8<T, HD>()) {
-        if (tiled_nw8(p.N)) {
+        if (family == LNX_ATTN_KERNEL_TILED8) {
             p.qtiles = cdiv(p.N, 128);
             hipLaunchKernelGGL((attn_fwd_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds, st, p);
             return;
@@ -1488,7 +1499,7 @@ void attn_fwd_tiled(AttnP& p, bool drop, hipStream_t st) {
 
 // returns the workgroups per (sample, head) of the launch (the fold's per_bh)
 template <typename T, int HD>
-int attn_bwd_tiled(AttnP& p, bool drop, hipStream_t st) {
+int attn_bwd_tiled(AttnP& p, int family, hipStream_t st) {
     using A = AT<T, HD>;
     const size_t lds_q = 2 * A::ROW_IMG + A::TR_IMG;
     const size_t lds_k = 2 * A::ROW_IMG + 2 * A::TR_IMG + 2 * BT * sizeof(float);  // fp32 head_dim 128: 130.5 KiB
@@ -1505,13 +1516,13 @@ int attn_bwd_tiled(AttnP& p, bool drop, hipStream_t st) {
         once = true;
     }
     const int bh = p.B * p.heads;
-    if (drop) {
+    if (p.amask) {
         hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
         hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
         return p.qtiles;
     }
     if constexpr (hd_nw8<T, HD>()) {
-        if (tiled_nw8(p.N)) {
+        if (family == LNX_ATTN_KERNEL_TILED8) {
             p.qtiles = cdiv(p.N, 128);
             hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds_q, st, p);
             hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds_k, st, p);
@@ -1589,25 +1600,25 @@ extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
     p.qtiles = cdiv(a->N, BT);
     const int grid = a->B * a->heads * p.qtiles;
     hipStream_t st = (hipStream_t)stream;
+    if (a->drop_mask) {  // attention-probability dropout: the 64-row tiled kernels with the DROP code
+        LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_fwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
+        p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
+    }
+    const int family = attn_family(a->dtype, a->N, hd, a->drop_mask != nullptr);
+    g_last_attn.store(family, std::memory_order_relaxed);
+    const bool resident = family == LNX_ATTN_KERNEL_RES4 || family == LNX_ATTN_KERNEL_RES8;
     if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
-        if (a->drop_mask) {
-            LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_fwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
-            p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
-        }
-        const bool drop = a->drop_mask != nullptr;
         if (a->dtype == LNX_BF16) {
-            if (hd == 32) attn_fwd_tiled<bf16_t, 32>(p, drop, st);
-            else attn_fwd_tiled<bf16_t, 128>(p, drop, st);
+            if (hd == 32) attn_fwd_tiled<bf16_t, 32>(p, family, st);
+            else attn_fwd_tiled<bf16_t, 128>(p, family, st);
         } else {
-            if (hd == 32) attn_fwd_tiled<float, 32>(p, drop, st);
-            else attn_fwd_tiled<float, 128>(p, drop, st);
+            if (hd == 32) attn_fwd_tiled<float, 32>(p, family, st);
+            else attn_fwd_tiled<float, 128>(p, family, st);
         }
         LNX_LAUNCH_CHECK();
         return 0;
     }
-    if (a->drop_mask) {  // attention-probability dropout: the 64-row tiled kernels with the DROP code
-        LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_fwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
-        p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
+    if (a->drop_mask) {
         if (a->dtype == LNX_BF16) {
             hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 4, true>), dim3(grid), dim3(256), AT<bf16_t>::ROW_IMG + AT<bf16_t>::TR_IMG, st, p);
         } else {
@@ -1616,7 +1627,7 @@ extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
         LNX_LAUNCH_CHECK();
         return 0;
     }
-    if (a->dtype == LNX_BF16 && a->N <= 256 && getenv("LNX_ATTN_TILED") == nullptr) {
+    if (resident) {
         typedef bf16_t T;
         const int npad = p.qtiles * BT;
         const size_t lds = (size_t)npad * (AT<T>::ROWB + AT<T>::TRB);
@@ -1625,11 +1636,11 @@ extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
             set_lds(attn_fwd_res_kernel<T>, 256 * (AT<T>::ROWB + AT<T>::TRB));
             once = true;
         }
-        if (a->N <= 64) hipLaunchKernelGGL((attn_fwd_res_kernel<T, 4>), dim3(a->B * a->heads), dim3(256), lds, st, p);
+        if (family == LNX_ATTN_KERNEL_RES4) hipLaunchKernelGGL((attn_fwd_res_kernel<T, 4>), dim3(a->B * a->heads), dim3(256), lds, st, p);
         else hipLaunchKernelGGL((attn_fwd_res_kernel<T>), dim3(a->B * a->heads), dim3(512), lds, st, p);
     } else if (a->dtype == LNX_BF16) {
         const size_t lds = AT<bf16_t>::ROW_IMG + AT<bf16_t>::TR_IMG;
-        if (tiled_nw8(a->N)) {  // 128 queries per workgroup
+        if (family == LNX_ATTN_KERNEL_TILED8) {  // 128 queries per workgroup
             p.qtiles = cdiv(a->N, 128);
             hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 8>), dim3(a->B * a->heads * p.qtiles), dim3(512), lds, st, p);
         } else {
@@ -1671,22 +1682,22 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
         else if (hd == 32) hipLaunchKernelGGL(rope_freqs_reduce_kernel<32>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
         else hipLaunchKernelGGL(rope_freqs_reduce_kernel<128>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
     };
+    if (a->drop_mask) {
+        LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_bwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
+        p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
+    }
+    const int family = attn_family(a->dtype, a->N, hd, a->drop_mask != nullptr);
+    g_last_attn.store(family, std::memory_order_relaxed);
+    const bool resident = family == LNX_ATTN_KERNEL_RES4 || family == LNX_ATTN_KERNEL_RES8;
     if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
-        if (a->drop_mask) {
-            LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_bwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
-            p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
-        }
-        const bool drop = a->drop_mask != nullptr;
         int per_bh;
-        if (a->dtype == LNX_BF16) per_bh = hd == 32 ? attn_bwd_tiled<bf16_t, 32>(p, drop, st) : attn_bwd_tiled<bf16_t, 128>(p, drop, st);
-        else per_bh = hd == 32 ? attn_bwd_tiled<float, 32>(p, drop, st) : attn_bwd_tiled<float, 128>(p, drop, st);
+        if (a->dtype == LNX_BF16) per_bh = hd == 32 ? attn_bwd_tiled<bf16_t, 32>(p, family, st) : attn_bwd_tiled<bf16_t, 128>(p, family, st);
+        else per_bh = hd == 32 ? attn_bwd_tiled<float, 32>(p, family, st) : attn_bwd_tiled<float, 128>(p, family, st);
         reduce_freqs(per_bh);
         LNX_LAUNCH_CHECK();
         return 0;
     }
     if (a->drop_mask) {
-        LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_bwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
-        p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
         if (a->dtype == LNX_BF16) {
             typedef bf16_t T;
             hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG, st, p);
@@ -1706,7 +1717,7 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
         LNX_LAUNCH_CHECK();
         return 0;
     }
-    if (a->dtype == LNX_BF16 && a->N <= 256 && getenv("LNX_ATTN_TILED") == nullptr) {
+    if (resident) {
         typedef bf16_t T;
         const int npad = (a->N + 31) & ~31;
         const size_t lds_q = (size_t)npad * (2 * AT<T>::TRB);
@@ -1717,7 +1728,7 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
             set_lds(attn_bwd_dkv_res_kernel<T>, 256 * (2 * AT<T>::TRB + 2 * sizeof(float)));
             once = true;
         }
-        if (a->N <= 64) {
+        if (family == LNX_ATTN_KERNEL_RES4) {
             hipLaunchKernelGGL((attn_bwd_dq_res_kernel<T, 4>), dim3(a->B * a->heads), dim3(256), lds_q, st, p);
             hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<T, 4>), dim3(a->B * a->heads), dim3(256), lds_k, st, p);
         } else {
@@ -1729,7 +1740,7 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
         typedef bf16_t T;
         const size_t lds_q = 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG;
         const size_t lds_k = 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float);
-        if (tiled_nw8(a->N)) {  // 128 queries / keys per workgroup
+        if (family == LNX_ATTN_KERNEL_TILED8) {  // 128 queries / keys per workgroup
             p.qtiles = cdiv(a->N, 128);
             const int g8 = a->B * a->heads * p.qtiles;
             hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8>), dim3(g8), dim3(512), lds_q, st, p);
@@ -1756,6 +1767,14 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
     LNX_LAUNCH_CHECK();
     return 0;
 }
+
+extern "C" int lnx_attn_dispatch(int dtype, int N, int head_dim, int has_drop_mask) {
+    const int hd = head_dim ? head_dim : 64;
+    if ((dtype != LNX_F32 && dtype != LNX_BF16) || N <= 0 || !hd_ok(hd)) return -1;
+    return attn_family(dtype, N, hd, has_drop_mask != 0);
+}
+
+extern "C" int lnx_last_attn_kernel(void) { return g_last_attn.load(std::memory_order_relaxed); }
 
 extern "C" int lnx_attn_bwd_flush(void* stream) { return freq_flush((hipStream_t)stream); }
 
