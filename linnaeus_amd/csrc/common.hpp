@@ -37,6 +37,17 @@ void lnx_set_error(const char* fmt, ...);
 
 #define LNX_LAUNCH_CHECK() LNX_HIP(hipGetLastError())
 
+// Launch of a kernel whose dynamic LDS exceeds the 64 KiB a kernel gets unasked (`lds` is a constant of the instantiation).  The
+// attribute is raised once per kernel instantiation, by whichever thread comes first (a function-local static: thread-safe); if the
+// runtime refused it, every launch of that instantiation reports the refusal (2, lnx_last_error) instead of launching.
+template <auto Kernel, class P>
+int launch_with_lds(int grid, int block, size_t lds, hipStream_t st, const P& p) {
+    static const hipError_t raise_dynamic_lds_limit = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    LNX_HIP(raise_dynamic_lds_limit);
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, st, p);
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------
 // Tile scheduling of the persistent kernels (round 4).  One workgroup per CU that owns the CU's LDS / registers cannot be placed
 // beside a resident collective kernel (data-parallel training: the previous backward segment's gradient all-reduce sits on

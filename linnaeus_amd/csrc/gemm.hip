@@ -15,8 +15,6 @@
 // a vectorised epilogue (bias/gamma as float4).
 #include <stdlib.h>
 
-#include <atomic>
-
 #include "gemm_common.hpp"
 
 namespace {
@@ -320,118 +318,14 @@ template <typename T>
 int launch_tn(const WgradP& p, hipStream_t st) {
     const int grid = p.tiles_n * p.tiles_k * p.splits;
     const size_t lds = 4 * WgradCfg<T>::BMC * WgradCfg<T>::ROW;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_tn_kernel<T>), dim3(grid), dim3(256), lds, st, p);
-    return 0;
+    return launch_with_lds<gemm_tn_kernel<T>>(grid, 256, lds, st, p);
 }
 
 }  // namespace
 
-static bool g_force_v1 = getenv("LNX_GEMM_V1") != nullptr;  // A/B switch for benchmarking
-
-// dispatch bookkeeping (include/lnx.h: lnx_last_nt_kernel / lnx_nt_kernel_launches)
-static std::atomic<int> g_last_nt{0};
-static std::atomic<long long> g_nt_launches[LNX_NT_KERNEL_KINDS];
-namespace lnxg {
-void note_nt_kernel(int kind) {
-    if (kind < 0 || kind >= LNX_NT_KERNEL_KINDS) return;
-    g_last_nt.store(kind, std::memory_order_relaxed);
-    g_nt_launches[kind].fetch_add(1, std::memory_order_relaxed);
-}
-}  // namespace lnxg
-extern "C" int lnx_last_nt_kernel(void) { return g_last_nt.load(std::memory_order_relaxed); }
-extern "C" int64_t lnx_nt_kernel_launches(int kind) {
-    return (kind < 0 || kind >= LNX_NT_KERNEL_KINDS) ? -1 : (int64_t)g_nt_launches[kind].load(std::memory_order_relaxed);
-}
-
-static void fill_gemm_p(const lnx_gemm_args* a, GemmP& p) {
-    p.A = (const unsigned char*)a->A;
-    p.W = (const unsigned char*)a->W;
-    p.C = (unsigned char*)a->C;
-    p.C2 = (unsigned char*)a->c2;
-    p.aux = (const unsigned char*)a->aux;
-    p.bias = a->bias;
-    p.gamma = a->gamma;
-    p.rowscale = a->rowscale;
-    p.res = a->res;
-    p.lda = a->lda;
-    p.ldw = a->ldw;
-    p.ldc = a->ldc;
-    p.ldc2 = a->ldc2;
-    p.ldaux = a->ldaux;
-    p.ldres = a->ldres;
-    p.M = a->M;
-    p.N = a->N;
-    p.K = a->K;
-    p.a_mode = a->a_mode;
-    p.c_mode = a->c_mode;
-    p.pg = PatchGeom{a->Hin, a->Win, a->Cin};
-    p.cmap = RowMap{a->c_map.group, a->c_map.pad, a->c_map.off};
-    p.act = a->act;
-    p.rows_per_sample = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
-    p.tiles_m = cdiv(a->M, TILE);
-    p.tiles_n = cdiv(a->N, TILE);
-}
-
-// The dispatcher's decision without a launch (include/lnx.h): only M / N / K / dtype / out_f32 / act / addressing modes and WHICH of the
-// optional operands are present matter -- the pointers are never dereferenced, so a host-side caller may pass any non-null value.
-extern "C" int lnx_nt_dispatch(const lnx_gemm_args* a) {
-    if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || (a->dtype != LNX_F32 && a->dtype != LNX_BF16)) return -1;
-    GemmP p;
-    fill_gemm_p(a, p);
-    if (nt_skinny_ok(p, a->dtype, a->out_f32 != 0) && !g_force_v1) return LNX_NT_KERNEL_SKINNY;
-    if (nt_v2_ok(p, a->dtype) && !g_force_v1) return nt_v2_family(p, a->out_f32 != 0, nullptr);
-    return LNX_NT_KERNEL_V1;
-}
-
-extern "C" int lnx_gemm_nt(const lnx_gemm_args* a, void* stream) {
-    LNX_CHECK(a != nullptr, "lnx_gemm_nt: null args");
-    LNX_CHECK(a->dtype == LNX_F32 || a->dtype == LNX_BF16, "lnx_gemm_nt: bad dtype %d", a->dtype);
-    const int epv = a->dtype == LNX_F32 ? 4 : 8;
-    LNX_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "lnx_gemm_nt: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
-    LNX_CHECK(a->K % epv == 0, "lnx_gemm_nt: K=%d must be a multiple of %d", a->K, epv);
-    LNX_CHECK(a->A && a->W && a->C, "lnx_gemm_nt: null operand");
-    LNX_CHECK(a->ldw % epv == 0, "lnx_gemm_nt: ldw=%lld must be a multiple of %d", (long long)a->ldw, epv);
-    LNX_CHECK((((uintptr_t)a->A) & 15) == 0 && (((uintptr_t)a->W) & 15) == 0, "lnx_gemm_nt: A/W must be 16-byte aligned");
-    if (a->a_mode == LNX_ADDR_PATCH2) {
-        LNX_CHECK(a->Hin % 2 == 0 && a->Win % 2 == 0 && a->Cin % epv == 0, "lnx_gemm_nt: bad PATCH2 geometry %dx%dx%d", a->Hin, a->Win, a->Cin);
-        LNX_CHECK(a->K == 4 * a->Cin, "lnx_gemm_nt: PATCH2 needs K == 4*Cin");
-        LNX_CHECK(a->M % ((a->Hin / 2) * (a->Win / 2)) == 0, "lnx_gemm_nt: PATCH2 needs M == B*Ho*Wo");
-    } else {
-        LNX_CHECK(a->lda % epv == 0, "lnx_gemm_nt: lda=%lld must be a multiple of %d", (long long)a->lda, epv);
-    }
-    if (a->c_mode == LNX_ADDR_PATCH2) {
-        LNX_CHECK(a->Hin % 2 == 0 && a->Win % 2 == 0 && a->Cin % 16 == 0, "lnx_gemm_nt: bad PATCH2 output geometry");
-        LNX_CHECK(a->N == 4 * a->Cin, "lnx_gemm_nt: PATCH2 output needs N == 4*Cin");
-        LNX_CHECK(a->a_mode == LNX_ADDR_PLAIN, "lnx_gemm_nt: PATCH2 on both sides is not supported");
-    }
-    LNX_CHECK(a->act >= LNX_ACT_NONE && a->act <= LNX_ACT_MUL_AUX, "lnx_gemm_nt: unknown act %d", a->act);
-    if (a->act == LNX_ACT_GELU_BWD || a->act == LNX_ACT_RELU_BWD || a->act == LNX_ACT_MUL_AUX) LNX_CHECK(a->aux != nullptr, "lnx_gemm_nt: act %d needs aux", a->act);
-    if (a->act == LNX_ACT_GELU_D) LNX_CHECK(a->c2 != nullptr, "lnx_gemm_nt: GELU_D writes the derivative to c2, which is NULL");
-    if (a->rowscale) LNX_CHECK(a->rows_per_sample > 0, "lnx_gemm_nt: rowscale needs rows_per_sample");
-
-    GemmP p;
-    fill_gemm_p(a, p);
-    hipStream_t st = (hipStream_t)stream;
-    if (nt_skinny_ok(p, a->dtype, a->out_f32 != 0) && !g_force_v1) {
-        note_nt_kernel(LNX_NT_KERNEL_SKINNY);
-        launch_nt_skinny(p, a->out_f32 != 0, st);
-    } else if (nt_v2_ok(p, a->dtype) && !g_force_v1) {
-        launch_nt_v2(p, a->out_f32 != 0, st);  // (notes its own choice: v2 / v4 / v7 / v9)
-    } else if (a->dtype == LNX_BF16) {
-        note_nt_kernel(LNX_NT_KERNEL_V1);
-        if (a->out_f32) launch_nt<bf16_t, true>(p, st);
-        else launch_nt<bf16_t, false>(p, st);
-    } else {
-        note_nt_kernel(LNX_NT_KERNEL_V1);
-        launch_nt<float, true>(p, st);  // T == float: both output kinds are fp32
-    }
-    LNX_LAUNCH_CHECK();
-    return 0;
+int lnxg::launch_nt_v1(const GemmP& p, int dtype, bool out_f32, hipStream_t st) {
+    if (dtype == LNX_BF16) return out_f32 ? launch_nt<bf16_t, true>(p, st) : launch_nt<bf16_t, false>(p, st);
+    return launch_nt<float, true>(p, st);  // T == float: both output kinds are fp32
 }
 
 extern "C" int lnx_gemm_nt_group_ok(const lnx_gemm_args* a, int n, int accumulate) {
@@ -515,9 +409,11 @@ extern "C" int lnx_gemm_tn(const lnx_wgrad_args* a, void* stream) {
     p.m_per_split = mps;
     hipStream_t st = (hipStream_t)stream;
     static const bool no_defer = getenv("LNX_TN_NO_DEFER") != nullptr;  // A/B switch: every product reduces its own partial tiles at once
-    if (tn_v2_ok(p, a->dtype) && !g_force_v1) launch_tn_v2(p, a->splits, st, a->defer != 0 && !no_defer);
-    else if (a->dtype == LNX_BF16) launch_tn<bf16_t>(p, st);
-    else launch_tn<float>(p, st);
+    int rc;
+    if (tn_v2_ok(p, a->dtype) && !nt_switches().force_v1) rc = launch_tn_v2(p, a->splits, st, a->defer != 0 && !no_defer);
+    else if (a->dtype == LNX_BF16) rc = launch_tn<bf16_t>(p, st);
+    else rc = launch_tn<float>(p, st);
+    if (rc != 0) return rc;
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -180,7 +180,6 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
         asm volatile("ds_read_b128 %0, %1 offset:768" : "=v"(dst[3]) : "v"(a_) : "memory");             \
     } while (0)
 
-constexpr int BM4 = 256, BN4 = 256, BK4 = 32, ROWB4 = 64;
 constexpr int STAGE4 = (BM4 + BN4) * ROWB4;   // 32 KiB
 constexpr int NST4 = 4;
 constexpr int PIECES4 = STAGE4 / 1024 / 8;    // 1-KiB LDS-DMA instructions per wave per stage = 4
@@ -297,152 +296,40 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
     }
 }
 
-nt_experiment_fn g_nt_experiment = nullptr;
+// The forms each family is compiled for (with_nt_form launches nothing else).  The 256x256 kernel has no generic epilogue; the
+// 256x128 kernel carries it for both output types, and is the only one that gathers 2x2 patches on the A side.
+constexpr bool nt_v4_carries(bool out_f32, int f) {
+    if (out_f32) return f == (F_BIAS | F_RES);
+    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == (F_BIAS | F_GELU) || f == F_GELU_BWD;
+}
+constexpr bool nt_v2_carries(bool out_f32, int f) { return f == F_GENERIC || nt_v4_carries(out_f32, f); }
 
-// default choice (LNX_NT_V7 unset): from the measurements of tools/bench_gemm_epi.py
-// Measured (profiles/r03_nt_v7.log, sm shapes at B = 256): against the one-shot 256x128 kernel the persistent kernel wins
-// 10-30 % when it has at least two tiles per CU (no pipeline refill per tile, stores spread over the K loop) and the epilogue is
-// light (plain / bias / fp32 residual); it ties with the 256x256 kernel where that one applies (N % 256 == 0) and with the GELU
-// forms (their epilogue arithmetic, not their stores, is what the K loop waits for), and loses a few percent below two tiles
-// per CU.
-// Round 4: 256x256 or 256x128 tiles for a product whose N allows both?  Every tile of a launch costs the same, so a launch takes
-// ceil(tiles / CUs) rounds whatever the scheduler: 600 tiles of 256x256 on 256 CUs are three rounds for 2.3 rounds of work (the
-// N = 1536 products of BASELINE config 3's 128 images per GPU), the same product in 1200 tiles of 256x128 five half-size rounds.  The
-// big tile moves 1.5x fewer operand bytes per FLOP, which is worth ~3 % at K = 384 and ~12 % on long K loops (profiles/r03_bare_gemm.log).
-// LNX_NT_TILE_COST=0: the round-3 rule (big tile wherever N % 256 == 0).
-static bool big_tile_wins(const GemmP& p) {
-    static const bool off = getenv("LNX_NT_TILE_COST") && atoi(getenv("LNX_NT_TILE_COST")) == 0;
-    if (off) return true;
-    const int dc = device_cus();
-    const int cus = persistent_cus(dc > 0 ? dc : 256);
-    const int64_t rows = cdiv(p.M, 256);
-    const double big = (double)cdiv(rows * (p.N / BN4), (int64_t)cus) * 2.0 * (p.K <= 512 ? 0.97 : 0.88);
-    const double small = (double)cdiv(rows * cdiv(p.N, 128), (int64_t)cus);
-    return small >= 0.93 * big;  // (the small tile has to win by a margin: measured, a tie on paper goes to the big tile at sm / lg / xl)
+int launch_nt_v4(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
+    GemmP p = p0;
+    p.tiles_m = cdiv(p.M, BM4);
+    p.tiles_n = p.N / BN4;
+    const int grid = p.tiles_m * p.tiles_n;
+    return with_nt_form<nt_v4_carries>("gemm_nt_v4", out_f32, f, [&](auto form) {
+        using Form = decltype(form);
+        return launch_with_lds<gemm_nt_v4_kernel<Form::out_f32, Form::f>>(grid, 512, NST4 * STAGE4, st, p);
+    });
 }
 
-static bool nt_v7_preferred(const GemmP& p, int f, bool out_f32) {
-    const bool two_per_cu = (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 512;
-    const bool big_better = p.N % BN4 == 0 && big_tile_wins(p);
-    if (f == F_GELU_BWD && p.act == LNX_ACT_MUL_AUX) return two_per_cu;  // 121.6 -> 115.7 us at the sm fc2 data gradient, also against the 256x256 tile
-    if (f == F_GELU_BWD || f == (F_BIAS | F_C2 | F_GELU)) return two_per_cu && p.N % BN4 == 0 && !big_better;  // only instead of a badly filling big tile
-    if (f != 0 && f != F_BIAS && !(out_f32 && f == (F_BIAS | F_RES))) return false;
-    if (big_better) return false;  // the 256x256 tile (half the fill traffic per FLOP) is the better kernel there
-    return two_per_cu;
-}
-
-static bool nt_v4_ok(const GemmP& p, int f) {
-    static const bool off = getenv("LNX_NT_V4") && atoi(getenv("LNX_NT_V4")) == 0;  // A/B switch for benchmarking
-    if (off || f == (int)F_GENERIC || p.a_mode == LNX_ADDR_PATCH2) return false;
-    return p.N % BN4 == 0 && p.K % BK4 == 0 && p.K >= 4 * BK4;
-}
-
-bool nt_v2_ok(const GemmP& p, int dtype) {
-    if (dtype != LNX_BF16) return false;
-    if (p.K % 64 != 0 || p.K < 128) return false;
-    if (p.M < 1024) return false;  // tiny-M GEMMs (tail, meta heads) stay on the 128x128 kernel
-    return true;
-}
-
-// Which pipelined family a product takes (no launch: lnx_nt_dispatch and launch_nt_v2 share this) -- the rules of DESIGN.md's dispatch table:
-//   LNX_NT_V7: 1 = every shape the persistent deferred-store kernel can run, 0 = never, unset = the measured choice (nt_v7_preferred)
-//   LNX_NT_V9: 1 = the persistent 256x256 kernel wherever it can run, 0 = never, unset = with at least 1.5 tiles per CU (below that a
-//              workgroup has no second tile to hide the first one's epilogue under) and where the big tile wins on rounds
-int nt_v2_family(const GemmP& p, bool out_f32, int* f_out) {
-    const bool patch = p.a_mode == LNX_ADDR_PATCH2;
-    static const bool no_fast = getenv("LNX_NT_GENERIC_EPI") != nullptr;  // A/B switch for benchmarking
-    const int f = (patch || no_fast) ? (int)F_GENERIC : fast_epilogue_mask(p, out_f32);
-    if (f_out) *f_out = f;
-    {
-        const char* e7 = getenv("LNX_NT_V7");
-        const int v7 = e7 ? atoi(e7) : -1;
-        if (v7 != 0 && nt_v7_ok(p, f, out_f32) && (v7 == 1 || nt_v7_preferred(p, f, out_f32))) return LNX_NT_KERNEL_V7;
-    }
-    const char* e9 = getenv("LNX_NT_V9");
-    const int v9 = e9 ? atoi(e9) : -1;
-    if (nt_v4_ok(p, f) && (v9 == 1 || big_tile_wins(p))) {
-        const int dc = device_cus();
-        const int64_t cus = dc > 0 ? dc : 256;
-        if (v9 != 0 && nt_v9_ok(p, f, out_f32) && (v9 == 1 || (int64_t)cdiv(p.M, BM4) * (p.N / BN4) * 2 >= 3 * cus)) return LNX_NT_KERNEL_V9;
-        return LNX_NT_KERNEL_V4;
-    }
-    return LNX_NT_KERNEL_V2;
-}
-
-int launch_nt_v2(const GemmP& p0, bool out_f32, hipStream_t st) {
+int launch_nt_v2(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
     GemmP p = p0;
     p.tiles_m = cdiv(p.M, BM2);
     p.tiles_n = cdiv(p.N, BN2);
     const int grid = p.tiles_m * p.tiles_n;
     const size_t lds = NSTAGE * STAGE_BYTES;
     const bool patch = p.a_mode == LNX_ADDR_PATCH2;
-    int f = 0;
-    const int family = nt_v2_family(p, out_f32, &f);
-    // measurement kernels kept outside the product (tools/experiments/: gemm_nt_v5, gemm_nt_v8) hook in here when their
-    // library is the one loaded (LNX_LIB_PATH=tools/liblnx_experiments.so); the shipped library never sets the hook
-    if (g_nt_experiment && g_nt_experiment(p, f, out_f32, st) == 0) return 0;
-    if (family == LNX_NT_KERNEL_V7) {
-        note_nt_kernel(LNX_NT_KERNEL_V7);
-        return launch_nt_v7(p, f, out_f32, st);
-    }
-    if (family == LNX_NT_KERNEL_V9) {
-        note_nt_kernel(LNX_NT_KERNEL_V9);
-        return launch_nt_v9(p, f, out_f32, st);
-    }
-    if (family == LNX_NT_KERNEL_V4) {
-        note_nt_kernel(LNX_NT_KERNEL_V4);
-        p.tiles_m = cdiv(p.M, BM4);
-        p.tiles_n = p.N / BN4;
-        const int grid4 = p.tiles_m * p.tiles_n;
-        const size_t lds4 = NST4 * STAGE4;
-#define V4_LAUNCH(O, FF)                                                                                                             \
-    do {                                                                                                                             \
-        static bool attr = false;                                                                                                    \
-        if (!attr) {                                                                                                                 \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_v4_kernel<O, FF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4); \
-            attr = true;                                                                                                             \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((gemm_nt_v4_kernel<O, FF>), dim3(grid4), dim3(512), lds4, st, p);                                         \
-    } while (0)
-        if (out_f32) V4_LAUNCH(true, F_BIAS | F_RES);
-        else if (f == 0) V4_LAUNCH(false, 0);
-        else if (f == F_BIAS) V4_LAUNCH(false, F_BIAS);
-        else if (f == (F_BIAS | F_C2 | F_GELU)) V4_LAUNCH(false, F_BIAS | F_C2 | F_GELU);
-        else if (f == (F_BIAS | F_GELU)) V4_LAUNCH(false, F_BIAS | F_GELU);
-        else V4_LAUNCH(false, F_GELU_BWD);
-#undef V4_LAUNCH
-        return 0;
-    }
-    note_nt_kernel(LNX_NT_KERNEL_V2);
-#define V2_LAUNCH(O, P, FF)                                                                                                          \
-    do {                                                                                                                             \
-        static bool attr = false;                                                                                                    \
-        if (!attr) {                                                                                                                 \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_v2_kernel<O, P, FF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            attr = true;                                                                                                             \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((gemm_nt_v2_kernel<O, P, FF>), dim3(grid), dim3(512), lds, st, p);                                        \
-    } while (0)
-    if (f == F_GENERIC) {
-        if (out_f32 && patch) V2_LAUNCH(true, true, F_GENERIC);
-        else if (out_f32) V2_LAUNCH(true, false, F_GENERIC);
-        else if (patch) V2_LAUNCH(false, true, F_GENERIC);
-        else V2_LAUNCH(false, false, F_GENERIC);
-    } else if (out_f32) {
-        V2_LAUNCH(true, false, F_BIAS | F_RES);
-    } else if (f == 0) {
-        V2_LAUNCH(false, false, 0);
-    } else if (f == F_BIAS) {
-        V2_LAUNCH(false, false, F_BIAS);
-    } else if (f == (F_BIAS | F_C2 | F_GELU)) {
-        V2_LAUNCH(false, false, F_BIAS | F_C2 | F_GELU);
-    } else if (f == (F_BIAS | F_GELU)) {
-        V2_LAUNCH(false, false, F_BIAS | F_GELU);
-    } else {
-        V2_LAUNCH(false, false, F_GELU_BWD);
-    }
-#undef V2_LAUNCH
-    return 0;
+    LNX_CHECK(!patch || f == F_GENERIC, "gemm_nt_v2: the 2x2 patch gather is compiled with the generic epilogue only (f = %d)", f);
+    return with_nt_form<nt_v2_carries>("gemm_nt_v2", out_f32, f, [&](auto form) {
+        using Form = decltype(form);
+        if constexpr (Form::f == F_GENERIC) {
+            if (patch) return launch_with_lds<gemm_nt_v2_kernel<Form::out_f32, true, Form::f>>(grid, 512, lds, st, p);
+        }
+        return launch_with_lds<gemm_nt_v2_kernel<Form::out_f32, false, Form::f>>(grid, 512, lds, st, p);
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -825,29 +712,16 @@ int launch_tn_v2(const WgradP& p0, int splits_hint, hipStream_t st, bool defer) 
     p.splits = cdiv(mtiles, per);
     const int grid = tiles * p.splits;
     const size_t lds = NSTAGE * (size_t)(TBM * (RW + CW) * 2);
-#define TNV2_(R, C, P)                                                                                                               \
-    do {                                                                                                                             \
-        static bool attr = false;                                                                                                    \
-        if (!attr) {                                                                                                                 \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_v2_kernel<R, C, P>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            attr = true;                                                                                                             \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((gemm_tn_v2_kernel<R, C, P>), dim3(grid), dim3(512), lds, st, p);                                         \
-    } while (0)
-#define TNV2(R, C)                                           \
-    do {                                                     \
-        if (p.a_mode == LNX_ADDR_PATCH2) TNV2_(R, C, true);  \
-        else TNV2_(R, C, false);                             \
-    } while (0)
     static const bool no_ws = getenv("LNX_TN_ATOMIC") != nullptr;  // A/B switch for benchmarking
     const size_t need = (size_t)p.splits * tiles * (256 * 128) + (size_t)p.splits * p.tiles_n * RW;
     // padded tiles are stored and re-read whole: with poorly filled tiles (N x K well below tiles x 256 x 128) the atomics move fewer bytes
     const bool sparse_tiles = (double)p.N * p.k_store < 0.7 * (double)tiles * (256 * 128);
     if (no_ws || p.ws == nullptr || (size_t)p.ws_floats < need || p.splits < 2 || sparse_tiles) p.ws = nullptr;
-    if (wide_r) TNV2(256, 128);
-    else TNV2(128, 256);
-#undef TNV2
-#undef TNV2_
+    const bool patch = p.a_mode == LNX_ADDR_PATCH2;
+    int rc;
+    if (wide_r) rc = patch ? launch_with_lds<gemm_tn_v2_kernel<256, 128, true>>(grid, 512, lds, st, p) : launch_with_lds<gemm_tn_v2_kernel<256, 128, false>>(grid, 512, lds, st, p);
+    else rc = patch ? launch_with_lds<gemm_tn_v2_kernel<128, 256, true>>(grid, 512, lds, st, p) : launch_with_lds<gemm_tn_v2_kernel<128, 256, false>>(grid, 512, lds, st, p);
+    if (rc != 0) return rc;
     if (p.ws) {
         const int64_t work = (int64_t)tiles * (RW * CW / 4) + (p.db ? p.N : 0);  // one thread per float4 slot of a partial tile, then one per bias entry
         const int blocks = (int)cdiv(work, 256);

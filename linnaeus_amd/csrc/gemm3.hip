@@ -416,15 +416,20 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
     if (reset_ctr && tid == 0) sched_reset(ctr);
 }
 
+// the forms this family is compiled for (no bias + GELU without the second output, no generic epilogue)
+constexpr bool nt_v7_carries(bool out_f32, int f) {
+    if (out_f32) return f == (F_BIAS | F_RES);
+    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == F_GELU_BWD;
+}
+
 bool nt_v7_ok(const GemmP& p, int f, bool out_f32) {
-    if (f == (int)F_GENERIC || p.a_mode == LNX_ADDR_PATCH2) return false;
+    if (p.a_mode == LNX_ADDR_PATCH2) return false;
     if (p.act == LNX_ACT_GELU_D) return false;  // this kernel's fc1 form keeps ONE tensor per tile; the derivative form needs two
     if (p.K % BK7 != 0 || p.K / BK7 < 6) return false;
     if (p.N % 64 != 0) return false;  // a wave's 64 columns are all inside or all outside N
     const int64_t lim = (int64_t)1 << 31;  // 32-bit byte offsets of the LDS-DMA sources
     if ((int64_t)p.M * p.lda * 2 >= lim || (int64_t)p.N * p.ldw * 2 >= lim) return false;
-    if (out_f32) return f == (F_BIAS | F_RES);
-    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == F_GELU_BWD;
+    return nt_v7_carries(out_f32, f);
 }
 
 int launch_nt_v7(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
@@ -433,34 +438,17 @@ int launch_nt_v7(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
     p.tiles_n = cdiv(p.N, BN7);
     const int ntiles = p.tiles_m * p.tiles_n;
     const int cus = device_cus();
-    if (cus <= 0) return 1;
+    LNX_CHECK(cus > 0, "gemm_nt_v7: no device");
     const int room = persistent_cus(cus);              // cus - LNX_CU_MARGIN / lnx_set_cu_margin()
     const int grid = ntiles < room ? ntiles : room;    // persistent: one workgroup per CU (144 KiB of LDS each)
     const size_t lds = NST7 * STAGE7 + 16;             // + the dword the next tile's position is published through
     p.tile_slot = tile_sched_static() ? -1 : tile_slot_of(st);
     const bool deep = p.K / BK7 >= 17;  // long K loops spread the deferred traffic over 8 + 8 iterations instead of 3 + 2
-#define V7_LAUNCH_(O, FF, H, T)                                                                                                      \
-    do {                                                                                                                             \
-        static bool attr = false;                                                                                                    \
-        if (!attr) {                                                                                                                 \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_v7_kernel<O, FF, H, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            attr = true;                                                                                                             \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((gemm_nt_v7_kernel<O, FF, H, T>), dim3(grid), dim3(512), lds, st, p);                                     \
-    } while (0)
-#define V7_LAUNCH(O, FF)                   \
-    do {                                   \
-        if (deep) V7_LAUNCH_(O, FF, 8, 8); \
-        else V7_LAUNCH_(O, FF, 3, 2);      \
-    } while (0)
-    if (out_f32) V7_LAUNCH(true, F_BIAS | F_RES);
-    else if (f == 0) V7_LAUNCH(false, 0);
-    else if (f == F_BIAS) V7_LAUNCH(false, F_BIAS);
-    else if (f == (F_BIAS | F_C2 | F_GELU)) V7_LAUNCH(false, F_BIAS | F_C2 | F_GELU);
-    else V7_LAUNCH(false, F_GELU_BWD);
-#undef V7_LAUNCH
-#undef V7_LAUNCH_
-    return 0;
+    return with_nt_form<nt_v7_carries>("gemm_nt_v7", out_f32, f, [&](auto form) {
+        using Form = decltype(form);
+        if (deep) return launch_with_lds<gemm_nt_v7_kernel<Form::out_f32, Form::f, 8, 8>>(grid, 512, lds, st, p);
+        return launch_with_lds<gemm_nt_v7_kernel<Form::out_f32, Form::f, 3, 2>>(grid, 512, lds, st, p);
+    });
 }
 
 }  // namespace lnxg

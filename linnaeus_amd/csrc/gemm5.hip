@@ -245,13 +245,18 @@ __global__ __launch_bounds__(512) void gemm_nt_v9_kernel(const GemmP p) {
     if (reset_ctr && tid == 0) sched_reset(ctr);
 }
 
+// the forms this family is compiled for (those of the one-shot 256x256 kernel: no generic epilogue)
+constexpr bool nt_v9_carries(bool out_f32, int f) {
+    if (out_f32) return f == (F_BIAS | F_RES);
+    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == (F_BIAS | F_GELU) || f == F_GELU_BWD;
+}
+
 bool nt_v9_ok(const GemmP& p, int f, bool out_f32) {
-    if (f == (int)F_GENERIC || p.a_mode == LNX_ADDR_PATCH2) return false;
+    if (p.a_mode == LNX_ADDR_PATCH2) return false;
     if (p.N % BN9 != 0 || p.K % BK9 != 0 || p.K / BK9 < 8) return false;
     const int64_t lim = (int64_t)1 << 31;
     if ((int64_t)p.M * p.lda * 2 >= lim || (int64_t)p.N * p.ldw * 2 >= lim) return false;
-    if (out_f32) return f == (F_BIAS | F_RES);
-    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == (F_BIAS | F_GELU) || f == F_GELU_BWD;
+    return nt_v9_carries(out_f32, f);
 }
 
 int launch_nt_v9(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
@@ -260,28 +265,15 @@ int launch_nt_v9(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
     p.tiles_n = p.N / BN9;
     const int ntiles = p.tiles_m * p.tiles_n;
     const int cus = device_cus();
-    if (cus <= 0) return 1;
+    LNX_CHECK(cus > 0, "gemm_nt_v9: no device");
     const int room = persistent_cus(cus);
     const int grid = ntiles < room ? ntiles : room;
     const size_t lds = NST9 * STAGE9 + 16;
     p.tile_slot = tile_sched_static() ? -1 : tile_slot_of(st);
-#define V9_LAUNCH(O, FF)                                                                                                             \
-    do {                                                                                                                             \
-        static bool attr = false;                                                                                                    \
-        if (!attr) {                                                                                                                 \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_v9_kernel<O, FF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            attr = true;                                                                                                             \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((gemm_nt_v9_kernel<O, FF>), dim3(grid), dim3(512), lds, st, p);                                           \
-    } while (0)
-    if (out_f32) V9_LAUNCH(true, F_BIAS | F_RES);
-    else if (f == 0) V9_LAUNCH(false, 0);
-    else if (f == F_BIAS) V9_LAUNCH(false, F_BIAS);
-    else if (f == (F_BIAS | F_C2 | F_GELU)) V9_LAUNCH(false, F_BIAS | F_C2 | F_GELU);
-    else if (f == (F_BIAS | F_GELU)) V9_LAUNCH(false, F_BIAS | F_GELU);
-    else V9_LAUNCH(false, F_GELU_BWD);
-#undef V9_LAUNCH
-    return 0;
+    return with_nt_form<nt_v9_carries>("gemm_nt_v9", out_f32, f, [&](auto form) {
+        using Form = decltype(form);
+        return launch_with_lds<gemm_nt_v9_kernel<Form::out_f32, Form::f>>(grid, 512, lds, st, p);
+    });
 }
 
 }  // namespace lnxg

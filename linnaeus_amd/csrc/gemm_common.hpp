@@ -1,5 +1,6 @@
 // Shared pieces of the MFMA GEMM kernels (gemm.hip: 128x128 register-staged kernels for both
-// storage types; gemm2.hip: 256x128 LDS-DMA pipelined bf16 kernel).
+// storage types; gemm2.hip: 256x128 LDS-DMA pipelined bf16 kernel), and the host-side seam between the dispatcher
+// (gemm_nt_dispatch.cpp) and the families' launchers.
 #pragma once
 #include "common.hpp"
 #include "../../include/lnx.h"
@@ -452,13 +453,28 @@ struct WgradP {
     int tiles_n, tiles_k, splits, m_per_split;
 };
 
-// gemm3.hip: persistent 256x128 kernel whose epilogue stores / fetches ride under the next tile's K loop
-bool nt_v7_ok(const GemmP& p, int f, bool out_f32);
-int launch_nt_v7(const GemmP& p, int f, bool out_f32, hipStream_t st);
+// ---- host side: one decision (gemm_nt_dispatch.cpp), one launcher per kernel family ----
 
-// gemm5.hip: persistent 256x256 kernel (the v4 K loop, tiles drawn from the counters, ring never drained)
-bool nt_v9_ok(const GemmP& p, int f, bool out_f32);
-int launch_nt_v9(const GemmP& p, int f, bool out_f32, hipStream_t st);
+// The A/B switches of the GEMM dispatch, all read in one place (nt_switches).  LNX_NT_V7, LNX_NT_V9 and LNX_FP8_X8 are read on every
+// call (the tests flip them inside one process); the other five are A/B switches for whole runs and are latched by the first call.
+struct NtSwitches {
+    bool force_v1;     // LNX_GEMM_V1 set: the 128x128 kernels for every product (lnx_gemm_nt and lnx_gemm_tn)
+    bool skinny;       // LNX_NT_SKINNY=0 clears it
+    bool v4;           // LNX_NT_V4=0 clears it: no 256x256 tile, one-shot or persistent
+    bool tile_cost;    // LNX_NT_TILE_COST=0 clears it: the round-3 rule (big tile wherever N % 256 == 0)
+    bool generic_epi;  // LNX_NT_GENERIC_EPI set: the generic epilogue for every pipelined product
+    int v7, v9;        // LNX_NT_V7 / LNX_NT_V9: 1 = wherever the kernel can run, 0 = never, -1 (unset) = the measured choice
+    bool fp8_x8;       // LNX_FP8_X8=0 clears it: the 256x128-tile kernel for every MXFP8 product
+};
+NtSwitches nt_switches();
+
+void fill_gemm_p(const lnx_gemm_args* a, GemmP& p);  // the one place a lnx_gemm_args becomes a GemmP (tiles_m / tiles_n: 128x128 tiles)
+
+// What lnx_gemm_nt does with a product: the LNX_NT_KERNEL_* family and, for the pipelined families, the epilogue mask of its launch.
+struct NtChoice {
+    int kind, f;
+};
+NtChoice nt_choose(const GemmP& p, int dtype, bool out_f32);
 
 // measurement kernels live outside the product (tools/experiments/); their library registers a dispatcher here.  It returns 0
 // when it has launched the product, anything else to decline.  nullptr in the shipped library.
@@ -468,15 +484,64 @@ extern nt_experiment_fn g_nt_experiment;
 // which NT kernel family a launch took (lnx_last_nt_kernel / lnx_nt_kernel_launches: the tests' proof of dispatch)
 void note_nt_kernel(int kind);
 
+// A compiled epilogue form as a type: what with_nt_form hands a family's launcher.
+template <bool O, int FF>
+struct NtForm {
+    static constexpr bool out_f32 = O;
+    static constexpr int f = FF;
+};
+int nt_form_error(const char* family, bool out_f32, int f);  // sets the error message, returns 1
+
+template <auto Carries, bool O, int FF, class Launch>
+int nt_form_case(const char* family, Launch& launch) {
+    if constexpr (Carries(O, FF)) return launch(NtForm<O, FF>{});
+    else return nt_form_error(family, O, FF);
+}
+
+// The one ladder from the run-time (out_f32, f) of a launch to the compiled forms.  `Carries` is the family's constexpr statement of the
+// forms it is compiled for (next to its kernel); `launch` is called with the NtForm of the product.  A form the family does not carry,
+// or a mask that is no compiled form at all, is an error (1, lnx_last_error) -- never another form's kernel.
+template <auto Carries, class Launch>
+int with_nt_form(const char* family, bool out_f32, int f, Launch&& launch) {
+    if (f == F_GENERIC) return out_f32 ? nt_form_case<Carries, true, F_GENERIC>(family, launch) : nt_form_case<Carries, false, F_GENERIC>(family, launch);
+    if (out_f32) {
+        if (f == (F_BIAS | F_RES)) return nt_form_case<Carries, true, F_BIAS | F_RES>(family, launch);
+        return nt_form_error(family, out_f32, f);
+    }
+    switch (f) {
+        case 0: return nt_form_case<Carries, false, 0>(family, launch);
+        case F_BIAS: return nt_form_case<Carries, false, F_BIAS>(family, launch);
+        case F_BIAS | F_C2 | F_GELU: return nt_form_case<Carries, false, F_BIAS | F_C2 | F_GELU>(family, launch);
+        case F_BIAS | F_C2 | F_GELU | F_MXOUT: return nt_form_case<Carries, false, F_BIAS | F_C2 | F_GELU | F_MXOUT>(family, launch);
+        case F_BIAS | F_GELU: return nt_form_case<Carries, false, F_BIAS | F_GELU>(family, launch);
+        case F_GELU_BWD: return nt_form_case<Carries, false, F_GELU_BWD>(family, launch);
+        case F_GELU_BWD | F_MXOUT: return nt_form_case<Carries, false, F_GELU_BWD | F_MXOUT>(family, launch);
+    }
+    return nt_form_error(family, out_f32, f);
+}
+
+// gemm.hip: 128x128 register-staged kernels (both storage types)
+int launch_nt_v1(const GemmP& p, int dtype, bool out_f32, hipStream_t st);
+
 // gemm_skinny.hip: M <= 256 (one wave per 32x32 output tile, operands straight from L2)
 bool nt_skinny_ok(const GemmP& p, int dtype, bool out_f32);
 int launch_nt_skinny(const GemmP& p, bool out_f32, hipStream_t st);
 int launch_nt_skinny_group(const GemmP* ps, int n, bool accumulate, bool out_f32, hipStream_t st);  // lnx_gemm_nt_group
 
-// gemm2.hip: 256x128 LDS-DMA pipelined kernels (bf16)
-int launch_nt_v2(const GemmP& p, bool out_f32, hipStream_t st);
-int nt_v2_family(const GemmP& p, bool out_f32, int* f_out);  // V7 / V9 / V4 / V2: the choice launch_nt_v2 makes, without launching
-bool nt_v2_ok(const GemmP& p, int dtype);
+// gemm2.hip: 256x128 (v2) and 256x256 (v4) LDS-DMA pipelined kernels (bf16)
+constexpr int BM4 = 256, BN4 = 256, BK4 = 32, ROWB4 = 64;  // v4: 256x256 tile, K in 32-element slices = 64-byte LDS rows
+int launch_nt_v2(const GemmP& p, int f, bool out_f32, hipStream_t st);
+int launch_nt_v4(const GemmP& p, int f, bool out_f32, hipStream_t st);
+
+// gemm3.hip: persistent 256x128 kernel whose epilogue stores / fetches ride under the next tile's K loop
+bool nt_v7_ok(const GemmP& p, int f, bool out_f32);
+int launch_nt_v7(const GemmP& p, int f, bool out_f32, hipStream_t st);
+
+// gemm5.hip: persistent 256x256 kernel (the v4 K loop, tiles drawn from the counters, ring never drained)
+bool nt_v9_ok(const GemmP& p, int f, bool out_f32);
+int launch_nt_v9(const GemmP& p, int f, bool out_f32, hipStream_t st);
+
+// gemm2.hip: weight gradients on the same LDS-DMA ring
 int launch_tn_v2(const WgradP& p, int splits_hint, hipStream_t st, bool defer);
 int tn_flush(hipStream_t st);  // launches the deferred second stages of this thread, if any (st: their stream, or nullptr); 1 = they belong to another stream
 int tn_discard();               // forgets them without launching (error paths / teardown); returns how many

@@ -586,6 +586,13 @@ __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(const TX* __restric
     }
 }
 
+// The forms both families (gemm_nt_fp8, gemm_nt_mx8) are compiled for: no generic epilogue, no bias + GELU without the second output; F_MXOUT (the MXFP8
+// copy of the output) rides on the two forms whose output feeds another MXFP8 product.
+constexpr bool nt_fp8_carries(bool out_f32, int f) {
+    if (out_f32) return f == (F_BIAS | F_RES);
+    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == (F_BIAS | F_C2 | F_GELU | F_MXOUT) || f == F_GELU_BWD || f == (F_GELU_BWD | F_MXOUT);
+}
+
 }  // namespace lnxg
 using namespace lnxg;
 
@@ -631,14 +638,7 @@ static int launch_fp8(const lnx_gemm_args* a, const float* a_scale, const float*
     const bool mx = mxa != nullptr;
     if (mx) LNX_CHECK(mxw != nullptr && ((((uintptr_t)mxa) | ((uintptr_t)mxw)) & 3) == 0, "%s: block-scale arrays must be 4-byte aligned", who);
     GemmP p;
-    p.A = (const unsigned char*)a->A; p.W = (const unsigned char*)a->W; p.C = (unsigned char*)a->C; p.C2 = (unsigned char*)a->c2;
-    p.aux = (const unsigned char*)a->aux; p.bias = a->bias; p.gamma = a->gamma; p.rowscale = a->rowscale; p.res = a->res;
-    p.lda = a->lda; p.ldw = a->ldw; p.ldc = a->ldc; p.ldc2 = a->ldc2; p.ldaux = a->ldaux; p.ldres = a->ldres;
-    p.M = a->M; p.N = a->N; p.K = a->K; p.a_mode = a->a_mode; p.c_mode = a->c_mode;
-    p.pg = PatchGeom{a->Hin, a->Win, a->Cin};
-    p.cmap = RowMap{0, 0, 0};
-    p.act = a->act;
-    p.rows_per_sample = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
+    fill_gemm_p(a, p);
     p.tiles_m = cdiv(a->M, F8_BM);
     p.tiles_n = cdiv(a->N, F8_BN);
     p.sa = a_scale; p.sw = w_scale;
@@ -653,72 +653,31 @@ static int launch_fp8(const lnx_gemm_args* a, const float* a_scale, const float*
     }
     LNX_CHECK(f != (int)F_GENERIC && a->gamma == nullptr, "%s: this epilogue needs the generic form, which the fp8 kernels do not carry", who);
     hipStream_t st = (hipStream_t)stream;
-    {
-        // the 256x256-tile MX kernel where it applies (LNX_FP8_X8=0: never)
-        const char* e = getenv("LNX_FP8_X8");
-        const bool x8_off = e && atoi(e) == 0;
-        if (mx && !x8_off && a->N % X8_BN == 0 && a->K % 128 == 0 && a->K / X8_BK >= 4 && (int64_t)cdiv(a->M, X8_BM) * (a->N / X8_BN) >= 128) {
-            p.tiles_m = cdiv(a->M, X8_BM);
-            p.tiles_n = a->N / X8_BN;
-            const int gridx = p.tiles_m * p.tiles_n;
-            const size_t ldsx = X8_NST * (size_t)(X8_STAGE + X8_SCALES);
-#define X8_LAUNCH(O, FF)                                                                                                              \
-    do {                                                                                                                              \
-        static bool attr = false;                                                                                                     \
-        if (!attr) {                                                                                                                  \
-            LNX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_mx8_kernel<O, FF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx)); \
-            attr = true;                                                                                                              \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((gemm_nt_mx8_kernel<O, FF>), dim3(gridx), dim3(512), ldsx, st, p);                                         \
-    } while (0)
-            bool done = true;
-            if (out_f32 && f == (F_BIAS | F_RES)) X8_LAUNCH(true, F_BIAS | F_RES);
-            else if (out_f32) done = false;
-            else if (f == 0) X8_LAUNCH(false, 0);
-            else if (f == F_BIAS) X8_LAUNCH(false, F_BIAS);
-            else if (f == (F_BIAS | F_C2 | F_GELU) && a->act == LNX_ACT_GELU) X8_LAUNCH(false, F_BIAS | F_C2 | F_GELU);
-            else if (f == (F_BIAS | F_C2 | F_GELU | F_MXOUT) && a->act == LNX_ACT_GELU) X8_LAUNCH(false, F_BIAS | F_C2 | F_GELU | F_MXOUT);
-            else if (f == F_GELU_BWD && a->act == LNX_ACT_GELU_BWD) X8_LAUNCH(false, F_GELU_BWD);
-            else if (f == (F_GELU_BWD | F_MXOUT) && a->act == LNX_ACT_GELU_BWD) X8_LAUNCH(false, F_GELU_BWD | F_MXOUT);
-            else done = false;
-#undef X8_LAUNCH
-            if (done) {
-                note_nt_kernel(LNX_NT_KERNEL_MX8);
-                LNX_LAUNCH_CHECK();
-                return 0;
-            }
-            p.tiles_m = cdiv(a->M, F8_BM);
-            p.tiles_n = cdiv(a->N, F8_BN);
-        }
+    // the 256x256-tile MX kernel where it applies (LNX_FP8_X8=0: never) and carries the form; its GELU forms only for the act they are named for
+    const bool act_twin = ((f & F_GELU) && a->act != LNX_ACT_GELU) || ((f & F_GELU_BWD) && a->act != LNX_ACT_GELU_BWD);
+    if (mx && nt_switches().fp8_x8 && a->N % X8_BN == 0 && a->K % 128 == 0 && a->K / X8_BK >= 4 && (int64_t)cdiv(a->M, X8_BM) * (a->N / X8_BN) >= 128 &&
+        nt_fp8_carries(out_f32, f) && !act_twin) {
+        p.tiles_m = cdiv(a->M, X8_BM);
+        p.tiles_n = a->N / X8_BN;
+        const int rc = with_nt_form<nt_fp8_carries>("gemm_nt_mx8", out_f32, f, [&](auto form) {
+            using Form = decltype(form);
+            return launch_with_lds<gemm_nt_mx8_kernel<Form::out_f32, Form::f>>(p.tiles_m * p.tiles_n, 512, X8_NST * (size_t)(X8_STAGE + X8_SCALES), st, p);
+        });
+        if (rc != 0) return rc;
+        note_nt_kernel(LNX_NT_KERNEL_MX8);
+        LNX_LAUNCH_CHECK();
+        return 0;
     }
+    if (out_f32) LNX_CHECK(f == (F_BIAS | F_RES), "%s: an fp32 output needs bias + residual (the model's form)", who);
     const int grid = p.tiles_m * p.tiles_n;
-#define F8_LAUNCH_(O, FF, MXV)                                                                                                        \
-    do {                                                                                                                              \
-        const size_t lds = F8_NSTAGE * (size_t)(F8_STAGE + ((MXV) ? F8_SCALES : 0));                                                  \
-        static bool attr = false;                                                                                                     \
-        if (!attr) {                                                                                                                  \
-            LNX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_fp8_kernel<O, FF, MXV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr = true;                                                                                                              \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((gemm_nt_fp8_kernel<O, FF, MXV>), dim3(grid), dim3(512), lds, st, p);                                      \
-    } while (0)
-#define F8_LAUNCH(O, FF)                 \
-    do {                                 \
-        if (mx) F8_LAUNCH_(O, FF, true); \
-        else F8_LAUNCH_(O, FF, false);   \
-    } while (0)
-    if (out_f32) {
-        LNX_CHECK(f == (F_BIAS | F_RES), "%s: an fp32 output needs bias + residual (the model's form)", who);
-        F8_LAUNCH(true, F_BIAS | F_RES);
-    } else if (f == 0) F8_LAUNCH(false, 0);
-    else if (f == F_BIAS) F8_LAUNCH(false, F_BIAS);
-    else if (f == (F_BIAS | F_C2 | F_GELU)) F8_LAUNCH(false, F_BIAS | F_C2 | F_GELU);
-    else if (f == (F_BIAS | F_C2 | F_GELU | F_MXOUT)) F8_LAUNCH_(false, F_BIAS | F_C2 | F_GELU | F_MXOUT, true);
-    else if (f == F_GELU_BWD) F8_LAUNCH(false, F_GELU_BWD);
-    else if (f == (F_GELU_BWD | F_MXOUT)) F8_LAUNCH_(false, F_GELU_BWD | F_MXOUT, true);
-    else LNX_CHECK(false, "%s: unsupported epilogue feature set %d", who, f);
-#undef F8_LAUNCH
-#undef F8_LAUNCH_
+    const int rc = with_nt_form<nt_fp8_carries>(who, out_f32, f, [&](auto form) {
+        using Form = decltype(form);
+        constexpr size_t lds_mx = F8_NSTAGE * (size_t)(F8_STAGE + F8_SCALES), lds = F8_NSTAGE * (size_t)F8_STAGE;
+        if constexpr (Form::f & F_MXOUT) return launch_with_lds<gemm_nt_fp8_kernel<Form::out_f32, Form::f, true>>(grid, 512, lds_mx, st, p);  // (c8 came with block scales: checked above)
+        else if (mx) return launch_with_lds<gemm_nt_fp8_kernel<Form::out_f32, Form::f, true>>(grid, 512, lds_mx, st, p);
+        else return launch_with_lds<gemm_nt_fp8_kernel<Form::out_f32, Form::f, false>>(grid, 512, lds, st, p);
+    });
+    if (rc != 0) return rc;
     note_nt_kernel(LNX_NT_KERNEL_FP8);
     LNX_LAUNCH_CHECK();
     return 0;

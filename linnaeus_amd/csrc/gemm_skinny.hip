@@ -144,8 +144,7 @@ __global__ __launch_bounds__(64) void gemm_nt_skinny_group_kernel(const SkGroup 
 }  // namespace
 
 bool nt_skinny_ok(const GemmP& p, int dtype, bool out_f32) {
-    static const bool off = getenv("LNX_NT_SKINNY") != nullptr && atoi(getenv("LNX_NT_SKINNY")) == 0;
-    if (off || dtype != LNX_BF16 || p.M > 256) return false;
+    if (dtype != LNX_BF16 || p.M > 256) return false;
     if (p.a_mode != LNX_ADDR_PLAIN || p.c_mode != LNX_ADDR_PLAIN || p.cmap.group > 0) return false;
     if (p.act != LNX_ACT_NONE || p.gamma || p.rowscale || p.aux || p.C2) return false;
     if (p.res && !out_f32) return false;  // the residual is fp32 like the output it is added to

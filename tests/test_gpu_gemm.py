@@ -519,7 +519,7 @@ XL_LG_NK = [(M_XL, 1024, 1024), (M_XL, 3072, 1024), (M_XL, 4096, 1024), (M_XL, 1
 @pytest.mark.parametrize("form", ["plain", "bias", "res_f32", "mul_aux", "gelu_bwd", "fc1", "fc1d", "bias_gelu"])
 def test_nt_default_dispatch_at_xl_lg_rows(form, M, N, K, monkeypatch):
     """Default dispatch: every N here is a multiple of 256 on 400+ tiles, so the persistent kernels take all of them -- gemm_nt_v9 except
-    the GELU'-multiply data gradients, which gemm2.hip's nt_v7_preferred gives to gemm_nt_v7 (the dispatcher's own record)."""
+    the GELU'-multiply data gradients, which gemm_nt_dispatch.cpp's nt_v7_preferred gives to gemm_nt_v7 (the dispatcher's own record)."""
     monkeypatch.delenv("LNX_NT_V7", raising=False)
     monkeypatch.delenv("LNX_NT_V9", raising=False)
     kind = _check_form(form, M, N, K, rows_per_sample=199 if M == M_XL else 580)

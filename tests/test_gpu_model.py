@@ -752,7 +752,7 @@ def test_xl_b128_batch_invariance():
         print(f"[xl@224 B=128 / {dtype}] NT launches in the step: {d}")
         if dtype == "bf16":
             # stage 3, per block: qkv, proj, fc1, fc2 and the proj / fc1 / qkv data gradients on the persistent 256x256 kernel (N % 256 == 0, 400+
-            # tiles); the fc2 data gradient (multiply-by-GELU' epilogue) on the persistent 256x128 kernel (gemm2.hip: nt_v7_preferred)
+            # tiles); the fc2 data gradient (multiply-by-GELU' epilogue) on the persistent 256x128 kernel (gemm_nt_dispatch.cpp: nt_v7_preferred)
             assert d["V9"] >= 7 * n_rope3 and d["V7"] + d["V9"] >= 8 * n_rope3, d
             assert d["MX8"] == 0 and d["FP8"] == 0, d
         else:

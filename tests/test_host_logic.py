@@ -295,7 +295,7 @@ def test_counted_waits_match_the_compiled_store_counts():
 
 def test_design_dispatch_table_is_what_the_library_decides():
     """DESIGN.md's NT dispatch table (section 6) is generated from lnx_nt_dispatch -- the decision function
-    lnx_gemm_nt itself uses (gemm2.hip: nt_v2_family), callable without a GPU -- and this test regenerates it: a dispatch rule
+    lnx_gemm_nt itself uses (gemm_nt_dispatch.cpp: nt_choose), callable without a GPU -- and this test regenerates it: a dispatch rule
     that changes without the document fails here.  Spot checks pin the rules the parity tests rely on."""
     import importlib.util
 
@@ -312,3 +312,60 @@ def test_design_dispatch_table_is_what_the_library_decides():
     assert gen.query(256 * 199, 1536, 384, "fc1d") == L.NT_KERNEL_V9 and gen.query(256 * 199, 384, 384, "res_f32") == L.NT_KERNEL_V7
     assert gen.query(128 * 199, 1536, 384, "mul_aux") == L.NT_KERNEL_V7 and gen.query(128 * 199, 4096, 1024, "fc1d") == L.NT_KERNEL_V9
     assert gen.query(200, 1000, 768, "bias") == L.NT_KERNEL_SKINNY and gen.query(800, 384, 384, "plain") == L.NT_KERNEL_V1
+
+
+# lnx_nt_dispatch at the spot-check shapes (those of the test above, the product LNX_NT_V7=1 moves to the persistent 256x128 kernel by
+# default as well, and the smallest product LNX_NT_V9=1 gives the persistent 256x256 kernel) under each A/B switch of the dispatcher.  The
+# expected families were recorded from the library as it was before the decision moved into gemm_nt_dispatch.cpp: V1 = 1, V2 = 2,
+# skinny = 3, V4 = 4, V7 = 7, V9 = 9.
+NT_SWITCH_SHAPES = [(256 * 199, 1536, 384, "fc1d"), (256 * 199, 384, 384, "res_f32"), (128 * 199, 1536, 384, "mul_aux"), (128 * 199, 4096, 1024, "fc1d"),
+                    (200, 1000, 768, "bias"), (800, 384, 384, "plain"), (50944, 448, 384, "plain"), (1024, 256, 256, "bias")]
+NT_SWITCH_MATRIX = [
+    ({}, [9, 7, 7, 9, 3, 1, 7, 2]),
+    ({"LNX_NT_V7": "0"}, [9, 2, 2, 9, 3, 1, 2, 2]),
+    ({"LNX_NT_V7": "1"}, [9, 7, 7, 9, 3, 1, 7, 2]),
+    ({"LNX_NT_V9": "1", "LNX_NT_V7": "0"}, [9, 2, 9, 9, 3, 1, 2, 9]),
+    ({"LNX_NT_V9": "0"}, [4, 7, 7, 4, 3, 1, 7, 2]),
+    ({"LNX_NT_V4": "0"}, [2, 7, 7, 2, 3, 1, 7, 2]),
+    ({"LNX_GEMM_V1": "1"}, [1, 1, 1, 1, 1, 1, 1, 1]),
+    ({"LNX_NT_SKINNY": "0"}, [9, 7, 7, 9, 1, 1, 7, 2]),
+    ({"LNX_NT_GENERIC_EPI": "1"}, [2, 2, 2, 2, 3, 1, 2, 2]),
+]
+
+
+@pytest.mark.parametrize("setting,expected", NT_SWITCH_MATRIX, ids=[" ".join(f"{k}={v}" for k, v in s.items()) or "default" for s, _ in NT_SWITCH_MATRIX])
+def test_nt_dispatch_switch_matrix(setting, expected):
+    """Every A/B switch of the NT dispatcher (gemm_nt_dispatch.cpp: nt_switches) bends lnx_nt_dispatch the way it did before the
+    switches were gathered there.  Five of them are latched by the first call of a process, so each setting gets a fresh child."""
+    import json
+    import subprocess
+    import sys
+
+    from linnaeus_amd import _lib as L
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, 'tools'); import gen_dispatch_table as g;"
+            f"print(json.dumps([g.query(*s) for s in {NT_SWITCH_SHAPES}]))")
+    env = {k: v for k, v in os.environ.items() if not (k.startswith("LNX_NT_") or k in ("LNX_GEMM_V1", "LNX_CU_MARGIN"))}
+    env.update(setting)
+    out = subprocess.run([sys.executable, "-c", code], env=env, cwd=repo, check=True, capture_output=True, text=True, timeout=300).stdout
+    got = json.loads(out.strip().splitlines()[-1])
+    assert got == expected, (setting, got)
+    # what each switch promises, read off the recorded table
+    assert (L.NT_KERNEL_V1, L.NT_KERNEL_V2, L.NT_KERNEL_SKINNY, L.NT_KERNEL_V4, L.NT_KERNEL_V7, L.NT_KERNEL_V9) == (1, 2, 3, 4, 7, 9)
+    if setting.get("LNX_NT_V7") == "0":
+        assert L.NT_KERNEL_V7 not in got
+    if setting.get("LNX_NT_V7") == "1":
+        assert got[6] == L.NT_KERNEL_V7
+    if setting.get("LNX_NT_V9") == "1":
+        assert got[7] == L.NT_KERNEL_V9
+    if setting.get("LNX_NT_V9") == "0":
+        assert L.NT_KERNEL_V9 not in got and [g for g, d in zip(got, NT_SWITCH_MATRIX[0][1]) if d == L.NT_KERNEL_V9] == [L.NT_KERNEL_V4, L.NT_KERNEL_V4]
+    if "LNX_NT_V4" in setting:
+        assert L.NT_KERNEL_V4 not in got and L.NT_KERNEL_V9 not in got
+    if "LNX_GEMM_V1" in setting:
+        assert set(got) == {L.NT_KERNEL_V1}
+    if "LNX_NT_SKINNY" in setting:
+        assert L.NT_KERNEL_SKINNY not in got
+    if "LNX_NT_GENERIC_EPI" in setting:
+        assert all(g == L.NT_KERNEL_V2 for g, d in zip(got, NT_SWITCH_MATRIX[0][1]) if d in (2, 4, 7, 9))

@@ -14,7 +14,7 @@ namespace lnxg {
         asm volatile("ds_read_b128 %0, %1 offset:512" : "=v"(dst[2]) : "v"(a_) : "memory");             \
         asm volatile("ds_read_b128 %0, %1 offset:768" : "=v"(dst[3]) : "v"(a_) : "memory");             \
     } while (0)
-constexpr int BK4 = 32, ROWB4 = 64;  // 32-element K slices in 64-byte LDS rows, as gemm_nt_v4
+// (BK4 / ROWB4 of gemm_common.hpp: 32-element K slices in 64-byte LDS rows, as gemm_nt_v4)
 __device__ __forceinline__ int key4r(int row) { return (row & 16) ? 3 : 0; }
 
 // ------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// Registers the measurement kernels of tools/experiments/ with the product's NT dispatcher (gemm2.hip: g_nt_experiment).
+// Registers the measurement kernels of tools/experiments/ with the product's NT dispatcher (gemm_nt_dispatch.cpp: g_nt_experiment).
 // LNX_NT_V8=1 / LNX_NT_V5=1 (read per launch, so one process can compare) route every product the kernel can run through it.
 #include <cstdlib>
 

@@ -1,5 +1,5 @@
 """The NT dispatch table of DESIGN.md (between the dispatch-table markers), generated from the library's own decision function
-lnx_nt_dispatch (gemm2.hip: nt_v2_family) -- no GPU needed.  tests/test_host_logic.py regenerates it and compares with DESIGN.md.
+lnx_nt_dispatch (gemm_nt_dispatch.cpp: nt_choose) -- no GPU needed.  tests/test_host_logic.py regenerates it and compares with DESIGN.md.
 
     python tools/gen_dispatch_table.py            print the table
     python tools/gen_dispatch_table.py --write    replace the table in DESIGN.md"""
