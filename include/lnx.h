@@ -714,6 +714,55 @@ typedef struct lnx_gradnorm_args {
 int lnx_gradnorm_update(const lnx_gradnorm_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Validation metrics on the device: the per-batch bookkeeping of MetricsTracker._update_phase_batch
+ * (linnaeus/utils/metrics/tracker.py:609-937) and of utils/metrics/chain_accuracy.py:143-166,299-344 as ONE launch that only ADDS to
+ * two caller-owned, caller-zeroed device tables, int64 counts[] and double sums[]; nothing is read back, nothing is allocated.
+ * Tasks come in ascending rank order (the tracker's `_L<n>` sort), n_tasks <= LNX_SOFTCE_MAX_TASKS.
+ *   ordering   value descending, then index ascending; a NaN ranks above every number (torch.argmax / torch.topk).  A sample is
+ *              top-1 (top-3) right when fewer than 1 (3) entries of its row come before its target's; with C < 3 correct3 = correct1
+ *              (tracker.py:723-725).  A target outside [0, C) is never right.  Columns >= C of a padded row are never read.
+ *   null split is_null[b] != 0, or target[b] == 0 where is_null is NULL; the chain figures always use target != 0.
+ *   chain      every task right; partial_n: samples with some target != 0, partial_correct: those right on every task up to their
+ *              highest non-null rank.
+ *   subsets    per subset type s < 2 with subset_ids[s] != NULL: per task and bin, n and correct1; an id outside [0, n_bins[s])
+ *              adds 1 to LNX_METRICS_SUBSET_OOR + s and nothing else.
+ *   sums       per task with loss != NULL: loss[b] summed in double in a fixed order by one workgroup -- the same input gives the
+ *              same bits on every run; LNX_METRICS_LOSS_N counts the samples summed.
+ * counts layout (lnx_metrics_table_sizes gives the lengths):
+ *   [0, LNX_METRICS_HEAD)                         the per-batch counters LNX_METRICS_CHAIN_N ...
+ *   LNX_METRICS_TASK(t) + LNX_METRICS_N ...       the per-task counters
+ *   LNX_METRICS_SUBSET(n_tasks, n_bins0, s) + 2 * (t * n_bins[s] + bin) + {0: n, 1: correct1}
+ * sums layout: LNX_METRICS_SUM(t) + LNX_METRICS_SUM_LOSS ...
+ * -----------------------------------------------------------------------------------*/
+enum { LNX_METRICS_CHAIN_N = 0, LNX_METRICS_CHAIN_CORRECT, LNX_METRICS_PARTIAL_N, LNX_METRICS_PARTIAL_CORRECT, LNX_METRICS_SUBSET_OOR /* +s */,
+       LNX_METRICS_HEAD = 8 };
+enum { LNX_METRICS_N = 0, LNX_METRICS_CORRECT1, LNX_METRICS_CORRECT3, LNX_METRICS_NULL_N, LNX_METRICS_NULL_CORRECT1, LNX_METRICS_NONNULL_N,
+       LNX_METRICS_NONNULL_CORRECT1, LNX_METRICS_LOSS_N, LNX_METRICS_TASK_STRIDE = 8 };
+enum { LNX_METRICS_SUM_LOSS = 0, LNX_METRICS_SUM_NULL_LOSS, LNX_METRICS_SUM_NONNULL_LOSS, LNX_METRICS_SUM_STRIDE = 4 };
+#define LNX_METRICS_TASK(t) (LNX_METRICS_HEAD + LNX_METRICS_TASK_STRIDE * (t))
+#define LNX_METRICS_SUBSET(n_tasks, n_bins0, s) (LNX_METRICS_TASK(n_tasks) + ((s) ? 2 * (int64_t)(n_tasks) * (n_bins0) : 0))
+#define LNX_METRICS_SUM(t) (LNX_METRICS_SUM_STRIDE * (t))
+typedef struct lnx_metrics_task {
+    const void* logits;           /* [B, ld] of the args' dtype */
+    int64_t ld;                   /* >= C */
+    const int64_t* target;        /* [B] class indices */
+    const unsigned char* is_null; /* [B] or NULL (= target == 0) */
+    const float* loss;            /* [B] per-sample losses or NULL */
+    int C;
+} lnx_metrics_task;
+typedef struct lnx_metrics_args {
+    int dtype; /* of every task's logits: 0 = fp32, 1 = bf16 */
+    int B, n_tasks;
+    lnx_metrics_task task[LNX_SOFTCE_MAX_TASKS];
+    const int64_t* subset_ids[2]; /* [B] each, or NULL */
+    int n_bins[2];                /* 0 where subset_ids[s] is NULL */
+    int64_t* counts;
+    double* sums;
+} lnx_metrics_args;
+int lnx_metrics_table_sizes(int n_tasks, int n_bins0, int n_bins1, int64_t* n_counts, int64_t* n_sums);
+int lnx_metrics_update(const lnx_metrics_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP branch (bf16 storage, C in {32,64,96,128,192}):
  *   out = x + rowscale * gamma * (GELU(ln . W1^T + b1) . W2^T + b2)
  * = pwconv1 -> GELU -> pwconv2 -> LayerScale -> DropPath -> residual (blocks/convnext.py:79-86)

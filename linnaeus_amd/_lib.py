@@ -95,6 +95,33 @@ class GradNormArgs(C.Structure):  # == lnx_gradnorm_args
                 ("weights", C.c_void_p), ("initial_losses", C.c_void_p), ("initted", C.c_void_p), ("metrics", C.c_void_p)]
 
 
+METRICS_MAX_TASKS = 8  # == LNX_SOFTCE_MAX_TASKS
+# offsets into the counts / sums tables of lnx_metrics_update (the LNX_METRICS_* enums of include/lnx.h)
+METRICS_CHAIN_N, METRICS_CHAIN_CORRECT, METRICS_PARTIAL_N, METRICS_PARTIAL_CORRECT, METRICS_SUBSET_OOR = range(5)
+METRICS_HEAD = 8
+METRICS_N, METRICS_CORRECT1, METRICS_CORRECT3, METRICS_NULL_N, METRICS_NULL_CORRECT1, METRICS_NONNULL_N, METRICS_NONNULL_CORRECT1, METRICS_LOSS_N = range(8)
+METRICS_TASK_STRIDE = 8
+METRICS_SUM_LOSS, METRICS_SUM_NULL_LOSS, METRICS_SUM_NONNULL_LOSS = range(3)
+METRICS_SUM_STRIDE = 4
+
+
+def metrics_task(t: int) -> int:  # == LNX_METRICS_TASK
+    return METRICS_HEAD + METRICS_TASK_STRIDE * t
+
+
+def metrics_subset(n_tasks: int, n_bins0: int, s: int) -> int:  # == LNX_METRICS_SUBSET
+    return metrics_task(n_tasks) + (2 * n_tasks * n_bins0 if s else 0)
+
+
+class MetricsTask(C.Structure):  # == lnx_metrics_task
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("target", C.c_void_p), ("is_null", C.c_void_p), ("loss", C.c_void_p), ("C", C.c_int)]
+
+
+class MetricsArgs(C.Structure):  # == lnx_metrics_args
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("n_tasks", C.c_int), ("task", MetricsTask * METRICS_MAX_TASKS),
+                ("subset_ids", C.c_void_p * 2), ("n_bins", C.c_int * 2), ("counts", C.c_void_p), ("sums", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -116,6 +143,9 @@ def lib() -> C.CDLL:
             _lib.lnx_ademamix_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(AdEMAMixHyper), C.c_void_p, C.c_float, C.c_void_p]
         if hasattr(_lib, "lnx_gradnorm_sumsq"):
             _lib.lnx_gradnorm_sumsq.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(_lib, "lnx_metrics_update"):
+            _lib.lnx_metrics_update.argtypes = [C.POINTER(MetricsArgs), C.c_void_p]
+            _lib.lnx_metrics_table_sizes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         # A/B runs against an OLDER build (LNX_LIB_PATH=... LNX_LIB_OLDER=1): entry points added since are allowed to be missing; calling
         # one then fails with ctypes' AttributeError
         older = bool(os.environ.get("LNX_LIB_PATH")) and os.environ.get("LNX_LIB_OLDER") == "1"
@@ -148,6 +178,7 @@ EXPORTS = [
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
+    "lnx_metrics_table_sizes", "lnx_metrics_update",
     "lnx_mix_rows", "lnx_mix_meta",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",

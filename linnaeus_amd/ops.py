@@ -443,3 +443,48 @@ def meta_heads_bwd(g, heads, saved, grads):
         keep += [w1t, w2t, part] + dp
     L.check(L.lib().lnx_meta_heads_bwd(arr, len(heads), _stream()), "lnx_meta_heads_bwd")
     torch.cuda.current_stream().synchronize()  # (the scratch tensors above die with this frame)
+
+
+def metrics_table_sizes(n_tasks: int, n_bins0: int = 0, n_bins1: int = 0) -> Tuple[int, int]:
+    """Lengths of the int64 counts / double sums tables of metrics_update (lnx_metrics_table_sizes)."""
+    nc, ns = C.c_int64(), C.c_int64()
+    L.check(L.lib().lnx_metrics_table_sizes(n_tasks, n_bins0, n_bins1, C.byref(nc), C.byref(ns)), "lnx_metrics_table_sizes")
+    return nc.value, ns.value
+
+
+def metrics_update(logits, targets, counts, sums, *, num_classes=None, is_null=None, losses=None, subset_ids=(), n_bins=()):
+    """One lnx_metrics_update launch: ADDS a batch's counters to counts (int64) / sums (float64).  logits: per task [B, >= C] rows of one
+    dtype (fp32 / bf16) with unit column stride (padded views welcome: stride(0) is the ld), tasks in ascending rank order; targets: per
+    task int64 [B]; num_classes: per task C (default: the logits' width); is_null / losses: per task uint8 [B] / fp32 [B] or None;
+    subset_ids: up to two int64 [B] with their n_bins."""
+    T = len(logits)
+    if not 1 <= T <= L.METRICS_MAX_TASKS or len(targets) != T:
+        raise L.LnxError(f"metrics_update: {T} tasks (1..{L.METRICS_MAX_TASKS}), {len(targets)} targets")
+    a = L.MetricsArgs()
+    a.dtype, a.B, a.n_tasks = code_of(logits[0]), logits[0].shape[0], T
+    for t in range(T):
+        x, tg = logits[t], targets[t]
+        nul = is_null[t] if is_null is not None else None
+        ls = losses[t] if losses is not None else None
+        if x.dim() != 2 or x.shape[0] != a.B or code_of(x) != a.dtype or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise L.LnxError(f"metrics_update: task {t} logits must be [B, C] rows of one dtype with unit column stride, got {tuple(x.shape)} {x.dtype} strides {x.stride()}")
+        if tg.dtype != torch.int64 or tg.shape != (a.B,) or not tg.is_contiguous():
+            raise L.LnxError(f"metrics_update: task {t} target must be contiguous int64 [B]")
+        if nul is not None and (nul.dtype not in (torch.uint8, torch.bool) or nul.shape != (a.B,) or not nul.is_contiguous()):
+            raise L.LnxError(f"metrics_update: task {t} is_null must be contiguous uint8 / bool [B]")
+        if ls is not None and (ls.dtype != torch.float32 or ls.shape != (a.B,) or not ls.is_contiguous()):
+            raise L.LnxError(f"metrics_update: task {t} loss must be contiguous fp32 [B]")
+        k = a.task[t]
+        k.logits, k.ld, k.C = _p(x), (x.stride(0) if a.B > 1 else x.shape[1]), (num_classes[t] if num_classes is not None else x.shape[1])
+        k.target, k.is_null, k.loss = _p(tg), _p(nul), _p(ls)
+    for s, (ids, nb) in enumerate(zip(subset_ids, n_bins)):
+        if ids is None:
+            continue
+        if ids.dtype != torch.int64 or ids.shape != (a.B,) or not ids.is_contiguous():
+            raise L.LnxError(f"metrics_update: subset ids {s} must be contiguous int64 [B]")
+        a.subset_ids[s], a.n_bins[s] = ids.data_ptr(), nb
+    nc, ns = metrics_table_sizes(T, a.n_bins[0], a.n_bins[1])
+    if counts.dtype != torch.int64 or sums.dtype != torch.float64 or counts.numel() < nc or sums.numel() < ns or not (counts.is_contiguous() and sums.is_contiguous()):
+        raise L.LnxError(f"metrics_update: tables must be contiguous int64 [>= {nc}] / float64 [>= {ns}]")
+    a.counts, a.sums = _p(counts), _p(sums)
+    L.check(L.lib().lnx_metrics_update(C.byref(a), _stream()), "lnx_metrics_update")
