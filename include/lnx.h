@@ -303,7 +303,26 @@ int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* args, void* stream);
  * qkv is the raw output of the qkv Linear, [B*N, 3*C] with column = which*C + head*D + d
  * (:432-437); o is [B*N, C] with column = head*D + d (:501).  The first E tokens of each
  * sample are extra (CLS/meta) tokens and are not scaled by cos.
+ *
+ * rope_mode (every struct below carries one; 0 = what the reference computes today, so callers that zero their structs are unchanged):
+ *   LNX_ROPE_COS     the pairs (x[2j], x[2j+1]) of the image tokens of q and k are multiplied by cos(theta): the reference as it runs,
+ *                    whose _get_current_freqs_cis casts the complex table to float32 and drops the imaginary part (finding F1);
+ *   LNX_ROPE_ROTATE  the rotation the reference's helpers define when they are handed the complex table itself -- compute_mixed_cis'
+ *                    polar(1, theta) (rope_2d_mhsa.py:114-155) through apply_rotary_emb's view_as_complex product (:176-218):
+ *                        x'[2j]   = x[2j] cos(theta) - x[2j+1] sin(theta)
+ *                        x'[2j+1] = x[2j] sin(theta) + x[2j+1] cos(theta)          x in {q, k}
+ *                    with theta[n,h,j] = t_x freqs[0,h,j] + t_y freqs[1,h,j], t_x = n % W, t_y = n / W over the N - E image tokens;
+ *                    v and the E extra tokens are untouched, q is then scaled by D^-0.5 (:456) as in the cos mode.  The rotation is
+ *                    applied where the cos multiply is: in the operand loaders, from the raw qkv rows, in fp32, rounded once to the
+ *                    storage type -- no pre-pass over qkv, no extra activation tensor.  Backward:
+ *                        dx[2j]   =  dx'[2j] cos(theta) + dx'[2j+1] sin(theta)
+ *                        dx[2j+1] = -dx'[2j] sin(theta) + dx'[2j+1] cos(theta)
+ *                        dtheta[n,h,j] = sum_b sum_{x in {q,k}} (dx'[2j+1] x'[2j] - dx'[2j] x'[2j+1])      (x' and dx' both after q's scale)
+ *                        dfreqs[0,h,j] += sum_n t_x dtheta[n,h,j],   dfreqs[1,h,j] += sum_n t_y dtheta[n,h,j]
+ *                    The backward takes t_x, t_y from the token index and grid_w (no d-cos table).  Same kernel families, same
+ *                    dispatch (lnx_attn_dispatch does not look at the mode), same freq_ws size, same deferred fold.
  * -----------------------------------------------------------------------------------*/
+enum { LNX_ROPE_COS = 0, LNX_ROPE_ROTATE = 1 };
 /* head_dim 64 */
 int lnx_rope_cos_table(const float* freqs /* [2,heads,32] */, int heads, int H, int W, float* cos_out /* [H*W,heads,32] */,
                        float* dsin_out /* optional [2][H*W,heads,32]: -t_x sin(theta), -t_y sin(theta) = d cos(theta) / d freqs[a] (what
@@ -311,6 +330,10 @@ int lnx_rope_cos_table(const float* freqs /* [2,heads,32] */, int heads, int H, 
                        void* stream);
 /* any supported head_dim D: freqs [2,heads,D/2], cos_out [H*W,heads,D/2], dsin_out optional [2][H*W,heads,D/2] */
 int lnx_rope_cos_table_hd(const float* freqs, int heads, int head_dim, int H, int W, float* cos_out, float* dsin_out, void* stream);
+/* lnx_rope_cos_table_hd with the optional sin table of LNX_ROPE_ROTATE: sin_out [H*W,heads,D/2] = sin(theta), the cos table's layout
+ * (entry (n * heads + h) * D/2 + j), from the same fp32 angle; NULL = lnx_rope_cos_table_hd.  dsin_out stays optional (the rotate
+ * backward does not read it). */
+int lnx_rope_cossin_table_hd(const float* freqs, int heads, int head_dim, int H, int W, float* cos_out, float* sin_out, float* dsin_out, void* stream);
 /* The same tables for several blocks in one launch (each RoPE block owns its freqs, rope_2d_mhsa.py:397-408; a plan fills the
  * tables of all its blocks once per forward, off the main stream).  Entries as lnx_rope_cos_table_hd's arguments; one launch per
  * head_dim present. */
@@ -321,6 +344,8 @@ typedef struct {
     float* dsin_out;    /* optional [2][H*W,heads,D/2] */
     int heads, H, W;
     int head_dim;       /* D; 0 = 64 */
+    int rope_mode;      /* LNX_ROPE_COS (0) or LNX_ROPE_ROTATE: the latter needs sin_out */
+    float* sin_out;     /* optional (required with LNX_ROPE_ROTATE) [H*W,heads,D/2]: sin(theta), laid out like cos_out */
 } lnx_rope_table;
 int lnx_rope_cos_tables(const lnx_rope_table* tables, int n, void* stream);
 /* floats of lnx_attn_bwd's freqs-gradient workspace (one [2][D/2] partial per workgroup of its finest tiling): head_dim 64, and any
@@ -341,6 +366,9 @@ typedef struct lnx_attn_args {
                                        Runs the 64-row tiled kernels (the dropout-free path keeps its own instantiations). */
     float drop_inv_keep; /* 1 / (1 - ATTN_DROP_RATE) */
     int head_dim;        /* D: 32, 64 or 128; 0 = 64 */
+    int rope_mode;       /* LNX_ROPE_COS (0) or LNX_ROPE_ROTATE */
+    const float* sin_tab;/* LNX_ROPE_ROTATE: [(N-E), heads, D/2] sin(theta), the layout of cos_tab (lnx_rope_cossin_table_hd /
+                            lnx_rope_table.sin_out); not read in the cos mode */
 } lnx_attn_args;
 int lnx_attn_fwd(const lnx_attn_args* args, void* stream);
 
@@ -366,6 +394,10 @@ typedef struct lnx_attn_bwd_args {
                               this thread on this stream; freq_ws and dfreqs must stay untouched and alive until then -- a plan gives every
                               pending call its own freq_ws region and flushes at the end of each backward segment) */
     int head_dim;          /* D: 32, 64 or 128; 0 = 64 */
+    int rope_mode;         /* LNX_ROPE_COS (0) or LNX_ROPE_ROTATE; the mode of the forward that produced o and lse */
+    const float* sin_tab;  /* LNX_ROPE_ROTATE: the forward's sin table [(N-E), heads, D/2]; dsin_tab is then not read (may be NULL) */
+    int grid_w;            /* LNX_ROPE_ROTATE: width W of the token grid the tables were built for ((N-E) = H * W): the kernels weight
+                              dtheta of image token n by t_x = n % W and t_y = n / W; not read in the cos mode */
 } lnx_attn_bwd_args;
 #define LNX_ATTN_DEFER_MAX 16
 int lnx_attn_bwd_flush(void* stream); /* folds every postponed call of this thread; refuses a stream other than theirs */
@@ -877,6 +909,10 @@ typedef struct lnx_mformer_cfg {
                                   writes beside its bf16 output -- measured: +1 % speed at xl for a quarter more gradient
                                   error, so off by default).  Needs RoPE dims and MLP widths that are multiples
                                   of 128. */
+    int rope_mode;             /* LNX_ROPE_COS (0, the reference as it runs) or LNX_ROPE_ROTATE (MODEL.ROPE_STAGES.ROPE_ROTATE): every RoPE
+                                  block's attention rotates q and k (see lnx_attn_args.rope_mode) in the forward, the backward and a
+                                  recompute plan's re-forward; the one-launch table fill writes cos and sin tables (the sin table takes
+                                  the place of the d-cos table in the workspace).  Parameters, their order and shapes do not change. */
 } lnx_mformer_cfg;
 
 typedef struct lnx_plan lnx_plan;

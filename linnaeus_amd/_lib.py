@@ -167,6 +167,10 @@ AUG_CLAMP, AUG_POSTERIZE, AUG_SOLARIZE, AUG_SOLARIZE_ADD, AUG_INVERT, AUG_BRIGHT
 NT_KERNEL_NONE, NT_KERNEL_V1, NT_KERNEL_V2, NT_KERNEL_SKINNY, NT_KERNEL_V4, NT_KERNEL_FP8, NT_KERNEL_V7, NT_KERNEL_MX8, NT_KERNEL_V9, NT_KERNEL_EXPERIMENT = 0, 1, 2, 3, 4, 6, 7, 8, 9, 15
 
 # lnx_attn_dispatch / lnx_last_attn_kernel families (include/lnx.h)
+# rope_mode of the attention structs, the table entries and lnx_mformer_cfg (include/lnx.h): cos-only scaling (the reference as it
+# runs, finding F1) or the true pair rotation
+ROPE_COS, ROPE_ROTATE = 0, 1
+
 ATTN_KERNEL_NONE, ATTN_KERNEL_RES4, ATTN_KERNEL_RES8, ATTN_KERNEL_TILED4, ATTN_KERNEL_TILED8 = range(5)
 
 # every symbol include/lnx.h declares (kept in sync by tests/test_abi.py)
@@ -175,7 +179,7 @@ EXPORTS = [
     "lnx_gemm_nt", "lnx_last_nt_kernel", "lnx_nt_kernel_launches", "lnx_nt_dispatch", "lnx_gemm_tn", "lnx_gemm_tn_flush", "lnx_gemm_tn_discard", "lnx_amax", "lnx_quantize_fp8", "lnx_gemm_nt_fp8", "lnx_quantize_mxfp8", "lnx_gemm_nt_mxfp8", "lnx_dropout_mul", "lnx_dropout_residual", "lnx_plan_dropout_bytes", "lnx_plan_set_dropout", "lnx_plan_attn_dropout_bytes", "lnx_plan_set_attn_dropout",
     "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard",
     "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad",
-    "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel",
+    "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update",
@@ -248,6 +252,7 @@ class RopeTable(C.Structure):
     _fields_ = [
         ("freqs", C.c_void_p), ("cos_out", C.c_void_p), ("dsin_out", C.c_void_p),
         ("heads", C.c_int), ("H", C.c_int), ("W", C.c_int), ("head_dim", C.c_int),
+        ("rope_mode", C.c_int), ("sin_out", C.c_void_p),
     ]
 
 
@@ -272,6 +277,7 @@ class AttnArgs(C.Structure):
         ("dtype", C.c_int), ("B", C.c_int), ("N", C.c_int), ("E", C.c_int), ("heads", C.c_int),
         ("qkv", C.c_void_p), ("cos_tab", C.c_void_p), ("o", C.c_void_p), ("lse", C.c_void_p),
         ("drop_mask", C.c_void_p), ("drop_inv_keep", C.c_float), ("head_dim", C.c_int),
+        ("rope_mode", C.c_int), ("sin_tab", C.c_void_p),
     ]
 
 
@@ -282,6 +288,7 @@ class AttnBwdArgs(C.Structure):
         ("d_o", C.c_void_p), ("dqkv", C.c_void_p), ("freq_ws", C.c_void_p), ("delta", C.c_void_p),
         ("drop_mask", C.c_void_p), ("drop_inv_keep", C.c_float),
         ("dsin_tab", C.c_void_p), ("dfreqs", C.c_void_p), ("defer_freqs", C.c_int), ("head_dim", C.c_int),
+        ("rope_mode", C.c_int), ("sin_tab", C.c_void_p), ("grid_w", C.c_int),
     ]
 
 

@@ -3,6 +3,8 @@
 // Reference: RoPE2DAttention.forward, standard path (blocks/rope_2d_mhsa.py:422-505):
 //   q,k image tokens scaled pairwise by cos(theta) (:176-218, finding F1), q *= d^-0.5
 //   (:456), S = q k^T in fp32 (:495), softmax (:496), O = P v (:498), O laid out [B,N,h*d].
+// Opt-in (rope_mode = LNX_ROPE_ROTATE, template parameter ROT below): the pair rotation by theta that apply_rotary_emb (:176-218)
+// computes from the complex table of compute_mixed_cis (:114-155), in the same places as the cos multiply.
 // head_dim (HD) is 32, 64 or 128: 64 in every shipped config, and the only one the resident kernels take (the tiled kernels,
 // the tables and the freqs fold are templated on it).  N is small (52..580), so the whole problem of a (batch, head) pair is a
 // few 64-key tiles; parallelism comes from batch x heads x q-tiles.
@@ -71,10 +73,15 @@ __device__ __forceinline__ uint2 tr_read(const unsigned char* p) {
 // batch before the first use: fetch() is unconditional (a row beyond N reads row N - 1, a class token reads the first
 // cos row) -- a load under `if (n < N)` whose result is merged with a zero is waited for on the spot, which turns a
 // staging loop into one memory round trip per chunk.
-template <typename T, bool COS, int HD = 64> struct Chunk {
+// ROT (with COS; LNX_ROPE_ROTATE): the pairs are rotated by theta instead -- the sin table, laid out like the cos table, is fetched
+// beside it and value() applies x'[2j] = x[2j] cos - x[2j+1] sin, x'[2j+1] = x[2j] sin + x[2j+1] cos in fp32 before the one rounding.
+template <typename T, bool COS, int HD = 64, bool ROT = false> struct Chunk {
+    static_assert(COS || !ROT, "a rotated operand is a RoPE operand");
     uint4 raw;
     float cf[COS ? TT<T>::EPV / 2 : 1];
-    __device__ __forceinline__ void fetch(const T* __restrict__ base, int64_t ld, int n, int N, int E, int d0, const float* __restrict__ cos_tab, int heads, int head) {
+    float sf[ROT ? TT<T>::EPV / 2 : 1];
+    __device__ __forceinline__ void fetch(const T* __restrict__ base, int64_t ld, int n, int N, int E, int d0, const float* __restrict__ cos_tab, int heads, int head,
+                                          const float* __restrict__ sin_tab = nullptr) {
         const int nc = min(n, N - 1);
         raw = ld16(base + (int64_t)nc * ld + d0);
         if constexpr (COS) {
@@ -87,12 +94,35 @@ template <typename T, bool COS, int HD = 64> struct Chunk {
                 cf[0] = c2.x; cf[1] = c2.y;
             }
         }
+        if constexpr (ROT) {
+            const float* sp = sin_tab + ((int64_t)max(nc - E, 0) * heads + head) * (HD / 2) + (d0 >> 1);
+            if constexpr (TT<T>::EPV == 8) {
+                const float4 s4 = *reinterpret_cast<const float4*>(sp);
+                sf[0] = s4.x; sf[1] = s4.y; sf[2] = s4.z; sf[3] = s4.w;
+            } else {
+                const float2 s2 = *reinterpret_cast<const float2*>(sp);
+                sf[0] = s2.x; sf[1] = s2.y;
+            }
+        }
     }
     __device__ __forceinline__ uint4 value(int n, int N, int E, float scale) const {
         if (n >= N) return make_uint4(0, 0, 0, 0);
         Vec16<T> v;
         v.raw = raw;
-        if constexpr (COS) {
+        if constexpr (ROT) {
+            constexpr int EPV = TT<T>::EPV;
+            if (n >= E) {
+#pragma unroll
+                for (int j = 0; j < EPV; j += 2) {
+                    const float a = v.get(j), b = v.get(j + 1), c = cf[j >> 1], sn = sf[j >> 1];
+                    v.set(j, (a * c - b * sn) * scale);
+                    v.set(j + 1, (a * sn + b * c) * scale);
+                }
+            } else if (scale != 1.0f) {
+#pragma unroll
+                for (int j = 0; j < EPV; ++j) v.set(j, v.get(j) * scale);
+            }
+        } else if constexpr (COS) {
             constexpr int EPV = TT<T>::EPV;
             if (n >= E) {
 #pragma unroll
@@ -131,17 +161,18 @@ __device__ __forceinline__ void stage_tile(unsigned char* rowimg, unsigned char*
 // The same staging split in two, for the tiled kernels' software pipeline: fetch() requests a 64-row tile into registers
 // (unconditional, clamped rows -- call it for min(next, last) rather than under `if (more)`), commit() writes it to the LDS
 // images one loop trip later, after the products of the current tile have been issued in between.
-template <typename T, bool COS, int NT, int HD = 64>
+template <typename T, bool COS, int NT, int HD = 64, bool ROT = false>
 struct TileFetch {
     using A = AT<T, HD>;
     static constexpr int NCH = A::NCH, EPV = A::EPV, PER = BT * NCH / NT;
     static_assert(PER > 0 && PER * NT == BT * NCH, "a tile's chunks split evenly over the workgroup");
-    Chunk<T, COS, HD> ch[PER];
-    __device__ __forceinline__ void fetch(const T* __restrict__ base, int64_t ld, int n0, int N, int E, const float* __restrict__ cos_tab, int heads, int head) {
+    Chunk<T, COS, HD, ROT> ch[PER];
+    __device__ __forceinline__ void fetch(const T* __restrict__ base, int64_t ld, int n0, int N, int E, const float* __restrict__ cos_tab, int heads, int head,
+                                          const float* __restrict__ sin_tab = nullptr) {
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int i = threadIdx.x + u * NT;
-            ch[u].fetch(base, ld, n0 + i / NCH, N, E, (i % NCH) * EPV, cos_tab, heads, head);
+            ch[u].fetch(base, ld, n0 + i / NCH, N, E, (i % NCH) * EPV, cos_tab, heads, head, sin_tab);
         }
     }
     template <bool ROWIMG, bool TRIMG>
@@ -158,12 +189,12 @@ struct TileFetch {
 };
 
 // fragment of a row operand held in registers: lane (s, g) <- token row, chunks kk*4 + g
-template <typename T, bool COS, int HD = 64>
+template <typename T, bool COS, int HD = 64, bool ROT = false>
 __device__ __forceinline__ void load_row_frag(uint4 (&f)[(AT<T, HD>::NKK)], const T* __restrict__ base, int64_t ld, int n, int N, int E, int g,
-                                              const float* __restrict__ cos_tab, int heads, int head, float scale) {
-    Chunk<T, COS, HD> c[(AT<T, HD>::NKK)];
+                                              const float* __restrict__ cos_tab, int heads, int head, float scale, const float* __restrict__ sin_tab = nullptr) {
+    Chunk<T, COS, HD, ROT> c[(AT<T, HD>::NKK)];
 #pragma unroll
-    for (int kk = 0; kk < AT<T, HD>::NKK; ++kk) c[kk].fetch(base, ld, n, N, E, (kk * 4 + g) * AT<T, HD>::EPV, cos_tab, heads, head);
+    for (int kk = 0; kk < AT<T, HD>::NKK; ++kk) c[kk].fetch(base, ld, n, N, E, (kk * 4 + g) * AT<T, HD>::EPV, cos_tab, heads, head, sin_tab);
 #pragma unroll
     for (int kk = 0; kk < AT<T, HD>::NKK; ++kk) f[kk] = c[kk].value(n, N, E, scale);
 }
@@ -485,11 +516,15 @@ struct AttnP {
     const unsigned char* amask = nullptr;  // DROP kernels: keep mask [B, heads, N, Np] of the attention probabilities
     float a_inv_keep = 1.0f;
     int Np = 0;                            // N rounded up to a multiple of 64
+    const float* sin_tab = nullptr;        // ROT kernels: sin(theta), laid out like cos_tab
+    int W = 1;                             // ROT backward: width of the token grid (t_x = n % W, t_y = n / W of image token n)
 };
 
 // dk / dv epilogue of one 16-key wave tile: every load in one batch (clamped rows, unconditional), 8-/16-byte stores, the k part
 // of the freqs gradient.  Shared by the resident and the tiled kernel.
-template <typename T, int HD = 64>
+// ROT: dk comes back through the inverse rotation, and the pair gradient is d theta = dk'[2j+1] k'[2j] - dk'[2j] k'[2j+1] (k' = the rotated
+// k, recomputed in fp32 from the raw row), weighted by t_x, t_y (from the token index and the grid width) instead of the d-cos table.
+template <typename T, int HD = 64, bool ROT = false>
 __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)[HD / 16], const f32x4_t (&dv)[HD / 16], const T* __restrict__ kb, int64_t ld, int C,
                                              int b, int head, int key, int s, int g, float* fl) {
     const int kc = min(key, p.N - 1);
@@ -499,6 +534,7 @@ __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)
     const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * (HD / 2);
     constexpr int ND = HD / 16;
     float kr[ND][4], cr[ND][2], gp[ND][2], dx[ND][2], dy[ND][2];
+    float sr[ROT ? ND : 1][2];
     const bool rope = p.E < p.N;  // uniform: without image tokens there are no tables
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) {
@@ -514,7 +550,17 @@ __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)
         }
         cr[dt][0] = cr[dt][1] = 1.0f;
         dx[dt][0] = dx[dt][1] = dy[dt][0] = dy[dt][1] = 0.f;
-        if (rope) {
+        if constexpr (ROT) {
+            sr[dt][0] = sr[dt][1] = 0.f;
+            if (rope) {
+                const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
+                const float2 s2 = *reinterpret_cast<const float2*>(p.sin_tab + ((int64_t)max(kc - p.E, 0) * p.heads + head) * (HD / 2) + (d0 >> 1));
+                cr[dt][0] = c2.x; cr[dt][1] = c2.y;
+                sr[dt][0] = s2.x; sr[dt][1] = s2.y;
+                dx[dt][0] = dx[dt][1] = (float)(max(kc - p.E, 0) % p.W);
+                dy[dt][0] = dy[dt][1] = (float)(max(kc - p.E, 0) / p.W);
+            }
+        } else if (rope) {
             const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
             cr[dt][0] = c2.x; cr[dt][1] = c2.y;
             const float2 a2 = *reinterpret_cast<const float2*>(sxp + (d0 >> 1));
@@ -530,6 +576,16 @@ __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) {
             const float c0 = img ? cr[dt][0] : 1.0f, c1 = img ? cr[dt][1] : 1.0f;
+            if constexpr (ROT) {
+                const float s0 = img ? sr[dt][0] : 0.f, s1 = img ? sr[dt][1] : 0.f;
+                ok[dt][0] = dk[dt][0] * c0 + dk[dt][1] * s0; ok[dt][1] = dk[dt][1] * c0 - dk[dt][0] * s0;
+                ok[dt][2] = dk[dt][2] * c1 + dk[dt][3] * s1; ok[dt][3] = dk[dt][3] * c1 - dk[dt][2] * s1;
+                const float x0 = kr[dt][0] * c0 - kr[dt][1] * s0, x1 = kr[dt][0] * s0 + kr[dt][1] * c0;
+                const float x2 = kr[dt][2] * c1 - kr[dt][3] * s1, x3 = kr[dt][2] * s1 + kr[dt][3] * c1;
+                gp[dt][0] = img ? dk[dt][1] * x0 - dk[dt][0] * x1 : 0.f;
+                gp[dt][1] = img ? dk[dt][3] * x2 - dk[dt][2] * x3 : 0.f;
+                continue;
+            }
             ok[dt][0] = dk[dt][0] * c0; ok[dt][1] = dk[dt][1] * c0; ok[dt][2] = dk[dt][2] * c1; ok[dt][3] = dk[dt][3] * c1;
             gp[dt][0] = img ? dk[dt][0] * kr[dt][0] + dk[dt][1] * kr[dt][1] : 0.f;
             gp[dt][1] = img ? dk[dt][2] * kr[dt][2] + dk[dt][3] * kr[dt][3] : 0.f;
@@ -547,7 +603,7 @@ __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)
     if (rope) freq_accum<HD>(fl, gp, dx, dy, s, g);
 }
 // dq epilogue of one 16-query wave tile (the tiled kernel; the resident one fetches its operands ahead of the key loop)
-template <typename T, int HD = 64>
+template <typename T, int HD = 64, bool ROT = false>
 __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[HD / 16], const T* __restrict__ qb, int64_t ld, int b, int head, int q, int s, int g,
                                             float scale, float* fl) {
     const int qc = min(q, p.N - 1);
@@ -557,6 +613,7 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
     const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * (HD / 2);
     constexpr int ND = HD / 16;
     float qr[ND][4], cr[ND][2], gp[ND][2], dx[ND][2], dy[ND][2];
+    float sr[ROT ? ND : 1][2];
     const bool rope = p.E < p.N;
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) {
@@ -572,7 +629,17 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
         }
         cr[dt][0] = cr[dt][1] = 1.0f;
         dx[dt][0] = dx[dt][1] = dy[dt][0] = dy[dt][1] = 0.f;
-        if (rope) {
+        if constexpr (ROT) {
+            sr[dt][0] = sr[dt][1] = 0.f;
+            if (rope) {
+                const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
+                const float2 s2 = *reinterpret_cast<const float2*>(p.sin_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * (HD / 2) + (d0 >> 1));
+                cr[dt][0] = c2.x; cr[dt][1] = c2.y;
+                sr[dt][0] = s2.x; sr[dt][1] = s2.y;
+                dx[dt][0] = dx[dt][1] = (float)(max(qc - p.E, 0) % p.W);
+                dy[dt][0] = dy[dt][1] = (float)(max(qc - p.E, 0) / p.W);
+            }
+        } else if (rope) {
             const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
             cr[dt][0] = c2.x; cr[dt][1] = c2.y;
             const float2 a2 = *reinterpret_cast<const float2*>(sxp + (d0 >> 1));
@@ -586,6 +653,16 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
     float oq[ND][4];
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) {
+        if constexpr (ROT) {  // dq is the gradient of q~ = scale q': inverse rotation, d theta = dq~[2j+1] q~[2j] - dq~[2j] q~[2j+1]
+            const float s0 = img ? sr[dt][0] : 0.f, s1 = img ? sr[dt][1] : 0.f, r0 = img ? cr[dt][0] : 1.0f, r1 = img ? cr[dt][1] : 1.0f;
+            oq[dt][0] = scale * (dq[dt][0] * r0 + dq[dt][1] * s0); oq[dt][1] = scale * (dq[dt][1] * r0 - dq[dt][0] * s0);
+            oq[dt][2] = scale * (dq[dt][2] * r1 + dq[dt][3] * s1); oq[dt][3] = scale * (dq[dt][3] * r1 - dq[dt][2] * s1);
+            const float x0 = qr[dt][0] * r0 - qr[dt][1] * s0, x1 = qr[dt][0] * s0 + qr[dt][1] * r0;
+            const float x2 = qr[dt][2] * r1 - qr[dt][3] * s1, x3 = qr[dt][2] * s1 + qr[dt][3] * r1;
+            gp[dt][0] = img ? scale * (dq[dt][1] * x0 - dq[dt][0] * x1) : 0.f;
+            gp[dt][1] = img ? scale * (dq[dt][3] * x2 - dq[dt][2] * x3) : 0.f;
+            continue;
+        }
         const float c0 = img ? cr[dt][0] * scale : scale, c1 = img ? cr[dt][1] * scale : scale;
         oq[dt][0] = dq[dt][0] * c0; oq[dt][1] = dq[dt][1] * c0; oq[dt][2] = dq[dt][2] * c1; oq[dt][3] = dq[dt][3] * c1;
         gp[dt][0] = img ? scale * (dq[dt][0] * qr[dt][0] + dq[dt][1] * qr[dt][1]) : 0.f;
@@ -602,7 +679,7 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
 // ---------------------------------------------------------------------------------
 // DROP: dropout on the attention probabilities (rope_2d_mhsa.py:497), applied after the normalisation: the running sum
 // takes the undropped exponentials, P . V the dropped ones
-template <typename T, int NW = 4, bool DROP = false, int HD = 64>
+template <typename T, int NW = 4, bool DROP = false, int HD = 64, bool ROT = false>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* kimg = smem;                       // K~ row image
@@ -621,7 +698,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
 
     const int q = qt * (16 * NW) + wave * 16 + s;
     uint4 qf[(AT<T, HD>::NKK)];
-    load_row_frag<T, true, HD>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale);
+    load_row_frag<T, true, HD, ROT>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale, p.sin_tab);
 
     f32x4_t oacc[HD / 16];
 #pragma unroll
@@ -631,9 +708,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
     if constexpr (DROP) mrow = p.amask + (((int64_t)b * p.heads + head) * p.N + min(q, p.N - 1)) * p.Np + 4 * g;
 
     const int nkt = (p.N + BT - 1) / BT;
-    TileFetch<T, true, 64 * NW, HD> fk;   // the next key tile travels in registers while this one is multiplied
+    TileFetch<T, true, 64 * NW, HD, ROT> fk;   // the next key tile travels in registers while this one is multiplied
     TileFetch<T, false, 64 * NW, HD> fv;
-    fk.fetch(kb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head);
+    fk.fetch(kb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
     fv.fetch(vb, ld, 0, p.N, p.E, nullptr, p.heads, head);
     for (int kt = 0; kt < nkt; ++kt) {
         uint32_t mk[4] = {0, 0, 0, 0};
@@ -645,7 +722,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
         fk.template commit<true, false>(kimg, nullptr, kt * BT, p.N, p.E, 1.0f);
         fv.template commit<false, true>(nullptr, vimg, kt * BT, p.N, p.E, 1.0f);
         const int nxt = min(kt + 1, nkt - 1) * BT;
-        fk.fetch(kb, ld, nxt, p.N, p.E, p.cos_tab, p.heads, head);
+        fk.fetch(kb, ld, nxt, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
         fv.fetch(vb, ld, nxt, p.N, p.E, nullptr, p.heads, head);
         __syncthreads();
         f32x4_t sacc[4];
@@ -708,7 +785,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
 // ---------------------------------------------------------------------------------
 // backward, query side: delta, dq (and the q part of the cos gradient)
 // ---------------------------------------------------------------------------------
-template <typename T, int NW = 4, bool DROP = false, int HD = 64>
+template <typename T, int NW = 4, bool DROP = false, int HD = 64, bool ROT = false>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* kimg = smem;                                        // K~ rows
@@ -732,7 +809,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     if (threadIdx.x < HD) fl[threadIdx.x] = 0.f;
     const int q = qt * (16 * NW) + wave * 16 + s;
     uint4 qf[(AT<T, HD>::NKK)], dof[(AT<T, HD>::NKK)];
-    load_row_frag<T, true, HD>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale);
+    load_row_frag<T, true, HD, ROT>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale, p.sin_tab);
     load_row_frag<T, false, HD>(dof, dob, C, q, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
     // delta = sum_d dO * O  (each lane holds 1/4 of the row)
     float dl = 0.f;
@@ -760,9 +837,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     if constexpr (DROP) mrow = p.amask + (((int64_t)b * p.heads + head) * p.N + min(q, p.N - 1)) * p.Np + 4 * g;
 
     const int nkt = (p.N + BT - 1) / BT;
-    TileFetch<T, true, 64 * NW, HD> fk;   // the next key tile travels in registers while this one is multiplied
+    TileFetch<T, true, 64 * NW, HD, ROT> fk;   // the next key tile travels in registers while this one is multiplied
     TileFetch<T, false, 64 * NW, HD> fv;
-    fk.fetch(kb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head);
+    fk.fetch(kb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
     fv.fetch(vb, ld, 0, p.N, p.E, nullptr, p.heads, head);
     for (int kt = 0; kt < nkt; ++kt) {
         uint32_t mk[4] = {0, 0, 0, 0};
@@ -774,7 +851,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
         fk.template commit<true, true>(kimg, ktr, kt * BT, p.N, p.E, 1.0f);
         fv.template commit<true, false>(vimg, nullptr, kt * BT, p.N, p.E, 1.0f);
         const int nxt = min(kt + 1, nkt - 1) * BT;
-        fk.fetch(kb, ld, nxt, p.N, p.E, p.cos_tab, p.heads, head);
+        fk.fetch(kb, ld, nxt, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
         fv.fetch(vb, ld, nxt, p.N, p.E, nullptr, p.heads, head);
         __syncthreads();
         // no masks: padding keys have zero rows in all three images (their finite dS meets a zero row of K~), padding queries
@@ -805,7 +882,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
             PHASE_FENCE();
         }
     }
-    dq_epilogue<T, HD>(p, dq, qb, ld, b, head, q, s, g, scale, fl);
+    dq_epilogue<T, HD, ROT>(p, dq, qb, ld, b, head, q, s, g, scale, fl);
     if (p.E < p.N) freq_flush<false, HD>(fl, p.fpart);
 }
 
@@ -815,7 +892,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
 // ---------------------------------------------------------------------------------
 // NW = 8: at least 4 waves per SIMD (two 8-wave workgroups per CU) -- left to itself the compiler takes 130 registers and
 // only one workgroup fits
-template <typename T, int NW = 4, bool DROP = false, int HD = 64>
+template <typename T, int NW = 4, bool DROP = false, int HD = 64, bool ROT = false>
 __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd_dkv_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* qimg = smem;                                   // Q~ rows
@@ -842,7 +919,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
     if (threadIdx.x < HD) fl[threadIdx.x] = 0.f;
     const int key = ktile * (16 * NW) + wave * 16 + s;
     uint4 kf[(AT<T, HD>::NKK)], vf[(AT<T, HD>::NKK)];
-    load_row_frag<T, true, HD>(kf, kb, ld, key, p.N, p.E, g, p.cos_tab, p.heads, head, 1.0f);
+    load_row_frag<T, true, HD, ROT>(kf, kb, ld, key, p.N, p.E, g, p.cos_tab, p.heads, head, 1.0f, p.sin_tab);
     load_row_frag<T, false, HD>(vf, vb, ld, key, p.N, p.E, g, nullptr, p.heads, head, 1.0f);
 
     f32x4_t dk[HD / 16], dv[HD / 16];
@@ -852,11 +929,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
         dv[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
     const int nqt = (p.N + BT - 1) / BT;
-    TileFetch<T, true, 64 * NW, HD> fq;   // the next query tile (and its statistics) travel in registers while this one is multiplied
+    TileFetch<T, true, 64 * NW, HD, ROT> fq;   // the next query tile (and its statistics) travel in registers while this one is multiplied
     TileFetch<T, false, 64 * NW, HD> fdo;
     const int stl = threadIdx.x & (BT - 1);  // every thread fetches a statistic (unconditional load); the first 64 commit
     float l_n, d_n;
-    fq.fetch(qb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head);
+    fq.fetch(qb, ld, 0, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
     fdo.fetch(dob, C, 0, p.N, p.E, nullptr, p.heads, head);
     l_n = p.lse[statbase + min(stl, p.N - 1)];
     d_n = p.delta[statbase + min(stl, p.N - 1)];
@@ -870,7 +947,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
             del_s[threadIdx.x] = qq < p.N ? d_n : 0.f;
         }
         const int nxt = min(qt + 1, nqt - 1) * BT;
-        fq.fetch(qb, ld, nxt, p.N, p.E, p.cos_tab, p.heads, head);
+        fq.fetch(qb, ld, nxt, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
         fdo.fetch(dob, C, nxt, p.N, p.E, nullptr, p.heads, head);
         l_n = p.lse[statbase + min(nxt + stl, p.N - 1)];
         d_n = p.delta[statbase + min(nxt + stl, p.N - 1)];
@@ -913,7 +990,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
             PHASE_FENCE();
         }
     }
-    dkv_epilogue<T, HD>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
+    dkv_epilogue<T, HD, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
     if (p.E < p.N) freq_flush<true, HD>(fl, p.fpart);
 }
 
@@ -923,19 +1000,19 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
 // 16-row tiles with no barrier in the loop.  Against the tiled kernels above this removes the
 // per-q-tile re-staging of K/V (4x at N = 199) and every in-loop __syncthreads.
 // ---------------------------------------------------------------------------------
-template <typename T, bool COS, bool ROWIMG, bool TRIMG>
+template <typename T, bool COS, bool ROWIMG, bool TRIMG, bool ROT = false>
 __device__ __forceinline__ void stage_all(unsigned char* rowimg, unsigned char* trimg, const T* __restrict__ base, int64_t ld, int nrows_pad, int N, int E,
-                                          const float* __restrict__ cos_tab, int heads, int head, float scale) {
+                                          const float* __restrict__ cos_tab, int heads, int head, float scale, const float* __restrict__ sin_tab = nullptr) {
     constexpr int NCH = AT<T>::NCH;
     constexpr int EPV = AT<T>::EPV;
     constexpr int UN = 4;  // chunks in flight per thread (N <= 256: the whole operand in one batch of 512 threads)
     const int total = nrows_pad * NCH;
     for (int i0 = threadIdx.x; i0 < total; i0 += UN * blockDim.x) {
-        Chunk<T, COS> ch[UN];
+        Chunk<T, COS, 64, ROT> ch[UN];
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int i = min(i0 + u * (int)blockDim.x, total - 1);
-            ch[u].fetch(base, ld, i / NCH, N, E, (i % NCH) * EPV, cos_tab, heads, head);
+            ch[u].fetch(base, ld, i / NCH, N, E, (i % NCH) * EPV, cos_tab, heads, head, sin_tab);
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
@@ -950,7 +1027,7 @@ __device__ __forceinline__ void stage_all(unsigned char* rowimg, unsigned char* 
     }
 }
 
-template <typename T, int NW = 8>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
+template <typename T, int NW = 8, bool ROT = false>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_res_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
@@ -967,14 +1044,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const T* kb = qb + C;
     const T* vb = qb + 2 * C;
     const float scale = 0.125f;
-    stage_all<T, true, true, false>(kimg, nullptr, kb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, 1.0f);
+    stage_all<T, true, true, false, ROT>(kimg, nullptr, kb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, 1.0f, p.sin_tab);
     stage_all<T, false, false, true>(nullptr, vimg, vb, ld, npad, p.N, p.E, nullptr, p.heads, head, 1.0f);
     __syncthreads();
     const int nq16 = (p.N + 15) / 16;
     for (int qt = wave; qt < nq16; qt += NW) {
         const int q = qt * 16 + s;
         uint4 qf[AT<T>::NKK];
-        load_row_frag<T, true>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale);
+        load_row_frag<T, true, 64, ROT>(qf, qb, ld, q, p.N, p.E, g, p.cos_tab, p.heads, head, scale, p.sin_tab);
         f32x4_t oacc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) oacc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -1037,7 +1114,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     }
 }
 
-template <typename T, int NW = 8>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
+template <typename T, int NW = 8, bool ROT = false>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dq_res_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
@@ -1058,7 +1135,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const float scale = 0.125f;
     __shared__ float fl[64];  // freqs-gradient partial of this (sample, head)
     if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
-    stage_all<T, true, false, true>(nullptr, kimg, kb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, 1.0f);
+    stage_all<T, true, false, true, ROT>(nullptr, kimg, kb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, 1.0f, p.sin_tab);
     stage_all<T, false, false, true>(nullptr, vimg, vb, ld, npad, p.N, p.E, nullptr, p.heads, head, 1.0f);
     __syncthreads();
     const int nq16 = (p.N + 15) / 16;
@@ -1068,12 +1145,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         // and cos factors of the epilogue, the row's LSE -- instead of one memory round trip per operand
         const int qc = min(q, p.N - 1);
         uint4 qf[AT<T>::NKK], dof[AT<T>::NKK];
-        Chunk<T, true> cq[AT<T>::NKK];
+        Chunk<T, true, 64, ROT> cq[AT<T>::NKK];
         Chunk<T, false> cdo[AT<T>::NKK], co[AT<T>::NKK];
 #pragma unroll
         for (int kk = 0; kk < AT<T>::NKK; ++kk) {
             const int d0 = (kk * 4 + g) * AT<T>::EPV;
-            cq[kk].fetch(qb, ld, q, p.N, p.E, d0, p.cos_tab, p.heads, head);
+            cq[kk].fetch(qb, ld, q, p.N, p.E, d0, p.cos_tab, p.heads, head, p.sin_tab);
             cdo[kk].fetch(dob, C, q, p.N, p.E, d0, nullptr, p.heads, head);
             co[kk].fetch(ob, C, q, p.N, p.E, d0, nullptr, p.heads, head);
         }
@@ -1093,8 +1170,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 const float4 r = *reinterpret_cast<const float4*>(qraw + d0);
                 qr[dt][0] = r.x; qr[dt][1] = r.y; qr[dt][2] = r.z; qr[dt][3] = r.w;
             }
-            const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
-            cr[dt][0] = c2.x; cr[dt][1] = c2.y;
+            if constexpr (!ROT) {  // (ROT: cos and sin are fetched behind the key loop, where the d-cos entries are fetched here)
+                const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
+                cr[dt][0] = c2.x; cr[dt][1] = c2.y;
+            }
         }
 #pragma unroll
         for (int kk = 0; kk < AT<T>::NKK; ++kk) {
@@ -1144,8 +1223,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
             const float* sxp = p.dsin + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
             const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * 32;
             float gp[4][2], dx[4][2], dy[4][2];
+            float sr[ROT ? 4 : 1][2];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
+                if constexpr (ROT) {
+                    const float2 c2 = *reinterpret_cast<const float2*>(cpr + ((dt * 16 + 4 * g) >> 1));
+                    const float2 s2 = *reinterpret_cast<const float2*>(p.sin_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32 + ((dt * 16 + 4 * g) >> 1));
+                    cr[dt][0] = c2.x; cr[dt][1] = c2.y;
+                    sr[dt][0] = s2.x; sr[dt][1] = s2.y;
+                    dx[dt][0] = dx[dt][1] = (float)(max(qc - p.E, 0) % p.W);
+                    dy[dt][0] = dy[dt][1] = (float)(max(qc - p.E, 0) / p.W);
+                    continue;
+                }
                 const float2 a = *reinterpret_cast<const float2*>(sxp + ((dt * 16 + 4 * g) >> 1));
                 const float2 c = *reinterpret_cast<const float2*>(syp + ((dt * 16 + 4 * g) >> 1));
                 dx[dt][0] = a.x; dx[dt][1] = a.y;
@@ -1156,6 +1245,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
             float oq[4][4];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
+                if constexpr (ROT) {  // (see dq_epilogue)
+                    const float s0 = img ? sr[dt][0] : 0.f, s1 = img ? sr[dt][1] : 0.f, r0 = img ? cr[dt][0] : 1.0f, r1 = img ? cr[dt][1] : 1.0f;
+                    oq[dt][0] = scale * (dq[dt][0] * r0 + dq[dt][1] * s0); oq[dt][1] = scale * (dq[dt][1] * r0 - dq[dt][0] * s0);
+                    oq[dt][2] = scale * (dq[dt][2] * r1 + dq[dt][3] * s1); oq[dt][3] = scale * (dq[dt][3] * r1 - dq[dt][2] * s1);
+                    const float x0 = qr[dt][0] * r0 - qr[dt][1] * s0, x1 = qr[dt][0] * s0 + qr[dt][1] * r0;
+                    const float x2 = qr[dt][2] * r1 - qr[dt][3] * s1, x3 = qr[dt][2] * s1 + qr[dt][3] * r1;
+                    gp[dt][0] = img ? scale * (dq[dt][1] * x0 - dq[dt][0] * x1) : 0.f;
+                    gp[dt][1] = img ? scale * (dq[dt][3] * x2 - dq[dt][2] * x3) : 0.f;
+                    continue;
+                }
                 const float c0 = img ? cr[dt][0] * scale : scale, c1 = img ? cr[dt][1] * scale : scale;
                 oq[dt][0] = dq[dt][0] * c0; oq[dt][1] = dq[dt][1] * c0; oq[dt][2] = dq[dt][2] * c1; oq[dt][3] = dq[dt][3] * c1;
                 gp[dt][0] = img ? scale * (dq[dt][0] * qr[dt][0] + dq[dt][1] * qr[dt][1]) : 0.f;
@@ -1177,7 +1276,7 @@ __device__ unsigned long long g_att_stamp[8];
 #define ATT_T(i) do { } while (0)
 #endif
 
-template <typename T, int NW = 8>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
+template <typename T, int NW = 8, bool ROT = false>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dkv_res_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
@@ -1204,7 +1303,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int64_t statbase = ((int64_t)b * p.heads + head) * p.N;
     __shared__ float fl[64];  // freqs-gradient partial of this (sample, head)
     if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
-    stage_all<T, true, false, true>(nullptr, qimg, qb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, scale);
+    stage_all<T, true, false, true, ROT>(nullptr, qimg, qb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, scale, p.sin_tab);
     stage_all<T, false, false, true>(nullptr, doimg, dob, C, npad, p.N, p.E, nullptr, p.heads, head, 1.0f);
     ATT_T(0);
     for (int i = threadIdx.x; i < nqt * BT; i += blockDim.x) {  // unconditional loads (clamped), zero by select
@@ -1221,12 +1320,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         // every fetch of this key tile in one batch (see the dq kernel).  (Requesting the first tile's fragments before the
         // staging loads was tried in round 3: the chunks held across the staging spill, 212 -> 290 us for the pair of kernels.)
         uint4 kf[AT<T>::NKK], vf[AT<T>::NKK];
-        Chunk<T, true> ck[AT<T>::NKK];
+        Chunk<T, true, 64, ROT> ck[AT<T>::NKK];
         Chunk<T, false> cv[AT<T>::NKK];
 #pragma unroll
         for (int kk = 0; kk < AT<T>::NKK; ++kk) {
             const int d0 = (kk * 4 + g) * AT<T>::EPV;
-            ck[kk].fetch(kb, ld, key, p.N, p.E, d0, p.cos_tab, p.heads, head);
+            ck[kk].fetch(kb, ld, key, p.N, p.E, d0, p.cos_tab, p.heads, head, p.sin_tab);
             cv[kk].fetch(vb, ld, key, p.N, p.E, d0, nullptr, p.heads, head);
         }
 #pragma unroll
@@ -1274,7 +1373,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
             PHASE_FENCE();
         }
         ATT_T(3);
-        dkv_epilogue<T>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
+        dkv_epilogue<T, 64, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
         ATT_T(4);
     }
     if (p.E < p.N) freq_flush<true>(fl, p.fpart);
@@ -1292,7 +1391,8 @@ extern "C" int lnx_dbg_attn_stamps(unsigned long long* out8) { return (int)hipMe
 // ---------------------------------------------------------------------------------
 // HD / 2 frequencies per head: entry i = (n * heads + h) * HD / 2 + j
 template <int HD = 64>
-__device__ __forceinline__ void rope_cos_entry(const float* __restrict__ freqs, int heads, int H, int W, float* __restrict__ out, float* __restrict__ dsin, int i) {
+__device__ __forceinline__ void rope_cos_entry(const float* __restrict__ freqs, int heads, int H, int W, float* __restrict__ out, float* __restrict__ dsin, int i,
+                                               float* __restrict__ sin_out = nullptr) {
     constexpr int HH = HD / 2, SH = HD == 32 ? 4 : HD == 64 ? 5 : 6;
     const int total = H * W * heads * HH;
     if (i >= total) return;
@@ -1306,6 +1406,7 @@ __device__ __forceinline__ void rope_cos_entry(const float* __restrict__ freqs, 
     const float ay = __fmul_rn(ty, freqs[(heads + h) * HH + j]);
     const float th = __fadd_rn(ax, ay);
     out[i] = cosf(th);
+    if (sin_out) sin_out[i] = sinf(th);  // LNX_ROPE_ROTATE: the imaginary part of polar(1, theta) (rope_2d_mhsa.py:143)
     if (dsin) {  // d cos(theta) / d freqs[a, h, j] = -t_a sin(theta): what the attention backward weights its pair gradients with
         const float ms = -sinf(th);
         dsin[i] = tx * ms;
@@ -1315,8 +1416,8 @@ __device__ __forceinline__ void rope_cos_entry(const float* __restrict__ freqs, 
 
 template <int HD = 64>
 __global__ __launch_bounds__(256) void rope_cos_kernel(const float* __restrict__ freqs, int heads, int H, int W, float* __restrict__ out,
-                                                       float* __restrict__ dsin) {
-    rope_cos_entry<HD>(freqs, heads, H, W, out, dsin, blockIdx.x * 256 + threadIdx.x);
+                                                       float* __restrict__ dsin, float* __restrict__ sin_out) {
+    rope_cos_entry<HD>(freqs, heads, H, W, out, dsin, blockIdx.x * 256 + threadIdx.x, sin_out);
 }
 
 // the tables of several blocks in one launch (every RoPE block of a plan has its own freqs): blockIdx.y picks the table.  One launch
@@ -1327,7 +1428,7 @@ struct RopeTabBatch {
 template <int HD = 64>
 __global__ __launch_bounds__(256) void rope_cos_batch_kernel(const RopeTabBatch b) {
     const lnx_rope_table& t = b.t[blockIdx.y];
-    rope_cos_entry<HD>(t.freqs, t.heads, t.H, t.W, t.cos_out, t.dsin_out, blockIdx.x * 256 + threadIdx.x);
+    rope_cos_entry<HD>(t.freqs, t.heads, t.H, t.W, t.cos_out, t.dsin_out, blockIdx.x * 256 + threadIdx.x, t.sin_out);
 }
 
 // dfreqs[a, h, j] += sum over the workgroups of head h of their partial [a][j]   (fixed order: deterministic given the partials)
@@ -1471,76 +1572,76 @@ int attn_family(int dtype, int N, int hd, bool drop) {
 
 std::atomic<int> g_last_attn{LNX_ATTN_KERNEL_NONE};
 
-template <typename T, int HD>
+template <typename T, int HD, bool ROT>
 void attn_fwd_tiled(AttnP& p, int family, hipStream_t st) {
     using A = AT<T, HD>;
     const size_t lds = A::ROW_IMG + A::TR_IMG;  // fp32 head_dim 128: 65 KiB
     static bool once = false;
     if (!once) {
-        set_lds(attn_fwd_kernel<T, 4, false, HD>, lds);
-        set_lds(attn_fwd_kernel<T, 4, true, HD>, lds);
-        if constexpr (hd_nw8<T, HD>()) set_lds(attn_fwd_kernel<T, 8, false, HD>, lds);
+        set_lds(attn_fwd_kernel<T, 4, false, HD, ROT>, lds);
+        set_lds(attn_fwd_kernel<T, 4, true, HD, ROT>, lds);
+        if constexpr (hd_nw8<T, HD>()) set_lds(attn_fwd_kernel<T, 8, false, HD, ROT>, lds);
         once = true;
     }
     const int bh = p.B * p.heads;
     if (p.amask) {
-        hipLaunchKernelGGL((attn_fwd_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
+        hipLaunchKernelGGL((attn_fwd_kernel<T, 4, true, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
         return;
     }
     if constexpr (hd_nw8<T, HD>()) {
         if (family == LNX_ATTN_KERNEL_TILED8) {
             p.qtiles = cdiv(p.N, 128);
-            hipLaunchKernelGGL((attn_fwd_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds, st, p);
+            hipLaunchKernelGGL((attn_fwd_kernel<T, 8, false, HD, ROT>), dim3(bh * p.qtiles), dim3(512), lds, st, p);
             return;
         }
     }
-    hipLaunchKernelGGL((attn_fwd_kernel<T, 4, false, HD>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((attn_fwd_kernel<T, 4, false, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
 }
 
 // returns the workgroups per (sample, head) of the launch (the fold's per_bh)
-template <typename T, int HD>
+template <typename T, int HD, bool ROT>
 int attn_bwd_tiled(AttnP& p, int family, hipStream_t st) {
     using A = AT<T, HD>;
     const size_t lds_q = 2 * A::ROW_IMG + A::TR_IMG;
     const size_t lds_k = 2 * A::ROW_IMG + 2 * A::TR_IMG + 2 * BT * sizeof(float);  // fp32 head_dim 128: 130.5 KiB
     static bool once = false;
     if (!once) {
-        set_lds(attn_bwd_dq_kernel<T, 4, false, HD>, lds_q);
-        set_lds(attn_bwd_dq_kernel<T, 4, true, HD>, lds_q);
-        set_lds(attn_bwd_dkv_kernel<T, 4, false, HD>, lds_k);
-        set_lds(attn_bwd_dkv_kernel<T, 4, true, HD>, lds_k);
+        set_lds(attn_bwd_dq_kernel<T, 4, false, HD, ROT>, lds_q);
+        set_lds(attn_bwd_dq_kernel<T, 4, true, HD, ROT>, lds_q);
+        set_lds(attn_bwd_dkv_kernel<T, 4, false, HD, ROT>, lds_k);
+        set_lds(attn_bwd_dkv_kernel<T, 4, true, HD, ROT>, lds_k);
         if constexpr (hd_nw8<T, HD>()) {
-            set_lds(attn_bwd_dq_kernel<T, 8, false, HD>, lds_q);
-            set_lds(attn_bwd_dkv_kernel<T, 8, false, HD>, lds_k);
+            set_lds(attn_bwd_dq_kernel<T, 8, false, HD, ROT>, lds_q);
+            set_lds(attn_bwd_dkv_kernel<T, 8, false, HD, ROT>, lds_k);
         }
         once = true;
     }
     const int bh = p.B * p.heads;
     if (p.amask) {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, HD>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
         return p.qtiles;
     }
     if constexpr (hd_nw8<T, HD>()) {
         if (family == LNX_ATTN_KERNEL_TILED8) {
             p.qtiles = cdiv(p.N, 128);
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false, HD>), dim3(bh * p.qtiles), dim3(512), lds_k, st, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8, false, HD, ROT>), dim3(bh * p.qtiles), dim3(512), lds_q, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false, HD, ROT>), dim3(bh * p.qtiles), dim3(512), lds_k, st, p);
             return p.qtiles;
         }
     }
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, HD>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, HD>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
     return p.qtiles;
 }
 
-int rope_table_hd(const float* freqs, int heads, int hd, int H, int W, float* cos_out, float* dsin_out, hipStream_t st, const char* who) {
+int rope_table_hd(const float* freqs, int heads, int hd, int H, int W, float* cos_out, float* dsin_out, hipStream_t st, const char* who, float* sin_out = nullptr) {
     LNX_CHECK(freqs && cos_out && heads > 0 && H > 0 && W > 0, "%s: bad arguments", who);
     LNX_CHECK(hd_ok(hd), "%s: head_dim %d is not supported (32, 64 or 128)", who, hd);
     const int total = H * W * heads * (hd / 2);
-    if (hd == 64) hipLaunchKernelGGL(rope_cos_kernel<64>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out);
-    else if (hd == 32) hipLaunchKernelGGL(rope_cos_kernel<32>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out);
-    else hipLaunchKernelGGL(rope_cos_kernel<128>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out);
+    if (hd == 64) hipLaunchKernelGGL(rope_cos_kernel<64>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out, sin_out);
+    else if (hd == 32) hipLaunchKernelGGL(rope_cos_kernel<32>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out, sin_out);
+    else hipLaunchKernelGGL(rope_cos_kernel<128>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out, sin_out);
     LNX_LAUNCH_CHECK();
     return 0;
 }
@@ -1555,11 +1656,19 @@ extern "C" int lnx_rope_cos_table_hd(const float* freqs, int heads, int head_dim
     return rope_table_hd(freqs, heads, head_dim, H, W, cos_out, dsin_out, (hipStream_t)stream, "lnx_rope_cos_table_hd");
 }
 
+extern "C" int lnx_rope_cossin_table_hd(const float* freqs, int heads, int head_dim, int H, int W, float* cos_out, float* sin_out, float* dsin_out, void* stream) {
+    return rope_table_hd(freqs, heads, head_dim, H, W, cos_out, dsin_out, (hipStream_t)stream, "lnx_rope_cossin_table_hd", sin_out);
+}
+
 extern "C" int lnx_rope_cos_tables(const lnx_rope_table* t, int n, void* stream) {
     LNX_CHECK(t && n > 0, "lnx_rope_cos_tables: bad arguments");
     for (int i = 0; i < n; ++i) LNX_CHECK(t[i].freqs && t[i].cos_out && t[i].heads > 0 && t[i].H > 0 && t[i].W > 0, "lnx_rope_cos_tables: bad table");
     for (int i = 0; i < n; ++i)
         LNX_CHECK(t[i].head_dim == 0 || hd_ok(t[i].head_dim), "lnx_rope_cos_tables: head_dim %d is not supported (32, 64 or 128)", t[i].head_dim);
+    for (int i = 0; i < n; ++i) {
+        LNX_CHECK(t[i].rope_mode == LNX_ROPE_COS || t[i].rope_mode == LNX_ROPE_ROTATE, "lnx_rope_cos_tables: bad rope_mode %d", t[i].rope_mode);
+        LNX_CHECK(t[i].rope_mode != LNX_ROPE_ROTATE || t[i].sin_out, "lnx_rope_cos_tables: a LNX_ROPE_ROTATE table needs sin_out");
+    }
     for (const int hd : {64, 32, 128}) {  // one launch (per LNX_ROPE_TABLES_MAX tables) per head_dim present, tables in their order
         std::vector<lnx_rope_table> g;
         for (int i = 0; i < n; ++i)
@@ -1589,13 +1698,16 @@ extern "C" int64_t lnx_attn_bwd_ws_floats_hd(int B, int N, int heads, int head_d
     return hd_ok(head_dim) ? (int64_t)B * heads * cdiv(N, BT) * head_dim : 0;
 }
 
-extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
-    LNX_CHECK(a && a->qkv && a->o, "lnx_attn_fwd: null operand");
+// ROT = the call's rope_mode is LNX_ROPE_ROTATE: the same families and launch shapes, the rotating instantiations
+template <bool ROT>
+int attn_fwd_launch(const lnx_attn_args* a, void* stream) {
     const int hd = a->head_dim ? a->head_dim : 64;
     if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, hd, "lnx_attn_fwd")) return 1;
     LNX_CHECK(a->E == a->N || a->cos_tab, "lnx_attn_fwd: cos table missing");
+    LNX_CHECK(!ROT || a->E == a->N || a->sin_tab, "lnx_attn_fwd: sin table missing (rope_mode = LNX_ROPE_ROTATE)");
     AttnP p{};
     p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = a->o; p.lse = a->lse;
+    if (ROT) p.sin_tab = cos_or_stub(a->sin_tab, a->qkv);
     p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
     p.qtiles = cdiv(a->N, BT);
     const int grid = a->B * a->heads * p.qtiles;
@@ -1609,20 +1721,20 @@ extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
     const bool resident = family == LNX_ATTN_KERNEL_RES4 || family == LNX_ATTN_KERNEL_RES8;
     if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
         if (a->dtype == LNX_BF16) {
-            if (hd == 32) attn_fwd_tiled<bf16_t, 32>(p, family, st);
-            else attn_fwd_tiled<bf16_t, 128>(p, family, st);
+            if (hd == 32) attn_fwd_tiled<bf16_t, 32, ROT>(p, family, st);
+            else attn_fwd_tiled<bf16_t, 128, ROT>(p, family, st);
         } else {
-            if (hd == 32) attn_fwd_tiled<float, 32>(p, family, st);
-            else attn_fwd_tiled<float, 128>(p, family, st);
+            if (hd == 32) attn_fwd_tiled<float, 32, ROT>(p, family, st);
+            else attn_fwd_tiled<float, 128, ROT>(p, family, st);
         }
         LNX_LAUNCH_CHECK();
         return 0;
     }
     if (a->drop_mask) {
         if (a->dtype == LNX_BF16) {
-            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 4, true>), dim3(grid), dim3(256), AT<bf16_t>::ROW_IMG + AT<bf16_t>::TR_IMG, st, p);
+            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 4, true, 64, ROT>), dim3(grid), dim3(256), AT<bf16_t>::ROW_IMG + AT<bf16_t>::TR_IMG, st, p);
         } else {
-            hipLaunchKernelGGL((attn_fwd_kernel<float, 4, true>), dim3(grid), dim3(256), AT<float>::ROW_IMG + AT<float>::TR_IMG, st, p);
+            hipLaunchKernelGGL((attn_fwd_kernel<float, 4, true, 64, ROT>), dim3(grid), dim3(256), AT<float>::ROW_IMG + AT<float>::TR_IMG, st, p);
         }
         LNX_LAUNCH_CHECK();
         return 0;
@@ -1633,33 +1745,42 @@ extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
         const size_t lds = (size_t)npad * (AT<T>::ROWB + AT<T>::TRB);
         static bool once = false;
         if (!once) {
-            set_lds(attn_fwd_res_kernel<T>, 256 * (AT<T>::ROWB + AT<T>::TRB));
+            set_lds(attn_fwd_res_kernel<T, 8, ROT>, 256 * (AT<T>::ROWB + AT<T>::TRB));
             once = true;
         }
-        if (family == LNX_ATTN_KERNEL_RES4) hipLaunchKernelGGL((attn_fwd_res_kernel<T, 4>), dim3(a->B * a->heads), dim3(256), lds, st, p);
-        else hipLaunchKernelGGL((attn_fwd_res_kernel<T>), dim3(a->B * a->heads), dim3(512), lds, st, p);
+        if (family == LNX_ATTN_KERNEL_RES4) hipLaunchKernelGGL((attn_fwd_res_kernel<T, 4, ROT>), dim3(a->B * a->heads), dim3(256), lds, st, p);
+        else hipLaunchKernelGGL((attn_fwd_res_kernel<T, 8, ROT>), dim3(a->B * a->heads), dim3(512), lds, st, p);
     } else if (a->dtype == LNX_BF16) {
         const size_t lds = AT<bf16_t>::ROW_IMG + AT<bf16_t>::TR_IMG;
         if (family == LNX_ATTN_KERNEL_TILED8) {  // 128 queries per workgroup
             p.qtiles = cdiv(a->N, 128);
-            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 8>), dim3(a->B * a->heads * p.qtiles), dim3(512), lds, st, p);
+            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 8, false, 64, ROT>), dim3(a->B * a->heads * p.qtiles), dim3(512), lds, st, p);
         } else {
-            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t>), dim3(grid), dim3(256), lds, st, p);
+            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 4, false, 64, ROT>), dim3(grid), dim3(256), lds, st, p);
         }
     } else {
         const size_t lds = AT<float>::ROW_IMG + AT<float>::TR_IMG;
-        hipLaunchKernelGGL((attn_fwd_kernel<float>), dim3(grid), dim3(256), lds, st, p);
+        hipLaunchKernelGGL((attn_fwd_kernel<float, 4, false, 64, ROT>), dim3(grid), dim3(256), lds, st, p);
     }
     LNX_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
-    LNX_CHECK(a && a->qkv && a->o && a->lse && a->d_o && a->dqkv && a->delta, "lnx_attn_bwd: null operand");
+template <bool ROT>
+int attn_bwd_launch(const lnx_attn_bwd_args* a, void* stream) {
     const int hd = a->head_dim ? a->head_dim : 64;
     if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, hd, "lnx_attn_bwd")) return 1;
-    LNX_CHECK(a->E == a->N || (a->cos_tab && a->dsin_tab && a->freq_ws && a->dfreqs), "lnx_attn_bwd: cos / d-cos tables, freqs-gradient workspace or dfreqs missing");
+    if (ROT) {
+        LNX_CHECK(a->E == a->N || (a->cos_tab && a->sin_tab && a->freq_ws && a->dfreqs), "lnx_attn_bwd: cos / sin tables, freqs-gradient workspace or dfreqs missing");
+        LNX_CHECK(a->E == a->N || (a->grid_w > 0 && (a->N - a->E) % a->grid_w == 0), "lnx_attn_bwd: grid_w %d does not divide the %d image tokens", a->grid_w, a->N - a->E);
+    } else {
+        LNX_CHECK(a->E == a->N || (a->cos_tab && a->dsin_tab && a->freq_ws && a->dfreqs), "lnx_attn_bwd: cos / d-cos tables, freqs-gradient workspace or dfreqs missing");
+    }
     AttnP p{};
+    if (ROT) {
+        p.sin_tab = cos_or_stub(a->sin_tab, a->qkv);
+        p.W = a->grid_w > 0 ? a->grid_w : 1;
+    }
     p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = const_cast<void*>(a->o); p.lse = const_cast<float*>(a->lse);
     p.d_o = a->d_o; p.dqkv = a->dqkv; p.fpart = a->freq_ws; p.dsin = cos_or_stub(a->dsin_tab, a->qkv); p.delta = a->delta;
     p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
@@ -1691,8 +1812,8 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
     const bool resident = family == LNX_ATTN_KERNEL_RES4 || family == LNX_ATTN_KERNEL_RES8;
     if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
         int per_bh;
-        if (a->dtype == LNX_BF16) per_bh = hd == 32 ? attn_bwd_tiled<bf16_t, 32>(p, family, st) : attn_bwd_tiled<bf16_t, 128>(p, family, st);
-        else per_bh = hd == 32 ? attn_bwd_tiled<float, 32>(p, family, st) : attn_bwd_tiled<float, 128>(p, family, st);
+        if (a->dtype == LNX_BF16) per_bh = hd == 32 ? attn_bwd_tiled<bf16_t, 32, ROT>(p, family, st) : attn_bwd_tiled<bf16_t, 128, ROT>(p, family, st);
+        else per_bh = hd == 32 ? attn_bwd_tiled<float, 32, ROT>(p, family, st) : attn_bwd_tiled<float, 128, ROT>(p, family, st);
         reduce_freqs(per_bh);
         LNX_LAUNCH_CHECK();
         return 0;
@@ -1700,18 +1821,18 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
     if (a->drop_mask) {
         if (a->dtype == LNX_BF16) {
             typedef bf16_t T;
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float), st, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float), st, p);
         } else {
             typedef float T;
             const size_t lds_k = 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float);
             static bool once = false;
             if (!once) {
-                set_lds(attn_bwd_dkv_kernel<T, 4, true>, lds_k);
+                set_lds(attn_bwd_dkv_kernel<T, 4, true, 64, ROT>, lds_k);
                 once = true;
             }
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true>), dim3(grid), dim3(256), lds_k, st, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), lds_k, st, p);
         }
         reduce_freqs(p.qtiles);
         LNX_LAUNCH_CHECK();
@@ -1724,16 +1845,16 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
         const size_t lds_k = (size_t)npad * (2 * AT<T>::TRB) + (size_t)p.qtiles * BT * 2 * sizeof(float);
         static bool once = false;
         if (!once) {
-            set_lds(attn_bwd_dq_res_kernel<T>, 256 * (2 * AT<T>::TRB));
-            set_lds(attn_bwd_dkv_res_kernel<T>, 256 * (2 * AT<T>::TRB + 2 * sizeof(float)));
+            set_lds(attn_bwd_dq_res_kernel<T, 8, ROT>, 256 * (2 * AT<T>::TRB));
+            set_lds(attn_bwd_dkv_res_kernel<T, 8, ROT>, 256 * (2 * AT<T>::TRB + 2 * sizeof(float)));
             once = true;
         }
         if (family == LNX_ATTN_KERNEL_RES4) {
-            hipLaunchKernelGGL((attn_bwd_dq_res_kernel<T, 4>), dim3(a->B * a->heads), dim3(256), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<T, 4>), dim3(a->B * a->heads), dim3(256), lds_k, st, p);
+            hipLaunchKernelGGL((attn_bwd_dq_res_kernel<T, 4, ROT>), dim3(a->B * a->heads), dim3(256), lds_q, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<T, 4, ROT>), dim3(a->B * a->heads), dim3(256), lds_k, st, p);
         } else {
-            hipLaunchKernelGGL((attn_bwd_dq_res_kernel<T>), dim3(a->B * a->heads), dim3(512), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<T>), dim3(a->B * a->heads), dim3(512), lds_k, st, p);
+            hipLaunchKernelGGL((attn_bwd_dq_res_kernel<T, 8, ROT>), dim3(a->B * a->heads), dim3(512), lds_q, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<T, 8, ROT>), dim3(a->B * a->heads), dim3(512), lds_k, st, p);
         }
         reduce_freqs(1);
     } else if (a->dtype == LNX_BF16) {
@@ -1743,12 +1864,12 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
         if (family == LNX_ATTN_KERNEL_TILED8) {  // 128 queries / keys per workgroup
             p.qtiles = cdiv(a->N, 128);
             const int g8 = a->B * a->heads * p.qtiles;
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8>), dim3(g8), dim3(512), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8>), dim3(g8), dim3(512), lds_k, st, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8, false, 64, ROT>), dim3(g8), dim3(512), lds_q, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false, 64, ROT>), dim3(g8), dim3(512), lds_k, st, p);
             reduce_freqs(p.qtiles);
         } else {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T>), dim3(grid), dim3(256), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T>), dim3(grid), dim3(256), lds_k, st, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_q, st, p);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_k, st, p);
             reduce_freqs(p.qtiles);
         }
     } else {
@@ -1757,15 +1878,27 @@ extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
         const size_t lds_k = 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float);
         static bool once = false;
         if (!once) {
-            set_lds(attn_bwd_dkv_kernel<T>, lds_k);
+            set_lds(attn_bwd_dkv_kernel<T, 4, false, 64, ROT>, lds_k);
             once = true;
         }
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T>), dim3(grid), dim3(256), lds_q, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T>), dim3(grid), dim3(256), lds_k, st, p);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_q, st, p);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_k, st, p);
         reduce_freqs(p.qtiles);
     }
     LNX_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
+    LNX_CHECK(a && a->qkv && a->o, "lnx_attn_fwd: null operand");
+    LNX_CHECK(a->rope_mode == LNX_ROPE_COS || a->rope_mode == LNX_ROPE_ROTATE, "lnx_attn_fwd: bad rope_mode %d", a->rope_mode);
+    return a->rope_mode == LNX_ROPE_ROTATE ? attn_fwd_launch<true>(a, stream) : attn_fwd_launch<false>(a, stream);
+}
+
+extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
+    LNX_CHECK(a && a->qkv && a->o && a->lse && a->d_o && a->dqkv && a->delta, "lnx_attn_bwd: null operand");
+    LNX_CHECK(a->rope_mode == LNX_ROPE_COS || a->rope_mode == LNX_ROPE_ROTATE, "lnx_attn_bwd: bad rope_mode %d", a->rope_mode);
+    return a->rope_mode == LNX_ROPE_ROTATE ? attn_bwd_launch<true>(a, stream) : attn_bwd_launch<false>(a, stream);
 }
 
 extern "C" int lnx_attn_dispatch(int dtype, int N, int head_dim, int has_drop_mask) {

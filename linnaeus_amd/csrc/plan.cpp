@@ -345,6 +345,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     if (c.n_meta < 0 || c.n_meta > LNX_MAX_META || c.n_tasks < 0 || c.n_tasks > LNX_MAX_TASKS) FAIL("lnx_plan_create: too many meta components / tasks");
     for (int m = 0; m < c.n_meta; ++m)
         if (c.meta_dims[m] <= 0 || c.meta_dims[m] > 16) FAIL("lnx_plan_create: meta dim %d must be in 1..16", c.meta_dims[m]);
+    if (c.rope_mode != LNX_ROPE_COS && c.rope_mode != LNX_ROPE_ROTATE) FAIL("lnx_plan_create: rope_mode %d (LNX_ROPE_COS or LNX_ROPE_ROTATE)", c.rope_mode);
 
     if (c.fp8) {
         if (c.dtype != LNX_BF16) FAIL("lnx_plan_create: fp8 = 1 needs dtype = LNX_BF16 (fp8 operands, bf16 storage)");
@@ -629,7 +630,9 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
             k.rstd1 = share ? f.rstd1 : cv.take(M * 4);
             k.qkvbuf = share ? f.qkvbuf : cv.take(M * 3 * C * esz);
             k.cos = cv.take((int64_t)p->HW[2 + s] * C / 2 * 4);  // [HW, heads, head_dim / 2]
-            k.dsin = inf ? 0 : cv.take((int64_t)2 * p->HW[2 + s] * C / 2 * 4);  // d cos / d freqs, for the attention backward
+            // d cos / d freqs, for the attention backward; rotate plans (forward and backward) keep sin(theta), one table, in its place
+            if (c.rope_mode == LNX_ROPE_ROTATE) k.dsin = cv.take((int64_t)p->HW[2 + s] * C / 2 * 4);
+            else k.dsin = inf ? 0 : cv.take((int64_t)2 * p->HW[2 + s] * C / 2 * 4);
             k.o = share ? f.o : cv.take(M * C * esz);
             k.lse = share ? f.lse : cv.take((int64_t)B * heads * N * 4);
             k.xmid = share ? f.xmid : cv.take(M * C * 4);
@@ -1368,6 +1371,9 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     memset(&a, 0, sizeof a);
     a.dtype = c.dt; a.B = B; a.N = N; a.E = E; a.heads = heads; a.head_dim = C / heads;
     a.qkv = c.at<void>(k.qkvbuf); a.cos_tab = c.at<float>(k.cos); a.o = c.at<void>(k.o); a.lse = c.at<float>(k.lse);
+    if (p->c.rope_mode == LNX_ROPE_ROTATE) {
+        a.rope_mode = LNX_ROPE_ROTATE; a.sin_tab = c.at<float>(k.dsin);
+    }
     if (p->amask) {
         a.drop_mask = p->amask + k.dm_attn; a.drop_inv_keep = p->a_inv_keep;
     }
@@ -1471,7 +1477,12 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
                 lnx_rope_table t;
                 memset(&t, 0, sizeof t);
                 t.freqs = p->P[k.freqs]; t.heads = cf.rope_heads[s]; t.H = p->H[2 + s]; t.W = p->W[2 + s]; t.head_dim = cf.dims[2 + s] / cf.rope_heads[s];
-                t.cos_out = c.at<float>(k.cos); t.dsin_out = cf.inference ? nullptr : c.at<float>(k.dsin);
+                t.cos_out = c.at<float>(k.cos);
+                if (cf.rope_mode == LNX_ROPE_ROTATE) {
+                    t.rope_mode = LNX_ROPE_ROTATE; t.sin_out = c.at<float>(k.dsin);
+                } else {
+                    t.dsin_out = cf.inference ? nullptr : c.at<float>(k.dsin);
+                }
                 tabs.push_back(t);
             }
         if (!tabs.empty()) RUN(lnx_rope_cos_tables(tabs.data(), (int)tabs.size(), mst ? (void*)mst : stream));
@@ -1683,6 +1694,9 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
         ++p->freq_pending;
     }
     ab.dsin_tab = c.at<float>(k.dsin); ab.dfreqs = p->G[k.freqs];
+    if (p->c.rope_mode == LNX_ROPE_ROTATE) {
+        ab.rope_mode = LNX_ROPE_ROTATE; ab.sin_tab = c.at<float>(k.dsin); ab.dsin_tab = nullptr; ab.grid_w = p->W[2 + s];
+    }
     if (p->amask) {
         ab.drop_mask = p->amask + k.dm_attn; ab.drop_inv_keep = p->a_inv_keep;
     }

@@ -34,6 +34,7 @@ class _Cfg(C.Structure):
         ("dims", C.c_int * 4), ("conv_depths", C.c_int * 2), ("rope_depths", C.c_int * 2), ("rope_heads", C.c_int * 2),
         ("mlp_hidden", C.c_int * 2), ("n_meta", C.c_int), ("meta_dims", C.c_int * 8), ("only_last_cls", C.c_int),
         ("n_tasks", C.c_int), ("task_classes", C.c_int * 16), ("inference", C.c_int), ("recompute", C.c_int), ("fp8", C.c_int),
+        ("rope_mode", C.c_int),
     ]
 
 
@@ -193,6 +194,9 @@ class mFormerV1(nn.Module):
         rdepths, rdims, rheads, rratio = list(rs.DEPTHS), list(rs.DIMS), list(rs.NUM_HEADS), list(rs.MLP_RATIO)
         self.rope_theta = rs.get("ROPE_THETA", 10000.0)
         self.rope_mixed = rs.get("ROPE_MIXED", True)
+        # ROPE_ROTATE (a key of this project, absent = False): True rotates the (even, odd) pairs of q and k by theta -- what the
+        # reference's helpers compute from the complex table; False multiplies them by cos(theta), what the reference runs
+        self.rope_rotate = bool(rs.get("ROPE_ROTATE", False))
         if len(rdepths) != 2 or len(rdims) != 2 or len(rheads) != 2 or len(rratio) != 2:
             raise ValueError("ROPE_STAGES depths, dims, num_heads, mlp_ratio must be lists of length 2.")
         if not self.rope_mixed:
@@ -420,6 +424,7 @@ class mFormerV1(nn.Module):
         cfg.inference = 0 if train else 1
         cfg.recompute = 1 if (train and recompute) else 0
         cfg.fp8 = 1 if self._fp8 else 0
+        cfg.rope_mode = L.ROPE_ROTATE if self.rope_rotate else L.ROPE_COS
         cfg.dtype, cfg.batch, cfg.img_h, cfg.img_w, cfg.in_chans = self._dtype_code, B, H, W, self._in_chans
         cfg.dims[:] = self._dims
         cfg.conv_depths[:] = self._depths[:2]

@@ -249,12 +249,25 @@ def rope_cos_table(freqs, H, W, out=None, dsin=None):
     return out
 
 
+def rope_cossin_table(freqs, H, W):
+    """(cos(theta), sin(theta)) tables, each [H*W, heads, head_dim/2], of freqs [2, heads, head_dim/2]: the operands of the rotate
+    form of attn_fwd / attn_bwd."""
+    heads, half = freqs.shape[1], freqs.shape[2]
+    cos = torch.empty(H * W, heads, half, device=freqs.device, dtype=torch.float32)
+    sin = torch.empty_like(cos)
+    L.check(L.lib().lnx_rope_cossin_table_hd(_p(freqs), heads, 2 * half, H, W, _p(cos), _p(sin), None, _stream()), "lnx_rope_cossin_table_hd")
+    return cos, sin
+
+
 def rope_cos_tables(entries):
-    """The tables of several blocks in one launch per head_dim: entries = [(freqs [2,heads,head_dim/2], H, W, cos_out, dsin_out or None), ...]."""
+    """The tables of several blocks in one launch per head_dim: entries = [(freqs [2,heads,head_dim/2], H, W, cos_out, dsin_out or None), ...];
+    a sixth element, sin_out, makes the entry a rotate-mode table (sin(theta) beside cos(theta))."""
     arr = (L.RopeTable * len(entries))()
-    for t, (freqs, H, W, out, dsin) in zip(arr, entries):
+    for t, (freqs, H, W, out, dsin, *rest) in zip(arr, entries):
         t.freqs, t.cos_out, t.dsin_out = _p(freqs), _p(out), _p(dsin) if dsin is not None else None
         t.heads, t.H, t.W, t.head_dim = freqs.shape[1], H, W, 2 * freqs.shape[2]
+        if rest and rest[0] is not None:
+            t.rope_mode, t.sin_out = L.ROPE_ROTATE, _p(rest[0])
     L.check(L.lib().lnx_rope_cos_tables(arr, len(entries), _stream()), "lnx_rope_cos_tables")
 
 
@@ -271,8 +284,11 @@ def _head_dim(qkv, heads, head_dim):
     return qkv.shape[-1] // (3 * heads) if qkv.dim() >= 2 and qkv.shape[-1] % (3 * heads) == 0 else 64
 
 
-def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=0.0, head_dim=None):
+def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=0.0, head_dim=None, sin_tab=None):
+    """sin_tab (the second table of rope_cossin_table): the rotate form -- q and k pairs rotated by theta instead of scaled by cos(theta)."""
     a = L.AttnArgs()
+    if sin_tab is not None:
+        a.rope_mode, a.sin_tab = L.ROPE_ROTATE, _p(sin_tab)
     a.dtype, a.B, a.N, a.E, a.heads = code_of(qkv), B, N, E, heads
     a.head_dim = _head_dim(qkv, heads, head_dim)
     a.qkv, a.cos_tab, a.o, a.lse = _p(qkv), _p(cos_tab), _p(o), _p(lse)
@@ -282,11 +298,14 @@ def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=
 
 
 def attn_bwd(qkv, cos_tab, o, lse, d_o, dqkv, delta, B, N, E, heads, *, dsin=None, dfreqs=None, drop_mask=None, drop_rate=0.0, defer_freqs=False,
-             head_dim=None):
+             head_dim=None, sin_tab=None, grid_w=0):
     """dq/dk/dv into dqkv; with image tokens (E < N) also dfreqs [2, heads, head_dim/2] += the gradient of the RoPE frequencies
     (`dsin` = the second table of rope_cos_table).  head_dim: from qkv's width unless given.  defer_freqs: the fold into dfreqs
-    waits for attn_bwd_flush(); the returned workspace (and dfreqs) must be kept alive until then."""
+    waits for attn_bwd_flush(); the returned workspace (and dfreqs) must be kept alive until then.
+    Rotate form: sin_tab (rope_cossin_table) and grid_w (the W of the tables) instead of dsin."""
     a = L.AttnBwdArgs()
+    if sin_tab is not None:
+        a.rope_mode, a.sin_tab, a.grid_w, a.dfreqs = L.ROPE_ROTATE, _p(sin_tab), int(grid_w), _p(dfreqs) if dfreqs is not None else None
     a.dtype, a.B, a.N, a.E, a.heads = code_of(qkv), B, N, E, heads
     a.head_dim = _head_dim(qkv, heads, head_dim)
     a.qkv, a.cos_tab, a.o, a.lse = _p(qkv), _p(cos_tab), _p(o), _p(lse)
