@@ -795,6 +795,50 @@ int lnx_metrics_table_sizes(int n_tasks, int n_bins0, int n_bins1, int64_t* n_co
 int lnx_metrics_update(const lnx_metrics_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Predictions on the device: what LinnaeusInferenceHandler.predict (linnaeus/inference/handler.py:186-228) does per sample and task
+ * with softmax / topk / .item(), followed by enforce_hierarchical_consistency (linnaeus/inference/postprocessing.py:14-171), as ONE
+ * launch per batch that reads every logit once and writes the final lists.  Nothing is allocated, nothing is read back.
+ * Tasks come FINEST FIRST (taxa_L10, taxa_L20, ...: DATA.TASK_KEYS_H5), n_tasks <= LNX_SOFTCE_MAX_TASKS.
+ *   ordering   value descending, then index ascending; a NaN ranks above every number (the order of lnx_metrics_update).  It is taken
+ *              on the logits as stored (bf16 -> float is exact), so the selected classes are exact.  Columns >= C are never read.
+ *   probs      exp(x - max) / sum exp(x - max) in fp32 over the whole row whatever the storage type (the reference runs softmax in the
+ *              logits' dtype under autocast); a row holding a NaN has NaN probabilities, a -inf entry has probability 0.
+ *   raw        per sample b and task: the n = min(k_b, C) best entries, k_b = k_per_sample[b] clamped to [1, K], or K.
+ *   chain      with consistency != 0, coarsest task first, keeping per sample the "consistent node" of the task above; for the coarsest
+ *              task that is its raw top-1 class.  For a finer task t with raw top-1 class c:
+ *                flag 1  the consistent node above is that task's null_index;
+ *                flag 2  otherwise, parent[c] differs from the consistent node above (-1 always differs);
+ *                flag 0  otherwise: kept, the consistent node becomes c.
+ *              Flagged with null_index >= 0: the result becomes the single entry (null_index, 1.0f), count 1, and the consistent node
+ *              null_index (postprocessing.py:124,141 write 1.0).  Flagged with null_index < 0: kept as it is, consistent node c
+ *              (:128,145).  A coarsest task whose own top-1 is null keeps its raw entries (:153-154) and nullifies all below it.
+ *   outputs    ids / probs [B, n_tasks, K], count / flags [B, n_tasks], all written in full: entries at or beyond count are
+ *              (-1, 0.0f).  ids go through id_map where given (the nullified entry too).  consistency == 0: flags 0, nothing nullified.
+ * -----------------------------------------------------------------------------------*/
+#define LNX_PREDICT_MAX_K 16
+typedef struct lnx_predict_task {
+    const void* logits;    /* [B, ld] rows of the args' dtype, any row alignment */
+    int64_t ld;            /* >= C */
+    int C;
+    const int32_t* parent; /* [C]: class index of this class's parent in the next coarser task, -1 = none; NULL for the coarsest task */
+    int null_index;        /* the null class of this task (linnaeus: 0); < 0 = this task cannot be nullified */
+    const int64_t* id_map; /* [C] class index -> the id written to ids[], or NULL (= the class index) */
+} lnx_predict_task;
+typedef struct lnx_predict_args {
+    int dtype; /* of every task's logits: 0 = fp32, 1 = bf16 */
+    int B, n_tasks;
+    int K; /* 1 .. LNX_PREDICT_MAX_K */
+    int consistency;
+    const int32_t* k_per_sample; /* [B] or NULL (= K) */
+    lnx_predict_task task[LNX_SOFTCE_MAX_TASKS];
+    int64_t* ids;
+    float* probs;
+    int32_t* count;
+    int32_t* flags;
+} lnx_predict_args;
+int lnx_predict(const lnx_predict_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP branch (bf16 storage, C in {32,64,96,128,192}):
  *   out = x + rowscale * gamma * (GELU(ln . W1^T + b1) . W2^T + b2)
  * = pwconv1 -> GELU -> pwconv2 -> LayerScale -> DropPath -> residual (blocks/convnext.py:79-86)

@@ -122,6 +122,18 @@ class MetricsArgs(C.Structure):  # == lnx_metrics_args
                 ("subset_ids", C.c_void_p * 2), ("n_bins", C.c_int * 2), ("counts", C.c_void_p), ("sums", C.c_void_p)]
 
 
+PREDICT_MAX_K = 16  # == LNX_PREDICT_MAX_K
+
+
+class PredictTask(C.Structure):  # == lnx_predict_task
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("C", C.c_int), ("parent", C.c_void_p), ("null_index", C.c_int), ("id_map", C.c_void_p)]
+
+
+class PredictArgs(C.Structure):  # == lnx_predict_args
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("n_tasks", C.c_int), ("K", C.c_int), ("consistency", C.c_int), ("k_per_sample", C.c_void_p),
+                ("task", PredictTask * METRICS_MAX_TASKS), ("ids", C.c_void_p), ("probs", C.c_void_p), ("count", C.c_void_p), ("flags", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -146,6 +158,9 @@ def lib() -> C.CDLL:
         if hasattr(_lib, "lnx_metrics_update"):
             _lib.lnx_metrics_update.argtypes = [C.POINTER(MetricsArgs), C.c_void_p]
             _lib.lnx_metrics_table_sizes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if hasattr(_lib, "lnx_predict"):
+            _lib.lnx_predict.argtypes = [C.POINTER(PredictArgs), C.c_void_p]
+            _lib.lnx_predict.restype = C.c_int
         # A/B runs against an OLDER build (LNX_LIB_PATH=... LNX_LIB_OLDER=1): entry points added since are allowed to be missing; calling
         # one then fails with ctypes' AttributeError
         older = bool(os.environ.get("LNX_LIB_PATH")) and os.environ.get("LNX_LIB_OLDER") == "1"
@@ -182,7 +197,7 @@ EXPORTS = [
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
-    "lnx_metrics_table_sizes", "lnx_metrics_update",
+    "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict",
     "lnx_mix_rows", "lnx_mix_meta",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",

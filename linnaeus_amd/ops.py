@@ -507,3 +507,49 @@ def metrics_update(logits, targets, counts, sums, *, num_classes=None, is_null=N
         raise L.LnxError(f"metrics_update: tables must be contiguous int64 [>= {nc}] / float64 [>= {ns}]")
     a.counts, a.sums = _p(counts), _p(sums)
     L.check(L.lib().lnx_metrics_update(C.byref(a), _stream()), "lnx_metrics_update")
+
+
+def predict_topk(logits, parents, *, K, null_index=0, id_maps=None, k_per_sample=None, consistency=True, num_classes=None, out=None):
+    """One lnx_predict launch: the final top-K (id, probability) lists of every sample and task.  logits: per task [B, >= C] rows of one
+    dtype (fp32 / bf16) with unit column stride (padded views welcome: stride(0) is the ld), tasks FINEST FIRST; parents: per task int32
+    [C] (class -> class of the next coarser task, -1 = none), None for the coarsest; null_index: an int or per task an int / None
+    (= the task cannot be nullified); id_maps: per task int64 [C] or None; k_per_sample: int32 [B] or None; num_classes: per task C
+    (default: the logits' width); out: (ids, probs, count, flags) to write into instead of new tensors.
+    Returns ids int64 [B, T, K], probs fp32 [B, T, K], count int32 [B, T], flags int32 [B, T]; never synchronises."""
+    T = len(logits)
+    if not 1 <= T <= L.METRICS_MAX_TASKS or len(parents) != T:
+        raise L.LnxError(f"predict_topk: {T} tasks (1..{L.METRICS_MAX_TASKS}), {len(parents)} parent tables")
+    nulls = list(null_index) if isinstance(null_index, (list, tuple)) else [null_index] * T
+    if len(nulls) != T or (id_maps is not None and len(id_maps) != T):
+        raise L.LnxError(f"predict_topk: {T} tasks need {T} null indices / id maps")
+    a = L.PredictArgs()
+    a.dtype, a.B, a.n_tasks, a.K, a.consistency = code_of(logits[0]), logits[0].shape[0], T, int(K), int(bool(consistency))
+    dev = logits[0].device
+    for t in range(T):
+        x, par = logits[t], parents[t]
+        ids = id_maps[t] if id_maps is not None else None
+        if x.dim() != 2 or x.shape[0] != a.B or code_of(x) != a.dtype or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise L.LnxError(f"predict_topk: task {t} logits must be [B, C] rows of one dtype with unit column stride, got {tuple(x.shape)} {x.dtype} strides {x.stride()}")
+        Ct = int(num_classes[t]) if num_classes is not None else x.shape[1]
+        if Ct > x.shape[1]:
+            raise L.LnxError(f"predict_topk: task {t} has {x.shape[1]} logit columns, {Ct} classes")
+        if par is not None and (par.dtype != torch.int32 or par.shape != (Ct,) or not par.is_contiguous()):
+            raise L.LnxError(f"predict_topk: task {t} parent table must be contiguous int32 [{Ct}]")
+        if ids is not None and (ids.dtype != torch.int64 or ids.shape != (Ct,) or not ids.is_contiguous()):
+            raise L.LnxError(f"predict_topk: task {t} id map must be contiguous int64 [{Ct}]")
+        k = a.task[t]
+        k.logits, k.ld, k.C = _p(x), (x.stride(0) if a.B > 1 else x.shape[1]), Ct
+        k.parent, k.id_map, k.null_index = _p(par), _p(ids), (-1 if nulls[t] is None else int(nulls[t]))
+    if k_per_sample is not None:
+        if k_per_sample.dtype != torch.int32 or k_per_sample.shape != (a.B,) or not k_per_sample.is_contiguous():
+            raise L.LnxError("predict_topk: k_per_sample must be contiguous int32 [B]")
+        a.k_per_sample = _p(k_per_sample)
+    if out is None:
+        out = (torch.empty(a.B, T, a.K, dtype=torch.int64, device=dev), torch.empty(a.B, T, a.K, dtype=torch.float32, device=dev),
+               torch.empty(a.B, T, dtype=torch.int32, device=dev), torch.empty(a.B, T, dtype=torch.int32, device=dev))
+    for o, dt, shape in zip(out, (torch.int64, torch.float32, torch.int32, torch.int32), ((a.B, T, a.K), (a.B, T, a.K), (a.B, T), (a.B, T))):
+        if o.dtype != dt or tuple(o.shape) != shape or not o.is_contiguous():
+            raise L.LnxError(f"predict_topk: outputs must be contiguous int64 / fp32 [B, T, K] and int32 [B, T] x 2, got {tuple(o.shape)} {o.dtype}")
+    a.ids, a.probs, a.count, a.flags = (_p(o) for o in out)
+    L.check(L.lib().lnx_predict(C.byref(a), _stream()), "lnx_predict")
+    return tuple(out)
