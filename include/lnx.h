@@ -839,6 +839,66 @@ typedef struct lnx_predict_args {
 int lnx_predict(const lnx_predict_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The hierarchical loss of the train / validation step in a fixed number of launches: weighted_hierarchical_loss
+ * (linnaeus/loss/hierarchical_loss.py:24-406) with apply_null_masking / apply_class_weighting / apply_loss_masking
+ * (loss/masking.py:19-465, 469-518, 521-700) and GradientWeighting.forward (loss/gradient_weighting.py:301-358), for every task at once.
+ * Replaces one lnx_softce launch per task and the chain of torch operations on [B] vectors behind it (and autograd's replay of it).
+ * Per task t < n_tasks and row b < B, with the row arithmetic of lnx_softce (same NaN loss / zero gradient for a target outside [0, C)):
+ *   class    target[b], or with soft_target the first maximum of soft_target[b, 0..C) (torch.argmax)
+ *   raw      = crit_weight[class] * (lse * sum_c S[c] - sum_c S[c] x[c]),  S = soft[class, :] or the smoothed one-hot row; 0 where class == ignore_index
+ *   null     = target[b] == 0, or soft_target[b, 0] > 0.5
+ *   keep     = !null || draws[t * B + b] < prob          (prob >= 1: everything is kept, prob <= 0: no null row; draws is read for 0 < prob < 1 only)
+ *   masked   = keep ? raw : 0        (mask_mul != 0, the PHASE1_MASK_NULL_LOSS branch: raw * keep, so that a NaN survives the mask)
+ *   cw       = class_weight[clamp(target, 0, n_cw - 1)] (1 where target >= n_cw), or with soft_target sum_c soft_target[b, c] * class_weight[c]
+ *   nvalid   = count_b(masked != 0)   (before any class weight; mask_mul != 0: B, the reference divides by the batch size there)
+ *   weighted = sum_b(masked * cw^p_w) / max(nvalid, 1e-6) * weights[t];   total = sum_t weighted   (fp32, in task order)
+ *   dlogits[b, c] = go * scale[t] * coef[b] * (exp(x[c] - lse) * sum S - S[c]),  scale[t] = weights[t] / max(nvalid, 1e-6),
+ *                   coef[b] = keep * cw^p_w * crit_weight[class] (0 for an ignored or out-of-range class); a row with coef == 0 is written as zeros
+ * lnx_hier_loss_fwd: two launches -- one workgroup per (row, task), then ONE workgroup that folds every [B] sum in double, each thread a
+ * fixed stride and a fixed LDS tree, so the same input gives the same bits.  lnx_hier_loss_bwd: one launch, reads ws / out of the forward
+ * and the upstream gradient `go` from the device.  Nothing is allocated, nothing is read back.
+ *   ws   [n_tasks][LNX_HL_WS_ROWS][B] floats: raw, lse, sum S, coef, masked * cw^p_cw, masked * cw^p_w, flags (bit 0 null, 1 keep, 2 masked != 0, the class from bit 3)
+ *   out  [LNX_HL_OUT_FLOATS] floats: out[LNX_HL_OUT_x * LNX_SOFTCE_MAX_TASKS + t] for x in RAW_MEAN (mean raw), MASKED_MEAN (mean masked * cw^p_cw),
+ *        WEIGHTED, SCALE; out[LNX_HL_OUT_TOTAL], out[LNX_HL_OUT_INCLUSION] (= 100 * null kept / max(null, 1) over all tasks)
+ *   counts [LNX_HL_COUNTS] int64: nvalid[t] at t, rows with null at LNX_HL_NULL_TOTAL, null and kept at LNX_HL_NULL_INCLUDED
+ * -----------------------------------------------------------------------------------*/
+enum { LNX_HL_WS_RAW = 0, LNX_HL_WS_LSE, LNX_HL_WS_SS, LNX_HL_WS_COEF, LNX_HL_WS_MASKED_CW, LNX_HL_WS_MASKED_W, LNX_HL_WS_FLAGS, LNX_HL_WS_ROWS };
+enum { LNX_HL_OUT_RAW_MEAN = 0, LNX_HL_OUT_MASKED_MEAN, LNX_HL_OUT_WEIGHTED, LNX_HL_OUT_SCALE, LNX_HL_OUT_TOTAL = 32, LNX_HL_OUT_INCLUSION = 33,
+       LNX_HL_OUT_FLOATS = 40 };
+enum { LNX_HL_NULL_TOTAL = 8, LNX_HL_NULL_INCLUDED = 9, LNX_HL_COUNTS = 10 };
+typedef struct lnx_hier_loss_task {
+    const void* logits;         /* [B, ld] of the args' dtype */
+    int64_t ld;                 /* >= C */
+    int C;
+    const int64_t* target;      /* [B] class indices, or NULL with soft_target */
+    const float* soft_target;   /* [B, ldt] mixup / cutmix targets, or NULL with target */
+    int64_t ldt;                /* >= C */
+    const float* soft;          /* [C, C] soft-label matrix, or NULL = one-hot with uniform smoothing */
+    float smoothing;            /* soft == NULL only, in [0, 1) */
+    const float* crit_weight;   /* [C] class weight of the criterion itself, or NULL */
+    int64_t ignore_index;       /* < 0: none */
+    const float* class_weight;  /* [n_cw] class weights of the task weighting, or NULL (then p_cw = p_w = 0) */
+    int n_cw;                   /* >= C with soft_target */
+    int p_cw, p_w;              /* 0..3, p_cw <= p_w: the power of cw in the logged masked loss and in the weighted loss (finding F13) */
+    float* dlogits;             /* lnx_hier_loss_bwd: [B, ldd] fp32, columns >= C are not written; NULL = no gradient for this task */
+    int64_t ldd;
+} lnx_hier_loss_task;
+typedef struct lnx_hier_loss_args {
+    int dtype;            /* of every task's logits: 0 = fp32, 1 = bf16 */
+    int B, n_tasks;       /* n_tasks <= LNX_SOFTCE_MAX_TASKS */
+    float prob;           /* inclusion probability of null rows */
+    int mask_mul;         /* != 0: masked = raw * keep and nvalid = B (PHASE1_MASK_NULL_LOSS in training) */
+    const float* draws;   /* [n_tasks, B] uniform draws; required when 0 < prob < 1 */
+    const float* weights; /* [n_tasks] task weights on the device */
+    float* ws;
+    float* out;
+    int64_t* counts;
+    lnx_hier_loss_task task[LNX_SOFTCE_MAX_TASKS];
+} lnx_hier_loss_args;
+int lnx_hier_loss_fwd(const lnx_hier_loss_args* args, void* stream);
+int lnx_hier_loss_bwd(const lnx_hier_loss_args* args, const float* go_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP branch (bf16 storage, C in {32,64,96,128,192}):
  *   out = x + rowscale * gamma * (GELU(ln . W1^T + b1) . W2^T + b2)
  * = pwconv1 -> GELU -> pwconv2 -> LayerScale -> DropPath -> residual (blocks/convnext.py:79-86)

@@ -134,6 +134,24 @@ class PredictArgs(C.Structure):  # == lnx_predict_args
                 ("task", PredictTask * METRICS_MAX_TASKS), ("ids", C.c_void_p), ("probs", C.c_void_p), ("count", C.c_void_p), ("flags", C.c_void_p)]
 
 
+# lnx_hier_loss_fwd / lnx_hier_loss_bwd: rows of ws, offsets into out / counts (the LNX_HL_* enums of include/lnx.h)
+HL_WS_RAW, HL_WS_LSE, HL_WS_SS, HL_WS_COEF, HL_WS_MASKED_CW, HL_WS_MASKED_W, HL_WS_FLAGS, HL_WS_ROWS = range(8)
+HL_OUT_RAW_MEAN, HL_OUT_MASKED_MEAN, HL_OUT_WEIGHTED, HL_OUT_SCALE = range(4)
+HL_OUT_TOTAL, HL_OUT_INCLUSION, HL_OUT_FLOATS = 32, 33, 40
+HL_NULL_TOTAL, HL_NULL_INCLUDED, HL_COUNTS = 8, 9, 10
+
+
+class HierLossTask(C.Structure):  # == lnx_hier_loss_task
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("C", C.c_int), ("target", C.c_void_p), ("soft_target", C.c_void_p), ("ldt", C.c_int64),
+                ("soft", C.c_void_p), ("smoothing", C.c_float), ("crit_weight", C.c_void_p), ("ignore_index", C.c_int64), ("class_weight", C.c_void_p),
+                ("n_cw", C.c_int), ("p_cw", C.c_int), ("p_w", C.c_int), ("dlogits", C.c_void_p), ("ldd", C.c_int64)]
+
+
+class HierLossArgs(C.Structure):  # == lnx_hier_loss_args
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("n_tasks", C.c_int), ("prob", C.c_float), ("mask_mul", C.c_int), ("draws", C.c_void_p),
+                ("weights", C.c_void_p), ("ws", C.c_void_p), ("out", C.c_void_p), ("counts", C.c_void_p), ("task", HierLossTask * METRICS_MAX_TASKS)]
+
+
 _lib = None
 
 
@@ -161,6 +179,9 @@ def lib() -> C.CDLL:
         if hasattr(_lib, "lnx_predict"):
             _lib.lnx_predict.argtypes = [C.POINTER(PredictArgs), C.c_void_p]
             _lib.lnx_predict.restype = C.c_int
+        if hasattr(_lib, "lnx_hier_loss_fwd"):
+            _lib.lnx_hier_loss_fwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p]
+            _lib.lnx_hier_loss_bwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p, C.c_void_p]
         # A/B runs against an OLDER build (LNX_LIB_PATH=... LNX_LIB_OLDER=1): entry points added since are allowed to be missing; calling
         # one then fails with ctypes' AttributeError
         older = bool(os.environ.get("LNX_LIB_PATH")) and os.environ.get("LNX_LIB_OLDER") == "1"
@@ -197,7 +218,7 @@ EXPORTS = [
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
-    "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict",
+    "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_mix_rows", "lnx_mix_meta",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",

@@ -629,9 +629,16 @@ class GradientWeighting(nn.Module):
 
 
 def weighted_hierarchical_loss(outputs, targets, criteria, task_weighting, ops_schedule, current_step: int, subset_ids=None, mixed_subset_ids=None,
-                               is_validation: bool = False, logger=None, config=None, *, sync_components: bool = True, _coin=None):
+                               is_validation: bool = False, logger=None, config=None, *, sync_components: bool = True, _coin=None, fused: bool = False):
     """(total_loss, loss_components, task_weights) of the reference's train / validation step.  With
-    `sync_components=False` the logging values stay device scalars (no host sync in the step)."""
+    `sync_components=False` the logging values stay device scalars (no host sync in the step).  `fused=True` runs the same
+    function as FusedHierarchicalLoss (three launches whatever the number of tasks), built once and kept on `task_weighting`."""
+    if fused:
+        cached = getattr(task_weighting, "_fused_loss", None)
+        if cached is None or cached[0] is not criteria or cached[1] is not config:
+            cached = (criteria, config, FusedHierarchicalLoss(task_weighting.task_keys, criteria, task_weighting, config))
+            task_weighting._fused_loss = cached  # rebuilt when another criteria dict or config object is passed
+        return cached[2](outputs, targets, ops_schedule, current_step, is_validation=is_validation, sync_components=sync_components, _coin=_coin)
     keys = _sorted_tasks(outputs)
     if not isinstance(targets, dict):
         targets = dict(zip(keys, targets))
@@ -661,3 +668,259 @@ def weighted_hierarchical_loss(outputs, targets, criteria, task_weighting, ops_s
     comps = {"total": val(total), "tasks": {t: val(per[t].mean()) for t in keys}, "masked_tasks": {t: val(after_cw[t].mean()) for t in keys},
              "weighted_tasks": {t: val(weighted[t]) for t in keys}, "raw_per_sample_losses": raw, "null_masking": stats}
     return total, comps, task_weights
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The same function in a fixed number of launches (lnx_hier_loss_fwd / lnx_hier_loss_bwd, csrc/hier_loss.hip): two forward, one
+# backward, whatever the number of tasks and the batch size, and no host synchronisation.  What the composed path above decides with
+# Python conditions per step, class_weight_powers() decides once per call into two small integers per task.
+# ----------------------------------------------------------------------------------------------------------------------
+def class_weight_powers(task_weighting, config, is_validation: bool, task: str):
+    """(p_cw, p_w): how often the composed path multiplies `task`'s per-sample class weight into the loss it logs as
+    masked_tasks, and into the weighted loss (finding F13).  apply_loss_masking multiplies once unless the PHASE1 training branch
+    skips it; weighted_hierarchical_loss once more under LOSS.GRAD_WEIGHTING.CLASS.TRAIN / .VAL (True when the config has no such
+    node); GradientWeighting.forward once more in the weighted loss only."""
+    cw = task_weighting.class_weights
+    if not cw or task not in cw:
+        return 0, 0
+    phase1 = bool(config is not None and getattr(config.TRAIN, "PHASE1_MASK_NULL_LOSS", False)) and not is_validation
+    try:
+        apply_cw = config.LOSS.GRAD_WEIGHTING.CLASS.TRAIN if not is_validation else config.LOSS.GRAD_WEIGHTING.CLASS.VAL
+    except Exception:
+        apply_cw = True
+    p_cw = (0 if phase1 else 1) + (1 if apply_cw else 0)
+    return p_cw, p_cw + 1
+
+
+class _HierLoss(torch.autograd.Function):
+    """total loss of all tasks; the gradients of all tasks are views of one flat buffer that one launch fills"""
+
+    @staticmethod
+    def forward(ctx, owner, call, *logits):
+        a, keep, out = call
+        st = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
+        L.check(L.lib().lnx_hier_loss_fwd(C.byref(a), st), "lnx_hier_loss_fwd")
+        ctx.call = call
+        ctx.meta = [(lg.shape, lg.dtype, lg.requires_grad) for lg in logits]
+        return out[L.HL_OUT_TOTAL]
+
+    @staticmethod
+    def backward(ctx, go):
+        a, keep, out = ctx.call
+        sizes = [shp[0] * shp[1] if need else 0 for shp, _, need in ctx.meta]
+        if not any(sizes):
+            return (None, None) + (None,) * len(sizes)
+        flat = torch.empty(sum(sizes), device=out.device, dtype=torch.float32)
+        grads, off = [], 0
+        for i, ((shp, dt, need), n) in enumerate(zip(ctx.meta, sizes)):
+            d = flat[off:off + n].view(shp) if n else None
+            off += n
+            a.task[i].dlogits, a.task[i].ldd = _ptr(d), (shp[1] if n else 0)
+            grads.append(d)
+        go = go.to(torch.float32).contiguous()
+        st = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
+        L.check(L.lib().lnx_hier_loss_bwd(C.byref(a), _ptr(go), st), "lnx_hier_loss_bwd")
+        if any(dt != torch.float32 for _, dt, need in ctx.meta if need):  # bf16 logits: one cast of the flat buffer per storage type
+            cast = {dt: flat.to(dt) for _, dt, need in ctx.meta if need and dt != torch.float32}
+            off = 0
+            for i, ((shp, dt, need), n) in enumerate(zip(ctx.meta, sizes)):
+                if n and dt != torch.float32:
+                    grads[i] = cast[dt][off:off + n].view(shp)
+                off += n
+        return (None, None) + tuple(grads)
+
+
+class FusedHierarchicalLoss:
+    """weighted_hierarchical_loss (above; loss/hierarchical_loss.py:24-406) as lnx_hier_loss_fwd / lnx_hier_loss_bwd: criterion, null
+    masking, class weighting with finding F13's multiplicities, valid-sample denominators, static or GradNorm task weights, the total,
+    every logged component and the null statistics in two launches, the gradients of every task's logits in one more.
+
+    Supported criteria: TaxonomyAwareLabelSmoothingCE, and torch.nn.CrossEntropyLoss(reduction="none", label_smoothing=eps) without a
+    class weight of its own.  Anything else, dict-valued head outputs and CPU tensors are refused by name (LnxError): there is no
+    fall-back to the composed path."""
+
+    def __init__(self, task_keys, criteria, task_weighting, config=None):
+        self.task_keys = list(task_keys)
+        if not 1 <= len(self.task_keys) <= SOFTCE_MAX_TASKS:
+            raise L.LnxError(f"FusedHierarchicalLoss: {len(self.task_keys)} tasks (1..{SOFTCE_MAX_TASKS})")
+        if list(task_weighting.task_keys) != self.task_keys:
+            raise L.LnxError(f"FusedHierarchicalLoss: task_keys {self.task_keys} differ from the task weighting's {list(task_weighting.task_keys)}")
+        self.criteria, self.task_weighting, self.config = criteria, task_weighting, config
+        self._crit = {}
+        for t in self.task_keys:
+            if t not in criteria:
+                raise L.LnxError(f"FusedHierarchicalLoss: no criterion for task {t!r}")
+            crit = criteria[t]
+            if isinstance(crit, TaxonomyAwareLabelSmoothingCE):
+                self._crit[t] = "soft"
+            elif type(crit) is nn.CrossEntropyLoss:
+                if crit.reduction != "none":
+                    raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: CrossEntropyLoss(reduction={crit.reduction!r}) is not supported (per-sample losses need reduction='none')")
+                if crit.weight is not None:
+                    raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: CrossEntropyLoss with a class weight is not supported")
+                if not 0.0 <= float(crit.label_smoothing) < 1.0:
+                    raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: label_smoothing={crit.label_smoothing} outside [0, 1)")
+                self._crit[t] = "ce"
+            else:
+                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: criterion {type(crit).__name__} is not supported "
+                                 "(TaxonomyAwareLabelSmoothingCE or torch.nn.CrossEntropyLoss(reduction='none'))")
+        self._dev = None
+        self._cw = {}      # task -> (device vector, length): uploaded once
+        self._static_w = None
+        self._draws = {}   # (n_tasks, B) -> [n_tasks, B] buffer of uniform draws
+        for crit in criteria.values():  # upload at construction when the criteria already live on a GPU
+            sl = getattr(crit, "soft_labels", None)
+            if isinstance(sl, torch.Tensor) and sl.is_cuda:
+                self._prepare(sl.device)
+                break
+
+    def _prepare(self, dev):
+        """what does not change from step to step: class-weight vectors, static task weights, the criteria's buffers on `dev`"""
+        self._dev = dev
+        tw = self.task_weighting
+        self._cw = {}
+        for t in self.task_keys:
+            crit = self.criteria[t]
+            if self._crit[t] == "soft":
+                if crit.soft_labels.device != dev:
+                    crit.soft_labels = crit.soft_labels.to(dev)
+                if crit.apply_class_weights and crit.weight is not None and crit.weight.device != dev:
+                    crit.weight = crit.class_weight = crit.weight.to(dev)
+            if tw.class_weights and t in tw.class_weights:
+                d = tw.class_weights[t]
+                nc = crit.num_classes if self._crit[t] == "soft" else 0
+                n = max(int(max(d.keys(), default=0)) + 1, 1, nc)  # (entries past _sample_weights' vector are its default, 1)
+                self._cw[t] = (_class_weight_vector(d, n, dev), n)
+        if tw.gradnorm is None:
+            self._static_w = tw._normalize_weights(tw.task_weights).to(torch.float32).to(dev)
+            self._static_w_host = dict(zip(self.task_keys, tw._normalize_weights(tw.task_weights).tolist()))
+        elif tw.gradnorm.task_weights.device != dev:
+            tw.gradnorm.to(dev)
+
+    def __call__(self, outputs, targets, ops_schedule, current_step, is_validation: bool = False, sync_components: bool = False, _coin=None):
+        keys = _sorted_tasks(outputs)
+        if sorted(keys) != sorted(self.task_keys):
+            raise L.LnxError(f"FusedHierarchicalLoss: outputs hold tasks {keys}, built for {self.task_keys}")
+        if not isinstance(targets, dict):
+            targets = dict(zip(keys, targets))
+        for t in keys:
+            if isinstance(outputs[t], dict):
+                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: dict-valued head outputs (ConditionalClassifierHead refinement) are not supported")
+            if not isinstance(outputs[t], torch.Tensor) or outputs[t].dim() != 2:
+                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: logits must be a [B, C] tensor")
+            if not outputs[t].is_cuda or not targets[t].is_cuda:
+                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: CPU tensors are not supported (logits and targets must be on the GPU)")
+        first = outputs[self.task_keys[0]]
+        dev, B, dtype = first.device, first.shape[0], first.dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise L.LnxError(f"FusedHierarchicalLoss: logits dtype {dtype} is not supported (float32 or bfloat16)")
+        if self._dev != dev:
+            self._prepare(dev)
+        config, tw, T = self.config, self.task_weighting, len(self.task_keys)
+        phase1 = bool(config is not None and getattr(config.TRAIN, "PHASE1_MASK_NULL_LOSS", False))
+        p1_train = phase1 and not is_validation
+        if is_validation:
+            prob = 1.0
+        elif phase1:
+            prob = 0.0
+        else:
+            prob = float(ops_schedule.get_null_mask_prob(current_step))
+
+        # one allocation per call for everything the launches write (the caching allocator: no launch, no synchronisation); the
+        # per-sample losses handed back and the rows the backward reads live in it, so a later call never overwrites them
+        buf = torch.empty(2 * L.HL_COUNTS + L.HL_OUT_FLOATS + L.HL_WS_ROWS * T * B, device=dev, dtype=torch.float32)
+        counts = buf[:2 * L.HL_COUNTS].view(torch.int64)
+        out = buf[2 * L.HL_COUNTS:2 * L.HL_COUNTS + L.HL_OUT_FLOATS]
+        ws = buf[2 * L.HL_COUNTS + L.HL_OUT_FLOATS:].view(T, L.HL_WS_ROWS, B)
+        draws = None
+        if 0.0 < prob < 1.0:
+            draws = self._draws.get((T, B))
+            if draws is None or draws.device != dev:
+                draws = self._draws[(T, B)] = torch.empty(T, B, device=dev, dtype=torch.float32)
+            for t in keys:  # in the composed path's order, so that the same seed keeps the same rows
+                row = draws[self.task_keys.index(t)]
+                if _coin is not None:
+                    row.copy_(_coin[t])
+                else:
+                    torch.rand(B, out=row)
+        weights = tw.gradnorm.task_weights if tw.gradnorm is not None else self._static_w
+
+        a = L.HierLossArgs()
+        a.dtype, a.B, a.n_tasks = (L.BF16 if dtype == torch.bfloat16 else L.F32), B, T
+        a.prob, a.mask_mul = prob, int(p1_train)
+        a.draws, a.weights = _ptr(draws), _ptr(weights)
+        a.ws, a.out, a.counts = _ptr(ws), _ptr(out), _ptr(counts)
+        keep = [buf, draws, weights]  # what the launches read or write must outlive them
+        logits = []
+        for i, t in enumerate(self.task_keys):
+            x, y, crit, k = outputs[t], targets[t], self.criteria[t], a.task[i]
+            if x.shape[0] != B or x.dtype != dtype:
+                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: logits {tuple(x.shape)} {x.dtype}, the first task has batch {B} and {dtype}")
+            if x.stride(1) != 1:
+                x = x.contiguous()
+            k.logits, k.ld, k.C = _ptr(x), x.stride(0), x.shape[1]
+            if self._crit[t] == "soft":
+                if x.shape[1] != crit.num_classes:
+                    raise ValueError(f"Logits dimension mismatch. Expected {crit.num_classes} classes, got {x.shape[1]}.")
+                k.soft, k.smoothing = _ptr(crit.soft_labels), 0.0
+                k.crit_weight = _ptr(crit.weight) if (crit.apply_class_weights and crit.weight is not None) else None
+                k.ignore_index = -1 if crit.ignore_index is None else int(crit.ignore_index)
+            else:
+                if y.dim() != 1:
+                    raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: CrossEntropyLoss with [B, C] targets is not supported")
+                k.soft, k.smoothing, k.crit_weight = None, float(crit.label_smoothing), None
+                k.ignore_index = int(crit.ignore_index) if crit.ignore_index >= 0 else -1
+            if y.dim() == 1:
+                y = y.to(torch.long).contiguous()
+                k.target, k.soft_target, k.ldt = _ptr(y), None, 0
+            elif y.dim() == 2 and y.shape[1] == x.shape[1]:
+                y = y.float()
+                if y.stride(1) != 1:
+                    y = y.contiguous()
+                k.target, k.soft_target, k.ldt = None, _ptr(y), y.stride(0)
+            else:
+                raise ValueError(f"Target tensor has invalid shape {tuple(y.shape)}. Expected 1D indices or [B, C] one-hot/soft-representing-one-class.")
+            if y.shape[0] != B:
+                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: {y.shape[0]} targets for a batch of {B}")
+            k.p_cw, k.p_w = class_weight_powers(tw, config, is_validation, t)
+            if t in self._cw and k.p_w:
+                k.class_weight, k.n_cw = _ptr(self._cw[t][0]), self._cw[t][1]
+            else:
+                k.class_weight, k.n_cw = None, 0
+            k.dlogits, k.ldd = None, 0
+            keep += [x, y]
+            logits.append(outputs[t])
+
+        call = (a, keep, out)
+        if torch.is_grad_enabled() and any(lg.requires_grad for lg in logits):
+            total = _HierLoss.apply(self, call, *logits)
+        else:
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            L.check(L.lib().lnx_hier_loss_fwd(C.byref(a), st), "lnx_hier_loss_fwd")
+            total = out[L.HL_OUT_TOTAL]
+
+        idx = {t: i for i, t in enumerate(self.task_keys)}
+        M = SOFTCE_MAX_TASKS
+        stats = {}
+        if p1_train:
+            zero = torch.zeros((), device=dev)
+            stats.update(null_samples_total=zero, null_samples_included=zero, inclusion_percentage=0.0, null_mask_prob=0.0)
+        else:
+            stats.update(null_mask_prob=prob, null_samples_total=counts[L.HL_NULL_TOTAL], null_samples_included=counts[L.HL_NULL_INCLUDED],
+                         inclusion_percentage=out[L.HL_OUT_INCLUSION], num_valid_samples_per_task={t: counts[idx[t]] for t in keys})
+        stats["phase1_active"] = p1_train
+        if sync_components:  # one read of the 40 floats
+            host = out.tolist()
+            val = lambda j: host[j]  # noqa: E731
+        else:
+            det = out.detach()
+            val = lambda j: det[j]  # noqa: E731
+        comps = {"total": val(L.HL_OUT_TOTAL), "tasks": {t: val(L.HL_OUT_RAW_MEAN * M + idx[t]) for t in keys},
+                 "masked_tasks": {t: val(L.HL_OUT_MASKED_MEAN * M + idx[t]) for t in keys},
+                 "weighted_tasks": {t: val(L.HL_OUT_WEIGHTED * M + idx[t]) for t in keys},
+                 "raw_per_sample_losses": {t: ws[idx[t], L.HL_WS_RAW] for t in keys}, "null_masking": stats}
+        if tw.gradnorm is not None:
+            task_weights = {t: weights[i] for i, t in enumerate(self.task_keys)}
+        else:
+            task_weights = dict(self._static_w_host)
+        return total, comps, task_weights
