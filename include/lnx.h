@@ -839,6 +839,61 @@ typedef struct lnx_predict_args {
 int lnx_predict(const lnx_predict_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Image preprocessing on the device: what preprocess_image_batch / preprocess_single_image (linnaeus/inference/preprocessing.py:29-82)
+ * do per image on one CPU thread -- TF.resize of a PIL image (Pillow's Image.resize on 8-bit RGB), TF.to_tensor, TF.normalize, then
+ * torch.stack and a host-to-device copy -- for a whole batch of images of different sizes in at most two launches, in Pillow's own
+ * integer arithmetic: the result equals the reference's bit for bit.
+ *   bilinear / bicubic  two separable passes in 22-bit fixed point with a uint8 rounding between them.  One axis in -> out, in double:
+ *                       scale = in / out, fs = max(scale, 1), support = S * fs (S = 1 bilinear, 2 bicubic), taps = 2 * ceil(support) + 1;
+ *                       per output xx: center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0),
+ *                       xmax = min((int)(center + support + 0.5), in), n = xmax - xmin; w[x] = f((x + xmin - center + 0.5) * (1 / fs)),
+ *                       divided by their in-order sum when that is not 0; k[x] = (int)(w * 2^22 + 0.5) (w < 0: - 0.5).
+ *                       A pass: out = clamp((2^21 + sum_x src[xmin + x] * k[x]) >> 22, 0, 255), int32.  Horizontal first, only where the
+ *                       width changes, into `scratch`; then vertical, only where the height changes.
+ *   nearest             per axis a = in / out, xo = a * 0.5; per output in turn: index = min((int)xo, in - 1), xo += a.  (torchvision's
+ *                       nearest_exact is the same for PIL inputs.)  One launch, no scratch.
+ *   to_tensor/normalize out[i, c, y, x] = ((float)u8 / 255.0f - mean[c]) / std[c], both divisions correctly rounded.
+ * lnx_resize_taps / lnx_resize_coeffs are host functions and need no GPU: the tables of one axis.  k is [out, taps] int32, zero beyond
+ * n; bounds is [out, 2] int32 = (xmin, n).  Nearest: taps is 1, k is not written (may be NULL) and bounds is [out] source indices.
+ *
+ * The batch reaches the device as ONE buffer (`blob`, one host-to-device copy made by the caller): the descriptor table, the tables of
+ * every distinct (in, out) pair and the packed [h, w, 3] uint8 sources, addressed by byte offsets.  lnx_preprocess_scratch_bytes fills
+ * y0 / rows / htaps / vtaps / scratch of every descriptor from its h and w and returns the scratch the batch needs (< 0 on refusal);
+ * lnx_preprocess checks every descriptor against that on the host copy before any launch, so the host copy and the one in the blob
+ * must hold the same bytes.  Launches: bilinear / bicubic one per pass that any image needs (the vertical one also normalizes and
+ * writes CHW, and runs as a copy for images whose height already fits); nearest one.  Nothing is allocated, nothing is read back.
+ * -----------------------------------------------------------------------------------*/
+#define LNX_RESIZE_NEAREST 0
+#define LNX_RESIZE_BILINEAR 1
+#define LNX_RESIZE_BICUBIC 2
+#define LNX_PREPROCESS_MAX_SIDE 16384
+int lnx_resize_taps(int in_size, int out_size, int filter); /* 0 on refusal */
+int lnx_resize_coeffs(int in_size, int out_size, int filter, int32_t* k, int32_t* bounds);
+typedef struct lnx_preprocess_image {
+    int64_t src;     /* blob: [h, w, 3] uint8 */
+    int64_t hk, hb;  /* blob: tables of the horizontal axis w -> W (multiples of 4; not read where w == W; nearest: hb alone) */
+    int64_t vk, vb;  /* blob: tables of the vertical axis h -> H (not read where h == H) */
+    int64_t scratch; /* scratch: the intermediate [rows, W, 3] uint8 of this image (set by lnx_preprocess_scratch_bytes) */
+    int32_t h, w;    /* 1 .. LNX_PREPROCESS_MAX_SIDE */
+    int32_t htaps, vtaps; /* lnx_resize_taps of the two axes, 0 where the pass does not run (set by lnx_preprocess_scratch_bytes) */
+    int32_t y0, rows;     /* the source rows the vertical pass reads, [y0, y0 + rows): all the horizontal pass produces (set likewise) */
+} lnx_preprocess_image;
+typedef struct lnx_preprocess_args {
+    int n, H, W;  /* images; output sides, 1 .. LNX_PREPROCESS_MAX_SIDE */
+    int filter;   /* LNX_RESIZE_* */
+    const lnx_preprocess_image* images; /* HOST copy of the descriptor table [n] */
+    const void* blob;                   /* device, 16-byte aligned */
+    int64_t blob_bytes;
+    int64_t images_off; /* blob: the device copy of the descriptor table (multiple of 8) */
+    void* scratch;      /* device; may be NULL when scratch_bytes is 0 */
+    int64_t scratch_bytes;
+    float mean[3], std[3]; /* std != 0 */
+    float* out;            /* [n, 3, H, W] fp32 */
+} lnx_preprocess_args;
+int64_t lnx_preprocess_scratch_bytes(lnx_preprocess_image* images, int n, int H, int W, int filter);
+int lnx_preprocess(const lnx_preprocess_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The hierarchical loss of the train / validation step in a fixed number of launches: weighted_hierarchical_loss
  * (linnaeus/loss/hierarchical_loss.py:24-406) with apply_null_masking / apply_class_weighting / apply_loss_masking
  * (loss/masking.py:19-465, 469-518, 521-700) and GradientWeighting.forward (loss/gradient_weighting.py:301-358), for every task at once.

@@ -14,4 +14,4 @@ from .config import ConfigNode, arch_config, default_config  # noqa: F401
 from .registry import build_model, create_model, install_into_linnaeus, register_head, register_model  # noqa: F401
 from .model import mFormerV1  # noqa: F401
 from . import autobatch, inference, loss, metrics, optim, prefetch  # noqa: F401
-from .inference import DevicePredictor  # noqa: F401
+from .inference import DevicePredictor, DevicePreprocessor  # noqa: F401

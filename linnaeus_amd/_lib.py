@@ -134,6 +134,22 @@ class PredictArgs(C.Structure):  # == lnx_predict_args
                 ("task", PredictTask * METRICS_MAX_TASKS), ("ids", C.c_void_p), ("probs", C.c_void_p), ("count", C.c_void_p), ("flags", C.c_void_p)]
 
 
+# lnx_preprocess: filter codes (the LNX_RESIZE_* of include/lnx.h) and the largest side of a source or output image
+RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC = range(3)
+PREPROCESS_MAX_SIDE = 16384  # == LNX_PREPROCESS_MAX_SIDE
+
+
+class PreprocessImage(C.Structure):  # == lnx_preprocess_image
+    _fields_ = [("src", C.c_int64), ("hk", C.c_int64), ("hb", C.c_int64), ("vk", C.c_int64), ("vb", C.c_int64), ("scratch", C.c_int64),
+                ("h", C.c_int32), ("w", C.c_int32), ("htaps", C.c_int32), ("vtaps", C.c_int32), ("y0", C.c_int32), ("rows", C.c_int32)]
+
+
+class PreprocessArgs(C.Structure):  # == lnx_preprocess_args
+    _fields_ = [("n", C.c_int), ("H", C.c_int), ("W", C.c_int), ("filter", C.c_int), ("images", C.POINTER(PreprocessImage)), ("blob", C.c_void_p),
+                ("blob_bytes", C.c_int64), ("images_off", C.c_int64), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64),
+                ("mean", C.c_float * 3), ("std", C.c_float * 3), ("out", C.c_void_p)]
+
+
 # lnx_hier_loss_fwd / lnx_hier_loss_bwd: rows of ws, offsets into out / counts (the LNX_HL_* enums of include/lnx.h)
 HL_WS_RAW, HL_WS_LSE, HL_WS_SS, HL_WS_COEF, HL_WS_MASKED_CW, HL_WS_MASKED_W, HL_WS_FLAGS, HL_WS_ROWS = range(8)
 HL_OUT_RAW_MEAN, HL_OUT_MASKED_MEAN, HL_OUT_WEIGHTED, HL_OUT_SCALE = range(4)
@@ -182,6 +198,13 @@ def lib() -> C.CDLL:
         if hasattr(_lib, "lnx_hier_loss_fwd"):
             _lib.lnx_hier_loss_fwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p]
             _lib.lnx_hier_loss_bwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p, C.c_void_p]
+        if hasattr(_lib, "lnx_preprocess"):
+            _lib.lnx_resize_taps.argtypes = [C.c_int, C.c_int, C.c_int]
+            _lib.lnx_resize_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            _lib.lnx_preprocess_scratch_bytes.argtypes = [C.POINTER(PreprocessImage), C.c_int, C.c_int, C.c_int, C.c_int]
+            _lib.lnx_preprocess_scratch_bytes.restype = C.c_int64
+            _lib.lnx_preprocess.argtypes = [C.POINTER(PreprocessArgs), C.c_void_p]
+            _lib.lnx_preprocess.restype = C.c_int
         # A/B runs against an OLDER build (LNX_LIB_PATH=... LNX_LIB_OLDER=1): entry points added since are allowed to be missing; calling
         # one then fails with ctypes' AttributeError
         older = bool(os.environ.get("LNX_LIB_PATH")) and os.environ.get("LNX_LIB_OLDER") == "1"
@@ -218,7 +241,7 @@ EXPORTS = [
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
-    "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
+    "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_mix_rows", "lnx_mix_meta",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",

@@ -1,4 +1,7 @@
-"""Predictions on the device: one HIP launch per batch from {task: logits} to the final top-k lists, no host synchronisation.
+"""Inference on the device.  DevicePreprocessor: a batch of images of any sizes -> the normalized fp32 input tensor in at most two HIP
+launches, bit-identical to the reference's PIL / torchvision recipe (inference/preprocessing.py:29-82).  DevicePredictor, below:
+
+Predictions on the device: one HIP launch per batch from {task: logits} to the final top-k lists, no host synchronisation.
 
 DevicePredictor does what the reference's LinnaeusInferenceHandler.predict does after the forward (inference/handler.py:186-228: per
 sample and task softmax, topk and two .item() per kept entry) and then enforce_hierarchical_consistency
@@ -11,8 +14,10 @@ metadata preprocessing and artifact loading are the caller's.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -191,3 +196,169 @@ class DevicePredictor:
         count_h = both[2 * n: 2 * n + B * T].view(B, T).tolist()
         return [[(self.task_keys[t], list(zip(ids_h[b][t][: count_h[b][t]], probs_h[b][t][: count_h[b][t]]))) for t in range(T - 1, -1, -1)]
                 for b in range(B)]
+
+
+class DevicePreprocessor:
+    """What the reference's preprocess_image_batch does (inference/preprocessing.py:29-82: per image TF.resize of a PIL image,
+    TF.to_tensor, TF.normalize, then torch.stack and a pageable copy) with lnx_preprocess: the whole batch travels to the device in ONE
+    copy from pinned memory and becomes fp32 [N, 3, H, W] there in at most two launches, in Pillow's own fixed-point arithmetic, so the
+    result is the reference's bit for bit.  Nothing synchronises the device.
+
+    What differs from the reference: an unknown interpolation name is refused (the reference silently takes bilinear), and so is an
+    image with other than three channels; images may also be uint8 [h, w, 3] numpy arrays or CPU tensors; metadata preprocessing
+    (preprocess_metadata_batch) stays the caller's."""
+
+    FILTERS = {"nearest": L.RESIZE_NEAREST, "nearest_exact": L.RESIZE_NEAREST, "bilinear": L.RESIZE_BILINEAR, "bicubic": L.RESIZE_BICUBIC}
+    _ALIGN = 16
+
+    def __init__(self, image_size=(3, 224, 224), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), interpolation: str = "bilinear", device=None):
+        """image_size: (3, H, W) as INPUT.image_size of the reference's inference config; mean / std: per channel; interpolation:
+        bilinear, bicubic, nearest or nearest_exact (the same as nearest for PIL inputs); device: default the current one."""
+        size = [int(v) for v in image_size]
+        if len(size) != 3 or size[0] != 3 or not all(1 <= v <= L.PREPROCESS_MAX_SIDE for v in size[1:]):
+            raise L.LnxError(f"DevicePreprocessor: image_size={tuple(image_size)}; expected (3, H, W) with sides in 1..{L.PREPROCESS_MAX_SIDE}")
+        name = str(interpolation).lower()
+        if name not in self.FILTERS:
+            raise L.LnxError(f"DevicePreprocessor: unknown interpolation {interpolation!r} (one of {sorted(self.FILTERS)})")
+        self.H, self.W = size[1], size[2]
+        self.interpolation, self.filter = name, self.FILTERS[name]
+        self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
+        if len(self.mean) != 3 or len(self.std) != 3 or any(C.c_float(v).value == 0.0 for v in self.std):
+            raise L.LnxError(f"DevicePreprocessor: mean={mean} std={std}; three values each, no zero std")
+        self.device = device
+        self._tables: Dict[tuple, np.ndarray] = {}  # (in, out) -> the axis tables as one int32 array (k rows, then bounds)
+        self._pinned = [None, None]                 # two staging buffers used in turn, each with the event of its last copy
+        self._copied = [None, None]
+        self._turn = 0
+        self._blob = self._scratch = self._done = None
+        self.scratch_bytes = 0  # what the last call needed
+
+    @classmethod
+    def from_input_config(cls, input_cfg, device=None):
+        """input_cfg: the reference's InputConfig or a mapping with image_size, image_mean, image_std, image_interpolation."""
+        get = input_cfg.get if isinstance(input_cfg, dict) else lambda k: getattr(input_cfg, k)
+        return cls(get("image_size"), get("image_mean"), get("image_std"), get("image_interpolation"), device=device)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _as_array(img, i: int) -> np.ndarray:
+        if isinstance(img, (bytes, bytearray, memoryview)):  # _decode_image (preprocessing.py:19-26)
+            from io import BytesIO
+
+            from PIL import Image
+
+            try:
+                img = Image.open(BytesIO(img)).convert("RGB")
+            except Exception as e:
+                raise ValueError("Invalid image data") from e
+        if isinstance(img, torch.Tensor):
+            if img.is_cuda:
+                raise L.LnxError(f"DevicePreprocessor: image {i} is a device tensor; sources are host uint8 [h, w, 3]")
+            arr = img.detach().numpy()
+        elif isinstance(img, np.ndarray):
+            arr = img
+        elif hasattr(img, "convert") and hasattr(img, "mode"):  # a PIL image (preprocessing.py:71)
+            arr = np.asarray(img if img.mode == "RGB" else img.convert("RGB"))
+        else:
+            raise TypeError(f"Unsupported image type: {type(img)}. Expected bytes, a PIL image, a uint8 numpy array or a CPU tensor.")
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise L.LnxError(f"DevicePreprocessor: image {i} has shape {tuple(arr.shape)}; expected [h, w, 3] (three channels)")
+        if arr.dtype != np.uint8:
+            raise L.LnxError(f"DevicePreprocessor: image {i} is {arr.dtype}; expected uint8")
+        if not all(1 <= v <= L.PREPROCESS_MAX_SIDE for v in arr.shape[:2]):
+            raise L.LnxError(f"DevicePreprocessor: image {i} is {arr.shape[0]}x{arr.shape[1]}; sides must be in 1..{L.PREPROCESS_MAX_SIDE}")
+        return arr
+
+    def _axis_tables(self, in_size: int, out_size: int) -> np.ndarray:
+        key = (in_size, out_size)
+        tab = self._tables.get(key)
+        if tab is None:
+            lib = L.lib()
+            if self.filter == L.RESIZE_NEAREST:
+                tab = np.empty(out_size, np.int32)
+                L.check(lib.lnx_resize_coeffs(in_size, out_size, self.filter, None, tab.ctypes.data), "lnx_resize_coeffs")
+            else:
+                taps = lib.lnx_resize_taps(in_size, out_size, self.filter)
+                tab = np.empty(out_size * (taps + 2), np.int32)
+                L.check(lib.lnx_resize_coeffs(in_size, out_size, self.filter, tab.ctypes.data, tab[out_size * taps:].ctypes.data), "lnx_resize_coeffs")
+            if len(self._tables) >= 4096:
+                self._tables.clear()
+            self._tables[key] = tab
+        return tab
+
+    def _staging(self, nbytes: int):
+        """The next of the two pinned buffers, at least nbytes long, once the copy that last read it has finished."""
+        t = self._turn
+        self._turn ^= 1
+        if self._copied[t] is not None:
+            self._copied[t].synchronize()  # the copy of two calls ago: long done unless the host runs far ahead of the device
+        if self._pinned[t] is None or self._pinned[t].numel() < nbytes:
+            self._pinned[t] = torch.empty(max(nbytes, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
+        return t, self._pinned[t]
+
+    def __call__(self, images) -> torch.Tensor:
+        """images: a list of uint8 [h, w, 3] numpy arrays / CPU tensors, PIL images or encoded bytes, of any sizes -> fp32
+        [N, 3, H, W] on the device.  One host-to-device copy and at most two launches on the current stream; no synchronisation."""
+        arrays = [self._as_array(img, i) for i, img in enumerate(images)]
+        if not torch.cuda.is_available():
+            raise L.LnxError("DevicePreprocessor needs a HIP device: linnaeus_amd has no CPU fallback")
+        device = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        n, H, W, A = len(arrays), self.H, self.W, self._ALIGN
+        if n == 0:  # preprocessing.py:78-80
+            return torch.empty((0, 3, H, W), dtype=torch.float32, device=device)
+        pad = lambda v: (v + A - 1) // A * A  # noqa: E731
+        # layout of the blob: descriptors, the tables of every distinct axis, the sources
+        nearest = self.filter == L.RESIZE_NEAREST
+        off = pad(n * C.sizeof(L.PreprocessImage))
+        table_at, tables = {}, []
+        for arr in arrays:
+            for in_size, out_size in ((arr.shape[1], W), (arr.shape[0], H)):
+                if (in_size, out_size) not in table_at and (nearest or in_size != out_size):
+                    tab = self._axis_tables(in_size, out_size)
+                    table_at[(in_size, out_size)] = (off, 4 * (tab.size - 2 * out_size))  # where the table starts, bytes of k in front of bounds
+                    tables.append((off, tab))
+                    off = pad(off + tab.nbytes)
+        src_at = []
+        for arr in arrays:
+            src_at.append(off)
+            off = pad(off + arr.shape[0] * arr.shape[1] * 3)
+        nbytes = off
+        turn, pinned = self._staging(nbytes)
+        host = pinned.numpy()
+        descs = (L.PreprocessImage * n).from_buffer(host)
+        for d, arr, at in zip(descs, arrays, src_at):
+            h, w = arr.shape[:2]
+            d.src, d.h, d.w = at, h, w
+            d.hk = d.hb = d.vk = d.vb = 0
+            if nearest or w != W:
+                d.hk, k_bytes = table_at[(w, W)]
+                d.hb = d.hk if nearest else d.hk + k_bytes
+            if nearest or h != H:
+                d.vk, k_bytes = table_at[(h, H)]
+                d.vb = d.vk if nearest else d.vk + k_bytes
+            np.copyto(host[at: at + h * w * 3].reshape(h, w, 3), arr)
+        for at, tab in tables:
+            host[at: at + tab.nbytes].view(np.int32)[:] = tab
+        scratch_bytes = L.lib().lnx_preprocess_scratch_bytes(descs, n, H, W, self.filter)
+        self.scratch_bytes = scratch_bytes
+        if scratch_bytes < 0:
+            raise L.LnxError(f"lnx_preprocess_scratch_bytes failed: {L.lib().lnx_last_error().decode()}")
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream()
+            if self._done is not None:
+                stream.wait_event(self._done)  # the device buffers are reused: behind the kernels of the call before, on any stream
+            if self._blob is None or self._blob.numel() < nbytes or self._blob.device != device:
+                self._blob = torch.empty(pinned.numel(), dtype=torch.uint8, device=device)
+            if scratch_bytes and (self._scratch is None or self._scratch.numel() < scratch_bytes or self._scratch.device != device):
+                self._scratch = torch.empty(scratch_bytes * 5 // 4, dtype=torch.uint8, device=device)
+            self._blob[:nbytes].copy_(pinned[:nbytes], non_blocking=True)
+            if self._copied[turn] is None:
+                self._copied[turn] = torch.cuda.Event()
+            self._copied[turn].record(stream)
+            out = torch.empty((n, 3, H, W), dtype=torch.float32, device=device)
+            ops.preprocess_images(self._blob, nbytes, descs, 0, n, H, W, self.filter, self.mean, self.std, self._scratch if scratch_bytes else None, out)
+            if self._done is None:
+                self._done = torch.cuda.Event()
+            self._done.record(stream)
+        del descs
+        return out

@@ -553,3 +553,24 @@ def predict_topk(logits, parents, *, K, null_index=0, id_maps=None, k_per_sample
     a.ids, a.probs, a.count, a.flags = (_p(o) for o in out)
     L.check(L.lib().lnx_predict(C.byref(a), _stream()), "lnx_predict")
     return tuple(out)
+
+
+def preprocess_images(blob, blob_bytes, images, images_off, n, H, W, filter_code, mean, std, scratch, out):
+    """lnx_preprocess on a batch that is already on the device: blob uint8 (descriptor table at images_off, tables, packed [h, w, 3]
+    sources: include/lnx.h), images the HOST copy of the descriptor table (a ctypes array of L.PreprocessImage that
+    lnx_preprocess_scratch_bytes has completed), scratch uint8 or None, out fp32 [n, 3, H, W] contiguous.  At most two launches, never
+    synchronises."""
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, 3, H, W) or not out.is_contiguous():
+        raise L.LnxError(f"preprocess_images: out must be contiguous fp32 [{n}, 3, {H}, {W}], got {tuple(out.shape)} {out.dtype}")
+    if blob.dtype != torch.uint8 or (scratch is not None and scratch.dtype != torch.uint8):
+        raise L.LnxError("preprocess_images: blob and scratch are uint8 buffers")
+    a = L.PreprocessArgs()
+    a.n, a.H, a.W, a.filter = int(n), int(H), int(W), int(filter_code)
+    a.images = C.cast(images, C.POINTER(L.PreprocessImage))
+    a.blob, a.blob_bytes, a.images_off = _p(blob), int(blob_bytes), int(images_off)
+    a.scratch, a.scratch_bytes = _p(scratch), (0 if scratch is None else scratch.numel())
+    a.mean[:] = [float(v) for v in mean]
+    a.std[:] = [float(v) for v in std]
+    a.out = _p(out)
+    L.check(L.lib().lnx_preprocess(C.byref(a), _stream()), "lnx_preprocess")
+    return out
