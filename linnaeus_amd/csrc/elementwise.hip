@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void prep_weights_kernel(const lnx_prep_desc* 
     const int64_t n_main = (int64_t)d.rows * d.ld;
     const int64_t base = (int64_t)lb * PREP_ELEMS;
     if (d.mode == LNX_PREP_DW49) {
-        // src [C, 49] -> dst fp32 [49][C];  rows = C, cols = 49, ld = C
+        // src [C, 49] -> dst fp32 [49][C];  rows = C, cols = 49, ld = 49 (lnx_plan_bind: ld only sizes the workgroup count, ceil(C * 49 / 2048))
         float* dst = reinterpret_cast<float*>(d.dst);
         const int64_t n = (int64_t)49 * d.rows;
         for (int64_t i = base + threadIdx.x; i < base + PREP_ELEMS && i < n; i += 256) {
@@ -438,10 +438,10 @@ extern "C" int lnx_layerscale_apply_wgrad(const float* s, const float* t, int64_
 extern "C" int lnx_layerscale_bwd(const float* g, const void* z, int dtype, const float* gamma, const float* rowscale, int rows_per_sample, void* dz,
                                   float* dgamma, int M, int C, void* stream) {
     LNX_CHECK(g && z && gamma && dz && dgamma, "lnx_layerscale_bwd: null operand");
-    LNX_CHECK(M > 0 && C > 0 && C % 4 == 0 && C <= 2048, "lnx_layerscale_bwd: bad shape M=%d C=%d", M, C);
+    // one lane per group of 4 columns, 256 lanes a workgroup: C / 4 <= 256
+    LNX_CHECK(M > 0 && C > 0 && C % 4 == 0 && C <= 1024, "lnx_layerscale_bwd: bad shape M=%d C=%d (C is a multiple of 4, at most 1024)", M, C);
     const int c4n = C / 4;
-    const int rows_pb = 256 / c4n > 0 ? 256 / c4n : 1;
-    LNX_CHECK(c4n <= 256, "lnx_layerscale_bwd: C=%d too large", C);
+    const int rows_pb = 256 / c4n;
     int grid = cdiv(M, rows_pb * 8);
     if (grid > 2048) grid = 2048;
     if (grid < 1) grid = 1;
