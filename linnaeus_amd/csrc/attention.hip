@@ -43,7 +43,16 @@ template <typename T, int HD = 64> struct AT {
     static constexpr int TRB = ROWB + (sizeof(T) == 2 ? 32 : 16);  // padded row bytes of the transposed-read image (HD 64: 160 / 272)
     static constexpr int ROW_IMG = BT * ROWB;
     static constexpr int TR_IMG = BT * TRB;
+    // dynamic LDS of the tiled kernels (what each carves out of `smem`; the launchers take the sizes from here)
+    static constexpr size_t FWD_LDS = ROW_IMG + TR_IMG;                                      // K~ rows, V transposed (fp32 head_dim 128: 65 KiB)
+    static constexpr size_t BWD_DQ_LDS = 2 * ROW_IMG + TR_IMG;                               // K~ rows, V rows, K~ transposed
+    static constexpr size_t BWD_DKV_LDS = 2 * ROW_IMG + 2 * TR_IMG + 2 * BT * sizeof(float);  // Q~, dO rows; Q~, dO transposed; lse, delta (fp32 head_dim 128: 130.5 KiB)
 };
+// dynamic LDS of the resident kernels (bf16 images of a whole sequence padded to npad rows).  The forward pads to whole 64-key tiles
+// (npad = qtiles * BT), the backward kernels to 32-row steps (npad = (N + 31) & ~31) plus two statistics per query slot of qtiles tiles.
+template <typename T> constexpr size_t res_fwd_lds(int npad) { return (size_t)npad * (AT<T>::ROWB + AT<T>::TRB); }
+template <typename T> constexpr size_t res_bwd_dq_lds(int npad) { return (size_t)npad * (2 * AT<T>::TRB); }
+template <typename T> constexpr size_t res_bwd_dkv_lds(int npad, int qtiles) { return (size_t)npad * (2 * AT<T>::TRB) + (size_t)qtiles * BT * 2 * sizeof(float); }
 // HD^-0.5 as the reference's fp32 product q * head_dim**-0.5 rounds it
 template <int HD> constexpr float attn_scale() { return HD == 32 ? 0.17677669529663688f : HD == 64 ? 0.125f : 0.08838834764831845f; }
 
@@ -135,30 +144,9 @@ template <typename T, bool COS, int HD = 64, bool ROT = false> struct Chunk {
         return v.raw;
     }
 };
-template <typename T, bool COS>
-__device__ __forceinline__ uint4 load_chunk(const T* __restrict__ base, int64_t ld, int n, int N, int E, int d0, const float* __restrict__ cos_tab,
-                                            int heads, int head, float scale) {
-    Chunk<T, COS> c;
-    c.fetch(base, ld, n, N, E, d0, cos_tab, heads, head);
-    return c.value(n, N, E, scale);
-}
 
-// Stage a 64-row tile (tokens n0..n0+63) into LDS: swizzled row image (16-byte fragment
-// reads, rows = MFMA rows) and/or padded image for transposed reads.
-template <typename T, bool COS, bool ROWIMG, bool TRIMG, int NT = 256>
-__device__ __forceinline__ void stage_tile(unsigned char* rowimg, unsigned char* trimg, const T* __restrict__ base, int64_t ld, int n0, int N, int E,
-                                           const float* __restrict__ cos_tab, int heads, int head, float scale) {
-    constexpr int NCH = AT<T>::NCH;
-    constexpr int EPV = AT<T>::EPV;
-    for (int i = threadIdx.x; i < BT * NCH; i += NT) {
-        const int r = i / NCH, c = i % NCH;
-        const uint4 v = load_chunk<T, COS>(base, ld, n0 + r, N, E, c * EPV, cos_tab, heads, head, scale);
-        if constexpr (ROWIMG) st16(rowimg + r * AT<T>::ROWB + ((c ^ (r & AT<T>::SWZ)) << 4), v);
-        if constexpr (TRIMG) st16(trimg + r * AT<T>::TRB + c * 16, v);
-    }
-}
-
-// The same staging split in two, for the tiled kernels' software pipeline: fetch() requests a 64-row tile into registers
+// Staging of a 64-row tile (tokens n0..n0+63) into LDS -- swizzled row image (16-byte fragment reads, rows = MFMA rows) and/or padded
+// image for transposed reads -- split in two for the tiled kernels' software pipeline: fetch() requests the tile into registers
 // (unconditional, clamped rows -- call it for min(next, last) rather than under `if (more)`), commit() writes it to the LDS
 // images one loop trip later, after the products of the current tile have been issued in between.
 template <typename T, bool COS, int NT, int HD = 64, bool ROT = false>
@@ -199,85 +187,14 @@ __device__ __forceinline__ void load_row_frag(uint4 (&f)[(AT<T, HD>::NKK)], cons
     for (int kk = 0; kk < AT<T, HD>::NKK; ++kk) f[kk] = c[kk].value(n, N, E, scale);
 }
 
-// acc[t] (t = 0..3, 16 rows each) = Rows(img, row0 + 16 t + s) . frag^T over the 64 channels
-// nt = number of 16-row groups of the tile that hold real tokens (the rest is padding: skipped, acc = 0)
-template <typename T>
-__device__ __forceinline__ void rows_times_frag(f32x4_t (&acc)[4], const unsigned char* rowimg, int s, int g, const uint4 (&frag)[AT<T>::NKK], int nt = 4) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (t >= nt) continue;
-        const int row = t * 16 + s;
-#pragma unroll
-        for (int kk = 0; kk < AT<T>::NKK; ++kk) {
-            const uint4 a = ld16(rowimg + row * AT<T>::ROWB + (((kk * 4 + g) ^ (row & AT<T>::SWZ)) << 4));
-            mfma_chunk<T>(acc[t], a, frag[kk]);
-        }
-    }
-}
-
-// out[dt] += Img^T . P   where P[t][r] holds, for the lane's column, the value of tile row
-// 16 t + 4 g + r (t = 0..3) -- i.e. contraction over the 64 tile rows.
-// Same product from the PADDED image (rows of TRB = 160 bytes, unswizzled): at that pitch the 16-byte fragment reads
-// of every 16-lane group of a ds_read_b128 also fall on 16 distinct bank slots, so one image serves both the row
-// fragments and the transposed reads (half the LDS of keeping a swizzled row image beside it).
-template <typename T>
-__device__ __forceinline__ void rows_times_frag_pad(f32x4_t (&acc)[4], const unsigned char* img, int s, int g, const uint4 (&frag)[AT<T>::NKK], int nt) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (t >= nt) continue;
-        const int row = t * 16 + s;
-#pragma unroll
-        for (int kk = 0; kk < AT<T>::NKK; ++kk) {
-            const uint4 a = ld16(img + row * AT<T>::TRB + ((kk * 4 + g) << 4));
-            mfma_chunk<T>(acc[t], a, frag[kk]);
-        }
-    }
-}
-
-// nt as above: 32-row contraction steps made of padding only are skipped
-template <typename T>
-__device__ __forceinline__ void imgT_times_regs(f32x4_t (&out)[4], const unsigned char* trimg, int s, int g, const float (&p)[4][4], int nt = 4) {
-    if constexpr (sizeof(T) == 2) {
-        uint4 pf[2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            Vec16<bf16_t> v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v.set(j, p[2 * ks + (j >> 2)][j & 3]);
-            pf[ks] = v.raw;
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            if (2 * ks >= nt) continue;
-            const int r0 = ks * 32 + 4 * g + (s >> 2);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const int col = (dt * 16 + 4 * (s & 3)) * 2;
-                const uint2 a0 = tr_read(trimg + r0 * AT<T>::TRB + col);
-                const uint2 a1 = tr_read(trimg + (r0 + 16) * AT<T>::TRB + col);
-                mfma_bf16(out[dt], make_uint4(a0.x, a0.y, a1.x, a1.y), pf[ks]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (t >= nt) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = t * 16 + 4 * g + r;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const float a = *reinterpret_cast<const float*>(trimg + row * AT<T>::TRB + (dt * 16 + s) * 4);
-                    mfma_f32(out[dt], a, p[t][r]);
-                }
-            }
-        }
-    }
-}
-
-// ---- the same two products with the number of live 16-row groups as a compile-time constant -------------------------------
+// ---- the two products of every kernel below, with the number NT of live 16-row groups of a tile as a compile-time constant ------
+//   rows_times_frag_n      acc[t] (t = 0..3, 16 rows each) = Rows(rowimg, 16 t + s) . frag^T over the HD channels; the groups t >= NT are
+//                          padding: skipped, acc = 0
+//   rows_times_frag_pad_n  the same product from the PADDED image (rows of TRB = 160 bytes, unswizzled): at that pitch the 16-byte fragment
+//                          reads of every 16-lane group of a ds_read_b128 also fall on 16 distinct bank slots, so one image serves both
+//                          the row fragments and the transposed reads (half the LDS of keeping a swizzled row image beside it)
+//   imgT_times_regs_n      out[dt] += Img^T . P   where P[t][r] holds, for the lane's column, the value of tile row 16 t + 4 g + r
+//                          (t = 0..3) -- i.e. contraction over the tile rows; 32-row contraction steps made of padding only are skipped
 // With a run-time `nt` every group sits under its own branch: hipcc then emits `ds_read; s_waitcnt lgkmcnt(0); v_mfma` per
 // group -- one exposed LDS round trip per pair of MFMAs (round 3: the resident backward kernels spent most of their key /
 // query loop that way).  The images are staged in units of 32 rows.  The forward uses NT = 4 for a tile with more than 32 live rows
@@ -357,21 +274,6 @@ __device__ __forceinline__ void imgT_times_regs_n(f32x4_t (&out)[HD / 16], const
                     mfma_f32(out[dt], a, p[t][r]);
                 }
             }
-    }
-}
-
-// four consecutive elements in one store (8 bytes of bf16 / 16 bytes of fp32); p is 8-/16-byte aligned
-template <typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d) {
-    if constexpr (sizeof(T) == 2) {
-        uint2 r;
-        T* h = reinterpret_cast<T*>(&r);
-        h[0] = from_f<T>(a);
-        h[1] = from_f<T>(b);
-        h[2] = from_f<T>(c);
-        h[3] = from_f<T>(d);
-        *reinterpret_cast<uint2*>(p) = r;
-    } else {
-        *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
     }
 }
 
@@ -477,11 +379,6 @@ template <bool ADD, int HD = 64> __device__ __forceinline__ void freq_flush(cons
     }
 }
 
-// exp of the softmax: the bf16 kernels use the hardware exponential (v_exp_f32, ~1 ulp), the fp32 (strict-parity) ones libm's
-template <typename T> __device__ __forceinline__ float fexp(float x) {
-    if constexpr (sizeof(T) == 2) return __expf(x);
-    else return expf(x);
-}
 // exp(x - m) with m fixed along a row.  bf16 kernels: log2(e) folded into the subtraction, one FMA in front of v_exp_f32
 // (prep(m) = m log2(e) once per row) instead of subtract + multiply; fp32 (strict parity) kernels: libm.  `clamped` bounds the
 // argument by 0 -- a no-op for real (query, key) pairs of the backward (x <= lse), it keeps padding entries finite.
@@ -682,7 +579,7 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
 template <typename T, int NW = 4, bool DROP = false, int HD = 64, bool ROT = false>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* kimg = smem;                       // K~ row image
+    unsigned char* kimg = smem;                       // K~ row image                 (AT<T, HD>::FWD_LDS bytes in all)
     unsigned char* vimg = smem + AT<T, HD>::ROW_IMG;      // V transposed-read image
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -788,7 +685,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
 template <typename T, int NW = 4, bool DROP = false, int HD = 64, bool ROT = false>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* kimg = smem;                                        // K~ rows
+    unsigned char* kimg = smem;                                        // K~ rows     (AT<T, HD>::BWD_DQ_LDS bytes in all)
     unsigned char* vimg = smem + AT<T, HD>::ROW_IMG;                       // V rows
     unsigned char* ktr = smem + 2 * AT<T, HD>::ROW_IMG;                    // K~ transposed-read image
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -895,7 +792,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
 template <typename T, int NW = 4, bool DROP = false, int HD = 64, bool ROT = false>
 __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd_dkv_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* qimg = smem;                                   // Q~ rows
+    unsigned char* qimg = smem;                                   // Q~ rows          (AT<T, HD>::BWD_DKV_LDS bytes in all)
     unsigned char* doimg = smem + AT<T, HD>::ROW_IMG;                 // dO rows
     unsigned char* qtr = smem + 2 * AT<T, HD>::ROW_IMG;               // Q~ transposed-read image
     unsigned char* dotr = qtr + AT<T, HD>::TR_IMG;                    // dO transposed-read image
@@ -1033,7 +930,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
     const int nkt = (p.N + BT - 1) / BT;
     const int npad = nkt * BT;
-    unsigned char* kimg = smem;
+    unsigned char* kimg = smem;  // res_fwd_lds<T>(npad) bytes in all
     unsigned char* vimg = smem + npad * AT<T>::ROWB;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -1120,7 +1017,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
     const int nkt = (p.N + BT - 1) / BT;
     const int npad = (p.N + 31) & ~31;  // image rows: padding groups beyond it are never read (nt below)
-    unsigned char* kimg = smem;         // padded-pitch images: row fragments AND transposed reads
+    unsigned char* kimg = smem;         // padded-pitch images: row fragments AND transposed reads (res_bwd_dq_lds<T>(npad) bytes in all)
     unsigned char* vimg = kimg + npad * AT<T>::TRB;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -1286,7 +1183,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
     const int nqt = (p.N + BT - 1) / BT;
     const int npad = (p.N + 31) & ~31;
-    unsigned char* qimg = smem;  // padded-pitch images: row fragments AND transposed reads
+    unsigned char* qimg = smem;  // padded-pitch images: row fragments AND transposed reads (res_bwd_dkv_lds<T>(npad, nqt) bytes in all)
     unsigned char* doimg = qimg + npad * AT<T>::TRB;
     float* lse_s = reinterpret_cast<float*>(doimg + npad * AT<T>::TRB);
     float* del_s = lse_s + nqt * BT;  // statistics are indexed by every query slot of a 64-query tile
@@ -1433,12 +1330,12 @@ __global__ __launch_bounds__(256) void rope_cos_batch_kernel(const RopeTabBatch 
 
 // dfreqs[a, h, j] += sum over the workgroups of head h of their partial [a][j]   (fixed order: deterministic given the partials)
 // one 1024-thread workgroup per head: SL = 1024 / HD slices of the partial list x HD entries (16 x 64 at head_dim 64), four loads in
-// flight per thread, LDS tree
-template <int HD = 64>
-__global__ __launch_bounds__(1024) void rope_freqs_reduce_kernel(const float* __restrict__ fpart, int B, int heads, int per_bh, float* __restrict__ dfreqs) {
+// flight per thread, LDS tree.  The one body of both fold kernels below: a call folded alone and in a batch gives the same bits.
+template <int HD>
+__device__ __forceinline__ void freqs_fold(const float* __restrict__ fpart, float* __restrict__ dfreqs, int B, int heads, int per_bh, int h) {
     constexpr int SL = 1024 / HD, HH = HD / 2;
     __shared__ float red[SL][HD];
-    const int h = blockIdx.x, t = threadIdx.x & (HD - 1), sl = threadIdx.x / HD;  // t = a * HD / 2 + j
+    const int t = threadIdx.x & (HD - 1), sl = threadIdx.x / HD;  // t = a * HD / 2 + j
     const int n = B * per_bh;  // partials of this head: (b, k) -> ((b * heads + h) * per_bh + k)
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     auto at = [&](int i) -> float {
@@ -1462,6 +1359,10 @@ __global__ __launch_bounds__(1024) void rope_freqs_reduce_kernel(const float* __
         dfreqs[((t / HH) * heads + h) * HH + (t & (HH - 1))] += acc;
     }
 }
+template <int HD = 64>
+__global__ __launch_bounds__(1024) void rope_freqs_reduce_kernel(const float* __restrict__ fpart, int B, int heads, int per_bh, float* __restrict__ dfreqs) {
+    freqs_fold<HD>(fpart, dfreqs, B, heads, per_bh, blockIdx.x);
+}
 
 // the same fold for several attention backward calls in ONE launch (lnx_attn_bwd_args.defer_freqs + lnx_attn_bwd_flush): blockIdx.y picks
 // the call.  Every RoPE block owns its freqs, so a backward segment of a plan has one of these small folds per block.  One launch folds
@@ -1476,35 +1377,24 @@ struct FreqBatch {
 };
 template <int HD = 64>
 __global__ __launch_bounds__(1024) void rope_freqs_reduce_batch_kernel(const FreqBatch fb) {
-    constexpr int SL = 1024 / HD, HH = HD / 2;
-    __shared__ float red[SL][HD];
     const FreqEntry& q = fb.e[blockIdx.y];
     if ((int)blockIdx.x >= q.heads) return;  // (uniform per workgroup: the grid's width is the largest head count of the batch)
-    const float* __restrict__ fpart = q.fpart;
-    const int heads = q.heads, per_bh = q.per_bh;
-    const int h = blockIdx.x, t = threadIdx.x & (HD - 1), sl = threadIdx.x / HD;
-    const int n = q.B * per_bh;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    auto at = [&](int i) -> float {
-        const int ii = min(i, n - 1);
-        const int b = ii / per_bh, k = ii - b * per_bh;
-        const float v = fpart[(((int64_t)b * heads + h) * per_bh + k) * HD + t];
-        return i < n ? v : 0.f;
-    };
-    for (int i = sl; i < n; i += 4 * SL) {  // (the order of rope_freqs_reduce_kernel: same bits)
-        a0 += at(i);
-        a1 += at(i + SL);
-        a2 += at(i + 2 * SL);
-        a3 += at(i + 3 * SL);
-    }
-    red[sl][t] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (sl == 0) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < SL; ++k) acc += red[k][t];
-        q.dfreqs[((t / HH) * heads + h) * HH + (t & (HH - 1))] += acc;
-    }
+    freqs_fold<HD>(q.fpart, q.dfreqs, q.B, q.heads, q.per_bh, blockIdx.x);
+}
+
+// ---------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------
+// f(IC<head_dim>{}) for a head_dim that passed hd_ok, and f(TC<element type>{}, IC<head_dim>{}): the only two places that turn the
+// run-time head_dim / dtype of a call into template arguments
+template <typename T> struct TC { using type = T; };
+template <class F> auto with_hd(int hd, F&& f) {
+    if (hd == 32) return f(IC<32>{});
+    if (hd == 64) return f(IC<64>{});
+    return f(IC<128>{});
+}
+template <class F> auto with_type_hd(int dtype, int hd, F&& f) {
+    return with_hd(hd, [&](auto hdc) { return dtype == LNX_BF16 ? f(TC<bf16_t>{}, hdc) : f(TC<float>{}, hdc); });
 }
 
 // postponed folds of this thread's lnx_attn_bwd calls (raw pointers: the caller keeps partials and targets alive until the flush)
@@ -1525,17 +1415,23 @@ int freq_flush(hipStream_t st) {
             ++m;
         }
         if (m == 0) continue;
-        if (hd == 64) hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel<64>, dim3(most, m), dim3(1024), 0, st, fb);
-        else if (hd == 32) hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel<32>, dim3(most, m), dim3(1024), 0, st, fb);
-        else hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel<128>, dim3(most, m), dim3(1024), 0, st, fb);
+        with_hd(hd, [&](auto hdc) { hipLaunchKernelGGL(rope_freqs_reduce_batch_kernel<decltype(hdc)::value>, dim3(most, m), dim3(1024), 0, st, fb); });
     }
     g_freq_n = 0;
     LNX_LAUNCH_CHECK();
     return 0;
 }
 
-template <typename K> void set_lds(K kernel, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// Every attention kernel is launched through here.  A kernel gets 64 KiB of dynamic LDS unasked; the limit of each instantiation is
+// raised once, before its first launch and by whichever thread comes first (a function-local static: thread-safe), to `lds_max`, the
+// most that instantiation is ever launched with -- so no list of "the ones beyond 64 KiB" has to follow the layouts.  If the runtime
+// refused it, every launch of that instantiation reports the refusal (2, lnx_last_error) instead of launching.
+template <auto Kernel>
+int attn_launch(int grid, int block, size_t lds, size_t lds_max, hipStream_t st, const AttnP& p) {
+    static const hipError_t raise_dynamic_lds_limit = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+    LNX_HIP(raise_dynamic_lds_limit);
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, st, p);
+    return 0;
 }
 
 bool hd_ok(int hd) { return hd == 32 || hd == 64 || hd == 128; }
@@ -1558,8 +1454,8 @@ static bool tiled_nw8(int N) {
     return !force4 && N > 128;
 }
 
-// ---- head_dim 32 / 128: the tiled kernels, NW = 4 (fp32, dropout, bf16 at N <= 128) or NW = 8 (bf16 beyond).  The resident kernels
-// carry head_dim 64 only.  bf16 head_dim 32 keeps NW = 4 throughout: a 64-row tile is 256 16-byte chunks, one per thread of 4 waves.
+// The tiled kernels exist with NW = 8 for bf16 at head_dim 64 and 128 only.  bf16 head_dim 32 keeps NW = 4 throughout: a 64-row tile
+// is 256 16-byte chunks, one per thread of 4 waves.
 template <typename T, int HD> constexpr bool hd_nw8() { return sizeof(T) == 2 && HD > 32; }
 
 // The kernel family of a forward / backward launch (include/lnx.h: lnx_attn_dispatch answers with this, lnx_attn_fwd / lnx_attn_bwd
@@ -1569,80 +1465,105 @@ int attn_family(int dtype, int N, int hd, bool drop) {
     if (hd == 64 && N <= 256 && getenv("LNX_ATTN_TILED") == nullptr) return N <= 64 ? LNX_ATTN_KERNEL_RES4 : LNX_ATTN_KERNEL_RES8;
     return tiled_nw8(N) ? LNX_ATTN_KERNEL_TILED8 : LNX_ATTN_KERNEL_TILED4;
 }
+bool is_resident(int family) { return family == LNX_ATTN_KERNEL_RES4 || family == LNX_ATTN_KERNEL_RES8; }
 
 std::atomic<int> g_last_attn{LNX_ATTN_KERNEL_NONE};
 
-template <typename T, int HD, bool ROT>
-void attn_fwd_tiled(AttnP& p, int family, hipStream_t st) {
-    using A = AT<T, HD>;
-    const size_t lds = A::ROW_IMG + A::TR_IMG;  // fp32 head_dim 128: 65 KiB
-    static bool once = false;
-    if (!once) {
-        set_lds(attn_fwd_kernel<T, 4, false, HD, ROT>, lds);
-        set_lds(attn_fwd_kernel<T, 4, true, HD, ROT>, lds);
-        if constexpr (hd_nw8<T, HD>()) set_lds(attn_fwd_kernel<T, 8, false, HD, ROT>, lds);
-        once = true;
-    }
-    const int bh = p.B * p.heads;
-    if (p.amask) {
-        hipLaunchKernelGGL((attn_fwd_kernel<T, 4, true, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
-        return;
-    }
+// ---- the tiled kernels (any dtype and head_dim).  The whole rule for their instantiation: a dropout mask -> NW = 4 with the DROP code;
+// LNX_ATTN_KERNEL_TILED8 -> NW = 8; everything else NW = 4.  f(IC<NW>{}, IC<DROP>{}) launches; p.qtiles becomes the workgroups per
+// (sample, head) of that NW (p.Np keeps the 64-row rounding of the mask).
+template <typename T, int HD, class F>
+int tiled_variant(AttnP& p, int family, F&& f) {
+    if (p.amask) return f(IC<4>{}, IC<1>{});
     if constexpr (hd_nw8<T, HD>()) {
         if (family == LNX_ATTN_KERNEL_TILED8) {
             p.qtiles = cdiv(p.N, 128);
-            hipLaunchKernelGGL((attn_fwd_kernel<T, 8, false, HD, ROT>), dim3(bh * p.qtiles), dim3(512), lds, st, p);
-            return;
+            return f(IC<8>{}, IC<0>{});
         }
     }
-    hipLaunchKernelGGL((attn_fwd_kernel<T, 4, false, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds, st, p);
+    return f(IC<4>{}, IC<0>{});
 }
 
-// returns the workgroups per (sample, head) of the launch (the fold's per_bh)
 template <typename T, int HD, bool ROT>
-int attn_bwd_tiled(AttnP& p, int family, hipStream_t st) {
-    using A = AT<T, HD>;
-    const size_t lds_q = 2 * A::ROW_IMG + A::TR_IMG;
-    const size_t lds_k = 2 * A::ROW_IMG + 2 * A::TR_IMG + 2 * BT * sizeof(float);  // fp32 head_dim 128: 130.5 KiB
-    static bool once = false;
-    if (!once) {
-        set_lds(attn_bwd_dq_kernel<T, 4, false, HD, ROT>, lds_q);
-        set_lds(attn_bwd_dq_kernel<T, 4, true, HD, ROT>, lds_q);
-        set_lds(attn_bwd_dkv_kernel<T, 4, false, HD, ROT>, lds_k);
-        set_lds(attn_bwd_dkv_kernel<T, 4, true, HD, ROT>, lds_k);
-        if constexpr (hd_nw8<T, HD>()) {
-            set_lds(attn_bwd_dq_kernel<T, 8, false, HD, ROT>, lds_q);
-            set_lds(attn_bwd_dkv_kernel<T, 8, false, HD, ROT>, lds_k);
-        }
-        once = true;
-    }
-    const int bh = p.B * p.heads;
-    if (p.amask) {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
-        return p.qtiles;
-    }
-    if constexpr (hd_nw8<T, HD>()) {
-        if (family == LNX_ATTN_KERNEL_TILED8) {
-            p.qtiles = cdiv(p.N, 128);
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8, false, HD, ROT>), dim3(bh * p.qtiles), dim3(512), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false, HD, ROT>), dim3(bh * p.qtiles), dim3(512), lds_k, st, p);
-            return p.qtiles;
-        }
-    }
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_q, st, p);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, HD, ROT>), dim3(bh * p.qtiles), dim3(256), lds_k, st, p);
-    return p.qtiles;
+int attn_fwd_tiled(AttnP& p, int family, hipStream_t st) {
+    return tiled_variant<T, HD>(p, family, [&](auto nwc, auto dropc) {
+        constexpr int NW = decltype(nwc)::value;
+        constexpr bool DROP = decltype(dropc)::value != 0;
+        constexpr size_t lds = AT<T, HD>::FWD_LDS;
+        return attn_launch<attn_fwd_kernel<T, NW, DROP, HD, ROT>>(p.B * p.heads * p.qtiles, 64 * NW, lds, lds, st, p);
+    });
+}
+
+// the backward launchers leave the workgroups per (sample, head) of their launches in per_bh (what the freqs fold needs)
+template <typename T, int HD, bool ROT>
+int attn_bwd_tiled(AttnP& p, int family, hipStream_t st, int& per_bh) {
+    return tiled_variant<T, HD>(p, family, [&](auto nwc, auto dropc) {
+        constexpr int NW = decltype(nwc)::value;
+        constexpr bool DROP = decltype(dropc)::value != 0;
+        constexpr size_t lds_q = AT<T, HD>::BWD_DQ_LDS, lds_k = AT<T, HD>::BWD_DKV_LDS;
+        const int grid = p.B * p.heads * p.qtiles;
+        per_bh = p.qtiles;
+        if (int rc = attn_launch<attn_bwd_dq_kernel<T, NW, DROP, HD, ROT>>(grid, 64 * NW, lds_q, lds_q, st, p)) return rc;
+        return attn_launch<attn_bwd_dkv_kernel<T, NW, DROP, HD, ROT>>(grid, 64 * NW, lds_k, lds_k, st, p);
+    });
+}
+
+// ---- the resident kernels (bf16, head_dim 64, N <= 256): one workgroup per (sample, head), NW = 4 up to 64 tokens
+// (LNX_ATTN_KERNEL_RES4) and 8 beyond (RES8).  f(IC<NW>{}, the longest sequence of that NW) launches.
+template <class F>
+int res_variant(int family, F&& f) {
+    return family == LNX_ATTN_KERNEL_RES4 ? f(IC<4>{}, 64) : f(IC<8>{}, 256);
+}
+
+template <bool ROT>
+int attn_fwd_res(AttnP& p, int family, hipStream_t st) {
+    typedef bf16_t T;
+    return res_variant(family, [&](auto nwc, int nmax) {
+        constexpr int NW = decltype(nwc)::value;
+        return attn_launch<attn_fwd_res_kernel<T, NW, ROT>>(p.B * p.heads, 64 * NW, res_fwd_lds<T>(p.qtiles * BT), res_fwd_lds<T>(nmax), st, p);
+    });
+}
+
+template <bool ROT>
+int attn_bwd_res(AttnP& p, int family, hipStream_t st, int& per_bh) {
+    typedef bf16_t T;
+    return res_variant(family, [&](auto nwc, int nmax) {
+        constexpr int NW = decltype(nwc)::value;
+        const int npad = (p.N + 31) & ~31, bh = p.B * p.heads;
+        per_bh = 1;
+        if (int rc = attn_launch<attn_bwd_dq_res_kernel<T, NW, ROT>>(bh, 64 * NW, res_bwd_dq_lds<T>(npad), res_bwd_dq_lds<T>(nmax), st, p)) return rc;
+        return attn_launch<attn_bwd_dkv_res_kernel<T, NW, ROT>>(bh, 64 * NW, res_bwd_dkv_lds<T>(npad, p.qtiles), res_bwd_dkv_lds<T>(nmax, nmax / BT), st, p);
+    });
 }
 
 int rope_table_hd(const float* freqs, int heads, int hd, int H, int W, float* cos_out, float* dsin_out, hipStream_t st, const char* who, float* sin_out = nullptr) {
     LNX_CHECK(freqs && cos_out && heads > 0 && H > 0 && W > 0, "%s: bad arguments", who);
     LNX_CHECK(hd_ok(hd), "%s: head_dim %d is not supported (32, 64 or 128)", who, hd);
     const int total = H * W * heads * (hd / 2);
-    if (hd == 64) hipLaunchKernelGGL(rope_cos_kernel<64>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out, sin_out);
-    else if (hd == 32) hipLaunchKernelGGL(rope_cos_kernel<32>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out, sin_out);
-    else hipLaunchKernelGGL(rope_cos_kernel<128>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out, sin_out);
+    with_hd(hd, [&](auto hdc) {
+        hipLaunchKernelGGL(rope_cos_kernel<decltype(hdc)::value>, dim3(cdiv(total, 256)), dim3(256), 0, st, freqs, heads, H, W, cos_out, dsin_out, sin_out);
+    });
     LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+// What lnx_attn_fwd and lnx_attn_bwd share once their own argument checks have passed: the dropout arguments (the last check of a
+// call: nothing has been launched or recorded before it), the fields of AttnP that both directions fill, and the choice of the kernel
+// family, which lnx_last_attn_kernel reports from here on.  Args = lnx_attn_args or lnx_attn_bwd_args.
+template <bool ROT, class Args>
+int attn_setup(const Args* a, int hd, const char* who, AttnP& p, int& family) {
+    if (a->drop_mask) {  // attention-probability dropout: the 64-row tiled kernels with the DROP code
+        LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "%s: drop_inv_keep >= 1 and a 4-byte aligned mask", who);
+    }
+    p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = const_cast<void*>(static_cast<const void*>(a->o)); p.lse = const_cast<float*>(a->lse);
+    if (ROT) p.sin_tab = cos_or_stub(a->sin_tab, a->qkv);
+    p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
+    p.qtiles = cdiv(a->N, BT);
+    if (a->drop_mask) {
+        p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
+    }
+    family = attn_family(a->dtype, a->N, hd, a->drop_mask != nullptr);
+    g_last_attn.store(family, std::memory_order_relaxed);
     return 0;
 }
 
@@ -1683,9 +1604,9 @@ extern "C" int lnx_rope_cos_tables(const lnx_rope_table* t, int n, void* stream)
                 const int total = g[i0 + i].H * g[i0 + i].W * g[i0 + i].heads * (hd / 2);
                 if (total > most) most = total;
             }
-            if (hd == 64) hipLaunchKernelGGL(rope_cos_batch_kernel<64>, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
-            else if (hd == 32) hipLaunchKernelGGL(rope_cos_batch_kernel<32>, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
-            else hipLaunchKernelGGL(rope_cos_batch_kernel<128>, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
+            with_hd(hd, [&](auto hdc) {
+                hipLaunchKernelGGL(rope_cos_batch_kernel<decltype(hdc)::value>, dim3(cdiv(most, 256), m), dim3(256), 0, (hipStream_t)stream, b);
+            });
             LNX_LAUNCH_CHECK();
         }
     }
@@ -1706,62 +1627,13 @@ int attn_fwd_launch(const lnx_attn_args* a, void* stream) {
     LNX_CHECK(a->E == a->N || a->cos_tab, "lnx_attn_fwd: cos table missing");
     LNX_CHECK(!ROT || a->E == a->N || a->sin_tab, "lnx_attn_fwd: sin table missing (rope_mode = LNX_ROPE_ROTATE)");
     AttnP p{};
-    p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = a->o; p.lse = a->lse;
-    if (ROT) p.sin_tab = cos_or_stub(a->sin_tab, a->qkv);
-    p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
-    p.qtiles = cdiv(a->N, BT);
-    const int grid = a->B * a->heads * p.qtiles;
+    int family = LNX_ATTN_KERNEL_NONE;
+    if (attn_setup<ROT>(a, hd, "lnx_attn_fwd", p, family)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    if (a->drop_mask) {  // attention-probability dropout: the 64-row tiled kernels with the DROP code
-        LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_fwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
-        p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
-    }
-    const int family = attn_family(a->dtype, a->N, hd, a->drop_mask != nullptr);
-    g_last_attn.store(family, std::memory_order_relaxed);
-    const bool resident = family == LNX_ATTN_KERNEL_RES4 || family == LNX_ATTN_KERNEL_RES8;
-    if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
-        if (a->dtype == LNX_BF16) {
-            if (hd == 32) attn_fwd_tiled<bf16_t, 32, ROT>(p, family, st);
-            else attn_fwd_tiled<bf16_t, 128, ROT>(p, family, st);
-        } else {
-            if (hd == 32) attn_fwd_tiled<float, 32, ROT>(p, family, st);
-            else attn_fwd_tiled<float, 128, ROT>(p, family, st);
-        }
-        LNX_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a->drop_mask) {
-        if (a->dtype == LNX_BF16) {
-            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 4, true, 64, ROT>), dim3(grid), dim3(256), AT<bf16_t>::ROW_IMG + AT<bf16_t>::TR_IMG, st, p);
-        } else {
-            hipLaunchKernelGGL((attn_fwd_kernel<float, 4, true, 64, ROT>), dim3(grid), dim3(256), AT<float>::ROW_IMG + AT<float>::TR_IMG, st, p);
-        }
-        LNX_LAUNCH_CHECK();
-        return 0;
-    }
-    if (resident) {
-        typedef bf16_t T;
-        const int npad = p.qtiles * BT;
-        const size_t lds = (size_t)npad * (AT<T>::ROWB + AT<T>::TRB);
-        static bool once = false;
-        if (!once) {
-            set_lds(attn_fwd_res_kernel<T, 8, ROT>, 256 * (AT<T>::ROWB + AT<T>::TRB));
-            once = true;
-        }
-        if (family == LNX_ATTN_KERNEL_RES4) hipLaunchKernelGGL((attn_fwd_res_kernel<T, 4, ROT>), dim3(a->B * a->heads), dim3(256), lds, st, p);
-        else hipLaunchKernelGGL((attn_fwd_res_kernel<T, 8, ROT>), dim3(a->B * a->heads), dim3(512), lds, st, p);
-    } else if (a->dtype == LNX_BF16) {
-        const size_t lds = AT<bf16_t>::ROW_IMG + AT<bf16_t>::TR_IMG;
-        if (family == LNX_ATTN_KERNEL_TILED8) {  // 128 queries per workgroup
-            p.qtiles = cdiv(a->N, 128);
-            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 8, false, 64, ROT>), dim3(a->B * a->heads * p.qtiles), dim3(512), lds, st, p);
-        } else {
-            hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 4, false, 64, ROT>), dim3(grid), dim3(256), lds, st, p);
-        }
-    } else {
-        const size_t lds = AT<float>::ROW_IMG + AT<float>::TR_IMG;
-        hipLaunchKernelGGL((attn_fwd_kernel<float, 4, false, 64, ROT>), dim3(grid), dim3(256), lds, st, p);
-    }
+    const int rc = is_resident(family) ? attn_fwd_res<ROT>(p, family, st) : with_type_hd(a->dtype, hd, [&](auto tc, auto hdc) {
+        return attn_fwd_tiled<typename decltype(tc)::type, decltype(hdc)::value, ROT>(p, family, st);
+    });
+    if (rc) return rc;
     LNX_LAUNCH_CHECK();
     return 0;
 }
@@ -1776,114 +1648,31 @@ int attn_bwd_launch(const lnx_attn_bwd_args* a, void* stream) {
     } else {
         LNX_CHECK(a->E == a->N || (a->cos_tab && a->dsin_tab && a->freq_ws && a->dfreqs), "lnx_attn_bwd: cos / d-cos tables, freqs-gradient workspace or dfreqs missing");
     }
-    AttnP p{};
-    if (ROT) {
-        p.sin_tab = cos_or_stub(a->sin_tab, a->qkv);
-        p.W = a->grid_w > 0 ? a->grid_w : 1;
-    }
-    p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = const_cast<void*>(a->o); p.lse = const_cast<float*>(a->lse);
-    p.d_o = a->d_o; p.dqkv = a->dqkv; p.fpart = a->freq_ws; p.dsin = cos_or_stub(a->dsin_tab, a->qkv); p.delta = a->delta;
-    p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
-    p.qtiles = cdiv(a->N, BT);
-    const int grid = a->B * a->heads * p.qtiles;
     hipStream_t st = (hipStream_t)stream;
-    // after the two kernels: the per-workgroup partials of the freqs gradient -> dfreqs (per_bh = workgroups per (sample, head))
     if (a->defer_freqs && a->E < a->N) {  // checked before anything is launched
         LNX_CHECK(g_freq_n == 0 || g_freq_stream == st, "lnx_attn_bwd: postponed freqs folds are pending on another stream (lnx_attn_bwd_flush them first)");
         LNX_CHECK(g_freq_n < LNX_ATTN_DEFER_MAX, "lnx_attn_bwd: %d postponed freqs folds are pending; call lnx_attn_bwd_flush", LNX_ATTN_DEFER_MAX);
     }
-    auto reduce_freqs = [&](int per_bh) {
-        if (a->E >= a->N) return;
+    AttnP p{};
+    int family = LNX_ATTN_KERNEL_NONE;
+    if (attn_setup<ROT>(a, hd, "lnx_attn_bwd", p, family)) return 1;
+    if (ROT) p.W = a->grid_w > 0 ? a->grid_w : 1;
+    p.d_o = a->d_o; p.dqkv = a->dqkv; p.fpart = a->freq_ws; p.dsin = cos_or_stub(a->dsin_tab, a->qkv); p.delta = a->delta;
+    int per_bh = 0;
+    const int rc = is_resident(family) ? attn_bwd_res<ROT>(p, family, st, per_bh) : with_type_hd(a->dtype, hd, [&](auto tc, auto hdc) {
+        return attn_bwd_tiled<typename decltype(tc)::type, decltype(hdc)::value, ROT>(p, family, st, per_bh);
+    });
+    if (rc) return rc;
+    // after the two kernels: the per-workgroup partials of the freqs gradient -> dfreqs (per_bh = workgroups per (sample, head))
+    if (a->E < a->N) {
         if (a->defer_freqs) {
             g_freq_pending[g_freq_n++] = FreqEntry{p.fpart, a->dfreqs, a->B, a->heads, per_bh, hd};
             g_freq_stream = st;
-            return;
-        }
-        if (hd == 64) hipLaunchKernelGGL(rope_freqs_reduce_kernel<64>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
-        else if (hd == 32) hipLaunchKernelGGL(rope_freqs_reduce_kernel<32>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
-        else hipLaunchKernelGGL(rope_freqs_reduce_kernel<128>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
-    };
-    if (a->drop_mask) {
-        LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "lnx_attn_bwd: drop_inv_keep >= 1 and a 4-byte aligned mask");
-        p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
-    }
-    const int family = attn_family(a->dtype, a->N, hd, a->drop_mask != nullptr);
-    g_last_attn.store(family, std::memory_order_relaxed);
-    const bool resident = family == LNX_ATTN_KERNEL_RES4 || family == LNX_ATTN_KERNEL_RES8;
-    if (hd != 64) {  // head_dim 32 / 128: the tiled kernels
-        int per_bh;
-        if (a->dtype == LNX_BF16) per_bh = hd == 32 ? attn_bwd_tiled<bf16_t, 32, ROT>(p, family, st) : attn_bwd_tiled<bf16_t, 128, ROT>(p, family, st);
-        else per_bh = hd == 32 ? attn_bwd_tiled<float, 32, ROT>(p, family, st) : attn_bwd_tiled<float, 128, ROT>(p, family, st);
-        reduce_freqs(per_bh);
-        LNX_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a->drop_mask) {
-        if (a->dtype == LNX_BF16) {
-            typedef bf16_t T;
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float), st, p);
         } else {
-            typedef float T;
-            const size_t lds_k = 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float);
-            static bool once = false;
-            if (!once) {
-                set_lds(attn_bwd_dkv_kernel<T, 4, true, 64, ROT>, lds_k);
-                once = true;
-            }
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, true, 64, ROT>), dim3(grid), dim3(256), lds_k, st, p);
+            with_hd(hd, [&](auto hdc) {
+                hipLaunchKernelGGL(rope_freqs_reduce_kernel<decltype(hdc)::value>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
+            });
         }
-        reduce_freqs(p.qtiles);
-        LNX_LAUNCH_CHECK();
-        return 0;
-    }
-    if (resident) {
-        typedef bf16_t T;
-        const int npad = (a->N + 31) & ~31;
-        const size_t lds_q = (size_t)npad * (2 * AT<T>::TRB);
-        const size_t lds_k = (size_t)npad * (2 * AT<T>::TRB) + (size_t)p.qtiles * BT * 2 * sizeof(float);
-        static bool once = false;
-        if (!once) {
-            set_lds(attn_bwd_dq_res_kernel<T, 8, ROT>, 256 * (2 * AT<T>::TRB));
-            set_lds(attn_bwd_dkv_res_kernel<T, 8, ROT>, 256 * (2 * AT<T>::TRB + 2 * sizeof(float)));
-            once = true;
-        }
-        if (family == LNX_ATTN_KERNEL_RES4) {
-            hipLaunchKernelGGL((attn_bwd_dq_res_kernel<T, 4, ROT>), dim3(a->B * a->heads), dim3(256), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<T, 4, ROT>), dim3(a->B * a->heads), dim3(256), lds_k, st, p);
-        } else {
-            hipLaunchKernelGGL((attn_bwd_dq_res_kernel<T, 8, ROT>), dim3(a->B * a->heads), dim3(512), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_res_kernel<T, 8, ROT>), dim3(a->B * a->heads), dim3(512), lds_k, st, p);
-        }
-        reduce_freqs(1);
-    } else if (a->dtype == LNX_BF16) {
-        typedef bf16_t T;
-        const size_t lds_q = 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG;
-        const size_t lds_k = 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float);
-        if (family == LNX_ATTN_KERNEL_TILED8) {  // 128 queries / keys per workgroup
-            p.qtiles = cdiv(a->N, 128);
-            const int g8 = a->B * a->heads * p.qtiles;
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 8, false, 64, ROT>), dim3(g8), dim3(512), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 8, false, 64, ROT>), dim3(g8), dim3(512), lds_k, st, p);
-            reduce_freqs(p.qtiles);
-        } else {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_k, st, p);
-            reduce_freqs(p.qtiles);
-        }
-    } else {
-        typedef float T;
-        const size_t lds_q = 2 * AT<T>::ROW_IMG + AT<T>::TR_IMG;
-        const size_t lds_k = 2 * AT<T>::ROW_IMG + 2 * AT<T>::TR_IMG + 2 * BT * sizeof(float);
-        static bool once = false;
-        if (!once) {
-            set_lds(attn_bwd_dkv_kernel<T, 4, false, 64, ROT>, lds_k);
-            once = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_q, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 4, false, 64, ROT>), dim3(grid), dim3(256), lds_k, st, p);
-        reduce_freqs(p.qtiles);
     }
     LNX_LAUNCH_CHECK();
     return 0;
