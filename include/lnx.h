@@ -204,7 +204,7 @@ typedef struct lnx_ln_args {
     int64_t ldy;
     lnx_rowmap y_map;
     const void* add;    /* optional [M, C] of x_dtype added to the output (ResNormLayer skip) */
-    int64_t ldadd;
+    int64_t ldadd;      /* a multiple of 4, as ldx / ldy */
     float* mean;        /* [M] or NULL */
     float* rstd;        /* [M] or NULL */
     void* y8;           /* optional second output: MXFP8 copy of the bf16 output (exactly lnx_quantize_mxfp8 of y), compact rows
@@ -229,14 +229,14 @@ typedef struct lnx_ln_bwd_args {
     const float* mean;
     const float* rstd;
     const float* gin;   /* optional fp32 gradient to add (rows via x_map, ldgin); may alias dx */
-    int64_t ldgin;
+    int64_t ldgin;      /* a multiple of 4, as the other leading dimensions */
     void* dx;           /* rows via x_map */
     int dx_dtype;
     int64_t lddx;
     float* dw;          /* [C] += (fp32 atomics) or NULL */
     float* db;
     int relu_mask;      /* 1: x is a ReLU output feeding this LN; dx *= (x > 0) */
-    float* ws;          /* optional scratch for the dw/db column partials (avoids contended atomics) */
+    float* ws;          /* optional scratch for the dw/db column partials (avoids contended atomics); 16-byte aligned */
     int64_t ws_floats;  /* its capacity in floats; 2048*2*C is the most that is used */
     /* optional second output: dx2[m, :] = dx2_rowscale[m / dx2_rows_per_sample] * dx[m, :] in dx2_dtype, identity rows,
      * leading dimension lddx2.  It is the operand the NEXT branch's GEMMs read (DropPath-scaled gradient in storage
@@ -263,6 +263,25 @@ int lnx_layernorm_bwd(const lnx_ln_bwd_args* args, void* stream);
 int lnx_layernorm_bwd_flush(void* stream);
 /* forgets them without summing (error paths; lnx_plan_backward does it on entry and when it fails); returns how many */
 int lnx_layernorm_bwd_discard(void);
+
+/* The launch lnx_layernorm_fwd / lnx_layernorm_bwd WOULD make for these arguments (no launch, no device work, no GPU needed; negative
+ * on arguments the entry point refuses, with its message in lnx_last_error): only shapes, dtypes, leading dimensions, the alignment
+ * of the pointers and WHICH optional operands are non-NULL are looked at, never the memory behind them.  The entry points take
+ * their decision from the same function, so a test can prove which instantiation, grid and column-sum route a case ran on. */
+enum { LNX_LN_COLS_NONE = 0 /* no dw / db wanted */, LNX_LN_COLS_ATOMICS = 1 /* one atomic per column per workgroup */,
+       LNX_LN_COLS_WORKSPACE = 2 /* per-workgroup partials in ws, summed by a second stage of `slices` slices */ };
+typedef struct lnx_ln_launch {
+    int G;       /* lanes per row (pair mode: lanes holding float4 pairs) */
+    int V;       /* float4 slots per lane */
+    int pair;    /* 1: 16-byte accesses on bf16 rows (streamed operands bf16, every pointer and leading dimension 16-byte aligned) */
+    int full;    /* 1: C / 4 == G * V, no partial-row code */
+    int mx;      /* 1: the variant that also writes the MXFP8 copy (y8, dx2_8) */
+    int grid;    /* workgroups of 256 threads */
+    int cols;    /* backward: LNX_LN_COLS_*; forward: 0 */
+    int slices;  /* LNX_LN_COLS_WORKSPACE: 1 or 64 slices of the second stage; otherwise 0 */
+} lnx_ln_launch;
+int lnx_layernorm_fwd_query(const lnx_ln_args* args, lnx_ln_launch* out);
+int lnx_layernorm_bwd_query(const lnx_ln_bwd_args* args, lnx_ln_launch* out);
 
 /* ------------------------------------------------------------------------------------
  * Depthwise 7x7 convolution, padding 3, NHWC (nn.Conv2d(C, C, 7, padding=3, groups=C),

@@ -205,6 +205,9 @@ def lib() -> C.CDLL:
             _lib.lnx_preprocess_scratch_bytes.restype = C.c_int64
             _lib.lnx_preprocess.argtypes = [C.POINTER(PreprocessArgs), C.c_void_p]
             _lib.lnx_preprocess.restype = C.c_int
+        if hasattr(_lib, "lnx_layernorm_fwd_query"):
+            _lib.lnx_layernorm_fwd_query.argtypes = [C.POINTER(LnArgs), C.POINTER(LnLaunch)]
+            _lib.lnx_layernorm_bwd_query.argtypes = [C.POINTER(LnBwdArgs), C.POINTER(LnLaunch)]
         # A/B runs against an OLDER build (LNX_LIB_PATH=... LNX_LIB_OLDER=1): entry points added since are allowed to be missing; calling
         # one then fails with ctypes' AttributeError
         older = bool(os.environ.get("LNX_LIB_PATH")) and os.environ.get("LNX_LIB_OLDER") == "1"
@@ -236,7 +239,7 @@ ATTN_KERNEL_NONE, ATTN_KERNEL_RES4, ATTN_KERNEL_RES8, ATTN_KERNEL_TILED4, ATTN_K
 EXPORTS = [
     "lnx_last_error", "lnx_version", "lnx_device_cus", "lnx_set_cu_margin",
     "lnx_gemm_nt", "lnx_last_nt_kernel", "lnx_nt_kernel_launches", "lnx_nt_dispatch", "lnx_gemm_tn", "lnx_gemm_tn_flush", "lnx_gemm_tn_discard", "lnx_amax", "lnx_quantize_fp8", "lnx_gemm_nt_fp8", "lnx_quantize_mxfp8", "lnx_gemm_nt_mxfp8", "lnx_dropout_mul", "lnx_dropout_residual", "lnx_plan_dropout_bytes", "lnx_plan_set_dropout", "lnx_plan_attn_dropout_bytes", "lnx_plan_set_attn_dropout",
-    "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard",
+    "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard", "lnx_layernorm_fwd_query", "lnx_layernorm_bwd_query",
     "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
@@ -305,6 +308,14 @@ class LnBwdArgs(C.Structure):
         ("dx2_8", C.c_void_p), ("dx2_8_scales", C.c_void_p), ("lddx2_8", C.c_int64),
         ("defer", C.c_int),
     ]
+
+
+# lnx_layernorm_fwd_query / lnx_layernorm_bwd_query: the column-sum route (the LNX_LN_COLS_* of include/lnx.h)
+LN_COLS_NONE, LN_COLS_ATOMICS, LN_COLS_WORKSPACE = range(3)
+
+
+class LnLaunch(C.Structure):  # == lnx_ln_launch
+    _fields_ = [("G", C.c_int), ("V", C.c_int), ("pair", C.c_int), ("full", C.c_int), ("mx", C.c_int), ("grid", C.c_int), ("cols", C.c_int), ("slices", C.c_int)]
 
 
 class RopeTable(C.Structure):

@@ -516,116 +516,121 @@ inline int pick_pair_g(int C) {
     return 0;
 }
 
-template <typename TX, typename TY>
-void launch_fwd(const LnP& p, hipStream_t st) {
-    int G, V;
-    pick_gv(p.C, G, V);
-    if constexpr (sizeof(TX) == 2) {
-        const int g2 = pick_pair_g(p.C);
-        if (g2 && (((uintptr_t)p.x | (uintptr_t)p.y | (uintptr_t)p.add) & 15) == 0 && (p.ldx * 2) % 16 == 0 && (p.ldy * sizeof(TY)) % 16 == 0 && (p.ldadd * 2) % 16 == 0) {
-            int grid = cdiv(p.M, 4 * (64 / g2));
-            if (grid > 4096) grid = 4096;
-            const dim3 gg(grid), bb(256);
-            if (g2 == 4) { if (p.C / 4 == 4 * 6) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 4, 6, 2, true>), gg, bb, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 4, 6, 2, false>), gg, bb, 0, st, p); }
-            else if (g2 == 8) { if (p.C / 4 == 8 * 6) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 8, 6, 2, true>), gg, bb, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 8, 6, 2, false>), gg, bb, 0, st, p); }
-            else if (g2 == 16) { if (p.C / 4 == 16 * 6) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 16, 6, 2, true>), gg, bb, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 16, 6, 2, false>), gg, bb, 0, st, p); }
-            else { if (p.C / 4 == 32 * 6) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 32, 6, 2, true>), gg, bb, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 32, 6, 2, false>), gg, bb, 0, st, p); }
-            return;
-        }
-    }
-    const int rows_per_wg = 4 * (64 / G);
-    int grid = cdiv(p.M, rows_per_wg);
-    if (grid > 4096) grid = 4096;
-    const dim3 g(grid), b(256);
-    if constexpr (sizeof(TX) == 4 && sizeof(TY) == 2) {
-        if (p.y8) {
-            const bool full = p.C / 4 == G * V;
-#define LN_MX(GG, VV)                                                                                            \
-    do {                                                                                                         \
-        if (full) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, GG, VV, 1, true, true>), g, b, 0, st, p);            \
-        else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, GG, VV, 1, false, true>), g, b, 0, st, p);                \
-    } while (0)
-            if (V == 8) LN_MX(64, 8);
-            else if (V == 4) LN_MX(64, 4);
-            else if (V == 6) LN_MX(64, 6);
-            else if (G == 8) LN_MX(8, 3);
-            else if (G == 16) LN_MX(16, 3);
-            else if (G == 32) LN_MX(32, 3);
-            else LN_MX(64, 3);
-#undef LN_MX
-            return;
-        }
-    }
-    if (V == 8) { if (p.C / 4 == 64 * 8) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 8, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 8, 1, false>), g, b, 0, st, p); }
-    else if (V == 4) { if (p.C / 4 == 64 * 4) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 4, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 4, 1, false>), g, b, 0, st, p); }
-    else if (V == 6) { if (p.C / 4 == 64 * 6) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 6, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 6, 1, false>), g, b, 0, st, p); }
-    else if (G == 8) { if (p.C / 4 == 8 * 3) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 8, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 8, 3, 1, false>), g, b, 0, st, p); }
-    else if (G == 16) { if (p.C / 4 == 16 * 3) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 16, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 16, 3, 1, false>), g, b, 0, st, p); }
-    else if (G == 32) { if (p.C / 4 == 32 * 3) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 32, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 32, 3, 1, false>), g, b, 0, st, p); }
-    else { if (p.C / 4 == 64 * 3) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, 64, 3, 1, false>), g, b, 0, st, p); }
-}
-
 constexpr int LN_WS_WGS = 2048;  // workgroups the partial-sum workspace is sized for
 
-template <typename TDY, typename TX, typename TDX>
-void launch_bwd(LnBwdP p, hipStream_t st, int64_t ws_floats, bool defer) {
-    int G, V;
-    pick_gv(p.C, G, V);
-    const int rows_per_wg = 4 * (64 / G);
+// The launch decisions.  They live here and nowhere else: lnx_layernorm_fwd_query / _bwd_query report what these two return, launch_fwd /
+// launch_bwd instantiate what they return.
+lnx_ln_launch plan_fwd(const LnP& p, int xd, int yd) {
+    lnx_ln_launch L = {};
+    pick_gv(p.C, L.G, L.V);
+    if (xd == LNX_BF16) {
+        const int g2 = pick_pair_g(p.C);
+        const int64_t ysize = yd == LNX_BF16 ? 2 : 4;
+        if (g2 && (((uintptr_t)p.x | (uintptr_t)p.y | (uintptr_t)p.add) & 15) == 0 && (p.ldx * 2) % 16 == 0 && (p.ldy * ysize) % 16 == 0 && (p.ldadd * 2) % 16 == 0) {
+            L.G = g2;
+            L.V = 6;
+            L.pair = 1;
+        }
+    }
+    L.full = p.C / 4 == L.G * L.V ? 1 : 0;
+    L.mx = p.y8 != nullptr ? 1 : 0;  // (x fp32: never in pair mode)
+    L.grid = cdiv(p.M, 4 * (64 / L.G));
+    if (L.grid > 4096) L.grid = 4096;
+    return L;
+}
+
+lnx_ln_launch plan_bwd(const LnBwdP& p, int dyd, int xd, int dxd, int64_t ws_floats) {
+    lnx_ln_launch L = {};
+    pick_gv(p.C, L.G, L.V);
     // same-address float atomics serialise (~0.1 us each): with a workspace every workgroup stores its
     // 2C column partials and a second tiny kernel sums them; without one the grid is kept at ~2
     // workgroups per CU so that few workgroups contend
-    int grid = cdiv(p.M, rows_per_wg * 2);
+    L.grid = cdiv(p.M, 4 * (64 / L.G) * 2);
     const bool need_cols = p.dw != nullptr || p.db != nullptr;
-    int cap = 512;
+    L.cols = need_cols ? LNX_LN_COLS_ATOMICS : LNX_LN_COLS_NONE;
+    int cap = need_cols ? 512 : 4096;
     if (p.part && need_cols) {
-        cap = (int)(ws_floats / (2 * (int64_t)p.C));
-        if (cap > LN_WS_WGS) cap = LN_WS_WGS;
-        if (cap < 1) {
-            p.part = nullptr;
-            cap = 512;
+        int64_t c = ws_floats / (2 * (int64_t)p.C);
+        if (c > LN_WS_WGS) c = LN_WS_WGS;
+        if (c >= 1) {
+            cap = (int)c;
+            L.cols = LNX_LN_COLS_WORKSPACE;
         }
-    } else {
-        p.part = nullptr;
-        if (!need_cols) cap = 4096;
     }
-    if (grid > cap) grid = cap;
-    if (grid < 1) grid = 1;
-    const dim3 g(grid), b(256);
-    bool launched = false;
-    if constexpr (sizeof(TDY) == 2 && sizeof(TX) == 2) {
+    if (L.grid > cap) L.grid = cap;
+    if (L.grid < 1) L.grid = 1;
+    if (L.cols == LNX_LN_COLS_WORKSPACE) L.slices = L.grid >= 64 ? 64 : 1;
+    if (dyd == LNX_BF16 && xd == LNX_BF16) {
         const int g2 = pick_pair_g(p.C);
-        if (g2 && (((uintptr_t)p.x | (uintptr_t)p.dy | (uintptr_t)p.dx) & 15) == 0 && (p.ldx * 2) % 16 == 0 && (p.lddy * 2) % 16 == 0 && (p.lddx * sizeof(TDX)) % 16 == 0) {
+        const int64_t dxsize = dxd == LNX_BF16 ? 2 : 4;
+        if (g2 && (((uintptr_t)p.x | (uintptr_t)p.dy | (uintptr_t)p.dx) & 15) == 0 && (p.ldx * 2) % 16 == 0 && (p.lddy * 2) % 16 == 0 && (p.lddx * dxsize) % 16 == 0) {
             // same grid: the partial-sum workspace is indexed by workgroup, rows are walked grid-stride
-            if (g2 == 4) { if (p.C / 4 == 4 * 6) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 4, 6, 2, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 4, 6, 2, false>), g, b, 0, st, p); }
-            else if (g2 == 8) { if (p.C / 4 == 8 * 6) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 8, 6, 2, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 8, 6, 2, false>), g, b, 0, st, p); }
-            else if (g2 == 16) { if (p.C / 4 == 16 * 6) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 16, 6, 2, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 16, 6, 2, false>), g, b, 0, st, p); }
-            else { if (p.C / 4 == 32 * 6) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 32, 6, 2, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 32, 6, 2, false>), g, b, 0, st, p); }
-            launched = true;
+            L.G = g2;
+            L.V = 6;
+            L.pair = 1;
         }
     }
-    if (launched) {
-    } else if (V == 8) { if (p.C / 4 == 64 * 8) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 8, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 8, 1, false>), g, b, 0, st, p); }
-    else if (V == 4) { if (p.C / 4 == 64 * 4) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 4, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 4, 1, false>), g, b, 0, st, p); }
-    else if (V == 6) { if (p.C / 4 == 64 * 6) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 6, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 6, 1, false>), g, b, 0, st, p); }
-    else if (G == 8) { if (p.C / 4 == 8 * 3) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 8, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 8, 3, 1, false>), g, b, 0, st, p); }
-    else if (G == 16) { if (p.C / 4 == 16 * 3) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 16, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 16, 3, 1, false>), g, b, 0, st, p); }
-    else if (G == 32) { if (p.C / 4 == 32 * 3) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 32, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 32, 3, 1, false>), g, b, 0, st, p); }
-    else { if (p.C / 4 == 64 * 3) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 3, 1, true>), g, b, 0, st, p); else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, 64, 3, 1, false>), g, b, 0, st, p); }
+    L.full = p.C / 4 == L.G * L.V ? 1 : 0;
+    L.mx = p.dx2_8 != nullptr ? 1 : 0;  // (x fp32: never in pair mode)
+    return L;
+}
+
+template <typename TX, typename TY>
+void launch_fwd(const LnP& p, const lnx_ln_launch& L, hipStream_t st) {
+    const dim3 g(L.grid), b(256);
+#define LN_FWD(GG, VV, PP, MX)                                                                                       \
+    if (L.G == GG && L.V == VV) {                                                                                    \
+        if (L.full) hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, GG, VV, PP, true, MX>), g, b, 0, st, p);               \
+        else hipLaunchKernelGGL((ln_fwd_kernel<TX, TY, GG, VV, PP, false, MX>), g, b, 0, st, p);                     \
+        return;                                                                                                      \
+    }
+    if constexpr (sizeof(TX) == 2) {
+        if (L.pair) {
+            LN_FWD(4, 6, 2, false) LN_FWD(8, 6, 2, false) LN_FWD(16, 6, 2, false) LN_FWD(32, 6, 2, false)
+        }
+    }
+    if constexpr (sizeof(TX) == 4 && sizeof(TY) == 2) {
+        if (L.mx) {
+            LN_FWD(8, 3, 1, true) LN_FWD(16, 3, 1, true) LN_FWD(32, 3, 1, true) LN_FWD(64, 3, 1, true) LN_FWD(64, 4, 1, true) LN_FWD(64, 6, 1, true) LN_FWD(64, 8, 1, true)
+        }
+    }
+    LN_FWD(8, 3, 1, false) LN_FWD(16, 3, 1, false) LN_FWD(32, 3, 1, false) LN_FWD(64, 3, 1, false) LN_FWD(64, 4, 1, false) LN_FWD(64, 6, 1, false) LN_FWD(64, 8, 1, false)
+#undef LN_FWD
+}
+
+template <typename TDY, typename TX, typename TDX>
+void launch_bwd(LnBwdP p, const lnx_ln_launch& L, hipStream_t st, bool defer) {
+    if (L.cols != LNX_LN_COLS_WORKSPACE) p.part = nullptr;
+    const dim3 g(L.grid), b(256);
+    bool launched = false;
+#define LN_BWD(GG, VV, PP)                                                                                           \
+    if (!launched && L.G == GG && L.V == VV) {                                                                       \
+        if (L.full) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, GG, VV, PP, true>), g, b, 0, st, p);             \
+        else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, GG, VV, PP, false>), g, b, 0, st, p);                   \
+        launched = true;                                                                                             \
+    }
+    if constexpr (sizeof(TDY) == 2 && sizeof(TX) == 2) {
+        if (L.pair) {
+            LN_BWD(4, 6, 2) LN_BWD(8, 6, 2) LN_BWD(16, 6, 2) LN_BWD(32, 6, 2)
+        }
+    }
+    LN_BWD(8, 3, 1) LN_BWD(16, 3, 1) LN_BWD(32, 3, 1) LN_BWD(64, 3, 1) LN_BWD(64, 4, 1) LN_BWD(64, 6, 1) LN_BWD(64, 8, 1)
+#undef LN_BWD
     if (p.part) {
-        const int slices = grid >= 64 ? 64 : 1;
-        if (defer) ln_postpone_reduce(p.part, grid, p.C, p.dw, p.db, slices, st);
-        else hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(cdiv(2 * p.C, 256), slices), dim3(256), 0, st, p.part, grid, p.C, p.dw, p.db);
+        if (defer) ln_postpone_reduce(p.part, L.grid, p.C, p.dw, p.db, L.slices, st);
+        else hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(cdiv(2 * p.C, 256), L.slices), dim3(256), 0, st, p.part, L.grid, p.C, p.dw, p.db);
     }
 }
 
-}  // namespace
+inline bool ln_dtype_ok(int d) { return d == LNX_F32 || d == LNX_BF16; }
 
-extern "C" int lnx_layernorm_fwd(const lnx_ln_args* a, void* stream) {
+// validation + kernel parameters of the forward entry point (shared with its query: host only, nothing is dereferenced)
+int fwd_setup(const lnx_ln_args* a, LnP& p) {
     LNX_CHECK(a && a->x && a->y && a->w && a->b, "lnx_layernorm_fwd: null operand");
     LNX_CHECK(a->M > 0 && a->C > 0 && a->C % 4 == 0 && a->C <= MAXC, "lnx_layernorm_fwd: bad shape M=%d C=%d", a->M, a->C);
     LNX_CHECK(a->ldx % 4 == 0 && a->ldy % 4 == 0, "lnx_layernorm_fwd: ldx/ldy must be multiples of 4");
-    LnP p;
+    LNX_CHECK(a->add == nullptr || a->ldadd % 4 == 0, "lnx_layernorm_fwd: ldadd must be a multiple of 4");
+    LNX_CHECK(ln_dtype_ok(a->x_dtype) && ln_dtype_ok(a->y_dtype), "lnx_layernorm_fwd: bad dtypes %d %d", a->x_dtype, a->y_dtype);
     p.x = a->x; p.add = a->add; p.y = a->y; p.w = a->w; p.b = a->b; p.mean = a->mean; p.rstd = a->rstd;
     p.ldx = a->ldx; p.ldy = a->ldy; p.ldadd = a->ldadd;
     p.xmap = RowMap{a->x_map.group, a->x_map.pad, a->x_map.off};
@@ -637,22 +642,16 @@ extern "C" int lnx_layernorm_fwd(const lnx_ln_args* a, void* stream) {
                   "lnx_layernorm_fwd: the MXFP8 output needs x fp32, y bf16, an identity y_map, C %% 128 == 0 and 4-byte aligned rows");
         p.y8 = (unsigned char*)a->y8; p.y8s = (unsigned char*)a->y8_scales; p.ldy8 = a->ldy8;
     }
-    hipStream_t st = (hipStream_t)stream;
-    const int xi = a->x_dtype, yi = a->y_dtype;
-    if (xi == LNX_F32 && yi == LNX_F32) launch_fwd<float, float>(p, st);
-    else if (xi == LNX_F32 && yi == LNX_BF16) launch_fwd<float, bf16_t>(p, st);
-    else if (xi == LNX_BF16 && yi == LNX_F32) launch_fwd<bf16_t, float>(p, st);
-    else if (xi == LNX_BF16 && yi == LNX_BF16) launch_fwd<bf16_t, bf16_t>(p, st);
-    else LNX_CHECK(false, "lnx_layernorm_fwd: bad dtypes %d %d", xi, yi);
-    LNX_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int lnx_layernorm_bwd(const lnx_ln_bwd_args* a, void* stream) {
+int bwd_setup(const lnx_ln_bwd_args* a, LnBwdP& p) {
     LNX_CHECK(a && a->dy && a->x && a->w && a->mean && a->rstd && a->dx, "lnx_layernorm_bwd: null operand");
     LNX_CHECK(a->M > 0 && a->C > 0 && a->C % 4 == 0 && a->C <= MAXC, "lnx_layernorm_bwd: bad shape M=%d C=%d", a->M, a->C);
     LNX_CHECK(a->ldx % 4 == 0 && a->lddy % 4 == 0 && a->lddx % 4 == 0, "lnx_layernorm_bwd: leading dims must be multiples of 4");
-    LnBwdP p;
+    LNX_CHECK(a->gin == nullptr || a->ldgin % 4 == 0, "lnx_layernorm_bwd: ldgin must be a multiple of 4");
+    LNX_CHECK(a->ws == nullptr || (uintptr_t)a->ws % 16 == 0, "lnx_layernorm_bwd: ws must be 16-byte aligned");
+    LNX_CHECK(ln_dtype_ok(a->dy_dtype) && ln_dtype_ok(a->x_dtype) && ln_dtype_ok(a->dx_dtype), "lnx_layernorm_bwd: bad dtypes");
     p.dy = a->dy; p.x = a->x; p.w = a->w; p.mean = a->mean; p.rstd = a->rstd; p.gin = a->gin; p.dx = a->dx; p.dw = a->dw; p.db = a->db;
     p.lddy = a->lddy; p.ldx = a->ldx; p.lddx = a->lddx; p.ldgin = a->ldgin;
     p.dymap = RowMap{a->dy_map.group, a->dy_map.pad, a->dy_map.off};
@@ -673,19 +672,62 @@ extern "C" int lnx_layernorm_bwd(const lnx_ln_bwd_args* a, void* stream) {
         p.dx2_8 = (unsigned char*)a->dx2_8; p.dx2_8s = (unsigned char*)a->dx2_8_scales; p.lddx2_8 = a->lddx2_8;
     }
     p.part = a->ws;
-    const int64_t wsf = a->ws ? a->ws_floats : 0;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int lnx_layernorm_fwd_query(const lnx_ln_args* a, lnx_ln_launch* out) {
+    LnP p;
+    if (out == nullptr) {
+        lnx_set_error("lnx_layernorm_fwd_query: null result");
+        return -1;
+    }
+    if (fwd_setup(a, p) != 0) return -1;
+    *out = plan_fwd(p, a->x_dtype, a->y_dtype);
+    return 0;
+}
+
+extern "C" int lnx_layernorm_bwd_query(const lnx_ln_bwd_args* a, lnx_ln_launch* out) {
+    LnBwdP p;
+    if (out == nullptr) {
+        lnx_set_error("lnx_layernorm_bwd_query: null result");
+        return -1;
+    }
+    if (bwd_setup(a, p) != 0) return -1;
+    *out = plan_bwd(p, a->dy_dtype, a->x_dtype, a->dx_dtype, a->ws ? a->ws_floats : 0);
+    return 0;
+}
+
+extern "C" int lnx_layernorm_fwd(const lnx_ln_args* a, void* stream) {
+    LnP p;
+    if (fwd_setup(a, p) != 0) return 1;
+    const lnx_ln_launch L = plan_fwd(p, a->x_dtype, a->y_dtype);
     hipStream_t st = (hipStream_t)stream;
-    const int code = a->dy_dtype * 4 + a->x_dtype * 2 + a->dx_dtype;
-    switch (code) {
-        case 0: launch_bwd<float, float, float>(p, st, wsf, a->defer != 0); break;
-        case 1: launch_bwd<float, float, bf16_t>(p, st, wsf, a->defer != 0); break;
-        case 2: launch_bwd<float, bf16_t, float>(p, st, wsf, a->defer != 0); break;
-        case 3: launch_bwd<float, bf16_t, bf16_t>(p, st, wsf, a->defer != 0); break;
-        case 4: launch_bwd<bf16_t, float, float>(p, st, wsf, a->defer != 0); break;
-        case 5: launch_bwd<bf16_t, float, bf16_t>(p, st, wsf, a->defer != 0); break;
-        case 6: launch_bwd<bf16_t, bf16_t, float>(p, st, wsf, a->defer != 0); break;
-        case 7: launch_bwd<bf16_t, bf16_t, bf16_t>(p, st, wsf, a->defer != 0); break;
-        default: LNX_CHECK(false, "lnx_layernorm_bwd: bad dtypes");
+    const int xi = a->x_dtype, yi = a->y_dtype;
+    if (xi == LNX_F32 && yi == LNX_F32) launch_fwd<float, float>(p, L, st);
+    else if (xi == LNX_F32 && yi == LNX_BF16) launch_fwd<float, bf16_t>(p, L, st);
+    else if (xi == LNX_BF16 && yi == LNX_F32) launch_fwd<bf16_t, float>(p, L, st);
+    else launch_fwd<bf16_t, bf16_t>(p, L, st);
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_layernorm_bwd(const lnx_ln_bwd_args* a, void* stream) {
+    LnBwdP p;
+    if (bwd_setup(a, p) != 0) return 1;
+    const lnx_ln_launch L = plan_bwd(p, a->dy_dtype, a->x_dtype, a->dx_dtype, a->ws ? a->ws_floats : 0);
+    hipStream_t st = (hipStream_t)stream;
+    const bool defer = a->defer != 0;
+    switch (a->dy_dtype * 4 + a->x_dtype * 2 + a->dx_dtype) {
+        case 0: launch_bwd<float, float, float>(p, L, st, defer); break;
+        case 1: launch_bwd<float, float, bf16_t>(p, L, st, defer); break;
+        case 2: launch_bwd<float, bf16_t, float>(p, L, st, defer); break;
+        case 3: launch_bwd<float, bf16_t, bf16_t>(p, L, st, defer); break;
+        case 4: launch_bwd<bf16_t, float, float>(p, L, st, defer); break;
+        case 5: launch_bwd<bf16_t, float, bf16_t>(p, L, st, defer); break;
+        case 6: launch_bwd<bf16_t, bf16_t, float>(p, L, st, defer); break;
+        default: launch_bwd<bf16_t, bf16_t, bf16_t>(p, L, st, defer); break;
     }
     LNX_LAUNCH_CHECK();
     return 0;

@@ -178,7 +178,7 @@ def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, 
     return dW
 
 
-def layernorm_fwd(x, w, b, y, eps, *, M=None, C_=None, ldx=None, ldy=None, x_map=None, y_map=None, add=None, mean=None, rstd=None, y8=None, y8_scales=None):
+def _ln_args(x, w, b, y, eps, *, M=None, C_=None, ldx=None, ldy=None, x_map=None, y_map=None, add=None, ldadd=None, mean=None, rstd=None, y8=None, y8_scales=None):
     a = L.LnArgs()
     a.M = M if M is not None else x.shape[0]
     a.C = C_ if C_ is not None else x.shape[-1]
@@ -186,16 +186,30 @@ def layernorm_fwd(x, w, b, y, eps, *, M=None, C_=None, ldx=None, ldy=None, x_map
     a.x, a.x_dtype, a.ldx, a.x_map = _p(x), code_of(x), (ldx if ldx is not None else x.stride(-2)), _map(x_map)
     a.w, a.b = _p(w), _p(b)
     a.y, a.y_dtype, a.ldy, a.y_map = _p(y), code_of(y), (ldy if ldy is not None else y.stride(-2)), _map(y_map)
-    a.add, a.ldadd = _p(add), (add.stride(-2) if add is not None else 0)
+    a.add, a.ldadd = _p(add), ((ldadd if ldadd is not None else add.stride(-2)) if add is not None else 0)
     a.mean, a.rstd = _p(mean), _p(rstd)
     if y8 is not None:
         a.y8, a.ldy8, a.y8_scales = _p(y8), y8.stride(0), _p(y8_scales)
+    return a
+
+
+def layernorm_fwd(x, w, b, y, eps, **kw):
+    a = _ln_args(x, w, b, y, eps, **kw)
     L.check(L.lib().lnx_layernorm_fwd(C.byref(a), _stream()), "lnx_layernorm_fwd")
     return y
 
 
-def layernorm_bwd(dy, x, w, mean, rstd, dx, *, M=None, C_=None, lddy=None, ldx=None, lddx=None, dy_map=None, x_map=None, gin=None,
-                  ldgin=None, dw=None, db=None, relu_mask=False, ws=None, dx2=None, dx2_rowscale=None, dx2_rows_per_sample=0, dx2_8=None, dx2_8_scales=None, defer=False):
+def layernorm_fwd_query(x, w, b, y, eps=0.0, **kw) -> L.LnLaunch:
+    """The launch layernorm_fwd would make for the same arguments (lnx_layernorm_fwd_query: nothing runs)."""
+    a, out = _ln_args(x, w, b, y, eps, **kw), L.LnLaunch()
+    if L.lib().lnx_layernorm_fwd_query(C.byref(a), C.byref(out)) != 0:
+        raise L.LnxError(f"lnx_layernorm_fwd_query refused: {L.lib().lnx_last_error().decode()}")
+    return out
+
+
+def _ln_bwd_args(dy, x, w, mean, rstd, dx, *, M=None, C_=None, lddy=None, ldx=None, lddx=None, dy_map=None, x_map=None, gin=None,
+                 ldgin=None, dw=None, db=None, relu_mask=False, ws=None, dx2=None, lddx2=None, dx2_rowscale=None, dx2_rows_per_sample=0, dx2_8=None,
+                 dx2_8_scales=None, defer=False):
     a = L.LnBwdArgs()
     a.M = M if M is not None else dy.shape[0]
     a.C = C_ if C_ is not None else x.shape[-1]
@@ -208,12 +222,25 @@ def layernorm_bwd(dy, x, w, mean, rstd, dx, *, M=None, C_=None, lddy=None, ldx=N
     a.ws, a.ws_floats = _p(ws), (ws.numel() if ws is not None else 0)
     a.defer = int(defer)  # column-sum reduce postponed to layernorm_bwd_flush() (needs ws, one per pending call)
     if dx2 is not None:  # second output: rowscale[m // rows_per_sample] * dx in dx2's type (+ its MXFP8 copy)
-        a.dx2, a.dx2_dtype, a.lddx2 = _p(dx2), code_of(dx2), dx2.stride(-2)
+        a.dx2, a.dx2_dtype, a.lddx2 = _p(dx2), code_of(dx2), (lddx2 if lddx2 is not None else dx2.stride(-2))
         a.dx2_rowscale, a.dx2_rows_per_sample = _p(dx2_rowscale), int(dx2_rows_per_sample)
         if dx2_8 is not None:
             a.dx2_8, a.dx2_8_scales, a.lddx2_8 = _p(dx2_8), _p(dx2_8_scales), dx2_8.stride(-2)
+    return a
+
+
+def layernorm_bwd(dy, x, w, mean, rstd, dx, **kw):
+    a = _ln_bwd_args(dy, x, w, mean, rstd, dx, **kw)
     L.check(L.lib().lnx_layernorm_bwd(C.byref(a), _stream()), "lnx_layernorm_bwd")
     return dx
+
+
+def layernorm_bwd_query(dy, x, w, mean, rstd, dx, **kw) -> L.LnLaunch:
+    """The launch layernorm_bwd would make for the same arguments (lnx_layernorm_bwd_query: nothing runs)."""
+    a, out = _ln_bwd_args(dy, x, w, mean, rstd, dx, **kw), L.LnLaunch()
+    if L.lib().lnx_layernorm_bwd_query(C.byref(a), C.byref(out)) != 0:
+        raise L.LnxError(f"lnx_layernorm_bwd_query refused: {L.lib().lnx_last_error().decode()}")
+    return out
 
 
 def layernorm_bwd_flush():

@@ -789,7 +789,8 @@ def test_mxfp8_256x256_kernel_at_xl_rows(M, N, K):
     torch.testing.assert_close(o32.double(), res.double() + rs.double().repeat_interleave(199)[:, None] * h, rtol=1e-4, atol=1e-4 * max(1.0, ref.abs().max().item()))
 
 
-@pytest.mark.parametrize("M,C", [(1000, 384), (777, 768), (300, 1024), (513, 2048), (64, 128), (200, 256), (130, 1536), (99, 1280)])
+@pytest.mark.parametrize("M,C", [(1000, 384), (777, 768), (300, 1024), (513, 2048), (64, 128), (200, 256), (130, 1536), (99, 1280),
+                                 (37, 512), (37, 640), (21, 896), (21, 1152), (21, 1792)])  # (the partial (64, 3 / 4 / 6 / 8) classes an fp8 plan can reach)
 def test_layernorm_fused_mxfp8_output(M, C):
     """LayerNorm forward with the MXFP8 second output (the producer side of the model's fp8 mode): the bf16 output is what
     it is without the second output, and the fp8 bytes / block scales equal lnx_quantize_mxfp8 of that bf16 output exactly."""
@@ -812,7 +813,8 @@ def test_layernorm_fused_mxfp8_output(M, C):
     torch.testing.assert_close(mean, x.mean(-1), rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("M,C,rps", [(1000, 384, 50), (777, 768, 7), (300, 1024, 100), (513, 2048, 53), (64, 128, 64), (130, 1536, 13), (2001, 1280, 200)])
+@pytest.mark.parametrize("M,C,rps", [(1000, 384, 50), (777, 768, 7), (300, 1024, 100), (513, 2048, 53), (64, 128, 64), (130, 1536, 13), (2001, 1280, 200),
+                                     (37, 512, 10), (37, 640, 7), (21, 896, 5), (21, 1152, 21), (21, 1792, 4)])
 def test_layernorm_bwd_second_output_and_its_mxfp8_copy(M, C, rps):
     """LayerNorm backward with the second output (dx2 = DropPath scale of the row's sample x dx in bf16: the dY the next branch's GEMMs read)
     and, round 4, its MXFP8 copy for fp8 plans' data-gradient products: dx and the column sums are what they are without the second
