@@ -1081,11 +1081,11 @@ typedef struct lnx_mformer_cfg {
     int fp8;                   /* 1 (with dtype = LNX_BF16): the forward products of the RoPE blocks' qkv / fc1 / fc2 Linear layers run
                                   on the block-scaled fp8 matrix cores (MXFP8: lnx_quantize_mxfp8 + lnx_gemm_nt_mxfp8) -- BASELINE
                                   config 5's "fp8 MFMA path".  Weights are re-quantised from the fp32 masters every forward,
-                                  activations as they are produced; everything saved for the backward, and the backward, stay
-                                  bf16 (environment LNX_FP8_DGRAD=1: the proj / fc2 / fc1 data-gradient products in MXFP8 as
-                                  well, gradients quantised per 32-element block, dY as the MXFP8 copy the LayerNorm backward
-                                  writes beside its bf16 output -- measured: +1 % speed at xl for a quarter more gradient
-                                  error, so off by default).  Needs RoPE dims and MLP widths that are multiples
+                                  activations as they are produced; everything saved for the backward stays bf16.  In the backward
+                                  the proj / fc2 / fc1 data-gradient products run in MXFP8 as well (gradients quantised per
+                                  32-element block, dY as the MXFP8 copy the LayerNorm backward writes beside its bf16 output --
+                                  measured: +1 % speed at xl for a quarter more gradient error); environment LNX_FP8_DGRAD=0,
+                                  read at plan creation, keeps them bf16.  Needs RoPE dims and MLP widths that are multiples
                                   of 128. */
     int rope_mode;             /* LNX_ROPE_COS (0, the reference as it runs) or LNX_ROPE_ROTATE (MODEL.ROPE_STAGES.ROPE_ROTATE): every RoPE
                                   block's attention rotates q and k (see lnx_attn_args.rope_mode) in the forward, the backward and a

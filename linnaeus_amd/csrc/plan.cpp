@@ -60,12 +60,12 @@ struct OpW {          // a GEMM weight in the T-typed operand arena
 struct ConvBlk {
     bool fused = false;  // pwconv1 -> GELU -> pwconv2 -> LayerScale -> residual in one kernel (hidden tensor stays on chip)
     bool fused_ln = false;  // ... and the block LayerNorm (forward and backward) inside those kernels: no separate LayerNorm pass
-    bool keep_z = true;     // the pwconv2 output z is saved for the LayerScale gradient; false (fused blocks, round 4): dgamma comes from the
-                            // pwconv2 weight gradient instead (lnx_layerscale_apply_wgrad) and z is neither written nor read
     int gamma, dww, dwb, lnw, lnb, b1, b2;
     OpW w1, w2;
     int64_t w49;  // fp32 [49][C] in the arena
     // saved
+    // hpre, act, z: unfused blocks only.  A fused block keeps the hidden tensor on chip and reads its LayerScale gradient off the pwconv2
+    // weight gradient (lnx_layerscale_apply_wgrad), so z is neither written nor read
     int64_t xin, y, ln, mean, rstd, hpre, act, z;
 };
 struct RopeBlk {
@@ -97,9 +97,10 @@ struct lnx_plan {
     int esz;  // sizeof(T)
     int E;    // extra tokens
     int H[4], W[4], HW[4];
-    int N2, N3;
+    int Ntok[2];  // tokens per sample of the two RoPE stages: HW + E
     std::vector<std::string> names;
     std::vector<int64_t> numel;
+    std::vector<signed char> seg;  // the backward segment (0-3) after which the parameter's gradient is final
     std::vector<const float*> P;
     std::vector<float*> G;
     bool bound = false, has_grads = false, fwd_done = false;
@@ -124,6 +125,7 @@ struct lnx_plan {
 
     // workspace offsets
     int64_t o_descs = 0, n_descs = 0, prep_blocks = 0;
+    int64_t arena_end = 0;  // end of the weight copies: zeroed at bind, so that their K / N padding stays zero across refreshes
     int64_t n_descs_t = 0, n_descs_f = 0, prep_blocks_f = 0;  // T-typed table first, fp32-typed table after it
     int64_t o_patches, o_stem_pre, o_stem_mean, o_stem_rstd;
     int64_t o_stage_out[4];   // fp32 output of each stage (input of the next downsample / norm)
@@ -195,124 +197,15 @@ struct lnx_plan {
 
 namespace {
 
-int find_param(const lnx_plan* p, const std::string& n) {
-    for (size_t i = 0; i < p->names.size(); ++i)
-        if (p->names[i] == n) return (int)i;
-    return -1;
+bool env_set(const char* name) { return getenv(name) != nullptr; }
+bool env_off(const char* name) {  // the A/B switches that default to on: set and equal to 0
+    const char* e = getenv(name);
+    return e != nullptr && atoi(e) == 0;
 }
 
-void add_param(lnx_plan* p, const std::string& n, int64_t numel) {
-    p->names.push_back(n);
-    p->numel.push_back(numel);
-}
-
-// parameter inventory in the reference's state_dict order (mFormerV1.py:145-343; checked
-// against the reference by tests/golden/gen/make_golden.py through oracle.param_shapes)
-void build_inventory(lnx_plan* p) {
-    const lnx_mformer_cfg& c = p->c;
-    const int* D = c.dims;
-    char b[128];
-    add_param(p, "cls_token_1", D[2]);
-    add_param(p, "cls_token_2", D[3]);
-    add_param(p, "stem.0.weight", (int64_t)D[0] * c.in_chans * 16);
-    add_param(p, "stem.0.bias", D[0]);
-    add_param(p, "stem.1.weight", D[0]);
-    add_param(p, "stem.1.bias", D[0]);
-    for (int i = 0; i < 3; ++i) {
-        snprintf(b, sizeof b, "downsample_layers.%d.", i);
-        const std::string pre(b);
-        add_param(p, pre + "norm.weight", D[i]);
-        add_param(p, pre + "norm.bias", D[i]);
-        add_param(p, pre + "conv.weight", (int64_t)D[i + 1] * D[i] * 4);
-        add_param(p, pre + "conv.bias", D[i + 1]);
-    }
-    for (int s = 0; s < 2; ++s)
-        for (int i = 0; i < c.conv_depths[s]; ++i) {
-            snprintf(b, sizeof b, "stages.%d.%d.", s, i);
-            const std::string pre(b);
-            const int64_t C = D[s];
-            add_param(p, pre + "gamma", C);
-            add_param(p, pre + "dwconv.weight", C * 49);
-            add_param(p, pre + "dwconv.bias", C);
-            add_param(p, pre + "norm.weight", C);
-            add_param(p, pre + "norm.bias", C);
-            add_param(p, pre + "pwconv1.weight", 4 * C * C);
-            add_param(p, pre + "pwconv1.bias", 4 * C);
-            add_param(p, pre + "pwconv2.weight", 4 * C * C);
-            add_param(p, pre + "pwconv2.bias", C);
-        }
-    for (int s = 0; s < 2; ++s)
-        for (int i = 0; i < c.rope_depths[s]; ++i) {
-            snprintf(b, sizeof b, "stages.%d.%d.", s + 2, i);
-            const std::string pre(b);
-            const int64_t C = D[2 + s], hid = c.mlp_hidden[s];
-            add_param(p, pre + "norm1.weight", C);
-            add_param(p, pre + "norm1.bias", C);
-            add_param(p, pre + "norm2.weight", C);
-            add_param(p, pre + "norm2.bias", C);
-            add_param(p, pre + "attn.freqs", C);  // [2, heads, head_dim / 2]: 2 * heads * head_dim / 2 = C
-            add_param(p, pre + "attn.qkv.weight", 3 * C * C);
-            add_param(p, pre + "attn.qkv.bias", 3 * C);
-            add_param(p, pre + "attn.proj.weight", C * C);
-            add_param(p, pre + "attn.proj.bias", C);
-            add_param(p, pre + "mlp.fc1.weight", hid * C);
-            add_param(p, pre + "mlp.fc1.bias", hid);
-            add_param(p, pre + "mlp.fc2.weight", C * hid);
-            add_param(p, pre + "mlp.fc2.bias", C);
-        }
-    add_param(p, "norm_1.weight", D[2]);
-    add_param(p, "norm_1.bias", D[2]);
-    add_param(p, "norm_2.weight", D[3]);
-    add_param(p, "norm_2.bias", D[3]);
-    for (int m = 0; m < c.n_meta; ++m)
-        for (int s = 0; s < 2; ++s) {
-            snprintf(b, sizeof b, "meta.%d.head_%d.", m, s + 1);
-            const std::string pre(b);
-            const int64_t C = D[2 + s];
-            add_param(p, pre + "0.weight", C * c.meta_dims[m]);
-            add_param(p, pre + "0.bias", C);
-            add_param(p, pre + "2.weight", C);
-            add_param(p, pre + "2.bias", C);
-            add_param(p, pre + "3.norm_fn1.weight", C);
-            add_param(p, pre + "3.norm_fn1.bias", C);
-            add_param(p, pre + "3.norm_fn2.weight", C);
-            add_param(p, pre + "3.norm_fn2.bias", C);
-            add_param(p, pre + "3.w1.weight", C * C);
-            add_param(p, pre + "3.w1.bias", C);
-            add_param(p, pre + "3.w2.weight", C * C);
-            add_param(p, pre + "3.w2.bias", C);
-        }
-    if (!c.only_last_cls) {
-        add_param(p, "cl_1_fc.0.fc1.weight", (int64_t)D[2] * D[2]);
-        add_param(p, "cl_1_fc.0.fc1.bias", D[2]);
-        add_param(p, "cl_1_fc.0.fc2.weight", (int64_t)D[3] * D[2]);
-        add_param(p, "cl_1_fc.0.fc2.bias", D[3]);
-        add_param(p, "cl_1_fc.1.weight", D[3]);
-        add_param(p, "cl_1_fc.1.bias", D[3]);
-        add_param(p, "aggregate.weight", 2);
-        add_param(p, "aggregate.bias", 1);
-    }
-    add_param(p, "final_norm.weight", D[3]);
-    add_param(p, "final_norm.bias", D[3]);
-    for (int t = 0; t < c.n_tasks; ++t) {
-        snprintf(b, sizeof b, "head.%d.", t);
-        add_param(p, std::string(b) + "weight", (int64_t)c.task_classes[t] * D[3]);
-        add_param(p, std::string(b) + "bias", c.task_classes[t]);
-    }
-}
-
-struct Carver {
-    int64_t cur = 0;
-    int64_t take(int64_t bytes) {
-        const int64_t o = cur;
-        cur += align_up(bytes > 0 ? bytes : 16, 256);
-        return o;
-    }
-};
-
-OpW make_w(lnx_plan* p, const std::string& name, int N, int K, bool want_t, int mode = LNX_PREP_CAST, int P = 0, bool f32 = false) {
+OpW make_w(lnx_plan* p, int param, int N, int K, bool want_t, int mode = LNX_PREP_CAST, int P = 0, bool f32 = false) {
     OpW w;
-    w.param = find_param(p, name);
+    w.param = param;
     w.N = N;
     w.K = K;
     w.f32 = f32 || p->esz == 4;
@@ -324,6 +217,150 @@ OpW make_w(lnx_plan* p, const std::string& name, int N, int K, bool want_t, int 
     w.P = P;
     return w;
 }
+
+// The parameters, once: inventory in the reference's state_dict order (mFormerV1.py:145-343; checked against the reference by
+// tests/golden/gen/make_golden.py through oracle.param_shapes), the handle of each in the plan, its operand-arena entry if it is a
+// GEMM weight, and the backward segment that finishes its gradient: 0 tail + stage 4 + downsample 3, 1 stage 3 + downsample 2,
+// 2 ConvNeXt stage 2 + downsample 1, 3 ConvNeXt stage 1 + stem.
+void build_params(lnx_plan* p) {
+    const lnx_mformer_cfg& c = p->c;
+    const int* D = c.dims;
+    const int B = c.batch;
+    char b[128];
+    auto add = [&](const std::string& name, int64_t numel, int seg) {
+        p->names.push_back(name);
+        p->numel.push_back(numel);
+        p->seg.push_back((signed char)seg);
+        return (int)p->names.size() - 1;
+    };
+    p->cls[0] = add("cls_token_1", D[2], 1);
+    p->cls[1] = add("cls_token_2", D[3], 0);
+    p->stem_w = make_w(p, add("stem.0.weight", (int64_t)D[0] * c.in_chans * 16, 3), D[0], c.in_chans * 16, false);
+    p->stem_w.ld = 64;
+    p->stem_b = add("stem.0.bias", D[0], 3);
+    p->stem_lnw = add("stem.1.weight", D[0], 3);
+    p->stem_lnb = add("stem.1.bias", D[0], 3);
+    for (int i = 0; i < 3; ++i) {
+        snprintf(b, sizeof b, "downsample_layers.%d.", i);
+        const std::string pre(b);
+        Down& k = p->down[i];
+        const int seg = 2 - i;
+        k.lnw = add(pre + "norm.weight", D[i], seg);
+        k.lnb = add(pre + "norm.bias", D[i], seg);
+        k.w = make_w(p, add(pre + "conv.weight", (int64_t)D[i + 1] * D[i] * 4, seg), D[i + 1], 4 * D[i], true, LNX_PREP_CONV_PERM, 4);
+        k.cb = add(pre + "conv.bias", D[i + 1], seg);
+    }
+    int call = 0;  // DropPath calls in forward order: the conv blocks, then per RoPE block the attention branch and the MLP branch
+    for (int s = 0; s < 2; ++s) {
+        p->conv[s].resize(c.conv_depths[s]);
+        for (int i = 0; i < c.conv_depths[s]; ++i) {
+            snprintf(b, sizeof b, "stages.%d.%d.", s, i);
+            const std::string pre(b);
+            ConvBlk& k = p->conv[s][i];
+            const int C = D[s], seg = 3 - s;
+            k.gamma = add(pre + "gamma", C, seg);
+            k.dww = add(pre + "dwconv.weight", (int64_t)C * 49, seg);
+            k.dwb = add(pre + "dwconv.bias", C, seg);
+            k.lnw = add(pre + "norm.weight", C, seg);
+            k.lnb = add(pre + "norm.bias", C, seg);
+            k.w1 = make_w(p, add(pre + "pwconv1.weight", (int64_t)4 * C * C, seg), 4 * C, C, true);
+            k.b1 = add(pre + "pwconv1.bias", 4 * C, seg);
+            k.w2 = make_w(p, add(pre + "pwconv2.weight", (int64_t)4 * C * C, seg), C, 4 * C, true);
+            k.b2 = add(pre + "pwconv2.bias", C, seg);
+            p->drop_conv[s].push_back(call++);
+        }
+    }
+    for (int s = 0; s < 2; ++s) {
+        p->rope[s].resize(c.rope_depths[s]);
+        for (int i = 0; i < c.rope_depths[s]; ++i) {
+            snprintf(b, sizeof b, "stages.%d.%d.", s + 2, i);
+            const std::string pre(b);
+            RopeBlk& k = p->rope[s][i];
+            const int C = D[2 + s], hid = c.mlp_hidden[s], seg = 1 - s;
+            k.n1w = add(pre + "norm1.weight", C, seg);
+            k.n1b = add(pre + "norm1.bias", C, seg);
+            k.n2w = add(pre + "norm2.weight", C, seg);
+            k.n2b = add(pre + "norm2.bias", C, seg);
+            k.freqs = add(pre + "attn.freqs", C, seg);  // [2, heads, head_dim / 2]: 2 * heads * head_dim / 2 = C
+            k.qkv = make_w(p, add(pre + "attn.qkv.weight", (int64_t)3 * C * C, seg), 3 * C, C, true);
+            k.qkvb = add(pre + "attn.qkv.bias", 3 * C, seg);
+            k.proj = make_w(p, add(pre + "attn.proj.weight", (int64_t)C * C, seg), C, C, true);
+            k.projb = add(pre + "attn.proj.bias", C, seg);
+            k.fc1 = make_w(p, add(pre + "mlp.fc1.weight", (int64_t)hid * C, seg), hid, C, true);
+            k.fc1b = add(pre + "mlp.fc1.bias", hid, seg);
+            k.fc2 = make_w(p, add(pre + "mlp.fc2.weight", (int64_t)C * hid, seg), C, hid, true);
+            k.fc2b = add(pre + "mlp.fc2.bias", C, seg);
+            p->drop_attn[s].push_back(call++);
+            p->drop_mlp[s].push_back(call++);
+        }
+    }
+    p->n_drop = call;
+    for (int s = 0; s < 2; ++s) {
+        snprintf(b, sizeof b, "norm_%d.", s + 1);
+        p->norm_w[s] = add(std::string(b) + "weight", D[2 + s], 0);
+        p->norm_b[s] = add(std::string(b) + "bias", D[2 + s], 0);
+        p->meta[s].resize(c.n_meta);
+    }
+    int off = 0;  // a component's columns in the metadata row: the prefix sum of meta_dims
+    for (int m = 0; m < c.n_meta; ++m) {
+        for (int s = 0; s < 2; ++s) {
+            snprintf(b, sizeof b, "meta.%d.head_%d.", m, s + 1);
+            const std::string pre(b);
+            MetaHead& k = p->meta[s][m];
+            // metadata heads run beside the launch stream and are joined one segment after the one that forks them
+            const int C = D[2 + s], seg = 2 - s;
+            k.dim = c.meta_dims[m];
+            k.off = off;
+            k.w0 = make_w(p, add(pre + "0.weight", (int64_t)C * k.dim, seg), C, k.dim, false, LNX_PREP_CAST, 0, true);
+            k.b0 = add(pre + "0.bias", C, seg);
+            k.lnw0 = add(pre + "2.weight", C, seg);
+            k.lnb0 = add(pre + "2.bias", C, seg);
+            k.nf1w = add(pre + "3.norm_fn1.weight", C, seg);
+            k.nf1b = add(pre + "3.norm_fn1.bias", C, seg);
+            k.nf2w = add(pre + "3.norm_fn2.weight", C, seg);
+            k.nf2b = add(pre + "3.norm_fn2.bias", C, seg);
+            k.w1 = make_w(p, add(pre + "3.w1.weight", (int64_t)C * C, seg), C, C, true, LNX_PREP_CAST, 0, true);
+            k.b1 = add(pre + "3.w1.bias", C, seg);
+            k.w2 = make_w(p, add(pre + "3.w2.weight", (int64_t)C * C, seg), C, C, true, LNX_PREP_CAST, 0, true);
+            k.b2 = add(pre + "3.w2.bias", C, seg);
+        }
+        off += c.meta_dims[m];
+    }
+    if (!c.only_last_cls) {
+        p->cl_w1 = make_w(p, add("cl_1_fc.0.fc1.weight", (int64_t)D[2] * D[2], 0), D[2], D[2], true);
+        p->cl_b1 = add("cl_1_fc.0.fc1.bias", D[2], 0);
+        p->cl_w2 = make_w(p, add("cl_1_fc.0.fc2.weight", (int64_t)D[3] * D[2], 0), D[3], D[2], true);
+        p->cl_b2 = add("cl_1_fc.0.fc2.bias", D[3], 0);
+        p->cl_lnw = add("cl_1_fc.1.weight", D[3], 0);
+        p->cl_lnb = add("cl_1_fc.1.bias", D[3], 0);
+        p->agg_w = add("aggregate.weight", 2, 0);
+        p->agg_b = add("aggregate.bias", 1, 0);
+    }
+    p->fin_w = add("final_norm.weight", D[3], 0);
+    p->fin_b = add("final_norm.bias", D[3], 0);
+    p->head_w.resize(c.n_tasks);
+    p->head_b.resize(c.n_tasks);
+    p->logit_ld.resize(c.n_tasks);
+    p->logit_off.resize(c.n_tasks);
+    for (int t = 0; t < c.n_tasks; ++t) {
+        snprintf(b, sizeof b, "head.%d.", t);
+        p->head_w[t] = make_w(p, add(std::string(b) + "weight", (int64_t)c.task_classes[t] * D[3], 0), c.task_classes[t], D[3], true);
+        p->head_b[t] = add(std::string(b) + "bias", c.task_classes[t], 0);
+        p->logit_ld[t] = (int)align_up(c.task_classes[t], 8);
+        p->head_w[t].ld_t = p->logit_ld[t];  // the data-gradient GEMM contracts over the padded logits row
+        p->logit_off[t] = p->logits_numel;
+        p->logits_numel += (int64_t)B * p->logit_ld[t];
+    }
+}
+
+struct Carver {
+    int64_t cur = 0;
+    int64_t take(int64_t bytes) {
+        const int64_t o = cur;
+        cur += align_up(bytes > 0 ? bytes : 16, 256);
+        return o;
+    }
+};
 
 }  // namespace
 
@@ -356,9 +393,9 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     lnx_plan* p = new lnx_plan();
     p->c = c;
     p->esz = c.dtype == LNX_BF16 ? 2 : 4;
-    p->meta_chain = !(getenv("LNX_META_CHAIN") && atoi(getenv("LNX_META_CHAIN")) == 0);
-    p->ln_defer = !(getenv("LNX_LN_DEFER") && atoi(getenv("LNX_LN_DEFER")) == 0);
-    p->freq_defer = !(getenv("LNX_FREQ_DEFER") && atoi(getenv("LNX_FREQ_DEFER")) == 0);
+    p->meta_chain = !env_off("LNX_META_CHAIN");
+    p->ln_defer = !env_off("LNX_LN_DEFER");
+    p->freq_defer = !env_off("LNX_FREQ_DEFER");
     for (int s = 0; s < 2; ++s) p->chain_ok[s] = p->meta_chain && lnx_meta_heads_supported(c.dims[2 + s]) != 0;
     p->E = 1 + c.n_meta;
     p->H[0] = c.img_h / 4;
@@ -368,128 +405,11 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         p->W[i] = p->W[i - 1] / 2;
     }
     for (int i = 0; i < 4; ++i) p->HW[i] = p->H[i] * p->W[i];
-    p->N2 = p->HW[2] + p->E;
-    p->N3 = p->HW[3] + p->E;
-    build_inventory(p);
+    for (int s = 0; s < 2; ++s) p->Ntok[s] = p->HW[2 + s] + p->E;
+    build_params(p);
     const int* D = c.dims;
     const int B = c.batch;
     const int esz = p->esz;
-    char b[128];
-
-    // ---- parameter handles and operand-arena entries ----
-    p->cls[0] = find_param(p, "cls_token_1");
-    p->cls[1] = find_param(p, "cls_token_2");
-    p->stem_w = make_w(p, "stem.0.weight", D[0], c.in_chans * 16, false);
-    p->stem_w.ld = 64;
-    p->stem_b = find_param(p, "stem.0.bias");
-    p->stem_lnw = find_param(p, "stem.1.weight");
-    p->stem_lnb = find_param(p, "stem.1.bias");
-    for (int i = 0; i < 3; ++i) {
-        snprintf(b, sizeof b, "downsample_layers.%d.", i);
-        const std::string pre(b);
-        p->down[i].lnw = find_param(p, pre + "norm.weight");
-        p->down[i].lnb = find_param(p, pre + "norm.bias");
-        p->down[i].cb = find_param(p, pre + "conv.bias");
-        p->down[i].w = make_w(p, pre + "conv.weight", D[i + 1], 4 * D[i], true, LNX_PREP_CONV_PERM, 4);
-    }
-    int call = 0;
-    for (int s = 0; s < 2; ++s) {
-        p->conv[s].resize(c.conv_depths[s]);
-        for (int i = 0; i < c.conv_depths[s]; ++i) {
-            snprintf(b, sizeof b, "stages.%d.%d.", s, i);
-            const std::string pre(b);
-            ConvBlk& k = p->conv[s][i];
-            const int C = D[s];
-            k.gamma = find_param(p, pre + "gamma");
-            k.dww = find_param(p, pre + "dwconv.weight");
-            k.dwb = find_param(p, pre + "dwconv.bias");
-            k.lnw = find_param(p, pre + "norm.weight");
-            k.lnb = find_param(p, pre + "norm.bias");
-            k.b1 = find_param(p, pre + "pwconv1.bias");
-            k.b2 = find_param(p, pre + "pwconv2.bias");
-            k.w1 = make_w(p, pre + "pwconv1.weight", 4 * C, C, true);
-            k.w2 = make_w(p, pre + "pwconv2.weight", C, 4 * C, true);
-            p->drop_conv[s].push_back(call++);
-        }
-    }
-    for (int s = 0; s < 2; ++s) {
-        p->rope[s].resize(c.rope_depths[s]);
-        for (int i = 0; i < c.rope_depths[s]; ++i) {
-            snprintf(b, sizeof b, "stages.%d.%d.", s + 2, i);
-            const std::string pre(b);
-            RopeBlk& k = p->rope[s][i];
-            const int C = D[2 + s], hid = c.mlp_hidden[s];
-            k.n1w = find_param(p, pre + "norm1.weight");
-            k.n1b = find_param(p, pre + "norm1.bias");
-            k.n2w = find_param(p, pre + "norm2.weight");
-            k.n2b = find_param(p, pre + "norm2.bias");
-            k.freqs = find_param(p, pre + "attn.freqs");
-            k.qkvb = find_param(p, pre + "attn.qkv.bias");
-            k.projb = find_param(p, pre + "attn.proj.bias");
-            k.fc1b = find_param(p, pre + "mlp.fc1.bias");
-            k.fc2b = find_param(p, pre + "mlp.fc2.bias");
-            k.qkv = make_w(p, pre + "attn.qkv.weight", 3 * C, C, true);
-            k.proj = make_w(p, pre + "attn.proj.weight", C, C, true);
-            k.fc1 = make_w(p, pre + "mlp.fc1.weight", hid, C, true);
-            k.fc2 = make_w(p, pre + "mlp.fc2.weight", C, hid, true);
-            p->drop_attn[s].push_back(call++);
-            p->drop_mlp[s].push_back(call++);
-        }
-    }
-    p->n_drop = call;
-    for (int s = 0; s < 2; ++s) {
-        snprintf(b, sizeof b, "norm_%d.", s + 1);
-        p->norm_w[s] = find_param(p, std::string(b) + "weight");
-        p->norm_b[s] = find_param(p, std::string(b) + "bias");
-        p->meta[s].resize(c.n_meta);
-        int off = 0;
-        for (int m = 0; m < c.n_meta; ++m) {
-            snprintf(b, sizeof b, "meta.%d.head_%d.", m, s + 1);
-            const std::string pre(b);
-            MetaHead& k = p->meta[s][m];
-            const int C = D[2 + s];
-            k.dim = c.meta_dims[m];
-            k.off = off;
-            off += k.dim;
-            k.w0 = make_w(p, pre + "0.weight", C, k.dim, false, LNX_PREP_CAST, 0, true);
-            k.b0 = find_param(p, pre + "0.bias");
-            k.lnw0 = find_param(p, pre + "2.weight");
-            k.lnb0 = find_param(p, pre + "2.bias");
-            k.nf1w = find_param(p, pre + "3.norm_fn1.weight");
-            k.nf1b = find_param(p, pre + "3.norm_fn1.bias");
-            k.nf2w = find_param(p, pre + "3.norm_fn2.weight");
-            k.nf2b = find_param(p, pre + "3.norm_fn2.bias");
-            k.w1 = make_w(p, pre + "3.w1.weight", C, C, true, LNX_PREP_CAST, 0, true);
-            k.b1 = find_param(p, pre + "3.w1.bias");
-            k.w2 = make_w(p, pre + "3.w2.weight", C, C, true, LNX_PREP_CAST, 0, true);
-            k.b2 = find_param(p, pre + "3.w2.bias");
-        }
-    }
-    if (!c.only_last_cls) {
-        p->cl_w1 = make_w(p, "cl_1_fc.0.fc1.weight", D[2], D[2], true);
-        p->cl_w2 = make_w(p, "cl_1_fc.0.fc2.weight", D[3], D[2], true);
-        p->cl_b1 = find_param(p, "cl_1_fc.0.fc1.bias");
-        p->cl_b2 = find_param(p, "cl_1_fc.0.fc2.bias");
-        p->cl_lnw = find_param(p, "cl_1_fc.1.weight");
-        p->cl_lnb = find_param(p, "cl_1_fc.1.bias");
-        p->agg_w = find_param(p, "aggregate.weight");
-        p->agg_b = find_param(p, "aggregate.bias");
-    }
-    p->fin_w = find_param(p, "final_norm.weight");
-    p->fin_b = find_param(p, "final_norm.bias");
-    p->head_w.resize(c.n_tasks);
-    p->head_b.resize(c.n_tasks);
-    p->logit_ld.resize(c.n_tasks);
-    p->logit_off.resize(c.n_tasks);
-    for (int t = 0; t < c.n_tasks; ++t) {
-        snprintf(b, sizeof b, "head.%d.", t);
-        p->head_w[t] = make_w(p, std::string(b) + "weight", c.task_classes[t], D[3], true);
-        p->head_b[t] = find_param(p, std::string(b) + "bias");
-        p->logit_ld[t] = (int)align_up(c.task_classes[t], 8);
-        p->head_w[t].ld_t = p->logit_ld[t];  // the data-gradient GEMM contracts over the padded logits row
-        p->logit_off[t] = p->logits_numel;
-        p->logits_numel += (int64_t)B * p->logit_ld[t];
-    }
 
     // collect every arena weight
     auto reg = [&](OpW& w) { p->all_w.push_back(&w); };
@@ -530,9 +450,11 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         w->off = cv.take((int64_t)w->N * w->ld * wes);
         if (w->ld_t) w->off_t = cv.take((int64_t)w->K * w->ld_t * wes);
     }
+    p->arena_end = cv.cur;
     for (int s = 0; s < 2; ++s)
         for (auto& k : p->conv[s]) k.w49 = cv.take((int64_t)49 * D[s] * 4);
-    if (c.fp8)
+    if (c.fp8) {
+        const bool fp8_dgrad = !c.inference && !env_off("LNX_FP8_DGRAD");
         for (int s = 0; s < 2; ++s)
             for (auto& k : p->rope[s]) {
                 for (OpW* w : {&k.qkv, &k.fc1, &k.fc2}) {
@@ -542,14 +464,13 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
                 // The proj / fc2 / fc1 data-gradient products in MXFP8 too (round 5: on by default, LNX_FP8_DGRAD=0 keeps them bf16).  Global
                 // gradient error against the fp32 oracle 8.7 % instead of 6.9 % (sm, B = 24) -- inside the mode's stated 12-13 % -- for
                 // 84.6 instead of 85.7 ms per xl step (round 4); dY arrives as the MXFP8 copy the LayerNorm backward writes beside its bf16 output.
-                if (!c.inference && !(getenv("LNX_FP8_DGRAD") && atoi(getenv("LNX_FP8_DGRAD")) == 0))
+                if (fp8_dgrad)
                     for (OpW* w : {&k.proj, &k.fc1, &k.fc2}) {
                         w->off8t = cv.take((int64_t)w->K * w->N);
                         w->off8ts = cv.take((int64_t)(w->N / 128) * w->K * 4);
                     }
             }
-    const int64_t arena_end = cv.cur;
-    (void)arena_end;
+    }
 
     const int64_t M0 = (int64_t)B * p->HW[0];
     p->o_patches = cv.take(M0 * 64 * esz);
@@ -564,6 +485,13 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     // re-runs a block's forward into the shared set before differentiating it.
     const bool inf = c.inference != 0;
     const bool ck = !inf && c.recompute != 0;
+    // LNX_NO_FUSED_MLP: every conv block on two GEMMs; LNX_FUSED_MLP_MAXC=n: only blocks with C <= n fused; LNX_NO_FUSED_LN: the block
+    // LayerNorm as its own passes again (A/B switches)
+    const bool fuse_mlp = !env_set("LNX_NO_FUSED_MLP"), fuse_ln = !env_set("LNX_NO_FUSED_LN");
+    int fuse_maxc = 2048;  // (no dims[] is larger)
+    if (const char* e = getenv("LNX_FUSED_MLP_MAXC")) fuse_maxc = atoi(e);
+    p->lnws_floats = (int64_t)2048 * 2 * (D[3] > D[0] ? D[3] : D[0]);
+    p->lnws_side_floats = (int64_t)256 * 2 * D[3];
     for (int s = 0; s < 2; ++s) {
         const int64_t M = (int64_t)B * p->HW[s], C = D[s];
         if (M * C > maxMC) maxMC = M * C;
@@ -583,23 +511,16 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
             k.ln = share ? f.ln : cv.take(M * C * esz);
             k.mean = share ? f.mean : cv.take(M * 4);
             k.rstd = share ? f.rstd : cv.take(M * 4);
-            // LNX_NO_FUSED_MLP: every conv block on two GEMMs; LNX_FUSED_MLP_MAXC=n: only blocks with C <= n fused (A/B switches)
-            k.fused = lnx_convmlp_supported(c.dtype, (int)C) != 0 && getenv("LNX_NO_FUSED_MLP") == nullptr &&
-                      (getenv("LNX_FUSED_MLP_MAXC") == nullptr || C <= atoi(getenv("LNX_FUSED_MLP_MAXC")));
+            k.fused = lnx_convmlp_supported(c.dtype, (int)C) != 0 && fuse_mlp && C <= fuse_maxc;
             any_fused = any_fused || k.fused;
-            // LNX_NO_FUSED_LN: the block LayerNorm as its own passes again (A/B switch).  The backward kernel leaves 2C floats of
-            // column sums per workgroup in the LayerNorm scratch; how many workgroups is the launcher's business
-            // (lnx_convmlp_bwd_ws_floats), a batch whose sums do not fit keeps the separate LayerNorm passes.
-            {
-                const int64_t lnws = (int64_t)2048 * 2 * (D[3] > D[0] ? D[3] : D[0]);  // = lnws_floats below
-                k.fused_ln = k.fused && getenv("LNX_NO_FUSED_LN") == nullptr && lnx_convmlp_bwd_ws_floats((int)C, (int)M) <= lnws;
-            }
+            // The backward kernel leaves 2C floats of column sums per workgroup in the LayerNorm scratch; how many workgroups is the
+            // launcher's business (lnx_convmlp_bwd_ws_floats), a batch whose sums do not fit keeps the separate LayerNorm passes.
+            k.fused_ln = k.fused && fuse_ln && lnx_convmlp_bwd_ws_floats((int)C, (int)M) <= p->lnws_floats;
             if (!k.fused) {
                 k.hpre = share ? f.hpre : cv.take(M * 4 * C * esz);
                 k.act = share ? f.act : cv.take(M * 4 * C * esz);
+                k.z = share ? f.z : cv.take(M * C * esz);
             }
-            k.keep_z = !k.fused || getenv("LNX_CONV_Z") != nullptr;  // LNX_CONV_Z: A/B switch, z saved and read as in round 3
-            k.z = !k.keep_z ? 0 : (share ? f.z : cv.take(M * C * esz));
         }
         p->o_stage_out[s] = inf ? pp[nb & 1] : cv.take(M * C * 4);
         p->down[s].ln = cv.take(M * C * esz);
@@ -608,7 +529,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         p->o_g[s] = inf ? 0 : cv.take(M * C * 4);
     }
     for (int s = 0; s < 2; ++s) {
-        const int N = s == 0 ? p->N2 : p->N3;
+        const int N = p->Ntok[s];
         const int64_t M = (int64_t)B * N, C = D[2 + s], hid = c.mlp_hidden[s];
         const int heads = c.rope_heads[s];
         if (M * C > maxMC) maxMC = M * C;
@@ -669,7 +590,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         }
     }
     {
-        const int64_t M2 = (int64_t)B * p->N2;
+        const int64_t M2 = (int64_t)B * p->Ntok[0];
         p->o_t1 = cv.take(M2 * D[2] * esz);
         p->o_t1_mean = cv.take(M2 * 4);
         p->o_t1_rstd = cv.take(M2 * 4);
@@ -700,7 +621,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     if (c.fp8) {
         int64_t mc = 0, mh = 0;
         for (int s = 0; s < 2; ++s) {
-            const int64_t M = (int64_t)B * (s == 0 ? p->N2 : p->N3);
+            const int64_t M = (int64_t)B * p->Ntok[s];
             if (M * D[2 + s] > mc) mc = M * D[2 + s];
             if (M * c.mlp_hidden[s] > mh) mh = M * c.mlp_hidden[s];
         }
@@ -709,13 +630,11 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         p->o_h8 = cv.take(mh);
         p->o_h8s = cv.take(mh / 32);
     }
-    p->lnws_floats = (int64_t)2048 * 2 * (D[3] > D[0] ? D[3] : D[0]);
-    p->lnws_side_floats = (int64_t)256 * 2 * D[3];
     if (!inf) {
         p->o_lnws = cv.take(p->lnws_floats * 4);
         {   // a postponed LayerNorm backward keeps its column partials until the segment's flush: LN_DEFER_SLOTS regions, each as large as the
             // largest launch-stream LayerNorm of this plan wants (workgroups x 2C floats; the kernel caps its grid by the region it is given)
-            const int64_t rows[5] = {(int64_t)B * p->HW[0], (int64_t)B * p->HW[1], (int64_t)B * p->N2, (int64_t)B * p->N3, (int64_t)B};
+            const int64_t rows[5] = {(int64_t)B * p->HW[0], (int64_t)B * p->HW[1], (int64_t)B * p->Ntok[0], (int64_t)B * p->Ntok[1], (int64_t)B};
             const int64_t wide[5] = {D[0], D[1], D[2], D[3], D[3]};
             int64_t need = 0;
             for (int i = 0; i < 5; ++i) {
@@ -743,7 +662,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     if (!inf) {
         int64_t gmax = 0, dmax = 0;
         for (int s = 0; s < 2; ++s) {
-            const int N = s == 0 ? p->N2 : p->N3;
+            const int N = p->Ntok[s];
             const int64_t gsz = lnx_attn_bwd_ws_floats_hd(B, N, c.rope_heads[s], D[2 + s] / c.rope_heads[s]) * 4;  // per-workgroup partials of the freqs gradient
             const int64_t dsz = (int64_t)B * c.rope_heads[s] * N * 4;
             if (gsz > gmax) gmax = gsz;
@@ -754,13 +673,12 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         p->o_delta = cv.take(dmax);
     }
     for (int s = 0; s < 2; ++s) {
-        const int64_t M = (int64_t)B * (s == 0 ? p->N2 : p->N3), C = D[2 + s], hid = c.mlp_hidden[s];
+        const int64_t N = p->Ntok[s], M = B * N, C = D[2 + s], hid = c.mlp_hidden[s];
         for (auto& k : p->rope[s]) {
             k.dm_proj = p->dmask_bytes;
             k.dm_hid = k.dm_proj + M * C;
             k.dm_fc2 = k.dm_hid + M * hid;
             p->dmask_bytes = k.dm_fc2 + M * C;  // M * C and M * hid are multiples of 8: every mask stays 8-byte aligned
-            const int64_t N = s == 0 ? p->N2 : p->N3;
             k.dm_attn = p->amask_bytes;
             p->amask_bytes += (int64_t)B * c.rope_heads[s] * N * ((N + 63) / 64 * 64);
         }
@@ -880,15 +798,7 @@ extern "C" int lnx_plan_bind(lnx_plan* p, const float* const* params, float* con
     p->ws = reinterpret_cast<unsigned char*>(workspace);
     if ((((uintptr_t)p->ws) & 255) != 0) FAIL("lnx_plan_bind: workspace must be 256-byte aligned");
     // operand arena starts zeroed: K / N padding stays zero across refreshes
-    int64_t arena_end = 0;
-    for (OpW* w : p->all_w) {
-        const int wes = w->f32 ? 4 : 2;
-        const int64_t e1 = w->off + (int64_t)w->N * w->ld * wes;
-        const int64_t e2 = w->ld_t ? w->off_t + (int64_t)w->K * w->ld_t * wes : 0;
-        if (e1 > arena_end) arena_end = e1;
-        if (e2 > arena_end) arena_end = e2;
-    }
-    HIPRUN(hipMemset(p->ws, 0, (size_t)arena_end));
+    HIPRUN(hipMemset(p->ws, 0, (size_t)p->arena_end));
     // descriptor tables: [T-typed weights + depthwise taps][fp32-typed weights]
     std::vector<lnx_prep_desc> d;
     int blk = 0;
@@ -933,9 +843,9 @@ extern "C" int lnx_plan_bind(lnx_plan* p, const float* const* params, float* con
             if (w->f32) push_w(w);
     p->n_descs_f = (int64_t)d.size() - p->n_descs_t;
     p->prep_blocks_f = blk;
-    if (getenv("LNX_NO_SIDE_STREAM") != nullptr) p->meta_mode = 0;
+    if (env_set("LNX_NO_SIDE_STREAM")) p->meta_mode = 0;
     if (const char* e = getenv("LNX_META_STREAM")) p->meta_mode = atoi(e) < 0 || atoi(e) > 2 ? 1 : atoi(e);
-    if (p->side == nullptr && p->c.n_meta > 0 && getenv("LNX_NO_SIDE_STREAM") == nullptr) {
+    if (p->side == nullptr && p->c.n_meta > 0 && !env_set("LNX_NO_SIDE_STREAM")) {
         p->side = shared_stream(0);
         if (!p->side) FAIL("lnx_plan: no side stream");
         HIPRUN(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
@@ -945,7 +855,7 @@ extern "C" int lnx_plan_bind(lnx_plan* p, const float* const* params, float* con
             HIPRUN(hipEventCreateWithFlags(&p->ev_bjoin[i], hipEventDisableTiming));
         }
     }
-    if (p->wgs == nullptr && !(getenv("LNX_WGRAD_STREAM") && atoi(getenv("LNX_WGRAD_STREAM")) == 0)) {
+    if (p->wgs == nullptr && !env_off("LNX_WGRAD_STREAM")) {
         p->wgs = shared_stream(1);
         if (!p->wgs) FAIL("lnx_plan: no weight-gradient stream");
         for (int i = 0; i < 4; ++i) {
@@ -1032,7 +942,7 @@ int gemm_nt_t(const Ctx& c, const lnx_gemm_args* a) {
 // The classification heads' products (M = batch rows): every head in one launch (lnx_gemm_nt_group) where the list qualifies -- bf16 plans --
 // otherwise one launch per head.  accumulate: C = res + sum_t A_t . W_t^T (the data gradient wrt the features); hg[0] carries C / res.
 int heads_nt(const Ctx& c, lnx_gemm_args* hg, int n, bool accumulate) {
-    static const bool off = getenv("LNX_HEADS_GROUP") != nullptr && atoi(getenv("LNX_HEADS_GROUP")) == 0;  // A/B switch
+    static const bool off = env_off("LNX_HEADS_GROUP");  // A/B switch
     // a model with more heads than one launch carries goes in several groups; LNX_HEADS_GROUP_MAX (read per call: the tests flip it) makes
     // the groups smaller so that a 4-head fixture walks that path too
     int gmax = LNX_GEMM_GROUP_MAX;
@@ -1091,6 +1001,20 @@ int ln_fwd(const Ctx& c, int M, int C, float eps, const void* x, int xdt, int64_
     return lnx_layernorm_fwd(&a, c.st);
 }
 
+// A LayerNorm backward whose column-sum reduce waits for the segment's flush (ln_flush below) keeps its partial sums in a region of its
+// own until then: takes the next of the LN_DEFER_SLOTS regions, flushing first when all are in use
+int ln_defer_slot(const Ctx& c, float*& ws, int64_t& ws_floats) {
+    lnx_plan* p = c.p;
+    if (p->ln_pending == LN_DEFER_SLOTS) {
+        RUN(lnx_layernorm_bwd_flush(c.st));
+        p->ln_pending = 0;
+    }
+    ws = c.at<float>(p->o_lnws_defer) + (int64_t)p->ln_pending * p->lnws_defer_floats;
+    ws_floats = p->lnws_defer_floats;
+    ++p->ln_pending;
+    return 0;
+}
+
 // dx2 (optional): DropPath-scaled copy of dx in storage type = the dY operand of the next branch's GEMMs
 struct Dx2 {
     void* p = nullptr;
@@ -1119,19 +1043,12 @@ int ln_bwd(const Ctx& c, int M, int C, const void* dy, int dydt, int64_t lddy, l
     const bool on_side = c.p->side != nullptr && c.st == (void*)c.p->side;
     a.ws = c.at<float>(on_side ? c.p->o_lnws_side : c.p->o_lnws);
     a.ws_floats = on_side ? c.p->lnws_side_floats : c.p->lnws_floats;
-    // Launch-stream calls postpone their column-sum reduce to the segment's flush (ln_flush below): each takes a partial-sum region of
-    // its own until then.  22 reduce launches of ~8 us per step become 4.
+    // Launch-stream calls postpone their column-sum reduce to the segment's flush.  22 reduce launches of ~8 us per step become 4.
     lnx_plan* p = c.p;
     const bool on_wgs = p->wgs != nullptr && c.st == (void*)p->wgs;  // (the launch stream may be the null stream: compare only with streams that exist)
     if (p->ln_defer && !on_side && !on_wgs && p->o_lnws_defer != 0 && (a.dw || a.db)) {
-        if (p->ln_pending == LN_DEFER_SLOTS) {
-            RUN(lnx_layernorm_bwd_flush(c.st));
-            p->ln_pending = 0;
-        }
-        a.ws = c.at<float>(p->o_lnws_defer) + (int64_t)p->ln_pending * p->lnws_defer_floats;
-        a.ws_floats = p->lnws_defer_floats;
+        RUN(ln_defer_slot(c, a.ws, a.ws_floats));
         a.defer = 1;
-        ++p->ln_pending;
     }
     return lnx_layernorm_bwd(&a, c.st);
 }
@@ -1209,12 +1126,11 @@ int linear_dgrad(const Ctx& c, lnx_gemm_args g, const OpW& w, bool quantise, int
 }
 
 // ------------------------------ forward pieces ------------------------------
-int conv_block_fwd(const Ctx& c, int s, int i, const float* xin, float* xout) {
+int conv_block_fwd(const Ctx& c, int s, int i, float* xout) {
     lnx_plan* p = c.p;
     ConvBlk& k = p->conv[s][i];
     const int B = p->c.batch, H = p->H[s], W = p->W[s], C = p->c.dims[s];
     const int M = B * H * W;
-    (void)xin;
     p->resident[s] = i;
     Timed span(c, 9, 2.0 * M * C * (8.0 * C + 49.0));
     lnx_dwconv_args d;
@@ -1244,16 +1160,14 @@ int conv_block_fwd(const Ctx& c, int s, int i, const float* xin, float* xout) {
         f.w1 = c.wptr(k.w1); f.b1 = p->P[k.b1]; f.w2 = c.wptr(k.w2); f.b2 = p->P[k.b2];
         f.gamma = p->P[k.gamma]; f.rowscale = p->drop_ptr(p->drop_conv[s][i]); f.rows_per_sample = H * W;
         f.x = c.at<float>(k.xin); f.out = xout;
-        if (!p->c.inference && k.keep_z) f.z = c.at<void>(k.z);  // (only the backward reads it)
         Timed t(c, 6, 2.0 * M * C * 4 * C * 2);
         RUN(lnx_convmlp_fwd(&f, c.st));
         return 0;
     }
     lnx_gemm_args g = gemm_base(c, M, 4 * C, C, c.at<void>(k.ln), C, c.wptr(k.w1), k.w1.ld, c.at<void>(k.act), 4 * C, false);
     g.bias = p->P[k.b1]; g.act = LNX_ACT_GELU;
-    if (!p->c.inference) {  // the backward's second tensor: GELU'(h), evaluated here once (as in the RoPE blocks' fc1; LNX_CONV_HPRE: h, round 3)
-        static const bool keep_h = getenv("LNX_CONV_HPRE") != nullptr;
-        g.act = keep_h ? LNX_ACT_GELU : LNX_ACT_GELU_D;
+    if (!p->c.inference) {  // the backward's second tensor: GELU'(h), evaluated here once (as in the RoPE blocks' fc1)
+        g.act = LNX_ACT_GELU_D;
         g.c2 = c.at<void>(k.hpre); g.ldc2 = 4 * C;
     }
     RUN(gemm_nt_t(c, &g));
@@ -1278,11 +1192,12 @@ int downsample_fwd(const Ctx& c, int i, const void* x, int xdt, int64_t ldx, lnx
     return 0;
 }
 
-int meta_head_fwd(const Ctx& cc, int s, int m, const float* meta, int meta_width, float* tok, int N) {
+int meta_head_fwd(const Ctx& cc, int s, int m, const float* meta, int meta_width) {
     const Ctx c{cc.p, cc.st, LNX_F32};  // fp32 storage for the M = batch meta-head chain
     lnx_plan* p = c.p;
     MetaHead& k = p->meta[s][m];
-    const int B = p->c.batch, C = p->c.dims[2 + s];
+    const int B = p->c.batch, C = p->c.dims[2 + s], N = p->Ntok[s];
+    float* tok = c.at<float>(p->o_tok[s]);
     RUN(lnx_pack_meta(meta, meta_width, k.off, k.dim, c.at<void>(k.t0), c.dt, B, c.st));
     lnx_gemm_args g = gemm_base(c, B, C, 16, c.at<void>(k.t0), 16, c.wptr(k.w0), k.w0.ld, c.at<void>(k.h0), C, false);
     g.bias = p->P[k.b0]; g.act = LNX_ACT_RELU;
@@ -1308,7 +1223,7 @@ int meta_chain_fwd(const Ctx& c, int s_lo, int s_hi, const float* meta, int meta
     for (int s = s_lo; s < s_hi; ++s)
         for (int m = 0; m < p->c.n_meta; ++m) {
             MetaHead& k = p->meta[s][m];
-            const int C = p->c.dims[2 + s], N = s == 0 ? p->N2 : p->N3;
+            const int C = p->c.dims[2 + s], N = p->Ntok[s];
             lnx_meta_head_args& h = a[n++];
             memset(&h, 0, sizeof h);
             h.B = p->c.batch; h.C = C; h.dim = k.dim; h.off = k.off; h.meta = meta; h.meta_width = meta_width; h.eps = 1e-5f;
@@ -1326,7 +1241,7 @@ int meta_chain_fwd(const Ctx& c, int s_lo, int s_hi, const float* meta, int meta
 int meta_chain_bwd(const Ctx& c, int s, const float* g) {
     lnx_plan* p = c.p;
     lnx_meta_head_bwd_args a[LNX_MAX_META];
-    const int C = p->c.dims[2 + s], N = s == 0 ? p->N2 : p->N3;
+    const int C = p->c.dims[2 + s], N = p->Ntok[s];
     for (int m = 0; m < p->c.n_meta; ++m) {
         MetaHead& k = p->meta[s][m];
         lnx_meta_head_bwd_args& h = a[m];
@@ -1345,6 +1260,30 @@ int meta_chain_bwd(const Ctx& c, int s, const float* g) {
     return p->c.n_meta ? lnx_meta_heads_bwd(a, p->c.n_meta, c.st) : 0;
 }
 
+// The metadata heads of stages [s_lo, s_hi), forward: the one-launch chain where it carries the stage's width (chain_ok), else head by head
+int meta_fwd(const Ctx& c, int s_lo, int s_hi, const float* meta, int meta_width) {
+    lnx_plan* p = c.p;
+    bool all_chain = true;
+    for (int s = s_lo; s < s_hi; ++s) all_chain = all_chain && p->chain_ok[s];
+    if (all_chain) return meta_chain_fwd(c, s_lo, s_hi, meta, meta_width);  // every head of these stages: one call (a launch per width)
+    for (int s = s_lo; s < s_hi; ++s) {
+        if (p->chain_ok[s]) {
+            RUN(meta_chain_fwd(c, s, s + 1, meta, meta_width));
+            continue;
+        }
+        for (int m = 0; m < p->c.n_meta; ++m) RUN(meta_head_fwd(c, s, m, meta, meta_width));
+    }
+    return 0;
+}
+
+// "next block's input, else the stage output": where block i of a stage writes (i = -1: where the stage reads)
+float* conv_out(const lnx_plan* p, int s, int i) {
+    return p->at<float>(i + 1 < (int)p->conv[s].size() ? p->conv[s][i + 1].xin : p->o_stage_out[s]);
+}
+float* rope_out(const lnx_plan* p, int s, int i) {
+    return p->at<float>(i + 1 < (int)p->rope[s].size() ? p->rope[s][i + 1].xin : p->o_stage_out[2 + s]);
+}
+
 // forward FLOPs of one RoPE2DMHSABlock: qkv + proj + fc1 + fc2 products and the two attention products (SURVEY 8d's count;
 // heads * head_dim = C)
 double rope_block_flops(int B, int N, int C, int hid) {
@@ -1356,7 +1295,7 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     lnx_plan* p = c.p;
     RopeBlk& k = p->rope[s][i];
     const int B = p->c.batch, C = p->c.dims[2 + s], heads = p->c.rope_heads[s], hid = p->c.mlp_hidden[s];
-    const int N = s == 0 ? p->N2 : p->N3, M = B * N, E = p->E;
+    const int N = p->Ntok[s], M = B * N, E = p->E;
     const float* xin = c.at<float>(k.xin);
     p->resident[2 + s] = i;
     Timed span(c, 8, rope_block_flops(B, N, C, hid));
@@ -1456,18 +1395,7 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
     if (mst) {
         HIPRUN(hipEventRecord(p->ev_fork, (hipStream_t)stream));
         HIPRUN(hipStreamWaitEvent(mst, p->ev_fork, 0));
-        Ctx cs{p, (void*)mst, cf.dtype};
-        if (p->chain_ok[0] && p->chain_ok[1]) {
-            RUN(meta_chain_fwd(cs, 0, 2, meta, mw_all));  // every head of both stages: one call (a launch per width)
-        } else {
-            for (int s2 = 0; s2 < 2; ++s2) {
-                if (p->chain_ok[s2]) {
-                    RUN(meta_chain_fwd(cs, s2, s2 + 1, meta, mw_all));
-                    continue;
-                }
-                for (int m = 0; m < cf.n_meta; ++m) RUN(meta_head_fwd(cs, s2, m, meta, mw_all, c.at<float>(p->o_tok[s2]), s2 == 0 ? p->N2 : p->N3));
-            }
-        }
+        RUN(meta_fwd(Ctx{p, (void*)mst, cf.dtype}, 0, 2, meta, mw_all));
     }
     {   // the cos tables of every RoPE block in one launch (each block owns its freqs); beside the stem and the ConvNeXt stages when there
         // is a side stream, which the RoPE stages join below.  A checkpointed block's re-forward reads the same tables.
@@ -1491,7 +1419,7 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
 
     // 1. stem: 4x4/4 patchify conv as im2col + GEMM, then channels-first LN (mFormerV1.py:145-148)
     const int M0 = B * p->HW[0];
-    float* first = cf.conv_depths[0] > 0 ? c.at<float>(p->conv[0][0].xin) : c.at<float>(p->o_stage_out[0]);
+    float* first = conv_out(p, 0, -1);
     if (lnx_stem_fwd_ok(cf.dtype, cf.in_chans, cf.img_h, cf.img_w, D[0])) {
         lnx_stem_args sa;
         memset(&sa, 0, sizeof sa);
@@ -1516,14 +1444,9 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
 
     // 2. ConvNeXt stages + downsamplers (mFormerV1.py:427-443)
     for (int s = 0; s < 2; ++s) {
-        const int nb = cf.conv_depths[s];
-        for (int i = 0; i < nb; ++i) {
-            float* xout = i + 1 < nb ? c.at<float>(p->conv[s][i + 1].xin) : c.at<float>(p->o_stage_out[s]);
-            RUN(conv_block_fwd(c, s, i, nullptr, xout));
-        }
+        for (int i = 0; i < cf.conv_depths[s]; ++i) RUN(conv_block_fwd(c, s, i, conv_out(p, s, i)));
         if (s == 0) {
-            float* nxt = cf.conv_depths[1] > 0 ? c.at<float>(p->conv[1][0].xin) : c.at<float>(p->o_stage_out[1]);
-            RUN(downsample_fwd(c, 0, c.at<float>(p->o_stage_out[0]), LNX_F32, D[0], IDM, nxt, D[1], IDM));
+            RUN(downsample_fwd(c, 0, c.at<float>(p->o_stage_out[0]), LNX_F32, D[0], IDM, conv_out(p, 1, -1), D[1], IDM));
         } else {
             const lnx_rowmap tm = {p->HW[2], p->E, p->E};
             RUN(downsample_fwd(c, 1, c.at<float>(p->o_stage_out[1]), LNX_F32, D[1], IDM, c.at<float>(p->o_tok[0]), D[2], tm));
@@ -1532,30 +1455,24 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
 
     // 3. RoPE stages (mFormerV1.py:445-510)
     for (int s = 0; s < 2; ++s) {
-        const int N = s == 0 ? p->N2 : p->N3, C = D[2 + s];
+        const int N = p->Ntok[s], C = D[2 + s];
         float* tok = c.at<float>(p->o_tok[s]);
         const lnx_rowmap clsmap = {1, N - 1, 0};
         RUN(lnx_fill_rows(p->P[p->cls[s]], tok, C, clsmap, B, C, stream));
         if (mst) {
             if (s == 0) HIPRUN(hipStreamWaitEvent((hipStream_t)stream, p->ev_meta, 0));  // join: all meta tokens written
-        } else if (p->chain_ok[s]) {
-            RUN(meta_chain_fwd(c, s, s + 1, meta, mw_all));
         } else {
-            for (int m = 0; m < cf.n_meta; ++m) RUN(meta_head_fwd(c, s, m, meta, mw_all, tok, N));
+            RUN(meta_fwd(c, s, s + 1, meta, mw_all));
         }
-        const int nb = cf.rope_depths[s];
-        for (int i = 0; i < nb; ++i) {
-            float* xout = i + 1 < nb ? c.at<float>(p->rope[s][i + 1].xin) : c.at<float>(p->o_stage_out[2 + s]);
-            RUN(rope_block_fwd(c, s, i, xout));
-        }
+        for (int i = 0; i < cf.rope_depths[s]; ++i) RUN(rope_block_fwd(c, s, i, rope_out(p, s, i)));
         if (s == 0) {
-            const int M2 = B * p->N2;
+            const int M2 = B * p->Ntok[0];
             // norm_1 over all tokens (mFormerV1.py:470); T output feeds cl_1_fc and downsample 3
             RUN(ln_fwd(c, M2, C, 1e-5f, c.at<float>(p->o_stage_out[2]), LNX_F32, C, IDM, p->norm_w[0], p->norm_b[0], c.at<void>(p->o_t1), cf.dtype, C, IDM,
                        nullptr, 0, c.at<float>(p->o_t1_mean), c.at<float>(p->o_t1_rstd)));
             if (!cf.only_last_cls) {
                 // cl_1_fc = Mlp(D2, D2, D3) + LayerNorm on the CLS row (mFormerV1.py:316-321,474-476)
-                lnx_gemm_args g = gemm_base(c, B, D[2], D[2], c.at<void>(p->o_t1), (int64_t)p->N2 * D[2], c.wptr(p->cl_w1), p->cl_w1.ld, c.at<void>(p->o_cl_act),
+                lnx_gemm_args g = gemm_base(c, B, D[2], D[2], c.at<void>(p->o_t1), (int64_t)p->Ntok[0] * D[2], c.wptr(p->cl_w1), p->cl_w1.ld, c.at<void>(p->o_cl_act),
                                             D[2], false);
                 g.bias = p->P[p->cl_b1]; g.act = LNX_ACT_GELU; g.c2 = c.at<void>(p->o_cl_hpre); g.ldc2 = D[2];
                 RUN(gemm_nt_t(c, &g));
@@ -1575,7 +1492,7 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
     // 4. tail: norm_2 on the CLS row, aggregate, final_norm, heads (mFormerV1.py:509-541)
     {
         const int C = D[3];
-        const lnx_rowmap clsrow = {1, p->N3 - 1, 0};
+        const lnx_rowmap clsrow = {1, p->Ntok[1] - 1, 0};
         RUN(ln_fwd(c, B, C, 1e-5f, c.at<float>(p->o_stage_out[3]), LNX_F32, C, clsrow, p->norm_w[1], p->norm_b[1], c.at<float>(p->o_c2n), LNX_F32, C, IDM, nullptr,
                    0, c.at<float>(p->o_n2_mean), c.at<float>(p->o_n2_rstd)));
         const float* fin_in = c.at<float>(p->o_c2n);
@@ -1634,7 +1551,7 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     lnx_plan* p = c.p;
     RopeBlk& k = p->rope[s][i];
     const int B = p->c.batch, C = p->c.dims[2 + s], heads = p->c.rope_heads[s], hid = p->c.mlp_hidden[s];
-    const int N = s == 0 ? p->N2 : p->N3, M = B * N, E = p->E;
+    const int N = p->Ntok[s], M = B * N, E = p->E;
     void* sA = c.at<void>(p->o_sA);
     void* sC = c.at<void>(p->o_sC);
     void* sD = c.at<void>(p->o_sD);
@@ -1653,7 +1570,7 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     a.act = fp8_rows(p, M, C) ? LNX_ACT_GELU_BWD : LNX_ACT_MUL_AUX; a.aux = c.at<void>(k.hpre); a.ldaux = hid;  // what the forward left in hpre
     // fp8 plans: dY comes in MXFP8 from the LayerNorm backward that wrote it (the block above's norm1 backward; quantised here when
     // there was none, or a dropout mask went over it since), the GELU' epilogue hands dH on in MXFP8 as well as in bf16 (the weight gradients read bf16)
-    const bool qpass = getenv("LNX_FP8_DGRAD_QPASS") != nullptr;  // A/B switch (read per call: the tests flip it): separate quantise passes over dY
+    const bool qpass = env_set("LNX_FP8_DGRAD_QPASS");  // A/B switch (read per call: the tests flip it): separate quantise passes over dY
     const bool mx_dgrad = c.dt == LNX_BF16 && fp8_rows(p, M, C) && k.fc2.off8ts != 0 && k.proj.off8ts != 0 && !p->dmask && C % 128 == 0 && !qpass;
     RUN(linear_dgrad(c, a, k.fc2, !(have_dy && p->dy8_ready), p->o_a8, p->o_a8s, p->o_h8, p->o_h8s));
     p->dy8_ready = false;
@@ -1741,24 +1658,18 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
         lnx_convmlp_bwd_args f;
         memset(&f, 0, sizeof f);
         f.dtype = c.dt; f.M = M; f.C = C;
-        f.g = g; f.ln = c.at<void>(k.ln); f.z = k.keep_z ? c.at<void>(k.z) : nullptr; f.w1 = c.wptr(k.w1); f.b1 = p->P[k.b1];
+        f.g = g; f.ln = c.at<void>(k.ln); f.w1 = c.wptr(k.w1); f.b1 = p->P[k.b1];
         f.w2t = c.wtptr(k.w2); f.w1t = c.wtptr(k.w1); f.gamma = p->P[k.gamma];
         f.rowscale = p->drop_ptr(p->drop_conv[s][i]); f.rows_per_sample = H * W;
         f.act = sB; f.dh = sA; f.dz = sC; f.dln = sD; f.dgamma = p->G[k.gamma];
-        f.dz_plain = k.keep_z ? 0 : 1;  // z-free: sC = rs g for the pwconv2 weight gradient, which then goes through lnx_layerscale_apply_wgrad
+        f.dz_plain = 1;  // sC = rs g for the pwconv2 weight gradient, which then goes through lnx_layerscale_apply_wgrad
         if (k.fused_ln) {  // sD then holds the gradient wrt the depthwise conv output
             f.y = c.at<void>(k.y); f.ln_w = p->P[k.lnw]; f.mean = c.at<float>(k.mean); f.rstd = c.at<float>(k.rstd);
             f.d_ln_w = p->G[k.lnw]; f.d_ln_b = p->G[k.lnb];
             f.ws = c.at<float>(p->o_lnws); f.ws_floats = p->lnws_floats;
             if (p->ln_defer && p->o_lnws_defer != 0 && lnx_convmlp_bwd_ws_floats(C, M) <= p->lnws_defer_floats) {  // (as ln_bwd: folded at the segment's flush)
-                if (p->ln_pending == LN_DEFER_SLOTS) {
-                    RUN(lnx_layernorm_bwd_flush(c.st));
-                    p->ln_pending = 0;
-                }
-                f.ws = c.at<float>(p->o_lnws_defer) + (int64_t)p->ln_pending * p->lnws_defer_floats;
-                f.ws_floats = p->lnws_defer_floats;
+                RUN(ln_defer_slot(c, f.ws, f.ws_floats));
                 f.ln_defer = 1;
-                ++p->ln_pending;
             }
         }
         {
@@ -1768,21 +1679,15 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
         const Ctx cw = wg_ctx(c);
         RUN(wg_fork(c, 0));  // the two pointwise weight gradients (and the LayerScale step behind them) beside the depthwise backward
         forked = true;
-        if (k.keep_z) {
-            RUN(wgrad(cw, M, C, 4 * C, sC, C, sB, 4 * C, k.w2.param, k.b2, 4 * C, 0, 0));
-            RUN(wgrad(cw, M, 4 * C, C, sA, 4 * C, c.at<void>(k.ln), C, k.w1.param, k.b1, C, 0, 1));
-            RUN(lnx_gemm_tn_flush(cw.st));
-        } else {
-            // LayerScale gradient without z (include/lnx.h): the pwconv2 weight-gradient product runs on dY = rs g into zeroed scratch S | T,
-            // then ONE launch adds gamma S / gamma T to the gradients and reads dgamma = rowdot(W2, S) + b2 T off them
-            float* S = c.at<float>(p->o_lsws);
-            float* T = S + (int64_t)C * 4 * C;
-            HIPRUN(hipMemsetAsync(S, 0, ((size_t)C * 4 * C + C) * 4, (hipStream_t)cw.st));
-            RUN(wgrad_into(cw, M, C, 4 * C, sC, C, sB, 4 * C, S, T, 4 * C, 0));
-            RUN(wgrad(cw, M, 4 * C, C, sA, 4 * C, c.at<void>(k.ln), C, k.w1.param, k.b1, C, 0, 1));
-            RUN(lnx_gemm_tn_flush(cw.st));
-            RUN(lnx_layerscale_apply_wgrad(S, T, 4 * C, p->P[k.w2.param], p->P[k.b2], 4 * C, p->P[k.gamma], p->G[k.w2.param], p->G[k.b2], 4 * C, p->G[k.gamma], C, 4 * C, cw.st));
-        }
+        // LayerScale gradient without z (include/lnx.h): the pwconv2 weight-gradient product runs on dY = rs g into zeroed scratch S | T,
+        // then ONE launch adds gamma S / gamma T to the gradients and reads dgamma = rowdot(W2, S) + b2 T off them
+        float* S = c.at<float>(p->o_lsws);
+        float* T = S + (int64_t)C * 4 * C;
+        HIPRUN(hipMemsetAsync(S, 0, ((size_t)C * 4 * C + C) * 4, (hipStream_t)cw.st));
+        RUN(wgrad_into(cw, M, C, 4 * C, sC, C, sB, 4 * C, S, T, 4 * C, 0));
+        RUN(wgrad(cw, M, 4 * C, C, sA, 4 * C, c.at<void>(k.ln), C, k.w1.param, k.b1, C, 0, 1));
+        RUN(lnx_gemm_tn_flush(cw.st));
+        RUN(lnx_layerscale_apply_wgrad(S, T, 4 * C, p->P[k.w2.param], p->P[k.b2], 4 * C, p->P[k.gamma], p->G[k.w2.param], p->G[k.b2], 4 * C, p->G[k.gamma], C, 4 * C, cw.st));
         RUN(wg_done(c, 0));
         if (!k.fused_ln) {  // the LayerNorm backward below overwrites sC
             RUN(wg_join(c, 0));
@@ -1792,8 +1697,7 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
         RUN(lnx_layerscale_bwd(g, c.at<void>(k.z), c.dt, p->P[k.gamma], p->drop_ptr(p->drop_conv[s][i]), H * W, sC, p->G[k.gamma], M, C, c.st));
         RUN(wgrad(c, M, C, 4 * C, sC, C, c.at<void>(k.act), 4 * C, k.w2.param, k.b2, 4 * C));
         lnx_gemm_args a = gemm_base(c, M, 4 * C, C, sC, C, c.wtptr(k.w2), k.w2.ld_t, sA, 4 * C, false);
-        static const bool keep_h = getenv("LNX_CONV_HPRE") != nullptr;
-        a.act = keep_h ? LNX_ACT_GELU_BWD : LNX_ACT_MUL_AUX; a.aux = c.at<void>(k.hpre); a.ldaux = 4 * C;  // what the forward left in hpre
+        a.act = LNX_ACT_MUL_AUX; a.aux = c.at<void>(k.hpre); a.ldaux = 4 * C;  // what the forward left in hpre
         RUN(gemm_nt_t(c, &a));
         RUN(wgrad(c, M, 4 * C, C, sA, 4 * C, c.at<void>(k.ln), C, k.w1.param, k.b1, C));
         a = gemm_base(c, M, C, 4 * C, sA, 4 * C, c.wtptr(k.w1), k.w1.ld_t, sD, C, false);
@@ -1852,11 +1756,11 @@ int downsample_bwd(const Ctx& c, int i, const float* gout, int64_t ldg, lnx_rowm
     return 0;
 }
 
-int meta_head_bwd(const Ctx& cc, int s, int m, const float* g, int N) {
+int meta_head_bwd(const Ctx& cc, int s, int m, const float* g) {
     const Ctx c{cc.p, cc.st, LNX_F32};
     lnx_plan* p = c.p;
     MetaHead& k = p->meta[s][m];
-    const int B = p->c.batch, C = p->c.dims[2 + s];
+    const int B = p->c.batch, C = p->c.dims[2 + s], N = p->Ntok[s];
     float* dtok = c.at<float>(p->o_mtmp[0]);   // [B, C] fp32
     void* t1 = c.at<void>(p->o_mtmp[1]);
     void* t2 = c.at<void>(p->o_mtmp[2]);
@@ -1877,9 +1781,16 @@ int meta_head_bwd(const Ctx& cc, int s, int m, const float* g, int N) {
     return 0;
 }
 
+// The metadata heads of stage s, backward: as meta_fwd
+int meta_bwd(const Ctx& c, int s, const float* g) {
+    if (c.p->chain_ok[s]) return meta_chain_bwd(c, s, g);
+    for (int m = 0; m < c.p->c.n_meta; ++m) RUN(meta_head_bwd(c, s, m, g));
+    return 0;
+}
+
 int tokens_bwd(const Ctx& c, int s, const float* g) {
     lnx_plan* p = c.p;
-    const int B = p->c.batch, C = p->c.dims[2 + s], N = s == 0 ? p->N2 : p->N3;
+    const int B = p->c.batch, C = p->c.dims[2 + s], N = p->Ntok[s];
     const lnx_rowmap clsmap = {1, N - 1, 0};
     RUN(lnx_colsum_rows(g, C, clsmap, p->G[p->cls[s]], B, C, c.st));
     hipStream_t const mst = meta_stream(p);
@@ -1888,15 +1799,10 @@ int tokens_bwd(const Ctx& c, int s, const float* g) {
         // fork: the metadata-head backward only reads g; joined at the end of the segment (join_side)
         HIPRUN(hipEventRecord(p->ev_bfork[s], (hipStream_t)c.st));
         HIPRUN(hipStreamWaitEvent(mst, p->ev_bfork[s], 0));
-        const Ctx cs{p, (void*)mst, c.dt};
-        if (p->chain_ok[s]) RUN(meta_chain_bwd(cs, s, g));
-        else
-            for (int m = 0; m < p->c.n_meta; ++m) RUN(meta_head_bwd(cs, s, m, g, N));
+        RUN(meta_bwd(Ctx{p, (void*)mst, c.dt}, s, g));
         HIPRUN(hipEventRecord(p->ev_bjoin[s], mst));
-    } else if (p->chain_ok[s]) {
-        RUN(meta_chain_bwd(c, s, g));
     } else {
-        for (int m = 0; m < p->c.n_meta; ++m) RUN(meta_head_bwd(c, s, m, g, N));
+        RUN(meta_bwd(c, s, g));
     }
     return 0;
 }
@@ -1907,17 +1813,13 @@ int tokens_bwd(const Ctx& c, int s, const float* g) {
 int conv_block_restore(const Ctx& c, int s, int i) {
     lnx_plan* p = c.p;
     if (!p->c.recompute || p->resident[s] == i) return 0;
-    const int nb = p->c.conv_depths[s];
-    float* xout = i + 1 < nb ? c.at<float>(p->conv[s][i + 1].xin) : c.at<float>(p->o_stage_out[s]);
-    return conv_block_fwd(c, s, i, nullptr, xout);
+    return conv_block_fwd(c, s, i, conv_out(p, s, i));
 }
 int rope_block_restore(const Ctx& c, int s, int i) {
     lnx_plan* p = c.p;
     if (!p->c.recompute || p->resident[2 + s] == i) return 0;
-    const int nb = p->c.rope_depths[s];
-    float* xout = i + 1 < nb ? c.at<float>(p->rope[s][i + 1].xin) : c.at<float>(p->o_stage_out[2 + s]);
     p->dy8_ready = false;  // (the re-forward's LayerNorms write their MXFP8 activation copies into the same scratch)
-    return rope_block_fwd(c, s, i, xout);
+    return rope_block_fwd(c, s, i, rope_out(p, s, i));
 }
 
 // the postponed LayerNorm column-sum reductions of this segment -> their gradients (one launch)
@@ -2021,8 +1923,8 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
         }
         // norm_2 acts on the CLS row only: every other row of the stage-4 output has zero gradient
         float* g3 = c.at<float>(p->o_g[3]);
-        HIPRUN(hipMemsetAsync(g3, 0, (size_t)B * p->N3 * C * 4, st));
-        const lnx_rowmap clsrow = {1, p->N3 - 1, 0};
+        HIPRUN(hipMemsetAsync(g3, 0, (size_t)B * p->Ntok[1] * C * 4, st));
+        const lnx_rowmap clsrow = {1, p->Ntok[1] - 1, 0};
         RUN(ln_bwd(c, B, C, dc2n, LNX_F32, C, IDM, c.at<float>(p->o_stage_out[3]), LNX_F32, C, clsrow, p->norm_w[1], p->norm_b[1], c.at<float>(p->o_n2_mean),
                    c.at<float>(p->o_n2_rstd), nullptr, g3, LNX_F32, C, false));
         for (int i = cf.rope_depths[1] - 1; i >= 0; --i) {
@@ -2033,7 +1935,7 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
         // downsample 3 backward into d(norm_1 output); meta/CLS rows of dt1 start at zero
         const int C2 = D[2];
         void* dt1 = c.at<void>(p->o_dt1);
-        HIPRUN(hipMemsetAsync(dt1, 0, (size_t)B * p->N2 * C2 * p->esz, st));
+        HIPRUN(hipMemsetAsync(dt1, 0, (size_t)B * p->Ntok[0] * C2 * p->esz, st));
         const lnx_rowmap gm = {p->HW[3], p->E, p->E};
         const lnx_rowmap pm = {p->HW[2], p->E, p->E};
         RUN(downsample_bwd(c, 2, g3, C, gm, c.at<void>(p->o_t1), cf.dtype, C2, pm, dt1, cf.dtype, C2));
@@ -2046,16 +1948,16 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
             lnx_gemm_args a = gemm_base(c, B, C2, C, du, C, c.wtptr(p->cl_w2), p->cl_w2.ld_t, dca, C2, false);
             a.act = LNX_ACT_GELU_BWD; a.aux = c.at<void>(p->o_cl_hpre); a.ldaux = C2;
             RUN(gemm_nt_t(c, &a));
-            RUN(wgrad(c, B, C2, C2, dca, C2, c.at<void>(p->o_t1), (int64_t)p->N2 * C2, p->cl_w1.param, p->cl_b1, C2));
+            RUN(wgrad(c, B, C2, C2, dca, C2, c.at<void>(p->o_t1), (int64_t)p->Ntok[0] * C2, p->cl_w1.param, p->cl_b1, C2));
             a = gemm_base(c, B, C2, C2, dca, C2, c.wtptr(p->cl_w1), p->cl_w1.ld_t, dt1, C2, false);
-            a.c_map = lnx_rowmap{1, p->N2 - 1, 0};
+            a.c_map = lnx_rowmap{1, p->Ntok[0] - 1, 0};
             RUN(gemm_nt_t(c, &a));
         }
         float* g2 = c.at<float>(p->o_g[2]);
         // norm_1 backward also leaves the last stage-3 block's MLP-branch dY in sC (consumed first thing in segment 1)
         Dx2 dn;
-        dn.p = c.at<void>(p->o_sC); dn.rowscale = p->drop_ptr(p->drop_mlp[0][cf.rope_depths[0] - 1]); dn.rps = p->N2;
-        RUN(ln_bwd(c, B * p->N2, C2, dt1, cf.dtype, C2, IDM, c.at<float>(p->o_stage_out[2]), LNX_F32, C2, IDM, p->norm_w[0], p->norm_b[0], c.at<float>(p->o_t1_mean),
+        dn.p = c.at<void>(p->o_sC); dn.rowscale = p->drop_ptr(p->drop_mlp[0][cf.rope_depths[0] - 1]); dn.rps = p->Ntok[0];
+        RUN(ln_bwd(c, B * p->Ntok[0], C2, dt1, cf.dtype, C2, IDM, c.at<float>(p->o_stage_out[2]), LNX_F32, C2, IDM, p->norm_w[0], p->norm_b[0], c.at<float>(p->o_t1_mean),
                    c.at<float>(p->o_t1_rstd), nullptr, g2, LNX_F32, C2, false, dn));
         // the stage-4 metadata-head backward (side stream, ~10 small fp32 GEMMs) is joined at the END OF SEGMENT 1: it only
         // produces parameter gradients, and joining here exposed most of its ~0.7 ms behind the three downsample kernels.
@@ -2124,34 +2026,25 @@ extern "C" int lnx_plan_backward_into(lnx_plan* p, const float* dlogits, const f
 
 extern "C" int lnx_plan_segment_params(const lnx_plan* p, int segment, int* idx_out, int max_out) {
     if (!p || segment < 0 || segment > 3) return -1;
-    // a parameter's gradient is final after the segment that owns it
     int n = 0;
-    auto seg_of = [&](const std::string& nm) -> int {
-        if (nm.rfind("stages.3.", 0) == 0 || nm.rfind("head.", 0) == 0 || nm.rfind("norm_", 0) == 0 || nm.rfind("cl_1_fc", 0) == 0 ||
-            nm.rfind("aggregate", 0) == 0 || nm.rfind("final_norm", 0) == 0 || nm == "cls_token_2" || nm.rfind("downsample_layers.2", 0) == 0)
-            return 0;
-        // metadata heads run on the side stream and are joined one segment after the one that forks them
-        if (nm.rfind("meta.", 0) == 0) return nm.find("head_2") != std::string::npos ? 1 : 2;
-        if (nm.rfind("stages.2.", 0) == 0 || nm == "cls_token_1" || nm.rfind("downsample_layers.1", 0) == 0) return 1;
-        if (nm.rfind("stages.1.", 0) == 0 || nm.rfind("downsample_layers.0", 0) == 0) return 2;
-        return 3;
-    };
-    for (size_t i = 0; i < p->names.size(); ++i)
-        if (seg_of(p->names[i]) == segment) {
+    for (size_t i = 0; i < p->seg.size(); ++i)
+        if (p->seg[i] == segment) {
             if (idx_out && n < max_out) idx_out[n] = (int)i;
             ++n;
         }
     return n;
 }
 
-extern "C" int lnx_plan_profile_begin(lnx_plan* p) {
-    if (!p) FAIL("lnx_plan_profile_begin: null plan");
+static int profile_begin(lnx_plan* p, bool spans, const char* who) {
+    if (!p) FAIL("%s: null plan", who);
     p->profile = true;
-    p->profile_spans = false;
+    p->profile_spans = spans;
     p->spans.clear();
     p->ev_used = 0;
     return 0;
 }
+extern "C" int lnx_plan_profile_begin(lnx_plan* p) { return profile_begin(p, false, "lnx_plan_profile_begin"); }
+extern "C" int lnx_plan_profile_begin_spans(lnx_plan* p) { return profile_begin(p, true, "lnx_plan_profile_begin_spans"); }
 
 extern "C" int lnx_plan_set_wgrad_stream(lnx_plan* p, int on) {
     if (!p || (on != 0 && on != 1)) {
@@ -2173,15 +2066,6 @@ extern "C" int lnx_plan_set_meta_stream(lnx_plan* p, int mode) {
     if (mode == 1 && p->side == nullptr) mode = 0;  // LNX_NO_SIDE_STREAM: the side stream was never created
     p->meta_mode = mode;
     return was;
-}
-
-extern "C" int lnx_plan_profile_begin_spans(lnx_plan* p) {
-    if (!p) FAIL("lnx_plan_profile_begin_spans: null plan");
-    p->profile = true;
-    p->profile_spans = true;
-    p->spans.clear();
-    p->ev_used = 0;
-    return 0;
 }
 
 // Ends profiling; synchronises the device and returns, per kernel class, the summed launch
