@@ -647,6 +647,44 @@ int lnx_mix_rows(const lnx_mix_args* args, void* stream);
 int lnx_mix_meta(const float* aux, const unsigned char* mask, const int64_t* perm, const float* pick, const int* bounds_dev, int nchunk, int B, int D,
                  float* out_aux, unsigned char* out_mask, void* stream);
 
+/* Scheduled metadata masking of the collate step, full and partial, in ONE launch.  Replaces the per-sample loop of
+ * linnaeus/h5data/h5dataloader.py:709-940 (with _apply_partial_mask, :366-482, and ops_schedule.py:628-650), the component
+ * statistics of :1677-1801 and the evaluation-time zeroing of validation.py:174-175,192,428-489.
+ *   training form (draws != NULL), per row b:
+ *     full     if draws[0][b] < p_full
+ *     partial  else if partial_on && draws[1][b] < p_partial, with combination k = combo_idx ? combo_idx[b]
+ *              : the first k with draws[2][b] < combo_thr[k] (the host makes combo_thr[ncombo-1] = 1); k outside [0, ncombo): none
+ *   evaluation form (draws == NULL; combo_idx NULL, p_full 0, partial_on 0): every row is full if row_full, else takes row_bits
+ *   a column is cleared (aux 0, mask byte 0) when its row is full or when a component holding it has its bit in the row's
+ *   bitmask; columns outside every component are cleared only by a full row; every other element copies through.
+ * Comparisons are strict, as in the reference: p = 0 masks nothing, p = 1 masks every draw of [0, 1).
+ * out_aux / out_mask may be the inputs (in place) or distinct buffers; a NULL output is not written (out_aux NULL: aux may be
+ * NULL too; out_mask and counts NULL: mask may be NULL).  counts[0] += full rows, counts[1] += rows with a combination,
+ * counts[2 + c] += rows whose OUTPUT mask is nonzero over all of component c (integer atomics; the caller zeroes counts).
+ * With nothing to mask the call is the statistics pass alone. */
+#define LNX_META_MASK_MAX_COMPONENTS 32
+typedef struct lnx_meta_mask_args {
+    const float* aux;              /* [B, D] fp32 */
+    const unsigned char* mask;     /* [B, D] bytes, nonzero = valid */
+    float* out_aux;                /* [B, D] or NULL */
+    unsigned char* out_mask;       /* [B, D] or NULL */
+    int B, D;
+    const int* bounds;             /* device int[2 * ncomp] of [start, end), as lnx_mix_meta takes; the kernel never indexes past D */
+    int ncomp;                     /* <= LNX_META_MASK_MAX_COMPONENTS */
+    int ncombo;
+    const unsigned int* combo_bits; /* device [ncombo]: bit c = component c belongs to the combination */
+    const float* combo_thr;        /* device [ncombo]: cumulative pick thresholds in (0, 1], non-decreasing, the last one 1 */
+    const float* draws;            /* device [3, B]: u_full, u_partial, u_combo; NULL = evaluation form */
+    const int* combo_idx;          /* device [B] or NULL: overrides the threshold pick (replay); -1 = no combination */
+    float p_full, p_partial;
+    int partial_on;
+    unsigned int row_bits;         /* evaluation form: the bitmask of every row */
+    int row_full;                  /* evaluation form: every row is full */
+    int* counts;                   /* device int32[2 + ncomp] or NULL */
+    int* row_combo;                /* device int32[B] or NULL: the combination each row took (-1: none or full) */
+} lnx_meta_mask_args;
+int lnx_meta_mask(const lnx_meta_mask_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * GPU-side image augmentations of the input pipeline: the tensor operations of the reference's
  * GPUAutoAugmentBatch (linnaeus/aug/gpu/autoaug.py:44-168) and GPURandomErasing (aug/gpu/random_erasing.py:24-94), on fp32

@@ -205,6 +205,9 @@ def lib() -> C.CDLL:
             _lib.lnx_preprocess_scratch_bytes.restype = C.c_int64
             _lib.lnx_preprocess.argtypes = [C.POINTER(PreprocessArgs), C.c_void_p]
             _lib.lnx_preprocess.restype = C.c_int
+        if hasattr(_lib, "lnx_meta_mask"):
+            _lib.lnx_meta_mask.argtypes = [C.POINTER(MetaMaskArgs), C.c_void_p]
+            _lib.lnx_meta_mask.restype = C.c_int
         if hasattr(_lib, "lnx_layernorm_fwd_query"):
             _lib.lnx_layernorm_fwd_query.argtypes = [C.POINTER(LnArgs), C.POINTER(LnLaunch)]
             _lib.lnx_layernorm_bwd_query.argtypes = [C.POINTER(LnBwdArgs), C.POINTER(LnLaunch)]
@@ -245,7 +248,7 @@ EXPORTS = [
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
-    "lnx_mix_rows", "lnx_mix_meta",
+    "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",
     "lnx_plan_create", "lnx_plan_destroy", "lnx_plan_workspace_bytes", "lnx_plan_num_params", "lnx_plan_param_name",
@@ -407,4 +410,17 @@ class MixArgs(C.Structure):
         ("x", C.c_void_p), ("perm", C.c_void_p), ("valid", C.c_void_p), ("out", C.c_void_p),
         ("B", C.c_int), ("row", C.c_int64), ("H", C.c_int), ("W", C.c_int), ("lam", C.c_float),
         ("h0", C.c_int), ("h1", C.c_int), ("w0", C.c_int), ("w1", C.c_int), ("mode", C.c_int),
+    ]
+
+
+META_MASK_MAX_COMPONENTS = 32  # == LNX_META_MASK_MAX_COMPONENTS
+
+
+class MetaMaskArgs(C.Structure):  # == lnx_meta_mask_args
+    _fields_ = [
+        ("aux", C.c_void_p), ("mask", C.c_void_p), ("out_aux", C.c_void_p), ("out_mask", C.c_void_p),
+        ("B", C.c_int), ("D", C.c_int), ("bounds", C.c_void_p), ("ncomp", C.c_int), ("ncombo", C.c_int),
+        ("combo_bits", C.c_void_p), ("combo_thr", C.c_void_p), ("draws", C.c_void_p), ("combo_idx", C.c_void_p),
+        ("p_full", C.c_float), ("p_partial", C.c_float), ("partial_on", C.c_int), ("row_bits", C.c_uint), ("row_full", C.c_int),
+        ("counts", C.c_void_p), ("row_combo", C.c_void_p),
     ]

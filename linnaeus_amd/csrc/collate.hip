@@ -2,6 +2,7 @@
 // chunk-level "hard pick" of metadata, as the reference's GPU augmentations compute them
 //   linnaeus/aug/gpu/selective_mixup.py:140-230 (lam x + (1-lam) x[perm]),  :420-560 (metadata chunks)
 //   linnaeus/aug/gpu/selective_cutmix.py:200-260 (box paste from x[perm] for samples of a mixable group)
+//   linnaeus/h5data/h5dataloader.py:709-940 (scheduled full / partial metadata masking), :1677-1801 (component statistics)
 // The reference walks the batch in Python for the metadata (one .item() per sample and chunk); here every piece is one
 // launch, HBM-bound: an image batch is read twice (own + partner sample) and written once.
 #include "common.hpp"
@@ -69,7 +70,89 @@ __global__ __launch_bounds__(256) void mix_meta_kernel(const float* __restrict__
     }
 }
 
+// Scheduled metadata masking: one wavefront per row (grid-stride over rows), lanes over the columns.  The row's decision (full,
+// partial with combination k, or none) is uniform over the wave; a column is cleared when the row is full or when a component that
+// holds it has its bit in the row's bitmask.  Every element is read and written by the same lane, so the outputs may be the inputs.
+// `bad` collects, per lane, the components that hold a column whose OUTPUT mask byte is zero; OR-ed over the wave it tells which
+// components are all-true in this row (an empty component is never bad: torch's all() over an empty slice is True as well).  Lane
+// c < ncomp tallies component c, lane 32 the full rows, lane 33 the partial rows; one integer atomic per lane and wave at the end.
+__global__ __launch_bounds__(256) void meta_mask_kernel(const lnx_meta_mask_args a) {
+    __shared__ int s_bounds[2 * LNX_META_MASK_MAX_COMPONENTS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((int)threadIdx.x < 2 * a.ncomp) s_bounds[threadIdx.x] = a.bounds[threadIdx.x];
+    __syncthreads();
+    int tally = 0;
+    for (int b = blockIdx.x * 4 + wave; b < a.B; b += gridDim.x * 4) {
+        bool full;
+        int k = -1;
+        unsigned bits;
+        if (a.draws != nullptr) {
+            full = a.draws[b] < a.p_full;
+            if (!full && a.partial_on && a.draws[a.B + b] < a.p_partial) {
+                if (a.combo_idx != nullptr) {
+                    k = a.combo_idx[b];
+                } else {  // first k with u < thr[k]; the last threshold is 1, so a draw of [0, 1) never runs past it
+                    const float u = a.draws[2 * a.B + b];
+                    for (k = 0; k < a.ncombo - 1 && !(u < a.combo_thr[k]); ++k) {}
+                }
+                if (k < 0 || k >= a.ncombo) k = -1;
+            }
+            bits = k >= 0 ? a.combo_bits[k] : 0u;
+        } else {
+            full = a.row_full != 0;
+            bits = a.row_bits;
+        }
+        unsigned bad = 0;
+        for (int d = lane; d < a.D; d += 64) {
+            unsigned cb = 0;
+            for (int c = 0; c < a.ncomp; ++c)
+                if (d >= s_bounds[2 * c] && d < s_bounds[2 * c + 1]) cb |= 1u << c;
+            const bool clear = full || (cb & bits) != 0;
+            const int64_t i = (int64_t)b * a.D + d;
+            if (a.mask != nullptr) {
+                const unsigned char m = clear ? (unsigned char)0 : a.mask[i];
+                if (a.out_mask != nullptr) a.out_mask[i] = m;
+                if (m == 0) bad |= cb;
+            }
+            if (a.out_aux != nullptr) a.out_aux[i] = clear ? 0.0f : a.aux[i];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bad |= __shfl_xor(bad, o, 64);
+        if (lane < a.ncomp) tally += (int)(((bad >> lane) & 1u) == 0);
+        else if (lane == 32) tally += (int)full;
+        else if (lane == 33) tally += (int)(k >= 0);
+        if (a.row_combo != nullptr && lane == 0) a.row_combo[b] = k;
+    }
+    if (a.counts != nullptr && tally != 0) {
+        if (lane < a.ncomp) atomicAdd(a.counts + 2 + lane, tally);
+        else if (lane == 32) atomicAdd(a.counts + 0, tally);
+        else if (lane == 33) atomicAdd(a.counts + 1, tally);
+    }
+}
+
 }  // namespace
+
+extern "C" int lnx_meta_mask(const lnx_meta_mask_args* a, void* stream) {
+    LNX_CHECK(a != nullptr, "lnx_meta_mask: null argument struct");
+    LNX_CHECK(a->B > 0 && a->D > 0, "lnx_meta_mask: bad shape B = %d, D = %d", a->B, a->D);
+    LNX_CHECK(a->ncomp >= 0 && a->ncomp <= LNX_META_MASK_MAX_COMPONENTS, "lnx_meta_mask: %d components (at most %d)", a->ncomp, LNX_META_MASK_MAX_COMPONENTS);
+    LNX_CHECK(a->ncomp == 0 || a->bounds != nullptr, "lnx_meta_mask: null component bounds");
+    LNX_CHECK(a->out_aux == nullptr || a->aux != nullptr, "lnx_meta_mask: null aux for out_aux");
+    LNX_CHECK((a->out_mask == nullptr && a->counts == nullptr) || a->mask != nullptr, "lnx_meta_mask: null mask for out_mask / counts");
+    LNX_CHECK(a->out_aux || a->out_mask || a->counts || a->row_combo, "lnx_meta_mask: null outputs (nothing to compute)");
+    if (a->draws != nullptr) {
+        LNX_CHECK(a->ncombo >= 0 && (a->ncombo == 0 || (a->combo_bits != nullptr && a->combo_thr != nullptr)), "lnx_meta_mask: null combination table");
+        LNX_CHECK(a->row_bits == 0 && a->row_full == 0, "lnx_meta_mask: row_bits / row_full belong to the form without draws");
+    } else {
+        LNX_CHECK(a->combo_idx == nullptr, "lnx_meta_mask: combo_idx needs draws");
+        LNX_CHECK(a->p_full == 0.0f && a->partial_on == 0, "lnx_meta_mask: null draws with a masking probability");
+    }
+    int grid = cdiv(a->B, 4);
+    if (grid > 256) grid = 256;
+    hipLaunchKernelGGL(meta_mask_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int lnx_mix_rows(const lnx_mix_args* a, void* stream) {
     LNX_CHECK(a && a->x && a->perm && a->out, "lnx_mix_rows: null operand");
