@@ -772,6 +772,66 @@ int lnx_ademamix_step(const lnx_adamw_desc* descs_dev, float* const* slow_dev, i
                       const float* sumsq, float max_norm, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Muon (linnaeus/optimizers/muon.py:27-65, 126-190, chosen by OPTIMIZER.NAME = muon in optimizers/build.py:130-154): the whole step
+ * for every 2-D / flattened 4-D parameter in 3 * max(ns_steps) + 3 launches, whatever the number of matrices.
+ *   buf = lerp(buf, g, 1 - momentum);  u = nesterov ? lerp(g, buf, momentum) : buf          (muon.py:159-167, torch's lerp formulas)
+ *   X = bf16(u), transposed when rows > cols;  X = bf16(X / (||X||_F + 1e-7))                (muon.py:45-52; norm and division in fp32)
+ *   ns_steps times:  A = X X^T;  B = c A A + b A;  X = B X + a X                             (muon.py:55-58; a, b, c = 3.4445, -4.7750, 2.0315)
+ *   p = p * decay - step * O,  decay = 1 - lr wd,  step = lr max(1, rows / cols)^(1/2)       (muon.py:156-157, 177-188)
+ * Each product is a bf16 MFMA product with fp32 accumulation whose affine term is applied to the accumulator and rounded to bf16 once
+ * (the reference rounds every product and every term).  g is not modified (the reference overwrites it with u, muon.py:167).
+ *
+ * Every matrix is held as X [m, n] with m = min(rows, cols), n = max(rows, cols), zero-padded to mp x np (multiples of
+ * LNX_MUON_TILE); zero rows and columns stay zero through every product, so no kernel predicates an edge.  lnx_muon_layout places the
+ * bf16 regions of every matrix in ONE workspace, which the caller allocates and zero-fills once:
+ *   x_off          X [mp, np], updated in place by the third product (an element is read and written by the same lane only)
+ *   xt_off[0..1]   X^T [np, mp], ping and pong: the third product reads one whole (its K runs along m) and writes the other
+ *   a_off, b_off   A and B [mp, mp]
+ * and lists the LNX_MUON_TILE x LNX_MUON_TILE output tiles of the three products in one table per stage (stage 0: A, 1: B, 2: X), the
+ * tiles of matrix i at tile_start[s] .. + tile_count[s] of stage s.  A launch takes a PREFIX of a stage's table: order the matrices by
+ * descending ns_steps and a matrix with fewer iterations drops out of the later launches.
+ * No float atomics anywhere: sums of squares are per-workgroup partials folded in a fixed order (as lnx_grad_sumsq), the same inputs give the same bits.
+ * -----------------------------------------------------------------------------------*/
+#define LNX_MUON_TILE 32
+#define LNX_MUON_ELEMS 4096 /* elements per workgroup of the momentum and apply launches */
+typedef struct lnx_muon_mat {
+    float* p;        /* parameter, fp32 [rows, cols] contiguous */
+    float* buf;      /* momentum_buffer, fp32, same shape */
+    const float* g;  /* gradient, or NULL: the parameter is skipped this step (muon.py:150-151) */
+    int rows, cols;  /* logical shape; a 4-D parameter is [out, in * kh * kw] */
+    int mp, np;      /* padded min(rows, cols), max(rows, cols) */
+    int64_t x_off, xt_off[2], a_off, b_off; /* byte offsets in the workspace */
+    int tile_start[3], tile_count[3];
+    int block_start;                        /* first workgroup in the momentum / apply launches (= first sum-of-squares partial) */
+    int ns_steps, nesterov;
+    float momentum, omm;                    /* momentum and 1 - momentum, each rounded from double */
+    float decay, step;                      /* 1 - lr wd and lr max(1, rows / cols)^(1/2): double on the host, rounded once */
+} lnx_muon_mat;
+typedef struct lnx_muon_tile {
+    int mat, tr, tc, pad;                   /* output tile (tr, tc) of matrix mat */
+} lnx_muon_tile;
+typedef struct lnx_muon_info {
+    int64_t workspace_bytes;
+    int64_t ntiles[3];                      /* the three stage tables follow each other in `tiles` in this order */
+    int total_blocks;
+} lnx_muon_info;
+/* Host side, no device work, no GPU needed.  shapes: n x [rows, cols].  Fills the geometry fields of mats[0..n) (pointers and
+ * hyper-parameters are left alone), info, and -- when tiles != NULL -- the tile tables (tile_cap entries must hold them all). */
+int lnx_muon_layout(const int* shapes, int n, lnx_muon_mat* mats, lnx_muon_tile* tiles, int64_t tile_cap, lnx_muon_info* info);
+typedef struct lnx_muon_step_args {
+    int n;
+    const lnx_muon_mat* mats;        /* HOST copy: checked against lnx_muon_layout of its shapes before anything is launched */
+    const lnx_muon_mat* mats_dev;    /* the same table on the device */
+    const lnx_muon_tile* tiles_dev;  /* the tile tables lnx_muon_layout wrote, on the device */
+    void* workspace;                 /* workspace_bytes, zero-filled once, 256-byte aligned */
+    int64_t workspace_bytes;
+    float* partials;                 /* total_blocks floats */
+} lnx_muon_step_args;
+int lnx_muon_step(const lnx_muon_step_args* args, void* stream);
+/* launches made by lnx_muon_step since the library was loaded (host-side counter, as lnx_nt_kernel_launches) */
+int64_t lnx_muon_launches(void);
+
+/* ------------------------------------------------------------------------------------
  * GradNorm task weighting (LOSS.GRAD_WEIGHTING.TASK.TYPE = gradnorm): loss/gradnorm.py GradNormModule.measure_and_update on the
  * device, behind one forward and one lnx_plan_backward_into per task (linnaeus_amd.loss.GradientWeighting).
  * lnx_gradnorm_sumsq: for task t < ntasks, sum of squares of the tensors of the AdamW-style descriptor table (only .g and .n are

@@ -341,3 +341,134 @@ class Muon(torch.optim.Optimizer):
                     scaling = max(1, p.size(-2) / p.size(-1)) ** 0.5
                 p.add_(o.view_as(p).to(p.dtype), alpha=-lr * scaling)
         return loss
+
+
+def muon_layout(shapes):
+    """lnx_muon_layout of a list of logical [rows, cols] shapes (host only, no GPU): (MuonMat array, tile table as an int32 array
+    [ntiles, 4] = (matrix, tile row, tile column, 0) with the three stage tables one after the other, MuonInfo)."""
+    lib = L.lib()
+    n = len(shapes)
+    flat = (C.c_int * (2 * max(n, 1)))(*(int(v) for s in shapes for v in s))
+    mats = (L.MuonMat * max(n, 1))()
+    info = L.MuonInfo()
+    L.check(lib.lnx_muon_layout(flat, n, mats, None, 0, C.byref(info)), "lnx_muon_layout")
+    tiles = np.zeros((sum(info.ntiles), 4), dtype=np.int32)
+    L.check(lib.lnx_muon_layout(flat, n, mats, tiles.ctypes.data, tiles.shape[0], C.byref(info)), "lnx_muon_layout")
+    return mats, tiles, info
+
+
+def muon_parameters(model):
+    """the parameters optimizers/build.py:130-154 hands to Muon: trainable, 2-D or 4-D, and no 'embed', 'token', 'head' or
+    'classifier' in the name (those, and every other shape, go to AdamW)"""
+    return [p for name, p in model.named_parameters()
+            if p.requires_grad and p.dim() in (2, 4) and not any(k in name.lower() for k in ("embed", "token", "cls_token", "head", "classifier"))]
+
+
+def _muon_shape(p):
+    return (p.size(0), p.numel() // p.size(0))
+
+
+class FusedMuon(torch.optim.Optimizer):
+    """Muon (linnaeus/optimizers/muon.py:67-190, OPTIMIZER.NAME = muon) as 3 * max(ns_steps) + 3 HIP launches per step for ALL matrices
+    together (csrc/muon.hip): momentum and Nesterov, normalisation, the Newton-Schulz products as grouped bf16 MFMA launches, and
+    the update, instead of the ~50 launches per parameter of `Muon` above.
+
+    Same constructor, `param_groups` keys (lr, weight_decay, momentum, nesterov, ns_steps) and per-parameter state
+    (`momentum_buffer`, fp32) as the reference and as `Muon`, so checkpoints move between the three with `load_state_dict`.
+    Groups may differ in every hyper-parameter; a parameter whose `.grad` is None is skipped for the step (no decay, no state).
+    Differences from the reference:
+      * parameters that are not 2-D or 4-D raise ValueError at construction whatever `strict` says (the reference fails inside
+        its first step);
+      * `.grad` is left untouched (the reference overwrites it with the Nesterov gradient, muon.py:167);
+      * each product is rounded to bf16 once, after its affine term, as `zeropower_via_newtonschulz5` above does.
+    Contiguous fp32 parameters and gradients on the GPU only.  Bit-reproducible: no atomics, the same inputs give the same
+    parameters whatever else is in the optimizer, so data-parallel replicas that each run the whole step stay equal.
+    """
+
+    def __init__(self, params, lr=0.02, weight_decay=0.01, momentum=0.95, nesterov=True, ns_steps=5, strict=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if int(ns_steps) != ns_steps or ns_steps < 0:
+            raise ValueError(f"Invalid ns_steps value: {ns_steps}")
+        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, ns_steps=ns_steps))
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.dim() not in (2, 4):
+                    raise ValueError(f"Muon optimizer requires 2D or 4D parameters, got shape {p.shape}")
+        self._key = None      # what the layout depends on: shapes and ns_steps in launch order
+        self._order = None    # [(group index, p)] by descending ns_steps: each iteration launches a prefix of the tile tables
+        self._mats = None     # host lnx_muon_mat table
+        self._sent = None     # bytes of the table as last copied to the device
+        self._dev = None      # (device table, device tile tables, workspace, partials, MuonInfo)
+
+    def _build(self, order, dev):
+        mats, tiles, info = muon_layout([_muon_shape(p) for _, p in order])
+        self._mats = mats
+        self._dev = (torch.empty(C.sizeof(mats), device=dev, dtype=torch.uint8), torch.from_numpy(tiles).to(dev),
+                     torch.zeros(info.workspace_bytes, device=dev, dtype=torch.uint8),  # zero-filled once: the padding stays zero
+                     torch.empty(info.total_blocks, device=dev, dtype=torch.float32), info)
+        self._sent = None
+
+    def workspace_bytes(self) -> int:
+        """bytes of the bf16 workspace of the last step's layout (0 before the first step)"""
+        return 0 if self._dev is None else int(self._dev[4].workspace_bytes)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        order = [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"]]
+        if not order:
+            return loss
+        for gi, g in enumerate(self.param_groups):
+            if int(g["ns_steps"]) != g["ns_steps"] or g["ns_steps"] < 0:
+                raise ValueError(f"Invalid ns_steps value: {g['ns_steps']}")
+        order.sort(key=lambda it: -int(self.param_groups[it[0]]["ns_steps"]))  # stable: ties keep the parameter order
+        with_grad = [p for _, p in order if p.grad is not None]
+        if not with_grad:
+            return loss
+        dev = with_grad[0].device
+        for p in with_grad:  # a parameter without a gradient is not touched this step
+            if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise L.LnxError("FusedMuon needs contiguous fp32 parameters on one GPU")
+            if p.grad.device != dev or p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.shape != p.shape:
+                raise L.LnxError("FusedMuon needs contiguous fp32 gradients on the parameters' GPU")
+        key = tuple((id(p), tuple(p.shape), int(self.param_groups[gi]["ns_steps"])) for gi, p in order)
+        if key != self._key:
+            self._build(order, dev)
+            self._key, self._order = key, order
+        mats = self._mats
+        for i, (gi, p) in enumerate(order):
+            g, m = self.param_groups[gi], mats[i]
+            m.p = p.data_ptr()
+            if p.grad is None:
+                m.g = m.buf = None
+            else:
+                st = self.state[p]
+                if "momentum_buffer" not in st:
+                    st["momentum_buffer"] = torch.zeros_like(p.grad)
+                buf = st["momentum_buffer"]
+                if buf.device != dev or buf.dtype != torch.float32 or buf.shape != p.shape or not buf.is_contiguous():
+                    raise L.LnxError("FusedMuon: state 'momentum_buffer' must be a contiguous fp32 tensor of the parameter's shape on its device")
+                m.g, m.buf = p.grad.data_ptr(), buf.data_ptr()
+            rows, cols = _muon_shape(p)
+            lr, mom = float(g["lr"]), float(g["momentum"])
+            m.ns_steps, m.nesterov = int(g["ns_steps"]), 1 if g["nesterov"] else 0
+            m.momentum, m.omm = mom, 1 - mom
+            m.decay, m.step = 1 - lr * float(g["weight_decay"]), lr * max(1, rows / cols) ** 0.5
+        table, tiles, ws, part, info = self._dev
+        raw = bytes(mats)
+        if raw != self._sent:  # gradient pointers and learning rates usually move between steps; the layout does not
+            table.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+            self._sent = raw
+        a = L.MuonStepArgs()
+        a.n, a.mats, a.mats_dev, a.tiles_dev = len(order), C.addressof(mats), table.data_ptr(), tiles.data_ptr()
+        a.workspace, a.workspace_bytes, a.partials = ws.data_ptr(), ws.numel(), part.data_ptr()
+        L.check(L.lib().lnx_muon_step(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_muon_step")
+        return loss
