@@ -8,6 +8,7 @@ import torch
 from linnaeus_amd import _lib as L
 from linnaeus_amd import ops
 from oracle import mformer_oracle as O
+from tests.fp8_ref import mx_reference as _mx_reference
 
 pytestmark = pytest.mark.gpu
 DT = {L.F32: torch.float32, L.BF16: torch.bfloat16}
@@ -664,19 +665,6 @@ def test_fp8_quantize_and_gemm(M, N, K, xd):
         ops.gemm_nt_fp8(x8, sx, w8, sw, o32, bias=bias, res=res, rowscale=rs, rows_per_sample=rps)
         rowf = rs.double().cpu()[torch.arange(M) // rps].reshape(M, 1)
         torch.testing.assert_close(o32.double().cpu(), res.double().cpu() + rowf * h, rtol=1e-4, atol=1e-4 * max(1.0, ref.abs().max().item()))
-
-
-def _mx_reference(x):
-    """The definition lnx_quantize_mxfp8 implements, restated with torch integer ops: per 32-element block the smallest
-    power of two 2^e with amax * 2^-e <= 448, elements = e4m3fn(x * 2^-e) (torch's round-to-nearest-even conversion)."""
-    M, K = x.shape
-    xb = x.float().view(M, K // 32, 32)
-    bits = xb.abs().amax(-1).contiguous().view(torch.int32)
-    e = ((bits >> 23) & 0xFF) - 8 + ((bits & 0x7FFFFF) > 0x600000).int()
-    e = e.clamp(0, 254)
-    inv = ((254 - e) << 23).view(torch.float32)
-    q = (xb * inv.unsqueeze(-1)).clamp(-448, 448).to(torch.float8_e4m3fn).view(M, K)
-    return q, e.to(torch.uint8)  # e: [M, K/32]
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 128, 256), (1000, 384, 512), (4096, 1152, 384 * 2), (513, 208, 1024), (33000, 512, 512), (16500, 1024, 384)])
