@@ -425,18 +425,25 @@ int lnx_attn_bwd(const lnx_attn_bwd_args* args, void* stream);
 
 /* Which kernel family lnx_attn_fwd / lnx_attn_bwd take (host-side bookkeeping, no device work; the forward and the backward of one
  * call take the same one): the boundary tests use it to prove that a sequence length ran on the kernels it is meant to cover.
- *   resident (bf16, head_dim 64, no dropout mask, N <= 256): 4 waves at N <= 64, 8 waves beyond;
+ *   resident (bf16, head_dim 64, no dropout mask, N <= 256): 4 waves at N <= 64, 8 waves beyond.  Their backward is ONE kernel per
+ *     call at N <= 224 (every operand staged in LDS once for both the dq and the dk / dv phase; 4 waves at N <= 64, 16 beyond) and the
+ *     dq / dk-dv pair of 4- / 8-wave kernels at 225..256 (four operand images no longer fit the LDS) and, at every resident N, with
+ *     LNX_ATTN_BWD_SPLIT in the environment (read per call: the A/B switch).  The family reported is the same either way, and so are
+ *     dqkv and delta bit for bit (the rotating mode included);
  *   tiled, 4 waves (64-row tiles): fp32; any call with a dropout mask; bf16 head_dim 32; bf16 head_dim 64 / 128 at N <= 128 where
  *     the resident kernels do not take it, and at every N with LNX_ATTN_NW=4 in the environment (read once per process);
  *   tiled, 8 waves (128-row tiles): bf16 head_dim 128 at N > 128; bf16 head_dim 64 at N > 256, and at N > 128 with LNX_ATTN_TILED
  *     in the environment (read per call: no resident kernels).
  * lnx_attn_dispatch(): the family a launch with these arguments would take now (head_dim 0 = 64; has_drop_mask != 0: a dropout
  *   mask is passed); negative for a dtype, N or head_dim the entry points refuse.  The entry points decide with the same function.
- * lnx_last_attn_kernel(): family of the most recent lnx_attn_fwd / lnx_attn_bwd launch of this process (any stream), 0 before the first. */
+ * lnx_last_attn_kernel(): family of the most recent lnx_attn_fwd / lnx_attn_bwd launch of this process (any stream), 0 before the first.
+ * lnx_last_attn_bwd_launches(): attention kernels the most recent lnx_attn_bwd launched (the freqs fold not counted): 1 for the
+ *   one-kernel resident backward, 2 for every pair; 0 before the first lnx_attn_bwd. */
 enum { LNX_ATTN_KERNEL_NONE = 0, LNX_ATTN_KERNEL_RES4 = 1 /* resident, 4 waves */, LNX_ATTN_KERNEL_RES8 = 2 /* resident, 8 waves */,
        LNX_ATTN_KERNEL_TILED4 = 3 /* tiled, 64-row tiles */, LNX_ATTN_KERNEL_TILED8 = 4 /* tiled, 128-row tiles */ };
 int lnx_attn_dispatch(int dtype, int N, int head_dim, int has_drop_mask);
 int lnx_last_attn_kernel(void);
+int lnx_last_attn_bwd_launches(void);
 
 /* ------------------------------------------------------------------------------------
  * Small data-movement / elementwise kernels of the path

@@ -18,6 +18,7 @@
 // Kernels:  attn_fwd  -> o, lse
 //           attn_bwd_dq   (per 64 queries: delta, dq, cos-gradient part of q)
 //           attn_bwd_dkv  (per 64 keys:    dk, dv, cos-gradient part of k)
+//           attn_bwd_res  (resident, N <= 224: both of the above for a whole (sample, head) in one workgroup)
 #include <stdlib.h>
 
 #include <atomic>
@@ -897,20 +898,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
 // 16-row tiles with no barrier in the loop.  Against the tiled kernels above this removes the
 // per-q-tile re-staging of K/V (4x at N = 199) and every in-loop __syncthreads.
 // ---------------------------------------------------------------------------------
-template <typename T, bool COS, bool ROWIMG, bool TRIMG, bool ROT = false>
-__device__ __forceinline__ void stage_all(unsigned char* rowimg, unsigned char* trimg, const T* __restrict__ base, int64_t ld, int nrows_pad, int N, int E,
-                                          const float* __restrict__ cos_tab, int heads, int head, float scale, const float* __restrict__ sin_tab = nullptr) {
-    constexpr int NCH = AT<T>::NCH;
-    constexpr int EPV = AT<T>::EPV;
-    constexpr int UN = 4;  // chunks in flight per thread (N <= 256: the whole operand in one batch of 512 threads)
-    const int total = nrows_pad * NCH;
-    for (int i0 = threadIdx.x; i0 < total; i0 += UN * blockDim.x) {
-        Chunk<T, COS, 64, ROT> ch[UN];
+// One batch of a whole operand's staging: chunks i0, i0 + blockDim, ... (UN per thread) of the `total` 16-byte chunks of its image.
+// Split like TileFetch: fetch() requests them (unconditional, clamped), commit() writes the images -- a kernel that stages several
+// operands issues every fetch() before the first commit() and pays one memory round trip for all of them.
+template <typename T, bool COS, bool ROT, int UN>
+struct StageBatch {
+    static constexpr int NCH = AT<T>::NCH, EPV = AT<T>::EPV;
+    Chunk<T, COS, 64, ROT> ch[UN];
+    __device__ __forceinline__ void fetch(const T* __restrict__ base, int64_t ld, int i0, int total, int N, int E, const float* __restrict__ cos_tab, int heads, int head,
+                                          const float* __restrict__ sin_tab = nullptr) {
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int i = min(i0 + u * (int)blockDim.x, total - 1);
             ch[u].fetch(base, ld, i / NCH, N, E, (i % NCH) * EPV, cos_tab, heads, head, sin_tab);
         }
+    }
+    template <bool ROWIMG, bool TRIMG>
+    __device__ __forceinline__ void commit(unsigned char* rowimg, unsigned char* trimg, int i0, int total, int N, int E, float scale) const {
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int i = i0 + u * (int)blockDim.x;
@@ -921,6 +925,17 @@ __device__ __forceinline__ void stage_all(unsigned char* rowimg, unsigned char* 
                 if constexpr (TRIMG) st16(trimg + r * AT<T>::TRB + c * 16, v);
             }
         }
+    }
+};
+template <typename T, bool COS, bool ROWIMG, bool TRIMG, bool ROT = false>
+__device__ __forceinline__ void stage_all(unsigned char* rowimg, unsigned char* trimg, const T* __restrict__ base, int64_t ld, int nrows_pad, int N, int E,
+                                          const float* __restrict__ cos_tab, int heads, int head, float scale, const float* __restrict__ sin_tab = nullptr) {
+    constexpr int UN = 4;  // chunks in flight per thread (N <= 256: the whole operand in one batch of 512 threads)
+    const int total = nrows_pad * AT<T>::NCH;
+    for (int i0 = threadIdx.x; i0 < total; i0 += UN * blockDim.x) {
+        StageBatch<T, COS, ROT, UN> sb;
+        sb.fetch(base, ld, i0, total, N, E, cos_tab, heads, head, sin_tab);
+        sb.template commit<ROWIMG, TRIMG>(rowimg, trimg, i0, total, N, E, scale);
     }
 }
 
@@ -1011,6 +1026,160 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     }
 }
 
+// ---- the pieces of the resident backward that attn_bwd_dq_res_kernel / attn_bwd_dkv_res_kernel (the pair) and attn_bwd_res_kernel
+// (both phases in one workgroup) share: the same code, so the same arithmetic in the same order on either path ---------------------
+// dq side, ahead of the key loop: the raw q values and (cos mode) the cos factors of the epilogue, requested with the tile's other fetches
+template <typename T, bool ROT>
+__device__ __forceinline__ void dq_res_prefetch(float (&qr)[4][4], float (&cr)[4][2], const AttnP& p, const T* __restrict__ qb, int64_t ld, int qc, int head, int g) {
+    const T* qraw = qb + (int64_t)qc * ld;
+    const float* cpr = p.cos_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        const int d0 = dt * 16 + 4 * g;
+        if constexpr (sizeof(T) == 2) {
+            const uint2 r = *reinterpret_cast<const uint2*>(qraw + d0);
+            const bf16_t* h = reinterpret_cast<const bf16_t*>(&r);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) qr[dt][j] = (float)h[j];
+        } else {
+            const float4 r = *reinterpret_cast<const float4*>(qraw + d0);
+            qr[dt][0] = r.x; qr[dt][1] = r.y; qr[dt][2] = r.z; qr[dt][3] = r.w;
+        }
+        if constexpr (!ROT) {  // (ROT: cos and sin are fetched behind the key loop, where the d-cos entries are fetched here)
+            const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
+            cr[dt][0] = c2.x; cr[dt][1] = c2.y;
+        }
+    }
+}
+// dq of one 16-query wave tile over every staged key.
+// No masks in the loop: the image rows of the padding keys (N <= key < npad) are zero, so whatever finite dS they
+// get multiplies a zero row of K~; lanes of padding queries are not stored.  exp's argument is <= 0 for every real
+// (query, key) pair, the clamp only keeps the padding ones finite.
+// Steps of 32 keys (two 16-key groups, one MFMA contraction step of dS . K~): the images are staged in units of 32 rows,
+// so every step is the same straight-line body -- and half the live registers of a 64-key step, which these kernels
+// need (128-register budget).
+template <typename T>
+__device__ __forceinline__ void dq_res_loop(f32x4_t (&dq)[4], const unsigned char* kimg, const unsigned char* vimg, int npad, int s, int g,
+                                            const uint4 (&qf)[AT<T>::NKK], const uint4 (&dof)[AT<T>::NKK], float lse, float delta) {
+    for (int k0 = 0; k0 < npad; k0 += 32) {
+        f32x4_t sacc[4], dpacc[4];
+        rows_times_frag_pad_n<T, 2>(sacc, kimg + k0 * AT<T>::TRB, s, g, qf);
+        PHASE_FENCE();
+        rows_times_frag_pad_n<T, 2>(dpacc, vimg + k0 * AT<T>::TRB, s, g, dof);
+        PHASE_FENCE();
+        float ds[4][4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ds[t][r] = t < 2 ? RowExp<T>::clamped(sacc[t][r], lse) * (dpacc[t][r] - delta) : 0.f;
+        PHASE_FENCE();
+        imgT_times_regs_n<T, 2>(dq, kimg + k0 * AT<T>::TRB, s, g, ds);
+        PHASE_FENCE();
+    }
+}
+// dq epilogue of the resident kernels (qr, cr: dq_res_prefetch)
+template <typename T, bool ROT>
+__device__ __forceinline__ void dq_res_epilogue(const AttnP& p, const f32x4_t (&dq)[4], const float (&qr)[4][4], float (&cr)[4][2], int64_t ld, int b, int head, int q,
+                                                int s, int g, float scale, float* fl) {
+    constexpr int HD = 64;
+    const int qc = min(q, p.N - 1);
+    const float* cpr = p.cos_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
+    // the d cos / d freqs table entries of this row: fetched here (after the key loop: held across it they would spill)
+    const float* sxp = p.dsin + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
+    const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * 32;
+    float gp[4][2], dx[4][2], dy[4][2];
+    float sr[ROT ? 4 : 1][2];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        if constexpr (ROT) {
+            const float2 c2 = *reinterpret_cast<const float2*>(cpr + ((dt * 16 + 4 * g) >> 1));
+            const float2 s2 = *reinterpret_cast<const float2*>(p.sin_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32 + ((dt * 16 + 4 * g) >> 1));
+            cr[dt][0] = c2.x; cr[dt][1] = c2.y;
+            sr[dt][0] = s2.x; sr[dt][1] = s2.y;
+            dx[dt][0] = dx[dt][1] = (float)(max(qc - p.E, 0) % p.W);
+            dy[dt][0] = dy[dt][1] = (float)(max(qc - p.E, 0) / p.W);
+            continue;
+        }
+        const float2 a = *reinterpret_cast<const float2*>(sxp + ((dt * 16 + 4 * g) >> 1));
+        const float2 c = *reinterpret_cast<const float2*>(syp + ((dt * 16 + 4 * g) >> 1));
+        dx[dt][0] = a.x; dx[dt][1] = a.y;
+        dy[dt][0] = c.x; dy[dt][1] = c.y;
+    }
+    const bool row = q < p.N, img = row && q >= p.E;
+    T* dqp = reinterpret_cast<T*>(p.dqkv) + ((int64_t)b * p.N + qc) * ld + head * HD;
+    float oq[4][4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        if constexpr (ROT) {  // (see dq_epilogue)
+            const float s0 = img ? sr[dt][0] : 0.f, s1 = img ? sr[dt][1] : 0.f, r0 = img ? cr[dt][0] : 1.0f, r1 = img ? cr[dt][1] : 1.0f;
+            oq[dt][0] = scale * (dq[dt][0] * r0 + dq[dt][1] * s0); oq[dt][1] = scale * (dq[dt][1] * r0 - dq[dt][0] * s0);
+            oq[dt][2] = scale * (dq[dt][2] * r1 + dq[dt][3] * s1); oq[dt][3] = scale * (dq[dt][3] * r1 - dq[dt][2] * s1);
+            const float x0 = qr[dt][0] * r0 - qr[dt][1] * s0, x1 = qr[dt][0] * s0 + qr[dt][1] * r0;
+            const float x2 = qr[dt][2] * r1 - qr[dt][3] * s1, x3 = qr[dt][2] * s1 + qr[dt][3] * r1;
+            gp[dt][0] = img ? scale * (dq[dt][1] * x0 - dq[dt][0] * x1) : 0.f;
+            gp[dt][1] = img ? scale * (dq[dt][3] * x2 - dq[dt][2] * x3) : 0.f;
+            continue;
+        }
+        const float c0 = img ? cr[dt][0] * scale : scale, c1 = img ? cr[dt][1] * scale : scale;
+        oq[dt][0] = dq[dt][0] * c0; oq[dt][1] = dq[dt][1] * c0; oq[dt][2] = dq[dt][2] * c1; oq[dt][3] = dq[dt][3] * c1;
+        gp[dt][0] = img ? scale * (dq[dt][0] * qr[dt][0] + dq[dt][1] * qr[dt][1]) : 0.f;
+        gp[dt][1] = img ? scale * (dq[dt][2] * qr[dt][2] + dq[dt][3] * qr[dt][3]) : 0.f;
+    }
+    store_row<T>(dqp, oq, g, row);
+    if (p.E < p.N) freq_accum(fl, gp, dx, dy, s, g);
+}
+// delta = rowsum(dO . O) of the lane's query: the four lanes g of a row each sum their chunks (kk, then the elements in order), then the group
+template <typename T>
+__device__ __forceinline__ float delta_of_row(const uint4 (&dof)[AT<T>::NKK], const uint4 (&of)[AT<T>::NKK]) {
+    float dl = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < AT<T>::NKK; ++kk) {
+        Vec16<T> a, bb;
+        a.raw = dof[kk];
+        bb.raw = of[kk];
+#pragma unroll
+        for (int j = 0; j < AT<T>::EPV; ++j) dl += a.get(j) * bb.get(j);
+    }
+    return group_sum(dl);
+}
+// dk, dv of one 16-key wave tile over every staged query (lse_s: prepared LSE, del_s: delta, one entry per image row).
+// No masks in the loop (see dq_res_loop): padding queries have zero rows in both images and finite statistics (0).
+// steps of 32 queries (see dq_res_loop)
+template <typename T>
+__device__ __forceinline__ void dkv_res_loop(f32x4_t (&dk)[4], f32x4_t (&dv)[4], const unsigned char* qimg, const unsigned char* doimg, const float* lse_s,
+                                             const float* del_s, int npad, int s, int g, const uint4 (&kf)[AT<T>::NKK], const uint4 (&vf)[AT<T>::NKK]) {
+    for (int q0 = 0; q0 < npad; q0 += 32) {
+        f32x4_t sacc[4], dpacc[4];
+        rows_times_frag_pad_n<T, 2>(sacc, qimg + q0 * AT<T>::TRB, s, g, kf);
+        PHASE_FENCE();
+        rows_times_frag_pad_n<T, 2>(dpacc, doimg + q0 * AT<T>::TRB, s, g, vf);
+        PHASE_FENCE();
+        float pr[4][4], ds[4][4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (t < 2) {
+                const float4 l4 = *reinterpret_cast<const float4*>(lse_s + q0 + t * 16 + 4 * g);
+                const float4 d4 = *reinterpret_cast<const float4*>(del_s + q0 + t * 16 + 4 * g);
+                const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float pp = RowExp<T>::clamped(sacc[t][r], lv[r]);
+                    pr[t][r] = pp;
+                    ds[t][r] = pp * (dpacc[t][r] - dvv[r]);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pr[t][r] = ds[t][r] = 0.f;
+            }
+        }
+        PHASE_FENCE();
+        imgT_times_regs_n<T, 2>(dv, doimg + q0 * AT<T>::TRB, s, g, pr);
+        PHASE_FENCE();
+        imgT_times_regs_n<T, 2>(dk, qimg + q0 * AT<T>::TRB, s, g, ds);
+        PHASE_FENCE();
+    }
+}
+
 template <typename T, int NW = 8, bool ROT = false>  // NW = 4: sequences of at most 64 tokens (4 tiles of 16: half of an 8-wave workgroup would idle)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dq_res_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1052,114 +1221,24 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
             co[kk].fetch(ob, C, q, p.N, p.E, d0, nullptr, p.heads, head);
         }
         const float lse_raw = p.lse[((int64_t)b * p.heads + head) * p.N + qc];
-        const T* qraw = qb + (int64_t)qc * ld;
-        const float* cpr = p.cos_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
         float qr[4][4], cr[4][2];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const int d0 = dt * 16 + 4 * g;
-            if constexpr (sizeof(T) == 2) {
-                const uint2 r = *reinterpret_cast<const uint2*>(qraw + d0);
-                const bf16_t* h = reinterpret_cast<const bf16_t*>(&r);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) qr[dt][j] = (float)h[j];
-            } else {
-                const float4 r = *reinterpret_cast<const float4*>(qraw + d0);
-                qr[dt][0] = r.x; qr[dt][1] = r.y; qr[dt][2] = r.z; qr[dt][3] = r.w;
-            }
-            if constexpr (!ROT) {  // (ROT: cos and sin are fetched behind the key loop, where the d-cos entries are fetched here)
-                const float2 c2 = *reinterpret_cast<const float2*>(cpr + (d0 >> 1));
-                cr[dt][0] = c2.x; cr[dt][1] = c2.y;
-            }
-        }
+        dq_res_prefetch<T, ROT>(qr, cr, p, qb, ld, qc, head, g);
 #pragma unroll
         for (int kk = 0; kk < AT<T>::NKK; ++kk) {
             qf[kk] = cq[kk].value(q, p.N, p.E, scale);
             dof[kk] = cdo[kk].value(q, p.N, p.E, 1.0f);
         }
-        float dl = 0.f;
-        {
+        uint4 of[AT<T>::NKK];
 #pragma unroll
-            for (int kk = 0; kk < AT<T>::NKK; ++kk) {
-                Vec16<T> a, bb;
-                a.raw = dof[kk];
-                bb.raw = co[kk].value(q, p.N, p.E, 1.0f);
-#pragma unroll
-                for (int j = 0; j < AT<T>::EPV; ++j) dl += a.get(j) * bb.get(j);
-            }
-        }
-        const float delta = group_sum(dl);
+        for (int kk = 0; kk < AT<T>::NKK; ++kk) of[kk] = co[kk].value(q, p.N, p.E, 1.0f);
+        const float delta = delta_of_row<T>(dof, of);
         const float lse = RowExp<T>::prep(q < p.N ? lse_raw : 0.f);
         if (q < p.N && g == 0) p.delta[((int64_t)b * p.heads + head) * p.N + q] = delta;
         f32x4_t dq[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) dq[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        // No masks in the loop: the image rows of the padding keys (N <= key < npad) are zero, so whatever finite dS they
-        // get multiplies a zero row of K~; lanes of padding queries are not stored.  exp's argument is <= 0 for every real
-        // (query, key) pair, the clamp only keeps the padding ones finite.
-        // Steps of 32 keys (two 16-key groups, one MFMA contraction step of dS . K~): the images are staged in units of 32 rows,
-        // so every step is the same straight-line body -- and half the live registers of a 64-key step, which this kernel
-        // needs (128-register budget: two workgroups per CU).
-        for (int k0 = 0; k0 < npad; k0 += 32) {
-            f32x4_t sacc[4], dpacc[4];
-            rows_times_frag_pad_n<T, 2>(sacc, kimg + k0 * AT<T>::TRB, s, g, qf);
-            PHASE_FENCE();
-            rows_times_frag_pad_n<T, 2>(dpacc, vimg + k0 * AT<T>::TRB, s, g, dof);
-            PHASE_FENCE();
-            float ds[4][4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ds[t][r] = t < 2 ? RowExp<T>::clamped(sacc[t][r], lse) * (dpacc[t][r] - delta) : 0.f;
-            PHASE_FENCE();
-            imgT_times_regs_n<T, 2>(dq, kimg + k0 * AT<T>::TRB, s, g, ds);
-            PHASE_FENCE();
-        }
-        {
-            // the d cos / d freqs table entries of this row: fetched here (after the key loop: held across it they would spill)
-            const float* sxp = p.dsin + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
-            const float* syp = sxp + (int64_t)(p.N - p.E) * p.heads * 32;
-            float gp[4][2], dx[4][2], dy[4][2];
-            float sr[ROT ? 4 : 1][2];
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                if constexpr (ROT) {
-                    const float2 c2 = *reinterpret_cast<const float2*>(cpr + ((dt * 16 + 4 * g) >> 1));
-                    const float2 s2 = *reinterpret_cast<const float2*>(p.sin_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32 + ((dt * 16 + 4 * g) >> 1));
-                    cr[dt][0] = c2.x; cr[dt][1] = c2.y;
-                    sr[dt][0] = s2.x; sr[dt][1] = s2.y;
-                    dx[dt][0] = dx[dt][1] = (float)(max(qc - p.E, 0) % p.W);
-                    dy[dt][0] = dy[dt][1] = (float)(max(qc - p.E, 0) / p.W);
-                    continue;
-                }
-                const float2 a = *reinterpret_cast<const float2*>(sxp + ((dt * 16 + 4 * g) >> 1));
-                const float2 c = *reinterpret_cast<const float2*>(syp + ((dt * 16 + 4 * g) >> 1));
-                dx[dt][0] = a.x; dx[dt][1] = a.y;
-                dy[dt][0] = c.x; dy[dt][1] = c.y;
-            }
-            const bool row = q < p.N, img = row && q >= p.E;
-            T* dqp = reinterpret_cast<T*>(p.dqkv) + ((int64_t)b * p.N + qc) * ld + head * HD;
-            float oq[4][4];
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                if constexpr (ROT) {  // (see dq_epilogue)
-                    const float s0 = img ? sr[dt][0] : 0.f, s1 = img ? sr[dt][1] : 0.f, r0 = img ? cr[dt][0] : 1.0f, r1 = img ? cr[dt][1] : 1.0f;
-                    oq[dt][0] = scale * (dq[dt][0] * r0 + dq[dt][1] * s0); oq[dt][1] = scale * (dq[dt][1] * r0 - dq[dt][0] * s0);
-                    oq[dt][2] = scale * (dq[dt][2] * r1 + dq[dt][3] * s1); oq[dt][3] = scale * (dq[dt][3] * r1 - dq[dt][2] * s1);
-                    const float x0 = qr[dt][0] * r0 - qr[dt][1] * s0, x1 = qr[dt][0] * s0 + qr[dt][1] * r0;
-                    const float x2 = qr[dt][2] * r1 - qr[dt][3] * s1, x3 = qr[dt][2] * s1 + qr[dt][3] * r1;
-                    gp[dt][0] = img ? scale * (dq[dt][1] * x0 - dq[dt][0] * x1) : 0.f;
-                    gp[dt][1] = img ? scale * (dq[dt][3] * x2 - dq[dt][2] * x3) : 0.f;
-                    continue;
-                }
-                const float c0 = img ? cr[dt][0] * scale : scale, c1 = img ? cr[dt][1] * scale : scale;
-                oq[dt][0] = dq[dt][0] * c0; oq[dt][1] = dq[dt][1] * c0; oq[dt][2] = dq[dt][2] * c1; oq[dt][3] = dq[dt][3] * c1;
-                gp[dt][0] = img ? scale * (dq[dt][0] * qr[dt][0] + dq[dt][1] * qr[dt][1]) : 0.f;
-                gp[dt][1] = img ? scale * (dq[dt][2] * qr[dt][2] + dq[dt][3] * qr[dt][3]) : 0.f;
-            }
-            store_row<T>(dqp, oq, g, row);
-            if (p.E < p.N) freq_accum(fl, gp, dx, dy, s, g);
-        }
+        dq_res_loop<T>(dq, kimg, vimg, npad, s, g, qf, dof, lse, delta);
+        dq_res_epilogue<T, ROT>(p, dq, qr, cr, ld, b, head, q, s, g, scale, fl);
     }
     if (p.E < p.N) freq_flush<false>(fl, p.fpart);
 }
@@ -1237,38 +1316,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
             dv[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
         ATT_T(2);
-        // No masks in the loop (see the dq kernel): padding queries have zero rows in both images and finite statistics (0).
-        // steps of 32 queries (see the dq kernel)
-        for (int q0 = 0; q0 < npad; q0 += 32) {
-            f32x4_t sacc[4], dpacc[4];
-            rows_times_frag_pad_n<T, 2>(sacc, qimg + q0 * AT<T>::TRB, s, g, kf);
-            PHASE_FENCE();
-            rows_times_frag_pad_n<T, 2>(dpacc, doimg + q0 * AT<T>::TRB, s, g, vf);
-            PHASE_FENCE();
-            float pr[4][4], ds[4][4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if (t < 2) {
-                    const float4 l4 = *reinterpret_cast<const float4*>(lse_s + q0 + t * 16 + 4 * g);
-                    const float4 d4 = *reinterpret_cast<const float4*>(del_s + q0 + t * 16 + 4 * g);
-                    const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float pp = RowExp<T>::clamped(sacc[t][r], lv[r]);
-                        pr[t][r] = pp;
-                        ds[t][r] = pp * (dpacc[t][r] - dvv[r]);
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pr[t][r] = ds[t][r] = 0.f;
-                }
-            }
-            PHASE_FENCE();
-            imgT_times_regs_n<T, 2>(dv, doimg + q0 * AT<T>::TRB, s, g, pr);
-            PHASE_FENCE();
-            imgT_times_regs_n<T, 2>(dk, qimg + q0 * AT<T>::TRB, s, g, ds);
-            PHASE_FENCE();
-        }
+        dkv_res_loop<T>(dk, dv, qimg, doimg, lse_s, del_s, npad, s, g, kf, vf);
         ATT_T(3);
         dkv_epilogue<T, 64, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
         ATT_T(4);
@@ -1282,6 +1330,148 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #ifdef ATT_STAMP
 extern "C" int lnx_dbg_attn_stamps(unsigned long long* out8) { return (int)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_att_stamp), 64); }
 #endif
+
+// The whole resident backward of a (sample, head) in ONE workgroup, N <= 224: Q~, K~, V and dO are staged once (four padded-pitch
+// images, 4 npad 160 bytes <= 140 KiB) and serve both phases, where the pair above stages two of them per kernel and fetches the other
+// two per wave tile from global memory -- every operand read twice, two staging round trips, one fragment round trip per tile and
+// `delta` through HBM.  One 16-row tile per wave per phase: NW = 4 for N <= 64, NW = 16 beyond.
+//   delta   of every query first: q~ / dO fragments from the images (the bits Chunk::value gave the pair: the images hold exactly
+//           those), O -- needed for delta only -- requested beside the staging loads; to LDS and to p.delta; one barrier
+//   phase B (queries on the lane: attn_bwd_dq_res_kernel's body)   dq of the wave's query tile
+//   phase A (keys on the lane: attn_bwd_dkv_res_kernel's body)     dk, dv of the wave's key tile; k~ / v fragments from the images
+// No barrier between B and A.  The loops and epilogues are the pair's (dq_res_loop, dq_res_epilogue, dkv_res_loop, dkv_epilogue), so
+// dqkv and delta are bit-equal to the pair's.  The freqs gradient is one LDS accumulator over both phases, published once
+// (per_bh = 1 as for the pair).
+// Image rows: the fragment reads take rows < 16 ntiles <= npad (N rounded up to 32), the loops rows < npad.  A wave whose tile lies
+// beyond the sequence (N = 199: waves 13..15 for queries) stages, skips that phase and meets every barrier.
+// Measured and not kept (stage-3 shape, B 256, N 199, 6 heads; the pair: 177-183 us): the phases behind one another with a barrier
+// between them and no tile rotation, 162-168 us; that form as a persistent kernel (one workgroup per CU) that touches the next (sample,
+// head)'s lines during phase A so that its staging finds them in L2, 170 us -- and holding the next problem's chunks in registers
+// across a phase or an epilogue instead spills (116-174 registers).
+template <typename T> constexpr size_t res_bwd_fused_lds(int npad, int qtiles) { return (size_t)npad * (4 * AT<T>::TRB) + (size_t)qtiles * BT * 2 * sizeof(float); }
+
+template <typename T, int NW = 16, bool ROT = false>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_res_kernel(const AttnP p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int HD = 64;  // the resident kernels carry head_dim 64 only
+#ifdef ATT_STAMP
+    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
+#endif
+    constexpr int UN = 2;   // staging chunks per thread and operand: 8 npad <= 2 * 64 NW chunks (npad <= 64 at NW = 4, <= 256 at NW = 16)
+    const int nqt = (p.N + BT - 1) / BT;
+    const int npad = (p.N + 31) & ~31;
+    unsigned char* qimg = smem;  // res_bwd_fused_lds<T>(npad, nqt) bytes in all
+    unsigned char* kimg = qimg + npad * AT<T>::TRB;
+    unsigned char* vimg = kimg + npad * AT<T>::TRB;
+    unsigned char* doimg = vimg + npad * AT<T>::TRB;
+    float* lse_s = reinterpret_cast<float*>(doimg + npad * AT<T>::TRB);
+    float* del_s = lse_s + nqt * BT;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = lane & 15, g = lane >> 4;
+    const int head = blockIdx.x % p.heads, b = blockIdx.x / p.heads;
+    const int C = p.heads * HD;
+    const int64_t ld = 3 * C;
+    const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
+    const T* kb = qb + C;
+    const T* vb = qb + 2 * C;
+    const T* dob = reinterpret_cast<const T*>(p.d_o) + (int64_t)b * p.N * C + head * HD;
+    const T* ob = reinterpret_cast<const T*>(p.o) + (int64_t)b * p.N * C + head * HD;
+    const float scale = 0.125f;
+    const int64_t statbase = ((int64_t)b * p.heads + head) * p.N;
+    __shared__ float fl[64];  // freqs-gradient partial of this (sample, head), both phases
+    if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
+    const int row = wave * 16 + s;  // the lane's query (delta, phase B)
+    const int ntiles = (p.N + 15) / 16;
+    const bool tile = wave < ntiles;
+    Chunk<T, false> co[AT<T>::NKK];
+    {
+        // one memory round trip: every load of the four operands, the statistics and this wave's O fragment before the first wait
+        const int total = npad * AT<T>::NCH, i0 = threadIdx.x;
+        StageBatch<T, true, ROT, UN> sq, sk;
+        StageBatch<T, false, false, UN> sv, sdo;
+        sq.fetch(qb, ld, i0, total, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
+        sk.fetch(kb, ld, i0, total, p.N, p.E, p.cos_tab, p.heads, head, p.sin_tab);
+        sv.fetch(vb, ld, i0, total, p.N, p.E, nullptr, p.heads, head);
+        sdo.fetch(dob, C, i0, total, p.N, p.E, nullptr, p.heads, head);
+        const float l = p.lse[statbase + min(i0, p.N - 1)];  // nqt * BT <= 64 NW: one statistic slot per thread at the most
+#pragma unroll
+        for (int kk = 0; kk < AT<T>::NKK; ++kk) co[kk].fetch(ob, C, row, p.N, p.E, (kk * 4 + g) * AT<T>::EPV, nullptr, p.heads, head);
+        sq.template commit<false, true>(nullptr, qimg, i0, total, p.N, p.E, scale);
+        sk.template commit<false, true>(nullptr, kimg, i0, total, p.N, p.E, 1.0f);
+        sv.template commit<false, true>(nullptr, vimg, i0, total, p.N, p.E, 1.0f);
+        sdo.template commit<false, true>(nullptr, doimg, i0, total, p.N, p.E, 1.0f);
+        if (i0 < nqt * BT) {
+            lse_s[i0] = RowExp<T>::prep(i0 < p.N ? l : 0.f);
+            del_s[i0] = 0.f;  // phase B fills the real queries' slots
+        }
+    }
+    ATT_T(0);
+    __syncthreads();
+    ATT_T(1);
+    // delta of every query first (cheap: two fragment reads and the O fragment), so that one barrier serves both phases and a wave
+    // walks from its dq tile into its dk / dv tile without waiting for the others
+    uint4 qf[AT<T>::NKK], dof[AT<T>::NKK];
+    float delta = 0.f;
+    if (tile) {
+        uint4 of[AT<T>::NKK];
+#pragma unroll
+        for (int kk = 0; kk < AT<T>::NKK; ++kk) {  // (s, g) <- row, chunk kk * 4 + g: load_row_frag's mapping
+            qf[kk] = ld16(qimg + row * AT<T>::TRB + ((kk * 4 + g) << 4));
+            dof[kk] = ld16(doimg + row * AT<T>::TRB + ((kk * 4 + g) << 4));
+            of[kk] = co[kk].value(row, p.N, p.E, 1.0f);
+        }
+        delta = delta_of_row<T>(dof, of);
+        if (row < p.N && g == 0) {
+            p.delta[statbase + row] = delta;
+            del_s[row] = delta;
+        }
+    }
+    ATT_T(2);
+    __syncthreads();  // del_s complete
+    ATT_T(3);
+    if (tile) {  // ---- phase B: query tile `wave`
+        const int q = row, qc = min(q, p.N - 1);
+        float qr[4][4], cr[4][2];
+        dq_res_prefetch<T, ROT>(qr, cr, p, qb, ld, qc, head, g);
+        const float lse = lse_s[q];
+        f32x4_t dq[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dq[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        dq_res_loop<T>(dq, kimg, vimg, npad, s, g, qf, dof, lse, delta);
+        ATT_T(4);
+        dq_res_epilogue<T, ROT>(p, dq, qr, cr, ld, b, head, q, s, g, scale, fl);
+        ATT_T(5);
+    }
+    // ---- phase A: key tile (wave - ntiles % 4) mod NW.  Both loops keep their SIMD busy (the waves of a SIMD finish one after the
+    // other, not together), so what counts is the tiles per SIMD over BOTH phases: with 13 tiles on 16 waves (wave w on SIMD w % 4)
+    // SIMD 0 walks a fourth dq tile, and the rotation hands the fourth dk / dv tile to SIMD 1 -- 7, 7, 6, 6 instead of 8, 6, 6, 6.
+    const int ktile = (wave + NW - ntiles % 4) % NW;
+    if (ktile < ntiles) {
+        const int key = ktile * 16 + s;
+        uint4 kf[AT<T>::NKK], vf[AT<T>::NKK];
+#pragma unroll
+        for (int kk = 0; kk < AT<T>::NKK; ++kk) {
+            kf[kk] = ld16(kimg + key * AT<T>::TRB + ((kk * 4 + g) << 4));
+            vf[kk] = ld16(vimg + key * AT<T>::TRB + ((kk * 4 + g) << 4));
+        }
+        f32x4_t dk[4], dv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            dk[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            dv[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+        dkv_res_loop<T>(dk, dv, qimg, doimg, lse_s, del_s, npad, s, g, kf, vf);
+        ATT_T(6);
+        dkv_epilogue<T, 64, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
+        ATT_T(7);
+    }
+    if (p.E < p.N) freq_flush<false>(fl, p.fpart);
+#ifdef ATT_STAMP
+    if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0)
+        for (int i = 0; i < 8; ++i) g_att_stamp[i] = tsum[i];
+#endif
+}
 
 // ---------------------------------------------------------------------------------
 // cos table and its backward to the learnable freqs
@@ -1524,13 +1714,25 @@ int attn_fwd_res(AttnP& p, int family, hipStream_t st) {
     });
 }
 
+// Backward: N <= 224 runs attn_bwd_res_kernel (one launch: 4 waves for LNX_ATTN_KERNEL_RES4, 16 for RES8 -- the family names the
+// forward's waves); 225..256, where four images no longer fit the 160 KiB of LDS, and any N with LNX_ATTN_BWD_SPLIT in the
+// environment (read per call: the A/B switch) run the dq / dk-dv pair.  g_last_bwd_launches: what lnx_last_attn_bwd_launches reports.
+constexpr int RES_BWD_FUSED_NMAX = 224;
+std::atomic<int> g_last_bwd_launches{0};
+
 template <bool ROT>
 int attn_bwd_res(AttnP& p, int family, hipStream_t st, int& per_bh) {
     typedef bf16_t T;
+    const int npad = (p.N + 31) & ~31, bh = p.B * p.heads;
+    per_bh = 1;
+    if (p.N <= RES_BWD_FUSED_NMAX && getenv("LNX_ATTN_BWD_SPLIT") == nullptr) {
+        g_last_bwd_launches.store(1, std::memory_order_relaxed);
+        const size_t lds = res_bwd_fused_lds<T>(npad, p.qtiles);
+        if (family == LNX_ATTN_KERNEL_RES4) return attn_launch<attn_bwd_res_kernel<T, 4, ROT>>(bh, 64 * 4, lds, res_bwd_fused_lds<T>(64, 1), st, p);
+        return attn_launch<attn_bwd_res_kernel<T, 16, ROT>>(bh, 64 * 16, lds, res_bwd_fused_lds<T>(RES_BWD_FUSED_NMAX, cdiv(RES_BWD_FUSED_NMAX, BT)), st, p);
+    }
     return res_variant(family, [&](auto nwc, int nmax) {
         constexpr int NW = decltype(nwc)::value;
-        const int npad = (p.N + 31) & ~31, bh = p.B * p.heads;
-        per_bh = 1;
         if (int rc = attn_launch<attn_bwd_dq_res_kernel<T, NW, ROT>>(bh, 64 * NW, res_bwd_dq_lds<T>(npad), res_bwd_dq_lds<T>(nmax), st, p)) return rc;
         return attn_launch<attn_bwd_dkv_res_kernel<T, NW, ROT>>(bh, 64 * NW, res_bwd_dkv_lds<T>(npad, p.qtiles), res_bwd_dkv_lds<T>(nmax, nmax / BT), st, p);
     });
@@ -1659,6 +1861,7 @@ int attn_bwd_launch(const lnx_attn_bwd_args* a, void* stream) {
     if (ROT) p.W = a->grid_w > 0 ? a->grid_w : 1;
     p.d_o = a->d_o; p.dqkv = a->dqkv; p.fpart = a->freq_ws; p.dsin = cos_or_stub(a->dsin_tab, a->qkv); p.delta = a->delta;
     int per_bh = 0;
+    g_last_bwd_launches.store(2, std::memory_order_relaxed);  // every path but the one-kernel resident backward
     const int rc = is_resident(family) ? attn_bwd_res<ROT>(p, family, st, per_bh) : with_type_hd(a->dtype, hd, [&](auto tc, auto hdc) {
         return attn_bwd_tiled<typename decltype(tc)::type, decltype(hdc)::value, ROT>(p, family, st, per_bh);
     });
@@ -1697,6 +1900,8 @@ extern "C" int lnx_attn_dispatch(int dtype, int N, int head_dim, int has_drop_ma
 }
 
 extern "C" int lnx_last_attn_kernel(void) { return g_last_attn.load(std::memory_order_relaxed); }
+
+extern "C" int lnx_last_attn_bwd_launches(void) { return g_last_bwd_launches.load(std::memory_order_relaxed); }
 
 extern "C" int lnx_attn_bwd_flush(void* stream) { return freq_flush((hipStream_t)stream); }
 

@@ -298,7 +298,9 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmP& p, f32x4_t (&acc
     if (F & F_RES) {
         // row scale (DropPath): rows of a 64-row sub-tile span at most two samples when rows_per_sample >= 64
         const bool scaled = p.rowscale != nullptr;
-        const int q0 = scaled ? mrow0 / p.rows_per_sample : 0;
+        // (a sub-tile that starts at or beyond M -- the lower half of a ragged last row tile -- stores nothing but still loads: its
+        // sample index is clamped like its rows, or q0 is one past the last entry of rowscale when M is a whole number of samples)
+        const int q0 = scaled ? min(mrow0, p.M - 1) / p.rows_per_sample : 0;
         const int edge = (q0 + 1) * p.rows_per_sample;
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {

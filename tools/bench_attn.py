@@ -1,6 +1,7 @@
 """Attention forward / backward at the mFormerV1_sm stage-3 / stage-4 shapes (B = 256) and the lg @384 stage-3 shape (B = 64, N = 580,
-the tiled kernels); run it under `rocprofv3 --kernel-trace --stats` for per-kernel times (the backward is two kernels + the freqs-gradient
-reduce).
+the tiled kernels); run it under `rocprofv3 --kernel-trace --stats` for per-kernel times (the backward is one kernel or two + the
+freqs-gradient reduce).  Where the resident backward runs as one kernel (`lnx_last_attn_bwd_launches() == 1`), the dq / dk-dv pair
+is timed beside it in the same process (`bwd/pair`: LNX_ATTN_BWD_SPLIT set for those calls, the rounds of the two interleaved).
 
     python tools/bench_attn.py [--rope-mode cos|rotate|both] [--rounds R]
 
@@ -16,6 +17,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from linnaeus_amd import _lib as L
 from linnaeus_amd import ops
 
 ap = argparse.ArgumentParser()
@@ -53,19 +55,44 @@ for B, H, W, E, heads in ((256, 14, 14, 3, 6), (256, 7, 7, 3, 12), (64, 24, 24, 
             def bwd():
                 ops.attn_bwd(qkv, cos, o, lse, do, dqkv, delta, B, N, E, heads, dfreqs=dfreqs, sin_tab=sin, grid_w=W)
 
-        for name, fn, fl in (("fwd", fwd, 4.0), ("bwd", bwd, 14.0)):
-            for _ in range(3):
-                fn()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(args.rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(20):
+        def rounds(fns):
+            """median and spread of R rounds of 20 calls of every fn, the rounds of the fns taking turns"""
+            for fn in fns:
+                for _ in range(3):
                     fn()
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1) / 20 * 1e-3)
-            t = statistics.median(ts)
-            print(f"N={N} heads={heads} {mode:6s} {name}: {t * 1e6:7.1f} us  spread {100 * (max(ts) - min(ts)) / t:4.1f} %  "
+            torch.cuda.synchronize()
+            ts = [[] for _ in fns]
+            for _ in range(args.rounds):
+                for fn, t in zip(fns, ts):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(20):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    t.append(e0.elapsed_time(e1) / 20 * 1e-3)
+            return [(statistics.median(t), (max(t) - min(t)) / statistics.median(t)) for t in ts]
+
+        def bwd_pair():
+            os.environ["LNX_ATTN_BWD_SPLIT"] = "1"  # read per call
+            try:
+                bwd()
+            finally:
+                del os.environ["LNX_ATTN_BWD_SPLIT"]
+
+        def show(name, t, spread, fl):
+            print(f"N={N} heads={heads} {mode:6s} {name}: {t * 1e6:7.1f} us  spread {100 * spread:4.1f} %  "
                   f"{fl * B * heads * N * N * 64 / t / 1e12:6.1f} TFLOP/s", flush=True)
+
+        (t, sp), = rounds([fwd])
+        show("fwd", t, sp, 4.0)
+        bwd()
+        one_kernel = hasattr(L.lib(), "lnx_last_attn_bwd_launches") and L.lib().lnx_last_attn_bwd_launches() == 1
+        if one_kernel:
+            (t, sp), (t2, sp2) = rounds([bwd, bwd_pair])
+            show("bwd", t, sp, 14.0)
+            show("bwd/pair", t2, sp2, 14.0)
+            print(f"    one kernel against the pair: {(t2 - t) * 1e6:+.1f} us ({100 * (t2 - t) / t2:+.1f} %); larger spread {100 * max(sp, sp2):.1f} %", flush=True)
+        else:
+            (t, sp), = rounds([bwd])
+            show("bwd", t, sp, 14.0)
