@@ -86,6 +86,40 @@ __device__ __forceinline__ void sched_draw(uint32_t& result, unsigned* ctr) {
                  : "=&v"(result), "=&s"(save) : "v"(ctr), "v"(one) : "memory");
 #endif
 }
+// The rest of the protocol of the kernels that count for themselves (gemm_nt_v7, gemm_nt_v9).  Wave 0 fetches the tile AFTER next with
+// one lane (sched_draw: global_atomic_add with return, issued in iteration 0 in front of the LDS-DMA pieces and counted like any other
+// extra of the in-order counter), publishes it through one LDS dword (sched_publish) in the first iteration whose counted wait has
+// retired the draw, and every wave reads the dword in the iteration after that -- iterations before the first use (the ring refill of
+// the tile's last K iterations).  The fetch that returns the range's last index is the last one the counter will see in this launch:
+// that workgroup zeroes it for the next launch (sched_last_draw, sched_reset).
+// EVERY tile is drawn, the first one too (0.6 us of L2 round trip per launch): a workgroup that starts late -- its CU was held by a
+// collective kernel -- then owes nothing.  sched_first_draw is that draw, made by the whole workgroup: wave 0 draws and publishes,
+// barrier, everyone reads, barrier (everyone has read the slot before iteration 1 of the first tile may overwrite it).  It returns
+// the position drawn.
+__device__ __forceinline__ int sched_first_draw(unsigned* ctr, uint32_t slot_addr, int wave) {
+    uint32_t seen = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (wave == 0) {
+        const uint32_t one = 1u;
+        uint32_t first;
+        uint64_t save;
+        asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, 1\n\tglobal_atomic_add %0, %2, %3, off sc0\n\ts_waitcnt vmcnt(0)\n\tds_write_b32 %4, %0\n\ts_mov_b64 exec, %1\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(first), "=&s"(save) : "v"(ctr), "v"(one), "v"(slot_addr) : "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(seen) : "v"(slot_addr) : "memory");
+#endif
+    const int pos = __builtin_amdgcn_readfirstlane((int)seen);
+    __builtin_amdgcn_s_barrier();
+    return pos;
+}
+// wave 0 hands the answer of its sched_draw (which a counted wait has retired) to the other waves
+__device__ __forceinline__ void sched_publish(uint32_t slot_addr, uint32_t fetched) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t save;
+    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_write_b32 %1, %2\n\ts_mov_b64 exec, %0" : "=&s"(save) : "v"(slot_addr), "v"(fetched) : "memory");
+#endif
+}
 __device__ __forceinline__ void sched_reset(unsigned* ctr) { __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // A launch of `grid` workgroups splits its n tiles into nx = min(8, grid) contiguous parts, one per XCD (part = blockIdx.x % nx:
 // round-robin dispatch; fewer than 8 workgroups = fewer parts, so that no part is left without a worker).  TileShare: this
@@ -103,6 +137,17 @@ __device__ __forceinline__ TileShare tile_share(int n) {
     t.cnt = q + (t.part < r ? 1 : 0);
     t.base = t.part < r ? t.part * (q + 1) : r * (q + 1) + (t.part - r) * q;
     return t;
+}
+// Draws per part and launch: one per tile + one failed draw per workgroup, so the draw that returns cnt + workers - 1 is the last the
+// counter sees in this launch: the workgroup that drew it zeroes the counter (sched_reset) on its way out.
+__device__ __forceinline__ bool sched_last_draw(const TileShare& t, int pos) { return pos == t.cnt + t.workers - 1; }
+// logical tile index (row-major over the launch's tiles_n column tiles of BM x BN) -> first row / column of the tile
+template <int BM, int BN>
+__device__ __forceinline__ void tile_origin(int logical, int tiles_n, int& m0, int& n0) {
+    const int tn = logical % tiles_n;
+    const int tm = logical / tiles_n;
+    n0 = tn * BN;
+    m0 = tm * BM;
 }
 
 // host side (api.cpp)

@@ -31,11 +31,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmP p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int s = lane & 15, g = lane >> 4;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int logical = xcd_remap(blockIdx.x, nwg);
-    const int tn = logical % p.tiles_n;
-    const int tm = logical / p.tiles_n;
-    const int m0 = tm * TILE, n0 = tn * TILE;
+    int m0, n0;
+    one_shot_origin<TILE, TILE>(p, m0, n0);
 
     // ---- global -> register staging: 4 x 16B chunks per operand per thread ----
     int ld_row[4], ld_ch[4];

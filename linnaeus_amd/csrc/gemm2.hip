@@ -20,27 +20,13 @@
 
 namespace lnxg {
 
-// four 16-byte fragment reads at rows +0, +4, +8, +12 (byte offsets 0/512/1024/1536) from one address
-#define DS_READ4(dst, addr)                                                                              \
-    do {                                                                                                 \
-        const uint32_t a_ = (addr);                                                                      \
-        asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(a_) : "memory");                         \
-        asm volatile("ds_read_b128 %0, %1 offset:512" : "=v"(dst[1]) : "v"(a_) : "memory");              \
-        asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(dst[2]) : "v"(a_) : "memory");             \
-        asm volatile("ds_read_b128 %0, %1 offset:1536" : "=v"(dst[3]) : "v"(a_) : "memory");             \
-    } while (0)
-
-constexpr int BM2 = 256, BN2 = 128;
-constexpr int STAGE_BYTES = (BM2 + BN2) * ROWB;  // 48 KiB
-constexpr int NSTAGE = 3;
-constexpr int LD_PER_WAVE = (BM2 + BN2) / 8 / 8;  // 1 KiB wave-instructions per wave per stage = 6
-
 // F = feature set of a specialised epilogue (gemm_common.hpp) or F_GENERIC
 template <bool OUT_F32, bool PATCH, int F>
 __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
     typedef bf16_t T;
-    constexpr int BK = 64;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [NSTAGE][A 256 rows | W 128 rows][128 B]
+    typedef NarrowRing R;
+    constexpr int BK = R::BK;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [R::NST][A 256 rows | W 128 rows][128 B]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -48,30 +34,27 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int s = lane & 15, g = lane >> 4;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int logical = xcd_remap(blockIdx.x, nwg);
-    const int tn = logical % p.tiles_n;
-    const int tm = logical / p.tiles_n;
-    const int m0 = tm * BM2, n0 = tn * BN2;
+    int m0, n0;
+    one_shot_origin<R::BM, R::BN>(p, m0, n0);
 
     // ---- LDS-DMA source addresses: wave w issues wave-instructions i = w + 8 j (j < 6); instruction
     // i fills LDS rows 8i..8i+7 of the stage (rows 0..255 = A, 256..383 = W), lane -> (row l>>3, slot l&7)
-    const unsigned char* src[LD_PER_WAVE];
+    const unsigned char* src[R::PIECES];
 #pragma unroll
-    for (int j = 0; j < LD_PER_WAVE; ++j) {
+    for (int j = 0; j < R::PIECES; ++j) {
         const int i = wave + 8 * j;
-        const int row = 8 * i + (lane >> 3);
-        const int slot = lane & 7;
-        if (row < BM2) {
-            const int chunk = slot ^ row_key(row);
+        const int row = R::ROWS_PER_PIECE * i + (lane >> R::CHUNK_SHIFT);
+        const int slot = lane & (R::CHUNKS - 1);
+        if (row < R::BM) {
+            const int chunk = slot ^ R::key(row);
             int m = m0 + row;
             if (m >= p.M) m = p.M - 1;
             const int64_t base = PATCH ? patch_base(p.pg, m) : (int64_t)m * p.lda;
             // PATCH2: a 16-byte chunk never straddles a (kh) segment because 2*Cin % 8 == 0
             src[j] = p.A + (base + chunk * 8) * 2;
         } else {
-            const int wr = row - BM2;
-            const int chunk = slot ^ row_key(wr);
+            const int wr = row - R::BM;
+            const int chunk = slot ^ R::key(wr);
             int n = n0 + wr;
             if (n >= p.N) n = p.N - 1;
             src[j] = p.W + ((int64_t)n * p.ldw + chunk * 8) * 2;
@@ -80,31 +63,31 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
     auto issue_tile = [&](int kt, int stage) {
         const int k0 = kt * BK;
 #pragma unroll
-        for (int j = 0; j < LD_PER_WAVE; ++j) {
+        for (int j = 0; j < R::PIECES; ++j) {
             const int i = wave + 8 * j;
             const unsigned char* gp = src[j];
-            if (PATCH && 8 * i < BM2) {
+            if (PATCH && R::ROWS_PER_PIECE * i < R::BM) {
                 // element offset k -> patch_col(k): add the row jump of the (kh) segment this chunk is in
-                const int slot = lane & 7;
-                const int row = 8 * i + (lane >> 3);
-                const int kk = k0 + ((slot ^ row_key(row)) * 8);
-                gp = src[j] + (patch_col(p.pg, kk) - ((slot ^ row_key(row)) * 8)) * 2;
+                const int slot = lane & (R::CHUNKS - 1);
+                const int row = R::ROWS_PER_PIECE * i + (lane >> R::CHUNK_SHIFT);
+                const int kk = k0 + ((slot ^ R::key(row)) * 8);
+                gp = src[j] + (patch_col(p.pg, kk) - ((slot ^ R::key(row)) * 8)) * 2;
             } else {
                 gp += (int64_t)k0 * 2;
             }
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
-                                             (__attribute__((address_space(3))) void*)(smem + stage * STAGE_BYTES + i * 1024), 16, 0, 0);
+                                             (__attribute__((address_space(3))) void*)(smem + stage * R::STAGE + i * 1024), 16, 0, 0);
         }
     };
 
     const int frag_row = (s >> 2) * 16 + (s & 3);
     const int frag_key = ((s >> 1) & 1) | ((s >> 2) << 1);
     const int a_row0 = wm * 64 + frag_row;
-    const int w_row0 = BM2 + wn * 64 + frag_row;
+    const int w_row0 = R::BM + wn * 64 + frag_row;
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const uint32_t ch0 = (uint32_t)((g ^ frag_key) << 4), ch1 = (uint32_t)(((g + 4) ^ frag_key) << 4);
-    const uint32_t a_off0 = a_row0 * ROWB + ch0, a_off1 = a_row0 * ROWB + ch1;
-    const uint32_t w_off0 = w_row0 * ROWB + ch0, w_off1 = w_row0 * ROWB + ch1;
+    const uint32_t a_off0 = a_row0 * R::ROWBYTES + ch0, a_off1 = a_row0 * R::ROWBYTES + ch1;
+    const uint32_t w_off0 = w_row0 * R::ROWBYTES + ch0, w_off1 = w_row0 * R::ROWBYTES + ch1;
 
     f32x4_t acc[4][4];
 #pragma unroll
@@ -130,14 +113,14 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
     __builtin_amdgcn_s_barrier();
     if (grp) __builtin_amdgcn_s_barrier();
     for (int kt = 0; kt < nk; ++kt) {
-        const uint32_t st = lds_base + (kt % NSTAGE) * STAGE_BYTES;
+        const uint32_t st = lds_base + (kt % R::NST) * R::STAGE;
         uint4 wf0[4], af0[4], wf1[4], af1[4];
-        DS_READ4(wf0, st + w_off0);
-        DS_READ4(af0, st + a_off0);
-        DS_READ4(wf1, st + w_off1);
-        DS_READ4(af1, st + a_off1);
+        lds_read4<R::ROWBYTES>(wf0, st + w_off0);
+        lds_read4<R::ROWBYTES>(af0, st + a_off0);
+        lds_read4<R::ROWBYTES>(wf1, st + w_off1);
+        lds_read4<R::ROWBYTES>(af1, st + a_off1);
         if (kt + 2 < nk) {
-            issue_tile(kt + 2, (kt + 2) % NSTAGE);
+            issue_tile(kt + 2, (kt + 2) % R::NST);
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -146,14 +129,8 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi) Mfma<T>::run(acc[ni][mi], wf0[ni], af0[mi]);
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi) Mfma<T>::run(acc[ni][mi], wf1[ni], af1[mi]);
+        mfma_4x4<T>(acc, wf0, af0);
+        mfma_4x4<T>(acc, wf1, af1);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         if (!(grp && kt + 1 == nk)) __builtin_amdgcn_s_barrier();
@@ -171,25 +148,11 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
 // 64-byte rows keep global chunk c at slot c ^ key, key = 3 * bit4(row): with it the permuted fragment rows
 // {0..3,16..19,32..35,48..51}+4i of every 16-lane group of a ds_read_b128 fall on 16 distinct 16-byte bank slots.
 // ------------------------------------------------------------------------------------
-#define DS4_READ4(dst, addr)                                                                            \
-    do {                                                                                                \
-        const uint32_t a_ = (addr);                                                                     \
-        asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(a_) : "memory");                        \
-        asm volatile("ds_read_b128 %0, %1 offset:256" : "=v"(dst[1]) : "v"(a_) : "memory");             \
-        asm volatile("ds_read_b128 %0, %1 offset:512" : "=v"(dst[2]) : "v"(a_) : "memory");             \
-        asm volatile("ds_read_b128 %0, %1 offset:768" : "=v"(dst[3]) : "v"(a_) : "memory");             \
-    } while (0)
-
-constexpr int STAGE4 = (BM4 + BN4) * ROWB4;   // 32 KiB
-constexpr int NST4 = 4;
-constexpr int PIECES4 = STAGE4 / 1024 / 8;    // 1-KiB LDS-DMA instructions per wave per stage = 4
-
-__device__ __forceinline__ int key4r(int row) { return (row & 16) ? 3 : 0; }
-
 template <bool OUT_F32, int F>
 __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
     typedef bf16_t T;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [NST4][A 256 rows | W 256 rows][64 B]
+    typedef WideRing R;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [R::NST][A 256 rows | W 256 rows][64 B]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -197,27 +160,24 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
     const int wm = wave & 1, wn = wave >> 1;  // waves 0-3 / 4-7 (the ping-pong groups) cover the column halves
     const int s = lane & 15, g = lane >> 4;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int logical = xcd_remap(blockIdx.x, nwg);
-    const int tn = logical % p.tiles_n;
-    const int tm = logical / p.tiles_n;
-    const int m0 = tm * BM4, n0 = tn * BN4;
+    int m0, n0;
+    one_shot_origin<R::BM, R::BN>(p, m0, n0);
 
     // piece i (32 per stage) fills LDS rows 16 i .. 16 i + 15 (rows 0..255 = A, 256..511 = W); wave w issues i = w + 8 j
-    const unsigned char* src[PIECES4];
+    const unsigned char* src[R::PIECES];
 #pragma unroll
-    for (int j = 0; j < PIECES4; ++j) {
+    for (int j = 0; j < R::PIECES; ++j) {
         const int i = wave + 8 * j;
-        const int row = 16 * i + (lane >> 2);
-        const int slot = lane & 3;
-        if (row < BM4) {
-            const int chunk = slot ^ key4r(row);
+        const int row = R::ROWS_PER_PIECE * i + (lane >> R::CHUNK_SHIFT);
+        const int slot = lane & (R::CHUNKS - 1);
+        if (row < R::BM) {
+            const int chunk = slot ^ R::key(row);
             int m = m0 + row;
             if (m >= p.M) m = p.M - 1;
             src[j] = p.A + ((int64_t)m * p.lda + chunk * 8) * 2;
         } else {
-            const int wr = row - BM4;
-            const int chunk = slot ^ key4r(wr);
+            const int wr = row - R::BM;
+            const int chunk = slot ^ R::key(wr);
             int n = n0 + wr;
             if (n >= p.N) n = p.N - 1;
             src[j] = p.W + ((int64_t)n * p.ldw + chunk * 8) * 2;
@@ -225,18 +185,18 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
     }
     auto issue_stage = [&](int kt, int stage) {
 #pragma unroll
-        for (int j = 0; j < PIECES4; ++j) {
+        for (int j = 0; j < R::PIECES; ++j) {
             const int i = wave + 8 * j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (int64_t)kt * BK4 * 2),
-                                             (__attribute__((address_space(3))) void*)(smem + stage * STAGE4 + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (int64_t)kt * R::BK * 2),
+                                             (__attribute__((address_space(3))) void*)(smem + stage * R::STAGE + i * 1024), 16, 0, 0);
         }
     };
 
     const int frag_row = (s >> 2) * 16 + (s & 3);
     const uint32_t chunk_off = (uint32_t)((g ^ (((s >> 2) & 1) * 3)) << 4);  // key of every row this lane reads = 3 * bit0(s >> 2)
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    const uint32_t a_off = (uint32_t)((wm * 128 + frag_row) * ROWB4) + chunk_off;
-    const uint32_t w_off = (uint32_t)((BM4 + wn * 64 + frag_row) * ROWB4) + chunk_off;
+    const uint32_t a_off = (uint32_t)((wm * 128 + frag_row) * R::ROWBYTES) + chunk_off;
+    const uint32_t w_off = (uint32_t)((R::BM + wn * 64 + frag_row) * R::ROWBYTES) + chunk_off;
 
     f32x4_t acc0[4][4], acc1[4][4];  // rows 0..63 / 64..127 of the wave tile
 #pragma unroll
@@ -247,7 +207,7 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
             acc1[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
 
-    const int nk = p.K / BK4;  // >= 4
+    const int nk = p.K / R::BK;  // >= 4
     issue_stage(0, 0);
     issue_stage(1, 1);
     issue_stage(2, 2);
@@ -256,15 +216,15 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
     __builtin_amdgcn_s_barrier();
     if (grp) __builtin_amdgcn_s_barrier();
     for (int kt = 0; kt < nk; ++kt) {
-        const uint32_t st = lds_base + (kt % NST4) * STAGE4;
+        const uint32_t st = lds_base + (kt % R::NST) * R::STAGE;
         uint4 wf[4], af0[4], af1[4];
-        DS4_READ4(wf, st + w_off);
-        DS4_READ4(af0, st + a_off);
-        DS4_READ4(af1, st + a_off + 64 * ROWB4);
+        lds_read4<R::ROWBYTES>(wf, st + w_off);
+        lds_read4<R::ROWBYTES>(af0, st + a_off);
+        lds_read4<R::ROWBYTES>(af1, st + a_off + 64 * R::ROWBYTES);
         // end of memory phase kt: own pieces of slice kt+1 landed, fragment reads of slice kt done; the slot refilled
         // in memory phase kt+1 (slice kt+4) is the one read in phase kt
         if (kt + 3 < nk) {
-            issue_stage(kt + 3, (kt + 3) % NST4);
+            issue_stage(kt + 3, (kt + 3) % R::NST);
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         } else if (kt + 2 < nk) {
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -275,6 +235,7 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
+        // (two mfma_4x4 written out: called from this loop, the helper gives this kernel another register allocation)
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
@@ -296,31 +257,29 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
     }
 }
 
-// The forms each family is compiled for (with_nt_form launches nothing else).  The 256x256 kernel has no generic epilogue; the
-// 256x128 kernel carries it for both output types, and is the only one that gathers 2x2 patches on the A side.
-constexpr bool nt_v4_carries(bool out_f32, int f) {
-    if (out_f32) return f == (F_BIAS | F_RES);
-    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == (F_BIAS | F_GELU) || f == F_GELU_BWD;
-}
+// The forms the 256x128 kernel is compiled for (with_nt_form launches nothing else): those of the 256x256 family (nt_v4_carries,
+// gemm_common.hpp) and the generic epilogue for both output types; it is the only one that gathers 2x2 patches on the A side.
 constexpr bool nt_v2_carries(bool out_f32, int f) { return f == F_GENERIC || nt_v4_carries(out_f32, f); }
 
 int launch_nt_v4(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
+    typedef WideRing R;
     GemmP p = p0;
-    p.tiles_m = cdiv(p.M, BM4);
-    p.tiles_n = p.N / BN4;
+    p.tiles_m = cdiv(p.M, R::BM);
+    p.tiles_n = p.N / R::BN;
     const int grid = p.tiles_m * p.tiles_n;
     return with_nt_form<nt_v4_carries>("gemm_nt_v4", out_f32, f, [&](auto form) {
         using Form = decltype(form);
-        return launch_with_lds<gemm_nt_v4_kernel<Form::out_f32, Form::f>>(grid, 512, NST4 * STAGE4, st, p);
+        return launch_with_lds<gemm_nt_v4_kernel<Form::out_f32, Form::f>>(grid, 512, R::NST * R::STAGE, st, p);
     });
 }
 
 int launch_nt_v2(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
+    typedef NarrowRing R;
     GemmP p = p0;
-    p.tiles_m = cdiv(p.M, BM2);
-    p.tiles_n = cdiv(p.N, BN2);
+    p.tiles_m = cdiv(p.M, R::BM);
+    p.tiles_n = cdiv(p.N, R::BN);
     const int grid = p.tiles_m * p.tiles_n;
-    const size_t lds = NSTAGE * STAGE_BYTES;
+    const size_t lds = R::NST * R::STAGE;
     const bool patch = p.a_mode == LNX_ADDR_PATCH2;
     LNX_CHECK(!patch || f == F_GENERIC, "gemm_nt_v2: the 2x2 patch gather is compiled with the generic epilogue only (f = %d)", f);
     return with_nt_form<nt_v2_carries>("gemm_nt_v2", out_f32, f, [&](auto form) {
@@ -479,7 +438,7 @@ __global__ __launch_bounds__(512) void gemm_tn_v2_kernel(const WgradP p) {
     __builtin_amdgcn_s_barrier();
     if (grp) __builtin_amdgcn_s_barrier();
     for (int t = 0; t < ntile; ++t) {
-        const uint32_t st = lds_base + (t % NSTAGE) * STG;
+        const uint32_t st = lds_base + (t % NarrowRing::NST) * STG;
         uint2 rl[2][4], rh[2][4], cl[2][4], chh[2][4];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -489,7 +448,7 @@ __global__ __launch_bounds__(512) void gemm_tn_v2_kernel(const WgradP p) {
                 DS_READ_TR2(cl[ks][i], chh[ks][i], st + offC[ks][i], 16 * CROW);
             }
         if (t + 2 < ntile) {
-            issue_tile((t + 2) % NSTAGE);
+            issue_tile((t + 2) % NarrowRing::NST);
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -711,7 +670,7 @@ int launch_tn_v2(const WgradP& p0, int splits_hint, hipStream_t st, bool defer) 
     p.m_per_split = per * TBM;
     p.splits = cdiv(mtiles, per);
     const int grid = tiles * p.splits;
-    const size_t lds = NSTAGE * (size_t)(TBM * (RW + CW) * 2);
+    const size_t lds = NarrowRing::NST * (size_t)(TBM * (RW + CW) * 2);
     static const bool no_ws = getenv("LNX_TN_ATOMIC") != nullptr;  // A/B switch for benchmarking
     const size_t need = (size_t)p.splits * tiles * (256 * 128) + (size_t)p.splits * p.tiles_n * RW;
     // padded tiles are stored and re-read whole: with poorly filled tiles (N x K well below tiles x 256 x 128) the atomics move fewer bytes

@@ -24,30 +24,12 @@
 // stride each of them still owes its whole share, the launch takes two rounds instead of (256 / free CUs) of one.  With a counter
 // the early workgroups eat the tiles and a latecomer finds none.  The XCD-local tile order is kept: XCD x owns the contiguous
 // logical range xcd_remap() gives it and a counter of its own (workgroup b runs on XCD b & 7 under round-robin dispatch); nothing
-// is stolen across XCDs (a collective's workgroups are dealt round-robin too).  Mechanics: wave 0 fetches the tile AFTER next with
-// one lane (global_atomic_add with return, issued in iteration 0 in front of the LDS-DMA pieces and counted like any other extra of
-// the in-order counter), publishes it through one LDS dword in iteration 1, every wave reads it in iteration 2 -- two iterations
-// before the first use (the ring refill at nk - 2).  The fetch that returns the range's last index is the last one the counter
-// will see in this launch: that workgroup zeroes it for the next launch.  LNX_TILE_SCHED=static restores the stride (A/B).
+// is stolen across XCDs (a collective's workgroups are dealt round-robin too).  Mechanics: the draw protocol of common.hpp (sched_draw
+// and what follows it) -- drawn in iteration 0, published in iteration 1, read by every wave in iteration 2, two iterations before the
+// first use (the ring refill at nk - 2).  LNX_TILE_SCHED=static restores the stride (A/B).
 #include "gemm_common.hpp"
 
 namespace lnxg {
-
-#define V7_READ4(dst, addr)                                                                              \
-    do {                                                                                                 \
-        const uint32_t a_ = (addr);                                                                      \
-        asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(a_) : "memory");                         \
-        asm volatile("ds_read_b128 %0, %1 offset:512" : "=v"(dst[1]) : "v"(a_) : "memory");              \
-        asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(dst[2]) : "v"(a_) : "memory");             \
-        asm volatile("ds_read_b128 %0, %1 offset:1536" : "=v"(dst[3]) : "v"(a_) : "memory");             \
-    } while (0)
-
-template <int N> struct IC { static constexpr int value = N; };
-
-constexpr int BM7 = 256, BN7 = 128, BK7 = 64;
-constexpr int STAGE7 = (BM7 + BN7) * ROWB;  // 48 KiB
-constexpr int NST7 = 3;
-constexpr int PIECES7 = (BM7 + BN7) / 8 / 8;  // 6 LDS-DMA wave-instructions (1 KiB each) per wave and K slice
 
 // inline-asm global fetches: the compiler must not track them (beside LDS-DMA in flight it would wait vmcnt(0) at their first
 // use, i.e. for the slices prefetched for the NEXT tile); the counted waits of the K loop cover them
@@ -62,6 +44,7 @@ __device__ __forceinline__ void asm_load4(float& d, const void* ptr) {
 template <bool OUT_F32, int F, int HEAD7, int TAIL7>
 __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
     typedef bf16_t T;
+    typedef NarrowRing R;
     constexpr bool TWO = (F & F_C2) != 0;
     constexpr int NSTORE = OUT_F32 ? 16 : (TWO ? 16 : 8);                      // 16-byte stores per lane and tile
     constexpr int NLOAD = (F & F_GELU_BWD) ? 8 : ((F & F_RES) ? 16 : 0);       // 16-byte epilogue-operand fetches per lane and tile
@@ -75,14 +58,14 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
     const int s = lane & 15, g = lane >> 4;
     const int grp = wave >> 2;
     const int ntiles = p.tiles_m * p.tiles_n;
-    const int nk = p.K / BK7;  // >= HEAD7 + TAIL7 + 1 (launch_nt_v7 picks HEAD7 / TAIL7 accordingly)
+    const int nk = p.K / R::BK;  // >= HEAD7 + TAIL7 + 1 (launch_nt_v7 picks HEAD7 / TAIL7 accordingly)
 
     const int frag_row = (s >> 2) * 16 + (s & 3);
     const int frag_key = ((s >> 1) & 1) | ((s >> 2) << 1);
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const uint32_t ch0 = (uint32_t)((g ^ frag_key) << 4);  // the second 64-byte half of a row is chunk ^ 4: offset ^ 64
-    const uint32_t a_off0 = (wm * 64 + frag_row) * ROWB + ch0;
-    const uint32_t w_off0 = (BM7 + wn * 64 + frag_row) * ROWB + ch0;
+    const uint32_t a_off0 = (wm * 64 + frag_row) * R::ROWBYTES + ch0;
+    const uint32_t w_off0 = (R::BM + wn * 64 + frag_row) * R::ROWBYTES + ch0;
 
     // LDS-DMA sources as 32-bit byte offsets from p.A / p.W (checked by nt_v7_ok): of the current tile and of the next one,
     // whose first two slices are issued by the last two iterations of the current tile -- the ring never drains
@@ -90,29 +73,29 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
     u32x8_t src = {0, 0, 0, 0, 0, 0, 0, 0}, srcn = {0, 0, 0, 0, 0, 0, 0, 0};
     auto piece_offset = [&](int j, int m0, int n0) __attribute__((always_inline)) -> uint32_t {
         const int i = wave + 8 * j;
-        const int row = 8 * i + (lane >> 3);
-        const int slot = lane & 7;
-        if (row < BM7) {
+        const int row = R::ROWS_PER_PIECE * i + (lane >> R::CHUNK_SHIFT);
+        const int slot = lane & (R::CHUNKS - 1);
+        if (row < R::BM) {
             int m = m0 + row;
             if (m >= p.M) m = p.M - 1;
-            return (uint32_t)(m * (int)p.lda + (slot ^ row_key(row)) * 8) * 2u;
+            return (uint32_t)(m * (int)p.lda + (slot ^ R::key(row)) * 8) * 2u;
         }
-        const int wr = row - BM7;
+        const int wr = row - R::BM;
         int n = n0 + wr;
         if (n >= p.N) n = p.N - 1;
-        return (uint32_t)(n * (int)p.ldw + (slot ^ row_key(wr)) * 8) * 2u;
+        return (uint32_t)(n * (int)p.ldw + (slot ^ R::key(wr)) * 8) * 2u;
     };
     // (nothing here may end up in scratch memory: a scratch access inside the K loop is a vector-memory load that the in-order
     // counter waits for -- check ScratchSize = 0 in -Rpass-analysis=kernel-resource-usage after every change)
     auto issue = [&](bool of_next, int kslice, int stage) __attribute__((always_inline)) {
         const u32x8_t sv = of_next ? srcn : src;
 #pragma unroll
-        for (int j = 0; j < PIECES7; ++j) {
+        for (int j = 0; j < R::PIECES; ++j) {
             const int i = wave + 8 * j;
-            const unsigned char* base = 8 * i < BM7 ? p.A : p.W;  // wave-uniform: a piece is all A rows or all W rows
+            const unsigned char* base = R::ROWS_PER_PIECE * i < R::BM ? p.A : p.W;  // wave-uniform: a piece is all A rows or all W rows
             const uint32_t so = sv[j];
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + (so + (uint32_t)(kslice * BK7 * 2))),
-                                             (__attribute__((address_space(3))) void*)(smem + stage * STAGE7 + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + (so + (uint32_t)(kslice * R::BK * 2))),
+                                             (__attribute__((address_space(3))) void*)(smem + stage * R::STAGE + i * 1024), 16, 0, 0);
         }
     };
 
@@ -158,43 +141,24 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
     const int xcnt = sh.cnt, xbase = sh.base, xgrid = sh.workers;  // (xgrid: workgroups of this launch on this XCD)
     const bool dyn = p.tile_slot >= 0;
     unsigned* const ctr = &g_tile_ctr[dyn ? p.tile_slot : 0][sh.part][0];
-    const uint32_t slot_addr = lds_base + NST7 * STAGE7;  // the LDS dword the fetched position travels through
+    const uint32_t slot_addr = lds_base + R::NST * R::STAGE;  // the LDS dword the fetched position travels through
     bool reset_ctr = false;  // this workgroup drew the range's last fetch: it zeroes the counter on its way out
     int pos = sh.index, m0, n0;
     if (dyn) {
-        // EVERY tile is drawn, the first one too (0.6 us of L2 round trip per launch): a workgroup that starts late -- its CU was
-        // held by a collective kernel -- then owes nothing.  Draws per XCD and launch: one per tile + one failed draw per workgroup,
-        // so the draw that returns xcnt + xgrid - 1 is the last the counter sees.
-        if (wave == 0) {
-            const uint32_t one = 1u;
-            uint32_t first;
-            uint64_t save;
-            asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, 1\n\tglobal_atomic_add %0, %2, %3, off sc0\n\ts_waitcnt vmcnt(0)\n\tds_write_b32 %4, %0\n\ts_mov_b64 exec, %1\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&v"(first), "=&s"(save) : "v"(ctr), "v"(one), "v"(slot_addr) : "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        uint32_t seen0;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(seen0) : "v"(slot_addr) : "memory");
-        pos = __builtin_amdgcn_readfirstlane((int)seen0);
-        reset_ctr = pos == xcnt + xgrid - 1;
-        __builtin_amdgcn_s_barrier();  // everyone has read the slot before iteration 1 of the first tile may overwrite it
+        pos = sched_first_draw(ctr, slot_addr, wave);
+        reset_ctr = sched_last_draw(sh, pos);
     }
     if (pos >= xcnt) {
         if (reset_ctr && tid == 0) sched_reset(ctr);
         return;
     }
-    auto pos_origin = [&](int ps, int& mo, int& no) __attribute__((always_inline)) {
-        const int logical = xbase + ps;
-        no = (logical % p.tiles_n) * BN7;
-        mo = (logical / p.tiles_n) * BM7;
-    };
-    pos_origin(pos, m0, n0);
+    tile_origin<R::BM, R::BN>(xbase + pos, p.tiles_n, m0, n0);
 #pragma unroll
-    for (int j = 0; j < PIECES7; ++j) src[j] = piece_offset(j, m0, n0);
+    for (int j = 0; j < R::PIECES; ++j) src[j] = piece_offset(j, m0, n0);
     issue(false, 0, 0);
     issue(false, 1, 1);
     int ring = 0;  // LDS stage of the current K slice; runs on across tiles
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES7) : "memory");  // slice 0 landed (slice 1 may be in flight)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(R::PIECES) : "memory");  // slice 0 landed (slice 1 may be in flight)
     __builtin_amdgcn_s_barrier();
     if (grp) __builtin_amdgcn_s_barrier();  // ping-pong: waves 4-7 run one barrier interval behind waves 0-3
 
@@ -203,7 +167,7 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
         const int nb = ncol0 + g * 16;                      // first of this lane's 16 columns
         const int mbase = mrow0 + (s >> 2) * 16 + (s & 3);  // row of slot mi = mbase + 4 mi
         const bool live = ncol0 < p.N;                      // column tiles beyond N (wave-uniform: N % 64 == 0): nothing to fetch or store
-        const bool full = m0 + BM7 <= p.M;                  // only full tiles defer their stores (every lane then issues every store)
+        const bool full = m0 + R::BM <= p.M;                // only full tiles defer their stores (every lane then issues every store)
         const int nbc = live ? nb : 0;
         // static stride: known now.  Counter: known after iteration 2 (has_next is first looked at in iteration nk - 2 >= 4)
         int next = pos + xgrid;
@@ -258,12 +222,12 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
             constexpr int st_g = decltype(ST)::value, ld_g = decltype(LD)::value, fx = decltype(FX)::value;
             constexpr int s_lo = st_g < 0 ? 0 : st_g * NSTORE / HEAD7, s_hi = st_g < 0 ? 0 : (st_g + 1) * NSTORE / HEAD7;
             constexpr int l_lo = ld_g < 0 ? 0 : ld_g * NLOAD / TAIL7, l_hi = ld_g < 0 ? 0 : (ld_g == TAIL7 - 1 ? NLOAD + NCONST : (ld_g + 1) * NLOAD / TAIL7);
-            const uint32_t stg = lds_base + ring * STAGE7;
+            const uint32_t stg = lds_base + ring * R::STAGE;
             uint4 wf0[4], af0[4], wf1[4], af1[4];
-            V7_READ4(wf0, stg + w_off0);
-            V7_READ4(af0, stg + a_off0);
-            V7_READ4(wf1, stg + (w_off0 ^ 64u));
-            V7_READ4(af1, stg + (a_off0 ^ 64u));
+            lds_read4<R::ROWBYTES>(wf0, stg + w_off0);
+            lds_read4<R::ROWBYTES>(af0, stg + a_off0);
+            lds_read4<R::ROWBYTES>(wf1, stg + (w_off0 ^ 64u));
+            lds_read4<R::ROWBYTES>(af1, stg + (a_off0 ^ 64u));
             if (fx == 3 && dyn) asm volatile("ds_read_b32 %0, %1" : "=v"(seen) : "v"(slot_addr) : "memory");  // waited for with the fragments below
             // (`pending` already says that the PREVIOUS tile's columns were inside N for this wave; this tile's `live` has nothing to
             // do with it -- consecutive tiles of a workgroup sit in different column tiles since round 4's drawn order)
@@ -291,31 +255,22 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
     } while (0)
             if (issued) {
                 if (s_hi > s_lo) {
-                    if (do_st) V7_WAIT(PIECES7 + (s_hi - s_lo));
-                    else V7_WAIT(PIECES7);
+                    if (do_st) V7_WAIT(R::PIECES + (s_hi - s_lo));
+                    else V7_WAIT(R::PIECES);
                 } else {
-                    V7_WAIT(PIECES7 + (l_hi - l_lo));
+                    V7_WAIT(R::PIECES + (l_hi - l_lo));
                 }
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // last tile of this workgroup, last two slices: nothing to keep in flight
             }
 #undef V7_WAIT
-            if (fx == 2 && dyn && wave == 0) {  // iteration 1's wait retired the draw of iteration 0: hand it to the other waves
-                uint64_t save;
-                asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_write_b32 %1, %2\n\ts_mov_b64 exec, %0" : "=&s"(save) : "v"(slot_addr), "v"(fetched) : "memory");
-            }
+            if (fx == 2 && dyn && wave == 0) sched_publish(slot_addr, fetched);  // iteration 1's wait retired the draw of iteration 0
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) Mfma<T>::run(acc[ni][mi], wf0[ni], af0[mi]);
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi) Mfma<T>::run(acc[ni][mi], wf1[ni], af1[mi]);
+            mfma_4x4<T>(acc, wf0, af0);
+            mfma_4x4<T>(acc, wf1, af1);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
@@ -329,12 +284,12 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
         if (dyn) {
             next = __builtin_amdgcn_readfirstlane((int)seen);  // the counter's value before this workgroup's add = the position drawn
             has_next = next < xcnt;
-            reset_ctr = reset_ctr || next == xcnt + xgrid - 1;  // nobody draws after the last of the xcnt + xgrid draws
+            reset_ctr = reset_ctr || sched_last_draw(sh, next);  // nobody draws after the last of the xcnt + xgrid draws
         }
         if (has_next) {  // where the next tile's operands are; needed from iteration nk-2 on
-            pos_origin(next, nm0, nn0);
+            tile_origin<R::BM, R::BN>(xbase + next, p.tiles_n, nm0, nn0);
 #pragma unroll
-            for (int j = 0; j < PIECES7; ++j) srcn[j] = piece_offset(j, nm0, nn0);
+            for (int j = 0; j < R::PIECES; ++j) srcn[j] = piece_offset(j, nm0, nn0);
         }
 #define V7_HEAD(i) \
     if constexpr (HEAD7 > i) kstep(i, IC<i>(), IC<-1>(), IC<0>());
@@ -423,27 +378,23 @@ constexpr bool nt_v7_carries(bool out_f32, int f) {
 }
 
 bool nt_v7_ok(const GemmP& p, int f, bool out_f32) {
+    typedef NarrowRing R;
     if (p.a_mode == LNX_ADDR_PATCH2) return false;
     if (p.act == LNX_ACT_GELU_D) return false;  // this kernel's fc1 form keeps ONE tensor per tile; the derivative form needs two
-    if (p.K % BK7 != 0 || p.K / BK7 < 6) return false;
+    if (p.K % R::BK != 0 || p.K / R::BK < 6) return false;
     if (p.N % 64 != 0) return false;  // a wave's 64 columns are all inside or all outside N
-    const int64_t lim = (int64_t)1 << 31;  // 32-bit byte offsets of the LDS-DMA sources
-    if ((int64_t)p.M * p.lda * 2 >= lim || (int64_t)p.N * p.ldw * 2 >= lim) return false;
-    return nt_v7_carries(out_f32, f);
+    return fits_32bit_offsets(p) && nt_v7_carries(out_f32, f);
 }
 
 int launch_nt_v7(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
+    typedef NarrowRing R;
     GemmP p = p0;
-    p.tiles_m = cdiv(p.M, BM7);
-    p.tiles_n = cdiv(p.N, BN7);
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int cus = device_cus();
-    LNX_CHECK(cus > 0, "gemm_nt_v7: no device");
-    const int room = persistent_cus(cus);              // cus - LNX_CU_MARGIN / lnx_set_cu_margin()
-    const int grid = ntiles < room ? ntiles : room;    // persistent: one workgroup per CU (144 KiB of LDS each)
-    const size_t lds = NST7 * STAGE7 + 16;             // + the dword the next tile's position is published through
-    p.tile_slot = tile_sched_static() ? -1 : tile_slot_of(st);
-    const bool deep = p.K / BK7 >= 17;  // long K loops spread the deferred traffic over 8 + 8 iterations instead of 3 + 2
+    p.tiles_m = cdiv(p.M, R::BM);
+    p.tiles_n = cdiv(p.N, R::BN);
+    size_t lds;
+    const int grid = persistent_geometry<R>(p, st, lds);  // one workgroup per CU (144 KiB of LDS each)
+    LNX_CHECK(grid > 0, "gemm_nt_v7: no device");
+    const bool deep = p.K / R::BK >= 17;  // long K loops spread the deferred traffic over 8 + 8 iterations instead of 3 + 2
     return with_nt_form<nt_v7_carries>("gemm_nt_v7", out_f32, f, [&](auto form) {
         using Form = decltype(form);
         if (deep) return launch_with_lds<gemm_nt_v7_kernel<Form::out_f32, Form::f, 8, 8>>(grid, 512, lds, st, p);

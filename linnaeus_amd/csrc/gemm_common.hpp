@@ -1,6 +1,6 @@
 // Shared pieces of the MFMA GEMM kernels (gemm.hip: 128x128 register-staged kernels for both
-// storage types; gemm2.hip: 256x128 LDS-DMA pipelined bf16 kernel), and the host-side seam between the dispatcher
-// (gemm_nt_dispatch.cpp) and the families' launchers.
+// storage types; gemm2.hip / gemm3.hip / gemm5.hip / gemm_fp8.hip: the LDS-DMA pipelined kernels and their two LDS rings), and the
+// host-side seam between the dispatcher (gemm_nt_dispatch.cpp) and the families' launchers.
 #pragma once
 #include "common.hpp"
 #include "../../include/lnx.h"
@@ -72,6 +72,66 @@ template <> struct Mfma<float> {
         for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[j], fb[j], acc, 0, 0, 0);
     }
 };
+
+// the 4x4 MFMA block over a wave's 64x64 sub-tile: one K step of the fragments wf (columns) / af (rows)
+template <typename T>
+__device__ __forceinline__ void mfma_4x4(f32x4_t (&acc)[4][4], const uint4 (&wf)[4], const uint4 (&af)[4]) {
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) Mfma<T>::run(acc[ni][mi], wf[ni], af[mi]);
+}
+
+template <int N> struct IC { static constexpr int value = N; };  // a compile-time int as a function argument
+
+// ---- the LDS rings of the LDS-DMA pipelined NT kernels (gemm2.hip, gemm3.hip, gemm5.hip, gemm_fp8.hip) ----
+// A stage is [A: BM rows | W: BN rows] of ROWBYTES bytes of K, NST stages deep.  Eight waves fill it with 1-KiB LDS-DMA
+// wave-instructions ("pieces"): piece i fills rows ROWS_PER_PIECE i .. of the stage, wave w issues pieces i = w + 8 j (j < PIECES),
+// lane l -> (row l >> CHUNK_SHIFT, 16-byte slot l & (CHUNKS - 1)) of the piece.  LDS slot (row, c) receives global chunk c ^ Key::of(row), and the fragment
+// reads use the same key.
+struct KeyNarrow {  // 128-byte rows: row_key
+    static __device__ __forceinline__ int of(int row) { return row_key(row); }
+};
+struct KeyWide {  // 64-byte rows: 3 * bit4(row) (why: gemm_nt_v4_kernel's header)
+    static __device__ __forceinline__ int of(int row) { return (row & 16) ? 3 : 0; }
+};
+template <int BM_, int BN_, int ROWBYTES_, int NST_, class Key>
+struct Ring {
+    static constexpr int BM = BM_, BN = BN_, ROWBYTES = ROWBYTES_, NST = NST_;
+    static constexpr int STAGE = (BM + BN) * ROWBYTES;
+    static constexpr int CHUNKS = ROWBYTES / 16;         // 16-byte slots per row
+    static constexpr int CHUNK_SHIFT = CHUNKS == 8 ? 3 : 2;
+    static_assert(CHUNKS == 1 << CHUNK_SHIFT, "128- or 64-byte rows");
+    static constexpr int ROWS_PER_PIECE = 64 / CHUNKS;   // rows one wave-instruction fills
+    static constexpr int PIECES = STAGE / 1024 / 8;      // wave-instructions per wave and stage
+    static constexpr int BK = ROWBYTES / 2;              // K elements per slice at two bytes per element
+    static __device__ __forceinline__ int key(int row) { return Key::of(row); }
+};
+using NarrowRing = Ring<256, 128, ROWB, 3, KeyNarrow>;  // 256x128 tile, 48 KiB stages, two slices in flight (v2, v7, fp8)
+using WideRing = Ring<256, 256, 64, 4, KeyWide>;        // 256x256 tile, 32 KiB stages, three slices in flight (v4, v9; mx8 with its own key)
+constexpr int BK4 = WideRing::BK, ROWB4 = WideRing::ROWBYTES;  // the names tools/experiments/gemm_nt_v5.hip knows the wide ring's slice by
+
+// four 16-byte fragment reads at rows +0, +4, +8, +12 from one address.  Inline asm on purpose: with compiler-visible LDS loads hipcc
+// puts an s_waitcnt vmcnt(0) in front of them (see gemm_nt_v2_kernel)
+template <int ROWBYTES>
+__device__ __forceinline__ void lds_read4(uint4 (&dst)[4], uint32_t addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(addr) : "memory");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(addr), "n"(4 * ROWBYTES) : "memory");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[2]) : "v"(addr), "n"(8 * ROWBYTES) : "memory");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[3]) : "v"(addr), "n"(12 * ROWBYTES) : "memory");
+#endif
+}
+// first row / column of the tile of a one-shot kernel's workgroup.  (tile_origin's arithmetic, written out: the persistent kernels'
+// device code comes out as it is with the column first, gemm_nt_fp8_kernel's with the row first.)
+template <int BM, int BN>
+__device__ __forceinline__ void one_shot_origin(const GemmP& p, int& m0, int& n0) {
+    const int logical = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+    const int tn = logical % p.tiles_n;
+    const int tm = logical / p.tiles_n;
+    m0 = tm * BM;
+    n0 = tn * BN;
+}
 
 // element offset of the 2x2 patch origin of output pixel m in an NHWC tensor
 __device__ __forceinline__ int64_t patch_base(const PatchGeom& g, int m) {
@@ -531,9 +591,33 @@ int launch_nt_skinny(const GemmP& p, bool out_f32, hipStream_t st);
 int launch_nt_skinny_group(const GemmP* ps, int n, bool accumulate, bool out_f32, hipStream_t st);  // lnx_gemm_nt_group
 
 // gemm2.hip: 256x128 (v2) and 256x256 (v4) LDS-DMA pipelined kernels (bf16)
-constexpr int BM4 = 256, BN4 = 256, BK4 = 32, ROWB4 = 64;  // v4: 256x256 tile, K in 32-element slices = 64-byte LDS rows
 int launch_nt_v2(const GemmP& p, int f, bool out_f32, hipStream_t st);
 int launch_nt_v4(const GemmP& p, int f, bool out_f32, hipStream_t st);
+
+// The forms the 256x256 family (one-shot v4, persistent v9) is compiled for: no generic epilogue
+constexpr bool nt_v4_carries(bool out_f32, int f) {
+    if (out_f32) return f == (F_BIAS | F_RES);
+    return f == 0 || f == F_BIAS || f == (F_BIAS | F_C2 | F_GELU) || f == (F_BIAS | F_GELU) || f == F_GELU_BWD;
+}
+
+// ---- the persistent kernels (tiles drawn from the counters of common.hpp) ----
+// LDS-DMA sources as 32-bit byte offsets from p.A / p.W (bf16)
+inline bool fits_32bit_offsets(const GemmP& p) {
+    const int64_t lim = (int64_t)1 << 31;
+    return (int64_t)p.M * p.lda * 2 < lim && (int64_t)p.N * p.ldw * 2 < lim;
+}
+// Launch geometry (p.tiles_m / p.tiles_n are set): the grid -- one workgroup per CU that LNX_CU_MARGIN / lnx_set_cu_margin() leaves, at
+// most one per tile; 0 = no device --, the ring + the dword the next tile's position is published through, and the stream's counter set.
+template <class R>
+int persistent_geometry(GemmP& p, hipStream_t st, size_t& lds) {
+    const int ntiles = p.tiles_m * p.tiles_n;
+    const int cus = device_cus();
+    if (cus <= 0) return 0;
+    const int room = persistent_cus(cus);
+    lds = R::NST * R::STAGE + 16;
+    p.tile_slot = tile_sched_static() ? -1 : tile_slot_of(st);
+    return ntiles < room ? ntiles : room;
+}
 
 // gemm3.hip: persistent 256x128 kernel whose epilogue stores / fetches ride under the next tile's K loop
 bool nt_v7_ok(const GemmP& p, int f, bool out_f32);

@@ -18,20 +18,7 @@
 
 namespace lnxg {
 
-#define F8_DS_READ4(dst, addr)                                                                           \
-    do {                                                                                                 \
-        const uint32_t a_ = (addr);                                                                      \
-        asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(a_) : "memory");                         \
-        asm volatile("ds_read_b128 %0, %1 offset:512" : "=v"(dst[1]) : "v"(a_) : "memory");              \
-        asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(dst[2]) : "v"(a_) : "memory");             \
-        asm volatile("ds_read_b128 %0, %1 offset:1536" : "=v"(dst[3]) : "v"(a_) : "memory");             \
-    } while (0)
-
-constexpr int F8_BM = 256, F8_BN = 128, F8_BK = 128;   // BK in elements = bytes
-constexpr int F8_STAGE = (F8_BM + F8_BN) * ROWB;       // 48 KiB
 constexpr int F8_SCALES = 8 * 64 * 4;                  // MX: one dword per tile row (384 used), one 256-byte DMA per wave
-constexpr int F8_NSTAGE = 3;
-constexpr int F8_LD = (F8_BM + F8_BN) / 8 / 8;         // 1-KiB LDS-DMA instructions per wave per stage = 6
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 
@@ -43,8 +30,10 @@ __device__ __forceinline__ void mfma_f8(f32x4_t& acc, const uint4& a_lo, const u
 
 template <bool OUT_F32, int F, bool MX>
 __global__ __launch_bounds__(512) void gemm_nt_fp8_kernel(const GemmP p) {
-    constexpr int STAGE = F8_STAGE + (MX ? F8_SCALES : 0);
-    constexpr int NLD = F8_LD + (MX ? 1 : 0);  // VMEM instructions per wave and stage
+    typedef NarrowRing R;  // a 128-byte row is one K slice of 128 e4m3 values
+    constexpr int BK = R::ROWBYTES;
+    constexpr int STAGE = R::STAGE + (MX ? F8_SCALES : 0);
+    constexpr int NLD = R::PIECES + (MX ? 1 : 0);  // VMEM instructions per wave and stage
     typedef bf16_t T;  // type of C / c2 / aux
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [3][A 256 rows | W 128 rows][128 B]
     const int tid = threadIdx.x;
@@ -53,28 +42,25 @@ __global__ __launch_bounds__(512) void gemm_nt_fp8_kernel(const GemmP p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int s = lane & 15, g = lane >> 4;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int logical = xcd_remap(blockIdx.x, nwg);
-    const int tn = logical % p.tiles_n;
-    const int tm = logical / p.tiles_n;
-    const int m0 = tm * F8_BM, n0 = tn * F8_BN;
+    int m0, n0;
+    one_shot_origin<R::BM, R::BN>(p, m0, n0);
 
     // LDS-DMA sources as in gemm_nt_v2_kernel (bytes == elements)
-    const unsigned char* src[F8_LD];
+    const unsigned char* src[R::PIECES];
 #pragma unroll
-    for (int j = 0; j < F8_LD; ++j) {
+    for (int j = 0; j < R::PIECES; ++j) {
         const int i = wave + 8 * j;
-        const int row = 8 * i + (lane >> 3);
-        const int slot = lane & 7;
-        if (row < F8_BM) {
+        const int row = R::ROWS_PER_PIECE * i + (lane >> R::CHUNK_SHIFT);
+        const int slot = lane & (R::CHUNKS - 1);
+        if (row < R::BM) {
             int m = m0 + row;
             if (m >= p.M) m = p.M - 1;
-            src[j] = p.A + (int64_t)m * p.lda + ((slot ^ row_key(row)) << 4);
+            src[j] = p.A + (int64_t)m * p.lda + ((slot ^ R::key(row)) << 4);
         } else {
-            const int wr = row - F8_BM;
+            const int wr = row - R::BM;
             int n = n0 + wr;
             if (n >= p.N) n = p.N - 1;
-            src[j] = p.W + (int64_t)n * p.ldw + ((slot ^ row_key(wr)) << 4);
+            src[j] = p.W + (int64_t)n * p.ldw + ((slot ^ R::key(wr)) << 4);
         }
     }
     // MX: lane `lane` of wave `wave` fetches the scale dword of tile row 64 wave + lane (A rows 0..255, W rows 256..383,
@@ -83,40 +69,40 @@ __global__ __launch_bounds__(512) void gemm_nt_fp8_kernel(const GemmP p) {
     int64_t sc_step = 0;
     if constexpr (MX) {
         const int row = 64 * wave + lane;
-        if (row < F8_BM) {
+        if (row < R::BM) {
             int m = m0 + row;
             if (m >= p.M) m = p.M - 1;
             sc_src = p.mxa + m;
             sc_step = p.M;
         } else {
-            int n = n0 + row - F8_BM;
-            if (row >= F8_BM + F8_BN || n >= p.N) n = p.N - 1;
+            int n = n0 + row - R::BM;
+            if (row >= R::BM + R::BN || n >= p.N) n = p.N - 1;
             sc_src = p.mxw + n;
             sc_step = p.N;
         }
     }
     auto issue_tile = [&](int kt, int stage) {
 #pragma unroll
-        for (int j = 0; j < F8_LD; ++j) {
+        for (int j = 0; j < R::PIECES; ++j) {
             const int i = wave + 8 * j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (int64_t)kt * F8_BK),
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (int64_t)kt * BK),
                                              (__attribute__((address_space(3))) void*)(smem + stage * STAGE + i * 1024), 16, 0, 0);
         }
         if constexpr (MX)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sc_src + (int64_t)kt * sc_step),
-                                             (__attribute__((address_space(3))) void*)(smem + stage * STAGE + F8_STAGE + wave * 256), 4, 0, 0);
+                                             (__attribute__((address_space(3))) void*)(smem + stage * STAGE + R::STAGE + wave * 256), 4, 0, 0);
     };
 
     const int frag_row = (s >> 2) * 16 + (s & 3);
     const int frag_key = ((s >> 1) & 1) | ((s >> 2) << 1);
     const int a_row0 = wm * 64 + frag_row;
-    const int w_row0 = F8_BM + wn * 64 + frag_row;
+    const int w_row0 = R::BM + wn * 64 + frag_row;
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     // plain: bytes 32g .. 32g+31 of the row (any k order does, as long as A and W agree); MX: the hardware's own k order
     const uint32_t ch0 = (uint32_t)(((MX ? g : 2 * g) ^ frag_key) << 4), ch1 = (uint32_t)(((MX ? g + 4 : 2 * g + 1) ^ frag_key) << 4);
-    const uint32_t sc_a0 = F8_STAGE + (wm * 64 + frag_row) * 4 + g, sc_w0 = F8_STAGE + (F8_BM + wn * 64 + frag_row) * 4 + g;
-    const uint32_t a_off0 = a_row0 * ROWB + ch0, a_off1 = a_row0 * ROWB + ch1;
-    const uint32_t w_off0 = w_row0 * ROWB + ch0, w_off1 = w_row0 * ROWB + ch1;
+    const uint32_t sc_a0 = R::STAGE + (wm * 64 + frag_row) * 4 + g, sc_w0 = R::STAGE + (R::BM + wn * 64 + frag_row) * 4 + g;
+    const uint32_t a_off0 = a_row0 * R::ROWBYTES + ch0, a_off1 = a_row0 * R::ROWBYTES + ch1;
+    const uint32_t w_off0 = w_row0 * R::ROWBYTES + ch0, w_off1 = w_row0 * R::ROWBYTES + ch1;
 
     f32x4_t acc[4][4];
 #pragma unroll
@@ -124,7 +110,7 @@ __global__ __launch_bounds__(512) void gemm_nt_fp8_kernel(const GemmP p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = p.K / F8_BK;  // >= 2
+    const int nk = p.K / BK;  // >= 2
     issue_tile(0, 0);
     issue_tile(1, 1);
     // ping-pong wave groups, two barriers per K slice, counted waits: see gemm_nt_v2_kernel
@@ -134,12 +120,12 @@ __global__ __launch_bounds__(512) void gemm_nt_fp8_kernel(const GemmP p) {
     __builtin_amdgcn_s_barrier();
     if (grp) __builtin_amdgcn_s_barrier();
     for (int kt = 0; kt < nk; ++kt) {
-        const uint32_t st = lds_base + (kt % F8_NSTAGE) * STAGE;
+        const uint32_t st = lds_base + (kt % R::NST) * STAGE;
         uint4 wf0[4], af0[4], wf1[4], af1[4];
-        F8_DS_READ4(wf0, st + w_off0);
-        F8_DS_READ4(af0, st + a_off0);
-        F8_DS_READ4(wf1, st + w_off1);
-        F8_DS_READ4(af1, st + a_off1);
+        lds_read4<R::ROWBYTES>(wf0, st + w_off0);
+        lds_read4<R::ROWBYTES>(af0, st + a_off0);
+        lds_read4<R::ROWBYTES>(wf1, st + w_off1);
+        lds_read4<R::ROWBYTES>(af1, st + a_off1);
         int scw[4], sca[4];
         if constexpr (MX) {
 #pragma unroll
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(512) void gemm_nt_fp8_kernel(const GemmP p) {
             for (int i = 0; i < 4; ++i) scw[i] = sca[i] = 0x7f;
         }
         if (kt + 2 < nk) {
-            issue_tile(kt + 2, (kt + 2) % F8_NSTAGE);
+            issue_tile(kt + 2, (kt + 2) % R::NST);
             if constexpr (MX) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         } else {
@@ -191,16 +177,15 @@ __global__ __launch_bounds__(512) void gemm_nt_fp8_kernel(const GemmP p) {
 // D[8 (i / 4) + 4 h + i % 4][r].  The W rows of a 32-row block are loaded PERMUTED (MFMA row j <- block row
 // 16 ((j >> 2) & 1) + 4 (j >> 3) + (j & 3)) so that a lane's 16 results are 16 consecutive output columns.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int X8_BM = 256, X8_BN = 256, X8_BK = 64, X8_ROWB = 64;
-constexpr int X8_STAGE = (X8_BM + X8_BN) * X8_ROWB;  // 32 KiB
-constexpr int X8_SCALES = 512 * 4;                    // one dword (the four block scales of a 128-wide K span) per tile row
-constexpr int X8_NST = 4;
-constexpr int X8_PIECES = X8_STAGE / 1024 / 8;        // 4 LDS-DMA wave-instructions per wave and stage (+ 1 for the scales)
+constexpr int X8_SCALES = 512 * 4;  // one dword (the four block scales of a 128-wide K span) per tile row
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 // chunk key of a 64-byte LDS row: conflict-free for 16 consecutive rows (the A fragments) and for the permuted W rows
-__device__ __forceinline__ int key_x8(int row) { return ((row >> 2) & 3) ^ (((row >> 4) & 1) << 1); }
+struct KeyX8 {
+    static __device__ __forceinline__ int of(int row) { return ((row >> 2) & 3) ^ (((row >> 4) & 1) << 1); }
+};
+using X8Ring = Ring<WideRing::BM, WideRing::BN, WideRing::ROWBYTES, WideRing::NST, KeyX8>;  // the wide ring's sizes, one byte per element
 
 template <bool OUT_F32, int F>
 __device__ __forceinline__ void mx8_epilogue(const GemmP& p, f32x16_t (&acc)[2][4], int mrow0, int ncol0, int lane) {
@@ -328,7 +313,9 @@ __device__ __forceinline__ void mx8_epilogue(const GemmP& p, f32x16_t (&acc)[2][
 
 template <bool OUT_F32, int F>
 __global__ __launch_bounds__(512) void gemm_nt_mx8_kernel(const GemmP p) {
-    constexpr int STAGE = X8_STAGE + X8_SCALES;
+    typedef X8Ring R;
+    constexpr int BK = R::ROWBYTES;  // a K slice is 64 e4m3 values
+    constexpr int STAGE = R::STAGE + X8_SCALES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [4][A 256 rows | W 256 rows][64 B] + [512] scale dwords
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -336,28 +323,25 @@ __global__ __launch_bounds__(512) void gemm_nt_mx8_kernel(const GemmP p) {
     const int wm = wave & 1, wn = wave >> 1;  // 128-row half, 64-column quarter; waves 0-3 / 4-7 = the ping-pong groups
     const int r = lane & 31, h = lane >> 5;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int logical = xcd_remap(blockIdx.x, nwg);
-    const int tn = logical % p.tiles_n;
-    const int tm = logical / p.tiles_n;
-    const int m0 = tm * X8_BM, n0 = tn * X8_BN;
+    int m0, n0;
+    one_shot_origin<R::BM, R::BN>(p, m0, n0);
 
     // piece i (32 per stage) fills LDS rows 16 i .. 16 i + 15 (rows 0..255 = A, 256..511 = W); wave w issues i = w + 8 j
-    const unsigned char* src[X8_PIECES];
+    const unsigned char* src[R::PIECES];
 #pragma unroll
-    for (int j = 0; j < X8_PIECES; ++j) {
+    for (int j = 0; j < R::PIECES; ++j) {
         const int i = wave + 8 * j;
-        const int row = 16 * i + (lane >> 2);
-        const int slot = lane & 3;
-        if (row < X8_BM) {
+        const int row = R::ROWS_PER_PIECE * i + (lane >> R::CHUNK_SHIFT);
+        const int slot = lane & (R::CHUNKS - 1);
+        if (row < R::BM) {
             int m = m0 + row;
             if (m >= p.M) m = p.M - 1;
-            src[j] = p.A + (int64_t)m * p.lda + ((slot ^ key_x8(row)) << 4);
+            src[j] = p.A + (int64_t)m * p.lda + ((slot ^ R::key(row)) << 4);
         } else {
-            const int wr = row - X8_BM;
+            const int wr = row - R::BM;
             int n = n0 + wr;
             if (n >= p.N) n = p.N - 1;
-            src[j] = p.W + (int64_t)n * p.ldw + ((slot ^ key_x8(wr)) << 4);
+            src[j] = p.W + (int64_t)n * p.ldw + ((slot ^ R::key(wr)) << 4);
         }
     }
     // scales: lane `lane` of wave `wave` fetches the dword of tile row 64 wave + lane (A rows 0..255, W rows 256..511): the four
@@ -366,13 +350,13 @@ __global__ __launch_bounds__(512) void gemm_nt_mx8_kernel(const GemmP p) {
     int64_t sc_step;
     {
         const int row = 64 * wave + lane;
-        if (row < X8_BM) {
+        if (row < R::BM) {
             int m = m0 + row;
             if (m >= p.M) m = p.M - 1;
             sc_src = p.mxa + m;
             sc_step = p.M;
         } else {
-            int n = n0 + row - X8_BM;
+            int n = n0 + row - R::BM;
             if (n >= p.N) n = p.N - 1;
             sc_src = p.mxw + n;
             sc_step = p.N;
@@ -380,13 +364,13 @@ __global__ __launch_bounds__(512) void gemm_nt_mx8_kernel(const GemmP p) {
     }
     auto issue_stage = [&](int kt, int stage) {
 #pragma unroll
-        for (int j = 0; j < X8_PIECES; ++j) {
+        for (int j = 0; j < R::PIECES; ++j) {
             const int i = wave + 8 * j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (int64_t)kt * X8_BK),
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (int64_t)kt * BK),
                                              (__attribute__((address_space(3))) void*)(smem + stage * STAGE + i * 1024), 16, 0, 0);
         }
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sc_src + (int64_t)(kt >> 1) * sc_step),
-                                         (__attribute__((address_space(3))) void*)(smem + stage * STAGE + X8_STAGE + wave * 256), 4, 0, 0);
+                                         (__attribute__((address_space(3))) void*)(smem + stage * STAGE + R::STAGE + wave * 256), 4, 0, 0);
     };
 
     // fragment rows: A natural (block row r), W permuted (see above)
@@ -397,15 +381,15 @@ __global__ __launch_bounds__(512) void gemm_nt_mx8_kernel(const GemmP p) {
     for (int mj = 0; mj < 4; ++mj) {
         const int row = wm * 128 + 32 * mj + r;
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) a_off[mj][kb] = (uint32_t)(row * X8_ROWB + (((2 * kb + h) ^ key_x8(row)) << 4));
-        a_sc[mj] = (uint32_t)(X8_STAGE + row * 4 + h);
+        for (int kb = 0; kb < 2; ++kb) a_off[mj][kb] = (uint32_t)(row * R::ROWBYTES + (((2 * kb + h) ^ R::key(row)) << 4));
+        a_sc[mj] = (uint32_t)(R::STAGE + row * 4 + h);
     }
 #pragma unroll
     for (int nj = 0; nj < 2; ++nj) {
         const int wr = wn * 64 + 32 * nj + wperm;
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) w_off[nj][kb] = (uint32_t)((X8_BM + wr) * X8_ROWB + (((2 * kb + h) ^ key_x8(wr)) << 4));
-        w_sc[nj] = (uint32_t)(X8_STAGE + (X8_BM + wr) * 4 + h);
+        for (int kb = 0; kb < 2; ++kb) w_off[nj][kb] = (uint32_t)((R::BM + wr) * R::ROWBYTES + (((2 * kb + h) ^ R::key(wr)) << 4));
+        w_sc[nj] = (uint32_t)(R::STAGE + (R::BM + wr) * 4 + h);
     }
 
     f32x16_t acc[2][4];  // [nj][mj]
@@ -416,16 +400,16 @@ __global__ __launch_bounds__(512) void gemm_nt_mx8_kernel(const GemmP p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[nj][mj][i] = 0.f;
 
-    const int nk = p.K / X8_BK;  // >= 4
+    const int nk = p.K / BK;  // >= 4
     issue_stage(0, 0);
     issue_stage(1, 1);
     issue_stage(2, 2);
     const int grp = wave >> 2;
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (X8_PIECES + 1)) : "memory");  // own pieces of slice 0 landed
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (R::PIECES + 1)) : "memory");  // own pieces of slice 0 landed
     __builtin_amdgcn_s_barrier();
     if (grp) __builtin_amdgcn_s_barrier();
     for (int kt = 0; kt < nk; ++kt) {
-        const uint32_t st = lds_base + (kt % X8_NST) * STAGE;
+        const uint32_t st = lds_base + (kt % R::NST) * STAGE;
         const uint32_t sb = (uint32_t)(2 * (kt & 1));  // which two of the dword's four block scales
         uint4 af[4][2], wf[2][2];
         int sca[4], scw[2];
@@ -442,10 +426,10 @@ __global__ __launch_bounds__(512) void gemm_nt_mx8_kernel(const GemmP p) {
             asm volatile("ds_read_u8 %0, %1" : "=v"(sca[mj]) : "v"(st + a_sc[mj] + sb) : "memory");
         }
         if (kt + 3 < nk) {
-            issue_stage(kt + 3, (kt + 3) % X8_NST);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (X8_PIECES + 1)) : "memory");
+            issue_stage(kt + 3, (kt + 3) % R::NST);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (R::PIECES + 1)) : "memory");
         } else if (kt + 2 < nk) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(X8_PIECES + 1) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(R::PIECES + 1) : "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -639,8 +623,8 @@ static int launch_fp8(const lnx_gemm_args* a, const float* a_scale, const float*
     if (mx) LNX_CHECK(mxw != nullptr && ((((uintptr_t)mxa) | ((uintptr_t)mxw)) & 3) == 0, "%s: block-scale arrays must be 4-byte aligned", who);
     GemmP p;
     fill_gemm_p(a, p);
-    p.tiles_m = cdiv(a->M, F8_BM);
-    p.tiles_n = cdiv(a->N, F8_BN);
+    p.tiles_m = cdiv(a->M, NarrowRing::BM);
+    p.tiles_n = cdiv(a->N, NarrowRing::BN);
     p.sa = a_scale; p.sw = w_scale;
     p.mxa = (const uint32_t*)mxa; p.mxw = (const uint32_t*)mxw;
     const bool out_f32 = a->out_f32 != 0;
@@ -655,13 +639,13 @@ static int launch_fp8(const lnx_gemm_args* a, const float* a_scale, const float*
     hipStream_t st = (hipStream_t)stream;
     // the 256x256-tile MX kernel where it applies (LNX_FP8_X8=0: never) and carries the form; its GELU forms only for the act they are named for
     const bool act_twin = ((f & F_GELU) && a->act != LNX_ACT_GELU) || ((f & F_GELU_BWD) && a->act != LNX_ACT_GELU_BWD);
-    if (mx && nt_switches().fp8_x8 && a->N % X8_BN == 0 && a->K % 128 == 0 && a->K / X8_BK >= 4 && (int64_t)cdiv(a->M, X8_BM) * (a->N / X8_BN) >= 128 &&
+    if (mx && nt_switches().fp8_x8 && a->N % X8Ring::BN == 0 && a->K % 128 == 0 && a->K / X8Ring::ROWBYTES >= 4 && (int64_t)cdiv(a->M, X8Ring::BM) * (a->N / X8Ring::BN) >= 128 &&
         nt_fp8_carries(out_f32, f) && !act_twin) {
-        p.tiles_m = cdiv(a->M, X8_BM);
-        p.tiles_n = a->N / X8_BN;
+        p.tiles_m = cdiv(a->M, X8Ring::BM);
+        p.tiles_n = a->N / X8Ring::BN;
         const int rc = with_nt_form<nt_fp8_carries>("gemm_nt_mx8", out_f32, f, [&](auto form) {
             using Form = decltype(form);
-            return launch_with_lds<gemm_nt_mx8_kernel<Form::out_f32, Form::f>>(p.tiles_m * p.tiles_n, 512, X8_NST * (size_t)(X8_STAGE + X8_SCALES), st, p);
+            return launch_with_lds<gemm_nt_mx8_kernel<Form::out_f32, Form::f>>(p.tiles_m * p.tiles_n, 512, X8Ring::NST * (size_t)(X8Ring::STAGE + X8_SCALES), st, p);
         });
         if (rc != 0) return rc;
         note_nt_kernel(LNX_NT_KERNEL_MX8);
@@ -672,7 +656,7 @@ static int launch_fp8(const lnx_gemm_args* a, const float* a_scale, const float*
     const int grid = p.tiles_m * p.tiles_n;
     const int rc = with_nt_form<nt_fp8_carries>(who, out_f32, f, [&](auto form) {
         using Form = decltype(form);
-        constexpr size_t lds_mx = F8_NSTAGE * (size_t)(F8_STAGE + F8_SCALES), lds = F8_NSTAGE * (size_t)F8_STAGE;
+        constexpr size_t lds_mx = NarrowRing::NST * (size_t)(NarrowRing::STAGE + F8_SCALES), lds = NarrowRing::NST * (size_t)NarrowRing::STAGE;
         if constexpr (Form::f & F_MXOUT) return launch_with_lds<gemm_nt_fp8_kernel<Form::out_f32, Form::f, true>>(grid, 512, lds_mx, st, p);  // (c8 came with block scales: checked above)
         else if (mx) return launch_with_lds<gemm_nt_fp8_kernel<Form::out_f32, Form::f, true>>(grid, 512, lds_mx, st, p);
         else return launch_with_lds<gemm_nt_fp8_kernel<Form::out_f32, Form::f, false>>(grid, 512, lds, st, p);

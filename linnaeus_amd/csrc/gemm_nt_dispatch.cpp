@@ -98,16 +98,16 @@ static bool big_tile_wins(const GemmP& p, const NtSwitches& sw) {
     const int dc = device_cus();
     const int cus = persistent_cus(dc > 0 ? dc : 256);
     const int64_t rows = cdiv(p.M, 256);
-    const double big = (double)cdiv(rows * (p.N / BN4), (int64_t)cus) * 2.0 * (p.K <= 512 ? 0.97 : 0.88);
+    const double big = (double)cdiv(rows * (p.N / WideRing::BN), (int64_t)cus) * 2.0 * (p.K <= 512 ? 0.97 : 0.88);
     const double small = (double)cdiv(rows * cdiv(p.N, 128), (int64_t)cus);
     return small >= 0.93 * big;  // (the small tile has to win by a margin: measured, a tie on paper goes to the big tile at sm / lg / xl)
 }
 
 static bool nt_v7_preferred(const GemmP& p, int f, bool out_f32, const NtSwitches& sw) {
     const bool two_per_cu = (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 512;
-    const bool big_better = p.N % BN4 == 0 && big_tile_wins(p, sw);
+    const bool big_better = p.N % WideRing::BN == 0 && big_tile_wins(p, sw);
     if (f == F_GELU_BWD && p.act == LNX_ACT_MUL_AUX) return two_per_cu;  // 121.6 -> 115.7 us at the sm fc2 data gradient, also against the 256x256 tile
-    if (f == F_GELU_BWD || f == (F_BIAS | F_C2 | F_GELU)) return two_per_cu && p.N % BN4 == 0 && !big_better;  // only instead of a badly filling big tile
+    if (f == F_GELU_BWD || f == (F_BIAS | F_C2 | F_GELU)) return two_per_cu && p.N % WideRing::BN == 0 && !big_better;  // only instead of a badly filling big tile
     if (f != 0 && f != F_BIAS && !(out_f32 && f == (F_BIAS | F_RES))) return false;
     if (big_better) return false;  // the 256x256 tile (half the fill traffic per FLOP) is the better kernel there
     return two_per_cu;
@@ -115,7 +115,7 @@ static bool nt_v7_preferred(const GemmP& p, int f, bool out_f32, const NtSwitche
 
 static bool nt_v4_ok(const GemmP& p, int f, const NtSwitches& sw) {
     if (!sw.v4 || f == (int)F_GENERIC || p.a_mode == LNX_ADDR_PATCH2) return false;
-    return p.N % BN4 == 0 && p.K % BK4 == 0 && p.K >= 4 * BK4;
+    return p.N % WideRing::BN == 0 && p.K % WideRing::BK == 0 && p.K >= 4 * WideRing::BK;
 }
 
 static bool nt_v2_ok(const GemmP& p, int dtype) {
@@ -139,7 +139,7 @@ NtChoice nt_choose(const GemmP& p, int dtype, bool out_f32) {
     if (nt_v4_ok(p, f, sw) && (sw.v9 == 1 || big_tile_wins(p, sw))) {
         const int dc = device_cus();
         const int64_t cus = dc > 0 ? dc : 256;
-        if (sw.v9 != 0 && nt_v9_ok(p, f, out_f32) && (sw.v9 == 1 || (int64_t)cdiv(p.M, BM4) * (p.N / BN4) * 2 >= 3 * cus)) return {LNX_NT_KERNEL_V9, f};
+        if (sw.v9 != 0 && nt_v9_ok(p, f, out_f32) && (sw.v9 == 1 || (int64_t)cdiv(p.M, WideRing::BM) * (p.N / WideRing::BN) * 2 >= 3 * cus)) return {LNX_NT_KERNEL_V9, f};
         return {LNX_NT_KERNEL_V4, f};
     }
     return {LNX_NT_KERNEL_V2, f};
