@@ -605,12 +605,20 @@ int lnx_prep_blocks(int rows, int ld, int cols, int ld_t, int has_t);
  * and, with soft == NULL, torch.nn.functional.cross_entropy(..., label_smoothing = smoothing) per sample.
  *   dlogits[b, c] = scale * row_scale[b] * class_weight[t_b] * (softmax(logits[b])[c] * sum_c soft[t_b, c] - soft[t_b, c])
  *   loss_sum     += scale * sum_b row_scale[b] * loss[b]                (atomic; caller zeroes it)
+ * `form` selects how the row S of `loss = cw * (lse * sum S - sum S x)`, `dlogits = coef * (exp(x - lse) * sum S - S)` is formed:
+ *   LNX_CE_FORM_DEFAULT    S = soft[t_b, :], or with soft == NULL smoothing / C everywhere plus 1 - smoothing at t_b (torch's label smoothing)
+ *   LNX_CE_FORM_OFF_TARGET S = 1 - smoothing at t_b, smoothing / (C - 1) elsewhere (LabelSmoothingCrossEntropy, loss/basic_loss.py:95-185);
+ *                          soft == NULL, C >= 2; smoothing == 0 gives the bits of the default form
+ *   LNX_CE_FORM_SOFT_ROW   S = soft_target[b, :] (SoftTargetCrossEntropy, loss/basic_loss.py:188-228): sum S is summed, never assumed to be 1, and
+ *                          cw = sum_c soft_target[b, c] * class_weight[c].  target is not read; no soft matrix, no ignore_index.  A row whose
+ *                          sum is not finite (NaN or infinite entries) gives a NaN loss and a zero gradient row
  * -----------------------------------------------------------------------------------*/
+enum { LNX_CE_FORM_DEFAULT = 0, LNX_CE_FORM_OFF_TARGET = 1, LNX_CE_FORM_SOFT_ROW = 2 };
 typedef struct lnx_softce_args {
     int B, C;
     const float* logits;       /* [B, ld] fp32 */
     int64_t ld;
-    const int64_t* target;     /* [B] class indices */
+    const int64_t* target;     /* [B] class indices (not read, may be NULL, with LNX_CE_FORM_SOFT_ROW) */
     const float* soft;         /* [C, C] soft-label matrix (rows sum to 1) or NULL = one-hot */
     float smoothing;           /* soft == NULL only: uniform label smoothing epsilon */
     const float* class_weight; /* [C] or NULL */
@@ -621,6 +629,9 @@ typedef struct lnx_softce_args {
     float* loss_sum;           /* scalar accumulator or NULL */
     float* dlogits;            /* [B, ldd] or NULL */
     int64_t ldd;
+    int form;                  /* LNX_CE_FORM_*; 0 = the two forms above */
+    const float* soft_target;  /* LNX_CE_FORM_SOFT_ROW: [B, ldt] per-sample rows; NULL otherwise */
+    int64_t ldt;               /* >= C */
 } lnx_softce_args;
 int lnx_softce(const lnx_softce_args* args, void* stream);
 /* n <= LNX_SOFTCE_MAX_TASKS independent argument sets (the tasks of the multi-task criterion: train.py's per-task loop over
@@ -1025,6 +1036,7 @@ int lnx_preprocess(const lnx_preprocess_args* args, void* stream);
  * Per task t < n_tasks and row b < B, with the row arithmetic of lnx_softce (same NaN loss / zero gradient for a target outside [0, C)):
  *   class    target[b], or with soft_target the first maximum of soft_target[b, 0..C) (torch.argmax)
  *   raw      = crit_weight[class] * (lse * sum_c S[c] - sum_c S[c] x[c]),  S = soft[class, :] or the smoothed one-hot row; 0 where class == ignore_index
+ *              (form LNX_CE_FORM_SOFT_ROW: S = soft_target[b, :] and sum_c soft_target[b, c] * crit_weight[c] in place of crit_weight[class])
  *   null     = target[b] == 0, or soft_target[b, 0] > 0.5
  *   keep     = !null || draws[t * B + b] < prob          (prob >= 1: everything is kept, prob <= 0: no null row; draws is read for 0 < prob < 1 only)
  *   masked   = keep ? raw : 0        (mask_mul != 0, the PHASE1_MASK_NULL_LOSS branch: raw * keep, so that a NaN survives the mask)
@@ -1061,6 +1073,8 @@ typedef struct lnx_hier_loss_task {
     int p_cw, p_w;              /* 0..3, p_cw <= p_w: the power of cw in the logged masked loss and in the weighted loss (finding F13) */
     float* dlogits;             /* lnx_hier_loss_bwd: [B, ldd] fp32, columns >= C are not written; NULL = no gradient for this task */
     int64_t ldd;
+    int form;                   /* LNX_CE_FORM_* of lnx_softce_args; 0 = the forms above.  LNX_CE_FORM_SOFT_ROW needs soft_target, which the
+                                   backward reads again; null stays soft_target[b, 0] > 0.5 and the class in the flags the first maximum */
 } lnx_hier_loss_task;
 typedef struct lnx_hier_loss_args {
     int dtype;            /* of every task's logits: 0 = fp32, 1 = bf16 */

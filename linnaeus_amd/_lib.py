@@ -71,8 +71,12 @@ class SoftCEArgs(C.Structure):
         ("row_scale", C.c_void_p), ("scale", C.c_float),
         ("loss", C.c_void_p), ("loss_sum", C.c_void_p),
         ("dlogits", C.c_void_p), ("ldd", C.c_int64),
+        ("form", C.c_int), ("soft_target", C.c_void_p), ("ldt", C.c_int64),
     ]
 
+
+# lnx_softce_args.form / lnx_hier_loss_task.form (the LNX_CE_FORM_* enum of include/lnx.h): how the row S is formed
+CE_FORM_DEFAULT, CE_FORM_OFF_TARGET, CE_FORM_SOFT_ROW = range(3)
 
 ADAMW_MAX_GROUPS = 16
 
@@ -188,7 +192,7 @@ HL_NULL_TOTAL, HL_NULL_INCLUDED, HL_COUNTS = 8, 9, 10
 class HierLossTask(C.Structure):  # == lnx_hier_loss_task
     _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("C", C.c_int), ("target", C.c_void_p), ("soft_target", C.c_void_p), ("ldt", C.c_int64),
                 ("soft", C.c_void_p), ("smoothing", C.c_float), ("crit_weight", C.c_void_p), ("ignore_index", C.c_int64), ("class_weight", C.c_void_p),
-                ("n_cw", C.c_int), ("p_cw", C.c_int), ("p_w", C.c_int), ("dlogits", C.c_void_p), ("ldd", C.c_int64)]
+                ("n_cw", C.c_int), ("p_cw", C.c_int), ("p_w", C.c_int), ("dlogits", C.c_void_p), ("ldd", C.c_int64), ("form", C.c_int)]
 
 
 class HierLossArgs(C.Structure):  # == lnx_hier_loss_args

@@ -32,8 +32,17 @@ __device__ __forceinline__ float mul_pow(float m, float cw, int p) {
     return m;
 }
 
-// the soft row (or smoothed one-hot row) entry of column c
-__device__ __forceinline__ float soft_at(const float* srow, int c, int64_t t, float on, float off) { return srow ? srow[c] : (c == t ? on + off : off); }
+// the soft row (or smoothed one-hot row) entry of column c: `at` at the class, `off` elsewhere
+__device__ __forceinline__ float soft_at(const float* srow, int c, int64_t t, float at, float off) { return srow ? srow[c] : (c == t ? at : off); }
+
+// (at, off) of the smoothed one-hot row: torch's eps / C everywhere plus 1 - eps at the class, or with LNX_CE_FORM_OFF_TARGET
+// 1 - eps at the class and eps / (C - 1) elsewhere (LabelSmoothingCrossEntropy)
+__device__ __forceinline__ void smooth_pair(const lnx_hier_loss_task& k, float& at, float& off) {
+    const bool off_target = k.form == LNX_CE_FORM_OFF_TARGET;
+    const float on = 1.0f - k.smoothing;
+    off = k.smoothing / (float)(off_target ? k.C - 1 : k.C);
+    at = off_target ? on : on + off;
+}
 
 template <typename T>
 __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_args a) {
@@ -47,10 +56,12 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     // ---- class, null flag, class weight of the sample
     int64_t t;
     bool null;
-    float cw = 1.0f;
-    if (k.soft_target) {
-        const float* st = k.soft_target + (int64_t)b * k.ldt;
-        float bv = -INFINITY, dot = 0.f;
+    float cw = 1.0f, cwc = 1.0f;
+    // LNX_CE_FORM_SOFT_ROW: the sample's own target row is S, and <row, crit_weight> the criterion's class weight
+    const bool soft_row = k.form == LNX_CE_FORM_SOFT_ROW;
+    const float* st = k.soft_target ? k.soft_target + (int64_t)b * k.ldt : nullptr;
+    if (st) {
+        float bv = -INFINITY, dot = 0.f, cdot = 0.f;
         int bi = 0x7fffffff;
         for (int c = tid; c < Cn; c += HL_T) {
             const float v = st[c];
@@ -59,6 +70,7 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
                 bi = c;
             }
             if (k.class_weight) dot = fmaf(v, k.class_weight[c], dot);
+            if (soft_row && k.crit_weight) cdot = fmaf(v, k.crit_weight[c], cdot);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -85,6 +97,7 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
         t = bi == 0x7fffffff ? 0 : bi;  // (a row of NaN / -inf only: torch returns an index too; 0 keeps every read in range)
         null = st[0] > 0.5f;
         if (k.class_weight) cw = hl_block_reduce(dot, red, false);
+        if (soft_row && k.crit_weight) cwc = hl_block_reduce(cdot, red, false);
     } else {
         t = k.target[b];
         null = t == 0;
@@ -95,10 +108,11 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     }
 
     // ---- the criterion (softce_row)
-    const bool bad = t < 0 || t >= Cn;
-    const bool ignored = k.ignore_index >= 0 && t == k.ignore_index;
-    const float* srow = (k.soft != nullptr && !bad) ? k.soft + t * (int64_t)Cn : nullptr;
-    const float on = 1.0f - k.smoothing, off = k.smoothing / (float)Cn;
+    bool bad = t < 0 || t >= Cn;
+    const bool ignored = k.ignore_index >= 0 && t == k.ignore_index && !soft_row;
+    const float* srow = (k.soft != nullptr && !bad && !soft_row) ? k.soft + t * (int64_t)Cn : nullptr;
+    float at, off;
+    smooth_pair(k, at, off);
     float mx = -INFINITY;
     for (int c = tid; c < Cn; c += HL_T) mx = fmaxf(mx, to_f(x[c]));
     mx = hl_block_reduce(mx, red, true);
@@ -106,7 +120,7 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     for (int c = tid; c < Cn; c += HL_T) {
         const float v = to_f(x[c]);
         se += __expf(v - mx);
-        const float sv = soft_at(srow, c, t, on, off);
+        const float sv = soft_row ? st[c] : soft_at(srow, c, t, at, off);
         sx = fmaf(sv, v, sx);
         ss += sv;
     }
@@ -115,7 +129,8 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     ss = hl_block_reduce(ss, red, false);
     if (tid != 0) return;
     const float lse = mx + __logf(se);
-    const float cwc = (k.crit_weight != nullptr && !bad) ? k.crit_weight[t] : 1.0f;
+    if (soft_row) bad = !(fabsf(ss) < INFINITY);  // NaN or infinite entries in the row: NaN loss, zero gradient row
+    else cwc = (k.crit_weight != nullptr && !bad) ? k.crit_weight[t] : 1.0f;
     const float raw = bad ? NAN : (ignored ? 0.f : cwc * (lse * ss - sx));
     const float gcrit = (ignored || bad) ? 0.f : cwc;
 
@@ -124,7 +139,7 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     const float masked = a.mask_mul ? raw * (keep ? 1.0f : 0.0f) : (keep ? raw : 0.0f);
     const float m_cw = mul_pow(masked, cw, k.p_cw);
     const float m_w = mul_pow(m_cw, cw, k.p_w - k.p_cw);
-    const float coef = keep ? mul_pow(gcrit, cw, k.p_w) : 0.0f;
+    const float coef = (keep && !(soft_row && bad)) ? mul_pow(gcrit, cw, k.p_w) : 0.0f;  // (a row that is not finite has no finite cw either)
     const unsigned flags = (null ? 1u : 0u) | (keep ? 2u : 0u) | (masked != 0.0f ? 4u : 0u) | (bad ? 0u : (unsigned)t << 3);  // the class for the backward
     float* w = a.ws + (int64_t)blockIdx.y * LNX_HL_WS_ROWS * a.B + b;
     w[(int64_t)LNX_HL_WS_RAW * a.B] = raw;
@@ -209,11 +224,20 @@ __global__ __launch_bounds__(HL_T) void hier_bwd_kernel(const lnx_hier_loss_args
     const float g = go[0] * a.out[LNX_HL_OUT_SCALE * LNX_SOFTCE_MAX_TASKS + blockIdx.y] * coef;
     const T* x = static_cast<const T*>(k.logits) + (int64_t)b * k.ld;
     const int64_t t = __float_as_uint(w[(int64_t)LNX_HL_WS_FLAGS * a.B]) >> 3;  // the forward's class (coef != 0: it was in range)
+    if (k.form == LNX_CE_FORM_SOFT_ROW) {  // S is the sample's target row, read again
+        const float* st = k.soft_target + (int64_t)b * k.ldt;
+        for (int c = tid; c < Cn; c += HL_T) {
+            const float p = __expf(to_f(x[c]) - lse);
+            d[c] = g * (p * ss - st[c]);
+        }
+        return;
+    }
     const float* srow = k.soft ? k.soft + t * (int64_t)Cn : nullptr;
-    const float on = 1.0f - k.smoothing, off = k.smoothing / (float)Cn;
+    float at, off;
+    smooth_pair(k, at, off);
     for (int c = tid; c < Cn; c += HL_T) {
         const float p = __expf(to_f(x[c]) - lse);
-        d[c] = g * (p * ss - soft_at(srow, c, t, on, off));
+        d[c] = g * (p * ss - soft_at(srow, c, t, at, off));
     }
 }
 
@@ -239,6 +263,17 @@ int hier_check(const lnx_hier_loss_args* a, const char* who) {
                   k.class_weight ? "given" : "NULL", k.n_cw, k.p_w);
         LNX_CHECK(!(k.class_weight && k.soft_target) || k.n_cw >= k.C, "%s: task %d has n_cw=%d < C=%d with soft_target", who, t, k.n_cw, k.C);
         LNX_CHECK(k.dlogits == nullptr || k.ldd >= k.C, "%s: task %d has ldd=%lld < C=%d", who, t, (long long)k.ldd, k.C);
+        LNX_CHECK(k.form == LNX_CE_FORM_DEFAULT || k.form == LNX_CE_FORM_OFF_TARGET || k.form == LNX_CE_FORM_SOFT_ROW,
+                  "%s: task %d has form=%d (0 = default, 1 = off-target smoothing, 2 = soft row)", who, t, k.form);
+        if (k.form == LNX_CE_FORM_OFF_TARGET) {
+            LNX_CHECK(k.C >= 2, "%s: off-target smoothing needs C >= 2, task %d has C=%d (smoothing / (C - 1))", who, t, k.C);
+            LNX_CHECK(k.soft == nullptr, "%s: off-target smoothing excludes a [C, C] soft matrix (task %d)", who, t);
+        }
+        if (k.form == LNX_CE_FORM_SOFT_ROW) {
+            LNX_CHECK(k.soft_target, "%s: the soft-row form needs soft_target (task %d)", who, t);
+            LNX_CHECK(k.soft == nullptr, "%s: the soft-row form excludes a [C, C] soft matrix (task %d)", who, t);
+            LNX_CHECK(k.ignore_index < 0, "%s: the soft-row form has no ignore_index (task %d has %lld)", who, t, (long long)k.ignore_index);
+        }
     }
     return 0;
 }

@@ -24,28 +24,40 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
 __device__ __forceinline__ void softce_row(const lnx_softce_args& a, const int b) {
     __shared__ float red[4];
     const float* x = a.logits + (int64_t)b * a.ld;
-    const int64_t t = a.target[b];
-    const bool bad = t < 0 || t >= a.C;  // out-of-range targets produce NaN loss and zero gradient (the host checks them when asked to)
-    const bool ignored = a.ignore_index >= 0 && t == a.ignore_index;
+    // LNX_CE_FORM_SOFT_ROW: the row S is the sample's own target row (SoftTargetCrossEntropy); target is not read
+    const float* st = a.form == LNX_CE_FORM_SOFT_ROW ? a.soft_target + (int64_t)b * a.ldt : nullptr;
+    const int64_t t = st ? 0 : a.target[b];
+    bool bad = t < 0 || t >= a.C;  // out-of-range targets produce NaN loss and zero gradient (the host checks them when asked to)
+    const bool ignored = a.ignore_index >= 0 && t == a.ignore_index && !st;
     const float* srow = (a.soft != nullptr && !bad) ? a.soft + t * (int64_t)a.C : nullptr;
-    const float on = 1.0f - a.smoothing, off = a.smoothing / (float)a.C;
+    // at the class / elsewhere: torch's uniform smoothing, or LabelSmoothingCrossEntropy's eps / (C - 1) off the target only
+    const bool off_target = a.form == LNX_CE_FORM_OFF_TARGET;
+    const float on = 1.0f - a.smoothing, off = a.smoothing / (float)(off_target ? a.C - 1 : a.C);
+    const float at = off_target ? on : on + off;
 
     float mx = -INFINITY;
     for (int c = threadIdx.x; c < a.C; c += 256) mx = fmaxf(mx, x[c]);
     mx = block_reduce(mx, red, true);
-    float se = 0.f, sx = 0.f, ss = 0.f;  // sum exp, sum S*x, sum S
+    float se = 0.f, sx = 0.f, ss = 0.f, sw = 0.f;  // sum exp, sum S*x, sum S, sum S*class_weight (soft rows)
     for (int c = threadIdx.x; c < a.C; c += 256) {
         const float v = x[c];
         se += __expf(v - mx);
-        const float sv = srow ? srow[c] : (c == t ? on + off : off);
+        const float sv = st ? st[c] : (srow ? srow[c] : (c == t ? at : off));
         sx = fmaf(sv, v, sx);
         ss += sv;
+        if (st && a.class_weight) sw = fmaf(sv, a.class_weight[c], sw);
     }
     se = block_reduce(se, red, false);
     sx = block_reduce(sx, red, false);
     ss = block_reduce(ss, red, false);
     const float lse = mx + __logf(se);
-    const float cw = (a.class_weight != nullptr && !bad) ? a.class_weight[t] : 1.0f;
+    float cw;
+    if (st) {
+        bad = !(fabsf(ss) < INFINITY);  // NaN or infinite entries: NaN loss, zero gradient row
+        cw = a.class_weight ? block_reduce(sw, red, false) : 1.0f;
+    } else {
+        cw = (a.class_weight != nullptr && !bad) ? a.class_weight[t] : 1.0f;
+    }
     float loss = bad ? NAN : (ignored ? 0.f : cw * (lse * ss - sx));
     const float g = (ignored || bad) ? 0.f : a.scale * (a.row_scale ? a.row_scale[b] : 1.0f) * cw;
     if (threadIdx.x == 0) {
@@ -55,9 +67,13 @@ __device__ __forceinline__ void softce_row(const lnx_softce_args& a, const int b
     if (a.dlogits) {
         float* d = a.dlogits + (int64_t)b * a.ldd;
         const float inv = 1.0f / se;
+        if (st && bad) {  // (the row itself is not finite: g * (p * ss - S) would be NaN)
+            for (int c = threadIdx.x; c < a.C; c += 256) d[c] = 0.0f;
+            return;
+        }
         for (int c = threadIdx.x; c < a.C; c += 256) {
             const float p = __expf(x[c] - mx) * inv;
-            const float sv = srow ? srow[c] : (c == t ? on + off : off);
+            const float sv = st ? st[c] : (srow ? srow[c] : (c == t ? at : off));
             d[c] = g * (p * ss - sv);
         }
     }
@@ -76,16 +92,35 @@ __global__ __launch_bounds__(256) void softce_multi_kernel(const SoftceMulti m) 
 
 }  // namespace
 
+// the argument checks of both entry points, before any launch
+static int softce_check(const lnx_softce_args* a, const char* who, int i) {
+    const bool soft_row = a->form == LNX_CE_FORM_SOFT_ROW;
+    LNX_CHECK(a->form == LNX_CE_FORM_DEFAULT || a->form == LNX_CE_FORM_OFF_TARGET || soft_row, "%s: form=%d in set %d (0 = default, 1 = off-target smoothing, 2 = soft row)", who,
+              a->form, i);
+    LNX_CHECK(a->logits && (a->target || soft_row), "%s: null operand in set %d", who, i);
+    LNX_CHECK(a->B > 0 && a->C > 0 && a->ld >= a->C, "%s: bad shape B=%d C=%d ld=%lld in set %d", who, a->B, a->C, (long long)a->ld, i);
+    LNX_CHECK(a->dlogits == nullptr || a->ldd >= a->C, "%s: ldd < C in set %d", who, i);
+    LNX_CHECK(a->smoothing >= 0.f && a->smoothing < 1.f, "%s: smoothing must be in [0, 1)", who);
+    if (a->form == LNX_CE_FORM_OFF_TARGET) {
+        LNX_CHECK(a->C >= 2, "%s: off-target smoothing needs C >= 2, set %d has C=%d (smoothing / (C - 1))", who, i, a->C);
+        LNX_CHECK(a->soft == nullptr, "%s: off-target smoothing excludes a [C, C] soft matrix (set %d)", who, i);
+    }
+    if (soft_row) {
+        LNX_CHECK(a->soft_target, "%s: the soft-row form needs soft_target (set %d)", who, i);
+        LNX_CHECK(a->ldt >= a->C, "%s: ldt=%lld < C=%d in set %d", who, (long long)a->ldt, a->C, i);
+        LNX_CHECK(a->soft == nullptr, "%s: the soft-row form excludes a [C, C] soft matrix (set %d)", who, i);
+        LNX_CHECK(a->ignore_index < 0, "%s: the soft-row form has no ignore_index (set %d has %lld)", who, i, (long long)a->ignore_index);
+    }
+    return 0;
+}
+
 extern "C" int lnx_softce_multi(const lnx_softce_args* args, int n, void* stream) {
     LNX_CHECK(args && n > 0 && n <= LNX_SOFTCE_MAX_TASKS, "lnx_softce_multi: 1..%d argument sets, got %d", LNX_SOFTCE_MAX_TASKS, n);
     SoftceMulti m;
     int bmax = 0;
     for (int i = 0; i < n; ++i) {
         const lnx_softce_args* a = args + i;
-        LNX_CHECK(a->logits && a->target, "lnx_softce_multi: null operand in set %d", i);
-        LNX_CHECK(a->B > 0 && a->C > 0 && a->ld >= a->C, "lnx_softce_multi: bad shape B=%d C=%d ld=%lld in set %d", a->B, a->C, (long long)a->ld, i);
-        LNX_CHECK(a->dlogits == nullptr || a->ldd >= a->C, "lnx_softce_multi: ldd < C in set %d", i);
-        LNX_CHECK(a->smoothing >= 0.f && a->smoothing < 1.f, "lnx_softce_multi: smoothing must be in [0, 1)");
+        if (int rc = softce_check(a, "lnx_softce_multi", i)) return rc;
         m.a[i] = *a;
         bmax = a->B > bmax ? a->B : bmax;
     }
@@ -95,10 +130,8 @@ extern "C" int lnx_softce_multi(const lnx_softce_args* args, int n, void* stream
 }
 
 extern "C" int lnx_softce(const lnx_softce_args* a, void* stream) {
-    LNX_CHECK(a && a->logits && a->target, "lnx_softce: null operand");
-    LNX_CHECK(a->B > 0 && a->C > 0 && a->ld >= a->C, "lnx_softce: bad shape B=%d C=%d ld=%lld", a->B, a->C, (long long)a->ld);
-    LNX_CHECK(a->dlogits == nullptr || a->ldd >= a->C, "lnx_softce: ldd < C");
-    LNX_CHECK(a->smoothing >= 0.f && a->smoothing < 1.f, "lnx_softce: smoothing must be in [0, 1)");
+    LNX_CHECK(a, "lnx_softce: null operand");
+    if (int rc = softce_check(a, "lnx_softce", 0)) return rc;
     hipLaunchKernelGGL(softce_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a);
     LNX_LAUNCH_CHECK();
     return 0;

@@ -3,6 +3,10 @@ of the train step as single HIP launches (`lnx_softce`, csrc/loss.hip) behind th
 
   TaxonomyAwareLabelSmoothingCE  <- linnaeus/loss/taxonomy_label_smoothing.py:131-408 (same constructor, same
                                     [B] per-sample return, same ignore_index / class-weight behaviour, same errors)
+  CrossEntropyLoss, LabelSmoothingCrossEntropy, SoftTargetCrossEntropy
+                                 <- linnaeus/loss/basic_loss.py:15-228, the other three names of LOSS.TASK_SPECIFIC.*.FUNCS
+  get_loss_function / prepare_loss_functions <- linnaeus/loss/utils.py:58-294; convert_criteria maps criteria the reference
+                                    built onto the classes here
   multitask_cross_entropy        <- the "per-task mean CE, static task weights, summed" loss of the throughput
                                     protocol; forward value and dlogits of all tasks without torch's
                                     log_softmax / nll_loss kernel chain
@@ -25,7 +29,7 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_scale, scale, loss, loss_sum, dlogits):
+def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_scale, scale, loss, loss_sum, dlogits, form=0, soft_target=None):
     if not logits.is_cuda:
         raise L.LnxError("linnaeus_amd.loss has no CPU path: logits must be on the GPU")
     a.B, a.C = logits.shape
@@ -37,6 +41,7 @@ def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_sc
     a.row_scale, a.scale = _ptr(row_scale), float(scale)
     a.loss, a.loss_sum = _ptr(loss), _ptr(loss_sum)
     a.dlogits, a.ldd = _ptr(dlogits), (dlogits.stride(0) if dlogits is not None else 0)
+    a.form, a.soft_target, a.ldt = int(form), _ptr(soft_target), (soft_target.stride(0) if soft_target is not None else 0)
 
 
 def _launch(*args):
@@ -68,20 +73,20 @@ class _SoftCE(torch.autograd.Function):
     """per-sample loss [B]; the unit gradient (d loss[b] / d logits[b, :]) is produced by the same launch"""
 
     @staticmethod
-    def forward(ctx, logits, target, soft, class_weight, ignore_index, smoothing):
+    def forward(ctx, logits, target, soft, class_weight, ignore_index, smoothing, form=0, soft_target=None):
         x = _as_rows(logits)
         B, Cn = x.shape
         loss = torch.empty(B, device=x.device, dtype=torch.float32)
         need = logits.requires_grad
         unit = torch.empty(B, Cn, device=x.device, dtype=torch.float32) if need else None
-        _launch(x, target, soft, smoothing, class_weight, ignore_index, None, 1.0, loss, None, unit)
+        _launch(x, target, soft, smoothing, class_weight, ignore_index, None, 1.0, loss, None, unit, form, soft_target)
         ctx.unit = unit
         ctx.in_dtype = logits.dtype
         return loss
 
     @staticmethod
     def backward(ctx, go):
-        return (ctx.unit * go.unsqueeze(1)).to(ctx.in_dtype), None, None, None, None, None
+        return (ctx.unit * go.unsqueeze(1)).to(ctx.in_dtype), None, None, None, None, None, None, None
 
 
 class TaxonomyAwareLabelSmoothingCE(nn.Module):
@@ -133,7 +138,7 @@ class TaxonomyAwareLabelSmoothingCE(nn.Module):
             if self.weight.device != logits.device:
                 self.weight = self.class_weight = self.weight.to(logits.device)
             cw = self.weight
-        loss = _SoftCE.apply(logits, target, self.soft_labels, cw, self.ignore_index, 0.0)
+        loss = _SoftCE.apply(logits, target, self.soft_labels, cw, self.ignore_index, 0.0, L.CE_FORM_DEFAULT, None)
         # Out-of-range targets surface as NaN rows from the kernel; the reference raises IndexError for them
         # (taxonomy_label_smoothing.py:330-343, itself a host sync).  This check is ONE host<->device sync per call:
         # set `validate_targets = False` on the criterion to keep the launch queue asynchronous (NaN rows then
@@ -143,6 +148,214 @@ class TaxonomyAwareLabelSmoothingCE(nn.Module):
             if bad:
                 raise IndexError(f"{bad} target indices out of bounds [0, {self.num_classes - 1}].")
         return loss
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The reference's other three criteria (loss/basic_loss.py), the default of LOSS.TASK_SPECIFIC.{TRAIN,VAL}.FUNCS among them.
+# Same constructor arguments in the same order, same attributes, same [B] per-sample return; each forward is ONE lnx_softce
+# launch that also leaves the unit gradient, as TaxonomyAwareLabelSmoothingCE above.
+# Stated differences from the reference, common to the three:
+#   * a target outside [0, C) (torch's -100 included: only `ignore_index` is ignored) gives a NaN loss and a zero gradient row;
+#     with `validate_targets` (default True) the call then raises IndexError after ONE host read, set it to False to keep the
+#     launch queue asynchronous;
+#   * a `weight` whose length is not C raises ValueError at the first call (the reference indexes it and fails, or not, later).
+# ----------------------------------------------------------------------------------------------------------------------
+class _BasicCriterion(nn.Module):
+    _form = L.CE_FORM_DEFAULT
+
+    def _device_weight(self, dev, num_classes: int):
+        """the [C] fp32 class weight on `dev`, uploaded once per (weight object, device); None when weights do not apply"""
+        if self.weight is None or not self.apply_class_weights:
+            return None
+        w = self.weight
+        cached = getattr(self, "_w_dev", None)
+        if cached is None or cached[0] is not w or cached[1].device != dev:
+            v = w if isinstance(w, torch.Tensor) else torch.tensor(w, dtype=torch.float32)
+            cached = (w, v.detach().to(dev, torch.float32).contiguous())
+            self._w_dev = cached
+        if cached[1].dim() != 1 or cached[1].numel() != num_classes:
+            raise ValueError(f"{type(self).__name__}: weight has {tuple(cached[1].shape)} entries, the logits have {num_classes} classes")
+        return cached[1]
+
+    @staticmethod
+    def _class_indices(logits, target):
+        if target.dim() == 2:
+            if target.shape[1] != logits.size(1):
+                raise ValueError(f"Target tensor shape {target.shape} incompatible with input shape {logits.shape}")
+            target = target.argmax(dim=1)
+        elif target.dim() != 1:
+            raise ValueError(f"Target tensor has invalid shape {target.shape}. Expected 1D indices or [B, C] one-hot/soft-representing-one-class.")
+        return target.to(logits.device, torch.long).contiguous()
+
+    def _hard(self, logits, target, smoothing: float):
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+            raise TypeError(f"{type(self).__name__}: logits must be a [B, C] tensor")
+        target = self._class_indices(logits, target)
+        num_classes = logits.shape[1]
+        cw = self._device_weight(logits.device, num_classes)
+        loss = _SoftCE.apply(logits, target, None, cw, self.ignore_index, smoothing, self._form, None)
+        if self.validate_targets and torch.isnan(loss).any():  # ONE host read per call, as TaxonomyAwareLabelSmoothingCE
+            bad = ((target < 0) | (target >= num_classes)).sum().item()
+            if bad:
+                raise IndexError(f"{bad} target indices out of bounds [0, {num_classes - 1}].")
+        return loss
+
+
+class CrossEntropyLoss(_BasicCriterion):
+    """Per-sample cross entropy [B] (loss/basic_loss.py:15-92): `[B]` integer targets of any integer dtype, or `[B, C]` targets
+    that are arg-maxed; rows whose class is `ignore_index` give loss 0 and gradient 0; `weight[class]` multiplies the loss only
+    when `weight is not None and apply_class_weights`.  Differences from the reference: see the comment above this class."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, apply_class_weights: bool = False, ignore_index: Optional[int] = None):
+        super().__init__()
+        self.ignore_index = ignore_index
+        self.criterion = nn.CrossEntropyLoss(weight=None, reduction="none", ignore_index=ignore_index if ignore_index is not None else -100)
+        self.weight = weight
+        self.apply_class_weights = apply_class_weights
+        self.validate_targets = True
+
+    def forward(self, input, target) -> torch.Tensor:
+        return self._hard(input, target, 0.0)
+
+
+class LabelSmoothingCrossEntropy(_BasicCriterion):
+    """Per-sample label-smoothing cross entropy [B] (loss/basic_loss.py:95-185): `1 - smoothing` on the class and
+    `smoothing / (C - 1)` on every other one (not torch's `smoothing / C` everywhere), targets, `ignore_index` and `weight` as
+    CrossEntropyLoss.  C == 1 is refused by name (the reference divides by zero).  Other differences: see the comment above."""
+    _form = L.CE_FORM_OFF_TARGET
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, smoothing: float = 0.1, apply_class_weights: bool = False,
+                 ignore_index: Optional[int] = None, config: Optional[Any] = None):
+        super().__init__()
+        assert 0.0 <= smoothing < 1.0
+        self.smoothing = smoothing
+        self.confidence = 1.0 - smoothing
+        self.weight = weight
+        self.apply_class_weights = apply_class_weights
+        self.ignore_index = ignore_index
+        self.config = config
+        self.validate_targets = True
+
+    def forward(self, x, target) -> torch.Tensor:
+        return self._hard(x, target, float(self.smoothing))
+
+
+class SoftTargetCrossEntropy(_BasicCriterion):
+    """Per-sample cross entropy against a `[B, C]` soft distribution (mixup / cutmix targets; loss/basic_loss.py:188-228):
+    `-(target * log_softmax(x)).sum(1)`, times `<target, weight>` when `weight is not None and apply_class_weights`.  The row's
+    sum is summed, not assumed to be 1 (gradient `softmax * sum(target) - target`).  There is no `ignore_index`.
+    Differences from the reference: a `[B]` target raises ValueError (the reference broadcasts it against the logits); a row
+    with NaN or infinite entries gives a NaN loss and a zero gradient row; a `weight` whose length is not C raises ValueError."""
+    _form = L.CE_FORM_SOFT_ROW
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, apply_class_weights: bool = False):
+        super().__init__()
+        self.weight = weight
+        self.apply_class_weights = apply_class_weights
+
+    @staticmethod
+    def _rows(logits, target):
+        if target.dim() != 2 or target.shape != logits.shape:
+            raise ValueError(f"SoftTargetCrossEntropy needs [B, C] targets of the logits' shape {tuple(logits.shape)}, got {tuple(target.shape)}")
+        y = target.to(logits.device, torch.float32)
+        return y if y.stride(1) == 1 else y.contiguous()
+
+    def forward(self, x, target) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise TypeError("SoftTargetCrossEntropy: logits must be a [B, C] tensor")
+        y = self._rows(x, target)
+        cw = self._device_weight(x.device, x.shape[1])
+        return _SoftCE.apply(x, None, None, cw, None, 0.0, self._form, y)
+
+
+LOSS_FUNCTIONS = ("CrossEntropyLoss", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "TaxonomyAwareLabelSmoothing")
+
+
+def get_loss_function(loss_type: str, config, class_weights=None, is_train: bool = True, task_key: Optional[str] = None,
+                      taxonomy_matrices: Optional[Dict[str, torch.Tensor]] = None, ignore_index: Optional[int] = None, taxonomy_tree=None) -> nn.Module:
+    """The criterion `loss_type` names (loss/utils.py:153-294: the same name table, the same LOSS.GRAD_WEIGHTING.CLASS.TRAIN / .VAL
+    switch).  A class-weight dict {class: weight} becomes a [max index + 1] tensor with missing entries 1.0; a tensor is passed on.
+    `taxonomy_tree` is accepted and unused, as in the reference."""
+    apply_class_weights = config.LOSS.GRAD_WEIGHTING.CLASS.TRAIN if is_train else config.LOSS.GRAD_WEIGHTING.CLASS.VAL
+    weight = None
+    if apply_class_weights and isinstance(class_weights, dict) and class_weights:
+        try:
+            table = {int(k): float(v) for k, v in class_weights.items()}
+            weight = torch.tensor([table.get(i, 1.0) for i in range(max(table) + 1)], dtype=torch.float32)
+        except (ValueError, TypeError):
+            weight = None
+    elif isinstance(class_weights, torch.Tensor):
+        weight = class_weights
+    if loss_type == "CrossEntropyLoss":
+        return CrossEntropyLoss(weight=weight, apply_class_weights=apply_class_weights, ignore_index=ignore_index)
+    if loss_type == "SoftTargetCrossEntropy":
+        return SoftTargetCrossEntropy(weight=weight, apply_class_weights=apply_class_weights)
+    if loss_type == "LabelSmoothingCrossEntropy":
+        smoothing = config.MODEL.LABEL_SMOOTHING if hasattr(config.MODEL, "LABEL_SMOOTHING") else 0.1
+        return LabelSmoothingCrossEntropy(smoothing=smoothing, weight=weight, apply_class_weights=apply_class_weights, ignore_index=ignore_index,
+                                          config=config)
+    if loss_type == "TaxonomyAwareLabelSmoothing":
+        if not task_key:
+            raise ValueError("task_key must be provided for TaxonomyAwareLabelSmoothing")
+        if taxonomy_matrices is None or task_key not in taxonomy_matrices:
+            raise ValueError(f"No taxonomy smoothing matrix found for task '{task_key}'")
+        return TaxonomyAwareLabelSmoothingCE(soft_label_matrix=taxonomy_matrices[task_key], weight=weight, apply_class_weights=apply_class_weights,
+                                             ignore_index=ignore_index, config=config)
+    raise ValueError(f"Unsupported loss function type: {loss_type}")
+
+
+def _per_task(value, task_keys, name: str) -> list:
+    if isinstance(value, (list, tuple)):
+        if len(value) != len(task_keys):
+            raise ValueError(f"{name} must match number of tasks. Expected {len(task_keys)}, got {len(value)}")
+        return list(value)
+    return [value for _ in task_keys]
+
+
+def prepare_loss_functions(config, class_weights_train=None, class_weights_val=None, taxonomy_matrices: Optional[Dict[str, torch.Tensor]] = None):
+    """(criteria_train, criteria_val), {task: criterion} over config.DATA.TASK_KEYS_H5 from LOSS.TASK_SPECIFIC.TRAIN.FUNCS / VAL.FUNCS
+    (loss/utils.py:58-150), with ignore_index = 0 under TRAIN.PHASE1_MASK_NULL_LOSS.  The class weights are {task: {class: weight}}
+    (or tensors) per split: computing them from label counts (calculate_class_weights) stays with the caller."""
+    task_keys = list(config.DATA.TASK_KEYS_H5)
+    ignore_index = 0 if getattr(config.TRAIN, "PHASE1_MASK_NULL_LOSS", False) else None
+    out = []
+    for is_train, funcs, cws in ((True, config.LOSS.TASK_SPECIFIC.TRAIN.FUNCS, class_weights_train), (False, config.LOSS.TASK_SPECIFIC.VAL.FUNCS, class_weights_val)):
+        funcs = _per_task(funcs, task_keys, "TRAIN.FUNCS" if is_train else "VAL.FUNCS")
+        out.append({t: get_loss_function(f, config, (cws or {}).get(t), is_train, t, taxonomy_matrices, ignore_index) for f, t in zip(funcs, task_keys)})
+    return out[0], out[1]
+
+
+def convert_criterion(crit):
+    """one criterion built by the reference -> the class here, recognised by its class name and read through its attributes"""
+    if isinstance(crit, (_BasicCriterion, TaxonomyAwareLabelSmoothingCE)) or type(crit) is nn.CrossEntropyLoss:
+        return crit
+    name = type(crit).__name__
+    try:
+        if name == "CrossEntropyLoss":
+            return CrossEntropyLoss(weight=crit.weight, apply_class_weights=crit.apply_class_weights, ignore_index=crit.ignore_index)
+        if name == "LabelSmoothingCrossEntropy":
+            return LabelSmoothingCrossEntropy(weight=crit.weight, smoothing=crit.smoothing, apply_class_weights=crit.apply_class_weights,
+                                              ignore_index=crit.ignore_index, config=getattr(crit, "config", None))
+        if name == "SoftTargetCrossEntropy":
+            return SoftTargetCrossEntropy(weight=crit.weight, apply_class_weights=crit.apply_class_weights)
+        if name == "TaxonomyAwareLabelSmoothingCE":
+            return TaxonomyAwareLabelSmoothingCE(crit.soft_labels, weight=crit.weight, apply_class_weights=crit.apply_class_weights,
+                                                 ignore_index=crit.ignore_index, config=getattr(crit, "config", None))
+    except AttributeError as e:
+        raise L.LnxError(f"convert_criteria: {name} lacks an attribute of the reference's class of that name: {e}") from None
+    raise L.LnxError(f"convert_criteria: criterion {name} is not supported ({ACCEPTED_CRITERIA})")
+
+
+def convert_criteria(criteria):
+    """{task: criterion} built by the reference's own prepare_loss_functions -> the same dict over the classes here.  The classes of
+    this module and torch.nn.CrossEntropyLoss instances are returned unchanged; anything else is refused by name (LnxError)."""
+    if isinstance(criteria, dict):
+        return {t: convert_criterion(c) for t, c in criteria.items()}
+    return convert_criterion(criteria)
+
+
+ACCEPTED_CRITERIA = ("TaxonomyAwareLabelSmoothingCE, CrossEntropyLoss, LabelSmoothingCrossEntropy, SoftTargetCrossEntropy "
+                     "or torch.nn.CrossEntropyLoss(reduction='none')")
 
 
 class _MultiCE(torch.autograd.Function):
@@ -735,9 +948,11 @@ class FusedHierarchicalLoss:
     masking, class weighting with finding F13's multiplicities, valid-sample denominators, static or GradNorm task weights, the total,
     every logged component and the null statistics in two launches, the gradients of every task's logits in one more.
 
-    Supported criteria: TaxonomyAwareLabelSmoothingCE, and torch.nn.CrossEntropyLoss(reduction="none", label_smoothing=eps) without a
-    class weight of its own.  Anything else, dict-valued head outputs and CPU tensors are refused by name (LnxError): there is no
-    fall-back to the composed path."""
+    Supported criteria, in any mix over up to 8 tasks: TaxonomyAwareLabelSmoothingCE, this module's CrossEntropyLoss,
+    LabelSmoothingCrossEntropy and SoftTargetCrossEntropy (with their class weights, uploaded once, and [B] or [B, C] targets; [B, C] only
+    for SoftTargetCrossEntropy), and torch.nn.CrossEntropyLoss(reduction="none", label_smoothing=eps) without a class weight of its own
+    and with [B] targets.  Anything else, dict-valued head outputs and CPU tensors are refused by name (LnxError): there is no fall-back
+    to the composed path."""
 
     def __init__(self, task_keys, criteria, task_weighting, config=None):
         self.task_keys = list(task_keys)
@@ -761,11 +976,15 @@ class FusedHierarchicalLoss:
                 if not 0.0 <= float(crit.label_smoothing) < 1.0:
                     raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: label_smoothing={crit.label_smoothing} outside [0, 1)")
                 self._crit[t] = "ce"
+            elif isinstance(crit, _BasicCriterion):
+                if isinstance(crit, LabelSmoothingCrossEntropy) and not 0.0 <= float(crit.smoothing) < 1.0:
+                    raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: smoothing={crit.smoothing} outside [0, 1)")
+                self._crit[t] = "basic"
             else:
-                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: criterion {type(crit).__name__} is not supported "
-                                 "(TaxonomyAwareLabelSmoothingCE or torch.nn.CrossEntropyLoss(reduction='none'))")
+                raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: criterion {type(crit).__name__} is not supported ({ACCEPTED_CRITERIA})")
         self._dev = None
         self._cw = {}      # task -> (device vector, length): uploaded once
+        self._critw = {}   # task -> [C] class weight of a CrossEntropyLoss / LabelSmoothingCrossEntropy / SoftTargetCrossEntropy: uploaded once
         self._static_w = None
         self._draws = {}   # (n_tasks, B) -> [n_tasks, B] buffer of uniform draws
         for crit in criteria.values():  # upload at construction when the criteria already live on a GPU
@@ -779,8 +998,12 @@ class FusedHierarchicalLoss:
         self._dev = dev
         tw = self.task_weighting
         self._cw = {}
+        self._critw = {}
         for t in self.task_keys:
             crit = self.criteria[t]
+            if self._crit[t] == "basic" and crit.weight is not None and crit.apply_class_weights:
+                w = crit.weight if isinstance(crit.weight, torch.Tensor) else torch.tensor(crit.weight, dtype=torch.float32)
+                self._critw[t] = w.detach().to(dev, torch.float32).contiguous()
             if self._crit[t] == "soft":
                 if crit.soft_labels.device != dev:
                     crit.soft_labels = crit.soft_labels.to(dev)
@@ -865,9 +1088,19 @@ class FusedHierarchicalLoss:
                 k.soft, k.smoothing = _ptr(crit.soft_labels), 0.0
                 k.crit_weight = _ptr(crit.weight) if (crit.apply_class_weights and crit.weight is not None) else None
                 k.ignore_index = -1 if crit.ignore_index is None else int(crit.ignore_index)
+            elif self._crit[t] == "basic":
+                w = self._critw.get(t)
+                if w is not None and (w.dim() != 1 or w.numel() != x.shape[1]):
+                    raise ValueError(f"{type(crit).__name__}: weight has {tuple(w.shape)} entries, the logits have {x.shape[1]} classes")
+                if crit._form == L.CE_FORM_SOFT_ROW and (y.dim() != 2 or y.shape[1] != x.shape[1]):
+                    raise ValueError(f"SoftTargetCrossEntropy needs [B, C] targets of the logits' shape {tuple(x.shape)}, got {tuple(y.shape)}")
+                k.form, k.soft, k.crit_weight = crit._form, None, _ptr(w)
+                k.smoothing = float(crit.smoothing) if crit._form == L.CE_FORM_OFF_TARGET else 0.0
+                ign = getattr(crit, "ignore_index", None)
+                k.ignore_index = int(ign) if (ign is not None and ign >= 0) else -1
             else:
                 if y.dim() != 1:
-                    raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: CrossEntropyLoss with [B, C] targets is not supported")
+                    raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: torch.nn.CrossEntropyLoss with [B, C] targets is not supported")
                 k.soft, k.smoothing, k.crit_weight = None, float(crit.label_smoothing), None
                 k.ignore_index = int(crit.ignore_index) if crit.ignore_index >= 0 else -1
             if y.dim() == 1:
@@ -884,6 +1117,8 @@ class FusedHierarchicalLoss:
                 raise L.LnxError(f"FusedHierarchicalLoss: task {t!r}: {y.shape[0]} targets for a batch of {B}")
             k.p_cw, k.p_w = class_weight_powers(tw, config, is_validation, t)
             if t in self._cw and k.p_w:
+                if y.dim() == 2 and self._cw[t][1] < x.shape[1]:  # [B, C] targets read every class: the missing ones weigh 1 (rebuilt once)
+                    self._cw[t] = (_class_weight_vector(tw.class_weights[t], x.shape[1], dev), x.shape[1])
                 k.class_weight, k.n_cw = _ptr(self._cw[t][0]), self._cw[t][1]
             else:
                 k.class_weight, k.n_cw = None, 0

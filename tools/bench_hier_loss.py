@@ -11,6 +11,11 @@ masking with inclusion probability 0.5 (the path with the most work: one torch.r
   step   (--step) model forward + loss + backward of mFormerV1_sm at 224 px in bf16; the difference of the two legs is the gap the
          loss leaves between the last forward kernel and the first backward kernel
 
+--criteria picks the per-task criterion of both legs (the composed leg runs the same classes in the same process): `taxonomy`
+(TaxonomyAwareLabelSmoothingCE, the default), `ce` (CrossEntropyLoss, the reference's default configuration), `ls`
+(LabelSmoothingCrossEntropy, smoothing 0.1) or `st` (SoftTargetCrossEntropy on [B, C] mixup rows, 0.6 / 0.4 of two samples' labels);
+the last three carry a class weight of their own.
+
 One JSON line at the end.  There is no CPU path."""
 import argparse
 import json
@@ -33,6 +38,16 @@ def median(v):
     return sorted(v)[len(v) // 2]
 
 
+def mixup_rows(targets, B, dev, g):
+    """[B, C] rows: 0.6 of each sample's label and 0.4 of another sample's"""
+    perm = torch.randperm(B, device=dev, generator=g)
+    out = {}
+    for t, c in TASKS:
+        one = torch.nn.functional.one_hot(targets[t], c).float()
+        out[t] = 0.6 * one + 0.4 * one[perm]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[256, 128])
@@ -41,10 +56,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--step", action="store_true", help="also time the whole train step of mFormerV1_sm around the two paths")
     ap.add_argument("--step-iters", type=int, default=10)
+    ap.add_argument("--criteria", choices=("taxonomy", "ce", "ls", "st"), default="taxonomy", help="the per-task criterion of both legs")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_hier_loss.py needs the MI355X: there is no CPU path")
-    from linnaeus_amd.loss import GradientWeighting, TaxonomyAwareLabelSmoothingCE, weighted_hierarchical_loss
+    from linnaeus_amd.loss import (CrossEntropyLoss, GradientWeighting, LabelSmoothingCrossEntropy, SoftTargetCrossEntropy, TaxonomyAwareLabelSmoothingCE,
+                                   weighted_hierarchical_loss)
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -54,12 +71,21 @@ def main():
     crit, cw = {}, {}
     for t, c in TASKS:
         m = 0.9 * torch.eye(c, device=dev) + 0.1 * torch.softmax(torch.randn(c, c, device=dev, generator=g), 1)
-        crit[t] = TaxonomyAwareLabelSmoothingCE(m / m.sum(1, keepdim=True)).to(dev)
+        w = 0.5 + torch.rand(c, device=dev, generator=g)
+        if args.criteria == "taxonomy":
+            crit[t] = TaxonomyAwareLabelSmoothingCE(m / m.sum(1, keepdim=True)).to(dev)
+        elif args.criteria == "ce":
+            crit[t] = CrossEntropyLoss(w, True)
+        elif args.criteria == "ls":
+            crit[t] = LabelSmoothingCrossEntropy(w, 0.1, True)
+        else:
+            crit[t] = SoftTargetCrossEntropy(w, True)
         crit[t].validate_targets = False  # no host read in the step
         cw[t] = {i: 0.5 + (i % 7) / 7.0 for i in range(0, c, 2)}
     gw = GradientWeighting(keys, CFG, "static", init_weights={t: 1.0 / (i + 1) for i, t in enumerate(keys)}, class_weights=cw)
     sched = NS(get_null_mask_prob=lambda step: 0.5)
-    result = {"workload": f"weighted_hierarchical_loss, heads {[c for _, c in TASKS]}, fp32 padded logits, class weights, null-mask probability 0.5; "
+    result = {"criteria": args.criteria,
+              "workload": f"weighted_hierarchical_loss, heads {[c for _, c in TASKS]}, fp32 padded logits, class weights, null-mask probability 0.5; "
                           f"{args.warmup} warm-up + {args.iters} timed calls per leg, {args.repeats} alternated repeats, median"}
 
     def loss_of(outputs, targets, fused):
@@ -69,6 +95,8 @@ def main():
         targets = {t: torch.randint(0, c, (B,), device=dev, generator=g) for t, c in TASKS}
         for t in keys:
             targets[t][torch.rand(B, device=dev, generator=g) < 0.2] = 0
+        if args.criteria == "st":
+            targets = mixup_rows(targets, B, dev, g)
         wide = {t: torch.randn(B, (c + 15) // 16 * 16 + 16, device=dev, generator=g) * 2 for t, c in TASKS}
         leaves = {t: wide[t][:, :c].detach().requires_grad_(True) for t, c in TASKS}
 
@@ -113,6 +141,8 @@ def main():
             x = torch.rand(B, 3, 224, 224, device=dev, generator=g)
             meta = torch.rand(B, meta_width, device=dev, generator=g) if meta_width else None
             targets = {t: torch.randint(0, c, (B,), device=dev, generator=g) for t, c in TASKS}
+            if args.criteria == "st":
+                targets = mixup_rows(targets, B, dev, g)
 
             def step(fused, n):
                 for _ in range(n):
