@@ -789,6 +789,26 @@ typedef struct lnx_ademamix_hyper {
 int lnx_ademamix_step(const lnx_adamw_desc* descs_dev, float* const* slow_dev, int ndesc, int total_blocks, const lnx_ademamix_hyper* hyper,
                       const float* sumsq, float max_norm, void* stream);
 
+/* torch.optim.SGD (built by optimizers/build.py for OPTIMIZER.NAME = sgd, always with nesterov) as one launch over the AdamW descriptor
+ * table, with the same clip: desc.m is the momentum buffer (may be NULL only in slots with momentum 0), desc.v is not read.  Per slot:
+ *   g *= coef;  g += weight_decay p;
+ *   momentum != 0:  buf = first ? g : momentum buf + (1 - dampening) g;  g = nesterov ? g + momentum buf : buf
+ *   p -= lr g
+ * `first` marks the slot of parameters whose buffer does not exist yet (torch initialises it with the gradient): it is written, not read.
+ * Refused on the host before any launch: NULL tables, ndesc <= 0, total_blocks <= 0, ngroups outside 1..LNX_ADAMW_MAX_GROUPS, a negative
+ * lr, momentum or weight_decay, nesterov with momentum <= 0 or dampening != 0.  sumsq == NULL or max_norm <= 0: no clip.
+ * 20 bytes per parameter, 12 without momentum. */
+typedef struct lnx_sgd_hyper {
+    int ngroups;
+    float lr[LNX_ADAMW_MAX_GROUPS], momentum[LNX_ADAMW_MAX_GROUPS], dampening[LNX_ADAMW_MAX_GROUPS], weight_decay[LNX_ADAMW_MAX_GROUPS];
+    int nesterov[LNX_ADAMW_MAX_GROUPS], first[LNX_ADAMW_MAX_GROUPS];
+} lnx_sgd_hyper;
+int lnx_sgd_step(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_sgd_hyper* hyper, const float* sumsq, float max_norm,
+                 void* stream);
+/* launches made by lnx_grad_sumsq (2), lnx_adamw_step, lnx_ademamix_step and lnx_sgd_step (1 each) since the library was loaded
+ * (host-side counter, the twin of lnx_muon_launches) */
+int64_t lnx_optim_launches(void);
+
 /* ------------------------------------------------------------------------------------
  * Muon (linnaeus/optimizers/muon.py:27-65, 126-190, chosen by OPTIMIZER.NAME = muon in optimizers/build.py:130-154): the whole step
  * for every 2-D / flattened 4-D parameter in 3 * max(ns_steps) + 3 launches, whatever the number of matrices.
@@ -844,6 +864,11 @@ typedef struct lnx_muon_step_args {
     void* workspace;                 /* workspace_bytes, zero-filled once, 256-byte aligned */
     int64_t workspace_bytes;
     float* partials;                 /* total_blocks floats */
+    /* appended (lnx_version 111): the global-norm clip of lnx_adamw_step.  sumsq is a DEVICE scalar, the sum of squares of every gradient
+     * of the run (lnx_grad_sumsq); each gradient element is multiplied by min(1, max_norm / (sqrt(*sumsq) + 1e-6)) as it is read, before
+     * the momentum lerp; g itself is not modified.  sumsq == NULL or max_norm <= 0 (a zero-filled tail): no clip, the step as before. */
+    const float* sumsq;
+    float max_norm;
 } lnx_muon_step_args;
 int lnx_muon_step(const lnx_muon_step_args* args, void* stream);
 /* launches made by lnx_muon_step since the library was loaded (host-side counter, as lnx_nt_kernel_launches) */

@@ -15,5 +15,5 @@ from .registry import build_model, create_model, install_into_linnaeus, register
 from .model import mFormerV1  # noqa: F401
 from . import autobatch, inference, loss, metrics, optim, prefetch  # noqa: F401
 from .inference import DevicePredictor, DevicePreprocessor  # noqa: F401
-from .optim import FusedMuon  # noqa: F401
+from .optim import FusedMultiOptimizer, FusedMuon, FusedSGD, build_optimizer  # noqa: F401
 from .collate import GPUMetaMasking, GPUTrainCollate, mask_meta_components  # noqa: F401

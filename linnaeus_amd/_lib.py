@@ -94,6 +94,11 @@ class AdEMAMixHyper(C.Structure):  # == lnx_ademamix_hyper
                                                                                   "alpha_t", "beta3_t", "omb3")]
 
 
+class SGDHyper(C.Structure):  # == lnx_sgd_hyper
+    _fields_ = ([("ngroups", C.c_int)] + [(k, C.c_float * ADAMW_MAX_GROUPS) for k in ("lr", "momentum", "dampening", "weight_decay")] +
+                [(k, C.c_int * ADAMW_MAX_GROUPS) for k in ("nesterov", "first")])
+
+
 MUON_TILE = 32  # == LNX_MUON_TILE
 MUON_ELEMS = 4096  # == LNX_MUON_ELEMS
 
@@ -115,7 +120,7 @@ class MuonInfo(C.Structure):  # == lnx_muon_info
 
 class MuonStepArgs(C.Structure):  # == lnx_muon_step_args
     _fields_ = [("n", C.c_int), ("mats", C.c_void_p), ("mats_dev", C.c_void_p), ("tiles_dev", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_int64), ("partials", C.c_void_p)]
+                ("workspace_bytes", C.c_int64), ("partials", C.c_void_p), ("sumsq", C.c_void_p), ("max_norm", C.c_float)]
 
 
 # the argument structs of include/lnx.h by their C names (tests compare sizeof against a compiled probe)
@@ -219,6 +224,9 @@ def lib() -> C.CDLL:
         _lib.lnx_meta_heads_bwd_part_floats.restype = C.c_int64
         if hasattr(_lib, "lnx_ademamix_step"):
             _lib.lnx_ademamix_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(AdEMAMixHyper), C.c_void_p, C.c_float, C.c_void_p]
+        if hasattr(_lib, "lnx_sgd_step"):
+            _lib.lnx_sgd_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SGDHyper), C.c_void_p, C.c_float, C.c_void_p]
+            _lib.lnx_optim_launches.restype = C.c_int64
         if hasattr(_lib, "lnx_muon_step"):
             _lib.lnx_muon_layout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MuonInfo)]
             _lib.lnx_muon_step.argtypes = [C.POINTER(MuonStepArgs), C.c_void_p]
@@ -282,7 +290,7 @@ EXPORTS = [
     "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
-    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
+    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",

@@ -1,6 +1,6 @@
 // Muon (linnaeus/optimizers/muon.py:27-65, 126-190) for gfx950: the whole step of every matrix parameter in
 // 3 * max(ns_steps) + 3 launches ("Muon's Newton-Schulz ... MFMA work").
-//   muon_momentum_kernel   buf = lerp(buf, g, 1 - mu); u = nesterov ? lerp(g, buf, mu) : buf; X = bf16(u) (transposed when tall);
+//   muon_momentum_kernel   g *= clip coefficient (when given); buf = lerp(buf, g, 1 - mu); u = nesterov ? lerp(g, buf, mu) : buf; X = bf16(u) (transposed when tall);
 //                          one sum-of-squares partial per workgroup
 //   muon_normalise_kernel  per 32 x 32 tile of X: fold the matrix's partials in a fixed order, X = bf16(X / (||X|| + 1e-7)), X^T
 //   muon_ns_kernel<0/1/2>  A = X X^T;  B = c A A + b A;  X = B X + a X (and X^T): grouped NT products, one wave per 32 x 32 output tile,
@@ -44,8 +44,12 @@ __device__ __forceinline__ int64_t x_index(const lnx_muon_mat& d, int r, int c) 
     return d.rows > d.cols ? (int64_t)c * d.np + r : (int64_t)r * d.np + c;
 }
 
-__global__ __launch_bounds__(256) void muon_momentum_kernel(const lnx_muon_mat* __restrict__ mats, int n, char* __restrict__ ws, float* __restrict__ part) {
+// sumsq / max_norm: the global-norm clip of lnx_adamw_step; every gradient element is scaled as it is read, g itself is not written
+__global__ __launch_bounds__(256) void muon_momentum_kernel(const lnx_muon_mat* __restrict__ mats, int n, char* __restrict__ ws, float* __restrict__ part,
+                                                            const float* __restrict__ sumsq, float max_norm) {
     __shared__ float red[4];
+    float coef = 1.0f;
+    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
     const lnx_muon_mat& d = mats[find_mat(mats, n, blockIdx.x)];
     float s = 0.f;
     if (d.g != nullptr) {
@@ -55,7 +59,7 @@ __global__ __launch_bounds__(256) void muon_momentum_kernel(const lnx_muon_mat* 
         const int64_t end = min(numel, base + ELEMS);
         const float mu = d.momentum, omm = d.omm;
         for (int64_t i = base + threadIdx.x; i < end; i += 256) {
-            const float g = d.g[i];
+            const float g = d.g[i] * coef;
             const float b = lerp_f(d.buf[i], g, omm);
             d.buf[i] = b;
             const float u = d.nesterov ? lerp_f(g, b, mu) : b;
@@ -293,7 +297,7 @@ extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     char* ws = static_cast<char*>(a->workspace);
     const lnx_muon_tile* tb[3] = {a->tiles_dev, a->tiles_dev + info.ntiles[0], a->tiles_dev + info.ntiles[0] + info.ntiles[1]};
-    hipLaunchKernelGGL(muon_momentum_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, ws, a->partials);
+    hipLaunchKernelGGL(muon_momentum_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, ws, a->partials, a->sumsq, a->max_norm);
     hipLaunchKernelGGL(muon_normalise_kernel, dim3(cdiv(info.ntiles[2], 4)), dim3(256), 0, st, a->mats_dev, tb[2], (int)info.ntiles[2], ws, (const float*)a->partials);
     g_launches += 2;
     for (int it = 0; it < max_steps; ++it) {

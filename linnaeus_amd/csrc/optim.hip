@@ -5,12 +5,16 @@
 // Launches per step over a device descriptor table (one entry per parameter tensor): sum of squares of all gradients
 // (partials per workgroup + a fixed-order fold; only when clipping), then the update, which reads the clip coefficient
 // from that scalar.
+#include <atomic>
+
 #include "common.hpp"
 #include "../../include/lnx.h"
 
 namespace {
 
 constexpr int OPT_ELEMS = 4096;  // elements per workgroup
+
+std::atomic<int64_t> g_launches{0};  // lnx_optim_launches
 
 // index of the tensor that owns workgroup `block` (descriptors sorted by block_start)
 __device__ __forceinline__ int find_desc_index(const lnx_adamw_desc* __restrict__ descs, int ndesc, int block) {
@@ -225,6 +229,78 @@ __global__ __launch_bounds__(256) void ademamix_kernel(const lnx_adamw_desc* __r
     }
 }
 
+// torch.optim.SGD (optimizers/build.py:89-96, 542-549, 578-585) over the same descriptor table; d.m is the momentum buffer, d.v is
+// not read.  Per element, in torch's order:
+//   g *= coef                                   (clip coefficient, as adamw_kernel)
+//   g += wd p                                   coupled weight decay
+//   momentum != 0:  buf = first ? g : momentum buf + (1 - dampening) g;   g = nesterov ? g + momentum buf : buf
+//   p -= lr g
+// `first` slots hold the parameters whose buffer does not exist yet (torch clones the gradient into it): the buffer is written, not
+// read.  Slots with momentum 0 touch no buffer at all (d.m may be NULL there).  20 bytes per parameter (read p, g, buf; write p,
+// buf), 16 in a first slot, 12 without momentum.  A descriptor with momentum but no buffer is left alone (the host API never builds one).
+__global__ __launch_bounds__(256) void sgd_kernel(const lnx_adamw_desc* __restrict__ descs, int ndesc, const lnx_sgd_hyper h, const float* __restrict__ sumsq,
+                                                  float max_norm) {
+    const lnx_adamw_desc& d = find_desc(descs, ndesc, blockIdx.x);
+    const int gi = d.group;
+    const float lr = h.lr[gi], mom = h.momentum[gi], omd = 1.0f - h.dampening[gi], wd = h.weight_decay[gi];
+    const bool nesterov = h.nesterov[gi] != 0, first = h.first[gi] != 0, has_buf = mom != 0.f, rd_buf = has_buf && !first;
+    if (has_buf && d.m == nullptr) return;
+    float coef = 1.0f;
+    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+    const int64_t base = (int64_t)(blockIdx.x - d.block_start) * OPT_ELEMS;
+    const int64_t end = min(d.n, base + OPT_ELEMS);
+    auto upd = [&](float g, float& p, float& m) __attribute__((always_inline)) {
+        g *= coef;
+        g = fmaf(wd, p, g);
+        if (has_buf) {
+            m = first ? g : fmaf(mom, m, omd * g);
+            g = nesterov ? fmaf(mom, m, g) : m;
+        }
+        p = fmaf(-lr, g, p);
+    };
+    // same access shape as adamw_kernel: 16-byte accesses, all four rounds of loads in flight before the first use; the scalar loop
+    // takes tails and tensors any of whose pointers is not 16-byte aligned (a NULL buffer counts as aligned and is never touched)
+    const bool vec = ((reinterpret_cast<uintptr_t>(d.p) | reinterpret_cast<uintptr_t>(d.g) | reinterpret_cast<uintptr_t>(d.m)) & 15) == 0;
+    int64_t done = base;
+    if (vec) {
+        constexpr int R = OPT_ELEMS / 1024;
+        float4 g4[R], p4[R], m4[R];
+        const int64_t full = base + ((end - base) & ~(int64_t)3);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t i = base + 1024 * r + 4 * threadIdx.x;
+            const int64_t ic = i + 3 < full ? i : base;  // unconditional loads (a workgroup's first four elements always exist when full > base)
+            m4[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (full > base) {
+                g4[r] = *reinterpret_cast<const float4*>(d.g + ic);
+                p4[r] = *reinterpret_cast<const float4*>(d.p + ic);
+                if (rd_buf) m4[r] = *reinterpret_cast<const float4*>(d.m + ic);
+            }
+        }
+        if (full > base) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int64_t i = base + 1024 * r + 4 * threadIdx.x;
+                if (i + 3 < full) {
+                    upd(g4[r].x, p4[r].x, m4[r].x);
+                    upd(g4[r].y, p4[r].y, m4[r].y);
+                    upd(g4[r].z, p4[r].z, m4[r].z);
+                    upd(g4[r].w, p4[r].w, m4[r].w);
+                    *reinterpret_cast<float4*>(d.p + i) = p4[r];
+                    if (has_buf) *reinterpret_cast<float4*>(d.m + i) = m4[r];
+                }
+            }
+        }
+        done = full;
+    }
+    for (int64_t i = done + threadIdx.x; i < end; i += 256) {
+        float p = d.p[i], m = rd_buf ? d.m[i] : 0.f;
+        upd(d.g[i], p, m);
+        d.p[i] = p;
+        if (has_buf) d.m[i] = m;
+    }
+}
+
 }  // namespace
 
 extern "C" int lnx_adamw_blocks(int64_t numel) { return (int)((numel + OPT_ELEMS - 1) / OPT_ELEMS); }
@@ -234,6 +310,7 @@ extern "C" int lnx_grad_sumsq(const lnx_adamw_desc* descs_dev, int ndesc, int to
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(total_blocks), dim3(256), 0, st, descs_dev, ndesc, ws);
     hipLaunchKernelGGL(grad_sumsq_fold_kernel, dim3(1), dim3(1024), 0, st, ws, total_blocks, out);
+    g_launches += 2;
     LNX_LAUNCH_CHECK();
     return 0;
 }
@@ -245,6 +322,7 @@ extern "C" int lnx_adamw_step(const lnx_adamw_desc* descs_dev, int ndesc, int to
     for (int i = 0; i < hyper->ngroups; ++i)
         LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_adamw_step: bias corrections of group %d must be positive (step >= 1)", i);
     hipLaunchKernelGGL(adamw_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, ndesc, *hyper, sumsq, max_norm);
+    g_launches += 1;
     LNX_LAUNCH_CHECK();
     return 0;
 }
@@ -256,6 +334,28 @@ extern "C" int lnx_ademamix_step(const lnx_adamw_desc* descs_dev, float* const* 
     for (int i = 0; i < hyper->ngroups; ++i)
         LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_ademamix_step: bias corrections of slot %d must be positive (step >= 1)", i);
     hipLaunchKernelGGL(ademamix_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, slow_dev, ndesc, *hyper, sumsq, max_norm);
+    g_launches += 1;
     LNX_LAUNCH_CHECK();
     return 0;
 }
+
+extern "C" int lnx_sgd_step(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_sgd_hyper* hyper, const float* sumsq, float max_norm,
+                            void* stream) {
+    LNX_CHECK(descs_dev != nullptr && hyper != nullptr, "lnx_sgd_step: NULL descriptor table or hyper-parameter table");
+    LNX_CHECK(ndesc > 0, "lnx_sgd_step: ndesc=%d (must be positive)", ndesc);
+    LNX_CHECK(total_blocks > 0, "lnx_sgd_step: total_blocks=%d (must be positive)", total_blocks);
+    LNX_CHECK(hyper->ngroups > 0 && hyper->ngroups <= LNX_ADAMW_MAX_GROUPS, "lnx_sgd_step: ngroups=%d (1..%d)", hyper->ngroups, LNX_ADAMW_MAX_GROUPS);
+    for (int i = 0; i < hyper->ngroups; ++i) {
+        LNX_CHECK(hyper->lr[i] >= 0.f, "lnx_sgd_step: negative lr in slot %d", i);
+        LNX_CHECK(hyper->momentum[i] >= 0.f, "lnx_sgd_step: negative momentum in slot %d", i);
+        LNX_CHECK(hyper->weight_decay[i] >= 0.f, "lnx_sgd_step: negative weight_decay in slot %d", i);
+        LNX_CHECK(!hyper->nesterov[i] || (hyper->momentum[i] > 0.f && hyper->dampening[i] == 0.f),
+                  "lnx_sgd_step: nesterov in slot %d needs a momentum above zero and zero dampening", i);
+    }
+    hipLaunchKernelGGL(sgd_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, ndesc, *hyper, sumsq, max_norm);
+    g_launches += 1;
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int64_t lnx_optim_launches(void) { return g_launches.load(); }
