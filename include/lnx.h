@@ -35,6 +35,18 @@ int lnx_device_cus(void);
  * take its tiles); a margin only spares the hardware the queue of unplaceable workgroups.  Replaces nothing in the reference:
  * torch DDP's NCCL kernels and cuBLAS share the SMs the same way (linnaeus/main.py:936-983). */
 int lnx_set_cu_margin(int cus);
+/* Deterministic mode: with it on, every reduction of the training path (forward, backward, losses, optimizers) takes a fixed-order
+ * route -- one contributor per output element, or per-contributor partial sums in caller-provided scratch that a second stage folds
+ * in index order and adds to the destination once -- and the persistent kernels stride over their tiles instead of drawing them.  The
+ * same inputs then give the same bits, run to run, on one GPU, one library build, one batch shape, one CU margin and one set of
+ * LNX_* switches (those change grids and split counts, hence the order).  Off by default: nothing changes then.  The value is
+ * process-wide and read per launch; its initial value is LNX_DETERMINISTIC=1 from the environment, read once.  An entry point that
+ * has no fixed-order route for what it is asked (missing scratch, a kernel that sums with float atomics only) refuses by name
+ * through lnx_last_error instead of taking the other route.  lnx_set_deterministic returns the previous value. */
+int lnx_set_deterministic(int on);
+int lnx_get_deterministic(void);
+/* 1 while the persistent kernels stride over their tiles (LNX_TILE_SCHED=static, or the deterministic mode), 0 while they draw them */
+int lnx_tile_sched_static(void);
 
 /* Row map for token buffers that carry E extra rows per sample:
  * phys_row = m + (m / group) * pad + off   (group == 0: identity). */
@@ -149,6 +161,10 @@ int lnx_gemm_nt_mxfp8(const lnx_gemm_args* args, const void* a_scales, const voi
  * Split over M across workgroups.  Partial tiles are added to dW/db with fp32 atomics, or, when the
  * caller passes a workspace (ws), stored there and summed into dW/db by a second kernel in a fixed
  * order (faster: no memory-side atomics; and bit-reproducible).  dW/db accumulate: caller zeroes them.
+ * Default mode: sparsely filled tiles, a missing or too small workspace and the fp32 / odd-M kernel take the atomics.
+ * Deterministic mode (lnx_set_deterministic): two or more splits always meet in the workspace second stage; where it is missing or too
+ * small (and in the kernel that has no second stage) the contraction is split less, down to one workgroup per output tile -- one
+ * contributor per element.
  * Replaces autograd's weight/bias gradient of every Linear/patchify conv above. */
 typedef struct lnx_wgrad_args {
     int dtype;
@@ -165,7 +181,7 @@ typedef struct lnx_wgrad_args {
     float* db;      /* [N] or NULL */
     int splits;     /* 0: choose automatically */
     int k_store;    /* >0: only columns k < k_store are stored (zero-padded K) */
-    float* ws;      /* optional split-K workspace (device), NULL = atomics */
+    float* ws;      /* optional split-K workspace (device), NULL = atomics (deterministic mode: NULL = fewer splits, down to one) */
     int64_t ws_floats; /* its size; LNX_TN_WS_FLOATS always suffices */
     int defer;      /* round 4.  != 0 (and ws given): the product leaves its split-K partial tiles in ws and the summation into dW / db
                        is postponed to lnx_gemm_tn_flush(), which sums the partial tiles of ALL postponed products of this host thread
@@ -233,7 +249,9 @@ typedef struct lnx_ln_bwd_args {
     void* dx;           /* rows via x_map */
     int dx_dtype;
     int64_t lddx;
-    float* dw;          /* [C] += (fp32 atomics) or NULL */
+    float* dw;          /* [C] += or NULL: fp32 atomics (one per workgroup without ws; with ws one per slice of workgroups of the second
+                           stage), or, in deterministic mode, the whole fold of the workgroups' partial sums in ws in index order and one
+                           addition (ws is then required: a call without it refuses by name) */
     float* db;
     int relu_mask;      /* 1: x is a ReLU output feeding this LN; dx *= (x > 0) */
     float* ws;          /* optional scratch for the dw/db column partials (avoids contended atomics); 16-byte aligned */
@@ -307,10 +325,16 @@ typedef struct lnx_dwconv_wgrad_args {
     int x_dtype;
     const void* dy;       /* [B,H,W,C] */
     int dy_dtype;
-    float* dw;            /* torch layout [C,1,7,7], += atomics */
-    float* db;            /* [C] += or NULL */
+    float* dw;            /* torch layout [C,1,7,7], +=: one float atomic per workgroup and tap, or (deterministic mode) the workgroups'
+                             partial sums through ws, folded in workgroup order and added once */
+    float* db;            /* [C] += (likewise) or NULL */
+    float* ws;            /* deterministic mode: scratch of lnx_dwconv7_wgrad_ws_floats(...) floats (overwritten), required; else ignored */
+    int64_t ws_floats;
 } lnx_dwconv_wgrad_args;
 int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* args, void* stream);
+/* floats of ws the deterministic route of lnx_dwconv7_wgrad needs for this shape and these dtypes on the current device (the launcher's
+ * own grid choice: walkers x 50 C); 0 for a shape the entry point refuses */
+int64_t lnx_dwconv7_wgrad_ws_floats(int B, int H, int W, int C, int x_dtype, int dy_dtype);
 
 /* ------------------------------------------------------------------------------------
  * Attention with the reference's cos-only "2D RoPE" (SURVEY F1), global over N tokens.
@@ -403,7 +427,11 @@ typedef struct lnx_attn_bwd_args {
     float* freq_ws;      /* workspace, lnx_attn_bwd_ws_floats_hd(B, N, heads, D) floats (overwritten): round 3 -- the gradient of the learnable
                             frequencies (autograd of compute_mixed_cis / apply_rotary_emb through the real part only, finding F1) is
                             reduced inside the two backward kernels to one [2][D/2] partial per workgroup; it used to be a
-                            [2][B, N-E, heads, D/2] tensor read back by a separate lnx_rope_freqs_bwd */
+                            [2][B, N-E, heads, D/2] tensor read back by a separate lnx_rope_freqs_bwd.  Inside a workgroup the waves add
+                            to the partial with LDS float atomics (order not fixed); in deterministic mode each wave sums into a slot
+                            of its own behind the partials and the slots are folded by wave index -- the size query reports the larger
+                            need while the mode is on, so allocate (and call) under the setting the query was made in.  The fold of
+                            the partials into dfreqs is fixed-order in both modes. */
     float* delta;        /* workspace [B, heads, N] */
     const unsigned char* drop_mask; /* the forward's keep mask (see lnx_attn_args), or NULL */
     float drop_inv_keep;
@@ -422,6 +450,10 @@ typedef struct lnx_attn_bwd_args {
 int lnx_attn_bwd_flush(void* stream); /* folds every postponed call of this thread; refuses a stream other than theirs */
 int lnx_attn_bwd_discard(void);       /* forgets them without folding (error paths); returns how many were dropped */
 int lnx_attn_bwd(const lnx_attn_bwd_args* args, void* stream);
+/* The same call with the size of freq_ws (floats).  Deterministic mode with image tokens (E < N): the waves' slots lie behind the
+ * workgroups' partials, so the call needs to know what it was given -- less than lnx_attn_bwd_ws_floats_hd reports with the mode on
+ * refuses by name, and so does lnx_attn_bwd (no size) there.  Outside the mode the size is not read. */
+int lnx_attn_bwd_sized(const lnx_attn_bwd_args* args, int64_t freq_ws_floats, void* stream);
 
 /* Which kernel family lnx_attn_fwd / lnx_attn_bwd take (host-side bookkeeping, no device work; the forward and the backward of one
  * call take the same one): the boundary tests use it to prove that a sequence length ran on the kernels it is meant to cover.
@@ -506,6 +538,14 @@ int lnx_dropout_residual(const void* z, int z_dtype, const unsigned char* mask, 
 /* out[map(m), :] = vec[:]  for m in [0, M)   (CLS token expand, mFormerV1.py:448,487) */
 int lnx_fill_rows(const float* vec, float* out, int64_t ldout, lnx_rowmap map, int M, int C, void* stream);
 /* out[c] += sum_m in[map(m), c]   (fp32 atomics) */
+/* lnx_layerscale_bwd with scratch for the deterministic mode: ws holds lnx_layerscale_bwd_ws_floats(M, C) floats (the workgroups'
+ * dgamma partial sums, folded in workgroup order and added to dgamma once).  Outside the mode ws is ignored; inside it
+ * lnx_layerscale_bwd (no scratch) refuses by name.  The size query returns 0 for a shape the entry point refuses. */
+int lnx_layerscale_bwd_ws(const float* g, const void* z, int dtype, const float* gamma, const float* rowscale, int rows_per_sample, void* dz,
+                          float* dgamma, int M, int C, float* ws, int64_t ws_floats, void* stream);
+int64_t lnx_layerscale_bwd_ws_floats(int M, int C);
+/* (deterministic mode: lnx_colsum_rows and lnx_agg2_bwd run ONE workgroup over all rows / elements -- one contributor per output,
+ * no scratch.  That is sized for their callers in the plan (M = batch rows); a caller with a large M gets a serial kernel there.) */
 int lnx_colsum_rows(const float* in, int64_t ldin, lnx_rowmap map, float* out, int M, int C, void* stream);
 
 /* aggregate = Conv1d(2,1,1) over [cls_1, cls_2] (mFormerV1.py:322,515-523):
@@ -626,12 +666,14 @@ typedef struct lnx_softce_args {
     const float* row_scale;    /* [B] or NULL: per-sample multiplier of the gradient / of loss_sum */
     float scale;               /* global multiplier (e.g. task_weight / B) */
     float* loss;               /* [B] per-sample losses or NULL */
-    float* loss_sum;           /* scalar accumulator or NULL */
+    float* loss_sum;           /* scalar accumulator or NULL (+=: float atomics, or the fold through sum_ws in deterministic mode) */
     float* dlogits;            /* [B, ldd] or NULL */
     int64_t ldd;
     int form;                  /* LNX_CE_FORM_*; 0 = the two forms above */
     const float* soft_target;  /* LNX_CE_FORM_SOFT_ROW: [B, ldt] per-sample rows; NULL otherwise */
     int64_t ldt;               /* >= C */
+    float* sum_ws;             /* [B] scratch or NULL.  Deterministic mode with loss_sum: required -- the rows' terms go here and are folded
+                                  into loss_sum in row order (otherwise one float atomic per row, in any order); ignored outside the mode */
 } lnx_softce_args;
 int lnx_softce(const lnx_softce_args* args, void* stream);
 /* n <= LNX_SOFTCE_MAX_TASKS independent argument sets (the tasks of the multi-task criterion: train.py's per-task loop over
@@ -1166,7 +1208,9 @@ typedef struct lnx_convmlp_bwd_args {
     void* dh;              /* out [M, 4C] bf16  dL/dh     (operand of the pwconv1 weight gradient)   not materialised  */
     void* dz;              /* out [M, C]  bf16  rowscale*gamma*g */
     void* dln;             /* out [M, C]  bf16  gradient wrt the LayerNorm output */
-    float* dgamma;         /* [C] += */
+    float* dgamma;         /* [C] += : LDS float atomics across the waves and one global float atomic per workgroup, or (deterministic mode)
+                              a [C] row per WAVE in ws behind the LayerNorm rows, folded in row order and added once -- ws is then
+                              required with z as well */
     /* Fused LayerNorm backward (round 3): with `y` set, `dln` receives the gradient wrt the LayerNorm INPUT y instead (what
      * lnx_layernorm_bwd would make of dln, y, mean, rstd), and d_ln_w / d_ln_b += the LayerNorm weight / bias gradient. */
     const void* y;         /* [M, C] bf16, or NULL */
@@ -1184,7 +1228,10 @@ typedef struct lnx_convmlp_bwd_args {
                               lnx_layernorm_bwd_flush() together with the postponed LayerNorm backward calls; `ws` must stay untouched until then */
 } lnx_convmlp_bwd_args;
 int lnx_convmlp_bwd(const lnx_convmlp_bwd_args* args, void* stream);
-/* floats of `ws` the fused-LayerNorm backward needs for (C, M), from the same grid choice the launcher makes (0: unsupported C) */
+/* floats of `ws` the fused-LayerNorm backward needs for (C, M), from the same grid choice the launcher makes (0: unsupported C).
+ * Deterministic mode: the larger need of its routes -- a [2C] LayerNorm row and a [C] dgamma row per wave (8 a workgroup; 4 at
+ * C >= 128 with LNX_CM_NW=4) instead of [2C] per workgroup; the rows are folded in row order by the shared second stage.  A ws that
+ * is too small for the mode the call runs in is refused by name. */
 int64_t lnx_convmlp_bwd_ws_floats(int C, int M);
 
 /* (round 2 had lnx_convmlp_wgrad here: both weight gradients from ln / dz with the hidden recomputed on chip, so that act / dH

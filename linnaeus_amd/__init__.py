@@ -10,6 +10,7 @@ or, with the reference installed, `linnaeus_amd.install_into_linnaeus()` re-regi
 """
 __version__ = "0.1.0"
 
+from ._lib import is_deterministic, set_deterministic  # noqa: F401
 from .config import ConfigNode, arch_config, default_config  # noqa: F401
 from .registry import build_model, create_model, install_into_linnaeus, register_head, register_model  # noqa: F401
 from .model import mFormerV1  # noqa: F401

@@ -72,6 +72,7 @@ class SoftCEArgs(C.Structure):
         ("loss", C.c_void_p), ("loss_sum", C.c_void_p),
         ("dlogits", C.c_void_p), ("ldd", C.c_int64),
         ("form", C.c_int), ("soft_target", C.c_void_p), ("ldt", C.c_int64),
+        ("sum_ws", C.c_void_p),
     ]
 
 
@@ -222,6 +223,11 @@ def lib() -> C.CDLL:
         _lib.lnx_nt_kernel_launches.restype = C.c_int64
         _lib.lnx_convmlp_bwd_ws_floats.restype = C.c_int64
         _lib.lnx_meta_heads_bwd_part_floats.restype = C.c_int64
+        if hasattr(_lib, "lnx_set_deterministic"):
+            _lib.lnx_dwconv7_wgrad_ws_floats.restype = C.c_int64
+            _lib.lnx_layerscale_bwd_ws_floats.restype = C.c_int64
+        _lib.lnx_attn_bwd_ws_floats.restype = C.c_int64
+        _lib.lnx_attn_bwd_ws_floats_hd.restype = C.c_int64
         if hasattr(_lib, "lnx_ademamix_step"):
             _lib.lnx_ademamix_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(AdEMAMixHyper), C.c_void_p, C.c_float, C.c_void_p]
         if hasattr(_lib, "lnx_sgd_step"):
@@ -264,6 +270,16 @@ def lib() -> C.CDLL:
     return _lib
 
 
+def set_deterministic(on: bool) -> bool:
+    """Switch the library's deterministic mode (include/lnx.h: lnx_set_deterministic); returns the previous setting.  Plans and scratch
+    sized before the switch do not fit the other setting: models go through `mFormerV1.set_deterministic`, which rebuilds its plans."""
+    return bool(lib().lnx_set_deterministic(1 if on else 0))
+
+
+def is_deterministic() -> bool:
+    return bool(lib().lnx_get_deterministic())
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise LnxError(f"{what} failed (rc={rc}): {lib().lnx_last_error().decode()}")
@@ -284,12 +300,12 @@ ATTN_KERNEL_NONE, ATTN_KERNEL_RES4, ATTN_KERNEL_RES8, ATTN_KERNEL_TILED4, ATTN_K
 
 # every symbol include/lnx.h declares (kept in sync by tests/test_abi.py)
 EXPORTS = [
-    "lnx_last_error", "lnx_version", "lnx_device_cus", "lnx_set_cu_margin",
+    "lnx_last_error", "lnx_version", "lnx_device_cus", "lnx_set_cu_margin", "lnx_set_deterministic", "lnx_get_deterministic", "lnx_tile_sched_static",
     "lnx_gemm_nt", "lnx_last_nt_kernel", "lnx_nt_kernel_launches", "lnx_nt_dispatch", "lnx_gemm_tn", "lnx_gemm_tn_flush", "lnx_gemm_tn_discard", "lnx_amax", "lnx_quantize_fp8", "lnx_gemm_nt_fp8", "lnx_quantize_mxfp8", "lnx_gemm_nt_mxfp8", "lnx_dropout_mul", "lnx_dropout_residual", "lnx_plan_dropout_bytes", "lnx_plan_set_dropout", "lnx_plan_attn_dropout_bytes", "lnx_plan_set_attn_dropout",
     "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard", "lnx_layernorm_fwd_query", "lnx_layernorm_bwd_query",
-    "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad",
-    "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
-    "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
+    "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_ws_floats",
+    "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
+    "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",
@@ -386,6 +402,7 @@ class DwconvWgradArgs(C.Structure):
         ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
         ("x", C.c_void_p), ("x_dtype", C.c_int), ("dy", C.c_void_p), ("dy_dtype", C.c_int),
         ("dw", C.c_void_p), ("db", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_floats", C.c_int64),
     ]
 
 

@@ -43,10 +43,30 @@ int persistent_cus(int cus) {
     return room < 8 ? 8 : room;
 }
 void set_cu_margin(int m) { g_cu_margin.store(m < 0 ? 0 : m, std::memory_order_relaxed); }
+// ---- deterministic mode (include/lnx.h): process-wide, read per launch; LNX_DETERMINISTIC=1 from the environment at first use ----
+static std::atomic<int> g_deterministic{-1};
+bool deterministic() {
+    int d = g_deterministic.load(std::memory_order_relaxed);
+    if (d < 0) {
+        const char* e = getenv("LNX_DETERMINISTIC");
+        d = e && atoi(e) == 1 ? 1 : 0;
+        int unset = -1;
+        if (!g_deterministic.compare_exchange_strong(unset, d, std::memory_order_relaxed)) d = unset;
+    }
+    return d != 0;
+}
+extern "C" int lnx_get_deterministic(void) { return deterministic() ? 1 : 0; }
+extern "C" int lnx_set_deterministic(int on) {
+    const int prev = deterministic() ? 1 : 0;
+    g_deterministic.store(on ? 1 : 0, std::memory_order_relaxed);
+    return prev;
+}
 bool tile_sched_static() {
+    if (deterministic()) return true;  // a drawn tile order would change every workgroup's partial sums from run to run
     const char* e = getenv("LNX_TILE_SCHED");
     return e && strcmp(e, "static") == 0;
 }
+extern "C" int lnx_tile_sched_static(void) { return tile_sched_static() ? 1 : 0; }
 int tile_slot_of(hipStream_t st) {
     // stream handle -> slot, first come first served; a 65th stream gets -1 = the static stride (no counters: a shared slot would let two
     // overlapping persistent launches skip or repeat each other's tiles)

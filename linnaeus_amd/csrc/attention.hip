@@ -356,8 +356,11 @@ __device__ __forceinline__ float row16_sum(float v) {
 // This lane holds the 8 pair gradients gp[dt][pr] (j = 8 dt + 2 g + pr) of ONE row and the matching table entries
 // dx / dy = -t_x sin(theta), -t_y sin(theta); rows are summed over the 16 lanes of the DPP row, then added to the
 // workgroup's HD LDS accumulators [a][j] (order of the LDS float adds is not fixed: last-bit differences from run to run).
+// Deterministic mode (fw != NULL): the wave adds to its own slot in global scratch instead -- entry j of a slot belongs to one lane
+// (s == 0 of its g), which zeroed it (freq_wave_slot) and is the only one to touch it, in program order; freq_flush folds the slots by
+// wave index.
 template <int HD = 64>
-__device__ __forceinline__ void freq_accum(float* fl, const float (&gp)[HD / 16][2], const float (&dx)[HD / 16][2], const float (&dy)[HD / 16][2], int s, int g) {
+__device__ __forceinline__ void freq_accum(float* fl, float* fw, const float (&gp)[HD / 16][2], const float (&dx)[HD / 16][2], const float (&dy)[HD / 16][2], int s, int g) {
 #pragma unroll
     for (int dt = 0; dt < HD / 16; ++dt)
 #pragma unroll
@@ -366,17 +369,30 @@ __device__ __forceinline__ void freq_accum(float* fl, const float (&gp)[HD / 16]
             const float ty = row16_sum(gp[dt][pr] * dy[dt][pr]);
             if (s == 0) {
                 const int j = 8 * dt + 2 * g + pr;
-                atomicAdd(fl + j, tx);
-                atomicAdd(fl + HD / 2 + j, ty);
+                if (fw) {
+                    fw[j] += tx;
+                    fw[HD / 2 + j] += ty;
+                } else {
+                    atomicAdd(fl + j, tx);
+                    atomicAdd(fl + HD / 2 + j, ty);
+                }
             }
         }
 }
 // after the workgroup's last freq_accum: publish (dq kernel) or add to (dk/dv kernel, same grid, launched after it) the partial
-template <bool ADD, int HD = 64> __device__ __forceinline__ void freq_flush(const float* fl, float* fpart) {
+constexpr int FREQ_WAVES = 16;  // wave slots per workgroup in the deterministic mode's scratch (the largest backward kernel has 16 waves)
+template <bool ADD, int HD = 64> __device__ __forceinline__ void freq_flush(const float* fl, float* fpart, const float* fwave) {
     __syncthreads();
     if (threadIdx.x < HD) {
+        float v = fl[threadIdx.x];
+        if (fwave) {  // (kernel-uniform)
+            const float* b = fwave + (int64_t)blockIdx.x * FREQ_WAVES * HD + threadIdx.x;
+            const int nw = blockDim.x >> 6;
+            v = 0.f;
+            for (int w = 0; w < nw; ++w) v += b[w * HD];
+        }
         float* dst = fpart + (int64_t)blockIdx.x * HD + threadIdx.x;
-        *dst = ADD ? *dst + fl[threadIdx.x] : fl[threadIdx.x];
+        *dst = ADD ? *dst + v : v;
     }
 }
 
@@ -416,7 +432,26 @@ struct AttnP {
     int Np = 0;                            // N rounded up to a multiple of 64
     const float* sin_tab = nullptr;        // ROT kernels: sin(theta), laid out like cos_tab
     int W = 1;                             // ROT backward: width of the token grid (t_x = n % W, t_y = n / W of image token n)
+    float* fwave = nullptr;                // deterministic mode: [workgroups][FREQ_WAVES][HD] per-wave sums of the freqs gradient; else NULL
 };
+
+// this wave's slot of p.fwave, zeroed by the lanes that own its entries (freq_accum); NULL outside the deterministic mode
+template <int HD = 64> __device__ __forceinline__ float* freq_wave_slot(const AttnP& p) {
+    if (p.fwave == nullptr) return nullptr;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    float* fw = p.fwave + ((int64_t)blockIdx.x * FREQ_WAVES + wave) * HD;
+    if ((lane & 15) == 0) {
+#pragma unroll
+        for (int dt = 0; dt < HD / 16; ++dt)
+#pragma unroll
+            for (int pr = 0; pr < 2; ++pr) {
+                const int j = 8 * dt + 2 * (lane >> 4) + pr;
+                fw[j] = 0.f;
+                fw[HD / 2 + j] = 0.f;
+            }
+    }
+    return fw;
+}
 
 // dk / dv epilogue of one 16-key wave tile: every load in one batch (clamped rows, unconditional), 8-/16-byte stores, the k part
 // of the freqs gradient.  Shared by the resident and the tiled kernel.
@@ -424,7 +459,7 @@ struct AttnP {
 // k, recomputed in fp32 from the raw row), weighted by t_x, t_y (from the token index and the grid width) instead of the d-cos table.
 template <typename T, int HD = 64, bool ROT = false>
 __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)[HD / 16], const f32x4_t (&dv)[HD / 16], const T* __restrict__ kb, int64_t ld, int C,
-                                             int b, int head, int key, int s, int g, float* fl) {
+                                             int b, int head, int key, int s, int g, float* fl, float* fw) {
     const int kc = min(key, p.N - 1);
     const T* kraw = kb + (int64_t)kc * ld;
     const float* cpr = p.cos_tab + ((int64_t)max(kc - p.E, 0) * p.heads + head) * (HD / 2);
@@ -498,12 +533,12 @@ __device__ __forceinline__ void dkv_epilogue(const AttnP& p, const f32x4_t (&dk)
             for (int j = 0; j < 4; ++j) ov[dt][j] = dv[dt][j];
         store_row<T, HD>(dkp + C, ov, g, row);
     }
-    if (rope) freq_accum<HD>(fl, gp, dx, dy, s, g);
+    if (rope) freq_accum<HD>(fl, fw, gp, dx, dy, s, g);
 }
 // dq epilogue of one 16-query wave tile (the tiled kernel; the resident one fetches its operands ahead of the key loop)
 template <typename T, int HD = 64, bool ROT = false>
 __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[HD / 16], const T* __restrict__ qb, int64_t ld, int b, int head, int q, int s, int g,
-                                            float scale, float* fl) {
+                                            float scale, float* fl, float* fw) {
     const int qc = min(q, p.N - 1);
     const T* qraw = qb + (int64_t)qc * ld;
     const float* cpr = p.cos_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * (HD / 2);
@@ -567,7 +602,7 @@ __device__ __forceinline__ void dq_epilogue(const AttnP& p, const f32x4_t (&dq)[
         gp[dt][1] = img ? scale * (dq[dt][2] * qr[dt][2] + dq[dt][3] * qr[dt][3]) : 0.f;
     }
     store_row<T, HD>(dqp, oq, g, row);
-    if (rope) freq_accum<HD>(fl, gp, dx, dy, s, g);
+    if (rope) freq_accum<HD>(fl, fw, gp, dx, dy, s, g);
 }
 
 // ---------------------------------------------------------------------------------
@@ -704,6 +739,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     const float scale = attn_scale<HD>();
 
     __shared__ float fl[HD];  // this workgroup's freqs-gradient partial [a][j]; zeroed here, published behind the loop's barriers
+    float* fw = freq_wave_slot<HD>(p);
     if (threadIdx.x < HD) fl[threadIdx.x] = 0.f;
     const int q = qt * (16 * NW) + wave * 16 + s;
     uint4 qf[(AT<T, HD>::NKK)], dof[(AT<T, HD>::NKK)];
@@ -780,8 +816,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
             PHASE_FENCE();
         }
     }
-    dq_epilogue<T, HD, ROT>(p, dq, qb, ld, b, head, q, s, g, scale, fl);
-    if (p.E < p.N) freq_flush<false, HD>(fl, p.fpart);
+    dq_epilogue<T, HD, ROT>(p, dq, qb, ld, b, head, q, s, g, scale, fl, fw);
+    if (p.E < p.N) freq_flush<false, HD>(fl, p.fpart, p.fwave);
 }
 
 // ---------------------------------------------------------------------------------
@@ -814,6 +850,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
     const int64_t statbase = ((int64_t)b * p.heads + head) * p.N;
 
     __shared__ float fl[HD];
+    float* fw = freq_wave_slot<HD>(p);
     if (threadIdx.x < HD) fl[threadIdx.x] = 0.f;
     const int key = ktile * (16 * NW) + wave * 16 + s;
     uint4 kf[(AT<T, HD>::NKK)], vf[(AT<T, HD>::NKK)];
@@ -888,8 +925,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
             PHASE_FENCE();
         }
     }
-    dkv_epilogue<T, HD, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
-    if (p.E < p.N) freq_flush<true, HD>(fl, p.fpart);
+    dkv_epilogue<T, HD, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl, fw);
+    if (p.E < p.N) freq_flush<true, HD>(fl, p.fpart, p.fwave);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1080,7 +1117,7 @@ __device__ __forceinline__ void dq_res_loop(f32x4_t (&dq)[4], const unsigned cha
 // dq epilogue of the resident kernels (qr, cr: dq_res_prefetch)
 template <typename T, bool ROT>
 __device__ __forceinline__ void dq_res_epilogue(const AttnP& p, const f32x4_t (&dq)[4], const float (&qr)[4][4], float (&cr)[4][2], int64_t ld, int b, int head, int q,
-                                                int s, int g, float scale, float* fl) {
+                                                int s, int g, float scale, float* fl, float* fw) {
     constexpr int HD = 64;
     const int qc = min(q, p.N - 1);
     const float* cpr = p.cos_tab + ((int64_t)max(qc - p.E, 0) * p.heads + head) * 32;
@@ -1126,7 +1163,7 @@ __device__ __forceinline__ void dq_res_epilogue(const AttnP& p, const f32x4_t (&
         gp[dt][1] = img ? scale * (dq[dt][2] * qr[dt][2] + dq[dt][3] * qr[dt][3]) : 0.f;
     }
     store_row<T>(dqp, oq, g, row);
-    if (p.E < p.N) freq_accum(fl, gp, dx, dy, s, g);
+    if (p.E < p.N) freq_accum(fl, fw, gp, dx, dy, s, g);
 }
 // delta = rowsum(dO . O) of the lane's query: the four lanes g of a row each sum their chunks (kk, then the elements in order), then the group
 template <typename T>
@@ -1200,6 +1237,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const T* ob = reinterpret_cast<const T*>(p.o) + (int64_t)b * p.N * C + head * HD;
     const float scale = 0.125f;
     __shared__ float fl[64];  // freqs-gradient partial of this (sample, head)
+    float* fw = freq_wave_slot<64>(p);
     if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
     stage_all<T, true, false, true, ROT>(nullptr, kimg, kb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, 1.0f, p.sin_tab);
     stage_all<T, false, false, true>(nullptr, vimg, vb, ld, npad, p.N, p.E, nullptr, p.heads, head, 1.0f);
@@ -1238,9 +1276,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #pragma unroll
         for (int i = 0; i < 4; ++i) dq[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         dq_res_loop<T>(dq, kimg, vimg, npad, s, g, qf, dof, lse, delta);
-        dq_res_epilogue<T, ROT>(p, dq, qr, cr, ld, b, head, q, s, g, scale, fl);
+        dq_res_epilogue<T, ROT>(p, dq, qr, cr, ld, b, head, q, s, g, scale, fl, fw);
     }
-    if (p.E < p.N) freq_flush<false>(fl, p.fpart);
+    if (p.E < p.N) freq_flush<false>(fl, p.fpart, p.fwave);
 }
 
 // Diagnostic build only (-DATT_STAMP, tools/build_stamp.sh): per-phase s_memtime sums of wave 0 of one workgroup
@@ -1278,6 +1316,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const float scale = 0.125f;
     const int64_t statbase = ((int64_t)b * p.heads + head) * p.N;
     __shared__ float fl[64];  // freqs-gradient partial of this (sample, head)
+    float* fw = freq_wave_slot<64>(p);
     if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
     stage_all<T, true, false, true, ROT>(nullptr, qimg, qb, ld, npad, p.N, p.E, p.cos_tab, p.heads, head, scale, p.sin_tab);
     stage_all<T, false, false, true>(nullptr, doimg, dob, C, npad, p.N, p.E, nullptr, p.heads, head, 1.0f);
@@ -1318,10 +1357,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         ATT_T(2);
         dkv_res_loop<T>(dk, dv, qimg, doimg, lse_s, del_s, npad, s, g, kf, vf);
         ATT_T(3);
-        dkv_epilogue<T, 64, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
+        dkv_epilogue<T, 64, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl, fw);
         ATT_T(4);
     }
-    if (p.E < p.N) freq_flush<true>(fl, p.fpart);
+    if (p.E < p.N) freq_flush<true>(fl, p.fpart, p.fwave);
 #ifdef ATT_STAMP
     if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0)
         for (int i = 0; i < 8; ++i) g_att_stamp[i] = tsum[i];
@@ -1380,6 +1419,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const float scale = 0.125f;
     const int64_t statbase = ((int64_t)b * p.heads + head) * p.N;
     __shared__ float fl[64];  // freqs-gradient partial of this (sample, head), both phases
+    float* fw = freq_wave_slot<64>(p);
     if (threadIdx.x < 64) fl[threadIdx.x] = 0.f;
     const int row = wave * 16 + s;  // the lane's query (delta, phase B)
     const int ntiles = (p.N + 15) / 16;
@@ -1440,7 +1480,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         for (int i = 0; i < 4; ++i) dq[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         dq_res_loop<T>(dq, kimg, vimg, npad, s, g, qf, dof, lse, delta);
         ATT_T(4);
-        dq_res_epilogue<T, ROT>(p, dq, qr, cr, ld, b, head, q, s, g, scale, fl);
+        dq_res_epilogue<T, ROT>(p, dq, qr, cr, ld, b, head, q, s, g, scale, fl, fw);
         ATT_T(5);
     }
     // ---- phase A: key tile (wave - ntiles % 4) mod NW.  Both loops keep their SIMD busy (the waves of a SIMD finish one after the
@@ -1463,10 +1503,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         }
         dkv_res_loop<T>(dk, dv, qimg, doimg, lse_s, del_s, npad, s, g, kf, vf);
         ATT_T(6);
-        dkv_epilogue<T, 64, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl);
+        dkv_epilogue<T, 64, ROT>(p, dk, dv, kb, ld, C, b, head, key, s, g, fl, fw);
         ATT_T(7);
     }
-    if (p.E < p.N) freq_flush<false>(fl, p.fpart);
+    if (p.E < p.N) freq_flush<false>(fl, p.fpart, p.fwave);
 #ifdef ATT_STAMP
     if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0)
         for (int i = 0; i < 8; ++i) g_att_stamp[i] = tsum[i];
@@ -1816,10 +1856,11 @@ extern "C" int lnx_rope_cos_tables(const lnx_rope_table* t, int n, void* stream)
 }
 
 // floats of lnx_attn_bwd's freqs-gradient workspace: one [2][head_dim / 2] partial per workgroup of its finest tiling
-extern "C" int64_t lnx_attn_bwd_ws_floats(int B, int N, int heads) { return (int64_t)B * heads * cdiv(N, BT) * 64; }
+// (deterministic mode: behind them, FREQ_WAVES per-wave slots of the same shape per workgroup -- freq_accum)
 extern "C" int64_t lnx_attn_bwd_ws_floats_hd(int B, int N, int heads, int head_dim) {
-    return hd_ok(head_dim) ? (int64_t)B * heads * cdiv(N, BT) * head_dim : 0;
+    return hd_ok(head_dim) ? (int64_t)B * heads * cdiv(N, BT) * head_dim * (deterministic() ? 1 + FREQ_WAVES : 1) : 0;
 }
+extern "C" int64_t lnx_attn_bwd_ws_floats(int B, int N, int heads) { return lnx_attn_bwd_ws_floats_hd(B, N, heads, 64); }
 
 // ROT = the call's rope_mode is LNX_ROPE_ROTATE: the same families and launch shapes, the rotating instantiations
 template <bool ROT>
@@ -1841,7 +1882,7 @@ int attn_fwd_launch(const lnx_attn_args* a, void* stream) {
 }
 
 template <bool ROT>
-int attn_bwd_launch(const lnx_attn_bwd_args* a, void* stream) {
+int attn_bwd_launch(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* stream) {
     const int hd = a->head_dim ? a->head_dim : 64;
     if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, hd, "lnx_attn_bwd")) return 1;
     if (ROT) {
@@ -1859,6 +1900,13 @@ int attn_bwd_launch(const lnx_attn_bwd_args* a, void* stream) {
     int family = LNX_ATTN_KERNEL_NONE;
     if (attn_setup<ROT>(a, hd, "lnx_attn_bwd", p, family)) return 1;
     if (ROT) p.W = a->grid_w > 0 ? a->grid_w : 1;
+    if (deterministic() && a->E < a->N) {
+        const int64_t partials = (int64_t)a->B * a->heads * cdiv(a->N, BT) * hd, need = partials * (1 + FREQ_WAVES);
+        LNX_CHECK(freq_ws_floats >= need,
+                  "lnx_attn_bwd: deterministic mode needs lnx_attn_bwd_sized with freq_ws_floats >= lnx_attn_bwd_ws_floats_hd(...) = %lld floats with the mode "
+                  "on (got %lld): the waves' slots lie behind the workgroups' partials", (long long)need, (long long)freq_ws_floats);
+        p.fwave = a->freq_ws + partials;
+    }
     p.d_o = a->d_o; p.dqkv = a->dqkv; p.fpart = a->freq_ws; p.dsin = cos_or_stub(a->dsin_tab, a->qkv); p.delta = a->delta;
     int per_bh = 0;
     g_last_bwd_launches.store(2, std::memory_order_relaxed);  // every path but the one-kernel resident backward
@@ -1887,11 +1935,13 @@ extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
     return a->rope_mode == LNX_ROPE_ROTATE ? attn_fwd_launch<true>(a, stream) : attn_fwd_launch<false>(a, stream);
 }
 
-extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) {
+extern "C" int lnx_attn_bwd_sized(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* stream) {
     LNX_CHECK(a && a->qkv && a->o && a->lse && a->d_o && a->dqkv && a->delta, "lnx_attn_bwd: null operand");
     LNX_CHECK(a->rope_mode == LNX_ROPE_COS || a->rope_mode == LNX_ROPE_ROTATE, "lnx_attn_bwd: bad rope_mode %d", a->rope_mode);
-    return a->rope_mode == LNX_ROPE_ROTATE ? attn_bwd_launch<true>(a, stream) : attn_bwd_launch<false>(a, stream);
+    return a->rope_mode == LNX_ROPE_ROTATE ? attn_bwd_launch<true>(a, freq_ws_floats, stream) : attn_bwd_launch<false>(a, freq_ws_floats, stream);
 }
+
+extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) { return lnx_attn_bwd_sized(a, 0, stream); }
 
 extern "C" int lnx_attn_dispatch(int dtype, int N, int head_dim, int has_drop_mask) {
     const int hd = head_dim ? head_dim : 64;

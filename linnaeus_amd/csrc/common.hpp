@@ -153,11 +153,17 @@ __device__ __forceinline__ void tile_origin(int logical, int tiles_n, int& m0, i
 // host side (api.cpp)
 int persistent_cus(int cus);   // CUs a persistent launch may occupy: cus - margin
 void set_cu_margin(int m);
-bool tile_sched_static();      // LNX_TILE_SCHED=static, read per launch
+bool tile_sched_static();      // LNX_TILE_SCHED=static or the deterministic mode, read per launch
+bool deterministic();          // lnx_set_deterministic / LNX_DETERMINISTIC=1, read per launch
+// fold.hip: the one second stage of the deterministic mode.  dst[e] += sum_i part[i * stride + e] for e < len, partials folded in index
+// order (16 contiguous row groups of four chains each, combined in a fixed order) and added to dst once
+void launch_fold(const float* part, int n, int64_t stride, int64_t len, float* dst, hipStream_t st);
 int tile_slot_of(hipStream_t st);  // the counter set launches on this stream draw from (one per stream: a stream's kernels run one after the other); -1 once 64 streams hold one (static stride)
 int device_cus();              // cached multiProcessorCount of the current device (0 on failure)
 // norm.hip: postpone the second stage of a LayerNorm-style column-sum reduction (part[nwg][2C] -> dw, db) to lnx_layernorm_bwd_flush()
 void ln_postpone_reduce(const float* part, int nwg, int C, float* dw, float* db, int slices, hipStream_t st);
+// norm.hip: deterministic mode -- dw[c] += the rows' part[row][c], db[c] += part[row][C + c], rows in index order (launch_fold)
+void ln_fold_rows(const float* part, int rows, int C, float* dw, float* db, hipStream_t st);
 
 // ---------------------------------------------------------------------------------
 // scalar type traits.  T is the storage type of activations / GEMM operands:

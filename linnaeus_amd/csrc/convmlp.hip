@@ -63,6 +63,12 @@ struct CmP {
                                 // kernel keeps it): operand of a pwconv2 weight gradient that lnx_layerscale_apply_wgrad scales afterwards
     float* dlnw;                // bwd: [C] += LayerNorm weight / bias gradient (host side of the launch: the reduce kernel's targets)
     float* dlnb;
+    // deterministic mode (lnx_set_deterministic; both 0 / NULL outside it): no float meets another in an order the code does not fix.
+    // Every WAVE leaves its column sums in a row of its own -- part is then [gridDim.x * waves][2C], dgpart [gridDim.x * waves][C] -- and
+    // the second stages fold the rows in index order.  A wave of the streamed-weight kernel owns one 16-row tile and stores its sums
+    // straight to its row; a wave of the resident-weight kernel adds its tiles' LayerNorm sums (program order) in an LDS slot of its own.
+    int det;
+    float* dgpart;
 };
 
 __device__ __forceinline__ void mfma16(f32x4_t& acc, const uint4& a, const uint4& b) {
@@ -367,7 +373,7 @@ __device__ __forceinline__ void ln_bwd_fetch(LnRow<NK>& r, const CmP& p, int m, 
 }
 template <int NK, int MT, int MTI>
 __device__ __forceinline__ void ln_bwd_rows(const CmP& p, const f32x4_t (&dl)[Geo<NK>::CT][MT], const LnRow<NK>& row, int m, int s, int g, const float* lnws,
-                                            float* dls) {
+                                            float* dls, float* grow = nullptr) {
     constexpr int C = Geo<NK>::C;
     constexpr int CT = Geo<NK>::CT;
     constexpr float invC = 1.0f / (float)C;
@@ -394,8 +400,13 @@ __device__ __forceinline__ void ln_bwd_rows(const CmP& p, const f32x4_t (&dl)[Ge
             const float dm = mv ? d : 0.f;
             const float a = row16_sum(dm * x), b = row16_sum(dm);
             if (s == 0) {
-                atomicAdd(&dls[c + r], a);
-                atomicAdd(&dls[C + c + r], b);
+                if (grow) {  // deterministic mode, one tile per wave: this wave's row of p.part, every entry written once
+                    grow[c + r] = a;
+                    grow[C + c + r] = b;
+                } else {  // (deterministic mode, resident kernel: dls is the wave's own slot -- one contributor, program order)
+                    atomicAdd(&dls[c + r], a);
+                    atomicAdd(&dls[C + c + r], b);
+                }
             }
         }
     }
@@ -658,7 +669,10 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
                     t += __shfl_xor(t, 2, 64);
                     t += __shfl_xor(t, 4, 64);
                     t += __shfl_xor(t, 8, 64);
-                    if (s == 0) atomicAdd(&dgs[c + j], t);  // LDS atomic, 4 lanes per wave
+                    if (s == 0) {
+                        if (p.dgpart) p.dgpart[((int64_t)blockIdx.x * NW + wave) * C + c + j] = t;  // (MT == 1: written once)
+                        else atomicAdd(&dgs[c + j], t);  // LDS atomic, 4 lanes per wave
+                    }
                 }
             }
             zf[mt][ks] = dzv.raw;
@@ -734,7 +748,7 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
     }
     if constexpr (LNB) {
         static_assert(MT == 1, "ln_bwd_rows is instantiated per m-tile");
-        ln_bwd_rows<NK, MT, 0>(p, dl, lrow, m_base + s, s, g, lws, dls);
+        ln_bwd_rows<NK, MT, 0>(p, dl, lrow, m_base + s, s, g, lws, dls, p.det ? p.part + ((int64_t)blockIdx.x * NW + wave) * (2 * C) : nullptr);
     } else {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -750,6 +764,7 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
         }
     }
     __syncthreads();
+    if (p.det) return;  // (every wave has stored its rows)
     if constexpr (DG)
         for (int i = threadIdx.x; i < C; i += 64 * NW) atomicAdd(p.dgamma + i, dgs[i]);
     if constexpr (LNB)
@@ -1034,6 +1049,12 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int s = lane & 15, g = lane >> 4;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
+    if constexpr (LNB) {
+        if (p.det) {  // this wave's own [2C] slot behind gms (the launch adds 8 x 2C floats of LDS in the mode), zeroed by the wave itself
+            dls = gms + C + wave * (2 * C);
+            for (int i = lane; i < 2 * C; i += 64) dls[i] = 0.f;
+        }
+    }
 
     for (int i = threadIdx.x; i < 4 * C; i += 512) b1s[i] = p.b1[i];
     for (int i = threadIdx.x; i < C; i += 512) {
@@ -1041,7 +1062,7 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
         gms[i] = p.gamma[i];
         if constexpr (LNB) {
             lws[i] = p.lnw[i];
-            dls[i] = dls[C + i] = 0.f;
+            if (!p.det) dls[i] = dls[C + i] = 0.f;
         }
     }
     const bool dyn = p.tile_slot >= 0;  // tile scheduling as in convmlp_fwd_res_kernel
@@ -1212,14 +1233,23 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
                 t += __shfl_xor(t, 2, 64);
                 t += __shfl_xor(t, 4, 64);
                 t += __shfl_xor(t, 8, 64);
-                if (s == 0) atomicAdd(&dgs[ks * 32 + 8 * g + j], t);
+                if (s == 0) {
+                    if (p.dgpart) p.dgpart[((int64_t)blockIdx.x * 8 + wave) * C + ks * 32 + 8 * g + j] = t;
+                    else atomicAdd(&dgs[ks * 32 + 8 * g + j], t);
+                }
             }
     }
     __syncthreads();
     if constexpr (DG)
-        for (int i = threadIdx.x; i < C; i += 512) atomicAdd(p.dgamma + i, dgs[i]);
-    if constexpr (LNB)
-        for (int i = threadIdx.x; i < 2 * C; i += 512) p.part[(int64_t)blockIdx.x * (2 * C) + i] = dls[i];
+        if (!p.dgpart)
+            for (int i = threadIdx.x; i < C; i += 512) atomicAdd(p.dgamma + i, dgs[i]);
+    if constexpr (LNB) {
+        if (p.det) {  // the wave's slot -> the wave's row
+            for (int i = lane; i < 2 * C; i += 64) p.part[((int64_t)blockIdx.x * 8 + wave) * (2 * C) + i] = dls[i];
+        } else {
+            for (int i = threadIdx.x; i < 2 * C; i += 512) p.part[(int64_t)blockIdx.x * (2 * C) + i] = dls[i];
+        }
+    }
     if (reset_ctr && lane == 0) sched_reset(ctr);
 }
 
@@ -1257,6 +1287,26 @@ static int bwd_grid(int C, int M) {
     return cdiv(M, 16 * (nw8 ? 8 : 4));  // streamed-weight kernels: NW waves x 16 rows per workgroup
 }
 
+// waves per workgroup of the backward launch for C: contributors per workgroup of the deterministic mode's per-wave rows
+static int bwd_waves(int C) { return C <= 96 ? 8 : (nw8 ? 8 : 4); }
+
+// deterministic mode: rows of [2C] (LNB) and [C] (DG) per wave of `grid` workgroups; sets p.det / p.dgpart or refuses (-1) a scratch too
+// small for the UNCLAMPED grid (what lnx_convmlp_bwd_ws_floats reports).  Outside the mode: the existing check.
+template <bool LNB, bool DG>
+static int bwd_scratch(CmP& q, int grid_unclamped) {
+    if (!deterministic()) return LNB && (int64_t)grid_unclamped * 2 * q.C > q.part_floats ? -1 : 0;
+    if (!LNB && !DG) return 0;
+    const int64_t rows = (int64_t)grid_unclamped * bwd_waves(q.C);
+    if (q.part == nullptr || rows * ((LNB ? 2 : 0) + (DG ? 1 : 0)) * q.C > q.part_floats) return -1;
+    q.det = 1;
+    if (DG) q.dgpart = q.part + (LNB ? rows * 2 * q.C : 0);
+    return 0;
+}
+// ... and behind the kernel: dgamma += the waves' rows in index order (the LayerNorm rows go through reduce_ln_partials)
+static void fold_dgamma(const CmP& q, int grid, hipStream_t st) {
+    if (q.dgpart) launch_fold(q.dgpart, grid * bwd_waves(q.C), q.C, q.C, q.dgamma, st);
+}
+
 // workgroups a resident-weight (one per CU) launch may use: the CUs minus the margin, 256 at most (the partial-sum scratch is sized for that)
 static int res_room() {
     const int cus = device_cus();
@@ -1287,6 +1337,10 @@ int launch_fwd_res(const CmP& p, hipStream_t st) {
 }
 // LNB launches: the workgroups' column sums (p.part) are folded into the LayerNorm weight / bias gradient right behind the kernel
 inline int reduce_ln_partials(const CmP& p, int nwg, hipStream_t st) {
+    if (deterministic()) {
+        ln_fold_rows(p.part, nwg, p.C, p.dlnw, p.dlnb, st);
+        return 0;
+    }
     if (p.ln_defer) {
         ln_postpone_reduce(p.part, nwg, p.C, p.dlnw, p.dlnb, nwg >= 64 ? 64 : 1, st);
         return 0;
@@ -1296,20 +1350,22 @@ inline int reduce_ln_partials(const CmP& p, int nwg, hipStream_t st) {
 }
 template <int NK, int MT, bool ST, bool LNB, bool DG>
 int launch_bwd_res_t(const CmP& p, hipStream_t st) {
-    const size_t lds = 2 * (4 * Geo<NK>::C / 64) * Geo<NK>::PART + 9 * Geo<NK>::C * sizeof(float);
+    const size_t lds0 = 2 * (4 * Geo<NK>::C / 64) * Geo<NK>::PART + 9 * Geo<NK>::C * sizeof(float);
+    const size_t lds_det = lds0 + (LNB ? 8 * 2 * Geo<NK>::C * sizeof(float) : 0);  // + the waves' own column-sum slots (deterministic mode)
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convmlp_bwd_res_kernel<NK, MT, ST, LNB, DG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convmlp_bwd_res_kernel<NK, MT, ST, LNB, DG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_det);
         attr = true;
     }
     int grid = bwd_grid(p.C, p.M);
-    if (LNB && (int64_t)grid * 2 * p.C > p.part_floats) return -1;  // (checked against the unclamped grid: what lnx_convmlp_bwd_ws_floats reports)
+    CmP q = p;
+    if (bwd_scratch<LNB, DG>(q, grid) != 0) return -1;  // (checked against the unclamped grid: what lnx_convmlp_bwd_ws_floats reports)
     const int room = res_room();
     if (grid > room) grid = room;
-    CmP q = p;
     q.tile_slot = tile_sched_static() ? -1 : tile_slot_of(st);
-    hipLaunchKernelGGL((convmlp_bwd_res_kernel<NK, MT, ST, LNB, DG>), dim3(grid), dim3(512), lds, st, q);
-    return LNB ? reduce_ln_partials(p, grid, st) : 0;
+    hipLaunchKernelGGL((convmlp_bwd_res_kernel<NK, MT, ST, LNB, DG>), dim3(grid), dim3(512), q.det ? lds_det : lds0, st, q);
+    fold_dgamma(q, grid, st);
+    return LNB ? reduce_ln_partials(p, q.det ? grid * 8 : grid, st) : 0;
 }
 template <int NK, int MT>
 int launch_bwd_res(const CmP& p, hipStream_t st) {
@@ -1349,9 +1405,11 @@ int launch_bwd_t(const CmP& p, hipStream_t st) {
     }
     static_assert(MT == 1, "bwd_grid() assumes 16-row wave tiles in the streamed-weight backward");
     const int grid = bwd_grid(p.C, p.M);
-    if (LNB && (int64_t)grid * 2 * p.C > p.part_floats) return -1;
-    hipLaunchKernelGGL((convmlp_bwd_kernel<NK, MT, NW, ST, LNB, DG>), dim3(grid), dim3(64 * NW), lds, st, p);
-    return LNB ? reduce_ln_partials(p, grid, st) : 0;
+    CmP q = p;
+    if (bwd_scratch<LNB, DG>(q, grid) != 0) return -1;
+    hipLaunchKernelGGL((convmlp_bwd_kernel<NK, MT, NW, ST, LNB, DG>), dim3(grid), dim3(64 * NW), lds, st, q);
+    fold_dgamma(q, grid, st);
+    return LNB ? reduce_ln_partials(p, q.det ? grid * NW : grid, st) : 0;
 }
 template <int NK, int MT, int NW>
 int launch_bwd(const CmP& p, hipStream_t st) {
@@ -1367,6 +1425,8 @@ int launch_bwd(const CmP& p, hipStream_t st) {
 
 extern "C" int64_t lnx_convmlp_bwd_ws_floats(int C, int M) {
     if (!lnx_convmlp_supported(LNX_BF16, C) || M <= 0) return 0;
+    // (deterministic mode: a [2C] LayerNorm row and a [C] dgamma row per WAVE instead of [2C] per workgroup)
+    if (deterministic()) return (int64_t)bwd_grid(C, M) * bwd_waves(C) * 3 * C;
     return (int64_t)bwd_grid(C, M) * 2 * C;
 }
 
@@ -1406,6 +1466,7 @@ extern "C" int lnx_convmlp_bwd(const lnx_convmlp_bwd_args* a, void* stream) {
     LNX_CHECK(lnx_convmlp_supported(a->dtype, a->C), "lnx_convmlp_bwd: unsupported dtype %d / C %d", a->dtype, a->C);
     LNX_CHECK(a->M > 0, "lnx_convmlp_bwd: empty");
     if (a->rowscale) LNX_CHECK(a->rows_per_sample > 0, "lnx_convmlp_bwd: rowscale needs rows_per_sample");
+    if (a->z && deterministic()) LNX_CHECK(a->ws, "lnx_convmlp_bwd: deterministic mode needs ws (lnx_convmlp_bwd_ws_floats) for the waves' dgamma partial sums");
     if (a->y) LNX_CHECK(a->ln_w && a->mean && a->rstd && a->d_ln_w && a->d_ln_b && a->ws, "lnx_convmlp_bwd: the fused LayerNorm form needs ln_w, mean, rstd, d_ln_w, d_ln_b and ws");
     CmP p{};
     p.y = (const unsigned char*)a->y; p.lnw = a->ln_w; p.mean = const_cast<float*>(a->mean); p.rstd = const_cast<float*>(a->rstd);
@@ -1426,7 +1487,7 @@ extern "C" int lnx_convmlp_bwd(const lnx_convmlp_bwd_args* a, void* stream) {
         case 128: rc = nw8 ? launch_bwd<4, 1, 8>(p, st) : launch_bwd<4, 1, 4>(p, st); break;
         case 192: rc = nw8 ? launch_bwd<6, 1, 8>(p, st) : launch_bwd<6, 1, 4>(p, st); break;
     }
-    LNX_CHECK(rc == 0, "lnx_convmlp_bwd: ws too small for the LayerNorm partial sums (M=%d C=%d ws_floats=%lld)", a->M, a->C, (long long)a->ws_floats);
+    LNX_CHECK(rc == 0, "lnx_convmlp_bwd: ws too small for the partial sums (M=%d C=%d ws_floats=%lld; lnx_convmlp_bwd_ws_floats says how many)", a->M, a->C, (long long)a->ws_floats);
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -195,6 +195,7 @@ struct DwWgP {
     float* db;
     int B, H, W, C;
     int tiles_h, tiles_w, cblocks, ntile;  // ntile = B * tiles_h * tiles_w
+    float* part;  // deterministic mode: [walkers][49 C | C] partial sums instead of the atomics (folded by launch_fold); else NULL
 };
 
 template <typename TDY>
@@ -294,7 +295,11 @@ __global__ __launch_bounds__(256) void dwconv7_wgrad_kernel(const DwWgP p) {
             float s = 0.f;
 #pragma unroll
             for (int rr = 0; rr < 8; ++rr) s += red[(rr * 25 + t) * CB + c];
-            if (t < tcnt) atomicAdd(p.dw + (int64_t)(c0 + c) * 49 + tbeg + t, s);
+            if (p.part) {
+                float* pw = p.part + (int64_t)walker * p.C * 50;
+                if (t < tcnt) pw[(c0 + c) * 49 + tbeg + t] = s;
+                else if (pass == 1) pw[p.C * 49 + c0 + c] = s;
+            } else if (t < tcnt) atomicAdd(p.dw + (int64_t)(c0 + c) * 49 + tbeg + t, s);
             else if (pass == 1 && p.db) atomicAdd(p.db + c0 + c, s);
         }
         __syncthreads();
@@ -340,18 +345,49 @@ extern "C" int lnx_dwconv7_fwd(const lnx_dwconv_args* a, void* stream) {
     return 0;
 }
 
+// workgroups per 32-channel block of the VALU weight-gradient kernel -- the launch and lnx_dwconv7_wgrad_ws_floats() agree through this
+static int wgrad_walkers(int B, int H, int W, int C) {
+    const int64_t ntile = (int64_t)B * cdiv(H, TH) * cdiv(W, TW);
+    int walkers = 768 / (C / CB);
+    if (walkers < 1) walkers = 1;
+    return walkers > ntile ? (int)ntile : walkers;
+}
+
+static bool wgrad_shape_ok(int B, int H, int W, int C) { return B > 0 && H > 0 && W > 0 && C > 0 && C % CB == 0; }
+static bool wgrad_dtype_ok(int d) { return d == LNX_F32 || d == LNX_BF16; }
+
+extern "C" int64_t lnx_dwconv7_wgrad_ws_floats(int B, int H, int W, int C, int x_dtype, int dy_dtype) {
+    if (!wgrad_shape_ok(B, H, W, C) || !wgrad_dtype_ok(x_dtype) || !wgrad_dtype_ok(dy_dtype)) return 0;
+    const bool mfma = lnx_dwconv_mfma_enabled() && (x_dtype == LNX_BF16 || dy_dtype == LNX_BF16);
+    return (int64_t)(mfma ? lnx_dwconv7_mfma_wgrad_walkers(B, H, W, C) : wgrad_walkers(B, H, W, C)) * 50 * C;
+}
+
+// deterministic mode: the walkers' partial sums [walkers][49 C | C] -> dw, db, in walker order (after either kernel)
+int lnx_dwconv7_wgrad_fold(const lnx_dwconv_wgrad_args* a, int walkers, hipStream_t st) {
+    launch_fold(a->ws, walkers, 50 * (int64_t)a->C, 49 * (int64_t)a->C, a->dw, st);
+    if (a->db) launch_fold(a->ws + 49 * (int64_t)a->C, walkers, 50 * (int64_t)a->C, a->C, a->db, st);
+    return 0;
+}
+
 extern "C" int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* a, void* stream) {
     LNX_CHECK(a && a->x && a->dy && a->dw, "lnx_dwconv7_wgrad: null operand");
-    LNX_CHECK(a->B > 0 && a->H > 0 && a->W > 0 && a->C > 0 && a->C % CB == 0, "lnx_dwconv7_wgrad: bad shape");
+    LNX_CHECK(wgrad_shape_ok(a->B, a->H, a->W, a->C), "lnx_dwconv7_wgrad: bad shape");
+    if (deterministic()) {
+        const int64_t need = lnx_dwconv7_wgrad_ws_floats(a->B, a->H, a->W, a->C, a->x_dtype, a->dy_dtype);
+        LNX_CHECK(wgrad_dtype_ok(a->x_dtype) && wgrad_dtype_ok(a->dy_dtype), "lnx_dwconv7_wgrad: bad dtypes");
+        LNX_CHECK(need > 0, "lnx_dwconv7_wgrad: too many tiles");
+        LNX_CHECK(a->ws != nullptr && a->ws_floats >= need,
+                  "lnx_dwconv7_wgrad: deterministic mode needs ws of lnx_dwconv7_wgrad_ws_floats(...) = %lld floats (got %lld): without it dw / db are summed by float atomics",
+                  (long long)need, (long long)(a->ws ? a->ws_floats : 0));
+    }
     if (lnx_dwconv_mfma_enabled() && (a->x_dtype == LNX_BF16 || a->dy_dtype == LNX_BF16)) return lnx_dwconv7_mfma_wgrad(a, (hipStream_t)stream);
     DwWgP p;
     p.x = a->x; p.dy = a->dy; p.dw = a->dw; p.db = a->db;
     p.B = a->B; p.H = a->H; p.W = a->W; p.C = a->C;
     p.tiles_h = cdiv(a->H, TH); p.tiles_w = cdiv(a->W, TW); p.cblocks = a->C / CB;
     p.ntile = a->B * p.tiles_h * p.tiles_w;
-    int walkers = 768 / p.cblocks;
-    if (walkers < 1) walkers = 1;
-    if (walkers > p.ntile) walkers = p.ntile;
+    const int walkers = wgrad_walkers(a->B, a->H, a->W, a->C);
+    p.part = deterministic() && a->ws && a->ws_floats >= (int64_t)walkers * 50 * a->C ? a->ws : nullptr;
     const int grid = walkers * p.cblocks;
     hipStream_t st = (hipStream_t)stream;
     const int code = a->x_dtype * 2 + a->dy_dtype;
@@ -362,6 +398,7 @@ extern "C" int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* a, void* stream) {
         case 3: hipLaunchKernelGGL((dwconv7_wgrad_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, st, p); break;
         default: LNX_CHECK(false, "lnx_dwconv7_wgrad: bad dtypes");
     }
+    if (p.part) lnx_dwconv7_wgrad_fold(a, walkers, st);
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -452,6 +452,7 @@ struct MwP {
     float* db;
     int B, H, W, C;
     int tiles_h, tiles_w, nwalk, per, ntile;  // walkers per 32-channel group, tiles per walker
+    float* part;  // deterministic mode: [walkers][49 C | C] partial sums instead of the atomics (folded by launch_fold); else NULL
 };
 
 template <typename TX, typename TDY>
@@ -547,6 +548,34 @@ __global__ __launch_bounds__(WT, 4) void dwconv7_mfma_wgrad_kernel(const MwP p) 
             __syncthreads();
         }
     }
+    if (p.part) {
+        // deterministic mode: every (channel, tap) of the workgroup has one owner lane -- plain stores to the walker's row; the bias
+        // sums go lane -> wave by shuffles, wave -> workgroup by wave index (slots in the x stage, which nobody reads any more)
+        float* pw = p.part + (int64_t)walker * p.C * 50;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = 4 * g + i;
+            const int kx = m & 7;
+            if ((m >> 3) == ch && kx < 7 && kk < 7) pw[(c0 + CPW * wave + ch) * 49 + kk * 7 + kx] = acc[i];
+        }
+        float* wsum = reinterpret_cast<float*>(xt);
+        static_assert(64 % Sd::NCG == 0 && (Sd::NCG & (Sd::NCG - 1)) == 0, "lanes of one channel group: lane % NCG");
+#pragma unroll
+        for (int j = 0; j < Sd::CH; ++j) {
+            float t = dbs[j];
+#pragma unroll
+            for (int o = Sd::NCG; o < 64; o <<= 1) t += __shfl_xor(t, o, 64);
+            if (lane < Sd::NCG) wsum[wave * WCB + lane * Sd::CH + j] = t;
+        }
+        __syncthreads();
+        if (threadIdx.x < WCB) {
+            float t = 0.f;
+#pragma unroll
+            for (int w = 0; w < WT / 64; ++w) t += wsum[w * WCB + threadIdx.x];
+            pw[p.C * 49 + c0 + threadIdx.x] = t;
+        }
+        return;
+    }
     // D[m = 4g + i][n]: valid where both indices name the same channel of the pair and kx, ky < 7
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -639,6 +668,18 @@ int lnx_dwconv7_mfma_fwd(const lnx_dwconv_args* a, hipStream_t st) {
     return 0;
 }
 
+// walkers (workgroups per 16-channel block) of the weight-gradient launch: here, and in lnx_dwconv7_wgrad_ws_floats()
+int lnx_dwconv7_mfma_wgrad_walkers(int B, int H, int W, int C) {
+    const int64_t ntile = (int64_t)B * cdiv(H, WH) * cdiv(W, WW);
+    if (ntile >= (1ll << 31)) return 0;
+    const int groups = C / (2 * WCB);
+    int walkers = cus() / groups;  // one resident sibling pair per CU
+    if (walkers < 1) walkers = 1;
+    if (walkers > ntile) walkers = (int)ntile;
+    const int per = cdiv((int)ntile, walkers);
+    return cdiv((int)ntile, per);  // same longest walk, no idle walkers
+}
+
 int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, hipStream_t st) {
     MwP p;
     p.x = a->x; p.dy = a->dy; p.dw = a->dw; p.db = a->db;
@@ -648,12 +689,10 @@ int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, hipStream_t st) {
     LNX_CHECK(ntile < (1ll << 31), "lnx_dwconv7_wgrad: too many tiles");
     p.ntile = (int)ntile;
     const int groups = a->C / (2 * WCB);
-    int walkers = cus() / groups;  // one resident sibling pair per CU
-    if (walkers < 1) walkers = 1;
-    if (walkers > p.ntile) walkers = p.ntile;
+    const int walkers = lnx_dwconv7_mfma_wgrad_walkers(a->B, a->H, a->W, a->C);
     p.per = cdiv(p.ntile, walkers);
-    walkers = cdiv(p.ntile, p.per);  // same longest walk, no idle walkers
     p.nwalk = walkers;
+    p.part = deterministic() && a->ws && a->ws_floats >= (int64_t)walkers * 50 * a->C ? a->ws : nullptr;  // (lnx_dwconv7_wgrad refused a smaller one)
     const int grid = 16 * cdiv(walkers * groups, 8);
     const int code = a->x_dtype * 2 + a->dy_dtype;
     int rc = 0;
@@ -664,6 +703,7 @@ int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, hipStream_t st) {
         default: LNX_CHECK(false, "lnx_dwconv7_wgrad: the MFMA path needs a bf16 operand");
     }
     if (rc) return rc;
+    if (p.part) lnx_dwconv7_wgrad_fold(a, walkers, st);
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -7,3 +7,6 @@
 bool lnx_dwconv_mfma_enabled();
 int lnx_dwconv7_mfma_fwd(const lnx_dwconv_args* a, hipStream_t st);
 int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, hipStream_t st);
+int lnx_dwconv7_mfma_wgrad_walkers(int B, int H, int W, int C);  // workgroups per 16-channel block of that launch
+// dwconv.hip: deterministic mode, after either weight-gradient kernel -- the walkers' partial sums in a->ws -> dw, db in walker order
+int lnx_dwconv7_wgrad_fold(const lnx_dwconv_wgrad_args* a, int walkers, hipStream_t st);

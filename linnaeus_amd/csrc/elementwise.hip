@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void scale_cast_kernel(const float* __restrict
 template <typename T>
 __global__ __launch_bounds__(256) void layerscale_bwd_kernel(const float* __restrict__ g, const T* __restrict__ z, const float* __restrict__ gamma,
                                                              const float* __restrict__ rowscale, int rps, T* __restrict__ dz,
-                                                             float* __restrict__ dgamma, int M, int C) {
+                                                             float* __restrict__ dgamma, float* __restrict__ part, int M, int C) {
     extern __shared__ float red[];  // [rows_per_block][C]
     const int c4n = C >> 2;
     const int rows_pb = 256 / c4n > 0 ? 256 / c4n : 1;
@@ -96,7 +96,8 @@ __global__ __launch_bounds__(256) void layerscale_bwd_kernel(const float* __rest
     for (int c = threadIdx.x; c < C; c += 256) {
         float t = 0.f;
         for (int r = 0; r < rows_pb; ++r) t += red[r * C + c];
-        atomicAdd(dgamma + c, t);
+        if (part) part[(int64_t)blockIdx.x * C + c] = t;  // deterministic mode: folded in workgroup order by launch_fold
+        else atomicAdd(dgamma + c, t);
     }
 }
 
@@ -435,22 +436,46 @@ extern "C" int lnx_layerscale_apply_wgrad(const float* s, const float* t, int64_
     return 0;
 }
 
-extern "C" int lnx_layerscale_bwd(const float* g, const void* z, int dtype, const float* gamma, const float* rowscale, int rows_per_sample, void* dz,
-                                  float* dgamma, int M, int C, void* stream) {
+// workgroups of lnx_layerscale_bwd for (M, C) -- the launch and lnx_layerscale_bwd_ws_floats() agree through this one function
+static int layerscale_bwd_grid(int M, int C) {
+    const int rows_pb = 256 / (C / 4);
+    int grid = cdiv(M, rows_pb * 8);
+    if (grid > 2048) grid = 2048;
+    return grid < 1 ? 1 : grid;
+}
+
+extern "C" int64_t lnx_layerscale_bwd_ws_floats(int M, int C) {
+    if (M <= 0 || C <= 0 || C % 4 != 0 || C > 1024) return 0;
+    return (int64_t)layerscale_bwd_grid(M, C) * C;
+}
+
+extern "C" int lnx_layerscale_bwd_ws(const float* g, const void* z, int dtype, const float* gamma, const float* rowscale, int rows_per_sample, void* dz,
+                                     float* dgamma, int M, int C, float* ws, int64_t ws_floats, void* stream) {
     LNX_CHECK(g && z && gamma && dz && dgamma, "lnx_layerscale_bwd: null operand");
     // one lane per group of 4 columns, 256 lanes a workgroup: C / 4 <= 256
     LNX_CHECK(M > 0 && C > 0 && C % 4 == 0 && C <= 1024, "lnx_layerscale_bwd: bad shape M=%d C=%d (C is a multiple of 4, at most 1024)", M, C);
     const int c4n = C / 4;
     const int rows_pb = 256 / c4n;
-    int grid = cdiv(M, rows_pb * 8);
-    if (grid > 2048) grid = 2048;
-    if (grid < 1) grid = 1;
+    const int grid = layerscale_bwd_grid(M, C);
     const size_t lds = (size_t)rows_pb * C * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
     const int rps = rows_per_sample > 0 ? rows_per_sample : 1;
-    DISPATCH_T(dtype, hipLaunchKernelGGL((layerscale_bwd_kernel<T>), dim3(grid), dim3(256), lds, st, g, (const T*)z, gamma, rowscale, rps, (T*)dz, dgamma, M, C));
+    float* part = nullptr;
+    if (deterministic()) {
+        LNX_CHECK(ws != nullptr && ws_floats >= (int64_t)grid * C,
+                  "lnx_layerscale_bwd: deterministic mode needs lnx_layerscale_bwd_ws with ws of lnx_layerscale_bwd_ws_floats(M=%d, C=%d) = %lld floats (got %lld): "
+                  "without it dgamma is summed by float atomics", M, C, (long long)grid * C, (long long)(ws ? ws_floats : 0));
+        part = ws;
+    }
+    DISPATCH_T(dtype, hipLaunchKernelGGL((layerscale_bwd_kernel<T>), dim3(grid), dim3(256), lds, st, g, (const T*)z, gamma, rowscale, rps, (T*)dz, dgamma, part, M, C));
+    if (part) launch_fold(part, grid, C, C, dgamma, st);
     LNX_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int lnx_layerscale_bwd(const float* g, const void* z, int dtype, const float* gamma, const float* rowscale, int rows_per_sample, void* dz,
+                                  float* dgamma, int M, int C, void* stream) {
+    return lnx_layerscale_bwd_ws(g, z, dtype, gamma, rowscale, rows_per_sample, dz, dgamma, M, C, nullptr, 0, stream);
 }
 
 extern "C" int lnx_fill_rows(const float* vec, float* out, int64_t ldout, lnx_rowmap map, int M, int C, void* stream) {
@@ -463,7 +488,8 @@ extern "C" int lnx_fill_rows(const float* vec, float* out, int64_t ldout, lnx_ro
 
 extern "C" int lnx_colsum_rows(const float* in, int64_t ldin, lnx_rowmap map, float* out, int M, int C, void* stream) {
     LNX_CHECK(in && out && M > 0 && C > 0, "lnx_colsum_rows: bad arguments");
-    const int rpb = 32;
+    // deterministic mode: one workgroup walks every row (one contributor per column) -- the strips' atomics meet in any order
+    const int rpb = deterministic() ? M : 32;
     hipLaunchKernelGGL(colsum_rows_kernel, dim3(cdiv(M, rpb)), dim3(256), 0, (hipStream_t)stream, in, ldin, RowMap{map.group, map.pad, map.off}, out, M, C, rpb);
     LNX_LAUNCH_CHECK();
     return 0;
@@ -483,6 +509,7 @@ extern "C" int lnx_agg2_bwd(const float* dout, const float* a, const float* b, c
     const int64_t total = (int64_t)M * C;
     int grid = ew_grid(total, 1024);
     if (grid > 256) grid = 256;
+    if (deterministic()) grid = 1;  // three scalars: one workgroup sums them in a fixed order, one contributor each
     hipLaunchKernelGGL(agg2_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dout, a, b, w2, da, db_, dw2, dbias1, total);
     LNX_LAUNCH_CHECK();
     return 0;

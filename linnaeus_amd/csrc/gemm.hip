@@ -400,6 +400,10 @@ extern "C" int lnx_gemm_tn(const lnx_wgrad_args* a, void* stream) {
         if (splits > max_splits) splits = max_splits;
         if (splits < 1) splits = 1;
     }
+    const bool v2 = tn_v2_ok(p, a->dtype) && !nt_switches().force_v1;
+    // deterministic mode: this kernel has no workspace second stage, its splits meet in float atomics -- one split, one contributor
+    // per element (launch_tn_v2 applies its own rule to the hint)
+    if (!v2 && deterministic()) splits = 1;
     int mps = cdiv(a->M, splits);
     mps = cdiv(mps, bmc) * bmc;
     p.splits = cdiv(a->M, mps);
@@ -407,7 +411,7 @@ extern "C" int lnx_gemm_tn(const lnx_wgrad_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     static const bool no_defer = getenv("LNX_TN_NO_DEFER") != nullptr;  // A/B switch: every product reduces its own partial tiles at once
     int rc;
-    if (tn_v2_ok(p, a->dtype) && !nt_switches().force_v1) rc = launch_tn_v2(p, a->splits, st, a->defer != 0 && !no_defer);
+    if (v2) rc = launch_tn_v2(p, a->splits, st, a->defer != 0 && !no_defer);
     else if (a->dtype == LNX_BF16) rc = launch_tn<bf16_t>(p, st);
     else rc = launch_tn<float>(p, st);
     if (rc != 0) return rc;

@@ -666,6 +666,14 @@ int launch_tn_v2(const WgradP& p0, int splits_hint, hipStream_t st, bool defer) 
     }
     if (splits > mtiles) splits = mtiles;
     if (splits < 1) splits = 1;
+    const bool det = deterministic();
+    auto ws_need = [&](int sp) { return (size_t)sp * tiles * (256 * 128) + (size_t)sp * p.tiles_n * RW; };
+    if (det) {
+        // deterministic mode: two or more splits always meet in the workspace second stage (fixed order); where the workspace cannot
+        // hold them the contraction is split less, down to one workgroup per output tile (one contributor per element)
+        const size_t have = p.ws ? (size_t)p.ws_floats : 0;
+        while (splits > 1 && ws_need(cdiv(mtiles, cdiv(mtiles, splits))) > have) --splits;
+    }
     const int per = cdiv(mtiles, splits);
     p.m_per_split = per * TBM;
     p.splits = cdiv(mtiles, per);
@@ -675,7 +683,11 @@ int launch_tn_v2(const WgradP& p0, int splits_hint, hipStream_t st, bool defer) 
     const size_t need = (size_t)p.splits * tiles * (256 * 128) + (size_t)p.splits * p.tiles_n * RW;
     // padded tiles are stored and re-read whole: with poorly filled tiles (N x K well below tiles x 256 x 128) the atomics move fewer bytes
     const bool sparse_tiles = (double)p.N * p.k_store < 0.7 * (double)tiles * (256 * 128);
-    if (no_ws || p.ws == nullptr || (size_t)p.ws_floats < need || p.splits < 2 || sparse_tiles) p.ws = nullptr;
+    if (det) {
+        if (p.splits < 2) p.ws = nullptr;  // (the loop above made the workspace fit otherwise)
+    } else if (no_ws || p.ws == nullptr || (size_t)p.ws_floats < need || p.splits < 2 || sparse_tiles) {
+        p.ws = nullptr;
+    }
     const bool patch = p.a_mode == LNX_ADDR_PATCH2;
     int rc;
     if (wide_r) rc = patch ? launch_with_lds<gemm_tn_v2_kernel<256, 128, true>>(grid, 512, lds, st, p) : launch_with_lds<gemm_tn_v2_kernel<256, 128, false>>(grid, 512, lds, st, p);

@@ -62,7 +62,11 @@ __device__ __forceinline__ void softce_row(const lnx_softce_args& a, const int b
     const float g = (ignored || bad) ? 0.f : a.scale * (a.row_scale ? a.row_scale[b] : 1.0f) * cw;
     if (threadIdx.x == 0) {
         if (a.loss) a.loss[b] = loss;
-        if (a.loss_sum) atomicAdd(a.loss_sum, a.scale * (a.row_scale ? a.row_scale[b] : 1.0f) * loss);
+        if (a.loss_sum) {
+            const float term = a.scale * (a.row_scale ? a.row_scale[b] : 1.0f) * loss;
+            if (a.sum_ws) a.sum_ws[b] = term;  // deterministic mode (the entry points decide): folded in row order by launch_fold
+            else atomicAdd(a.loss_sum, term);
+        }
     }
     if (a.dlogits) {
         float* d = a.dlogits + (int64_t)b * a.ldd;
@@ -111,7 +115,15 @@ static int softce_check(const lnx_softce_args* a, const char* who, int i) {
         LNX_CHECK(a->soft == nullptr, "%s: the soft-row form excludes a [C, C] soft matrix (set %d)", who, i);
         LNX_CHECK(a->ignore_index < 0, "%s: the soft-row form has no ignore_index (set %d has %lld)", who, i, (long long)a->ignore_index);
     }
+    // the row sums meet in one float atomic per row unless the rows' terms go through sum_ws (deterministic mode)
+    LNX_CHECK(a->loss_sum == nullptr || a->sum_ws != nullptr || !deterministic(),
+              "%s: deterministic mode needs sum_ws ([B] floats) beside loss_sum in set %d: without it loss_sum is summed by float atomics", who, i);
     return 0;
+}
+
+// deterministic mode: loss_sum += the rows' terms in row order; outside it sum_ws is ignored (same kernel path as without it)
+static void softce_route(lnx_softce_args& a) {
+    if (!deterministic() || a.loss_sum == nullptr) a.sum_ws = nullptr;
 }
 
 extern "C" int lnx_softce_multi(const lnx_softce_args* args, int n, void* stream) {
@@ -122,9 +134,12 @@ extern "C" int lnx_softce_multi(const lnx_softce_args* args, int n, void* stream
         const lnx_softce_args* a = args + i;
         if (int rc = softce_check(a, "lnx_softce_multi", i)) return rc;
         m.a[i] = *a;
+        softce_route(m.a[i]);
         bmax = a->B > bmax ? a->B : bmax;
     }
     hipLaunchKernelGGL(softce_multi_kernel, dim3(bmax, n), dim3(256), 0, (hipStream_t)stream, m);
+    for (int i = 0; i < n; ++i)  // (sets may share one loss_sum: set after set)
+        if (m.a[i].sum_ws) launch_fold(m.a[i].sum_ws, m.a[i].B, 1, 1, m.a[i].loss_sum, (hipStream_t)stream);
     LNX_LAUNCH_CHECK();
     return 0;
 }
@@ -132,7 +147,10 @@ extern "C" int lnx_softce_multi(const lnx_softce_args* args, int n, void* stream
 extern "C" int lnx_softce(const lnx_softce_args* a, void* stream) {
     LNX_CHECK(a, "lnx_softce: null operand");
     if (int rc = softce_check(a, "lnx_softce", 0)) return rc;
-    hipLaunchKernelGGL(softce_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a);
+    lnx_softce_args q = *a;
+    softce_route(q);
+    hipLaunchKernelGGL(softce_kernel, dim3(q.B), dim3(256), 0, (hipStream_t)stream, q);
+    if (q.sum_ws) launch_fold(q.sum_ws, q.B, 1, 1, q.loss_sum, (hipStream_t)stream);
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -484,11 +484,19 @@ int ln_discard() {
     return n;
 }
 }  // namespace
+void ln_fold_rows(const float* part, int rows, int C, float* dw, float* db, hipStream_t st) {
+    if (dw) launch_fold(part, rows, 2 * (int64_t)C, C, dw, st);
+    if (db) launch_fold(part + C, rows, 2 * (int64_t)C, C, db, st);
+}
 void ln_postpone_reduce(const float* part, int nwg, int C, float* dw, float* db, int slices, hipStream_t st) {
+    if (deterministic()) {  // the shared fold, at once: rows in index order, one addition to dw / db (nothing waits for the flush)
+        ln_fold_rows(part, nwg, C, dw, db, st);
+        return;
+    }
     if (g_ln_pending.n > 0 && (g_ln_pending_stream != st || g_ln_pending.n == LN_BATCH)) (void)ln_flush(nullptr);
     LnReduceDesc& d = g_ln_pending.d[g_ln_pending.n++];
     d.part = part; d.dw = dw; d.db = db; d.nwg = nwg; d.C = C; d.slices = slices; d.block_start = g_ln_pending_blocks;
-    g_ln_pending_blocks += ((2 * C + 255) / 256) * slices;
+    g_ln_pending_blocks += ((2 * C + 255) / 256) * d.slices;
     g_ln_pending_stream = st;
 }
 namespace {
@@ -559,7 +567,8 @@ lnx_ln_launch plan_bwd(const LnBwdP& p, int dyd, int xd, int dxd, int64_t ws_flo
     }
     if (L.grid > cap) L.grid = cap;
     if (L.grid < 1) L.grid = 1;
-    if (L.cols == LNX_LN_COLS_WORKSPACE) L.slices = L.grid >= 64 ? 64 : 1;
+    // (deterministic mode: one slice per entry -- the whole fold in index order, then one add to the destination)
+    if (L.cols == LNX_LN_COLS_WORKSPACE) L.slices = L.grid >= 64 && !deterministic() ? 64 : 1;
     if (dyd == LNX_BF16 && xd == LNX_BF16) {
         const int g2 = pick_pair_g(p.C);
         const int64_t dxsize = dxd == LNX_BF16 ? 2 : 4;
@@ -617,7 +626,8 @@ void launch_bwd(LnBwdP p, const lnx_ln_launch& L, hipStream_t st, bool defer) {
     LN_BWD(8, 3, 1) LN_BWD(16, 3, 1) LN_BWD(32, 3, 1) LN_BWD(64, 3, 1) LN_BWD(64, 4, 1) LN_BWD(64, 6, 1) LN_BWD(64, 8, 1)
 #undef LN_BWD
     if (p.part) {
-        if (defer) ln_postpone_reduce(p.part, L.grid, p.C, p.dw, p.db, L.slices, st);
+        if (deterministic()) ln_fold_rows(p.part, L.grid, p.C, p.dw, p.db, st);
+        else if (defer) ln_postpone_reduce(p.part, L.grid, p.C, p.dw, p.db, L.slices, st);
         else hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(cdiv(2 * p.C, 256), L.slices), dim3(256), 0, st, p.part, L.grid, p.C, p.dw, p.db);
     }
 }
@@ -717,6 +727,8 @@ extern "C" int lnx_layernorm_bwd(const lnx_ln_bwd_args* a, void* stream) {
     LnBwdP p;
     if (bwd_setup(a, p) != 0) return 1;
     const lnx_ln_launch L = plan_bwd(p, a->dy_dtype, a->x_dtype, a->dx_dtype, a->ws ? a->ws_floats : 0);
+    LNX_CHECK(L.cols != LNX_LN_COLS_ATOMICS || !deterministic(),
+              "lnx_layernorm_bwd: deterministic mode needs the partial-sum workspace ws (at least 2 C floats) for dw / db: without it they are summed by float atomics");
     hipStream_t st = (hipStream_t)stream;
     const bool defer = a->defer != 0;
     switch (a->dy_dtype * 4 + a->x_dtype * 2 + a->dx_dtype) {

@@ -145,6 +145,8 @@ struct lnx_plan {
     bool ln_defer = true;      // LNX_LN_DEFER=0: every LayerNorm backward reduces its column partials at once (A/B)
     int64_t o_tnws = 0;  // split-K workspace of the weight-gradient GEMMs (main stream only)
     int64_t o_lsws = 0, lsws_floats = 0;  // S | T scratch of the z-free LayerScale gradient
+    bool det = false;                     // created in deterministic mode (lnx_set_deterministic): scratch and kernel choice fit its fixed-order routes
+    int64_t o_detws = 0, detws_floats = 0;  // ... the partial sums of the depthwise weight gradient / the LayerScale gradient (launch stream, one at a time)
     int64_t o_gcos /* freqs-gradient partials of lnx_attn_bwd */, o_delta, o_dt1, o_tail[6], o_mtmp[4], o_dlT;
     // fp8 plans, forward scratch: MXFP8 copy (+ block scales) of the LayerNorm output feeding qkv / fc1, and of the MLP hidden
     // feeding fc2 (two buffers: fc1 reads the first while its epilogue writes the second)
@@ -395,6 +397,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     p->esz = c.dtype == LNX_BF16 ? 2 : 4;
     p->meta_chain = !env_off("LNX_META_CHAIN");
     p->ln_defer = !env_off("LNX_LN_DEFER");
+    p->det = lnx_get_deterministic() != 0;
     p->freq_defer = !env_off("LNX_FREQ_DEFER");
     for (int s = 0; s < 2; ++s) p->chain_ok[s] = p->meta_chain && lnx_meta_heads_supported(c.dims[2 + s]) != 0;
     p->E = 1 + c.n_meta;
@@ -492,6 +495,11 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     if (const char* e = getenv("LNX_FUSED_MLP_MAXC")) fuse_maxc = atoi(e);
     p->lnws_floats = (int64_t)2048 * 2 * (D[3] > D[0] ? D[3] : D[0]);
     p->lnws_side_floats = (int64_t)256 * 2 * D[3];
+    if (p->det)  // the fused conv-MLP backward then leaves a row per WAVE: room for the largest conv stage, so it keeps the LayerNorm inside
+        for (int s = 0; s < 2; ++s) {
+            const int64_t need = lnx_convmlp_bwd_ws_floats((int)D[s], (int)((int64_t)B * p->HW[s]));
+            if (need > p->lnws_floats) p->lnws_floats = need;
+        }
     for (int s = 0; s < 2; ++s) {
         const int64_t M = (int64_t)B * p->HW[s], C = D[s];
         if (M * C > maxMC) maxMC = M * C;
@@ -646,6 +654,15 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
             p->o_lnws_defer = cv.take(need * 4 * LN_DEFER_SLOTS);
         }
         p->o_lnws_side = cv.take(p->lnws_side_floats * 4);
+        if (p->det) {
+            for (int s = 0; s < 2; ++s) {
+                const int M = B * p->HW[s];
+                const int64_t dw = lnx_dwconv7_wgrad_ws_floats(B, p->H[s], p->W[s], D[s], LNX_F32, c.dtype), ls = lnx_layerscale_bwd_ws_floats(M, D[s]);
+                if (dw > p->detws_floats) p->detws_floats = dw;
+                if (ls > p->detws_floats) p->detws_floats = ls;
+            }
+            p->o_detws = cv.take(p->detws_floats * 4);
+        }
         p->o_tnws = cv.take((int64_t)LNX_TN_WS_FLOATS * 4 * TN_WS_SLOTS);
         {   // pwconv2 weight / bias gradient of dY = rs g, before the LayerScale factor (lnx_layerscale_apply_wgrad): [C, 4C] + [C] fp32
             const int64_t cmax = D[0] > D[1] ? D[0] : D[1];
@@ -1619,7 +1636,7 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     }
     {
         Timed t(c, 3, 14.0 * B * (double)N * N * C);
-        RUN(lnx_attn_bwd(&ab, c.st));
+        RUN(lnx_attn_bwd_sized(&ab, p->gcos_floats, c.st));
     }
     RUN(wfork(3));
     RUN(wgrad(cw, M, 3 * C, C, sA, 3 * C, c.at<void>(k.n1), C, k.qkv.param, k.qkvb, C, 0, 3));
@@ -1694,7 +1711,8 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
             joined = true;
         }
     } else {
-        RUN(lnx_layerscale_bwd(g, c.at<void>(k.z), c.dt, p->P[k.gamma], p->drop_ptr(p->drop_conv[s][i]), H * W, sC, p->G[k.gamma], M, C, c.st));
+        RUN(lnx_layerscale_bwd_ws(g, c.at<void>(k.z), c.dt, p->P[k.gamma], p->drop_ptr(p->drop_conv[s][i]), H * W, sC, p->G[k.gamma], M, C,
+                                  p->det ? c.at<float>(p->o_detws) : nullptr, p->detws_floats, c.st));
         RUN(wgrad(c, M, C, 4 * C, sC, C, c.at<void>(k.act), 4 * C, k.w2.param, k.b2, 4 * C));
         lnx_gemm_args a = gemm_base(c, M, 4 * C, C, sC, C, c.wtptr(k.w2), k.w2.ld_t, sA, 4 * C, false);
         a.act = LNX_ACT_MUL_AUX; a.aux = c.at<void>(k.hpre); a.ldaux = 4 * C;  // what the forward left in hpre
@@ -1713,6 +1731,9 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
     w.B = B; w.H = H; w.W = W; w.C = C;
     w.x = c.at<float>(k.xin); w.x_dtype = LNX_F32; w.dy = dy; w.dy_dtype = c.dt;
     w.dw = p->G[k.dww]; w.db = p->G[k.dwb];
+    if (p->det) {
+        w.ws = c.at<float>(p->o_detws); w.ws_floats = p->detws_floats;
+    }
     {
         Timed t(c, 5, (double)M * C * (4 + p->esz));
         RUN(lnx_dwconv7_wgrad(&w, c.st));
@@ -1851,6 +1872,9 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
     if (p && p->c.inference) FAIL("lnx_plan_backward: this plan was created for inference (cfg.inference = 1)");
     if (!p || !p->bound || !p->has_grads) FAIL("lnx_plan_backward: plan is not bound with gradient buffers");
     if (!p->fwd_done) FAIL("lnx_plan_backward: no forward to differentiate");
+    if (lnx_get_deterministic() && !p->det)
+        FAIL("lnx_plan_backward: deterministic mode is on but this plan was created with it off (its scratch and kernel choice do not fit the fixed-order routes): "
+             "create the plan after lnx_set_deterministic(1)");
     if (segment < -1 || segment > 3) FAIL("lnx_plan_backward: bad segment %d", segment);
     // Postponed split-K second stages (lnx_wgrad_args.defer) are raw workspace / gradient pointers held per host thread: whatever an earlier
     // call that failed midway left behind is dropped here, and whatever THIS call leaves behind on an error path is dropped when it

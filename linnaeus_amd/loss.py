@@ -29,7 +29,7 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_scale, scale, loss, loss_sum, dlogits, form=0, soft_target=None):
+def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_scale, scale, loss, loss_sum, dlogits, form=0, soft_target=None, sum_ws=None):
     if not logits.is_cuda:
         raise L.LnxError("linnaeus_amd.loss has no CPU path: logits must be on the GPU")
     a.B, a.C = logits.shape
@@ -42,6 +42,7 @@ def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_sc
     a.loss, a.loss_sum = _ptr(loss), _ptr(loss_sum)
     a.dlogits, a.ldd = _ptr(dlogits), (dlogits.stride(0) if dlogits is not None else 0)
     a.form, a.soft_target, a.ldt = int(form), _ptr(soft_target), (soft_target.stride(0) if soft_target is not None else 0)
+    a.sum_ws = _ptr(sum_ws)
 
 
 def _launch(*args):
@@ -367,10 +368,12 @@ class _MultiCE(torch.autograd.Function):
         sizes = [x.numel() if lg.requires_grad else 0 for x, lg in zip(xs, logits)]
         flat = torch.empty(sum(sizes), device=total.device, dtype=torch.float32) if any(sizes) else None
         grads, sets, off = [], [], 0
+        det = L.is_deterministic()  # the rows' terms then reach `total` through a per-row buffer, folded in row order
         for w, t, x, n in zip(weights, targets, xs, sizes):
             d = flat[off:off + n].view_as(x) if n else None
             off += n
-            sets.append((x, t, None, smoothing, None, None, None, w / x.shape[0], None, total, d))
+            rows = torch.empty(x.shape[0], device=total.device, dtype=torch.float32) if det else None
+            sets.append((x, t, None, smoothing, None, None, None, w / x.shape[0], None, total, d, 0, None, rows))
             grads.append(d)
         _launch_multi(sets)
         ctx.flat, ctx.sizes = flat, sizes

@@ -340,6 +340,14 @@ class mFormerV1(nn.Module):
         self._dtype_code = L.BF16 if self._fp8 else _DTYPES[name]
         self.release_plans()
 
+    def set_deterministic(self, on: bool) -> None:
+        """Switch the library's deterministic mode (process-wide: `linnaeus_amd.set_deterministic`, include/lnx.h) and drop this
+        model's cached plans, as a change of compute dtype does: a plan sizes its scratch and picks its kernels for the mode it was
+        created in, and the library refuses to run one under the other setting.  Other models of the process rebuild theirs through
+        their own `set_deterministic` / `release_plans`."""
+        L.set_deterministic(bool(on))
+        self.release_plans()
+
     def set_wgrad_stream(self, on: bool) -> None:
         """Backward scheduling of this model's native plans, present and future (include/lnx.h lnx_plan_set_wgrad_stream): True (the
         default) runs the weight-gradient products on a second HIP stream beside the data-gradient chain, False keeps everything on the

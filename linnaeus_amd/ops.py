@@ -162,7 +162,9 @@ def gemm_nt_mxfp8(A8, a_scales, W8, w_scales, out, *, bias=None, act=L.ACT_NONE,
     return out
 
 
-def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, a_patch=None, k_perm_c=0, k_store=0, splits=0, dtype=None):
+def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, a_patch=None, k_perm_c=0, k_store=0, splits=0, dtype=None, ws=None):
+    """ws (optional fp32 scratch): split-K partial tiles meet there and a second stage sums them in a fixed order; without it (or where
+    it is too small) the splits meet in float atomics -- in deterministic mode the contraction is then split less, down to not at all."""
     a = L.WgradArgs()
     a.dtype = dtype if dtype is not None else code_of(dY)
     a.M = M if M is not None else dY.shape[0]
@@ -174,6 +176,8 @@ def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, 
         a.a_mode, a.Hin, a.Win, a.Cin = L.ADDR_PATCH2, *a_patch
     a.dW, a.lddw = _p(dW), (lddw if lddw is not None else dW.stride(0))
     a.k_perm_c, a.db, a.splits, a.k_store = k_perm_c, _p(db), splits, k_store
+    if ws is not None:
+        a.ws, a.ws_floats = _p(ws), ws.numel()
     L.check(L.lib().lnx_gemm_tn(C.byref(a), _stream()), "lnx_gemm_tn")
     return dW
 
@@ -262,7 +266,14 @@ def dwconv7_wgrad(x, dy, dw, db):
     a = L.DwconvWgradArgs()
     a.B, a.H, a.W, a.C = B, H, W, Cc
     a.x, a.x_dtype, a.dy, a.dy_dtype, a.dw, a.db = _p(x), code_of(x), _p(dy), code_of(dy), _p(dw), _p(db)
+    if L.is_deterministic():  # the walkers' partial sums, folded in walker order (the launcher says how many floats)
+        ws = torch.empty(max(dwconv7_wgrad_ws_floats(B, H, W, Cc, a.x_dtype, a.dy_dtype), 1), device=x.device, dtype=torch.float32)
+        a.ws, a.ws_floats = _p(ws), ws.numel()
     L.check(L.lib().lnx_dwconv7_wgrad(C.byref(a), _stream()), "lnx_dwconv7_wgrad")
+
+
+def dwconv7_wgrad_ws_floats(B, H, W, Cc, x_dtype, dy_dtype) -> int:
+    return int(L.lib().lnx_dwconv7_wgrad_ws_floats(B, H, W, Cc, x_dtype, dy_dtype))
 
 
 def rope_cos_table(freqs, H, W, out=None, dsin=None):
@@ -343,7 +354,7 @@ def attn_bwd(qkv, cos_tab, o, lse, d_o, dqkv, delta, B, N, E, heads, *, dsin=Non
     if drop_mask is not None:
         a.drop_mask, a.drop_inv_keep = _p(drop_mask), 1.0 / (1.0 - drop_rate)
     a.defer_freqs = int(bool(defer_freqs))
-    L.check(L.lib().lnx_attn_bwd(C.byref(a), _stream()), "lnx_attn_bwd")
+    L.check(L.lib().lnx_attn_bwd_sized(C.byref(a), C.c_int64(ws.numel()), _stream()), "lnx_attn_bwd")
     return ws
 
 
@@ -373,6 +384,11 @@ def scale_cast(inp, out, M, Cc, *, ldin=None, in_map=None, rowscale=None, rows_p
 
 
 def layerscale_bwd(g, z, gamma, rowscale, rows_per_sample, dz, dgamma, M, Cc):
+    if L.is_deterministic():  # the workgroups' dgamma partial sums, folded in workgroup order
+        ws = torch.empty(max(int(L.lib().lnx_layerscale_bwd_ws_floats(M, Cc)), 1), device=g.device, dtype=torch.float32)
+        L.check(L.lib().lnx_layerscale_bwd_ws(_p(g), _p(z), code_of(z), _p(gamma), _p(rowscale), rows_per_sample, _p(dz), _p(dgamma), M, Cc, _p(ws),
+                                              C.c_int64(ws.numel()), _stream()), "lnx_layerscale_bwd_ws")
+        return
     L.check(L.lib().lnx_layerscale_bwd(_p(g), _p(z), code_of(z), _p(gamma), _p(rowscale), rows_per_sample, _p(dz), _p(dgamma), M, Cc, _stream()),
             "lnx_layerscale_bwd")
 
