@@ -103,6 +103,17 @@ typedef struct lnx_gemm_args {
     int64_t ldc8;          /* ldc8 bytes per row, block scales in c8_scales ([N/128][M][4]); needs N % 128 == 0 and the */
     void* c8_scales;       /* bias + GELU + pre-activation form or the GELU' form (the fc1 -> fc2 hand-over of the model's fp8 mode
                               and its mirror image in the backward) */
+    /* Compact rows (DropPath compaction lists, below), lnx_gemm_nt only (the fp8 entry points refuse them):
+     * m_dev  optional device int: the product covers the rows m < min(M, *m_dev), read once at kernel entry.  The launch is sized
+     *        from M on the host; rows >= the effective count of A / aux are never read into a result and rows >= it of C / c2 are
+     *        never written (they may hold anything, NaN included; all M rows must be allocated).  NULL: all M rows.
+     * perm   optional sample permutation [M / rows_per_sample] (device ints) for the residual forms: compact row m stands for sample
+     *        b = perm[m / rows_per_sample], so rowscale is read at b and res / C are addressed at row b * rows_per_sample + m %
+     *        rows_per_sample; A, aux and c2 stay compact (row m).  Needs res and rowscale (refused without), plain C addressing and an
+     *        identity c_map.  Rows of C that
+     *        belong to samples behind the effective count are not touched.  NULL: identity. */
+    const int* m_dev;
+    const int* perm;
 } lnx_gemm_args;
 
 int lnx_gemm_nt(const lnx_gemm_args* args, void* stream);
@@ -187,6 +198,11 @@ typedef struct lnx_wgrad_args {
                        is postponed to lnx_gemm_tn_flush(), which sums the partial tiles of ALL postponed products of this host thread
                        in one launch (up to 8; a ninth, or one on another stream, flushes first).  Every pending product needs its
                        own ws, untouched until the flush; dW / db are final only after it. */
+    const int* m_dev; /* optional device int (DropPath compaction lists, below: a list's m_eff): the contraction runs over the rows
+                       m < min(M, *m_dev) only.  The launch (splits, workspace) is sized from M on the host; every split takes its
+                       contraction range from the effective count inside the kernel, a split left without rows adds nothing (its
+                       workspace tiles are zeros).  Rows >= the effective count of dY and A are never multiplied in: they may hold
+                       anything, NaN included -- they must exist, though (M rows are allocated).  NULL: all M rows. */
 } lnx_wgrad_args;
 #define LNX_TN_WS_FLOATS (256 * (256 * 128 + 256))
 
@@ -228,6 +244,13 @@ typedef struct lnx_ln_args {
                            an identity y_map and C % 128 == 0: the producer side of the model's fp8 mode. */
     int64_t ldy8;
     void* y8_scales;
+    /* Compact rows (DropPath compaction lists, below): a sample gather on the x side.
+     * perm    optional [M / rows_per_sample]: output row m (y, mean, rstd: compact) is the LayerNorm of x row
+     *         perm[m / rows_per_sample] * rows_per_sample + m % rows_per_sample.  Needs an identity x_map, no add, no y8.
+     * m_dev   optional device int: rows m >= min(M, *m_dev) are not processed (nothing of theirs is read or written). */
+    const int* perm;
+    const int* m_dev;
+    int rows_per_sample;
 } lnx_ln_args;
 int lnx_layernorm_fwd(const lnx_ln_args* args, void* stream);
 
@@ -275,6 +298,18 @@ typedef struct lnx_ln_bwd_args {
      * lnx_layernorm_bwd_flush(), which sums the partials of ALL postponed calls of this host thread in one launch (up to 16; a 17th, or
      * one on another stream, flushes first).  Every pending call needs its own ws, untouched until the flush. */
     int defer;
+    /* Compact rows (DropPath compaction lists, below); rows per sample = dx2_rows_per_sample, identity row maps.
+     * perm / m_dev   as lnx_ln_args: dy, mean and rstd are compact (row m < min(M, *m_dev)), x, gin and dx are the sample's own rows
+     *                (the gather on the x side, the scatter on the dx side).  dx rows of the samples behind the effective M are left
+     *                untouched, and nothing of theirs enters dw / db.
+     * dx2_inv / dx2_nkeep   the second output is compact under ANOTHER list (it is the other branch's dY): sample b's rows go to
+     *                position dx2_inv[b] of dx2 and are written only if dx2_inv[b] < *dx2_nkeep; dx2_rowscale is read at b.  Without
+     *                them dx2 has the samples' own rows.  With m_dev and dx2, the rows of the samples behind the effective M still get
+     *                their dx2 = dx2_rowscale * gin (they take no other part), so gin is required. */
+    const int* perm;
+    const int* m_dev;
+    const int* dx2_inv;
+    const int* dx2_nkeep;
 } lnx_ln_bwd_args;
 int lnx_layernorm_bwd(const lnx_ln_bwd_args* args, void* stream);
 /* sums the postponed column partials into their dw / db (no-op when nothing is pending; `stream` = the postponed calls' stream or NULL) */
@@ -454,6 +489,12 @@ int lnx_attn_bwd(const lnx_attn_bwd_args* args, void* stream);
  * workgroups' partials, so the call needs to know what it was given -- less than lnx_attn_bwd_ws_floats_hd reports with the mode on
  * refuses by name, and so does lnx_attn_bwd (no size) there.  Outside the mode the size is not read. */
 int lnx_attn_bwd_sized(const lnx_attn_bwd_args* args, int64_t freq_ws_floats, void* stream);
+/* Compact rows (DropPath compaction lists: a list's nkeep, a device int): lnx_attn_fwd / lnx_attn_bwd_sized on buffers that are compact by
+ * sample -- qkv / o / lse, d_o / dqkv / delta.  The problems of the samples b >= *nkeep are skipped before anything of theirs is read
+ * or written (their slots may hold anything), their slots of freq_ws are neither written nor folded into dfreqs (immediate and
+ * postponed fold alike: nkeep must stay valid until the flush).  Not together with drop_mask.  nkeep == NULL: the plain calls. */
+int lnx_attn_fwd_compact(const lnx_attn_args* args, const int* nkeep, void* stream);
+int lnx_attn_bwd_compact(const lnx_attn_bwd_args* args, const int* nkeep, int64_t freq_ws_floats, void* stream);
 
 /* Which kernel family lnx_attn_fwd / lnx_attn_bwd take (host-side bookkeeping, no device work; the forward and the backward of one
  * call take the same one): the boundary tests use it to prove that a sequence length ran on the kernels it is meant to cover.
@@ -509,6 +550,41 @@ int lnx_stem_fwd(const lnx_stem_args* args, void* stream);
 /* out[m, :] = rowscale[m / rows_per_sample] * in[map(m), :]   (fp32 in, T or fp32 out) */
 int lnx_scale_cast(const float* in, int64_t ldin, lnx_rowmap in_map, const float* rowscale, int rows_per_sample, void* out,
                    int out_dtype, int64_t ldout, int M, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * DropPath compaction lists.  A DropPath multiplier (drop_path.py:29-33) is 1 / keep or exactly 0 per sample; for a sample with 0 the
+ * branch's forward result is its input and its dY rows are 0, so none of the branch's kernels has anything to compute for it.  The
+ * multipliers are drawn on the device, so the lists are built there too (no host synchronisation), and every consumer reads the
+ * kept count from device memory.
+ *
+ * lnx_drop_partition: scales is [n_calls][B]; for every call c (with call_mask[c] != 0 when the HOST array call_mask is given) one
+ * launch writes that call's list, LNX_DROP_LIST_INTS(B) ints at lists + c * LNX_DROP_LIST_INTS(B):
+ *   [0]            nkeep  = number of samples whose multiplier is not exactly 0.0 (any other value, NaN included, counts as kept)
+ *   [1]            m_eff  = nkeep * rows_per_sample[c]   (rows_per_sample: HOST array or NULL = 1): what `m_dev` arguments point at
+ *   [2, 2 + B)     perm   : stable partition of 0 .. B-1 -- the kept samples in ascending order, then the dropped ones in ascending order
+ *   [2 + B, 2+2B)  inv    : inv[perm[j]] = j, a sample's position under this list
+ * COMPACT ROWS of a call: compact row m' stands for sample perm[m' / rows_per_sample], token m' % rows_per_sample; rows m' < m_eff are
+ * the kept samples' rows, rows >= m_eff are nobody's: a kernel with an `m_dev` argument neither reads them into a result nor writes them
+ * (they may hold anything, NaN included).
+ * -----------------------------------------------------------------------------------*/
+#define LNX_DROP_LIST_INTS(B) (2 * (B) + 2)
+#define LNX_DROP_PARTITION_MAX 64 /* calls per launch (more calls: more launches) */
+int lnx_drop_partition(const float* scales, int n_calls, int B, const unsigned char* call_mask, const int* rows_per_sample, int* lists, void* stream);
+/* lnx_scale_cast with compact output rows: out[m', :] = rowscale[b] * in[b * rows_per_sample + m' % rows_per_sample, :] with
+ * b = perm[m' / rows_per_sample], for m' < min(M, *m_dev); M = B * rows_per_sample.  rowscale may be NULL (1). */
+int lnx_scale_cast_compact(const float* in, int64_t ldin, const float* rowscale, int rows_per_sample, const int* perm, const int* m_dev, void* out,
+                           int out_dtype, int64_t ldout, int M, int C, void* stream);
+
+/* dst rows of the samples a list drops = src rows, bit for bit (the residual forms with perm leave them untouched): rows
+ * perm[j] * rows_per_sample + t for j >= *nkeep, C fp32 columns, leading dimension ld for both. */
+int lnx_copy_dropped_rows(const float* src, float* dst, int64_t ld, const int* perm, const int* nkeep, int B, int rows_per_sample, int C, void* stream);
+
+/* A/B switch of the DropPath compaction inside lnx_plan_forward / lnx_plan_backward, process-wide: on = 0 / 1, or -1 = back to the
+ * environment (LNX_DROP_COMPACT, on unless it is 0).  Returns the previous setting (-1, 0 or 1).  Read by every lnx_plan_forward; a
+ * backward follows its forward's choice.  lnx_drop_compact_branches(): RoPE-block branches that ran a forward on compact rows since
+ * the library was loaded (the tests' proof of which path a plan took, like lnx_last_nt_kernel). */
+int lnx_set_drop_compact(int on);
+int64_t lnx_drop_compact_branches(void);
 
 /* LayerScale+DropPath backward of a ConvNeXt block branch (blocks/convnext.py:82-86):
  * dz = rowscale * gamma * g  (T),  dgamma[c] += sum_m rowscale * g * z */

@@ -14,6 +14,11 @@ LIB_PATH = os.environ.get("LNX_LIB_PATH") or os.path.join(_HERE, "liblnx_hip.so"
 F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_BWD, ACT_RELU_BWD, ACT_GELU_D, ACT_MUL_AUX = 0, 1, 2, 3, 4, 5, 6
 TN_WS_FLOATS = 256 * (256 * 128 + 256)  # == LNX_TN_WS_FLOATS
+DROP_PARTITION_MAX = 64  # == LNX_DROP_PARTITION_MAX
+
+
+def drop_list_ints(B: int) -> int:  # == LNX_DROP_LIST_INTS(B): nkeep, m_eff, perm[B], inv[B]
+    return 2 * B + 2
 ADDR_PLAIN, ADDR_PATCH2 = 0, 1
 
 
@@ -41,6 +46,7 @@ class GemmArgs(C.Structure):
         ("gamma", C.c_void_p), ("rowscale", C.c_void_p), ("rows_per_sample", C.c_int),
         ("res", C.c_void_p), ("ldres", C.c_int64),
         ("c8", C.c_void_p), ("ldc8", C.c_int64), ("c8_scales", C.c_void_p),
+        ("m_dev", C.c_void_p), ("perm", C.c_void_p),
     ]
 
 
@@ -57,6 +63,7 @@ class WgradArgs(C.Structure):
         ("k_store", C.c_int),
         ("ws", C.c_void_p), ("ws_floats", C.c_int64),
         ("defer", C.c_int),
+        ("m_dev", C.c_void_p),
     ]
 
 
@@ -258,6 +265,12 @@ def lib() -> C.CDLL:
         if hasattr(_lib, "lnx_meta_mask"):
             _lib.lnx_meta_mask.argtypes = [C.POINTER(MetaMaskArgs), C.c_void_p]
             _lib.lnx_meta_mask.restype = C.c_int
+        if hasattr(_lib, "lnx_drop_partition"):
+            _lib.lnx_drop_partition.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+            _lib.lnx_copy_dropped_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+            _lib.lnx_drop_compact_branches.restype = C.c_int64
+            _lib.lnx_scale_cast_compact.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                                    C.c_void_p]
         if hasattr(_lib, "lnx_layernorm_fwd_query"):
             _lib.lnx_layernorm_fwd_query.argtypes = [C.POINTER(LnArgs), C.POINTER(LnLaunch)]
             _lib.lnx_layernorm_bwd_query.argtypes = [C.POINTER(LnBwdArgs), C.POINTER(LnLaunch)]
@@ -304,8 +317,8 @@ EXPORTS = [
     "lnx_gemm_nt", "lnx_last_nt_kernel", "lnx_nt_kernel_launches", "lnx_nt_dispatch", "lnx_gemm_tn", "lnx_gemm_tn_flush", "lnx_gemm_tn_discard", "lnx_amax", "lnx_quantize_fp8", "lnx_gemm_nt_fp8", "lnx_quantize_mxfp8", "lnx_gemm_nt_mxfp8", "lnx_dropout_mul", "lnx_dropout_residual", "lnx_plan_dropout_bytes", "lnx_plan_set_dropout", "lnx_plan_attn_dropout_bytes", "lnx_plan_set_attn_dropout",
     "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard", "lnx_layernorm_fwd_query", "lnx_layernorm_bwd_query",
     "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_ws_floats",
-    "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
-    "lnx_im2col_stem", "lnx_scale_cast", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
+    "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_fwd_compact", "lnx_attn_bwd_compact", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
+    "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",
@@ -354,6 +367,7 @@ class LnArgs(C.Structure):
         ("add", C.c_void_p), ("ldadd", C.c_int64),
         ("mean", C.c_void_p), ("rstd", C.c_void_p),
         ("y8", C.c_void_p), ("ldy8", C.c_int64), ("y8_scales", C.c_void_p),
+        ("perm", C.c_void_p), ("m_dev", C.c_void_p), ("rows_per_sample", C.c_int),
     ]
 
 
@@ -370,6 +384,7 @@ class LnBwdArgs(C.Structure):
         ("dx2", C.c_void_p), ("dx2_dtype", C.c_int), ("lddx2", C.c_int64), ("dx2_rowscale", C.c_void_p), ("dx2_rows_per_sample", C.c_int),
         ("dx2_8", C.c_void_p), ("dx2_8_scales", C.c_void_p), ("lddx2_8", C.c_int64),
         ("defer", C.c_int),
+        ("perm", C.c_void_p), ("m_dev", C.c_void_p), ("dx2_inv", C.c_void_p), ("dx2_nkeep", C.c_void_p),
     ]
 
 

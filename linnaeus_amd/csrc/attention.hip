@@ -433,6 +433,7 @@ struct AttnP {
     const float* sin_tab = nullptr;        // ROT kernels: sin(theta), laid out like cos_tab
     int W = 1;                             // ROT backward: width of the token grid (t_x = n % W, t_y = n / W of image token n)
     float* fwave = nullptr;                // deterministic mode: [workgroups][FREQ_WAVES][HD] per-wave sums of the freqs gradient; else NULL
+    const int* nkeep = nullptr;            // compact rows: device int, the problems of samples b >= *nkeep are skipped
 };
 
 // this wave's slot of p.fwave, zeroed by the lanes that own its entries (freq_accum); NULL outside the deterministic mode
@@ -622,6 +623,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const AttnP p) {
     const int qt = blockIdx.x % p.qtiles;
     const int bh = blockIdx.x / p.qtiles;
     const int head = bh % p.heads, b = bh / p.heads;
+    if (p.nkeep && b >= *p.nkeep) return;  // compact rows: samples at or beyond the kept count are nobody's (before any staging)
     const int C = p.heads * HD;
     const int64_t ld = 3 * C;
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
@@ -729,6 +731,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const AttnP p) {
     const int qt = blockIdx.x % p.qtiles;
     const int bh = blockIdx.x / p.qtiles;
     const int head = bh % p.heads, b = bh / p.heads;
+    if (p.nkeep && b >= *p.nkeep) return;  // compact rows: samples at or beyond the kept count are nobody's (before any staging)
     const int C = p.heads * HD;
     const int64_t ld = 3 * C;
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
@@ -840,6 +843,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 && HD == 64 ? 4 : 1) void attn_bwd
     const int ktile = blockIdx.x % p.qtiles;  // same tiling for keys
     const int bh = blockIdx.x / p.qtiles;
     const int head = bh % p.heads, b = bh / p.heads;
+    if (p.nkeep && b >= *p.nkeep) return;  // compact rows: samples at or beyond the kept count are nobody's (before any staging)
     const int C = p.heads * HD;
     const int64_t ld = 3 * C;
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
@@ -987,6 +991,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
     const int head = blockIdx.x % p.heads, b = blockIdx.x / p.heads;
+    if (p.nkeep && b >= *p.nkeep) return;  // compact rows: samples at or beyond the kept count are nobody's (before any staging)
     const int C = p.heads * HD;
     const int64_t ld = 3 * C;
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
@@ -1228,6 +1233,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
     const int head = blockIdx.x % p.heads, b = blockIdx.x / p.heads;
+    if (p.nkeep && b >= *p.nkeep) return;  // compact rows: samples at or beyond the kept count are nobody's (before any staging)
     const int C = p.heads * HD;
     const int64_t ld = 3 * C;
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
@@ -1307,6 +1313,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
     const int head = blockIdx.x % p.heads, b = blockIdx.x / p.heads;
+    if (p.nkeep && b >= *p.nkeep) return;  // compact rows: samples at or beyond the kept count are nobody's (before any staging)
     const int C = p.heads * HD;
     const int64_t ld = 3 * C;
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
@@ -1409,6 +1416,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
     const int head = blockIdx.x % p.heads, b = blockIdx.x / p.heads;
+    if (p.nkeep && b >= *p.nkeep) return;  // compact rows: samples at or beyond the kept count are nobody's (before any staging)
     const int C = p.heads * HD;
     const int64_t ld = 3 * C;
     const T* qb = reinterpret_cast<const T*>(p.qkv) + (int64_t)b * p.N * ld + head * HD;
@@ -1562,14 +1570,15 @@ __global__ __launch_bounds__(256) void rope_cos_batch_kernel(const RopeTabBatch 
 // one 1024-thread workgroup per head: SL = 1024 / HD slices of the partial list x HD entries (16 x 64 at head_dim 64), four loads in
 // flight per thread, LDS tree.  The one body of both fold kernels below: a call folded alone and in a batch gives the same bits.
 template <int HD>
-__device__ __forceinline__ void freqs_fold(const float* __restrict__ fpart, float* __restrict__ dfreqs, int B, int heads, int per_bh, int h) {
+__device__ __forceinline__ void freqs_fold(const float* __restrict__ fpart, float* __restrict__ dfreqs, int B, int heads, int per_bh, int h, const int* nkeep) {
     constexpr int SL = 1024 / HD, HH = HD / 2;
     __shared__ float red[SL][HD];
     const int t = threadIdx.x & (HD - 1), sl = threadIdx.x / HD;  // t = a * HD / 2 + j
+    if (nkeep) B = min(B, max(*nkeep, 0));  // compact rows: the skipped samples' workgroups wrote no partial (their slots hold anything)
     const int n = B * per_bh;  // partials of this head: (b, k) -> ((b * heads + h) * per_bh + k)
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     auto at = [&](int i) -> float {
-        const int ii = min(i, n - 1);
+        const int ii = max(min(i, n - 1), 0);
         const int b = ii / per_bh, k = ii - b * per_bh;
         const float v = fpart[(((int64_t)b * heads + h) * per_bh + k) * HD + t];
         return i < n ? v : 0.f;
@@ -1590,8 +1599,9 @@ __device__ __forceinline__ void freqs_fold(const float* __restrict__ fpart, floa
     }
 }
 template <int HD = 64>
-__global__ __launch_bounds__(1024) void rope_freqs_reduce_kernel(const float* __restrict__ fpart, int B, int heads, int per_bh, float* __restrict__ dfreqs) {
-    freqs_fold<HD>(fpart, dfreqs, B, heads, per_bh, blockIdx.x);
+__global__ __launch_bounds__(1024) void rope_freqs_reduce_kernel(const float* __restrict__ fpart, int B, int heads, int per_bh, float* __restrict__ dfreqs,
+                                                                 const int* nkeep) {
+    freqs_fold<HD>(fpart, dfreqs, B, heads, per_bh, blockIdx.x, nkeep);
 }
 
 // the same fold for several attention backward calls in ONE launch (lnx_attn_bwd_args.defer_freqs + lnx_attn_bwd_flush): blockIdx.y picks
@@ -1601,6 +1611,7 @@ struct FreqEntry {
     const float* fpart;
     float* dfreqs;
     int B, heads, per_bh, hd;
+    const int* nkeep;
 };
 struct FreqBatch {
     FreqEntry e[LNX_ATTN_DEFER_MAX];
@@ -1609,7 +1620,7 @@ template <int HD = 64>
 __global__ __launch_bounds__(1024) void rope_freqs_reduce_batch_kernel(const FreqBatch fb) {
     const FreqEntry& q = fb.e[blockIdx.y];
     if ((int)blockIdx.x >= q.heads) return;  // (uniform per workgroup: the grid's width is the largest head count of the batch)
-    freqs_fold<HD>(q.fpart, q.dfreqs, q.B, q.heads, q.per_bh, blockIdx.x);
+    freqs_fold<HD>(q.fpart, q.dfreqs, q.B, q.heads, q.per_bh, blockIdx.x, q.nkeep);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1793,13 +1804,15 @@ int rope_table_hd(const float* freqs, int heads, int hd, int H, int W, float* co
 // call: nothing has been launched or recorded before it), the fields of AttnP that both directions fill, and the choice of the kernel
 // family, which lnx_last_attn_kernel reports from here on.  Args = lnx_attn_args or lnx_attn_bwd_args.
 template <bool ROT, class Args>
-int attn_setup(const Args* a, int hd, const char* who, AttnP& p, int& family) {
+int attn_setup(const Args* a, const int* nkeep, int hd, const char* who, AttnP& p, int& family) {
     if (a->drop_mask) {  // attention-probability dropout: the 64-row tiled kernels with the DROP code
         LNX_CHECK(a->drop_inv_keep >= 1.0f && (((uintptr_t)a->drop_mask) & 3) == 0, "%s: drop_inv_keep >= 1 and a 4-byte aligned mask", who);
     }
     p.qkv = a->qkv; p.cos_tab = cos_or_stub(a->cos_tab, a->qkv); p.o = const_cast<void*>(static_cast<const void*>(a->o)); p.lse = const_cast<float*>(a->lse);
     if (ROT) p.sin_tab = cos_or_stub(a->sin_tab, a->qkv);
     p.B = a->B; p.N = a->N; p.E = a->E; p.heads = a->heads;
+    p.nkeep = nkeep;
+    LNX_CHECK(!(nkeep && a->drop_mask), "%s: nkeep (compact rows) and the attention-probability mask (laid out by full rows) do not go together", who);
     p.qtiles = cdiv(a->N, BT);
     if (a->drop_mask) {
         p.amask = a->drop_mask; p.a_inv_keep = a->drop_inv_keep; p.Np = p.qtiles * BT;
@@ -1864,14 +1877,14 @@ extern "C" int64_t lnx_attn_bwd_ws_floats(int B, int N, int heads) { return lnx_
 
 // ROT = the call's rope_mode is LNX_ROPE_ROTATE: the same families and launch shapes, the rotating instantiations
 template <bool ROT>
-int attn_fwd_launch(const lnx_attn_args* a, void* stream) {
+int attn_fwd_launch(const lnx_attn_args* a, const int* nkeep, void* stream) {
     const int hd = a->head_dim ? a->head_dim : 64;
     if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, hd, "lnx_attn_fwd")) return 1;
     LNX_CHECK(a->E == a->N || a->cos_tab, "lnx_attn_fwd: cos table missing");
     LNX_CHECK(!ROT || a->E == a->N || a->sin_tab, "lnx_attn_fwd: sin table missing (rope_mode = LNX_ROPE_ROTATE)");
     AttnP p{};
     int family = LNX_ATTN_KERNEL_NONE;
-    if (attn_setup<ROT>(a, hd, "lnx_attn_fwd", p, family)) return 1;
+    if (attn_setup<ROT>(a, nkeep, hd, "lnx_attn_fwd", p, family)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int rc = is_resident(family) ? attn_fwd_res<ROT>(p, family, st) : with_type_hd(a->dtype, hd, [&](auto tc, auto hdc) {
         return attn_fwd_tiled<typename decltype(tc)::type, decltype(hdc)::value, ROT>(p, family, st);
@@ -1882,7 +1895,7 @@ int attn_fwd_launch(const lnx_attn_args* a, void* stream) {
 }
 
 template <bool ROT>
-int attn_bwd_launch(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* stream) {
+int attn_bwd_launch(const lnx_attn_bwd_args* a, const int* nkeep, int64_t freq_ws_floats, void* stream) {
     const int hd = a->head_dim ? a->head_dim : 64;
     if (check_attn(a->dtype, a->B, a->N, a->E, a->heads, hd, "lnx_attn_bwd")) return 1;
     if (ROT) {
@@ -1898,7 +1911,7 @@ int attn_bwd_launch(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* st
     }
     AttnP p{};
     int family = LNX_ATTN_KERNEL_NONE;
-    if (attn_setup<ROT>(a, hd, "lnx_attn_bwd", p, family)) return 1;
+    if (attn_setup<ROT>(a, nkeep, hd, "lnx_attn_bwd", p, family)) return 1;
     if (ROT) p.W = a->grid_w > 0 ? a->grid_w : 1;
     if (deterministic() && a->E < a->N) {
         const int64_t partials = (int64_t)a->B * a->heads * cdiv(a->N, BT) * hd, need = partials * (1 + FREQ_WAVES);
@@ -1917,11 +1930,11 @@ int attn_bwd_launch(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* st
     // after the two kernels: the per-workgroup partials of the freqs gradient -> dfreqs (per_bh = workgroups per (sample, head))
     if (a->E < a->N) {
         if (a->defer_freqs) {
-            g_freq_pending[g_freq_n++] = FreqEntry{p.fpart, a->dfreqs, a->B, a->heads, per_bh, hd};
+            g_freq_pending[g_freq_n++] = FreqEntry{p.fpart, a->dfreqs, a->B, a->heads, per_bh, hd, nkeep};
             g_freq_stream = st;
         } else {
             with_hd(hd, [&](auto hdc) {
-                hipLaunchKernelGGL(rope_freqs_reduce_kernel<decltype(hdc)::value>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs);
+                hipLaunchKernelGGL(rope_freqs_reduce_kernel<decltype(hdc)::value>, dim3(a->heads), dim3(1024), 0, st, p.fpart, a->B, a->heads, per_bh, a->dfreqs, nkeep);
             });
         }
     }
@@ -1929,17 +1942,19 @@ int attn_bwd_launch(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* st
     return 0;
 }
 
-extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) {
+extern "C" int lnx_attn_fwd_compact(const lnx_attn_args* a, const int* nkeep, void* stream) {
     LNX_CHECK(a && a->qkv && a->o, "lnx_attn_fwd: null operand");
     LNX_CHECK(a->rope_mode == LNX_ROPE_COS || a->rope_mode == LNX_ROPE_ROTATE, "lnx_attn_fwd: bad rope_mode %d", a->rope_mode);
-    return a->rope_mode == LNX_ROPE_ROTATE ? attn_fwd_launch<true>(a, stream) : attn_fwd_launch<false>(a, stream);
+    return a->rope_mode == LNX_ROPE_ROTATE ? attn_fwd_launch<true>(a, nkeep, stream) : attn_fwd_launch<false>(a, nkeep, stream);
 }
+extern "C" int lnx_attn_fwd(const lnx_attn_args* a, void* stream) { return lnx_attn_fwd_compact(a, nullptr, stream); }
 
-extern "C" int lnx_attn_bwd_sized(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* stream) {
+extern "C" int lnx_attn_bwd_compact(const lnx_attn_bwd_args* a, const int* nkeep, int64_t freq_ws_floats, void* stream) {
     LNX_CHECK(a && a->qkv && a->o && a->lse && a->d_o && a->dqkv && a->delta, "lnx_attn_bwd: null operand");
     LNX_CHECK(a->rope_mode == LNX_ROPE_COS || a->rope_mode == LNX_ROPE_ROTATE, "lnx_attn_bwd: bad rope_mode %d", a->rope_mode);
-    return a->rope_mode == LNX_ROPE_ROTATE ? attn_bwd_launch<true>(a, freq_ws_floats, stream) : attn_bwd_launch<false>(a, freq_ws_floats, stream);
+    return a->rope_mode == LNX_ROPE_ROTATE ? attn_bwd_launch<true>(a, nkeep, freq_ws_floats, stream) : attn_bwd_launch<false>(a, nkeep, freq_ws_floats, stream);
 }
+extern "C" int lnx_attn_bwd_sized(const lnx_attn_bwd_args* a, int64_t freq_ws_floats, void* stream) { return lnx_attn_bwd_compact(a, nullptr, freq_ws_floats, stream); }
 
 extern "C" int lnx_attn_bwd(const lnx_attn_bwd_args* a, void* stream) { return lnx_attn_bwd_sized(a, 0, stream); }
 

@@ -60,6 +60,102 @@ __global__ __launch_bounds__(256) void scale_cast_kernel(const float* __restrict
     }
 }
 
+// compact form (include/lnx.h: DropPath compaction lists): out[m', c] = rowscale[b] * in[b * rps + m' % rps, c] with b = perm[m' / rps],
+// for the compact rows m' < *m_dev only
+template <typename T>
+__global__ __launch_bounds__(256) void scale_cast_compact_kernel(const float* __restrict__ in, int64_t ldin, const float* __restrict__ rowscale, int rps,
+                                                                 const int* __restrict__ perm, const int* __restrict__ m_dev, T* __restrict__ out, int64_t ldout,
+                                                                 int M, int C) {
+    const int c4n = C >> 2;
+    const int64_t total = (int64_t)min(M, max(*m_dev, 0)) * c4n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int m = (int)(i / c4n);
+        const int c = (int)(i % c4n) * 4;
+        const int q = m / rps, b = perm[q];
+        const float s = rowscale ? rowscale[b] : 1.f;
+        const float4 v = *reinterpret_cast<const float4*>(in + ((int64_t)b * rps + (m - q * rps)) * ldin + c);
+        T* o = out + (int64_t)m * ldout + c;
+        o[0] = from_f<T>(v.x * s);
+        o[1] = from_f<T>(v.y * s);
+        o[2] = from_f<T>(v.z * s);
+        o[3] = from_f<T>(v.w * s);
+    }
+}
+
+// dst rows of the samples a list drops = src rows (x + 0 . branch(x) = x, bit for bit): the tail perm[nkeep ..) of the list
+__global__ __launch_bounds__(256) void copy_dropped_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t ld, const int* __restrict__ perm,
+                                                               const int* __restrict__ nkeep, int B, int rps, int C) {
+    const int c4n = C >> 2, nk = min(max(*nkeep, 0), B);
+    const int64_t total = (int64_t)(B - nk) * rps * c4n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4n) * 4;
+        const int64_t r = i / c4n;
+        const int q = (int)(r / rps);
+        const int64_t off = ((int64_t)perm[nk + q] * rps + (r - (int64_t)q * rps)) * ld + c;
+        *reinterpret_cast<float4*>(dst + off) = *reinterpret_cast<const float4*>(src + off);
+    }
+}
+
+// DropPath compaction lists (include/lnx.h: lnx_drop_partition): workgroup j writes the list of call calls[j] -- a stable partition of
+// the sample indices by "multiplier != 0", its inverse, the kept count and the kept count in rows.
+struct DropCalls {
+    int call[LNX_DROP_PARTITION_MAX];
+    int rps[LNX_DROP_PARTITION_MAX];
+};
+__global__ __launch_bounds__(256) void drop_partition_kernel(const float* __restrict__ scales, DropCalls dc, int B, int* __restrict__ lists) {
+    __shared__ int wsum[4][2];
+    __shared__ int total_keep;
+    const int call = dc.call[blockIdx.x];
+    const float* sc = scales + (int64_t)call * B;
+    int* list = lists + (int64_t)call * LNX_DROP_LIST_INTS(B);
+    int* perm = list + 2;
+    int* inv = perm + B;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // pass 1: the kept count (the dropped samples' positions start behind it)
+    int mine = 0;
+    for (int i = tid; i < B; i += 256) mine += sc[i] != 0.f ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if (lane == 0) wsum[wave][0] = mine;
+    __syncthreads();
+    if (tid == 0) total_keep = wsum[0][0] + wsum[1][0] + wsum[2][0] + wsum[3][0];
+    __syncthreads();
+    const int nkeep = total_keep;
+    if (tid == 0) {
+        list[0] = nkeep;
+        list[1] = nkeep * dc.rps[blockIdx.x];
+    }
+    // pass 2: positions, 256 samples at a time in index order
+    int base_keep = 0, base_drop = 0;
+    for (int i0 = 0; i0 < B; i0 += 256) {
+        const int i = i0 + tid;
+        const bool in = i < B;
+        const bool keep = in && sc[i] != 0.f;
+        const bool drop = in && !keep;
+        const unsigned long long mk = __ballot(keep), md = __ballot(drop);
+        const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+        __syncthreads();  // (the previous round's wsum has been read)
+        if (lane == 0) {
+            wsum[wave][0] = __popcll(mk);
+            wsum[wave][1] = __popcll(md);
+        }
+        __syncthreads();
+        int pk = base_keep + __popcll(mk & below), pd = base_drop + __popcll(md & below);
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) {
+                pk += wsum[w][0];
+                pd += wsum[w][1];
+            }
+            base_keep += wsum[w][0];
+            base_drop += wsum[w][1];
+        }
+        if (in) {
+            const int pos = keep ? pk : nkeep + pd;
+            perm[pos] = i;
+            inv[i] = pos;
+        }
+    }
+}
+
 // dz = s * gamma * g ; dgamma += sum_m s * g * z.  Block = 256 threads as (rows x C/4
 // column groups); per-thread column partials are reduced through LDS, one atomic per column.
 template <typename T>
@@ -384,6 +480,45 @@ extern "C" int lnx_scale_cast(const float* in, int64_t ldin, lnx_rowmap in_map, 
     const int rps = rows_per_sample > 0 ? rows_per_sample : 1;
     DISPATCH_T(out_dtype, hipLaunchKernelGGL((scale_cast_kernel<T>), dim3(ew_grid((int64_t)M * (C / 4), 256)), dim3(256), 0, st, in, ldin, map, rowscale,
                                              rps, (T*)out, ldout, M, C));
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_scale_cast_compact(const float* in, int64_t ldin, const float* rowscale, int rows_per_sample, const int* perm, const int* m_dev, void* out,
+                                      int out_dtype, int64_t ldout, int M, int C, void* stream) {
+    LNX_CHECK(in && out && perm && m_dev && M > 0 && C > 0 && C % 4 == 0 && ldin % 4 == 0 && rows_per_sample > 0 && M % rows_per_sample == 0,
+              "lnx_scale_cast_compact: bad arguments M=%d C=%d rows_per_sample=%d", M, C, rows_per_sample);
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_T(out_dtype, hipLaunchKernelGGL((scale_cast_compact_kernel<T>), dim3(ew_grid((int64_t)M * (C / 4), 256)), dim3(256), 0, st, in, ldin, rowscale,
+                                             rows_per_sample, perm, m_dev, (T*)out, ldout, M, C));
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_copy_dropped_rows(const float* src, float* dst, int64_t ld, const int* perm, const int* nkeep, int B, int rows_per_sample, int C, void* stream) {
+    LNX_CHECK(src && dst && perm && nkeep && B > 0 && rows_per_sample > 0 && C > 0 && C % 4 == 0 && ld % 4 == 0, "lnx_copy_dropped_rows: bad arguments B=%d C=%d", B, C);
+    // (sized for a quarter of the samples: a grid-stride loop, and an empty tail costs one scalar load per workgroup)
+    hipLaunchKernelGGL(copy_dropped_rows_kernel, dim3(ew_grid((int64_t)cdiv(B, 4) * rows_per_sample * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, src, dst, ld,
+                       perm, nkeep, B, rows_per_sample, C);
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_drop_partition(const float* scales, int n_calls, int B, const unsigned char* call_mask, const int* rows_per_sample, int* lists, void* stream) {
+    LNX_CHECK(scales && lists && n_calls > 0 && B > 0, "lnx_drop_partition: bad arguments n_calls=%d B=%d", n_calls, B);
+    DropCalls dc;
+    int n = 0;
+    auto flush = [&]() {
+        if (n > 0) hipLaunchKernelGGL(drop_partition_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, scales, dc, B, lists);
+        n = 0;
+    };
+    for (int c = 0; c < n_calls; ++c) {
+        if (call_mask && !call_mask[c]) continue;
+        dc.call[n] = c;
+        dc.rps[n] = rows_per_sample ? rows_per_sample[c] : 1;
+        if (++n == LNX_DROP_PARTITION_MAX) flush();
+    }
+    flush();
     LNX_LAUNCH_CHECK();
     return 0;
 }

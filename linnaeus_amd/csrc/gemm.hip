@@ -20,7 +20,7 @@
 namespace {
 
 template <typename T, bool OUT_F32>
-__global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmP p) {
+__global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmP p_host) {
     constexpr int EPV = TT<T>::EPV;
     constexpr int BK = 8 * EPV;  // elements per K tile (128 bytes)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2 buf][A, W][TILE_BYTES]
@@ -31,8 +31,11 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmP p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int s = lane & 15, g = lane >> 4;
 
+    GemmP p = p_host;
+    effective_rows(p);
     int m0, n0;
     one_shot_origin<TILE, TILE>(p, m0, n0);
+    if (m0 >= p.M) return;  // (only with m_dev: a surplus workgroup of the host-sized grid)
 
     // ---- global -> register staging: 4 x 16B chunks per operand per thread ----
     int ld_row[4], ld_ch[4];
@@ -166,8 +169,16 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const WgradP p) {
     const int tk = bid % p.tiles_k;
     const int tn = bid / p.tiles_k;
     const int n0 = tn * TILE, k0 = tk * TILE;
-    const int m_begin = split * p.m_per_split;
-    const int m_end = min(p.M, m_begin + p.m_per_split);
+    // m_dev (compact rows): the contraction covers rows < min(M, *m_dev) only, and every split takes its range from that count (with the
+    // host's partition of the full M the last splits would idle and nothing would be saved); a split whose range is empty adds nothing
+    int m_all = p.M, m_per = p.m_per_split;
+    if (p.m_dev) {
+        m_all = min(p.M, max(*p.m_dev, 0));
+        m_per = (m_all + p.splits - 1) / p.splits;
+        m_per = (m_per + BMC - 1) / BMC * BMC;
+    }
+    const int m_begin = split * m_per;
+    const int m_end = min(m_all, m_begin + m_per);
     if (m_begin >= m_end) return;
 
     int ld_row[NLD], ld_ch[NLD];
@@ -388,6 +399,7 @@ extern "C" int lnx_gemm_tn(const lnx_wgrad_args* a, void* stream) {
     p.ws = a->ws;
     p.ws_floats = a->ws ? a->ws_floats : 0;
     p.k_store = (a->k_store > 0 && a->k_store < a->K) ? a->k_store : a->K;
+    p.m_dev = a->m_dev;
     p.tiles_n = cdiv(a->N, TILE);
     p.tiles_k = cdiv(a->K, TILE);
     const int bmc = a->dtype == LNX_BF16 ? 64 : 32;

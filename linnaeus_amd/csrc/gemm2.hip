@@ -22,7 +22,7 @@ namespace lnxg {
 
 // F = feature set of a specialised epilogue (gemm_common.hpp) or F_GENERIC
 template <bool OUT_F32, bool PATCH, int F>
-__global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
+__global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p_host) {
     typedef bf16_t T;
     typedef NarrowRing R;
     constexpr int BK = R::BK;
@@ -34,8 +34,11 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int s = lane & 15, g = lane >> 4;
 
+    GemmP p = p_host;
+    effective_rows(p);
     int m0, n0;
     one_shot_origin<R::BM, R::BN>(p, m0, n0);
+    if (m0 >= p.M) return;  // (only with m_dev: a surplus workgroup of the host-sized grid leaves before any load)
 
     // ---- LDS-DMA source addresses: wave w issues wave-instructions i = w + 8 j (j < 6); instruction
     // i fills LDS rows 8i..8i+7 of the stage (rows 0..255 = A, 256..383 = W), lane -> (row l>>3, slot l&7)
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(512) void gemm_nt_v2_kernel(const GemmP p) {
 // {0..3,16..19,32..35,48..51}+4i of every 16-lane group of a ds_read_b128 fall on 16 distinct 16-byte bank slots.
 // ------------------------------------------------------------------------------------
 template <bool OUT_F32, int F>
-__global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
+__global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p_host) {
     typedef bf16_t T;
     typedef WideRing R;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [R::NST][A 256 rows | W 256 rows][64 B]
@@ -160,8 +163,11 @@ __global__ __launch_bounds__(512) void gemm_nt_v4_kernel(const GemmP p) {
     const int wm = wave & 1, wn = wave >> 1;  // waves 0-3 / 4-7 (the ping-pong groups) cover the column halves
     const int s = lane & 15, g = lane >> 4;
 
+    GemmP p = p_host;
+    effective_rows(p);
     int m0, n0;
     one_shot_origin<R::BM, R::BN>(p, m0, n0);
+    if (m0 >= p.M) return;  // (only with m_dev: a surplus workgroup of the host-sized grid leaves before any load)
 
     // piece i (32 per stage) fills LDS rows 16 i .. 16 i + 15 (rows 0..255 = A, 256..511 = W); wave w issues i = w + 8 j
     const unsigned char* src[R::PIECES];
@@ -301,6 +307,7 @@ int launch_nt_v2(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
 // Requires bf16, M % 64 == 0, plain (non-patch) A.
 // ------------------------------------------------------------------------------------
 constexpr int TBM = 64;
+__device__ const uint4 g_tn_zero16 = {0u, 0u, 0u, 0u};  // what a ragged contraction tile fetches for its rows beyond the effective M
 
 #define DS_READ_TR2(lo, hi, addr, off2)                                                                                  \
     do {                                                                                                                 \
@@ -334,10 +341,20 @@ __global__ __launch_bounds__(512) void gemm_tn_v2_kernel(const WgradP p) {
     const int tc = bid % p.tiles_k;
     const int tr = bid / p.tiles_k;
     const int n0 = tr * RW, k0 = tc * CW;
-    const int m_begin = split * p.m_per_split;
-    const int m_end = min(p.M, m_begin + p.m_per_split);
-    if (m_begin >= m_end) return;
-    const int ntile = (m_end - m_begin) / TBM;
+    // m_dev (compact rows): the contraction covers rows < min(M, *m_dev) only, and every split takes its range from that count (with the
+    // host's partition of the full M the last splits would idle and nothing would be saved).  The count need not be a multiple of TBM:
+    // the ragged last contraction tile fetches zeros for its rows beyond the count (issue_tile), whatever those rows hold.
+    int m_all = p.M, m_per = p.m_per_split;
+    if (p.m_dev) {
+        m_all = min(p.M, max(*p.m_dev, 0));
+        const int mt = (m_all + TBM - 1) / TBM;
+        m_per = (mt + p.splits - 1) / p.splits * TBM;
+    }
+    const int m_begin = split * m_per;
+    const int m_end = min(m_all, m_begin + m_per);
+    // an empty range: nothing to add -- but a workspace slot is summed by the second stage whatever happened here, so it gets its zeros
+    if (m_begin >= m_end && !(p.m_dev && p.ws)) return;
+    const int ntile = m_begin < m_end ? (m_end - m_begin + TBM - 1) / TBM : 0;
 
     const unsigned char* src[NINS];
     int64_t step[NINS];
@@ -381,7 +398,9 @@ __global__ __launch_bounds__(512) void gemm_tn_v2_kernel(const WgradP p) {
             }
         }
     }
+    int m_issue = m_begin;  // first contraction row of the tile the next issue_tile fetches
     auto issue_tile = [&](int stage) {
+        const bool ragged = m_issue + TBM > m_end;  // (only with m_dev: M itself is a multiple of TBM)
 #pragma unroll
         for (int j = 0; j < NINS; ++j) {
             const int i = wave + 8 * j;
@@ -395,9 +414,14 @@ __global__ __launch_bounds__(512) void gemm_tn_v2_kernel(const WgradP p) {
             } else {
                 src[j] += step[j];
             }
+            if (ragged) {
+                const int row = i < RINS ? i * (64 / (RW / 8)) + lane / (RW / 8) : (i - RINS) * (64 / (CW / 8)) + lane / (CW / 8);
+                if (m_issue + row >= m_end) gp = reinterpret_cast<const unsigned char*>(&g_tn_zero16);
+            }
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
                                              (__attribute__((address_space(3))) void*)(smem + stage * STG + i * 1024), 16, 0, 0);
         }
+        m_issue += TBM;
     };
 
     // lane-constant fragment offsets (relative to the stage base): transposed block of rows
@@ -427,7 +451,7 @@ __global__ __launch_bounds__(512) void gemm_tn_v2_kernel(const WgradP p) {
     const bool do_bias = p.db != nullptr && tc == 0 && wc == 0;
     const uint4 ones = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);
 
-    issue_tile(0);
+    if (ntile > 0) issue_tile(0);  // (ntile == 0: the empty range of an m_dev product -- no fetch, no K loop, zeros to the workspace)
     if (ntile > 1) issue_tile(1);
     // Ping-pong schedule as in gemm_nt_v2_kernel: waves 0-3 / 4-7 run half a contraction tile apart, so the 32
     // transposed fragment reads and the 6 LDS-DMA pieces of one wave are issued under the 40 MFMAs of its SIMD
@@ -436,7 +460,7 @@ __global__ __launch_bounds__(512) void gemm_tn_v2_kernel(const WgradP p) {
     if (ntile > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (grp) __builtin_amdgcn_s_barrier();
+    if (grp && ntile > 0) __builtin_amdgcn_s_barrier();  // (the K loop's last iteration is where waves 4-7 make one barrier fewer)
     for (int t = 0; t < ntile; ++t) {
         const uint32_t st = lds_base + (t % NarrowRing::NST) * STG;
         uint2 rl[2][4], rh[2][4], cl[2][4], chh[2][4];

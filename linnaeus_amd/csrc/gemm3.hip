@@ -41,10 +41,16 @@ __device__ __forceinline__ void asm_load4(float& d, const void* ptr) {
 }
 
 // HEAD7 / TAIL7: K iterations at the start / before the last one of a tile that carry the deferred stores / the operand fetches
-template <bool OUT_F32, int F, int HEAD7, int TAIL7>
-__global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
+// PERM (F_RES only): compact rows -- res / C rows and the DropPath scale go through GemmP::perm.  That instantiation stores a tile's
+// results at once instead of under the next K loop: the translated rows would have to outlive the tile beside its 64 result registers,
+// which the 256-register budget does not hold (the fetches of the residual still ride under the K loop's TAIL).
+template <bool OUT_F32, int F, int HEAD7, int TAIL7, bool PERM = false>
+__global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p_host) {
     typedef bf16_t T;
     typedef NarrowRing R;
+    GemmP p = p_host;
+    effective_rows_persistent<R::BM>(p);  // m_dev: the tile total, the row clamps and the store masks all come from the effective M
+    if (p.M <= 0) return;                 // (nobody draws: the counters stay at zero)
     constexpr bool TWO = (F & F_C2) != 0;
     constexpr int NSTORE = OUT_F32 ? 16 : (TWO ? 16 : 8);                      // 16-byte stores per lane and tile
     constexpr int NLOAD = (F & F_GELU_BWD) ? 8 : ((F & F_RES) ? 16 : 0);       // 16-byte epilogue-operand fetches per lane and tile
@@ -169,6 +175,23 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
         const bool live = ncol0 < p.N;                      // column tiles beyond N (wave-uniform: N % 64 == 0): nothing to fetch or store
         const bool full = m0 + R::BM <= p.M;                // only full tiles defer their stores (every lane then issues every store)
         const int nbc = live ? nb : 0;
+        // PERM: the 64 rows of a wave's sub-tile belong to at most three samples (rows_per_sample >= 32, nt_v7_ok), whose entries are
+        // fetched here as scalars (the scalar counter, not the in-order vector one the K loop counts): compact row m -> its sample (the index
+        // of its DropPath scale) and its row of res / C
+        int prow[4] = {0, 0, 0, 0};  // PERM: the row of res / C of slot mi (its sample, for the DropPath scale: prow / rows_per_sample)
+        (void)prow;
+        if constexpr (PERM) {
+            const int rps = p.rows_per_sample;
+            const int q0 = __builtin_amdgcn_readfirstlane(min(mrow0, p.M - 1) / rps), last = p.M_host / rps - 1;
+            const int sp0 = p.perm[min(q0, last)], sp1 = p.perm[min(q0 + 1, last)], sp2 = p.perm[min(q0 + 2, last)];
+            const int e0 = q0 * rps;
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const int m = min(mbase + 4 * mi, p.M - 1);
+                const int jj = (m >= e0 + rps ? 1 : 0) + (m >= e0 + 2 * rps ? 1 : 0);
+                prow[mi] = (jj == 0 ? sp0 : (jj == 1 ? sp1 : sp2)) * rps + (m - e0 - jj * rps);
+            }
+        }
         // static stride: known now.  Counter: known after iteration 2 (has_next is first looked at in iteration nk - 2 >= 4)
         int next = pos + xgrid;
         bool has_next = !dyn && next < xcnt;
@@ -195,14 +218,14 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
                     const bool scaled = p.rowscale != nullptr;
                     const float* rsp = scaled ? p.rowscale : p.bias;  // always a fetch of something valid
                     const int m = min(mbase + 4 * mi, p.M - 1);
-                    asm_load4(rs[mi], rsp + (scaled ? m / p.rows_per_sample : 0));
+                    asm_load4(rs[mi], rsp + (scaled ? (PERM ? prow[mi] : m) / p.rows_per_sample : 0));
                 }
             } else if (F & F_GELU_BWD) {
                 const int mi = slot >> 1, h = slot & 1, m = min(mbase + 4 * mi, p.M - 1);
                 asm_load16(pa[mi][h], reinterpret_cast<const T*>(p.aux) + ((int64_t)m * p.ldaux + nbc) + 8 * h);
             } else if (F & F_RES) {
                 const int mi = slot >> 2, q = slot & 3, m = min(mbase + 4 * mi, p.M - 1);
-                asm_load16(pr[mi][q], p.res + ((int64_t)m * p.ldres + nbc) + 4 * q);
+                asm_load16(pr[mi][q], p.res + ((int64_t)(PERM ? prow[mi] : m) * p.ldres + nbc) + 4 * q);
             }
         };
 
@@ -231,7 +254,7 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
             if (fx == 3 && dyn) asm volatile("ds_read_b32 %0, %1" : "=v"(seen) : "v"(slot_addr) : "memory");  // waited for with the fragments below
             // (`pending` already says that the PREVIOUS tile's columns were inside N for this wave; this tile's `live` has nothing to
             // do with it -- consecutive tiles of a workgroup sit in different column tiles since round 4's drawn order)
-            const bool do_st = s_hi > s_lo && pending;
+            const bool do_st = s_hi > s_lo && pending && !PERM;  // (PERM: never anything pending -- say so, or the results stay live across the K loop)
             if (do_st) {
 #pragma unroll
                 for (int sl = s_lo; sl < s_hi; ++sl) store_slot(sl, false);
@@ -339,7 +362,13 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
                     v[4 * q + 3] = fmaf(v[4 * q + 3], sc, __uint_as_float(pr[mi][q].w));
                 }
             }
-            if (OUT_F32) {
+            if constexpr (PERM) {  // stored at once, to the compact row's own sample's row of C; nothing is kept
+                if (live && mbase + 4 * mi < p.M) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + ((int64_t)prow[mi] * p.ldc + nb) + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+                }
+            } else if (OUT_F32) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) hf[mi][q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
             } else {
@@ -354,11 +383,13 @@ __global__ __launch_bounds__(512) void gemm_nt_v7_kernel(const GemmP p) {
         }
         pend_row = live ? mbase : -1;
         pend_col = nb;
-        if (pend_row >= 0 && (!full || !has_next)) {
+        if (pend_row >= 0 && (!full || !has_next || PERM)) {
             // a partial tile (rows beyond M: some lanes store nothing, the counted waits need every lane to) and the last
             // tile (no K loop left to hide behind) store at once; the next iteration's wait then also covers these stores
+            if constexpr (!PERM) {  // (PERM: the epilogue arithmetic stored them)
 #pragma unroll
-            for (int sl = 0; sl < NSTORE; ++sl) store_slot(sl, true);
+                for (int sl = 0; sl < NSTORE; ++sl) store_slot(sl, true);
+            }
             pend_row = -1;
         }
         if (!has_next) break;  // (waves 4-7 leave one barrier short: they made one more at the start)
@@ -383,6 +414,7 @@ bool nt_v7_ok(const GemmP& p, int f, bool out_f32) {
     if (p.act == LNX_ACT_GELU_D) return false;  // this kernel's fc1 form keeps ONE tensor per tile; the derivative form needs two
     if (p.K % R::BK != 0 || p.K / R::BK < 6) return false;
     if (p.N % 64 != 0) return false;  // a wave's 64 columns are all inside or all outside N
+    if (p.perm && (p.rows_per_sample < 32 || !p.rowscale || !(f & F_RES))) return false;  // PERM: 64 rows span at most the three samples it fetches entries for
     return fits_32bit_offsets(p) && nt_v7_carries(out_f32, f);
 }
 
@@ -397,6 +429,12 @@ int launch_nt_v7(const GemmP& p0, int f, bool out_f32, hipStream_t st) {
     const bool deep = p.K / R::BK >= 17;  // long K loops spread the deferred traffic over 8 + 8 iterations instead of 3 + 2
     return with_nt_form<nt_v7_carries>("gemm_nt_v7", out_f32, f, [&](auto form) {
         using Form = decltype(form);
+        if constexpr ((Form::f & F_RES) != 0) {
+            if (p.perm) {
+                if (deep) return launch_with_lds<gemm_nt_v7_kernel<Form::out_f32, Form::f, 8, 8, true>>(grid, 512, lds, st, p);
+                return launch_with_lds<gemm_nt_v7_kernel<Form::out_f32, Form::f, 3, 2, true>>(grid, 512, lds, st, p);
+            }
+        }
         if (deep) return launch_with_lds<gemm_nt_v7_kernel<Form::out_f32, Form::f, 8, 8>>(grid, 512, lds, st, p);
         return launch_with_lds<gemm_nt_v7_kernel<Form::out_f32, Form::f, 3, 2>>(grid, 512, lds, st, p);
     });

@@ -24,9 +24,12 @@ template <bool OUT_F32, int F> struct EpiStores {
 };
 
 template <bool OUT_F32, int F>
-__global__ __launch_bounds__(512) void gemm_nt_v9_kernel(const GemmP p) {
+__global__ __launch_bounds__(512) void gemm_nt_v9_kernel(const GemmP p_host) {
     typedef bf16_t T;
     typedef WideRing R;
+    GemmP p = p_host;
+    effective_rows_persistent<R::BM>(p);  // m_dev: the tile total, the row clamps and the store masks all come from the effective M
+    if (p.M <= 0) return;                 // (nobody draws: the counters stay at zero)
     constexpr int NSTORE = EpiStores<OUT_F32, F>::value;
     static_assert(2 * R::PIECES + NSTORE + 1 <= 63, "vmcnt is a 6-bit counter");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [R::NST][A 256 rows | W 256 rows][64 B] + one dword

@@ -42,7 +42,30 @@ struct GemmP {
     int64_t ldc8 = 0;
     int stagger = 0;  // tools/experiments/gemm_nt_v5: start delay of the workgroup in the odd wave slot, in steps of ~1024 cycles
     int tile_slot = -1;  // persistent kernels: which set of tile counters this launch draws from (-1: static stride)
+    // compact rows (lnx_gemm_args.m_dev / perm): the kernel works on min(M, *m_dev) rows; the residual forms address res / C by sample
+    const int* m_dev = nullptr;
+    const int* perm = nullptr;
+    int M_host = 0;  // M as the host passed it (what the launch is sized from, and perm's length in rows)
 };
+
+// m_dev, read once at kernel entry.  One-shot kernels keep the host's tile grid (xcd_remap is a bijection on it) and a workgroup whose
+// tile starts at or beyond the effective M leaves before any load; persistent kernels count their tiles from the effective M.
+__device__ __forceinline__ void effective_rows(GemmP& p) {
+    if (p.m_dev) p.M = min(p.M, max(*p.m_dev, 0));
+}
+template <int BM>
+__device__ __forceinline__ void effective_rows_persistent(GemmP& p) {
+    if (p.m_dev) {
+        p.M = min(p.M, max(*p.m_dev, 0));
+        p.tiles_m = (p.M + BM - 1) / BM;
+    }
+}
+// compact row m of a residual form -> sample (for rowscale) and row of res / C: perm[m / rps] * rps + m % rps (identity without perm)
+__device__ __forceinline__ void compact_row(const GemmP& p, int m, int& sample, int& row) {
+    const int q = m / p.rows_per_sample;
+    sample = p.perm ? p.perm[q] : q;
+    row = p.perm ? sample * p.rows_per_sample + (m - q * p.rows_per_sample) : m;
+}
 
 // XCD-aware bijective remap of the linear workgroup id: consecutive logical tiles land on
 // the same XCD (blocks b and b+8 share an XCD under round-robin dispatch) so that the
@@ -191,12 +214,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4_t (&acc)[4][
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
         const int m = min(mrow0 + (s >> 2) * 16 + mi * 4 + (s & 3), p.M - 1);  // rows beyond M are loaded, never stored
-        rs[mi] = p.rowscale ? p.rowscale[m / p.rows_per_sample] : 1.f;
+        int sample, prow;
+        compact_row(p, m, sample, prow);  // (perm: plain addressing and an identity row map, checked by lnx_gemm_nt)
+        rs[mi] = p.rowscale ? p.rowscale[sample] : 1.f;
         if (p.c_mode == LNX_ADDR_PATCH2) {
             coffs[mi] = patch_base(p.pg, m) + patch_col(p.pg, nb);
             roffs[mi] = coffs[mi];
         } else {
-            const int64_t row = map_row(p.cmap, m);
+            const int64_t row = map_row(p.cmap, prow);
             coffs[mi] = row * p.ldc + nb;
             roffs[mi] = row * p.ldres + nb;
         }
@@ -341,6 +366,8 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmP& p, f32x4_t (&acc
     // loads first (see the generic epilogue): aux for GELU_BWD, or the fp32 residual
     float ld[4][16];
     float rs[4];
+    int prow[4];  // F_RES: row of res / C (the compact row's own sample under perm)
+    (void)prow;
     if (F & F_GELU_BWD) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
@@ -366,8 +393,14 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmP& p, f32x4_t (&acc
         for (int mi = 0; mi < 4; ++mi) {
             const int m = min(mbase + 4 * mi, p.M - 1);
             rs[mi] = 1.f;
-            if (scaled) rs[mi] = p.rows_per_sample >= 64 ? p.rowscale[q0 + (m >= edge ? 1 : 0)] : p.rowscale[m / p.rows_per_sample];
-            const float* rp = p.res + (m * (int)p.ldres + nb);
+            prow[mi] = m;
+            if (scaled) {
+                const int q = p.rows_per_sample >= 64 ? q0 + (m >= edge ? 1 : 0) : m / p.rows_per_sample;
+                const int sample = p.perm ? p.perm[q] : q;  // compact rows: the sample's own rows of res / C, its own scale
+                if (p.perm) prow[mi] = sample * p.rows_per_sample + (m - q * p.rows_per_sample);
+                rs[mi] = p.rowscale[sample];
+            }
+            const float* rp = p.res + (prow[mi] * (int)p.ldres + nb);
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
                 const float4 t = *reinterpret_cast<const float4*>(rp + 4 * h);
@@ -420,7 +453,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmP& p, f32x4_t (&acc
 #pragma unroll
             for (int j = 0; j < 16; ++j) v[j] = fmaf(v[j], rs[mi], ld[mi][j]);
         }
-        const int coff = m * (int)p.ldc + nb;
+        const int coff = ((F & F_RES) ? prow[mi] : m) * (int)p.ldc + nb;
         if (OUT_F32) {
             float* cp = reinterpret_cast<float*>(p.C) + coff;
 #pragma unroll
@@ -513,6 +546,7 @@ struct WgradP {
     float* ws;  // split-K partial tiles (gemm2.hip) or nullptr = atomics
     int64_t ws_floats;
     int tiles_n, tiles_k, splits, m_per_split;
+    const int* m_dev = nullptr;  // lnx_wgrad_args.m_dev: device int, the contraction stops at row min(M, *m_dev)
 };
 
 // ---- host side: one decision (gemm_nt_dispatch.cpp), one launcher per kernel family ----

@@ -614,6 +614,7 @@ static int launch_fp8(const lnx_gemm_args* a, const float* a_scale, const float*
     LNX_CHECK(a->lda % 16 == 0 && a->ldw % 16 == 0 && ((((uintptr_t)a->A) | ((uintptr_t)a->W)) & 15) == 0, "%s: A/W rows must be 16-byte aligned", who);
     LNX_CHECK(a->a_mode == LNX_ADDR_PLAIN && a->c_mode == LNX_ADDR_PLAIN && a->c_map.group == 0 && a->c_map.pad == 0 && a->c_map.off == 0,
               "%s: plain addressing only", who);
+    LNX_CHECK(a->m_dev == nullptr && a->perm == nullptr, "%s: compact rows (m_dev / perm) are not carried by the fp8 kernels", who);
     // the fp8 epilogues carry GELU (+ pre-activation copy) and GELU' only: GELU_D / MUL_AUX / ReLU would be dispatched on the
     // feature mask of their bf16 twins and silently compute something else
     LNX_CHECK(a->act == LNX_ACT_NONE || a->act == LNX_ACT_GELU || a->act == LNX_ACT_GELU_BWD, "%s: act %d is not carried by the fp8 kernels (NONE, GELU, GELU_BWD)", who, a->act);

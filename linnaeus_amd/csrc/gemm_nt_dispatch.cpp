@@ -70,6 +70,9 @@ void fill_gemm_p(const lnx_gemm_args* a, GemmP& p) {
     p.ldaux = a->ldaux;
     p.ldres = a->ldres;
     p.M = a->M;
+    p.M_host = a->M;
+    p.m_dev = a->m_dev;
+    p.perm = a->perm;
     p.N = a->N;
     p.K = a->K;
     p.a_mode = a->a_mode;
@@ -132,7 +135,8 @@ static bool nt_v2_ok(const GemmP& p, int dtype) {
 //              workgroup has no second tile to hide the first one's epilogue under) and where the big tile wins on rounds
 NtChoice nt_choose(const GemmP& p, int dtype, bool out_f32) {
     const NtSwitches sw = nt_switches();
-    if (sw.skinny && !sw.force_v1 && nt_skinny_ok(p, dtype, out_f32)) return {LNX_NT_KERNEL_SKINNY, 0};
+    // (compact rows -- m_dev / perm -- are carried by every family but the skinny kernel, whose M <= 256 products then go to the 128x128 one)
+    if (sw.skinny && !sw.force_v1 && !p.m_dev && !p.perm && nt_skinny_ok(p, dtype, out_f32)) return {LNX_NT_KERNEL_SKINNY, 0};
     if (sw.force_v1 || !nt_v2_ok(p, dtype)) return {LNX_NT_KERNEL_V1, 0};
     const int f = (p.a_mode == LNX_ADDR_PATCH2 || sw.generic_epi) ? (int)F_GENERIC : fast_epilogue_mask(p, out_f32);
     if (sw.v7 != 0 && nt_v7_ok(p, f, out_f32) && (sw.v7 == 1 || nt_v7_preferred(p, f, out_f32, sw))) return {LNX_NT_KERNEL_V7, f};
@@ -181,6 +185,12 @@ extern "C" int lnx_gemm_nt(const lnx_gemm_args* a, void* stream) {
     if (a->act == LNX_ACT_GELU_BWD || a->act == LNX_ACT_RELU_BWD || a->act == LNX_ACT_MUL_AUX) LNX_CHECK(a->aux != nullptr, "lnx_gemm_nt: act %d needs aux", a->act);
     if (a->act == LNX_ACT_GELU_D) LNX_CHECK(a->c2 != nullptr, "lnx_gemm_nt: GELU_D writes the derivative to c2, which is NULL");
     if (a->rowscale) LNX_CHECK(a->rows_per_sample > 0, "lnx_gemm_nt: rowscale needs rows_per_sample");
+    if (a->perm) {
+        LNX_CHECK(a->rows_per_sample > 0 && a->M % a->rows_per_sample == 0 && a->c_mode == LNX_ADDR_PLAIN && a->c_map.group == 0 && a->c_map.off == 0,
+                  "lnx_gemm_nt: perm needs rows_per_sample, M a whole number of samples and plain C addressing with an identity row map");
+        // (the fast epilogues translate rows where they look the row scale up, and only their residual form does)
+        LNX_CHECK(a->res && a->rowscale, "lnx_gemm_nt: perm is for the residual form with a row scale (it needs res and rowscale)");
+    }
 
     GemmP p;
     fill_gemm_p(a, p);

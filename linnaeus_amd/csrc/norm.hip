@@ -34,6 +34,10 @@ struct LnP {
     unsigned char* y8 = nullptr;   // optional MXFP8 copy of the bf16 output (ln_fwd_kernel<..., MX = true>)
     unsigned char* y8s = nullptr;  // its block scales, [C/128][M][4]
     int64_t ldy8 = 0;
+    // compact rows (lnx_ln_args.perm / m_dev): output row m < min(M, *m_dev) reads x row perm[m / rps] * rps + m % rps
+    const int* perm = nullptr;
+    const int* m_dev = nullptr;
+    int rps = 1;
 };
 
 template <typename T> __device__ __forceinline__ float4 load4(const T* p);
@@ -124,11 +128,19 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnP p) {
         wv[i] = *reinterpret_cast<const float4*>(p.w + col[i]);
         bv[i] = *reinterpret_cast<const float4*>(p.b + col[i]);
     }
-    for (int m0 = (blockIdx.x * 4 + wave) * R; m0 < p.M; m0 += gridDim.x * 4 * R) {
+    const int M = p.m_dev ? min(p.M, max(*p.m_dev, 0)) : p.M;  // rows at or beyond the effective M are not processed
+    for (int m0 = (blockIdx.x * 4 + wave) * R; m0 < M; m0 += gridDim.x * 4 * R) {
         const int m = m0 + rw;
-        const bool rv = m < p.M;
-        const int mc = rv ? m : p.M - 1;
-        const TX* xr = reinterpret_cast<const TX*>(p.x) + map_row(p.xmap, mc) * p.ldx;
+        const bool rv = m < M;
+        const int mc = rv ? m : M - 1;
+        int64_t xrow;
+        if (p.perm) {  // (uniform) the compact row's own sample's row of x
+            const int q = mc / p.rps;
+            xrow = (int64_t)p.perm[q] * p.rps + (mc - q * p.rps);
+        } else {
+            xrow = map_row(p.xmap, mc);
+        }
+        const TX* xr = reinterpret_cast<const TX*>(p.x) + xrow * p.ldx;
         float4 v[V], av[V];
 #pragma unroll
         for (int i = 0; i < V; i += PAIR) {
@@ -226,11 +238,18 @@ struct LnBwdP {
     unsigned char* dx2_8;   // optional MXFP8 copy of the bf16 dx2 (lnx_ln_bwd_args.dx2_8): elements, E8M0 block scales
     unsigned char* dx2_8s;
     int64_t lddx2_8;
+    // compact rows (lnx_ln_bwd_args.perm / m_dev / dx2_inv / dx2_nkeep)
+    const int* perm = nullptr;
+    const int* m_dev = nullptr;
+    const int* inv2 = nullptr;
+    const int* nkeep2 = nullptr;
 };
 
 // dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * w,  xhat = (x - mean) * rstd
 // dw += sum_m dy * xhat,  db += sum_m dy
-template <typename TDY, typename TX, typename TDX, int G, int V, int PAIR = 1, bool FULL = false>
+// CPT: the compact-row form (perm / m_dev / inv2), an instantiation of its own so that the full-row form carries none of its selects.
+// The dx row arithmetic is written with explicit fmaf / __fmul_rn: both forms round it the same way.
+template <typename TDY, typename TX, typename TDX, int G, int V, int PAIR = 1, bool FULL = false, bool CPT = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdP p) {
     constexpr int R = 64 / G;
     __shared__ float red[4][G * V * 4];
@@ -251,14 +270,30 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdP p) {
         wv[i] = *reinterpret_cast<const float4*>(p.w + col[i]);
     }
 
-    for (int m0 = (blockIdx.x * 4 + wave) * R; m0 < p.M; m0 += gridDim.x * 4 * R) {
+    // Compact rows.  Row m < Meff is a kept sample's: dy / mean / rstd at m, x / gin / dx at the sample's own row.  Rows of the samples
+    // behind Meff are walked only when there is a second output: its list is another one, so a sample dropped here may be kept there --
+    // such a row takes no LayerNorm arithmetic (dy counts as zero, dx is left alone), its dx2 is the scaled gin.
+    const bool compact = CPT && (p.perm != nullptr || p.inv2 != nullptr);
+    const int Meff = (CPT && p.m_dev) ? min(p.M, max(*p.m_dev, 0)) : p.M;
+    const int M = p.dx2 ? p.M : Meff;
+    const int nkeep2 = (CPT && p.nkeep2) ? *p.nkeep2 : 0x7fffffff;
+    for (int m0 = (blockIdx.x * 4 + wave) * R; m0 < M; m0 += gridDim.x * 4 * R) {
         const int m = m0 + rw;
-        const bool rv = m < p.M;
-        const int mc = rv ? m : p.M - 1;
-        const int64_t xrow = map_row(p.xmap, mc);
+        const bool rv = m < M;
+        const int mc = rv ? m : M - 1;
+        const bool live = !CPT || mc < Meff;
+        int sample = 0, tok = 0;
+        if (compact) {  // (uniform)
+            const int q = mc / p.rps2;
+            sample = p.perm ? p.perm[q] : q;
+            tok = mc - q * p.rps2;
+        }
+        const int64_t xrow = (CPT && p.perm) ? (int64_t)sample * p.rps2 + tok : map_row(p.xmap, mc);
+        const int ms = live ? mc : 0;  // (a row behind Meff reads row 0 of dy / mean / rstd and uses none of it)
         const TX* xr = reinterpret_cast<const TX*>(p.x) + xrow * p.ldx;
-        const TDY* dr = reinterpret_cast<const TDY*>(p.dy) + map_row(p.dymap, mc) * p.lddy;
-        const float mu = p.mean[mc], rs = p.rstd[mc];
+        const TDY* dr = reinterpret_cast<const TDY*>(p.dy) + map_row(p.dymap, ms) * p.lddy;
+        float mu = p.mean[ms], rs = p.rstd[ms];
+        if (!live) mu = rs = 0.f;  // xhat = 0: nothing stale reaches the column sums
         float4 xh[V], g[V];
         unsigned pos[V];  // bit j: x element j > 0 (ReLU mask)
         float s1 = 0.f, s2 = 0.f;
@@ -285,7 +320,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdP p) {
             if (ok[i]) {
                 const float4 xv = xraw[i];
                 float4 dv = draw[i];
-                if (!rv) dv = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!rv || !live) dv = make_float4(0.f, 0.f, 0.f, 0.f);
                 pos[i] = (xv.x > 0.f ? 1u : 0u) | (xv.y > 0.f ? 2u : 0u) | (xv.z > 0.f ? 4u : 0u) | (xv.w > 0.f ? 8u : 0u);
                 xh[i] = make_float4((xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs, (xv.w - mu) * rs);
                 g[i] = make_float4(dv.x * wv[i].x, dv.y * wv[i].y, dv.z * wv[i].z, dv.w * wv[i].w);
@@ -299,6 +334,19 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdP p) {
         const float m2 = group_sum<G>(s2) * invC;
         if (!rv) continue;
         TDX* ox = reinterpret_cast<TDX*>(p.dx) + xrow * p.lddx;
+        // the second output's row and scale: the sample's position under ITS list (none for a sample that list drops)
+        int64_t row2 = m;
+        int s2i = 0;
+        bool has2 = p.dx2 != nullptr;
+        if (!compact) {
+            if (has2 && p.rs2) s2i = m / p.rps2;  // (rps2 may be 0 where there is no scaled second output)
+        } else {
+            const int pos2 = (CPT && p.inv2) ? p.inv2[sample] : sample;
+            has2 = has2 && pos2 < nkeep2;
+            row2 = (int64_t)pos2 * p.rps2 + tok;
+            s2i = sample;
+        }
+        if (!live && !has2) continue;
 #pragma unroll
         for (int i = 0; i < V; i += PAIR) {
             const int c4 = col[i] >> 2;
@@ -308,11 +356,17 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdP p) {
 #pragma unroll
                 for (int q = 0; q < PAIR; ++q) {
                     const int k = i + q;
-                    float4 o = make_float4(rs * (g[k].x - m1 - xh[k].x * m2), rs * (g[k].y - m1 - xh[k].y * m2),
-                                           rs * (g[k].z - m1 - xh[k].z * m2), rs * (g[k].w - m1 - xh[k].w * m2));
+                    // contraction spelled out: the full-row and the compact-row instantiation round dx the same way (left to the
+                    // compiler, the compact form's extra selects kept it from fusing what the full-row form fuses)
+                    const float4 t = make_float4(fmaf(-xh[k].x, m2, g[k].x - m1), fmaf(-xh[k].y, m2, g[k].y - m1),
+                                                 fmaf(-xh[k].z, m2, g[k].z - m1), fmaf(-xh[k].w, m2, g[k].w - m1));
+                    float4 o;
                     if (p.gin) {
                         const float4 a = gv[k];
-                        o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
+                        o = make_float4(fmaf(rs, t.x, a.x), fmaf(rs, t.y, a.y), fmaf(rs, t.z, a.z), fmaf(rs, t.w, a.w));
+                        if (!live) o = a;  // (exactly gin: 0 + a would turn a -0 into +0)
+                    } else {
+                        o = make_float4(__fmul_rn(rs, t.x), __fmul_rn(rs, t.y), __fmul_rn(rs, t.z), __fmul_rn(rs, t.w));
                     }
                     if (p.relu_mask) {
                         if (!(pos[k] & 1u)) o.x = 0.f;
@@ -322,18 +376,20 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdP p) {
                     }
                     ov[q] = o;
                 }
-                if constexpr (PAIR == 2) store4x2<TDX>(ox + 4 * c4, ov[0], ov[1]);
-                else store4<TDX>(ox + 4 * c4, ov[0]);
-                if (p.dx2) {  // DropPath-scaled copy in storage type for the next branch's GEMMs (wave-uniform branch)
-                    const float sc = p.rs2 ? p.rs2[m / p.rps2] : 1.0f;
+                if (live) {
+                    if constexpr (PAIR == 2) store4x2<TDX>(ox + 4 * c4, ov[0], ov[1]);
+                    else store4<TDX>(ox + 4 * c4, ov[0]);
+                }
+                if (has2) {  // DropPath-scaled copy in storage type for the next branch's GEMMs
+                    const float sc = p.rs2 ? p.rs2[s2i] : 1.0f;
 #pragma unroll
                     for (int q = 0; q < PAIR; ++q) ov[q] = make_float4(ov[q].x * sc, ov[q].y * sc, ov[q].z * sc, ov[q].w * sc);
                     if (p.dx2_f32) {
-                        float* o2 = reinterpret_cast<float*>(p.dx2) + (int64_t)m * p.lddx2 + 4 * c4;
+                        float* o2 = reinterpret_cast<float*>(p.dx2) + row2 * p.lddx2 + 4 * c4;
 #pragma unroll
                         for (int q = 0; q < PAIR; ++q) store4<float>(o2 + 4 * q, ov[q]);
                     } else {
-                        bf16_t* o2 = reinterpret_cast<bf16_t*>(p.dx2) + (int64_t)m * p.lddx2 + 4 * c4;
+                        bf16_t* o2 = reinterpret_cast<bf16_t*>(p.dx2) + row2 * p.lddx2 + 4 * c4;
                         if constexpr (PAIR == 2) store4x2<bf16_t>(o2, ov[0], ov[1]);
                         else store4<bf16_t>(o2, ov[0]);
                         q8 = make_float4((float)(bf16_t)ov[0].x, (float)(bf16_t)ov[0].y, (float)(bf16_t)ov[0].z, (float)(bf16_t)ov[0].w);
@@ -612,9 +668,13 @@ void launch_bwd(LnBwdP p, const lnx_ln_launch& L, hipStream_t st, bool defer) {
     if (L.cols != LNX_LN_COLS_WORKSPACE) p.part = nullptr;
     const dim3 g(L.grid), b(256);
     bool launched = false;
+    const bool cpt = p.perm != nullptr || p.inv2 != nullptr || p.m_dev != nullptr;
 #define LN_BWD(GG, VV, PP)                                                                                           \
     if (!launched && L.G == GG && L.V == VV) {                                                                       \
-        if (L.full) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, GG, VV, PP, true>), g, b, 0, st, p);             \
+        if (cpt) {                                                                                                   \
+            if (L.full) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, GG, VV, PP, true, true>), g, b, 0, st, p);   \
+            else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, GG, VV, PP, false, true>), g, b, 0, st, p);         \
+        } else if (L.full) hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, GG, VV, PP, true>), g, b, 0, st, p);      \
         else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, GG, VV, PP, false>), g, b, 0, st, p);                   \
         launched = true;                                                                                             \
     }
@@ -652,6 +712,12 @@ int fwd_setup(const lnx_ln_args* a, LnP& p) {
                   "lnx_layernorm_fwd: the MXFP8 output needs x fp32, y bf16, an identity y_map, C %% 128 == 0 and 4-byte aligned rows");
         p.y8 = (unsigned char*)a->y8; p.y8s = (unsigned char*)a->y8_scales; p.ldy8 = a->ldy8;
     }
+    if (a->perm) {
+        LNX_CHECK(a->rows_per_sample > 0 && a->M % a->rows_per_sample == 0 && a->x_map.group == 0 && a->x_map.off == 0 && a->add == nullptr && a->y8 == nullptr,
+                  "lnx_layernorm_fwd: perm needs rows_per_sample, M a whole number of samples, an identity x_map and neither add nor the MXFP8 output");
+        p.perm = a->perm; p.rps = a->rows_per_sample;
+    }
+    p.m_dev = a->m_dev;
     return 0;
 }
 
@@ -682,6 +748,15 @@ int bwd_setup(const lnx_ln_bwd_args* a, LnBwdP& p) {
         p.dx2_8 = (unsigned char*)a->dx2_8; p.dx2_8s = (unsigned char*)a->dx2_8_scales; p.lddx2_8 = a->lddx2_8;
     }
     p.part = a->ws;
+    p.perm = a->perm; p.m_dev = a->m_dev; p.inv2 = a->dx2_inv; p.nkeep2 = a->dx2_nkeep;
+    if (a->perm || a->dx2_inv) {
+        LNX_CHECK(a->dx2_rows_per_sample > 0 && a->M % a->dx2_rows_per_sample == 0 && a->x_map.group == 0 && a->x_map.off == 0 && a->dy_map.group == 0 &&
+                      a->dy_map.off == 0 && a->dx2_8 == nullptr && !a->relu_mask,
+                  "lnx_layernorm_bwd: compact rows need dx2_rows_per_sample, M a whole number of samples, identity row maps and neither the MXFP8 copy nor relu_mask");
+        LNX_CHECK(a->dx2_inv == nullptr || (a->dx2 != nullptr && a->dx2_nkeep != nullptr), "lnx_layernorm_bwd: dx2_inv needs dx2 and dx2_nkeep");
+    }
+    if (a->m_dev && a->dx2)
+        LNX_CHECK(a->perm != nullptr && a->gin != nullptr, "lnx_layernorm_bwd: with m_dev the second output needs perm (which samples the rows behind the effective M belong to) and gin");
     return 0;
 }
 

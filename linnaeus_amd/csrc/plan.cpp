@@ -195,7 +195,26 @@ struct lnx_plan {
         if (last_drop == nullptr || call < 0 || !mask_host[call]) return nullptr;
         return last_drop + (int64_t)call * c.batch;
     }
+    // DropPath compaction: the lists lnx_plan_forward built for the RoPE blocks' drop calls of this forward, n_drop regions of
+    // LNX_DROP_LIST_INTS(batch) ints; valid until the next forward (the backward and a recompute plan's re-forward read them).  A device
+    // allocation of the plan's own (a few KiB, made by the first forward that compacts, freed by lnx_plan_destroy): the caller's
+    // workspace keeps its size.
+    int* droplists = nullptr;
+    bool compact_now = false;
+    const int* drop_list(int call) const {
+        if (!compact_now || droplists == nullptr || drop_ptr(call) == nullptr) return nullptr;
+        return droplists + (int64_t)call * LNX_DROP_LIST_INTS(c.batch);
+    }
 };
+
+// A/B switch of the DropPath compaction, process-wide: -1 = LNX_DROP_COMPACT (on unless set to 0), else what lnx_set_drop_compact said
+static std::atomic<int> g_drop_compact{-1};
+static std::atomic<long long> g_compact_branches{0};
+extern "C" int lnx_set_drop_compact(int on) {
+    const int was = g_drop_compact.exchange(on < 0 ? -1 : (on ? 1 : 0));
+    return was;
+}
+extern "C" int64_t lnx_drop_compact_branches(void) { return (int64_t)g_compact_branches.load(std::memory_order_relaxed); }
 
 namespace {
 
@@ -758,6 +777,10 @@ extern "C" void lnx_plan_destroy(lnx_plan* p) {
     if (!p) return;
     (void)lnx_gemm_tn_discard();  // no postponed reduce of this thread may outlive the workspace / gradient arena it points into
     (void)lnx_layernorm_bwd_discard();
+    if (p->droplists) {
+        (void)hipDeviceSynchronize();  // (a kernel of the last step may still read the lists)
+        (void)hipFree(p->droplists);
+    }
     if (p->side) {
         (void)hipStreamSynchronize(p->side);  // (shared_stream: not destroyed)
         (void)hipEventDestroy(p->ev_fork);
@@ -1005,10 +1028,21 @@ lnx_gemm_args gemm_base(const Ctx& c, int M, int N, int K, const void* A, int64_
     return a;
 }
 
+// The compaction list of one branch (all NULL: the branch runs on full rows) and rows per sample
+struct Compact {
+    const int* nkeep = nullptr;
+    const int* m_dev = nullptr;
+    const int* perm = nullptr;
+    const int* inv = nullptr;
+    int rps = 0;
+    explicit operator bool() const { return perm != nullptr; }
+};
+
 int ln_fwd(const Ctx& c, int M, int C, float eps, const void* x, int xdt, int64_t ldx, lnx_rowmap xm, int wi, int bi, void* y, int ydt, int64_t ldy,
-           lnx_rowmap ym, const void* add, int64_t ldadd, float* mean, float* rstd, void* y8 = nullptr, void* y8s = nullptr) {
+           lnx_rowmap ym, const void* add, int64_t ldadd, float* mean, float* rstd, void* y8 = nullptr, void* y8s = nullptr, Compact cl = Compact()) {
     lnx_ln_args a;
     memset(&a, 0, sizeof a);
+    a.perm = cl.perm; a.m_dev = cl.m_dev; a.rows_per_sample = cl.rps;
     a.y8 = y8; a.ldy8 = C; a.y8_scales = y8s;
     a.M = M; a.C = C; a.eps = eps;
     a.x = x; a.x_dtype = xdt; a.ldx = ldx; a.x_map = xm;
@@ -1039,12 +1073,15 @@ struct Dx2 {
     int rps = 0;
     void* p8 = nullptr;   // fp8 plans with MXFP8 data gradients: the MXFP8 copy of p (elements, block scales), written by the same pass
     void* p8s = nullptr;
+    const int* inv = nullptr;    // the branch that reads p runs on compact rows: sample -> position under its list, and its kept count
+    const int* nkeep = nullptr;
 };
 int ln_bwd(const Ctx& c, int M, int C, const void* dy, int dydt, int64_t lddy, lnx_rowmap dym, const void* x, int xdt, int64_t ldx, lnx_rowmap xm, int wi,
-           int bi, const float* mean, const float* rstd, const float* gin, void* dx, int dxdt, int64_t lddx, bool relu, Dx2 d2 = Dx2()) {
+           int bi, const float* mean, const float* rstd, const float* gin, void* dx, int dxdt, int64_t lddx, bool relu, Dx2 d2 = Dx2(), Compact cl = Compact()) {
     lnx_ln_bwd_args a;
     memset(&a, 0, sizeof a);
-    a.dx2 = d2.p; a.dx2_dtype = c.dt; a.lddx2 = C; a.dx2_rowscale = d2.rowscale; a.dx2_rows_per_sample = d2.rps;
+    a.perm = cl.perm; a.m_dev = cl.m_dev; a.dx2_inv = d2.inv; a.dx2_nkeep = d2.nkeep;
+    a.dx2 = d2.p; a.dx2_dtype = c.dt; a.lddx2 = C; a.dx2_rowscale = d2.rowscale; a.dx2_rows_per_sample = d2.rps > 0 ? d2.rps : cl.rps;
     if (d2.p && d2.p8) {
         a.dx2_8 = d2.p8; a.dx2_8_scales = d2.p8s; a.lddx2_8 = C;
     }
@@ -1072,9 +1109,11 @@ int ln_bwd(const Ctx& c, int M, int C, const void* dy, int dydt, int64_t lddy, l
 
 // `slot` >= 0: the product's split-K partial tiles go to workspace region `slot` and their summation into the gradient is postponed to
 // the block's tn_flush() (lnx_wgrad_args.defer); -1: summed at once
-int wgrad_to(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, const void* A, int64_t lda, float* dW, float* db, int64_t lddw, int k_store, int slot) {
+int wgrad_to(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, const void* A, int64_t lda, float* dW, float* db, int64_t lddw, int k_store, int slot,
+             const int* m_dev = nullptr) {
     lnx_wgrad_args a;
     memset(&a, 0, sizeof a);
+    a.m_dev = m_dev;
     a.dtype = c.dt;
     a.M = M; a.N = N; a.K = K;
     a.dY = dY; a.lddy = lddy;
@@ -1092,8 +1131,8 @@ int wgrad_to(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, co
 }
 // ... into the gradient arena's slices of parameters `wparam` / `bparam`
 int wgrad(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, const void* A, int64_t lda, int wparam, int bparam, int64_t lddw, int k_store = 0,
-          int slot = -1) {
-    return wgrad_to(c, M, N, K, dY, lddy, A, lda, c.p->G[wparam], bparam >= 0 ? c.p->G[bparam] : nullptr, lddw, k_store, slot);
+          int slot = -1, const int* m_dev = nullptr) {
+    return wgrad_to(c, M, N, K, dY, lddy, A, lda, c.p->G[wparam], bparam >= 0 ? c.p->G[bparam] : nullptr, lddw, k_store, slot, m_dev);
 }
 // ... into explicit buffers (the z-free LayerScale path's scratch)
 int wgrad_into(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, const void* A, int64_t lda, float* dW, float* db, int64_t lddw, int slot) {
@@ -1308,20 +1347,34 @@ double rope_block_flops(int B, int N, int C, int hid) {
     return 2.0 * M * C * (3.0 * C + C + 2.0 * hid) + 4.0 * B * (double)N * N * C;
 }
 
+// The compaction list of a RoPE-block branch, or none: the forward built the lists (training plan, the switch on), the call has a DropPath
+// multiplier, the block does not run its products in fp8 and no dropout mask (laid out by full rows) is set.
+Compact compact_of(const lnx_plan* p, int call, int M, int C, int N) {
+    Compact cl;
+    const int* list = p->drop_list(call);
+    if (list == nullptr || fp8_rows(p, M, C) || p->dmask || p->amask) return cl;
+    cl.nkeep = list; cl.m_dev = list + 1; cl.perm = list + 2; cl.inv = list + 2 + p->c.batch; cl.rps = N;
+    return cl;
+}
+
 int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     lnx_plan* p = c.p;
     RopeBlk& k = p->rope[s][i];
     const int B = p->c.batch, C = p->c.dims[2 + s], heads = p->c.rope_heads[s], hid = p->c.mlp_hidden[s];
     const int N = p->Ntok[s], M = B * N, E = p->E;
     const float* xin = c.at<float>(k.xin);
+    // DropPath compaction: a branch whose call has a list runs on the kept samples' rows only (compact rows: n1 / qkvbuf / o / lse,
+    // n2 / act / hpre and the LayerNorm statistics); the fp32 stream keeps its layout, the dropped samples' rows of xmid / xout are copies
+    const Compact ca = compact_of(p, p->drop_attn[s][i], M, C, N), cm = compact_of(p, p->drop_mlp[s][i], M, C, N);
+    g_compact_branches.fetch_add((ca ? 1 : 0) + (cm ? 1 : 0), std::memory_order_relaxed);
     p->resident[2 + s] = i;
     Timed span(c, 8, rope_block_flops(B, N, C, hid));
     const bool f8 = fp8_rows(p, M, C);
     void* a8 = f8 ? c.at<void>(p->o_a8) : nullptr;
     void* a8s = f8 ? c.at<void>(p->o_a8s) : nullptr;
-    RUN(ln_fwd(c, M, C, 1e-5f, xin, LNX_F32, C, IDM, k.n1w, k.n1b, c.at<void>(k.n1), c.dt, C, IDM, nullptr, 0, c.at<float>(k.mean1), c.at<float>(k.rstd1), a8, a8s));
+    RUN(ln_fwd(c, M, C, 1e-5f, xin, LNX_F32, C, IDM, k.n1w, k.n1b, c.at<void>(k.n1), c.dt, C, IDM, nullptr, 0, c.at<float>(k.mean1), c.at<float>(k.rstd1), a8, a8s, ca));
     lnx_gemm_args g = gemm_base(c, M, 3 * C, C, c.at<void>(k.n1), C, c.wptr(k.qkv), k.qkv.ld, c.at<void>(k.qkvbuf), 3 * C, false);
-    g.bias = p->P[k.qkvb];
+    g.bias = p->P[k.qkvb]; g.m_dev = ca.m_dev;
     RUN(linear_fwd(c, g, k.qkv, p->o_a8, p->o_a8s));
     lnx_attn_args a;
     memset(&a, 0, sizeof a);
@@ -1335,7 +1388,7 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     }
     {
         Timed t(c, 2, 4.0 * B * (double)N * N * C);
-        RUN(lnx_attn_fwd(&a, c.st));
+        RUN(lnx_attn_fwd_compact(&a, ca.nkeep, c.st));
     }
     if (p->dmask) {
         // proj_drop (rope_2d_mhsa.py:503): the product with its bias goes to scratch, dropout + DropPath + residual in one pass
@@ -1346,10 +1399,13 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     } else {
         g = gemm_base(c, M, C, C, c.at<void>(k.o), C, c.wptr(k.proj), k.proj.ld, c.at<float>(k.xmid), C, true);
         g.bias = p->P[k.projb]; g.rowscale = p->drop_ptr(p->drop_attn[s][i]); g.rows_per_sample = N; g.res = xin; g.ldres = C;
+        g.m_dev = ca.m_dev; g.perm = ca.perm;
         RUN(gemm_nt_t(c, &g));
+        if (ca) RUN(lnx_copy_dropped_rows(xin, c.at<float>(k.xmid), C, ca.perm, ca.nkeep, B, N, C, c.st));  // x + 0 . branch(x) = x, bit for bit
     }
-    RUN(ln_fwd(c, M, C, 1e-5f, c.at<float>(k.xmid), LNX_F32, C, IDM, k.n2w, k.n2b, c.at<void>(k.n2), c.dt, C, IDM, nullptr, 0, c.at<float>(k.mean2), c.at<float>(k.rstd2), a8, a8s));
+    RUN(ln_fwd(c, M, C, 1e-5f, c.at<float>(k.xmid), LNX_F32, C, IDM, k.n2w, k.n2b, c.at<void>(k.n2), c.dt, C, IDM, nullptr, 0, c.at<float>(k.mean2), c.at<float>(k.rstd2), a8, a8s, cm));
     g = gemm_base(c, M, hid, C, c.at<void>(k.n2), C, c.wptr(k.fc1), k.fc1.ld, c.at<void>(k.act), hid, false);
+    g.m_dev = cm.m_dev;
     // k.hpre holds GELU'(fc1 output) on bf16 / fp32 plans (evaluated here, once, from the fp32 pre-activation: the data-gradient
     // product's epilogue is then one multiply), the pre-activation itself in blocks that run their products in fp8 (those epilogue forms predate this)
     g.bias = p->P[k.fc1b]; g.act = f8 ? LNX_ACT_GELU : LNX_ACT_GELU_D; g.c2 = c.at<void>(k.hpre); g.ldc2 = hid;
@@ -1369,7 +1425,9 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     }
     g = gemm_base(c, M, C, hid, c.at<void>(k.act), hid, c.wptr(k.fc2), k.fc2.ld, xout, C, true);
     g.bias = p->P[k.fc2b]; g.rowscale = p->drop_ptr(p->drop_mlp[s][i]); g.rows_per_sample = N; g.res = c.at<float>(k.xmid); g.ldres = C;
+    g.m_dev = cm.m_dev; g.perm = cm.perm;
     RUN(linear_fwd(c, g, k.fc2, p->o_h8, p->o_h8s));
+    if (cm) RUN(lnx_copy_dropped_rows(c.at<float>(k.xmid), xout, C, cm.perm, cm.nkeep, B, N, C, c.st));
     return 0;
 }
 
@@ -1404,6 +1462,32 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
                     if (w->off8ts)
                         RUN(lnx_quantize_mxfp8(c.wtptr(*w), LNX_BF16, w->ld_t, w->K, w->N, c.at<void>(w->off8t), w->N, c.at<void>(w->off8ts), stream));
             }
+
+    // DropPath compaction lists of the RoPE blocks' drop calls of this forward, one launch (the multipliers are drawn on the device:
+    // no host synchronisation).  LNX_DROP_COMPACT=0 / lnx_set_drop_compact(0): every branch on full rows, as before.
+    p->compact_now = false;
+    {
+        const int sw = g_drop_compact.load(std::memory_order_relaxed);
+        const bool on = sw < 0 ? !env_off("LNX_DROP_COMPACT") : sw != 0;
+        if (on && !cf.inference && p->n_drop > 0 && drop_scales && !p->dmask && !p->amask) {
+            std::vector<unsigned char> want(p->n_drop, 0);
+            std::vector<int> rps(p->n_drop, 1);
+            bool any = false;
+            for (int s = 0; s < 2; ++s)
+                for (size_t i = 0; i < p->rope[s].size(); ++i)
+                    for (const int call : {p->drop_attn[s][i], p->drop_mlp[s][i]})
+                        if (p->mask_host[call] && !fp8_rows(p, B * p->Ntok[s], D[2 + s])) {
+                            want[call] = 1;
+                            rps[call] = p->Ntok[s];
+                            any = true;
+                        }
+            if (any) {
+                if (p->droplists == nullptr) HIPRUN(hipMalloc((void**)&p->droplists, (size_t)p->n_drop * LNX_DROP_LIST_INTS(B) * sizeof(int)));
+                RUN(lnx_drop_partition(drop_scales, p->n_drop, B, want.data(), rps.data(), p->droplists, stream));
+                p->compact_now = true;
+            }
+        }
+    }
 
     // metadata heads of both RoPE stages: forked onto the side stream right after the weight refresh
     int mw_all = 0;
@@ -1577,13 +1661,20 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     auto wfork = [&](int j) { return wg_fork(c, j); };
     auto wdone = [&](int j) { return wg_done(c, j); };
     auto wjoin = [&](int j) { return wg_join(c, j); };
+    // DropPath compaction (the forward's decision, from the same lists): sC / sA / sD hold compact rows inside a branch, g keeps its layout
+    const Compact ca = compact_of(p, p->drop_attn[s][i], M, C, N), cm = compact_of(p, p->drop_mlp[s][i], M, C, N);
+    const Compact cprev = i > 0 ? compact_of(p, p->drop_mlp[s][i - 1], M, C, N) : Compact();
     // ---- MLP branch ----
-    if (!have_dy) RUN(lnx_scale_cast(g, C, IDM, p->drop_ptr(p->drop_mlp[s][i]), N, sC, c.dt, C, M, C, c.st));
+    if (!have_dy) {
+        if (cm) RUN(lnx_scale_cast_compact(g, C, p->drop_ptr(p->drop_mlp[s][i]), N, cm.perm, cm.m_dev, sC, c.dt, C, M, C, c.st));
+        else RUN(lnx_scale_cast(g, C, IDM, p->drop_ptr(p->drop_mlp[s][i]), N, sC, c.dt, C, M, C, c.st));
+    }
     if (p->dmask) RUN(lnx_dropout_mul(sC, c.dt, p->dmask + k.dm_fc2, p->inv_keep, M, C, c.st));  // through the dropout after fc2
     RUN(wfork(0));
-    RUN(wgrad(cw, M, C, hid, sC, C, c.at<void>(k.act), hid, k.fc2.param, k.fc2b, hid, 0, 0));
+    RUN(wgrad(cw, M, C, hid, sC, C, c.at<void>(k.act), hid, k.fc2.param, k.fc2b, hid, 0, 0, cm.m_dev));
     RUN(wdone(0));
     lnx_gemm_args a = gemm_base(c, M, hid, C, sC, C, c.wtptr(k.fc2), k.fc2.ld_t, sA, hid, false);
+    a.m_dev = cm.m_dev;
     a.act = fp8_rows(p, M, C) ? LNX_ACT_GELU_BWD : LNX_ACT_MUL_AUX; a.aux = c.at<void>(k.hpre); a.ldaux = hid;  // what the forward left in hpre
     // fp8 plans: dY comes in MXFP8 from the LayerNorm backward that wrote it (the block above's norm1 backward; quantised here when
     // there was none, or a dropout mask went over it since), the GELU' epilogue hands dH on in MXFP8 as well as in bf16 (the weight gradients read bf16)
@@ -1593,24 +1684,26 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     p->dy8_ready = false;
     if (p->dmask) RUN(lnx_dropout_mul(sA, c.dt, p->dmask + k.dm_hid, p->inv_keep, M, hid, c.st));  // through the dropout after the activation
     RUN(wfork(1));
-    RUN(wgrad(cw, M, hid, C, sA, hid, c.at<void>(k.n2), C, k.fc1.param, k.fc1b, C, 0, 1));
+    RUN(wgrad(cw, M, hid, C, sA, hid, c.at<void>(k.n2), C, k.fc1.param, k.fc1b, C, 0, 1, cm.m_dev));
     RUN(wdone(1));
     a = gemm_base(c, M, C, hid, sA, hid, c.wtptr(k.fc1), k.fc1.ld_t, sD, C, false);
+    a.m_dev = cm.m_dev;
     RUN(linear_dgrad(c, a, k.fc1, false, p->o_h8, p->o_h8s));
     RUN(wjoin(0));  // norm2 backward overwrites sC
     // norm2 backward adds into g and, in the same pass, writes the attention branch's dY (DropPath-scaled g in storage type)
     Dx2 d2;
-    d2.p = sC; d2.rowscale = p->drop_ptr(p->drop_attn[s][i]); d2.rps = N;
+    d2.p = sC; d2.rowscale = p->drop_ptr(p->drop_attn[s][i]); d2.rps = N; d2.inv = ca.inv; d2.nkeep = ca.nkeep;
     if (mx_dgrad) {
         d2.p8 = c.at<void>(p->o_a8); d2.p8s = c.at<void>(p->o_a8s);
     }
-    RUN(ln_bwd(c, M, C, sD, c.dt, C, IDM, c.at<float>(k.xmid), LNX_F32, C, IDM, k.n2w, k.n2b, c.at<float>(k.mean2), c.at<float>(k.rstd2), g, g, LNX_F32, C, false, d2));
+    RUN(ln_bwd(c, M, C, sD, c.dt, C, IDM, c.at<float>(k.xmid), LNX_F32, C, IDM, k.n2w, k.n2b, c.at<float>(k.mean2), c.at<float>(k.rstd2), g, g, LNX_F32, C, false, d2, cm));
     // ---- attention branch ----
     if (p->dmask) RUN(lnx_dropout_mul(sC, c.dt, p->dmask + k.dm_proj, p->inv_keep, M, C, c.st));  // through proj_drop
     RUN(wfork(2));
-    RUN(wgrad(cw, M, C, C, sC, C, c.at<void>(k.o), C, k.proj.param, k.projb, C, 0, 2));
+    RUN(wgrad(cw, M, C, C, sC, C, c.at<void>(k.o), C, k.proj.param, k.projb, C, 0, 2, ca.m_dev));
     RUN(wdone(2));
     a = gemm_base(c, M, C, C, sC, C, c.wtptr(k.proj), k.proj.ld_t, sD, C, false);
+    a.m_dev = ca.m_dev;
     RUN(linear_dgrad(c, a, k.proj, !mx_dgrad, p->o_a8, p->o_a8s));
     RUN(wjoin(1));  // the attention backward overwrites sA
     lnx_attn_bwd_args ab;
@@ -1636,26 +1729,30 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     }
     {
         Timed t(c, 3, 14.0 * B * (double)N * N * C);
-        RUN(lnx_attn_bwd_sized(&ab, p->gcos_floats, c.st));
+        RUN(lnx_attn_bwd_compact(&ab, ca.nkeep, p->gcos_floats, c.st));
     }
     RUN(wfork(3));
-    RUN(wgrad(cw, M, 3 * C, C, sA, 3 * C, c.at<void>(k.n1), C, k.qkv.param, k.qkvb, C, 0, 3));
+    RUN(wgrad(cw, M, 3 * C, C, sA, 3 * C, c.at<void>(k.n1), C, k.qkv.param, k.qkvb, C, 0, 3, ca.m_dev));
     RUN(lnx_gemm_tn_flush(cw.st));  // the four products' partial tiles -> their gradients, one launch
     RUN(wdone(3));
     RUN(wjoin(2));  // the qkv data gradient overwrites sC
-    a = gemm_base(c, M, C, 3 * C, sA, 3 * C, c.wtptr(k.qkv), k.qkv.ld_t, sC, C, false);
+    // (compact rows on either side of norm1's backward: its dy rows and the dx2 rows it writes are then different rows, so the in-place
+    // hand-over below is off and this product writes sD, free since the attention backward read it)
+    void* dn1 = (ca || cprev) ? sD : sC;
+    a = gemm_base(c, M, C, 3 * C, sA, 3 * C, c.wtptr(k.qkv), k.qkv.ld_t, dn1, C, false);
+    a.m_dev = ca.m_dev;
     RUN(gemm_nt_t(c, &a));
     // norm1 backward: g is final for this block; block i-1's MLP-branch dY goes into sC in place of this LN's dy (row-wise
     // in-place is safe: a row's dy is consumed before its statistics are known, its dx2 written after)
     Dx2 d1;
     if (i > 0) {
-        d1.p = sC; d1.rowscale = p->drop_ptr(p->drop_mlp[s][i - 1]); d1.rps = N;
+        d1.p = sC; d1.rowscale = p->drop_ptr(p->drop_mlp[s][i - 1]); d1.rps = N; d1.inv = cprev.inv; d1.nkeep = cprev.nkeep;
         if (mx_dgrad) {  // block i - 1's fc2 data gradient reads it (same stage, same shapes: its own mx_dgrad is this one)
             d1.p8 = c.at<void>(p->o_a8); d1.p8s = c.at<void>(p->o_a8s);
             p->dy8_ready = true;
         }
     }
-    RUN(ln_bwd(c, M, C, sC, c.dt, C, IDM, c.at<float>(k.xin), LNX_F32, C, IDM, k.n1w, k.n1b, c.at<float>(k.mean1), c.at<float>(k.rstd1), g, g, LNX_F32, C, false, d1));
+    RUN(ln_bwd(c, M, C, dn1, c.dt, C, IDM, c.at<float>(k.xin), LNX_F32, C, IDM, k.n1w, k.n1b, c.at<float>(k.mean1), c.at<float>(k.rstd1), g, g, LNX_F32, C, false, d1, ca));
     RUN(wjoin(3));  // the next kernel of the main stream may overwrite sA, and the block's gradients count as written from here on
     return 0;
 }
@@ -1981,6 +2078,10 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
         // norm_1 backward also leaves the last stage-3 block's MLP-branch dY in sC (consumed first thing in segment 1)
         Dx2 dn;
         dn.p = c.at<void>(p->o_sC); dn.rowscale = p->drop_ptr(p->drop_mlp[0][cf.rope_depths[0] - 1]); dn.rps = p->Ntok[0];
+        {
+            const Compact cl = compact_of(p, p->drop_mlp[0][cf.rope_depths[0] - 1], B * p->Ntok[0], C2, p->Ntok[0]);
+            dn.inv = cl.inv; dn.nkeep = cl.nkeep;
+        }
         RUN(ln_bwd(c, B * p->Ntok[0], C2, dt1, cf.dtype, C2, IDM, c.at<float>(p->o_stage_out[2]), LNX_F32, C2, IDM, p->norm_w[0], p->norm_b[0], c.at<float>(p->o_t1_mean),
                    c.at<float>(p->o_t1_rstd), nullptr, g2, LNX_F32, C2, false, dn));
         // the stage-4 metadata-head backward (side stream, ~10 small fp32 GEMMs) is joined at the END OF SEGMENT 1: it only

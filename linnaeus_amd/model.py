@@ -348,6 +348,18 @@ class mFormerV1(nn.Module):
         L.set_deterministic(bool(on))
         self.release_plans()
 
+    @staticmethod
+    def set_drop_compact(on: Optional[bool]) -> int:
+        """A/B switch of the DropPath compaction (process-wide, include/lnx.h lnx_set_drop_compact): True / False, or None = back to the
+        environment (LNX_DROP_COMPACT, on unless 0).  Read by every forward; a backward follows its forward.  Same logits bit for bit
+        either way; gradients differ by summation order only.  Returns the previous setting (-1, 0 or 1)."""
+        return int(L.lib().lnx_set_drop_compact(-1 if on is None else int(bool(on))))
+
+    @staticmethod
+    def drop_compact_branches() -> int:
+        """RoPE-block branches whose forward ran on compact rows since the library was loaded (lnx_drop_compact_branches)."""
+        return int(L.lib().lnx_drop_compact_branches())
+
     def set_wgrad_stream(self, on: bool) -> None:
         """Backward scheduling of this model's native plans, present and future (include/lnx.h lnx_plan_set_wgrad_stream): True (the
         default) runs the weight-gradient products on a second HIP stream beside the data-gradient chain, False keeps everything on the

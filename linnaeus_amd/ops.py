@@ -46,8 +46,8 @@ def _map(m) -> L.RowMap:
 
 
 def gemm_nt(A, W, out, *, M=None, N=None, K=None, lda=None, ldw=None, ldc=None, bias=None, act=L.ACT_NONE, aux=None, c2=None,
-            gamma=None, rowscale=None, rows_per_sample=0, res=None, c_map=None, a_patch=None, c_patch=None, dtype=None):
-    """out = epilogue(A . W^T); see lnx_gemm_args.  a_patch / c_patch = (Hin, Win, Cin)."""
+            gamma=None, rowscale=None, rows_per_sample=0, res=None, c_map=None, a_patch=None, c_patch=None, dtype=None, m_dev=None, perm=None):
+    """out = epilogue(A . W^T); see lnx_gemm_args.  a_patch / c_patch = (Hin, Win, Cin).  m_dev / perm: compact rows (int32 device tensors)."""
     a = L.GemmArgs()
     a.dtype = dtype if dtype is not None else code_of(W)
     a.M = M if M is not None else A.shape[0]
@@ -67,6 +67,7 @@ def gemm_nt(A, W, out, *, M=None, N=None, K=None, lda=None, ldw=None, ldc=None, 
     a.act, a.aux, a.ldaux = act, _p(aux), (aux.stride(0) if aux is not None else 0)
     a.gamma, a.rowscale, a.rows_per_sample = _p(gamma), _p(rowscale), rows_per_sample
     a.res, a.ldres = _p(res), ((res.stride(0) if c_patch is None else 0) if res is not None else 0)
+    a.m_dev, a.perm = _p(m_dev), _p(perm)
     L.check(L.lib().lnx_gemm_nt(C.byref(a), _stream()), "lnx_gemm_nt")
     return out
 
@@ -162,8 +163,9 @@ def gemm_nt_mxfp8(A8, a_scales, W8, w_scales, out, *, bias=None, act=L.ACT_NONE,
     return out
 
 
-def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, a_patch=None, k_perm_c=0, k_store=0, splits=0, dtype=None, ws=None):
-    """ws (optional fp32 scratch): split-K partial tiles meet there and a second stage sums them in a fixed order; without it (or where
+def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, a_patch=None, k_perm_c=0, k_store=0, splits=0, dtype=None, ws=None,
+            m_dev=None):
+    """m_dev (optional device int32 tensor): the contraction stops at row min(M, m_dev[0]) -- see lnx_wgrad_args.m_dev.  ws (optional fp32 scratch): split-K partial tiles meet there and a second stage sums them in a fixed order; without it (or where
     it is too small) the splits meet in float atomics -- in deterministic mode the contraction is then split less, down to not at all."""
     a = L.WgradArgs()
     a.dtype = dtype if dtype is not None else code_of(dY)
@@ -178,11 +180,13 @@ def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, 
     a.k_perm_c, a.db, a.splits, a.k_store = k_perm_c, _p(db), splits, k_store
     if ws is not None:
         a.ws, a.ws_floats = _p(ws), ws.numel()
+    a.m_dev = _p(m_dev)
     L.check(L.lib().lnx_gemm_tn(C.byref(a), _stream()), "lnx_gemm_tn")
     return dW
 
 
-def _ln_args(x, w, b, y, eps, *, M=None, C_=None, ldx=None, ldy=None, x_map=None, y_map=None, add=None, ldadd=None, mean=None, rstd=None, y8=None, y8_scales=None):
+def _ln_args(x, w, b, y, eps, *, M=None, C_=None, ldx=None, ldy=None, x_map=None, y_map=None, add=None, ldadd=None, mean=None, rstd=None, y8=None, y8_scales=None,
+             perm=None, m_dev=None, rows_per_sample=0):
     a = L.LnArgs()
     a.M = M if M is not None else x.shape[0]
     a.C = C_ if C_ is not None else x.shape[-1]
@@ -194,6 +198,7 @@ def _ln_args(x, w, b, y, eps, *, M=None, C_=None, ldx=None, ldy=None, x_map=None
     a.mean, a.rstd = _p(mean), _p(rstd)
     if y8 is not None:
         a.y8, a.ldy8, a.y8_scales = _p(y8), y8.stride(0), _p(y8_scales)
+    a.perm, a.m_dev, a.rows_per_sample = _p(perm), _p(m_dev), int(rows_per_sample)  # compact rows: see lnx_ln_args
     return a
 
 
@@ -213,7 +218,7 @@ def layernorm_fwd_query(x, w, b, y, eps=0.0, **kw) -> L.LnLaunch:
 
 def _ln_bwd_args(dy, x, w, mean, rstd, dx, *, M=None, C_=None, lddy=None, ldx=None, lddx=None, dy_map=None, x_map=None, gin=None,
                  ldgin=None, dw=None, db=None, relu_mask=False, ws=None, dx2=None, lddx2=None, dx2_rowscale=None, dx2_rows_per_sample=0, dx2_8=None,
-                 dx2_8_scales=None, defer=False):
+                 dx2_8_scales=None, defer=False, perm=None, m_dev=None, dx2_inv=None, dx2_nkeep=None):
     a = L.LnBwdArgs()
     a.M = M if M is not None else dy.shape[0]
     a.C = C_ if C_ is not None else x.shape[-1]
@@ -230,6 +235,9 @@ def _ln_bwd_args(dy, x, w, mean, rstd, dx, *, M=None, C_=None, lddy=None, ldx=No
         a.dx2_rowscale, a.dx2_rows_per_sample = _p(dx2_rowscale), int(dx2_rows_per_sample)
         if dx2_8 is not None:
             a.dx2_8, a.dx2_8_scales, a.lddx2_8 = _p(dx2_8), _p(dx2_8_scales), dx2_8.stride(-2)
+    if perm is not None or dx2_inv is not None:  # compact rows: see lnx_ln_bwd_args (rows per sample = dx2_rows_per_sample)
+        a.dx2_rows_per_sample = int(dx2_rows_per_sample)
+    a.perm, a.m_dev, a.dx2_inv, a.dx2_nkeep = _p(perm), _p(m_dev), _p(dx2_inv), _p(dx2_nkeep)
     return a
 
 
@@ -322,7 +330,7 @@ def _head_dim(qkv, heads, head_dim):
     return qkv.shape[-1] // (3 * heads) if qkv.dim() >= 2 and qkv.shape[-1] % (3 * heads) == 0 else 64
 
 
-def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=0.0, head_dim=None, sin_tab=None):
+def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=0.0, head_dim=None, sin_tab=None, nkeep=None):
     """sin_tab (the second table of rope_cossin_table): the rotate form -- q and k pairs rotated by theta instead of scaled by cos(theta)."""
     a = L.AttnArgs()
     if sin_tab is not None:
@@ -332,11 +340,14 @@ def attn_fwd(qkv, cos_tab, o, lse, B, N, E, heads, *, drop_mask=None, drop_rate=
     a.qkv, a.cos_tab, a.o, a.lse = _p(qkv), _p(cos_tab), _p(o), _p(lse)
     if drop_mask is not None:
         a.drop_mask, a.drop_inv_keep = _p(drop_mask), 1.0 / (1.0 - drop_rate)
+    if nkeep is not None:  # compact rows (int32 device tensor): samples b >= nkeep[0] are skipped
+        L.check(L.lib().lnx_attn_fwd_compact(C.byref(a), _p(nkeep), _stream()), "lnx_attn_fwd_compact")
+        return
     L.check(L.lib().lnx_attn_fwd(C.byref(a), _stream()), "lnx_attn_fwd")
 
 
 def attn_bwd(qkv, cos_tab, o, lse, d_o, dqkv, delta, B, N, E, heads, *, dsin=None, dfreqs=None, drop_mask=None, drop_rate=0.0, defer_freqs=False,
-             head_dim=None, sin_tab=None, grid_w=0):
+             head_dim=None, sin_tab=None, grid_w=0, nkeep=None):
     """dq/dk/dv into dqkv; with image tokens (E < N) also dfreqs [2, heads, head_dim/2] += the gradient of the RoPE frequencies
     (`dsin` = the second table of rope_cos_table).  head_dim: from qkv's width unless given.  defer_freqs: the fold into dfreqs
     waits for attn_bwd_flush(); the returned workspace (and dfreqs) must be kept alive until then.
@@ -354,6 +365,9 @@ def attn_bwd(qkv, cos_tab, o, lse, d_o, dqkv, delta, B, N, E, heads, *, dsin=Non
     if drop_mask is not None:
         a.drop_mask, a.drop_inv_keep = _p(drop_mask), 1.0 / (1.0 - drop_rate)
     a.defer_freqs = int(bool(defer_freqs))
+    if nkeep is not None:  # compact rows, as attn_fwd (kept alive by the caller until attn_bwd_flush when the fold is postponed)
+        L.check(L.lib().lnx_attn_bwd_compact(C.byref(a), _p(nkeep), C.c_int64(ws.numel()), _stream()), "lnx_attn_bwd_compact")
+        return ws
     L.check(L.lib().lnx_attn_bwd_sized(C.byref(a), C.c_int64(ws.numel()), _stream()), "lnx_attn_bwd")
     return ws
 
@@ -381,6 +395,48 @@ def stem_fwd(x, w, bias, ln_w, ln_b, y, *, patches=None, pre=None, mean=None, rs
 def scale_cast(inp, out, M, Cc, *, ldin=None, in_map=None, rowscale=None, rows_per_sample=0, ldout=None):
     L.check(L.lib().lnx_scale_cast(_p(inp), C.c_int64(ldin if ldin is not None else inp.stride(-2)), _map(in_map), _p(rowscale), rows_per_sample,
                                    _p(out), code_of(out), C.c_int64(ldout if ldout is not None else out.stride(-2)), M, Cc, _stream()), "lnx_scale_cast")
+
+
+def scale_cast_compact(inp, out, M, Cc, *, perm, m_dev, rows_per_sample, rowscale=None, ldin=None, ldout=None):
+    """out[m', :] = rowscale[b] * inp[b * rows_per_sample + m' % rows_per_sample, :], b = perm[m' // rows_per_sample], for m' < min(M, m_dev[0])"""
+    L.check(L.lib().lnx_scale_cast_compact(_p(inp), C.c_int64(ldin if ldin is not None else inp.stride(-2)), _p(rowscale), rows_per_sample, _p(perm), _p(m_dev),
+                                           _p(out), code_of(out), C.c_int64(ldout if ldout is not None else out.stride(-2)), M, Cc, _stream()), "lnx_scale_cast_compact")
+
+
+def copy_dropped_rows(src, dst, *, perm, nkeep, rows_per_sample, Cc=None, ld=None):
+    """dst rows of the samples behind nkeep[0] in perm = src rows, bit for bit: rows perm[j] * rows_per_sample + t, j >= nkeep[0]; both fp32 with
+    leading dimension ld"""
+    L.check(L.lib().lnx_copy_dropped_rows(_p(src), _p(dst), C.c_int64(ld if ld is not None else dst.stride(-2)), _p(perm), _p(nkeep), perm.numel(), rows_per_sample,
+                                          Cc if Cc is not None else dst.shape[-1], _stream()), "lnx_copy_dropped_rows")
+
+
+class DropLists:
+    """The DropPath compaction lists of lnx_drop_partition as views of one int32 tensor [n_calls, 2 B + 2]."""
+
+    def __init__(self, lists: torch.Tensor, B: int):
+        self.lists, self.B = lists, B
+
+    def nkeep(self, c):
+        return self.lists[c, 0:1]
+
+    def m_dev(self, c):
+        return self.lists[c, 1:2]
+
+    def perm(self, c):
+        return self.lists[c, 2:2 + self.B]
+
+    def inv(self, c):
+        return self.lists[c, 2 + self.B:2 + 2 * self.B]
+
+
+def drop_partition(scales: torch.Tensor, rows_per_sample=None, call_mask=None) -> DropLists:
+    """scales [n_calls, B] fp32 (device): one list per call (call_mask: host sequence of 0 / 1, calls with 0 are left unwritten)."""
+    n, B = scales.shape
+    lists = torch.zeros((n, L.drop_list_ints(B)), device=scales.device, dtype=torch.int32)
+    rps = (C.c_int * n)(*[int(r) for r in rows_per_sample]) if rows_per_sample is not None else None
+    mask = bytes(bytearray(int(bool(m)) for m in call_mask)) if call_mask is not None else None
+    L.check(L.lib().lnx_drop_partition(_p(scales.contiguous()), n, B, mask, rps, _p(lists), _stream()), "lnx_drop_partition")
+    return DropLists(lists, B)
 
 
 def layerscale_bwd(g, z, gamma, rowscale, rows_per_sample, dz, dgamma, M, Cc):

@@ -48,17 +48,18 @@ def audit(hipcc=None, arch="gfx950"):
         bad += not ok
         seen += 1
         lines.append(f"{'ok ' if ok else 'BAD'} gemm_nt_v9<OUT_F32={o}, F={f}>: {x4} 16-byte stores (EpiStores {want}), {other} other stores, {scratch} scratch accesses")
-    # ---- gemm_nt_v7: template <bool OUT_F32, int F, int HEAD, int TAIL>; NSTORE = OUT_F32 ? 16 : (TWO ? 16 : 8), TWO = F has C2 and GELU
+    # ---- gemm_nt_v7: template <bool OUT_F32, int F, int HEAD, int TAIL, bool PERM>; NSTORE = OUT_F32 ? 16 : (TWO ? 16 : 8), TWO = F has C2 and GELU
     text = _asm(os.path.join(CSRC, "gemm3.hip"), hipcc, arch)
-    for m in re.finditer(r"^(_ZN4lnxg17gemm_nt_v7_kernelILb(\d)ELi(\d+)ELi(\d+)ELi(\d+)EEEvNS_5GemmPE):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
-        o, f, body = int(m.group(2)), int(m.group(3)), m.group(6)
+    # PERM (fifth argument): that instantiation defers nothing -- its NSTORE stores appear once, in the epilogue, and no wait counts them
+    for m in re.finditer(r"^(_ZN4lnxg17gemm_nt_v7_kernelILb(\d)ELi(\d+)ELi(\d+)ELi(\d+)ELb(\d)EEEvNS_5GemmPE):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
+        o, f, perm, body = int(m.group(2)), int(m.group(3)), int(m.group(6)), m.group(7)
         two = (f & F_C2) and (f & F_GELU)
-        want = 2 * (16 if (o or two) else 8)
+        want = (1 if perm else 2) * (16 if (o or two) else 8)
         x4, other, scratch = _counts(body)
         ok = x4 == want and other <= 1 and scratch == 0
         bad += not ok
         seen += 1
-        lines.append(f"{'ok ' if ok else 'BAD'} gemm_nt_v7<OUT_F32={o}, F={f}, {m.group(4)}, {m.group(5)}>: {x4} 16-byte stores (2 x NSTORE = {want}), {other} other stores, {scratch} scratch accesses")
+        lines.append(f"{'ok ' if ok else 'BAD'} gemm_nt_v7<OUT_F32={o}, F={f}, {m.group(4)}, {m.group(5)}{', PERM' if perm else ''}>: {x4} 16-byte stores ({1 if perm else 2} x NSTORE = {want}), {other} other stores, {scratch} scratch accesses")
     if seen < 12:
         bad += 1
         lines.append(f"BAD only {seen} kernel instantiations found in the assembly (mangled names changed?)")
