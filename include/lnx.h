@@ -353,6 +353,11 @@ typedef struct lnx_dwconv_args {
     int y_dtype;
 } lnx_dwconv_args;
 int lnx_dwconv7_fwd(const lnx_dwconv_args* args, void* stream);
+/* ... through a DropPath compaction list (lnx_drop_partition: perm [B] device, kept samples first; nkeep device int).  The kernel walks
+ * the tiles of the kept samples perm[0 .. *nkeep) only, divided anew over the workgroups of the launch: the samples perm[j],
+ * j >= *nkeep, are neither read nor written (their rows of y -- and with res == y their rows of the residual stream -- stay as they
+ * are).  Kept samples get the bits of the call without a list. */
+int lnx_dwconv7_fwd_kept(const lnx_dwconv_args* args, const int* perm, const int* nkeep, void* stream);
 
 typedef struct lnx_dwconv_wgrad_args {
     int B, H, W, C;
@@ -367,6 +372,10 @@ typedef struct lnx_dwconv_wgrad_args {
     int64_t ws_floats;
 } lnx_dwconv_wgrad_args;
 int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* args, void* stream);
+/* ... through a DropPath compaction list, as lnx_dwconv7_fwd_kept: the sums run over the kept samples perm[0 .. *nkeep) only, x and dy
+ * of the others are not read.  The deterministic route keeps one row of partial sums per walker of the launch for B samples (ws as
+ * for lnx_dwconv7_wgrad), folded in walker order; a walker the list leaves without tiles adds zeros. */
+int lnx_dwconv7_wgrad_kept(const lnx_dwconv_wgrad_args* args, const int* perm, const int* nkeep, void* stream);
 /* floats of ws the deterministic route of lnx_dwconv7_wgrad needs for this shape and these dtypes on the current device (the launcher's
  * own grid choice: walkers x 50 C); 0 for a shape the entry point refuses */
 int64_t lnx_dwconv7_wgrad_ws_floats(int B, int H, int W, int C, int x_dtype, int dy_dtype);
@@ -585,6 +594,10 @@ int lnx_copy_dropped_rows(const float* src, float* dst, int64_t ld, const int* p
  * the library was loaded (the tests' proof of which path a plan took, like lnx_last_nt_kernel). */
 int lnx_set_drop_compact(int on);
 int64_t lnx_drop_compact_branches(void);
+/* The conv blocks' share (blocks that run fused with the LayerNorm inside): LNX_DROP_COMPACT_CONV=0 keeps them on full rows while the
+ * RoPE blocks compact (read by every lnx_plan_forward).  lnx_drop_compact_conv_blocks(): conv blocks that ran a forward on compact
+ * rows since the library was loaded; lnx_drop_compact_branches() keeps counting RoPE branches only. */
+int64_t lnx_drop_compact_conv_blocks(void);
 
 /* LayerScale+DropPath backward of a ConvNeXt block branch (blocks/convnext.py:82-86):
  * dz = rowscale * gamma * g  (T),  dgamma[c] += sum_m rowscale * g * z */
@@ -1264,6 +1277,13 @@ typedef struct lnx_convmlp_args {
     void* ln_out;          /* optional out [M, C] bf16 */
     float* mean;           /* optional out [M] (with rstd) */
     float* rstd;
+    /* DropPath compaction (lnx_drop_partition; both NULL = every row in natural order).  The kernel walks COMPACT rows: row m' < *m_dev
+     * is sample perm[m' / rows_per_sample], pixel m' % rows_per_sample (rows_per_sample | M).  x, y and out keep natural sample order
+     * and are addressed through perm; ln (in or out), mean and rstd hold compact rows, rows >= *m_dev are neither read nor written.
+     * Kept rows get the bits of the full-row call; the rows of out that belong to dropped samples are copies of their rows of x (by
+     * the kernel itself: no launch is added).  z must be NULL. */
+    const int* perm;       /* [M / rows_per_sample] device: kept samples first */
+    const int* m_dev;      /* device int: kept samples x rows_per_sample */
 } lnx_convmlp_args;
 int lnx_convmlp_fwd(const lnx_convmlp_args* args, void* stream);
 
@@ -1302,6 +1322,13 @@ typedef struct lnx_convmlp_bwd_args {
                               lnx_layerscale_apply_wgrad multiplies by gamma afterwards (and reads the LayerScale gradient from) */
     int ln_defer;          /* round 5.  != 0 (fused LayerNorm form): the fold of the workgroups' column sums into d_ln_w / d_ln_b is postponed to
                               lnx_layernorm_bwd_flush() together with the postponed LayerNorm backward calls; `ws` must stay untouched until then */
+    /* DropPath compaction, as in lnx_convmlp_args (both NULL = every row).  g, y and dln keep natural sample order and are addressed
+     * through perm; ln, mean, rstd, act, dh and dz hold compact rows, rows >= *m_dev are neither read nor written and stay out of every
+     * column sum (dgamma, d_ln_w, d_ln_b).  The rows of dln that belong to dropped samples are not written (the depthwise gradients take
+     * the same list and do not read them); g is only read.  The weight-gradient products over act / dh / dz / ln take the same m_dev.
+     * z must be NULL. */
+    const int* perm;
+    const int* m_dev;
 } lnx_convmlp_bwd_args;
 int lnx_convmlp_bwd(const lnx_convmlp_bwd_args* args, void* stream);
 /* floats of `ws` the fused-LayerNorm backward needs for (C, M), from the same grid choice the launcher makes (0: unsupported C).

@@ -269,6 +269,10 @@ def lib() -> C.CDLL:
             _lib.lnx_drop_partition.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
             _lib.lnx_copy_dropped_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
             _lib.lnx_drop_compact_branches.restype = C.c_int64
+            if hasattr(_lib, "lnx_drop_compact_conv_blocks"):
+                _lib.lnx_drop_compact_conv_blocks.restype = C.c_int64
+                _lib.lnx_dwconv7_fwd_kept.argtypes = [C.POINTER(DwconvArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+                _lib.lnx_dwconv7_wgrad_kept.argtypes = [C.POINTER(DwconvWgradArgs), C.c_void_p, C.c_void_p, C.c_void_p]
             _lib.lnx_scale_cast_compact.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                                     C.c_void_p]
         if hasattr(_lib, "lnx_layernorm_fwd_query"):
@@ -316,9 +320,9 @@ EXPORTS = [
     "lnx_last_error", "lnx_version", "lnx_device_cus", "lnx_set_cu_margin", "lnx_set_deterministic", "lnx_get_deterministic", "lnx_tile_sched_static",
     "lnx_gemm_nt", "lnx_last_nt_kernel", "lnx_nt_kernel_launches", "lnx_nt_dispatch", "lnx_gemm_tn", "lnx_gemm_tn_flush", "lnx_gemm_tn_discard", "lnx_amax", "lnx_quantize_fp8", "lnx_gemm_nt_fp8", "lnx_quantize_mxfp8", "lnx_gemm_nt_mxfp8", "lnx_dropout_mul", "lnx_dropout_residual", "lnx_plan_dropout_bytes", "lnx_plan_set_dropout", "lnx_plan_attn_dropout_bytes", "lnx_plan_set_attn_dropout",
     "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard", "lnx_layernorm_fwd_query", "lnx_layernorm_bwd_query",
-    "lnx_dwconv7_fwd", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_ws_floats",
+    "lnx_dwconv7_fwd", "lnx_dwconv7_fwd_kept", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_kept", "lnx_dwconv7_wgrad_ws_floats",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_fwd_compact", "lnx_attn_bwd_compact", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
-    "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
+    "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_drop_compact_conv_blocks", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",
@@ -460,6 +464,7 @@ class ConvMlpArgs(C.Structure):
         ("x", C.c_void_p), ("out", C.c_void_p), ("z", C.c_void_p),
         ("y", C.c_void_p), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("ln_eps", C.c_float), ("ln_out", C.c_void_p),
         ("mean", C.c_void_p), ("rstd", C.c_void_p),
+        ("perm", C.c_void_p), ("m_dev", C.c_void_p),
     ]
 
 
@@ -472,6 +477,7 @@ class ConvMlpBwdArgs(C.Structure):
         ("y", C.c_void_p), ("ln_w", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("d_ln_w", C.c_void_p), ("d_ln_b", C.c_void_p),
         ("ws", C.c_void_p), ("ws_floats", C.c_int64),
         ("dz_plain", C.c_int), ("ln_defer", C.c_int),
+        ("perm", C.c_void_p), ("m_dev", C.c_void_p),
     ]
 
 

@@ -69,7 +69,37 @@ struct CmP {
     // straight to its row; a wave of the resident-weight kernel adds its tiles' LayerNorm sums (program order) in an LDS slot of its own.
     int det;
     float* dgpart;
+    // DropPath compaction (include/lnx.h, lnx_convmlp_args::perm): both NULL = every row, natural order
+    const int* perm;            // [B] kept samples first: compact row m is sample perm[m / rps], pixel m % rps
+    const int* m_dev;           // device int: the compact rows that exist (kept samples x rps)
 };
+
+// rows the kernel walks: read once at entry (uniform)
+__device__ __forceinline__ int eff_rows(const CmP& p) { return p.m_dev ? min(max(__builtin_amdgcn_readfirstlane(*p.m_dev), 0), p.M) : p.M; }
+// compact row m -> its sample and its row in the natural-order tensors (x, y, out, g, dln).  The list is read unconditionally (a valid
+// address without one, the value selected away): no memory operation under a branch in the persistent kernels' tile loops.
+struct RowAt {
+    int nat, smp;
+};
+__device__ __forceinline__ RowAt row_at(const CmP& p, int m) {
+    const int b = (p.perm || p.rowscale) ? m / p.rps : 0;
+    const int* pp = p.perm ? p.perm : reinterpret_cast<const int*>(p.gamma);
+    const int pb = pp[p.perm ? b : 0];
+    RowAt r;
+    r.smp = p.perm ? pb : b;
+    r.nat = m + (r.smp - b) * p.rps;
+    return r;
+}
+// compact rows [lo, hi) belong to dropped samples: in the forward their rows of out are their rows of x, bit for bit.  One wave per row.
+// (The backward has nothing to do for them: their rows of dln are neither written here nor read by the depthwise gradients, which take
+// the same list.)
+__device__ __forceinline__ void copy_dropped_x(const CmP& p, int lo, int hi, int wv, int nwv, int lane) {
+    const int c4 = p.C >> 2;
+    for (int m = lo + wv; m < hi; m += nwv) {
+        const int64_t off = (int64_t)row_at(p, m).nat * p.C;
+        if (lane < c4) reinterpret_cast<float4*>(p.out + off)[lane] = reinterpret_cast<const float4*>(p.x + off)[lane];
+    }
+}
 
 __device__ __forceinline__ void mfma16(f32x4_t& acc, const uint4& a, const uint4& b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
@@ -361,24 +391,25 @@ template <int NK>
 struct LnRow {
     uint2 yr[Geo<NK>::CT];
     float mu, rs;
+    int mn;  // the row of y / dln (natural order) this compact row stands for
 };
 template <int NK>
-__device__ __forceinline__ void ln_bwd_fetch(LnRow<NK>& r, const CmP& p, int m, int g) {
+__device__ __forceinline__ void ln_bwd_fetch(LnRow<NK>& r, const CmP& p, int mc, int mn, int g) {  // mc: the (clamped) compact row, mn: its natural row
     constexpr int C = Geo<NK>::C;
-    const int mc = m < p.M ? m : p.M - 1;
+    r.mn = mn;
 #pragma unroll
-    for (int ct = 0; ct < Geo<NK>::CT; ++ct) r.yr[ct] = *reinterpret_cast<const uint2*>(p.y + ((int64_t)mc * C + ct * 16 + 4 * g) * 2);
+    for (int ct = 0; ct < Geo<NK>::CT; ++ct) r.yr[ct] = *reinterpret_cast<const uint2*>(p.y + ((int64_t)r.mn * C + ct * 16 + 4 * g) * 2);
     r.mu = p.mean[mc];
     r.rs = p.rstd[mc];
 }
 template <int NK, int MT, int MTI>
-__device__ __forceinline__ void ln_bwd_rows(const CmP& p, const f32x4_t (&dl)[Geo<NK>::CT][MT], const LnRow<NK>& row, int m, int s, int g, const float* lnws,
-                                            float* dls, float* grow = nullptr) {
+__device__ __forceinline__ void ln_bwd_rows(const CmP& p, const f32x4_t (&dl)[Geo<NK>::CT][MT], const LnRow<NK>& row, int m, int Me, int s, int g,
+                                            const float* lnws, float* dls, float* grow = nullptr) {
     constexpr int C = Geo<NK>::C;
     constexpr int CT = Geo<NK>::CT;
     constexpr float invC = 1.0f / (float)C;
-    const bool mv = m < p.M;        // a lane beyond M holds row M - 1 again (clamped loads): it stores the same dy as its live twin
-    const int mc = mv ? m : p.M - 1;  // and contributes nothing to the column sums
+    const bool mv = m < Me;  // a lane beyond the last row holds that row again (clamped loads): it stores the same dy as its live twin
+                             // and contributes nothing to the column sums (a select: the twin's values are finite whenever the row's are)
     const uint2 (&yr)[CT] = row.yr;
     const float mu = row.mu, rs = row.rs;
     float xh[CT][4], gv[CT][4];
@@ -417,7 +448,7 @@ __device__ __forceinline__ void ln_bwd_rows(const CmP& p, const f32x4_t (&dl)[Ge
         bf16_t* vh = reinterpret_cast<bf16_t*>(&v);
 #pragma unroll
         for (int r = 0; r < 4; ++r) vh[r] = (bf16_t)(rs * (gv[ct][r] - m1 - xh[ct][r] * m2));
-        *reinterpret_cast<uint2*>(p.dln + ((int64_t)mc * C + ct * 16 + 4 * g) * 2) = v;
+        *reinterpret_cast<uint2*>(p.dln + ((int64_t)row.mn * C + ct * 16 + 4 * g) * 2) = v;
     }
 }
 
@@ -456,6 +487,15 @@ __global__ __launch_bounds__(64 * NW) void convmlp_fwd_kernel(const CmP p) {
     const int m_base = blockIdx.x * (16 * NW * MT) + wave * (16 * MT);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
+    // compact rows (CmP::perm): the grid is sized for M rows; this workgroup's rows beyond the kept ones are dropped samples' -- copied
+    // here -- and a workgroup that owns no kept row leaves before any other load
+    const int Me = eff_rows(p);
+    if (p.perm) {
+        const int wg0 = blockIdx.x * (16 * NW * MT), wg1 = min(wg0 + 16 * NW * MT, p.M);
+        if (wg1 > Me) copy_dropped_x(p, max(wg0, Me), wg1, wave, NW, lane);
+        if (wg0 >= Me) return;
+    }
+
     for (int i = threadIdx.x; i < 4 * C; i += 64 * NW) b1s[i] = p.b1[i];
 
     // this lane's ln fragments: row m (clamped), channels ks*32 + 8g .. +7
@@ -463,9 +503,10 @@ __global__ __launch_bounds__(64 * NW) void convmlp_fwd_kernel(const CmP p) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         int m = m_base + mt * 16 + s;
-        if (m >= p.M) m = p.M - 1;
+        if (m >= Me) m = Me - 1;
+        const int64_t mr = LNF ? row_at(p, m).nat : m;  // y keeps natural order, ln is the kernel's own
 #pragma unroll
-        for (int ks = 0; ks < NK; ++ks) xf[mt][ks] = ld16((LNF ? p.y : p.ln) + ((int64_t)m * C + ks * 32 + 8 * g) * 2);
+        for (int ks = 0; ks < NK; ++ks) xf[mt][ks] = ld16((LNF ? p.y : p.ln) + (mr * C + ks * 32 + 8 * g) * 2);
     }
     if constexpr (LNF) {
 #pragma unroll
@@ -473,7 +514,7 @@ __global__ __launch_bounds__(64 * NW) void convmlp_fwd_kernel(const CmP p) {
             float mu, rs;
             ln_row_frags<NK>(xf[mt], p.lnw, p.lnb, g, p.eps, mu, rs);
             const int m = m_base + mt * 16 + s;
-            if (m < p.M) {
+            if (m < Me) {
                 if (p.ln_out) {
 #pragma unroll
                     for (int ks = 0; ks < NK; ++ks) st16(p.ln_out + ((int64_t)m * C + ks * 32 + 8 * g) * 2, xf[mt][ks]);
@@ -551,16 +592,18 @@ __global__ __launch_bounds__(64 * NW) void convmlp_fwd_kernel(const CmP p) {
     // epilogue: lane (s = row m, g) holds channels c = 16 ct + 4 g + r
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-        const int m = m_base + mt * 16 + s;
-        if (m >= p.M) continue;
-        const float rs = p.rowscale ? p.rowscale[m / p.rps] : 1.0f;
+        const int mk = m_base + mt * 16 + s;
+        if (mk >= Me) continue;
+        const RowAt ra = row_at(p, mk);
+        const int64_t m = ra.nat;  // x / out (and z, a form without a list) by natural row
+        const float rs = p.rowscale ? p.rowscale[ra.smp] : 1.0f;
         // all loads first: as far as the compiler knows the stores below may alias them, and interleaving
         // would serialise one full memory round trip per channel tile
         float4 xrv[CT], b2v[CT], gmv[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const int c = ct * 16 + 4 * g;
-            xrv[ct] = *reinterpret_cast<const float4*>(p.x + (int64_t)m * C + c);
+            xrv[ct] = *reinterpret_cast<const float4*>(p.x + m * C + c);
             b2v[ct] = *reinterpret_cast<const float4*>(p.b2 + c);
             gmv[ct] = *reinterpret_cast<const float4*>(p.gamma + c);
         }
@@ -573,9 +616,9 @@ __global__ __launch_bounds__(64 * NW) void convmlp_fwd_kernel(const CmP p) {
                 uint2 zz;
                 bf16_t* zh = reinterpret_cast<bf16_t*>(&zz);
                 zh[0] = (bf16_t)z0; zh[1] = (bf16_t)z1; zh[2] = (bf16_t)z2; zh[3] = (bf16_t)z3;
-                *reinterpret_cast<uint2*>(p.z + ((int64_t)m * C + c) * 2) = zz;
+                *reinterpret_cast<uint2*>(p.z + (m * C + c) * 2) = zz;
             }
-            *reinterpret_cast<float4*>(p.out + (int64_t)m * C + c) =
+            *reinterpret_cast<float4*>(p.out + m * C + c) =
                 make_float4(xr.x + rs * gm.x * z0, xr.y + rs * gm.y * z1, xr.z + rs * gm.z * z2, xr.w + rs * gm.w * z3);
         }
     }
@@ -616,6 +659,23 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
     const int m_base = blockIdx.x * (16 * NW * MT) + wave * (16 * MT);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
+    // compact rows (CmP::perm): a workgroup that owns no kept row leaves before any load -- its rows of the column-sum scratch, which the
+    // folds behind the kernel read in full, hold zeros
+    const int Me = eff_rows(p);
+    if (p.perm) {
+        if (blockIdx.x * (16 * NW * MT) >= Me) {
+            if (p.det) {
+                if constexpr (LNB)
+                    for (int i = lane; i < 2 * C; i += 64) p.part[((int64_t)blockIdx.x * NW + wave) * (2 * C) + i] = 0.f;
+                if constexpr (DG)
+                    for (int i = lane; i < C; i += 64) p.dgpart[((int64_t)blockIdx.x * NW + wave) * C + i] = 0.f;
+            } else if constexpr (LNB) {
+                for (int i = threadIdx.x; i < 2 * C; i += 64 * NW) p.part[(int64_t)blockIdx.x * (2 * C) + i] = 0.f;
+            }
+            return;
+        }
+    }
+
     for (int i = threadIdx.x; i < 4 * C; i += 64 * NW) b1s[i] = p.b1[i];
     for (int i = threadIdx.x; i < C; i += 64 * NW) {
         dgs[i] = 0.f;
@@ -631,9 +691,11 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         int m = m_base + mt * 16 + s;
-        mvalid[mt] = m < p.M;
-        if (!mvalid[mt]) m = p.M - 1;  // such a lane redoes row M - 1 and stores the same bytes as its live twin; only the column sums mask it
-        const float rs = p.rowscale ? p.rowscale[m / p.rps] : 1.0f;
+        mvalid[mt] = m < Me;
+        if (!mvalid[mt]) m = Me - 1;  // such a lane redoes the last row and stores the same bytes as its live twin; only the column sums mask it
+        const RowAt ra = row_at(p, m);
+        const int64_t mg = ra.nat;  // g (and z) by natural row; ln, dz, act, dh by the kernel's own
+        const float rs = p.rowscale ? p.rowscale[ra.smp] : 1.0f;
         // loads of every k-step first, then compute + dz stores (see the forward epilogue note)
         float4 g0v[NK], g1v[NK], a0v[NK], a1v[NK];
         uint4 zraw[NK];
@@ -641,11 +703,11 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
         for (int ks = 0; ks < NK; ++ks) {
             const int c = ks * 32 + 8 * g;
             xf[mt][ks] = ld16(p.ln + ((int64_t)m * C + c) * 2);
-            g0v[ks] = *reinterpret_cast<const float4*>(p.g + (int64_t)m * C + c);
-            g1v[ks] = *reinterpret_cast<const float4*>(p.g + (int64_t)m * C + c + 4);
+            g0v[ks] = *reinterpret_cast<const float4*>(p.g + mg * C + c);
+            g1v[ks] = *reinterpret_cast<const float4*>(p.g + mg * C + c + 4);
             a0v[ks] = *reinterpret_cast<const float4*>(p.gamma + c);
             a1v[ks] = *reinterpret_cast<const float4*>(p.gamma + c + 4);
-            if constexpr (DG) zraw[ks] = ld16(p.zin + ((int64_t)m * C + c) * 2);
+            if constexpr (DG) zraw[ks] = ld16(p.zin + (mg * C + c) * 2);
         }
 #pragma unroll
         for (int ks = 0; ks < NK; ++ks) {
@@ -685,7 +747,10 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) dl[ct][mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     LnRow<NK> lrow;
-    if constexpr (LNB) ln_bwd_fetch<NK>(lrow, p, m_base + s, g);
+    if constexpr (LNB) {
+        const int mc = min(m_base + s, Me - 1);
+        ln_bwd_fetch<NK>(lrow, p, mc, row_at(p, mc).nat, g);
+    }
 
     __syncthreads();
     dma_nmajor<NK, NW>(smem, p.w1, 0, wave, lane);
@@ -735,7 +800,7 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
             pd[mt][0] = pack8(da[0][mt], da[1][mt]);
             pd[mt][1] = pack8(da[2][mt], da[3][mt]);
             // packed element j of k-step ks2 <-> hidden n = 64 j_chunk + 32 ks2 + 8 g + j : 16 contiguous bytes per row
-            const int m = min(m_base + mt * 16 + s, p.M - 1);
+            const int m = min(m_base + mt * 16 + s, Me - 1);
             if constexpr (ST) {
                 const int64_t off = ((int64_t)m * (4 * C) + 64 * j + 8 * g) * 2;
                 st16(p.act + off, pa[mt][0]);
@@ -748,11 +813,11 @@ __global__ __launch_bounds__(64 * NW) void convmlp_bwd_kernel(const CmP p) {
     }
     if constexpr (LNB) {
         static_assert(MT == 1, "ln_bwd_rows is instantiated per m-tile");
-        ln_bwd_rows<NK, MT, 0>(p, dl, lrow, m_base + s, s, g, lws, dls, p.det ? p.part + ((int64_t)blockIdx.x * NW + wave) * (2 * C) : nullptr);
+        ln_bwd_rows<NK, MT, 0>(p, dl, lrow, m_base + s, Me, s, g, lws, dls, p.det ? p.part + ((int64_t)blockIdx.x * NW + wave) * (2 * C) : nullptr);
     } else {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const int m = min(m_base + mt * 16 + s, p.M - 1);
+            const int64_t m = row_at(p, min(m_base + mt * 16 + s, Me - 1)).nat;  // dln by natural row
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
                 const int c = ct * 16 + 4 * g;
@@ -876,11 +941,16 @@ __global__ __launch_bounds__(512) void convmlp_fwd_res_kernel(const CmP p) {
     // tile scheduling (common.hpp): each WAVE draws its 32-row tiles from the launch's counter, the first one here, under the
     // weight DMA (its round trip is covered by the wait below); static stride when tile_slot < 0
     const bool dyn = p.tile_slot >= 0;
-    const TileShare sh = tile_share((p.M + 31) / 32);
+    // compact rows (CmP::perm): the tiles are counted from the rows that exist.  Not in the forms that save z, which lnx_convmlp_fwd
+    // refuses together with a list (at C = 96 they have no register left for the translated row)
+    constexpr bool CP = SAVE != 1;
+    const int Me = CP ? eff_rows(p) : p.M;
+    const TileShare sh = tile_share((Me + 31) / 32);
     unsigned* const ctr = &g_tile_ctr[dyn ? p.tile_slot : 0][sh.part][0];
     int drawn = dyn ? sched_draw_counted(ctr) : 0;
     dma_all_nmajor<NK>(w1img, p.w1, wave, lane);
     dma_all_cmajor<NK>(w2img, p.w2, wave, lane);
+    if (CP && p.perm) copy_dropped_x(p, Me, p.M, blockIdx.x * 8 + wave, gridDim.x * 8, lane);  // under the weight DMA, shared by the whole grid
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -893,13 +963,14 @@ __global__ __launch_bounds__(512) void convmlp_fwd_res_kernel(const CmP p) {
     // branch it drains the counter instead, which made every tile wait for the previous tile's store acknowledgements AND the next
     // tile's prefetch (round 3).  So: rows beyond M are clamped to M - 1 (such a lane recomputes row M - 1 and stores the same bytes
     // as its live twin), the optional outputs are a template parameter (SAVE), the DropPath scale is loaded unconditionally.
-    const int ntile = (p.M + 31) / 32;
     auto load_x = [&](uint4 (&dst)[MT][NK], int tile) __attribute__((always_inline)) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const int m = min(tile * 32 + mt * 16 + s, p.M - 1);
+            const int m = min(tile * 32 + mt * 16 + s, Me - 1);
+            int64_t mr = m;  // ln is the kernel's own, y keeps natural order
+            if constexpr (LNF && CP) mr = row_at(p, m).nat;
 #pragma unroll
-            for (int ks = 0; ks < NK; ++ks) dst[mt][ks] = ld16((LNF ? p.y : p.ln) + ((int64_t)m * C + ks * 32 + 8 * g) * 2);
+            for (int ks = 0; ks < NK; ++ks) dst[mt][ks] = ld16((LNF ? p.y : p.ln) + (mr * C + ks * 32 + 8 * g) * 2);
         }
     };
     // this XCD's tiles [xbase, xbase + xcnt) and its waves; positions are drawn (or strided over, LNX_TILE_SCHED=static) within them
@@ -921,7 +992,7 @@ __global__ __launch_bounds__(512) void convmlp_fwd_res_kernel(const CmP p) {
             for (int mt = 0; mt < MT; ++mt) {
                 float mu, rs;
                 ln_row_frags<NK>(xf[mt], lws, lbs, g, p.eps, mu, rs);
-                const int m = min(m_base + mt * 16 + s, p.M - 1);
+                const int m = min(m_base + mt * 16 + s, Me - 1);
                 if constexpr (SAVE != 0) {
 #pragma unroll
                     for (int ks = 0; ks < NK; ++ks) st16(p.ln_out + ((int64_t)m * C + ks * 32 + 8 * g) * 2, xf[mt][ks]);
@@ -941,6 +1012,7 @@ __global__ __launch_bounds__(512) void convmlp_fwd_res_kernel(const CmP p) {
         // last tile fetches itself again (unconditional).
         float4 xrv[MT][CT];
         float rsv[MT];
+        int mnat[MT];  // the tile's rows of x / out (natural order)
         f32x4_t o[CT][MT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
@@ -958,10 +1030,18 @@ __global__ __launch_bounds__(512) void convmlp_fwd_res_kernel(const CmP p) {
                 }
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
-                    const int m = min(m_base + mt * 16 + s, p.M - 1);
+                    if constexpr (CP) {
+                        const RowAt ra = row_at(p, min(m_base + mt * 16 + s, Me - 1));
+                        mnat[mt] = ra.nat;
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) xrv[mt][ct] = *reinterpret_cast<const float4*>(p.x + (int64_t)m * C + ct * 16 + 4 * g);
-                    rsv[mt] = rsp[p.rowscale ? m / p.rps : 0];
+                        for (int ct = 0; ct < CT; ++ct) xrv[mt][ct] = *reinterpret_cast<const float4*>(p.x + (int64_t)ra.nat * C + ct * 16 + 4 * g);
+                        rsv[mt] = rsp[p.rowscale ? ra.smp : 0];
+                    } else {
+                        const int m = min(m_base + mt * 16 + s, p.M - 1);
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) xrv[mt][ct] = *reinterpret_cast<const float4*>(p.x + (int64_t)m * C + ct * 16 + 4 * g);
+                        rsv[mt] = rsp[p.rowscale ? m / p.rps : 0];
+                    }
                 }
             }
             f32x4_t h[4][MT];
@@ -1006,7 +1086,7 @@ __global__ __launch_bounds__(512) void convmlp_fwd_res_kernel(const CmP p) {
         // epilogue: b2 / gamma come from LDS, the residual and the scale from the registers requested above
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const int m = min(m_base + mt * 16 + s, p.M - 1);
+            const int m = CP ? mnat[mt] : min(m_base + mt * 16 + s, Me - 1);
             const float rs = fmaf(rsv[mt] - 1.0f, rsf, 1.0f);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
@@ -1066,7 +1146,8 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
         }
     }
     const bool dyn = p.tile_slot >= 0;  // tile scheduling as in convmlp_fwd_res_kernel
-    const TileShare sh = tile_share((p.M + 16 * MT - 1) / (16 * MT));
+    const int Me = eff_rows(p);         // compact rows (CmP::perm): the tiles are counted from the rows that exist
+    const TileShare sh = tile_share((Me + 16 * MT - 1) / (16 * MT));
     unsigned* const ctr = &g_tile_ctr[dyn ? p.tile_slot : 0][sh.part][0];
     int drawn = dyn ? sched_draw_counted(ctr) : 0;
     dma_all_nmajor<NK>(w1img, p.w1, wave, lane);
@@ -1083,7 +1164,6 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
     // Software pipeline over this wave's tiles, no memory operation under a branch (see convmlp_fwd_res_kernel): the operands of tile
     // t + 1 are requested after tile t's hidden-chunk loop, BEFORE its epilogue stores, so their round trip runs under the epilogue's
     // arithmetic and the wait for them does not include those stores' acknowledgements.
-    const int ntile = (p.M + 16 * MT - 1) / (16 * MT);
     const float* rsp = p.rowscale ? p.rowscale : p.gamma;
     const float rsf = p.rowscale ? 1.0f : 0.0f;
     struct TileIn {
@@ -1095,17 +1175,19 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
     auto fetch_tile = [&](TileIn& t, int tile) __attribute__((always_inline)) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const int m = min(tile * (16 * MT) + mt * 16 + s, p.M - 1);
+            const int m = min(tile * (16 * MT) + mt * 16 + s, Me - 1);
+            const RowAt ra = row_at(p, m);
+            const int64_t mg = ra.nat;  // g (and z) by natural row; ln, dz, act, dh by the kernel's own
 #pragma unroll
             for (int ks = 0; ks < NK; ++ks) {
                 const int c = ks * 32 + 8 * g;
                 t.x[mt][ks] = ld16(p.ln + ((int64_t)m * C + c) * 2);
-                t.g0[mt][ks] = *reinterpret_cast<const float4*>(p.g + (int64_t)m * C + c);
-                t.g1[mt][ks] = *reinterpret_cast<const float4*>(p.g + (int64_t)m * C + c + 4);
-                if constexpr (DG) t.z[mt][ks] = ld16(p.zin + ((int64_t)m * C + c) * 2);
+                t.g0[mt][ks] = *reinterpret_cast<const float4*>(p.g + mg * C + c);
+                t.g1[mt][ks] = *reinterpret_cast<const float4*>(p.g + mg * C + c + 4);
+                if constexpr (DG) t.z[mt][ks] = ld16(p.zin + (mg * C + c) * 2);
             }
-            t.rs[mt] = rsp[p.rowscale ? m / p.rps : 0];
-            if constexpr (LNB) ln_bwd_fetch<NK>(t.lr[mt], p, m, g);
+            t.rs[mt] = rsp[p.rowscale ? ra.smp : 0];
+            if constexpr (LNB) ln_bwd_fetch<NK>(t.lr[mt], p, m, ra.nat, g);
         }
     };
     const int xbase = sh.base, xcnt = sh.cnt, xwaves = 8 * sh.workers;
@@ -1123,8 +1205,8 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             int m = m_base + mt * 16 + s;
-            const bool mv = m < p.M;
-            if (!mv) m = p.M - 1;  // redoes row M - 1, stores the same bytes as its live twin; masked out of the column sums only
+            const bool mv = m < Me;
+            if (!mv) m = Me - 1;  // redoes the last row, stores the same bytes as its live twin; masked out of the column sums only
             const float rs = fmaf(cur.rs[mt] - 1.0f, rsf, 1.0f);
             lrow[mt] = cur.lr[mt];
 #pragma unroll
@@ -1184,7 +1266,7 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
                 const uint4 pa0 = pack8(h[0][mt], h[1][mt]), pa1 = pack8(h[2][mt], h[3][mt]);
                 pd[mt][0] = pack8(da[0][mt], da[1][mt]);
                 pd[mt][1] = pack8(da[2][mt], da[3][mt]);
-                const int m = min(m_base + mt * 16 + s, p.M - 1);
+                const int m = min(m_base + mt * 16 + s, Me - 1);
                 if constexpr (ST) {
                     const int64_t off = ((int64_t)m * (4 * C) + 64 * j + 8 * g) * 2;
                     st16(p.act + off, pa0);
@@ -1205,19 +1287,19 @@ __global__ __launch_bounds__(512) void convmlp_bwd_res_kernel(const CmP p) {
         }
         fetch_tile(cur, next < xcnt ? xbase + next : tile);  // (the last tile fetches itself again: unconditional)
         if constexpr (LNB) {
-            ln_bwd_rows<NK, MT, 0>(p, dl, lrow[0], m_base + s, s, g, lws, dls);
-            if constexpr (MT == 2) ln_bwd_rows<NK, MT, 1>(p, dl, lrow[MT - 1], m_base + 16 + s, s, g, lws, dls);
+            ln_bwd_rows<NK, MT, 0>(p, dl, lrow[0], m_base + s, Me, s, g, lws, dls);
+            if constexpr (MT == 2) ln_bwd_rows<NK, MT, 1>(p, dl, lrow[MT - 1], m_base + 16 + s, Me, s, g, lws, dls);
         } else {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                const int m = min(m_base + mt * 16 + s, p.M - 1);
+                const int64_t m = row_at(p, min(m_base + mt * 16 + s, Me - 1)).nat;  // dln by natural row
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
                     const int c = ct * 16 + 4 * g;
                     uint2 v;
                     bf16_t* vh = reinterpret_cast<bf16_t*>(&v);
                     vh[0] = (bf16_t)dl[ct][mt][0]; vh[1] = (bf16_t)dl[ct][mt][1]; vh[2] = (bf16_t)dl[ct][mt][2]; vh[3] = (bf16_t)dl[ct][mt][3];
-                    *reinterpret_cast<uint2*>(p.dln + ((int64_t)m * C + c) * 2) = v;
+                    *reinterpret_cast<uint2*>(p.dln + (m * C + c) * 2) = v;
                 }
             }
         }
@@ -1447,6 +1529,9 @@ extern "C" int lnx_convmlp_fwd(const lnx_convmlp_args* a, void* stream) {
     p.b1 = a->b1; p.b2 = a->b2; p.gamma = a->gamma; p.rowscale = a->rowscale; p.x = a->x; p.out = a->out; p.z = (unsigned char*)a->z;
     p.M = a->M; p.C = a->C; p.rps = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
     p.y = (const unsigned char*)a->y; p.lnw = a->ln_w; p.lnb = a->ln_b; p.eps = a->ln_eps; p.ln_out = (unsigned char*)a->ln_out; p.mean = a->mean; p.rstd = a->rstd;
+    LNX_CHECK((a->perm == nullptr) == (a->m_dev == nullptr), "lnx_convmlp_fwd: perm and m_dev go together");
+    if (a->perm) LNX_CHECK(a->rows_per_sample > 0 && a->M % a->rows_per_sample == 0 && a->z == nullptr, "lnx_convmlp_fwd: compact rows need rows_per_sample | M and no z");
+    p.perm = a->perm; p.m_dev = a->m_dev;
     hipStream_t st = (hipStream_t)stream;
     switch (a->C) {
         case 32: launch_fwd_res<1>(p, st); break;
@@ -1476,6 +1561,9 @@ extern "C" int lnx_convmlp_bwd(const lnx_convmlp_bwd_args* a, void* stream) {
     p.act = (unsigned char*)a->act; p.dh = (unsigned char*)a->dh; p.dz = (unsigned char*)a->dz; p.dln = (unsigned char*)a->dln; p.dgamma = a->dgamma;
     p.M = a->M; p.C = a->C; p.rps = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
     p.dz_plain = a->dz_plain != 0;
+    LNX_CHECK((a->perm == nullptr) == (a->m_dev == nullptr), "lnx_convmlp_bwd: perm and m_dev go together");
+    if (a->perm) LNX_CHECK(a->rows_per_sample > 0 && a->M % a->rows_per_sample == 0 && a->z == nullptr, "lnx_convmlp_bwd: compact rows need rows_per_sample | M and no z");
+    p.perm = a->perm; p.m_dev = a->m_dev;
     hipStream_t st = (hipStream_t)stream;
     int rc = 0;
     switch (a->C) {

@@ -35,6 +35,8 @@ struct DwP {
     int flip;
     int tiles_h, tiles_w, cblocks;
     int tiles_per_wg;  // consecutive tiles (same channel block) one workgroup walks
+    const int* perm;   // DropPath compaction (lnx_dwconv7_fwd_kept) or NULL: the tile index then counts the kept samples,
+    const int* nkeep;  // sample j of the walk is perm[j]
 };
 
 template <typename TX> struct Raw4;  // 4 consecutive channels as loaded
@@ -62,6 +64,13 @@ __device__ __forceinline__ TilePos tile_pos(int t, int tiles_h, int tiles_w) {
     q.w0 = tw * TW;
     return q;
 }
+// ... through a compaction list (t < kept samples x tiles per sample, so the index is in range)
+__device__ __forceinline__ TilePos tile_pos(int t, int tiles_h, int tiles_w, const int* perm) {
+    TilePos q = tile_pos(t, tiles_h, tiles_w);
+    if (perm) q.b = perm[q.b];
+    return q;
+}
+__device__ __forceinline__ int kept_samples(const int* nkeep, int B) { return min(max(*nkeep, 0), B); }
 
 template <typename TX>
 __device__ __forceinline__ void halo_issue(typename Raw4<TX>::type (&pre)[NPRE], const TX* __restrict__ x, const TilePos& q, int c0, int H, int W, int C) {
@@ -106,7 +115,8 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const DwP p) {
     const int chunks = (ntile + p.tiles_per_wg - 1) / p.tiles_per_wg;
     const int cb = blockIdx.x / chunks;
     const int t_begin = (blockIdx.x % chunks) * p.tiles_per_wg;
-    const int t_end = min(ntile, t_begin + p.tiles_per_wg);
+    const int t_end = min(p.perm ? kept_samples(p.nkeep, p.B) * p.tiles_h * p.tiles_w : ntile, t_begin + p.tiles_per_wg);
+    if (t_begin >= t_end) return;  // (only with a list: the grid is sized for every sample) before any load
     const int c0 = cb * CB;
     const int cl = threadIdx.x & 31;
     const int r = threadIdx.x >> 5;
@@ -120,7 +130,7 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const DwP p) {
     const float bv = p.bias ? p.bias[c] : 0.f;
 
     typename Raw4<TX>::type pre[NPRE];
-    halo_issue<TX>(pre, xg, tile_pos(t_begin, p.tiles_h, p.tiles_w), c0, p.H, p.W, p.C);
+    halo_issue<TX>(pre, xg, tile_pos(t_begin, p.tiles_h, p.tiles_w, p.perm), c0, p.H, p.W, p.C);
     halo_commit<TX>(tile, pre);
     __syncthreads();
 
@@ -129,9 +139,9 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const DwP p) {
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
 #endif
     for (int t = t_begin; t < t_end; ++t) {
-        const TilePos q = tile_pos(t, p.tiles_h, p.tiles_w);
+        const TilePos q = tile_pos(t, p.tiles_h, p.tiles_w, p.perm);
         const bool more = t + 1 < t_end;
-        if (more) halo_issue<TX>(pre, xg, tile_pos(t + 1, p.tiles_h, p.tiles_w), c0, p.H, p.W, p.C);
+        if (more) halo_issue<TX>(pre, xg, tile_pos(t + 1, p.tiles_h, p.tiles_w, p.perm), c0, p.H, p.W, p.C);
         DW_T(0);
 
         float acc[TW];
@@ -196,6 +206,8 @@ struct DwWgP {
     int B, H, W, C;
     int tiles_h, tiles_w, cblocks, ntile;  // ntile = B * tiles_h * tiles_w
     float* part;  // deterministic mode: [walkers][49 C | C] partial sums instead of the atomics (folded by launch_fold); else NULL
+    const int* perm;   // DropPath compaction (lnx_dwconv7_wgrad_kept) or NULL
+    const int* nkeep;
 };
 
 template <typename TDY>
@@ -228,6 +240,7 @@ __global__ __launch_bounds__(256) void dwconv7_wgrad_kernel(const DwWgP p) {
     const int r = threadIdx.x >> 5;
     const TX* xg = reinterpret_cast<const TX*>(p.x);
     const TDY* dg = reinterpret_cast<const TDY*>(p.dy);
+    const int ntile = p.perm ? kept_samples(p.nkeep, p.B) * p.tiles_h * p.tiles_w : p.ntile;  // a walker left without tiles adds zeros
 
     float acc[49];
 #pragma unroll
@@ -236,8 +249,8 @@ __global__ __launch_bounds__(256) void dwconv7_wgrad_kernel(const DwWgP p) {
 
     typename Raw4<TX>::type pre[NPRE];
     typename Raw4<TDY>::type pdy[NDY];
-    if (walker < p.ntile) {
-        const TilePos q0 = tile_pos(walker, p.tiles_h, p.tiles_w);
+    if (walker < ntile) {
+        const TilePos q0 = tile_pos(walker, p.tiles_h, p.tiles_w, p.perm);
         halo_issue<TX>(pre, xg, q0, c0, p.H, p.W, p.C);
         dy_issue<TDY>(pdy, dg, q0, c0, p.H, p.W, p.C);
         halo_commit<TX>(tile, pre);
@@ -245,10 +258,10 @@ __global__ __launch_bounds__(256) void dwconv7_wgrad_kernel(const DwWgP p) {
         for (int k = 0; k < NDY; ++k) *reinterpret_cast<float4*>(dyt + 4 * (threadIdx.x + 256 * k)) = widen(pdy[k]);
     }
     __syncthreads();
-    for (int t = walker; t < p.ntile; t += nwalk) {
-        const bool more = t + nwalk < p.ntile;
+    for (int t = walker; t < ntile; t += nwalk) {
+        const bool more = t + nwalk < ntile;
         if (more) {
-            const TilePos qn = tile_pos(t + nwalk, p.tiles_h, p.tiles_w);
+            const TilePos qn = tile_pos(t + nwalk, p.tiles_h, p.tiles_w, p.perm);
             halo_issue<TX>(pre, xg, qn, c0, p.H, p.W, p.C);
             dy_issue<TDY>(pdy, dg, qn, c0, p.H, p.W, p.C);
         }
@@ -308,15 +321,19 @@ __global__ __launch_bounds__(256) void dwconv7_wgrad_kernel(const DwWgP p) {
 
 }  // namespace
 
-extern "C" int lnx_dwconv7_fwd(const lnx_dwconv_args* a, void* stream) {
+extern "C" int lnx_dwconv7_fwd(const lnx_dwconv_args* a, void* stream) { return lnx_dwconv7_fwd_kept(a, nullptr, nullptr, stream); }
+
+extern "C" int lnx_dwconv7_fwd_kept(const lnx_dwconv_args* a, const int* perm, const int* nkeep, void* stream) {
     LNX_CHECK(a && a->x && a->w49 && a->y, "lnx_dwconv7_fwd: null operand");
+    LNX_CHECK((perm == nullptr) == (nkeep == nullptr), "lnx_dwconv7_fwd_kept: perm and nkeep go together");
     LNX_CHECK(a->B > 0 && a->H > 0 && a->W > 0 && a->C > 0 && a->C % CB == 0, "lnx_dwconv7_fwd: bad shape B=%d H=%d W=%d C=%d (C %% 32)", a->B, a->H, a->W, a->C);
     // bf16 compute: the matrix-core kernels (dwconv_mfma.hip); fp32 (strict-parity mode) stays on the VALU kernels below
     if (lnx_dwconv_mfma_enabled() && (a->x_dtype == LNX_BF16 || a->y_dtype == LNX_BF16) && !(a->res && a->y_dtype != LNX_F32))
-        return lnx_dwconv7_mfma_fwd(a, (hipStream_t)stream);
+        return lnx_dwconv7_mfma_fwd(a, perm, nkeep, (hipStream_t)stream);
     DwP p;
     p.x = a->x; p.w49 = a->w49; p.bias = a->bias; p.res = a->res; p.y = a->y;
     p.B = a->B; p.H = a->H; p.W = a->W; p.C = a->C; p.flip = a->flip;
+    p.perm = perm; p.nkeep = nkeep;
     p.tiles_h = cdiv(a->H, TH); p.tiles_w = cdiv(a->W, TW); p.cblocks = a->C / CB;
     // each workgroup walks the tiles of (up to) one image; with fewer than ~3 workgroups per CU the
     // walk is shortened so the chip stays full
@@ -369,8 +386,11 @@ int lnx_dwconv7_wgrad_fold(const lnx_dwconv_wgrad_args* a, int walkers, hipStrea
     return 0;
 }
 
-extern "C" int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* a, void* stream) {
+extern "C" int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* a, void* stream) { return lnx_dwconv7_wgrad_kept(a, nullptr, nullptr, stream); }
+
+extern "C" int lnx_dwconv7_wgrad_kept(const lnx_dwconv_wgrad_args* a, const int* perm, const int* nkeep, void* stream) {
     LNX_CHECK(a && a->x && a->dy && a->dw, "lnx_dwconv7_wgrad: null operand");
+    LNX_CHECK((perm == nullptr) == (nkeep == nullptr), "lnx_dwconv7_wgrad_kept: perm and nkeep go together");
     LNX_CHECK(wgrad_shape_ok(a->B, a->H, a->W, a->C), "lnx_dwconv7_wgrad: bad shape");
     if (deterministic()) {
         const int64_t need = lnx_dwconv7_wgrad_ws_floats(a->B, a->H, a->W, a->C, a->x_dtype, a->dy_dtype);
@@ -380,10 +400,11 @@ extern "C" int lnx_dwconv7_wgrad(const lnx_dwconv_wgrad_args* a, void* stream) {
                   "lnx_dwconv7_wgrad: deterministic mode needs ws of lnx_dwconv7_wgrad_ws_floats(...) = %lld floats (got %lld): without it dw / db are summed by float atomics",
                   (long long)need, (long long)(a->ws ? a->ws_floats : 0));
     }
-    if (lnx_dwconv_mfma_enabled() && (a->x_dtype == LNX_BF16 || a->dy_dtype == LNX_BF16)) return lnx_dwconv7_mfma_wgrad(a, (hipStream_t)stream);
+    if (lnx_dwconv_mfma_enabled() && (a->x_dtype == LNX_BF16 || a->dy_dtype == LNX_BF16)) return lnx_dwconv7_mfma_wgrad(a, perm, nkeep, (hipStream_t)stream);
     DwWgP p;
     p.x = a->x; p.dy = a->dy; p.dw = a->dw; p.db = a->db;
     p.B = a->B; p.H = a->H; p.W = a->W; p.C = a->C;
+    p.perm = perm; p.nkeep = nkeep;
     p.tiles_h = cdiv(a->H, TH); p.tiles_w = cdiv(a->W, TW); p.cblocks = a->C / CB;
     p.ntile = a->B * p.tiles_h * p.tiles_w;
     const int walkers = wgrad_walkers(a->B, a->H, a->W, a->C);

@@ -209,7 +209,14 @@ struct MfP {
     void* y;
     int B, H, W, C;
     int tiles_h, tiles_w, tiles_per_wg, ntile, chunks;
+    const int* perm;   // DropPath compaction (lnx_dwconv7_fwd_kept) or NULL
+    const int* nkeep;
 };
+
+// With a list the kernels walk the tiles of the kept samples only: the tile index counts COMPACT samples, sample j of the walk is perm[j].
+// kept_samples(): read once at entry (uniform).  sample_at(): the cursor may stand one tile beyond the walk, so the index is clamped.
+__device__ __forceinline__ int kept_samples(const int* nkeep, int B) { return min(max(__builtin_amdgcn_readfirstlane(*nkeep), 0), B); }
+__device__ __forceinline__ int sample_at(const int* perm, int j, int B) { return perm ? __builtin_amdgcn_readfirstlane(perm[min(j, B - 1)]) : j; }
 
 struct TileAt {
     int b, h0, w0;
@@ -218,7 +225,9 @@ struct TileAt {
 // 16 waves each doing four per tile showed up as 15 % of the tile time)
 struct TileCursor {
     int b, h0, w0;
-    __device__ __forceinline__ void step(int H, int W, int th, int tw) {
+    int bs;  // with a list: the sample the tile lies in, perm[b] (sample())
+    __device__ __forceinline__ int sample(const int* perm) const { return perm ? bs : b; }
+    __device__ __forceinline__ void step(int H, int W, int th, int tw, const int* perm, int B) {
         w0 += tw;
         if (w0 >= W) {
             w0 = 0;
@@ -226,6 +235,7 @@ struct TileCursor {
             if (h0 >= H) {
                 h0 = 0;
                 ++b;
+                if (perm) bs = sample_at(perm, b, B);
             }
         }
     }
@@ -248,7 +258,9 @@ __device__ unsigned long long g_dwm_stamp[8];
 #define DWM_T(i) do { } while (0)
 #endif
 
-template <typename TX, typename TY, bool FLIP>
+// LIST: the walk goes through a compaction list (MfP::perm).  A variant of its own: the kernel lives at its register limit, and the
+// form without a list stays the code it was.
+template <typename TX, typename TY, bool FLIP, bool LIST>
 __global__ __launch_bounds__(FT) void dwconv7_mfma_kernel(const MfP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef Stage<TX, FT, FCB, MI, MI / 2, XPITCH, XPLANE> St;
@@ -256,8 +268,14 @@ __global__ __launch_bounds__(FT) void dwconv7_mfma_kernel(const MfP p) {
     char* xt = smem;
     char* ot = smem + X_BYTES;
     const int cb = blockIdx.x / p.chunks;
-    const int t_begin = (blockIdx.x % p.chunks) * p.tiles_per_wg;
-    const int t_end = min(p.ntile, t_begin + p.tiles_per_wg);
+    int ntile = p.ntile, per = p.tiles_per_wg;
+    if constexpr (LIST) {  // the kept samples' tiles, divided anew over the launch's workgroups
+        ntile = kept_samples(p.nkeep, p.B) * p.tiles_h * p.tiles_w;
+        per = (ntile + p.chunks - 1) / p.chunks;
+    }
+    const int t_begin = (blockIdx.x % p.chunks) * per;
+    const int t_end = min(ntile, t_begin + per);
+    const int* const perm = LIST ? p.perm : nullptr;
     const int c0 = cb * FCB;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = lane & 15, g = lane >> 4;
@@ -268,10 +286,10 @@ __global__ __launch_bounds__(FT) void dwconv7_mfma_kernel(const MfP p) {
     TileCursor cq, cq2;  // tiles t and t + 1
     {
         const TileAt q = tile_at(t_begin, p.tiles_h, p.tiles_w, MT, MT);
-        cq.b = q.b; cq.h0 = q.h0; cq.w0 = q.w0;
+        cq.b = q.b; cq.h0 = q.h0; cq.w0 = q.w0; cq.bs = sample_at(perm, q.b, p.B);
         cq2 = cq;
-        sa.issue(xg, cq2.b, cq2.h0 - 3, cq2.w0 - 3, p.H, p.W, p.C, true);
-        cq2.step(p.H, p.W, MT, MT);
+        sa.issue(xg, cq2.sample(perm), cq2.h0 - 3, cq2.w0 - 3, p.H, p.W, p.C, LIST ? t_begin < t_end : true);  // (a workgroup a list leaves without tiles fetches no pixel)
+        cq2.step(p.H, p.W, MT, MT, perm, p.B);
     }
     zero_lds<FT>(xt, X_BYTES);
     // taps of this channel block -> LDS (in the output-tile area), then the Toeplitz operands of this wave's channels:
@@ -329,7 +347,7 @@ __global__ __launch_bounds__(FT) void dwconv7_mfma_kernel(const MfP p) {
 #endif
     for (int t = t_begin; t < t_end; ++t) {
         const TileCursor q = cq;
-        const int64_t tile0 = (((int64_t)q.b * p.H + q.h0) * p.W + q.w0) * p.C + c0;
+        const int64_t tile0 = (((int64_t)q.sample(perm) * p.H + q.h0) * p.W + q.w0) * p.C + c0;
         u32 go[Ot::NPO];
         uint4 rv[Ot::NPO];
 #pragma unroll
@@ -343,9 +361,10 @@ __global__ __launch_bounds__(FT) void dwconv7_mfma_kernel(const MfP p) {
         }
         // the fetch of tile t + 1 is spread over the MFMA loop: issued in one burst, 16 waves x 4 loads queue up in
         // the texture-address unit and every wave sits in that queue before its first MFMA
-        const typename St::Tile ft = St::tile(xg, cq2.b, cq2.h0 - 3, cq2.w0 - 3, p.H, p.W, p.C, t + 1 < t_end);
-        cq.step(p.H, p.W, MT, MT);
-        cq2.step(p.H, p.W, MT, MT);
+        const typename St::Tile ft = St::tile(xg, cq2.sample(perm), cq2.h0 - 3, cq2.w0 - 3, p.H, p.W, p.C, t + 1 < t_end);
+        if constexpr (LIST) cq = cq2;  // (one step, and one read of the list, per tile)
+        else cq.step(p.H, p.W, MT, MT, perm, p.B);
+        cq2.step(p.H, p.W, MT, MT, perm, p.B);
         DWM_T(0);
 
         f32x4_t acc[CPW];
@@ -453,6 +472,8 @@ struct MwP {
     int B, H, W, C;
     int tiles_h, tiles_w, nwalk, per, ntile;  // walkers per 32-channel group, tiles per walker
     float* part;  // deterministic mode: [walkers][49 C | C] partial sums instead of the atomics (folded by launch_fold); else NULL
+    const int* perm;   // DropPath compaction (lnx_dwconv7_wgrad_kept) or NULL
+    const int* nkeep;
 };
 
 template <typename TX, typename TDY>
@@ -468,7 +489,12 @@ __global__ __launch_bounds__(WT, 4) void dwconv7_mfma_wgrad_kernel(const MwP p) 
     const int groups = p.C / (2 * WCB);
     if (pair >= p.nwalk * groups) return;  // grid padding
     const int walker = pair / groups;
-    const int t_begin = walker * p.per, t_end = min(p.ntile, t_begin + p.per);  // a contiguous run of tiles (row-major)
+    int ntile = p.ntile, per = p.per;
+    if (p.perm) {  // the kept samples' tiles, divided anew over the walkers (a walker left without tiles fetches nothing and adds zeros)
+        ntile = kept_samples(p.nkeep, p.B) * p.tiles_h * p.tiles_w;
+        per = (ntile + p.nwalk - 1) / p.nwalk;
+    }
+    const int t_begin = walker * per, t_end = min(ntile, t_begin + per);  // a contiguous run of tiles (row-major)
     const int c0 = (2 * (pair % groups) + half) * WCB;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = lane & 15, g = lane >> 4;
@@ -487,10 +513,10 @@ __global__ __launch_bounds__(WT, 4) void dwconv7_mfma_wgrad_kernel(const MwP p) 
     TileCursor cq;  // the tile being fetched
     {
         const TileAt q = tile_at(t_begin, p.tiles_h, p.tiles_w, WH, WW);
-        cq.b = q.b; cq.h0 = q.h0; cq.w0 = q.w0;
-        sx.issue(xg, q.b, q.h0 - 3, q.w0 - 3, p.H, p.W, p.C, t_begin < t_end);
-        sd.issue(dg, q.b, q.h0, q.w0, p.H, p.W, p.C, t_begin < t_end);
-        cq.step(p.H, p.W, WH, WW);
+        cq.b = q.b; cq.h0 = q.h0; cq.w0 = q.w0; cq.bs = sample_at(p.perm, q.b, p.B);
+        sx.issue(xg, cq.sample(p.perm), q.h0 - 3, q.w0 - 3, p.H, p.W, p.C, t_begin < t_end);
+        sd.issue(dg, cq.sample(p.perm), q.h0, q.w0, p.H, p.W, p.C, t_begin < t_end);
+        cq.step(p.H, p.W, WH, WW, p.perm, p.B);
     }
     zero_lds<WT>(smem, WX_BYTES + WD_BYTES);
     if (threadIdx.x < WCB) dbl[threadIdx.x] = 0.f;
@@ -514,9 +540,9 @@ __global__ __launch_bounds__(WT, 4) void dwconv7_mfma_wgrad_kernel(const MwP p) 
         const bool more = t + 1 < t_end;
         // the next tile's fetches are spread over the MFMA loop (one every other input row); operands are read one row
         // ahead of their MFMA, the fences keep that order
-        const typename Sx::Tile tx = Sx::tile(xg, cq.b, cq.h0 - 3, cq.w0 - 3, p.H, p.W, p.C, more);
-        const typename Sd::Tile td = Sd::tile(dg, cq.b, cq.h0, cq.w0, p.H, p.W, p.C, more);
-        cq.step(p.H, p.W, WH, WW);
+        const typename Sx::Tile tx = Sx::tile(xg, cq.sample(p.perm), cq.h0 - 3, cq.w0 - 3, p.H, p.W, p.C, more);
+        const typename Sd::Tile td = Sd::tile(dg, cq.sample(p.perm), cq.h0, cq.w0, p.H, p.W, p.C, more);
+        cq.step(p.H, p.W, WH, WW, p.perm, p.B);
         u32 da[2][5];
         uint4 bq[2];
         auto operands = [&](int r) {
@@ -597,15 +623,18 @@ template <typename K> int set_lds(K kernel, int bytes) {
     return 0;
 }
 
-template <typename TX, typename TY, bool FLIP> int launch_fwd(const MfP& p, int grid, hipStream_t st) {
+template <typename TX, typename TY, bool FLIP, bool LIST> int launch_fwd_t(const MfP& p, int grid, hipStream_t st) {
     const int lds = X_BYTES + OutT<TY>::BYTES;
     static bool ready = false;  // one attribute call per instantiation
     if (!ready) {
-        if (int rc = set_lds(dwconv7_mfma_kernel<TX, TY, FLIP>, lds)) return rc;
+        if (int rc = set_lds(dwconv7_mfma_kernel<TX, TY, FLIP, LIST>, lds)) return rc;
         ready = true;
     }
-    hipLaunchKernelGGL((dwconv7_mfma_kernel<TX, TY, FLIP>), dim3(grid), dim3(FT), lds, st, p);
+    hipLaunchKernelGGL((dwconv7_mfma_kernel<TX, TY, FLIP, LIST>), dim3(grid), dim3(FT), lds, st, p);
     return 0;
+}
+template <typename TX, typename TY, bool FLIP> int launch_fwd(const MfP& p, int grid, hipStream_t st) {
+    return p.perm ? launch_fwd_t<TX, TY, FLIP, true>(p, grid, st) : launch_fwd_t<TX, TY, FLIP, false>(p, grid, st);
 }
 
 template <typename TX, typename TDY> int launch_wgrad(const MwP& p, int grid, hipStream_t st) {
@@ -635,10 +664,11 @@ bool lnx_dwconv_mfma_enabled() {
     return on;
 }
 
-int lnx_dwconv7_mfma_fwd(const lnx_dwconv_args* a, hipStream_t st) {
+int lnx_dwconv7_mfma_fwd(const lnx_dwconv_args* a, const int* perm, const int* nkeep, hipStream_t st) {
     MfP p;
     p.x = a->x; p.w49 = a->w49; p.bias = a->bias; p.res = a->res; p.y = a->y;
     p.B = a->B; p.H = a->H; p.W = a->W; p.C = a->C;
+    p.perm = perm; p.nkeep = nkeep;
     const int code = a->x_dtype * 2 + a->y_dtype + (a->flip ? 4 : 0);
     p.tiles_h = cdiv(a->H, MT); p.tiles_w = cdiv(a->W, MT);
     const int64_t ntile = (int64_t)a->B * p.tiles_h * p.tiles_w;
@@ -680,10 +710,11 @@ int lnx_dwconv7_mfma_wgrad_walkers(int B, int H, int W, int C) {
     return cdiv((int)ntile, per);  // same longest walk, no idle walkers
 }
 
-int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, hipStream_t st) {
+int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, const int* perm, const int* nkeep, hipStream_t st) {
     MwP p;
     p.x = a->x; p.dy = a->dy; p.dw = a->dw; p.db = a->db;
     p.B = a->B; p.H = a->H; p.W = a->W; p.C = a->C;
+    p.perm = perm; p.nkeep = nkeep;
     p.tiles_h = cdiv(a->H, WH); p.tiles_w = cdiv(a->W, WW);
     const int64_t ntile = (int64_t)a->B * p.tiles_h * p.tiles_w;
     LNX_CHECK(ntile < (1ll << 31), "lnx_dwconv7_wgrad: too many tiles");

@@ -5,8 +5,9 @@
 #include "../../include/lnx.h"
 
 bool lnx_dwconv_mfma_enabled();
-int lnx_dwconv7_mfma_fwd(const lnx_dwconv_args* a, hipStream_t st);
-int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, hipStream_t st);
+// perm / nkeep: the list of lnx_dwconv7_fwd_kept / lnx_dwconv7_wgrad_kept, or NULL
+int lnx_dwconv7_mfma_fwd(const lnx_dwconv_args* a, const int* perm, const int* nkeep, hipStream_t st);
+int lnx_dwconv7_mfma_wgrad(const lnx_dwconv_wgrad_args* a, const int* perm, const int* nkeep, hipStream_t st);
 int lnx_dwconv7_mfma_wgrad_walkers(int B, int H, int W, int C);  // workgroups per 16-channel block of that launch
 // dwconv.hip: deterministic mode, after either weight-gradient kernel -- the walkers' partial sums in a->ws -> dw, db in walker order
 int lnx_dwconv7_wgrad_fold(const lnx_dwconv_wgrad_args* a, int walkers, hipStream_t st);

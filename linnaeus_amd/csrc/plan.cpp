@@ -201,6 +201,7 @@ struct lnx_plan {
     // workspace keeps its size.
     int* droplists = nullptr;
     bool compact_now = false;
+    bool compact_conv_now = false;  // ... and the conv blocks' calls are among them (LNX_DROP_COMPACT_CONV)
     const int* drop_list(int call) const {
         if (!compact_now || droplists == nullptr || drop_ptr(call) == nullptr) return nullptr;
         return droplists + (int64_t)call * LNX_DROP_LIST_INTS(c.batch);
@@ -215,6 +216,8 @@ extern "C" int lnx_set_drop_compact(int on) {
     return was;
 }
 extern "C" int64_t lnx_drop_compact_branches(void) { return (int64_t)g_compact_branches.load(std::memory_order_relaxed); }
+static std::atomic<long long> g_compact_conv_blocks{0};
+extern "C" int64_t lnx_drop_compact_conv_blocks(void) { return (int64_t)g_compact_conv_blocks.load(std::memory_order_relaxed); }
 
 namespace {
 
@@ -1135,8 +1138,9 @@ int wgrad(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, const
     return wgrad_to(c, M, N, K, dY, lddy, A, lda, c.p->G[wparam], bparam >= 0 ? c.p->G[bparam] : nullptr, lddw, k_store, slot, m_dev);
 }
 // ... into explicit buffers (the z-free LayerScale path's scratch)
-int wgrad_into(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, const void* A, int64_t lda, float* dW, float* db, int64_t lddw, int slot) {
-    return wgrad_to(c, M, N, K, dY, lddy, A, lda, dW, db, lddw, 0, slot);
+int wgrad_into(const Ctx& c, int M, int N, int K, const void* dY, int64_t lddy, const void* A, int64_t lda, float* dW, float* db, int64_t lddw, int slot,
+               const int* m_dev = nullptr) {
+    return wgrad_to(c, M, N, K, dY, lddy, A, lda, dW, db, lddw, 0, slot, m_dev);
 }
 
 const lnx_rowmap IDM = {0, 0, 0};
@@ -1182,6 +1186,19 @@ int linear_dgrad(const Ctx& c, lnx_gemm_args g, const OpW& w, bool quantise, int
 }
 
 // ------------------------------ forward pieces ------------------------------
+// The compaction list of a conv block's DropPath call, or none: the forward built it (training plan, both switches on, the call has a
+// multiplier, no dropout masks) and the block runs fused with the LayerNorm inside.  The conv-MLP kernels and the two pointwise
+// weight-gradient products then run on the kept samples' rows (compact: ln / mean / rstd, act, dh, dz); the depthwise kernels walk
+// the kept samples of y / dy (natural order) only.
+Compact conv_compact_of(const lnx_plan* p, int s, int i) {
+    Compact cl;
+    const ConvBlk& k = p->conv[s][i];
+    const int* list = p->compact_conv_now && k.fused && k.fused_ln ? p->drop_list(p->drop_conv[s][i]) : nullptr;
+    if (list == nullptr) return cl;
+    cl.nkeep = list; cl.m_dev = list + 1; cl.perm = list + 2; cl.inv = list + 2 + p->c.batch; cl.rps = p->H[s] * p->W[s];
+    return cl;
+}
+
 int conv_block_fwd(const Ctx& c, int s, int i, float* xout) {
     lnx_plan* p = c.p;
     ConvBlk& k = p->conv[s][i];
@@ -1195,9 +1212,10 @@ int conv_block_fwd(const Ctx& c, int s, int i, float* xout) {
     d.x = c.at<float>(k.xin); d.x_dtype = LNX_F32;
     d.w49 = c.at<float>(k.w49); d.bias = p->P[k.dwb];
     d.y = c.at<void>(k.y); d.y_dtype = c.dt;
+    const Compact cl = conv_compact_of(p, s, i);  // y of the dropped samples is then neither written here nor read by the conv-MLP kernel
     {
         Timed t(c, 4, (double)M * C * (4 + p->esz));  // bytes: read fp32 x, write T y
-        RUN(lnx_dwconv7_fwd(&d, c.st));
+        RUN(lnx_dwconv7_fwd_kept(&d, cl.perm, cl.nkeep, c.st));
     }
     if (!k.fused_ln)
         RUN(ln_fwd(c, M, C, 1e-6f, c.at<void>(k.y), c.dt, C, IDM, k.lnw, k.lnb, c.at<void>(k.ln), c.dt, C, IDM, nullptr, 0, c.at<float>(k.mean), c.at<float>(k.rstd)));
@@ -1216,6 +1234,8 @@ int conv_block_fwd(const Ctx& c, int s, int i, float* xout) {
         f.w1 = c.wptr(k.w1); f.b1 = p->P[k.b1]; f.w2 = c.wptr(k.w2); f.b2 = p->P[k.b2];
         f.gamma = p->P[k.gamma]; f.rowscale = p->drop_ptr(p->drop_conv[s][i]); f.rows_per_sample = H * W;
         f.x = c.at<float>(k.xin); f.out = xout;
+        f.perm = cl.perm; f.m_dev = cl.m_dev;  // (the kernel copies the dropped samples' rows itself)
+        if (cl) g_compact_conv_blocks.fetch_add(1, std::memory_order_relaxed);
         Timed t(c, 6, 2.0 * M * C * 4 * C * 2);
         RUN(lnx_convmlp_fwd(&f, c.st));
         return 0;
@@ -1463,16 +1483,28 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
                         RUN(lnx_quantize_mxfp8(c.wtptr(*w), LNX_BF16, w->ld_t, w->K, w->N, c.at<void>(w->off8t), w->N, c.at<void>(w->off8ts), stream));
             }
 
-    // DropPath compaction lists of the RoPE blocks' drop calls of this forward, one launch (the multipliers are drawn on the device:
-    // no host synchronisation).  LNX_DROP_COMPACT=0 / lnx_set_drop_compact(0): every branch on full rows, as before.
+    // DropPath compaction lists of the RoPE blocks' and the fused conv blocks' drop calls of this forward, one launch (the multipliers are
+    // drawn on the device: no host synchronisation).  LNX_DROP_COMPACT=0 / lnx_set_drop_compact(0): every branch on full rows, as before;
+    // LNX_DROP_COMPACT_CONV=0: the conv blocks alone.
     p->compact_now = false;
+    p->compact_conv_now = false;
     {
         const int sw = g_drop_compact.load(std::memory_order_relaxed);
         const bool on = sw < 0 ? !env_off("LNX_DROP_COMPACT") : sw != 0;
         if (on && !cf.inference && p->n_drop > 0 && drop_scales && !p->dmask && !p->amask) {
             std::vector<unsigned char> want(p->n_drop, 0);
             std::vector<int> rps(p->n_drop, 1);
-            bool any = false;
+            bool any = false, any_conv = false;
+            if (!env_off("LNX_DROP_COMPACT_CONV"))  // the conv blocks that run fused with the LayerNorm inside (conv_compact_of)
+                for (int s = 0; s < 2; ++s)
+                    for (size_t i = 0; i < p->conv[s].size(); ++i) {
+                        const int call = p->drop_conv[s][i];
+                        if (p->mask_host[call] && p->conv[s][i].fused && p->conv[s][i].fused_ln) {
+                            want[call] = 1;
+                            rps[call] = p->H[s] * p->W[s];
+                            any = any_conv = true;
+                        }
+                    }
             for (int s = 0; s < 2; ++s)
                 for (size_t i = 0; i < p->rope[s].size(); ++i)
                     for (const int call : {p->drop_attn[s][i], p->drop_mlp[s][i]})
@@ -1485,6 +1517,7 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
                 if (p->droplists == nullptr) HIPRUN(hipMalloc((void**)&p->droplists, (size_t)p->n_drop * LNX_DROP_LIST_INTS(B) * sizeof(int)));
                 RUN(lnx_drop_partition(drop_scales, p->n_drop, B, want.data(), rps.data(), p->droplists, stream));
                 p->compact_now = true;
+                p->compact_conv_now = any_conv;
             }
         }
     }
@@ -1767,6 +1800,8 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
     void* sD = c.at<void>(p->o_sD);
     Timed span(c, 9, 4.0 * M * C * (8.0 * C + 49.0));
     bool forked = false, joined = false;  // (only a block that forked work onto the weight-gradient stream waits for it)
+    // the forward's list: sA / sB / sC then hold compact rows; sD keeps natural order, and the depthwise gradients skip the dropped samples
+    const Compact cl = conv_compact_of(p, s, i);
     if (k.fused) {
         void* sB = c.at<void>(p->o_sB);
         lnx_convmlp_bwd_args f;
@@ -1777,6 +1812,7 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
         f.rowscale = p->drop_ptr(p->drop_conv[s][i]); f.rows_per_sample = H * W;
         f.act = sB; f.dh = sA; f.dz = sC; f.dln = sD; f.dgamma = p->G[k.gamma];
         f.dz_plain = 1;  // sC = rs g for the pwconv2 weight gradient, which then goes through lnx_layerscale_apply_wgrad
+        f.perm = cl.perm; f.m_dev = cl.m_dev;
         if (k.fused_ln) {  // sD then holds the gradient wrt the depthwise conv output
             f.y = c.at<void>(k.y); f.ln_w = p->P[k.lnw]; f.mean = c.at<float>(k.mean); f.rstd = c.at<float>(k.rstd);
             f.d_ln_w = p->G[k.lnw]; f.d_ln_b = p->G[k.lnb];
@@ -1798,8 +1834,8 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
         float* S = c.at<float>(p->o_lsws);
         float* T = S + (int64_t)C * 4 * C;
         HIPRUN(hipMemsetAsync(S, 0, ((size_t)C * 4 * C + C) * 4, (hipStream_t)cw.st));
-        RUN(wgrad_into(cw, M, C, 4 * C, sC, C, sB, 4 * C, S, T, 4 * C, 0));
-        RUN(wgrad(cw, M, 4 * C, C, sA, 4 * C, c.at<void>(k.ln), C, k.w1.param, k.b1, C, 0, 1));
+        RUN(wgrad_into(cw, M, C, 4 * C, sC, C, sB, 4 * C, S, T, 4 * C, 0, cl.m_dev));
+        RUN(wgrad(cw, M, 4 * C, C, sA, 4 * C, c.at<void>(k.ln), C, k.w1.param, k.b1, C, 0, 1, cl.m_dev));
         RUN(lnx_gemm_tn_flush(cw.st));
         RUN(lnx_layerscale_apply_wgrad(S, T, 4 * C, p->P[k.w2.param], p->P[k.b2], 4 * C, p->P[k.gamma], p->G[k.w2.param], p->G[k.b2], 4 * C, p->G[k.gamma], C, 4 * C, cw.st));
         RUN(wg_done(c, 0));
@@ -1833,7 +1869,7 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
     }
     {
         Timed t(c, 5, (double)M * C * (4 + p->esz));
-        RUN(lnx_dwconv7_wgrad(&w, c.st));
+        RUN(lnx_dwconv7_wgrad_kept(&w, cl.perm, cl.nkeep, c.st));
     }
     lnx_dwconv_args d;
     memset(&d, 0, sizeof d);
@@ -1841,7 +1877,7 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
     d.x = dy; d.x_dtype = c.dt; d.w49 = c.at<float>(k.w49); d.bias = nullptr; d.flip = 1; d.res = g; d.y = g; d.y_dtype = LNX_F32;
     {
         Timed t(c, 4, (double)M * C * (8 + p->esz));  // bytes: read T dy + fp32 g, write fp32 g
-        RUN(lnx_dwconv7_fwd(&d, c.st));
+        RUN(lnx_dwconv7_fwd_kept(&d, cl.perm, cl.nkeep, c.st));  // g of a dropped sample passes through unchanged
     }
     if (forked && !joined) RUN(wg_join(c, 0));  // the next block's kernels overwrite sA / sB / sC, and this block's gradients count as written from here on
     return 0;

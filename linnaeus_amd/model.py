@@ -360,6 +360,11 @@ class mFormerV1(nn.Module):
         """RoPE-block branches whose forward ran on compact rows since the library was loaded (lnx_drop_compact_branches)."""
         return int(L.lib().lnx_drop_compact_branches())
 
+    @staticmethod
+    def drop_compact_conv_blocks() -> int:
+        """Conv blocks whose forward ran on compact rows since the library was loaded (lnx_drop_compact_conv_blocks)."""
+        return int(L.lib().lnx_drop_compact_conv_blocks())
+
     def set_wgrad_stream(self, on: bool) -> None:
         """Backward scheduling of this model's native plans, present and future (include/lnx.h lnx_plan_set_wgrad_stream): True (the
         default) runs the weight-gradient products on a second HIP stream beside the data-gradient chain, False keeps everything on the

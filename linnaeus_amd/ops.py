@@ -259,17 +259,21 @@ def layernorm_bwd_flush():
     L.check(L.lib().lnx_layernorm_bwd_flush(_stream()), "lnx_layernorm_bwd_flush")
 
 
-def dwconv7(x, w49, bias, y, *, flip=False, res=None):
+def dwconv7(x, w49, bias, y, *, flip=False, res=None, perm=None, nkeep=None):
+    """`perm` / `nkeep` (int32 device tensors of a lnx_drop_partition list): the kept samples only, include/lnx.h lnx_dwconv7_fwd_kept."""
     B, H, W, Cc = x.shape
     a = L.DwconvArgs()
     a.B, a.H, a.W, a.C = B, H, W, Cc
     a.x, a.x_dtype, a.w49, a.bias = _p(x), code_of(x), _p(w49), _p(bias)
     a.flip, a.res, a.y, a.y_dtype = int(flip), _p(res), _p(y), code_of(y)
+    if perm is not None:
+        L.check(L.lib().lnx_dwconv7_fwd_kept(C.byref(a), _p(perm), _p(nkeep), _stream()), "lnx_dwconv7_fwd_kept")
+        return y
     L.check(L.lib().lnx_dwconv7_fwd(C.byref(a), _stream()), "lnx_dwconv7_fwd")
     return y
 
 
-def dwconv7_wgrad(x, dy, dw, db):
+def dwconv7_wgrad(x, dy, dw, db, *, perm=None, nkeep=None):
     B, H, W, Cc = x.shape
     a = L.DwconvWgradArgs()
     a.B, a.H, a.W, a.C = B, H, W, Cc
@@ -277,6 +281,9 @@ def dwconv7_wgrad(x, dy, dw, db):
     if L.is_deterministic():  # the walkers' partial sums, folded in walker order (the launcher says how many floats)
         ws = torch.empty(max(dwconv7_wgrad_ws_floats(B, H, W, Cc, a.x_dtype, a.dy_dtype), 1), device=x.device, dtype=torch.float32)
         a.ws, a.ws_floats = _p(ws), ws.numel()
+    if perm is not None:
+        L.check(L.lib().lnx_dwconv7_wgrad_kept(C.byref(a), _p(perm), _p(nkeep), _stream()), "lnx_dwconv7_wgrad_kept")
+        return
     L.check(L.lib().lnx_dwconv7_wgrad(C.byref(a), _stream()), "lnx_dwconv7_wgrad")
 
 
@@ -470,14 +477,16 @@ def pack_meta(meta, off, dim, out):
 
 
 def convmlp_fwd(ln, w1, b1, w2, b2, gamma, x, out, *, rowscale=None, rows_per_sample=0, z=None, y=None, ln_w=None, ln_b=None, ln_eps=1e-6,
-                ln_out=None, mean=None, rstd=None):
-    """`y` given (and `ln` None): the kernel applies the block LayerNorm (ln_w, ln_b, ln_eps) to y itself and writes ln_out / mean / rstd."""
+                ln_out=None, mean=None, rstd=None, perm=None, m_dev=None):
+    """`y` given (and `ln` None): the kernel applies the block LayerNorm (ln_w, ln_b, ln_eps) to y itself and writes ln_out / mean / rstd.
+    `perm` / `m_dev` (int32 device tensors of a lnx_drop_partition list): compact rows, include/lnx.h lnx_convmlp_args."""
     a = L.ConvMlpArgs()
     src = ln if y is None else y
     a.dtype, a.M, a.C = code_of(src), src.shape[0], src.shape[1]
     a.ln, a.w1, a.b1, a.w2, a.b2, a.gamma = _p(ln), _p(w1), _p(b1), _p(w2), _p(b2), _p(gamma)
     a.rowscale, a.rows_per_sample, a.x, a.out, a.z = _p(rowscale), rows_per_sample, _p(x), _p(out), _p(z)
     a.y, a.ln_w, a.ln_b, a.ln_eps, a.ln_out, a.mean, a.rstd = _p(y), _p(ln_w), _p(ln_b), ln_eps, _p(ln_out), _p(mean), _p(rstd)
+    a.perm, a.m_dev = _p(perm), _p(m_dev)
     L.check(L.lib().lnx_convmlp_fwd(C.byref(a), _stream()), "lnx_convmlp_fwd")
     return out
 
@@ -490,7 +499,7 @@ def layerscale_apply_wgrad(s, t, w, b, gamma, dw, db, dgamma):
 
 
 def convmlp_bwd(g, ln, z, w1, b1, w2t, w1t, gamma, act, dh, dz, dln, dgamma, *, rowscale=None, rows_per_sample=0, y=None, ln_w=None, mean=None,
-                rstd=None, d_ln_w=None, d_ln_b=None, ws=None, dz_plain=False):
+                rstd=None, d_ln_w=None, d_ln_b=None, ws=None, dz_plain=False, ln_defer=False, perm=None, m_dev=None):
     """`y` given: the LayerNorm backward runs in the kernel too -- `dln` receives the gradient wrt y, d_ln_w / d_ln_b are accumulated."""
     a = L.ConvMlpBwdArgs()
     a.dtype, a.M, a.C = code_of(ln), ln.shape[0], ln.shape[1]
@@ -499,7 +508,8 @@ def convmlp_bwd(g, ln, z, w1, b1, w2t, w1t, gamma, act, dh, dz, dln, dgamma, *, 
     a.act, a.dh, a.dz, a.dln, a.dgamma = _p(act), _p(dh), _p(dz), _p(dln), _p(dgamma)
     a.y, a.ln_w, a.mean, a.rstd, a.d_ln_w, a.d_ln_b = _p(y), _p(ln_w), _p(mean), _p(rstd), _p(d_ln_w), _p(d_ln_b)
     a.ws, a.ws_floats = _p(ws), (ws.numel() if ws is not None else 0)
-    a.dz_plain = int(dz_plain)
+    a.dz_plain, a.ln_defer = int(dz_plain), int(ln_defer)
+    a.perm, a.m_dev = _p(perm), _p(m_dev)
     L.check(L.lib().lnx_convmlp_bwd(C.byref(a), _stream()), "lnx_convmlp_bwd")
 
 
