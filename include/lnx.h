@@ -1468,6 +1468,41 @@ int lnx_plan_set_meta_stream(lnx_plan* p, int mode);
  * segment 1 and the stage-3 heads segment 2 (a caller that stops early must run the following segment, or -1, to join). */
 int lnx_plan_segment_params(const lnx_plan* p, int segment, int* idx_out, int max_out);
 
+/* Fine-tuning: a frozen prefix (lnx_version 112).  The reference freezes parameters by requires_grad (its parameter filters,
+ * rl_train_abstention.py:368-403); autograd then neither saves activations for, nor differentiates, what lies before the first
+ * trainable parameter.  A plan does the same at the granularity of UNITS, a fixed list in forward order:
+ *     stem | stages.0.<i> | downsample_layers.0 | stages.1.<i> | downsample_layers.1 | tokens_1 | stages.2.<i> | mid | tokens_2 |
+ *     stages.3.<i> | tail | heads
+ * tokens_k = cls_token_k and every metadata head of RoPE stage k; mid = norm_1, cl_1_fc, downsample_layers.2; tail = norm_2, aggregate,
+ * final_norm; heads = every head.<t>.  Every plan parameter belongs to exactly one unit.
+ *   lnx_plan_num_units / lnx_plan_unit_name(u) / lnx_plan_param_unit(i)   the list, and the unit of parameter i
+ *   lnx_plan_set_trainable(mask)   mask[i] != 0: parameter i (plan order, lnx_plan_num_params bytes) trains.  The CUT is the first unit
+ *       that holds a trainable parameter.  Legal only between lnx_plan_create and lnx_plan_bind (it changes lnx_plan_workspace_bytes);
+ *       refused by name on an inference plan, after the bind, with a NULL mask and with an all-zero mask (that is an inference plan).
+ *       Not calling it, or a mask whose cut is the stem (all ones), is the plan as created: same workspace bytes, same launches, same bits.
+ *   lnx_plan_first_trained_unit    the cut (0 when nothing is frozen)
+ *   lnx_plan_last_backward_units   units the last lnx_plan_backward (segment -1, or the segments 0..3 summed) / lnx_plan_backward_into ran
+ * With a cut at unit u:
+ *   forward   every unit runs the kernels it always runs -- DropPath, dropout masks and the fp8 mode apply to frozen units as to any other,
+ *             and logits / feats are bit-equal to the uncut plan's -- but the blocks before u write one shared set of activation buffers
+ *             per stage and a ping-pong pair of fp32 stream buffers (as the blocks of an inference plan do), so nothing of theirs is kept.
+ *             Units from u on keep their activations (or recompute them, cfg.recompute).
+ *   backward  runs heads, tail, ... down to u inclusive and stops: no kernel of a unit before u is launched on any stream, no gradient
+ *             slice of a parameter of such a unit is written or read (the pointers must still be valid addresses at the bind).  heads as
+ *             the cut: the heads' weight and bias gradients only (dfeats is ignored, no final_norm backward).  At the cut unit a launch
+ *             that only produces the unit's input gradient is skipped where it is a launch of its own (a conv block's depthwise data
+ *             gradient); input gradients that fall out of a fused launch (a LayerNorm backward's dx) are still written, to scratch.
+ *             A segment whose units all lie before u launches nothing and returns 0; it may still be called, in order, and the joins of
+ *             what an earlier segment forked still happen in it.  lnx_plan_segment_params is unchanged.
+ *   frozen parameters at or behind the cut: their gradient slices are unspecified after a backward (the fused launches write them).
+ * LNX_FROZEN_PREFIX=0 in the environment, read by lnx_plan_create: lnx_plan_set_trainable checks and then ignores its mask (the A/B switch). */
+int lnx_plan_num_units(const lnx_plan* p);
+const char* lnx_plan_unit_name(const lnx_plan* p, int u);
+int lnx_plan_param_unit(const lnx_plan* p, int i);
+int lnx_plan_set_trainable(lnx_plan* p, const unsigned char* mask /* [lnx_plan_num_params] */);
+int lnx_plan_first_trained_unit(const lnx_plan* p);
+int lnx_plan_last_backward_units(const lnx_plan* p);
+
 #ifdef __cplusplus
 }
 #endif

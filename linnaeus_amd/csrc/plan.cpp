@@ -101,6 +101,16 @@ struct lnx_plan {
     std::vector<std::string> names;
     std::vector<int64_t> numel;
     std::vector<signed char> seg;  // the backward segment (0-3) after which the parameter's gradient is final
+    // Units: the model in forward order -- stem, conv blocks, downsample 1, conv blocks, downsample 2, tokens_1, RoPE blocks, mid,
+    // tokens_2, RoPE blocks, tail, heads.  `cut` is the first unit that holds a trainable parameter (lnx_plan_set_trainable; 0 = everything
+    // trains): the units before it run forward-only on shared activation buffers and the backward stops behind unit `cut`.
+    std::vector<std::string> unit_names;
+    std::vector<int> unit_of;  // unit of each parameter
+    int u_conv[2] = {0, 0}, u_down[2] = {0, 0}, u_tok[2] = {0, 0}, u_rope[2] = {0, 0}, u_mid = 0, u_tail = 0, u_heads = 0;
+    int cut = 0;
+    bool frozen_prefix = true;  // LNX_FROZEN_PREFIX=0 (read at creation): lnx_plan_set_trainable accepts and ignores its mask (A/B switch)
+    int bwd_units = 0;          // units the last backward ran (lnx_plan_last_backward_units)
+    bool runs(int unit) const { return unit >= cut; }  // the backward runs this unit
     std::vector<const float*> P;
     std::vector<float*> G;
     bool bound = false, has_grads = false, fwd_done = false;
@@ -377,6 +387,56 @@ void build_params(lnx_plan* p) {
     }
 }
 
+// The unit list in forward order and the unit of every parameter, by name: "stem", "stages.<s>.<i>", "downsample_layers.0|1", "tokens_1|2"
+// (cls_token_k and every metadata head of stage k), "mid" (norm_1, cl_1_fc, downsample_layers.2), "tail" (norm_2, aggregate, final_norm),
+// "heads".  Returns false on a parameter name it cannot place (a parameter added to build_params without a unit).
+bool build_units(lnx_plan* p) {
+    const lnx_mformer_cfg& c = p->c;
+    char b[64];
+    auto unit = [&](const std::string& name) {
+        p->unit_names.push_back(name);
+        return (int)p->unit_names.size() - 1;
+    };
+    auto blocks = [&](int stage, int depth) {
+        const int first = (int)p->unit_names.size();
+        for (int i = 0; i < depth; ++i) {
+            snprintf(b, sizeof b, "stages.%d.%d", stage, i);
+            unit(b);
+        }
+        return first;
+    };
+    unit("stem");
+    for (int s = 0; s < 2; ++s) {
+        p->u_conv[s] = blocks(s, c.conv_depths[s]);
+        snprintf(b, sizeof b, "downsample_layers.%d", s);
+        p->u_down[s] = unit(b);
+    }
+    p->u_tok[0] = unit("tokens_1");
+    p->u_rope[0] = blocks(2, c.rope_depths[0]);
+    p->u_mid = unit("mid");
+    p->u_tok[1] = unit("tokens_2");
+    p->u_rope[1] = blocks(3, c.rope_depths[1]);
+    p->u_tail = unit("tail");
+    p->u_heads = unit("heads");
+    auto starts = [](const std::string& s, const char* pre) { return s.compare(0, strlen(pre), pre) == 0; };
+    p->unit_of.assign(p->names.size(), -1);
+    for (size_t i = 0; i < p->names.size(); ++i) {
+        const std::string& n = p->names[i];
+        int u = -1, s = 0, k = 0, m = 0;
+        if (starts(n, "stem.")) u = 0;
+        else if (sscanf(n.c_str(), "stages.%d.%d.", &s, &k) == 2 && s >= 0 && s < 4) u = (s < 2 ? p->u_conv[s] : p->u_rope[s - 2]) + k;
+        else if (sscanf(n.c_str(), "downsample_layers.%d.", &s) == 1) u = s < 2 ? p->u_down[s] : p->u_mid;
+        else if (sscanf(n.c_str(), "cls_token_%d", &s) == 1 && (s == 1 || s == 2)) u = p->u_tok[s - 1];
+        else if (sscanf(n.c_str(), "meta.%d.head_%d.", &m, &s) == 2 && (s == 1 || s == 2)) u = p->u_tok[s - 1];
+        else if (starts(n, "norm_1.") || starts(n, "cl_1_fc.")) u = p->u_mid;
+        else if (starts(n, "norm_2.") || starts(n, "aggregate.") || starts(n, "final_norm.")) u = p->u_tail;
+        else if (starts(n, "head.")) u = p->u_heads;
+        if (u < 0 || u >= (int)p->unit_names.size()) return false;
+        p->unit_of[i] = u;
+    }
+    return true;
+}
+
 struct Carver {
     int64_t cur = 0;
     int64_t take(int64_t bytes) {
@@ -387,6 +447,8 @@ struct Carver {
 };
 
 }  // namespace
+
+static void layout_workspace(lnx_plan* p);
 
 extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     if (!cfg || !out) FAIL("lnx_plan_create: null argument");
@@ -432,9 +494,11 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     for (int i = 0; i < 4; ++i) p->HW[i] = p->H[i] * p->W[i];
     for (int s = 0; s < 2; ++s) p->Ntok[s] = p->HW[2 + s] + p->E;
     build_params(p);
-    const int* D = c.dims;
-    const int B = c.batch;
-    const int esz = p->esz;
+    p->frozen_prefix = !env_off("LNX_FROZEN_PREFIX");
+    if (!build_units(p)) {
+        delete p;
+        FAIL("lnx_plan_create: a parameter without a unit (build_units does not know its name)");
+    }
 
     // collect every arena weight
     auto reg = [&](OpW& w) { p->all_w.push_back(&w); };
@@ -463,8 +527,21 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         reg(p->cl_w2);
     }
     for (auto& w : p->head_w) reg(w);
+    layout_workspace(p);
+    *out = p;
+    return 0;
+}
 
-    // ---- workspace layout ----
+// The workspace layout for the plan's cut (lnx_plan::cut; 0 = every unit trains: the layout of a plan without frozen units).  Run by
+// lnx_plan_create and again by lnx_plan_set_trainable: every offset and size is assigned here, nothing accumulates across runs.
+static void layout_workspace(lnx_plan* p) {
+    const lnx_mformer_cfg& c = p->c;
+    const int* D = c.dims;
+    const int B = c.batch;
+    const int esz = p->esz;
+    const int cut = p->cut;
+    p->dmask_bytes = p->amask_bytes = 0;
+    p->detws_floats = 0;
     Carver cv;
     int ndw = 0;
     for (int s = 0; s < 2; ++s) ndw += c.conv_depths[s];
@@ -503,6 +580,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     p->o_stem_mean = cv.take(M0 * 4);
     p->o_stem_rstd = cv.take(M0 * 4);
     int64_t maxMC = 0, maxM4C = 0;
+    int64_t fwdMC = 0;  // what the FORWARD writes into sD: with dropout masks bound, the proj / fc2 product of every RoPE block, frozen or not
     bool any_fused = false;
     // Inference plans: nothing is saved for a backward, so the blocks of a stage share one set of activation buffers
     // and the residual stream ping-pongs between two (the workspace no longer grows with the depth).
@@ -522,21 +600,38 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
             const int64_t need = lnx_convmlp_bwd_ws_floats((int)D[s], (int)((int64_t)B * p->HW[s]));
             if (need > p->lnws_floats) p->lnws_floats = need;
         }
+    // Frozen prefix (cut > 0, training plans): the nf blocks of a stage that lie before the cut run forward-only.  They share one set of
+    // activation buffers (block 0's), and the fp32 stream through them ping-pongs between two buffers; the input of the first trained
+    // block is the last buffer they wrote and stays valid (every later block writes a buffer of its own).  The backward scratch is sized
+    // by the stages whose units still run a backward.  With cut == 0 nothing below differs from the plan without frozen units.
+    auto frozen_blocks = [&](int first_unit, size_t nb) {  // blocks of a stage before the cut: cut - first_unit, clamped to [0, nb]
+        if (inf || cut <= first_unit) return 0;
+        return cut - first_unit < (int)nb ? cut - first_unit : (int)nb;
+    };
     for (int s = 0; s < 2; ++s) {
         const int64_t M = (int64_t)B * p->HW[s], C = D[s];
-        if (M * C > maxMC) maxMC = M * C;
-        if (M * 4 * C > maxM4C) maxM4C = M * 4 * C;
+        const bool active = cut <= p->u_down[s];  // a unit of this stage's row count (s == 0: the stem too) runs a backward
+        if (active && M * C > maxMC) maxMC = M * C;
+        if (active && M * 4 * C > maxM4C) maxM4C = M * 4 * C;
         int64_t pp[2] = {0, 0};
         if (inf) {
             pp[0] = cv.take(M * C * 4);
             pp[1] = cv.take(M * C * 4);
         }
         const size_t nb = p->conv[s].size();
+        const int nf = frozen_blocks(p->u_conv[s], nb);
+        // fp32 stream buffer k of the stage (k < nb: input of block k; k == nb: the stage output)
+        auto stream_buf = [&](size_t k) {
+            if (inf) return pp[k & 1];
+            if ((int)k > nf) return cv.take(M * C * 4);
+            if (pp[k & 1] == 0) pp[k & 1] = cv.take(M * C * 4);
+            return pp[k & 1];
+        };
         for (size_t i = 0; i < nb; ++i) {
             ConvBlk& k = p->conv[s][i];
-            const bool share = (inf || ck) && i > 0;
+            const bool share = i > 0 && (inf || ck || (int)i < nf);
             const ConvBlk& f = p->conv[s][0];
-            k.xin = inf ? pp[i & 1] : cv.take(M * C * 4);
+            k.xin = stream_buf(i);
             k.y = share ? f.y : cv.take(M * C * esz);
             k.ln = share ? f.ln : cv.take(M * C * esz);
             k.mean = share ? f.mean : cv.take(M * 4);
@@ -552,28 +647,32 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
                 k.z = share ? f.z : cv.take(M * C * esz);
             }
         }
-        p->o_stage_out[s] = inf ? pp[nb & 1] : cv.take(M * C * 4);
+        p->o_stage_out[s] = stream_buf(nb);
         p->down[s].ln = cv.take(M * C * esz);
         p->down[s].mean = cv.take(M * 4);
         p->down[s].rstd = cv.take(M * 4);
-        p->o_g[s] = inf ? 0 : cv.take(M * C * 4);
+        p->o_g[s] = inf || !active ? 0 : cv.take(M * C * 4);
     }
     for (int s = 0; s < 2; ++s) {
         const int N = p->Ntok[s];
         const int64_t M = (int64_t)B * N, C = D[2 + s], hid = c.mlp_hidden[s];
         const int heads = c.rope_heads[s];
-        if (M * C > maxMC) maxMC = M * C;
+        // a unit of this stage's row count runs a backward: its blocks, and for stage 3 `mid` behind it (norm_1, downsample 3)
+        const bool active = s == 0 ? cut <= p->u_mid : cut < p->u_tail;
+        if (active && M * C > maxMC) maxMC = M * C;
+        if (M * C > fwdMC) fwdMC = M * C;
         const int64_t wide = hid > 3 * C ? hid : 3 * C;
-        if (M * wide > maxM4C) maxM4C = M * wide;
+        if (active && M * wide > maxM4C) maxM4C = M * wide;
         p->o_tok[s] = cv.take(M * C * 4);
         int64_t pp[2] = {0, 0};
         if (inf) {
             pp[0] = cv.take(M * C * 4);
             pp[1] = cv.take(M * C * 4);
         }
+        const int nf = frozen_blocks(p->u_rope[s], p->rope[s].size());
         for (size_t i = 0; i < p->rope[s].size(); ++i) {
             RopeBlk& k = p->rope[s][i];
-            const bool share = (inf || ck) && i > 0;
+            const bool share = i > 0 && (inf || ck || (int)i < nf);
             const RopeBlk& f = p->rope[s][0];
             if (i == 0) k.xin = p->o_tok[s];  // later blocks: output buffer of the previous block (set below)
             k.n1 = share ? f.n1 : cv.take(M * C * esz);
@@ -592,11 +691,15 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
             k.rstd2 = share ? f.rstd2 : cv.take(M * 4);
             k.hpre = share ? f.hpre : cv.take(M * hid * esz);
             k.act = share ? f.act : cv.take(M * hid * esz);
-            const int64_t outb = inf ? pp[i & 1] : cv.take(M * C * 4);
+            int64_t outb = 0;
+            if (inf) outb = pp[i & 1];
+            else if ((int)i < nf) outb = pp[i & 1] ? pp[i & 1] : (pp[i & 1] = cv.take(M * C * 4));  // a frozen block's output: ping-pong
+            else outb = cv.take(M * C * 4);
             if (i + 1 < p->rope[s].size()) p->rope[s][i + 1].xin = outb;
             else p->o_stage_out[2 + s] = outb;
         }
-        p->o_g[2 + s] = inf ? 0 : cv.take(M * C * 4);
+        // the gradient stream of the stage: written from norm_1's (s == 0) / norm_2's (s == 1) backward on
+        p->o_g[2 + s] = inf || cut > (s == 0 ? p->u_mid : p->u_tail) ? 0 : cv.take(M * C * 4);
         for (auto& k : p->meta[s]) {
             // meta heads run in fp32 storage in both modes (M = batch rows: negligible cost)
             k.t0 = cv.take((int64_t)B * 16 * 4);
@@ -611,7 +714,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
             k.h2 = cv.take((int64_t)B * C * 4);
             k.m2 = cv.take(B * 4);
             k.r2 = cv.take(B * 4);
-            if (!inf && p->chain_ok[s]) {  // the heads of a stage run side by side in one launch: scratch per head
+            if (!inf && p->chain_ok[s] && cut <= p->u_tok[s]) {  // the heads of a stage run side by side in one launch: backward scratch per head
                 k.dp2 = cv.take((int64_t)B * C * 4);
                 k.dp1 = cv.take((int64_t)B * C * 4);
                 k.dp0 = cv.take((int64_t)B * C * 4);
@@ -624,7 +727,7 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         p->o_t1 = cv.take(M2 * D[2] * esz);
         p->o_t1_mean = cv.take(M2 * 4);
         p->o_t1_rstd = cv.take(M2 * 4);
-        p->o_dt1 = inf ? 0 : cv.take(M2 * D[2] * esz);
+        p->o_dt1 = inf || cut > p->u_mid ? 0 : cv.take(M2 * D[2] * esz);
         p->down[2].ln = cv.take((int64_t)B * p->HW[2] * D[2] * esz);
         p->down[2].mean = cv.take((int64_t)B * p->HW[2] * 4);
         p->down[2].rstd = cv.take((int64_t)B * p->HW[2] * 4);
@@ -696,11 +799,13 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         p->o_sA = cv.take(maxM4C * esz);
         if (any_fused) p->o_sB = cv.take(maxM4C * esz);
         p->o_sC = cv.take(maxMC * esz);
-        p->o_sD = cv.take(maxMC * esz);
+        // (lnx_plan_set_dropout may come after the layout: a training plan always has room for the dropout forward of its RoPE stages)
+        p->o_sD = cv.take((maxMC > fwdMC ? maxMC : fwdMC) * esz);
     }
     if (!inf) {
         int64_t gmax = 0, dmax = 0;
         for (int s = 0; s < 2; ++s) {
+            if (cut >= p->u_rope[s] + c.rope_depths[s]) continue;  // no block of this stage runs its attention backward
             const int N = p->Ntok[s];
             const int64_t gsz = lnx_attn_bwd_ws_floats_hd(B, N, c.rope_heads[s], D[2 + s] / c.rope_heads[s]) * 4;  // per-workgroup partials of the freqs gradient
             const int64_t dsz = (int64_t)B * c.rope_heads[s] * N * 4;
@@ -723,7 +828,30 @@ extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
         }
     }
     p->ws_bytes = cv.cur;
-    *out = p;
+}
+
+extern "C" int lnx_plan_num_units(const lnx_plan* p) { return p ? (int)p->unit_names.size() : 0; }
+extern "C" const char* lnx_plan_unit_name(const lnx_plan* p, int u) {
+    return (p && u >= 0 && u < (int)p->unit_names.size()) ? p->unit_names[u].c_str() : nullptr;
+}
+extern "C" int lnx_plan_param_unit(const lnx_plan* p, int i) { return (p && i >= 0 && i < (int)p->unit_of.size()) ? p->unit_of[i] : -1; }
+extern "C" int lnx_plan_first_trained_unit(const lnx_plan* p) { return p ? p->cut : -1; }
+extern "C" int lnx_plan_last_backward_units(const lnx_plan* p) { return p ? p->bwd_units : -1; }
+
+extern "C" int lnx_plan_set_trainable(lnx_plan* p, const unsigned char* mask) {
+    if (!p) FAIL("lnx_plan_set_trainable: null plan");
+    if (p->c.inference) FAIL("lnx_plan_set_trainable: this is an inference plan (cfg.inference = 1): it has no backward to cut");
+    if (p->bound) FAIL("lnx_plan_set_trainable: the plan is already bound (lnx_plan_bind); the mask changes lnx_plan_workspace_bytes, so set it between create and bind");
+    if (!mask) FAIL("lnx_plan_set_trainable: the mask is NULL (one byte per parameter, lnx_plan_num_params of them)");
+    int cut = -1;
+    for (size_t i = 0; i < p->unit_of.size(); ++i)
+        if (mask[i] && (cut < 0 || p->unit_of[i] < cut)) cut = p->unit_of[i];
+    if (cut < 0) FAIL("lnx_plan_set_trainable: the mask is all zero: nothing trains; use an inference plan (cfg.inference = 1) for that");
+    if (!p->frozen_prefix) return 0;  // LNX_FROZEN_PREFIX=0: the full plan, whatever the mask says
+    if (cut != p->cut) {
+        p->cut = cut;
+        layout_workspace(p);
+    }
     return 0;
 }
 
@@ -1696,7 +1824,8 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     auto wjoin = [&](int j) { return wg_join(c, j); };
     // DropPath compaction (the forward's decision, from the same lists): sC / sA / sD hold compact rows inside a branch, g keeps its layout
     const Compact ca = compact_of(p, p->drop_attn[s][i], M, C, N), cm = compact_of(p, p->drop_mlp[s][i], M, C, N);
-    const Compact cprev = i > 0 ? compact_of(p, p->drop_mlp[s][i - 1], M, C, N) : Compact();
+    const bool prev_runs = i > 0 && p->runs(p->u_rope[s] + i - 1);  // block i - 1 is not behind the cut: it takes its dY from this block's norm1 backward
+    const Compact cprev = prev_runs ? compact_of(p, p->drop_mlp[s][i - 1], M, C, N) : Compact();
     // ---- MLP branch ----
     if (!have_dy) {
         if (cm) RUN(lnx_scale_cast_compact(g, C, p->drop_ptr(p->drop_mlp[s][i]), N, cm.perm, cm.m_dev, sC, c.dt, C, M, C, c.st));
@@ -1778,7 +1907,7 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     // norm1 backward: g is final for this block; block i-1's MLP-branch dY goes into sC in place of this LN's dy (row-wise
     // in-place is safe: a row's dy is consumed before its statistics are known, its dx2 written after)
     Dx2 d1;
-    if (i > 0) {
+    if (prev_runs) {
         d1.p = sC; d1.rowscale = p->drop_ptr(p->drop_mlp[s][i - 1]); d1.rps = N; d1.inv = cprev.inv; d1.nkeep = cprev.nkeep;
         if (mx_dgrad) {  // block i - 1's fc2 data gradient reads it (same stage, same shapes: its own mx_dgrad is this one)
             d1.p8 = c.at<void>(p->o_a8); d1.p8s = c.at<void>(p->o_a8s);
@@ -1790,7 +1919,9 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     return 0;
 }
 
-int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
+// need_dx = false (the block is the cut: nothing before it trains): the depthwise data gradient, which only produces the block's input
+// gradient, is not launched
+int conv_block_bwd(const Ctx& c, int s, int i, float* g, bool need_dx) {
     lnx_plan* p = c.p;
     ConvBlk& k = p->conv[s][i];
     const int B = p->c.batch, H = p->H[s], W = p->W[s], C = p->c.dims[s];
@@ -1875,7 +2006,7 @@ int conv_block_bwd(const Ctx& c, int s, int i, float* g) {
     memset(&d, 0, sizeof d);
     d.B = B; d.H = H; d.W = W; d.C = C;
     d.x = dy; d.x_dtype = c.dt; d.w49 = c.at<float>(k.w49); d.bias = nullptr; d.flip = 1; d.res = g; d.y = g; d.y_dtype = LNX_F32;
-    {
+    if (need_dx) {
         Timed t(c, 4, (double)M * C * (8 + p->esz));  // bytes: read T dy + fp32 g, write fp32 g
         RUN(lnx_dwconv7_fwd_kept(&d, cl.perm, cl.nkeep, c.st));  // g of a dropped sample passes through unchanged
     }
@@ -2032,12 +2163,18 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
     const int B = cf.batch;
     const int* D = cf.dims;
     const bool all = segment < 0;
+    // Frozen prefix: a unit runs only if it is not before the cut (lnx_plan::runs); every unit that runs counts once per backward.  The
+    // flushes and joins at the end of each segment stay: they act on whatever was postponed or forked, and on nothing otherwise.
+    const int cut = p->cut;
+    if (segment <= 0) p->bwd_units = 0;
+    auto ran = [&]() { ++p->bwd_units; };
 
     if (all || segment == 0) {
         const int C = D[3];
         float* dfe = c.at<float>(p->o_tail[0]);  // d feats [B, C]
         bool have = false, heads_forked = false;
-        if (dfeats) {
+        const bool below_heads = cut < p->u_heads;  // (the heads as the cut: their weight and bias gradients only -- no features gradient)
+        if (dfeats && below_heads) {
             HIPRUN(hipMemcpyAsync(dfe, dfeats, (size_t)B * C * 4, hipMemcpyDeviceToDevice, st));
             have = true;
         }
@@ -2062,64 +2199,75 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
                 hg[0].res = dfe;
                 hg[0].ldres = C;
             }
-            RUN(heads_nt(c, hg, cf.n_tasks, true));
+            if (below_heads) RUN(heads_nt(c, hg, cf.n_tasks, true));
             have = true;
         }
-        if (!have) FAIL("lnx_plan_backward: neither dlogits nor dfeats given");
-        // final_norm
-        const float* fin_in = cf.only_last_cls ? c.at<float>(p->o_c2n) : c.at<float>(p->o_agg);
-        float* dfin = c.at<float>(p->o_tail[1]);
-        RUN(ln_bwd(c, B, C, dfe, LNX_F32, C, IDM, fin_in, LNX_F32, C, IDM, p->fin_w, p->fin_b, c.at<float>(p->o_fin_mean), c.at<float>(p->o_fin_rstd), nullptr, dfin,
-                   LNX_F32, C, false));
-        float* dc2n = dfin;
+        if (!have && (below_heads || !dfeats)) FAIL("lnx_plan_backward: neither dlogits nor dfeats given");
+        ran();  // heads
         float* dc1n = nullptr;
-        if (!cf.only_last_cls) {
-            dc1n = c.at<float>(p->o_tail[2]);
-            dc2n = c.at<float>(p->o_tail[3]);
-            RUN(lnx_agg2_bwd(dfin, c.at<float>(p->o_c1n), c.at<float>(p->o_c2n), p->P[p->agg_w], dc1n, dc2n, p->G[p->agg_w], p->G[p->agg_b], B, C, stream));
-        }
-        // norm_2 acts on the CLS row only: every other row of the stage-4 output has zero gradient
         float* g3 = c.at<float>(p->o_g[3]);
-        HIPRUN(hipMemsetAsync(g3, 0, (size_t)B * p->Ntok[1] * C * 4, st));
-        const lnx_rowmap clsrow = {1, p->Ntok[1] - 1, 0};
-        RUN(ln_bwd(c, B, C, dc2n, LNX_F32, C, IDM, c.at<float>(p->o_stage_out[3]), LNX_F32, C, clsrow, p->norm_w[1], p->norm_b[1], c.at<float>(p->o_n2_mean),
-                   c.at<float>(p->o_n2_rstd), nullptr, g3, LNX_F32, C, false));
-        for (int i = cf.rope_depths[1] - 1; i >= 0; --i) {
+        if (p->runs(p->u_tail)) {
+            // final_norm
+            const float* fin_in = cf.only_last_cls ? c.at<float>(p->o_c2n) : c.at<float>(p->o_agg);
+            float* dfin = c.at<float>(p->o_tail[1]);
+            RUN(ln_bwd(c, B, C, dfe, LNX_F32, C, IDM, fin_in, LNX_F32, C, IDM, p->fin_w, p->fin_b, c.at<float>(p->o_fin_mean), c.at<float>(p->o_fin_rstd), nullptr,
+                       dfin, LNX_F32, C, false));
+            float* dc2n = dfin;
+            if (!cf.only_last_cls) {
+                dc1n = c.at<float>(p->o_tail[2]);
+                dc2n = c.at<float>(p->o_tail[3]);
+                RUN(lnx_agg2_bwd(dfin, c.at<float>(p->o_c1n), c.at<float>(p->o_c2n), p->P[p->agg_w], dc1n, dc2n, p->G[p->agg_w], p->G[p->agg_b], B, C, stream));
+            }
+            // norm_2 acts on the CLS row only: every other row of the stage-4 output has zero gradient
+            if (cut < p->u_tail) HIPRUN(hipMemsetAsync(g3, 0, (size_t)B * p->Ntok[1] * C * 4, st));  // (tail as the cut: nobody reads g3)
+            const lnx_rowmap clsrow = {1, p->Ntok[1] - 1, 0};
+            RUN(ln_bwd(c, B, C, dc2n, LNX_F32, C, IDM, c.at<float>(p->o_stage_out[3]), LNX_F32, C, clsrow, p->norm_w[1], p->norm_b[1], c.at<float>(p->o_n2_mean),
+                       c.at<float>(p->o_n2_rstd), nullptr, g3, LNX_F32, C, false));
+            ran();
+        }
+        for (int i = cf.rope_depths[1] - 1; i >= 0 && p->runs(p->u_rope[1] + i); --i) {
             RUN(rope_block_restore(c, 1, i));
             RUN(rope_block_bwd(c, 1, i, g3, i != cf.rope_depths[1] - 1));
+            ran();
         }
-        RUN(tokens_bwd(c, 1, g3));
-        // downsample 3 backward into d(norm_1 output); meta/CLS rows of dt1 start at zero
-        const int C2 = D[2];
-        void* dt1 = c.at<void>(p->o_dt1);
-        HIPRUN(hipMemsetAsync(dt1, 0, (size_t)B * p->Ntok[0] * C2 * p->esz, st));
-        const lnx_rowmap gm = {p->HW[3], p->E, p->E};
-        const lnx_rowmap pm = {p->HW[2], p->E, p->E};
-        RUN(downsample_bwd(c, 2, g3, C, gm, c.at<void>(p->o_t1), cf.dtype, C2, pm, dt1, cf.dtype, C2));
-        if (!cf.only_last_cls) {
-            void* du = c.at<void>(p->o_tail[4]);
-            void* dca = c.at<void>(p->o_tail[5]);
-            RUN(ln_bwd(c, B, C, dc1n, LNX_F32, C, IDM, c.at<float>(p->o_cl_u), LNX_F32, C, IDM, p->cl_lnw, p->cl_lnb, c.at<float>(p->o_cl_mean), c.at<float>(p->o_cl_rstd),
-                       nullptr, du, cf.dtype, C, false));
-            RUN(wgrad(c, B, C, C2, du, C, c.at<void>(p->o_cl_act), C2, p->cl_w2.param, p->cl_b2, C2));
-            lnx_gemm_args a = gemm_base(c, B, C2, C, du, C, c.wtptr(p->cl_w2), p->cl_w2.ld_t, dca, C2, false);
-            a.act = LNX_ACT_GELU_BWD; a.aux = c.at<void>(p->o_cl_hpre); a.ldaux = C2;
-            RUN(gemm_nt_t(c, &a));
-            RUN(wgrad(c, B, C2, C2, dca, C2, c.at<void>(p->o_t1), (int64_t)p->Ntok[0] * C2, p->cl_w1.param, p->cl_b1, C2));
-            a = gemm_base(c, B, C2, C2, dca, C2, c.wtptr(p->cl_w1), p->cl_w1.ld_t, dt1, C2, false);
-            a.c_map = lnx_rowmap{1, p->Ntok[0] - 1, 0};
-            RUN(gemm_nt_t(c, &a));
+        if (p->runs(p->u_tok[1])) {
+            RUN(tokens_bwd(c, 1, g3));
+            ran();
         }
-        float* g2 = c.at<float>(p->o_g[2]);
-        // norm_1 backward also leaves the last stage-3 block's MLP-branch dY in sC (consumed first thing in segment 1)
-        Dx2 dn;
-        dn.p = c.at<void>(p->o_sC); dn.rowscale = p->drop_ptr(p->drop_mlp[0][cf.rope_depths[0] - 1]); dn.rps = p->Ntok[0];
-        {
-            const Compact cl = compact_of(p, p->drop_mlp[0][cf.rope_depths[0] - 1], B * p->Ntok[0], C2, p->Ntok[0]);
-            dn.inv = cl.inv; dn.nkeep = cl.nkeep;
+        if (p->runs(p->u_mid)) {
+            // downsample 3 backward into d(norm_1 output); meta/CLS rows of dt1 start at zero
+            const int C2 = D[2];
+            void* dt1 = c.at<void>(p->o_dt1);
+            HIPRUN(hipMemsetAsync(dt1, 0, (size_t)B * p->Ntok[0] * C2 * p->esz, st));
+            const lnx_rowmap gm = {p->HW[3], p->E, p->E};
+            const lnx_rowmap pm = {p->HW[2], p->E, p->E};
+            RUN(downsample_bwd(c, 2, g3, C, gm, c.at<void>(p->o_t1), cf.dtype, C2, pm, dt1, cf.dtype, C2));
+            if (!cf.only_last_cls) {
+                void* du = c.at<void>(p->o_tail[4]);
+                void* dca = c.at<void>(p->o_tail[5]);
+                RUN(ln_bwd(c, B, C, dc1n, LNX_F32, C, IDM, c.at<float>(p->o_cl_u), LNX_F32, C, IDM, p->cl_lnw, p->cl_lnb, c.at<float>(p->o_cl_mean),
+                           c.at<float>(p->o_cl_rstd), nullptr, du, cf.dtype, C, false));
+                RUN(wgrad(c, B, C, C2, du, C, c.at<void>(p->o_cl_act), C2, p->cl_w2.param, p->cl_b2, C2));
+                lnx_gemm_args a = gemm_base(c, B, C2, C, du, C, c.wtptr(p->cl_w2), p->cl_w2.ld_t, dca, C2, false);
+                a.act = LNX_ACT_GELU_BWD; a.aux = c.at<void>(p->o_cl_hpre); a.ldaux = C2;
+                RUN(gemm_nt_t(c, &a));
+                RUN(wgrad(c, B, C2, C2, dca, C2, c.at<void>(p->o_t1), (int64_t)p->Ntok[0] * C2, p->cl_w1.param, p->cl_b1, C2));
+                a = gemm_base(c, B, C2, C2, dca, C2, c.wtptr(p->cl_w1), p->cl_w1.ld_t, dt1, C2, false);
+                a.c_map = lnx_rowmap{1, p->Ntok[0] - 1, 0};
+                RUN(gemm_nt_t(c, &a));
+            }
+            float* g2 = c.at<float>(p->o_g[2]);
+            // norm_1 backward also leaves the last stage-3 block's MLP-branch dY in sC (consumed first thing in segment 1) -- if that block runs
+            Dx2 dn;
+            if (p->runs(p->u_rope[0] + cf.rope_depths[0] - 1)) {
+                dn.p = c.at<void>(p->o_sC); dn.rowscale = p->drop_ptr(p->drop_mlp[0][cf.rope_depths[0] - 1]); dn.rps = p->Ntok[0];
+                const Compact cl = compact_of(p, p->drop_mlp[0][cf.rope_depths[0] - 1], B * p->Ntok[0], C2, p->Ntok[0]);
+                dn.inv = cl.inv; dn.nkeep = cl.nkeep;
+            }
+            RUN(ln_bwd(c, B * p->Ntok[0], C2, dt1, cf.dtype, C2, IDM, c.at<float>(p->o_stage_out[2]), LNX_F32, C2, IDM, p->norm_w[0], p->norm_b[0],
+                       c.at<float>(p->o_t1_mean), c.at<float>(p->o_t1_rstd), nullptr, g2, LNX_F32, C2, false, dn));
+            ran();
         }
-        RUN(ln_bwd(c, B * p->Ntok[0], C2, dt1, cf.dtype, C2, IDM, c.at<float>(p->o_stage_out[2]), LNX_F32, C2, IDM, p->norm_w[0], p->norm_b[0], c.at<float>(p->o_t1_mean),
-                   c.at<float>(p->o_t1_rstd), nullptr, g2, LNX_F32, C2, false, dn));
         // the stage-4 metadata-head backward (side stream, ~10 small fp32 GEMMs) is joined at the END OF SEGMENT 1: it only
         // produces parameter gradients, and joining here exposed most of its ~0.7 ms behind the three downsample kernels.
         // That holds for segment-wise callers too (segments run 0..3 in order): the gradients of the stage-4 metadata heads
@@ -2129,38 +2277,53 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
     }
     if (all || segment == 1) {
         float* g2 = c.at<float>(p->o_g[2]);
-        for (int i = cf.rope_depths[0] - 1; i >= 0; --i) {
+        for (int i = cf.rope_depths[0] - 1; i >= 0 && p->runs(p->u_rope[0] + i); --i) {
             RUN(rope_block_restore(c, 0, i));
             RUN(rope_block_bwd(c, 0, i, g2, true));
+            ran();
         }
-        RUN(tokens_bwd(c, 0, g2));
-        const lnx_rowmap gm = {p->HW[2], p->E, p->E};
-        RUN(downsample_bwd(c, 1, g2, D[2], gm, c.at<float>(p->o_stage_out[1]), LNX_F32, D[1], IDM, c.at<float>(p->o_g[1]), LNX_F32, D[1]));
+        if (p->runs(p->u_tok[0])) {
+            RUN(tokens_bwd(c, 0, g2));
+            ran();
+        }
+        if (p->runs(p->u_down[1])) {
+            const lnx_rowmap gm = {p->HW[2], p->E, p->E};
+            RUN(downsample_bwd(c, 1, g2, D[2], gm, c.at<float>(p->o_stage_out[1]), LNX_F32, D[1], IDM, c.at<float>(p->o_g[1]), LNX_F32, D[1]));
+            ran();
+        }
         RUN(ln_flush(c));
         RUN(join_side(c, 1));
     }
     if (all || segment == 2) {
         float* g1 = c.at<float>(p->o_g[1]);
-        for (int i = cf.conv_depths[1] - 1; i >= 0; --i) {
+        for (int i = cf.conv_depths[1] - 1; i >= 0 && p->runs(p->u_conv[1] + i); --i) {
             RUN(conv_block_restore(c, 1, i));
-            RUN(conv_block_bwd(c, 1, i, g1));
+            RUN(conv_block_bwd(c, 1, i, g1, cut < p->u_conv[1] + i));
+            ran();
         }
-        RUN(downsample_bwd(c, 0, g1, D[1], IDM, c.at<float>(p->o_stage_out[0]), LNX_F32, D[0], IDM, c.at<float>(p->o_g[0]), LNX_F32, D[0]));
+        if (p->runs(p->u_down[0])) {
+            RUN(downsample_bwd(c, 0, g1, D[1], IDM, c.at<float>(p->o_stage_out[0]), LNX_F32, D[0], IDM, c.at<float>(p->o_g[0]), LNX_F32, D[0]));
+            ran();
+        }
         RUN(ln_flush(c));
         RUN(join_side(c, 0));  // stage-3 metadata heads: hidden behind the whole ConvNeXt stage-2 backward
     }
     if (all || segment == 3) {
         float* g0 = c.at<float>(p->o_g[0]);
-        for (int i = cf.conv_depths[0] - 1; i >= 0; --i) {
+        for (int i = cf.conv_depths[0] - 1; i >= 0 && p->runs(p->u_conv[0] + i); --i) {
             RUN(conv_block_restore(c, 0, i));
-            RUN(conv_block_bwd(c, 0, i, g0));
+            RUN(conv_block_bwd(c, 0, i, g0, cut < p->u_conv[0] + i));
+            ran();
         }
-        const int M0 = B * p->HW[0];
-        void* sC = c.at<void>(p->o_sC);
-        RUN(ln_bwd(c, M0, D[0], g0, LNX_F32, D[0], IDM, c.at<void>(p->o_stem_pre), cf.dtype, D[0], IDM, p->stem_lnw, p->stem_lnb, c.at<float>(p->o_stem_mean),
-                   c.at<float>(p->o_stem_rstd), nullptr, sC, cf.dtype, D[0], false));
-        const int kst = cf.in_chans * 16;
-        RUN(wgrad(c, M0, D[0], 64, sC, D[0], c.at<void>(p->o_patches), 64, p->stem_w.param, p->stem_b, kst, kst));
+        if (p->runs(0)) {  // the stem
+            const int M0 = B * p->HW[0];
+            void* sC = c.at<void>(p->o_sC);
+            RUN(ln_bwd(c, M0, D[0], g0, LNX_F32, D[0], IDM, c.at<void>(p->o_stem_pre), cf.dtype, D[0], IDM, p->stem_lnw, p->stem_lnb, c.at<float>(p->o_stem_mean),
+                       c.at<float>(p->o_stem_rstd), nullptr, sC, cf.dtype, D[0], false));
+            const int kst = cf.in_chans * 16;
+            RUN(wgrad(c, M0, D[0], 64, sC, D[0], c.at<void>(p->o_patches), 64, p->stem_w.param, p->stem_b, kst, kst));
+            ran();
+        }
         RUN(ln_flush(c));
     }
     return 0;

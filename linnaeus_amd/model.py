@@ -407,6 +407,7 @@ class mFormerV1(nn.Module):
             self._destroy_plan(st)
         self._plans.clear()
         self._active = None
+        self._units = None  # (the tensors behind the plan's parameter names are looked up again with the next plan)
 
     @property
     def compute_dtype(self) -> str:
@@ -466,17 +467,89 @@ class mFormerV1(nn.Module):
             cfg.task_classes[i] = self.head[t].effective_linear.out_features
         return cfg
 
+    # ------------------------------------------------------------------ fine-tuning: frozen parameters
+    def plan_units(self) -> Dict[str, Any]:
+        """Host-only (no GPU, nothing allocated): the plan's unit list in forward order (include/lnx.h, "Fine-tuning: a frozen
+        prefix"), the plan's parameter names, the unit index of each and the module tensor behind each."""
+        info = getattr(self, "_units", None)
+        if info is None:
+            lib = L.lib()
+            lib.lnx_plan_param_name.restype = C.c_char_p
+            cfg = self._make_cfg(1, int(self.img_size[0]), int(self.img_size[1]), True, False)
+            handle = C.c_void_p()
+            L.check(lib.lnx_plan_create(C.byref(cfg), C.byref(handle)), "lnx_plan_create")
+            try:
+                n = lib.lnx_plan_num_params(handle)
+                names = [lib.lnx_plan_param_name(handle, i).decode() for i in range(n)]
+                units = [lib.lnx_plan_unit_name(handle, u).decode() for u in range(lib.lnx_plan_num_units(handle))]
+                unit_of = [int(lib.lnx_plan_param_unit(handle, i)) for i in range(n)]
+            finally:
+                lib.lnx_plan_destroy(handle)
+            # (the tensors are looked up once, as a cached plan does: a forward reads 200-odd requires_grad flags, not 200 names)
+            info = self._units = dict(names=names, units=units, unit_of=unit_of, params=[self._param_for(nm) for nm in names])
+        return info
+
+    def _trainable_mask(self, trainable=None) -> Optional[bytes]:
+        """One byte per plan parameter: it trains.  From `requires_grad` now, or from `trainable` (an iterable of module or plan
+        parameter names).  None when everything trains: the plan, and its cache key, are then those of a model without frozen
+        parameters."""
+        info = self.plan_units()
+        if trainable is None:
+            mask = bytes(int(p_.requires_grad) for p_ in info["params"])
+        else:
+            named = dict(self.named_parameters())
+            ids = {id(named[nm] if nm in named else self._param_for(nm)) for nm in trainable}
+            mask = bytes(int(id(p_) in ids) for p_ in info["params"])
+        return None if all(mask) else mask
+
+    def freeze_through(self, unit_name: str) -> None:
+        """requires_grad = False on every parameter of the units before `unit_name`, True from it on: the backward of the next
+        training forward stops behind that unit, and the units before it keep no activations."""
+        info = self.plan_units()
+        if unit_name not in info["units"]:
+            raise ValueError(f"unknown unit {unit_name!r}; this model's units are {info['units']}")
+        u = info["units"].index(unit_name)
+        for p_, pu in zip(info["params"], info["unit_of"]):
+            p_.requires_grad_(pu >= u)
+
+    def unfreeze_last_blocks(self, n: int) -> None:
+        """The reference's phase-2 rule (rl_train_abstention.py:385-396) over this model's block list (stages 0-3 in order): the
+        backbone is frozen and its last `n` blocks are unfrozen; n > number of blocks unfreezes everything, n = 0 leaves every block
+        frozen.  `tail` and `heads` always train, and so do the `tokens_*` / `mid` units that follow the first unfrozen block (the
+        gradient passes through them anyway); stem and the ConvNeXt downsample layers train only with n > number of blocks."""
+        info = self.plan_units()
+        units = info["units"]
+        blocks = [u for u, nm in enumerate(units) if nm.startswith("stages.")]
+        n = int(n)
+        if n > len(blocks):
+            on = set(range(len(units)))
+        else:
+            on = {units.index("tail"), units.index("heads")}
+            if n > 0:
+                first = blocks[len(blocks) - n]
+                on |= set(blocks[len(blocks) - n:])
+                on |= {u for u, nm in enumerate(units) if u > first and (nm.startswith("tokens_") or nm == "mid")}
+        for p_, pu in zip(info["params"], info["unit_of"]):
+            p_.requires_grad_(pu in on)
+
+    def trainable_report(self, batch: int = 1, img_h: Optional[int] = None, img_w: Optional[int] = None) -> Dict[str, Any]:
+        """The current freeze state as the planner sees it: the cut unit's name, the number of units a backward runs and the
+        workspace bytes of a training plan of this batch shape."""
+        q = self._plan_query(batch, img_h, img_w, True, None, None)
+        return {"cut": q["cut"], "backward_units": q["backward_units"], "workspace": q["workspace"]}
+
     def workspace_bytes(self, batch: int, img_h: Optional[int] = None, img_w: Optional[int] = None, train: bool = True,
-                        recompute: Optional[bool] = None) -> int:
+                        recompute: Optional[bool] = None, trainable=None) -> int:
         """Bytes of plan workspace (saved activations + operand arena + scratch) a forward[/backward] of this batch shape
         needs -- computed by the native planner WITHOUT allocating anything, which is what lets AutoBatch size a batch
-        for 288 GB analytically instead of by out-of-memory trials (utils/autobatch.py:111-265)."""
+        for 288 GB analytically instead of by out-of-memory trials (utils/autobatch.py:111-265).  A training plan is the one
+        of the current freeze state (`requires_grad`), or of `trainable` (parameter names) when given."""
         H = img_h or self.img_size[0]
         W = img_w or img_h or self.img_size[1]
-        return self.plan_footprint(batch, H, W, train, recompute)["workspace"]
+        return self.plan_footprint(batch, H, W, train, recompute, trainable=trainable)["workspace"]
 
     def plan_footprint(self, batch: int, img_h: Optional[int] = None, img_w: Optional[int] = None, train: bool = True,
-                       recompute: Optional[bool] = None, gradnorm_arenas: int = 0) -> Dict[str, int]:
+                       recompute: Optional[bool] = None, gradnorm_arenas: int = 0, trainable=None) -> Dict[str, int]:
         """Everything a plan of this shape holds on the device, computed by the native planner without allocating: the
         workspace, the per-forward dropout keep masks that live OUTSIDE it (`lnx_plan_dropout_bytes` /
         `lnx_plan_attn_dropout_bytes`; only when MODEL.DROP_RATE / ATTN_DROP_RATE > 0 and in training) and the fp32 logits
@@ -484,9 +557,15 @@ class mFormerV1(nn.Module):
         `gradnorm_arenas` > 0 the dict also holds "gradnorm": the scratch gradient arenas of a GradNorm update
         (`loss.GradientWeighting.scratch_arenas()`: 1, or T with GRADNORM_ACCUM_STEPS > 1) and its dlogits buffer."""
         if gradnorm_arenas:
-            fp = self.plan_footprint(batch, img_h, img_w, train, recompute)
+            fp = self.plan_footprint(batch, img_h, img_w, train, recompute, trainable=trainable)
             fp["gradnorm"] = int(gradnorm_arenas) * 4 * self.grad_arena_layout()["total"] + fp["logits"] // 2
             return fp
+        q = self._plan_query(batch, img_h, img_w, train, recompute, trainable)
+        return {k: q[k] for k in ("workspace", "dropout", "attn_dropout", "logits")}
+
+    def _plan_query(self, batch, img_h, img_w, train, recompute, trainable) -> Dict[str, Any]:
+        """One throw-away plan of this shape and freeze state (host only): the footprint figures, and the cut as the planner itself
+        reports it -- unit name (None: nothing trains, an inference plan) and the number of units its backward runs."""
         lib = L.lib()
         for fn in (lib.lnx_plan_workspace_bytes, lib.lnx_plan_dropout_bytes, lib.lnx_plan_attn_dropout_bytes, lib.lnx_plan_logits_numel):
             fn.restype = C.c_int64
@@ -494,14 +573,21 @@ class mFormerV1(nn.Module):
         W = img_w or img_h or self.img_size[1]
         if recompute is None:  # what a training forward would use
             recompute = self._checkpoint_policy()
+        mask = self._trainable_mask(trainable) if train else None
+        if mask is not None and not any(mask):  # nothing trains: what a forward of this model runs is an inference plan
+            train, mask = False, None
         cfg = self._make_cfg(int(batch), int(H), int(W), train, bool(recompute))
         handle = C.c_void_p()
         L.check(lib.lnx_plan_create(C.byref(cfg), C.byref(handle)), "lnx_plan_create")
         try:
+            if mask is not None:
+                L.check(lib.lnx_plan_set_trainable(handle, mask), "lnx_plan_set_trainable")
             drop = int(lib.lnx_plan_dropout_bytes(handle)) if (train and self.drop_rate > 0.0) else 0
             adrop = int(lib.lnx_plan_attn_dropout_bytes(handle)) if (train and self.attn_drop_rate > 0.0) else 0
             logits = int(lib.lnx_plan_logits_numel(handle)) * 4 * (2 if train else 1)
-            return {"workspace": int(lib.lnx_plan_workspace_bytes(handle)) + 256, "dropout": drop, "attn_dropout": adrop, "logits": logits}
+            cut, n_units = lib.lnx_plan_first_trained_unit(handle), lib.lnx_plan_num_units(handle)
+            return {"workspace": int(lib.lnx_plan_workspace_bytes(handle)) + 256, "dropout": drop, "attn_dropout": adrop, "logits": logits,
+                    "cut": lib.lnx_plan_unit_name(handle, cut).decode() if train else None, "backward_units": n_units - cut if train else 0}
         finally:
             lib.lnx_plan_destroy(handle)
 
@@ -510,8 +596,21 @@ class mFormerV1(nn.Module):
         frozen model) carry no backward scratch and share activation buffers between blocks; recompute plans (gradient
         checkpointing) keep block inputs only.  The cache is a small LRU: an evicted plan is destroyed and its workspace freed."""
         recompute = bool(train and recompute)
-        key = (B, H, W, self._dtype_code, self._fp8, bool(train), recompute)
-        st = self._plans.get(key)
+        # the freeze state at forward time: frozen parameters select (or create) a plan of their own, whose backward stops at the
+        # first unit that trains; with everything trainable the key and the plan are those of a model that never froze anything
+        def lookup():
+            mask = self._trainable_mask() if train else None
+            key = (B, H, W, self._dtype_code, self._fp8, bool(train), recompute)
+            if mask is not None:
+                key = key[:-1] + (mask, recompute)
+            return mask, key, self._plans.get(key)
+
+        mask, key, st = lookup()
+        if st is None and train and getattr(self, "_units", None) is not None:
+            # a new plan looks the tensors behind its parameter names up again (a head's Linear may have been replaced): so does
+            # the mask it is made for
+            self._units = None
+            mask, key, st = lookup()
         lib = L.lib()
         if st is not None:
             self._plans.move_to_end(key)
@@ -526,6 +625,12 @@ class mFormerV1(nn.Module):
             tasks = self._task_list()
             handle = C.c_void_p()
             L.check(lib.lnx_plan_create(C.byref(cfg), C.byref(handle)), "lnx_plan_create")
+            if mask is not None:
+                try:
+                    L.check(lib.lnx_plan_set_trainable(handle, mask), "lnx_plan_set_trainable")
+                except L.LnxError:
+                    lib.lnx_plan_destroy(handle)
+                    raise
             if not getattr(self, "_wgrad_stream", True) and lib.lnx_plan_set_wgrad_stream(handle, 0) < 0:
                 L.check(1, "lnx_plan_set_wgrad_stream")
             if getattr(self, "_meta_stream", None) is not None and lib.lnx_plan_set_meta_stream(handle, self._meta_stream) < 0:
@@ -553,7 +658,8 @@ class mFormerV1(nn.Module):
             st = dict(handle=handle, names=names, params=params, ws=ws, ptrs=None, n=n, seg_of=seg_of,
                       ndrop=lib.lnx_plan_num_drop_calls(handle), logits_numel=lib.lnx_plan_logits_numel(handle),
                       logit_off=[lib.lnx_plan_logits_offset(handle, i) for i in range(len(tasks))],
-                      logit_ld=[lib.lnx_plan_logits_ld(handle, i) for i in range(len(tasks))], tasks=tasks, B=B, fwd_id=0, train=bool(train))
+                      logit_ld=[lib.lnx_plan_logits_ld(handle, i) for i in range(len(tasks))], tasks=tasks, B=B, fwd_id=0, train=bool(train),
+                      trains=[True] * n if mask is None else [bool(m) for m in mask])
             self._plans[key] = st
         self._ensure_bound(st)
         return st
@@ -715,6 +821,24 @@ class mFormerV1(nn.Module):
         st["fwd_id"] = st.get("fwd_id", 0) + 1
         return feats, logits
 
+    def _zero_unaliased(self, st, alias) -> None:
+        """Zero the arena slices whose parameter's .grad is not that slice, one fill per RUN of neighbouring slices (a frozen
+        prefix is a few runs of the segment-ordered arena, not one fill per tensor); the runs are kept per alias pattern."""
+        key = bytes(alias)
+        cached = st.get("zero_runs")
+        if cached is None or cached[0] != key:
+            base = self._grad_arena.data_ptr()
+            spans = sorted(((v.data_ptr() - base) // 4, v.numel()) for v, a in zip(self._grad_views, alias) if not a)
+            runs: List[List[int]] = []
+            for lo, n in spans:
+                if runs and runs[-1][1] == lo:
+                    runs[-1][1] = lo + (n + 3) // 4 * 4  # (slices are padded to 16 bytes: _arena_offsets)
+                else:
+                    runs.append([lo, lo + (n + 3) // 4 * 4])
+            cached = st["zero_runs"] = (key, runs)
+        for lo, hi in cached[1]:
+            self._grad_arena[lo:hi].zero_()
+
     def _plan_backward(self, st, dfeats, dlogits):
         direct = self.grad_mode == "direct"
         params = st["params"]
@@ -722,14 +846,20 @@ class mFormerV1(nn.Module):
         # The kernels ACCUMULATE into the arena.  A slice may keep its contents only if the parameter's .grad IS that
         # slice (gradient accumulation in direct mode); every other slice (grad None, or a foreign tensor such as a clone
         # left by autograd mode / zero_grad(set_to_none=False)) must start from zero.
+        # A parameter that was frozen at the forward (st["trains"]) gets no gradient in either mode: its slice is zeroed like any
+        # non-aliased one (the fused launches of a trained unit may write it) and never handed out.
+        trains = st["trains"]
         if direct:
-            alias = [p_.grad is not None and p_.grad.data_ptr() == v.data_ptr() for p_, v in zip(params, views)]
+            for p_, v, t in zip(params, views, trains):
+                # frozen since it was trained in this mode: its .grad still IS the slice, which the fused launches of a trained unit
+                # may write -- an optimizer steps on `grad is not None`, so the stale view must not stay
+                if not t and p_.grad is not None and p_.grad.data_ptr() == v.data_ptr():
+                    p_.grad = None
+            alias = [t and p_.grad is not None and p_.grad.data_ptr() == v.data_ptr() for p_, v, t in zip(params, views, trains)]
             if not any(alias):
                 self._grad_arena.zero_()
             elif not all(alias):
-                for a, v in zip(alias, views):
-                    if not a:
-                        v.zero_()
+                self._zero_unaliased(st, alias)
         else:
             alias = None
             self._grad_arena.zero_()
@@ -748,7 +878,9 @@ class mFormerV1(nn.Module):
                                               C.c_void_p(df.data_ptr()) if df is not None else None, seg, stream), "lnx_plan_backward")
                 self._segment_hook(seg)
         if direct:
-            for p_, v, a in zip(params, views, alias):
+            for p_, v, a, t in zip(params, views, alias, trains):
+                if not t:
+                    continue
                 if p_.grad is None:
                     p_.grad = v
                 elif not a:
@@ -758,7 +890,7 @@ class mFormerV1(nn.Module):
         # the next backward zeroes
         snap = self._grad_arena.clone()
         base = self._grad_arena.data_ptr()
-        return [snap[(v.data_ptr() - base) // 4: (v.data_ptr() - base) // 4 + v.numel()].view(v.shape) for v in views]
+        return [snap[(v.data_ptr() - base) // 4: (v.data_ptr() - base) // 4 + v.numel()].view(v.shape) if t else None for v, t in zip(views, trains)]
 
     # ------------------------------------------------------------------ GradNorm
     def _gradnorm_arenas(self, n: int) -> torch.Tensor:
