@@ -1248,6 +1248,56 @@ int lnx_hier_loss_fwd(const lnx_hier_loss_args* args, void* stream);
 int lnx_hier_loss_bwd(const lnx_hier_loss_args* args, const float* go_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Top-down refinement of the hierarchical heads (MODEL.CLASSIFICATION.HIERARCHICAL_REFINEMENT): what ConditionalClassifierHead.forward
+ * (heads/conditional_classifier_head.py:191-224) and HierarchicalSoftmaxHead were written to do and never do (findings F3 / F4), in
+ * ONE launch per direction for every level of every row.  Levels come FINEST FIRST, as in lnx_predict, n_tasks <= LNX_SOFTCE_MAX_TASKS.
+ * Forward, from the coarsest level down; level t with parent level t + 1 and R = that level's finished `out` row AS STORED:
+ *   prob   LNX_HIER_ROUTE_SOFT    softmax(R / temperature)
+ *          LNX_HIER_ROUTE_GUMBEL  softmax((R + noise) / temperature), noise [B, C of level t + 1] fp32 supplied by the caller
+ *          LNX_HIER_ROUTE_HARD    one-hot at the arg-max of R (torch.argmax: the lowest index on a tie, a NaN above every number)
+ *   out[c] = base[c] + log(prob[parent[c]] + 1e-10),  prob = 0 where parent[c] < 0 (or beyond the parent level's C)
+ *   The coarsest level and a level whose `parent` is NULL (no matrix for that pair) are passed through: out = base (not copied where
+ *   out == base).  stats[b, t, 0..1] = the max and the sum of exponentials of level t's routing softmax (0, 0 for a pass-through).
+ * Backward, from the finest level up: G_t = dout_t + (what level t - 1 sends up), dbase_t = G_t.  Level t - 1 sends to its parent t
+ *   S[j] = sum of G_{t-1}[c] over the children c of j, dprob[j] = S[j] / (prob[j] + 1e-10),
+ *   dR[j] = prob[j] * (dprob[j] - sum_k prob[k] dprob[k]) / temperature;  nothing for LNX_HIER_ROUTE_HARD or a NULL parent table.
+ *   The children come from a CSR table: child_idx[child_start[j] .. child_start[j + 1]) in ascending class order, classes without a
+ *   parent in no list.  The backward reads out, stats and noise of the forward, dout (NULL = zeros), and writes every dbase in full.
+ * Storage of base / out / dout / dbase is the args' dtype, arithmetic fp32 (the segment sums accumulate in fp64); a level's row enters the next level as stored (rounded
+ * to bf16 on bf16 tensors) in both directions.  Columns >= C are neither read nor written.  One workgroup per row walks the levels,
+ * rows in strides (no class count has to fit on chip), fixed-order reductions, no atomics: bit-identical run to run.
+ * Refused on the host before any launch: n_tasks outside 1..LNX_SOFTCE_MAX_TASKS, B <= 0, C <= 0, ld < C (backward: ldd < C), a NULL
+ * stats / out / base (forward) / dbase (backward); and for every level that routes: temperature <= 0, an unknown mode, gumbel
+ * without noise, and in the backward a parent table without child_start / child_idx.
+ * -----------------------------------------------------------------------------------*/
+enum { LNX_HIER_ROUTE_SOFT = 0, LNX_HIER_ROUTE_HARD = 1, LNX_HIER_ROUTE_GUMBEL = 2 };
+typedef struct lnx_hier_refine_level {
+    const void* base;           /* [B, ld] base logits (forward) */
+    void* out;                  /* [B, ld] refined logits: written by the forward, read by the backward */
+    const void* dout;           /* [B, ldd] gradient of out, or NULL = zeros (backward) */
+    void* dbase;                /* [B, ldd] gradient of base (backward) */
+    int64_t ld, ldd;            /* >= C */
+    int C;
+    int mode;                   /* LNX_HIER_ROUTE_*: how THIS level is routed from the level above */
+    const int32_t* parent;      /* [C] class of the next coarser level, -1 = none (the convention of lnx_predict_task.parent); NULL = pass-through */
+    const int32_t* child_start; /* [C of level t + 1, + 1] */
+    const int32_t* child_idx;   /* [C] (as many entries as classes with a parent) */
+    const float* noise;         /* [B, C of level t + 1] gumbel noise, LNX_HIER_ROUTE_GUMBEL only */
+    float temperature;          /* > 0 */
+} lnx_hier_refine_level;
+typedef struct lnx_hier_refine_args {
+    int dtype;    /* of base / out / dout / dbase of every level: 0 = fp32, 1 = bf16 */
+    int B, n_tasks;
+    float* stats; /* [B, n_tasks, 2] fp32 */
+    lnx_hier_refine_level level[LNX_SOFTCE_MAX_TASKS];
+} lnx_hier_refine_args;
+int lnx_hier_refine_fwd(const lnx_hier_refine_args* args, void* stream);
+int lnx_hier_refine_bwd(const lnx_hier_refine_args* args, void* stream);
+/* launches made by lnx_hier_refine_fwd and lnx_hier_refine_bwd (1 each) since the library was loaded (host-side counter, the twin of
+ * lnx_optim_launches) */
+int64_t lnx_hier_refine_launches(void);
+
+/* ------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP branch (bf16 storage, C in {32,64,96,128,192}):
  *   out = x + rowscale * gamma * (GELU(ln . W1^T + b1) . W2^T + b2)
  * = pwconv1 -> GELU -> pwconv2 -> LayerScale -> DropPath -> residual (blocks/convnext.py:79-86)

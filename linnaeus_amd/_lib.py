@@ -213,6 +213,24 @@ class HierLossArgs(C.Structure):  # == lnx_hier_loss_args
                 ("weights", C.c_void_p), ("ws", C.c_void_p), ("out", C.c_void_p), ("counts", C.c_void_p), ("task", HierLossTask * METRICS_MAX_TASKS)]
 
 
+# lnx_hier_refine_level.mode (the LNX_HIER_ROUTE_* enum of include/lnx.h)
+HIER_ROUTE_SOFT, HIER_ROUTE_HARD, HIER_ROUTE_GUMBEL = range(3)
+
+
+class HierRefineLevel(C.Structure):  # == lnx_hier_refine_level
+    _fields_ = [("base", C.c_void_p), ("out", C.c_void_p), ("dout", C.c_void_p), ("dbase", C.c_void_p), ("ld", C.c_int64), ("ldd", C.c_int64),
+                ("C", C.c_int), ("mode", C.c_int), ("parent", C.c_void_p), ("child_start", C.c_void_p), ("child_idx", C.c_void_p),
+                ("noise", C.c_void_p), ("temperature", C.c_float)]
+
+
+class HierRefineArgs(C.Structure):  # == lnx_hier_refine_args
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("n_tasks", C.c_int), ("stats", C.c_void_p), ("level", HierRefineLevel * METRICS_MAX_TASKS)]
+
+
+# the argument structs of the hierarchical refinement by their C names (tests compare sizeof against a compiled probe)
+HIER_REFINE_STRUCTS = {"lnx_hier_refine_level": HierRefineLevel, "lnx_hier_refine_args": HierRefineArgs}
+
+
 _lib = None
 
 
@@ -255,6 +273,10 @@ def lib() -> C.CDLL:
         if hasattr(_lib, "lnx_hier_loss_fwd"):
             _lib.lnx_hier_loss_fwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p]
             _lib.lnx_hier_loss_bwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p, C.c_void_p]
+        if hasattr(_lib, "lnx_hier_refine_fwd"):
+            _lib.lnx_hier_refine_fwd.argtypes = [C.POINTER(HierRefineArgs), C.c_void_p]
+            _lib.lnx_hier_refine_bwd.argtypes = [C.POINTER(HierRefineArgs), C.c_void_p]
+            _lib.lnx_hier_refine_launches.restype = C.c_int64
         if hasattr(_lib, "lnx_preprocess"):
             _lib.lnx_resize_taps.argtypes = [C.c_int, C.c_int, C.c_int]
             _lib.lnx_resize_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -329,6 +351,7 @@ EXPORTS = [
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_drop_compact_conv_blocks", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
+    "lnx_hier_refine_fwd", "lnx_hier_refine_bwd", "lnx_hier_refine_launches",
     "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",

@@ -15,11 +15,13 @@ Inside mFormerV1.forward the head GEMMs run in the native plan; the modules' own
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional
+import os
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
+from . import _lib as L
 from . import ops
 from ._lib import LnxError
 from .registry import create_head, register_head
@@ -212,3 +214,141 @@ def refine_logits_top_down(base: Dict[str, torch.Tensor], heads: nn.ModuleDict, 
         prior = _LinearFn.apply(probs, getattr(head, name).t().contiguous().float(), None)  # probs . M
         refined[child] = base[child] + torch.log(prior + 1e-10).to(base[child].dtype)
     return refined
+
+
+def parent_index_from_matrix(m: torch.Tensor, strict_name: Optional[str] = None) -> torch.Tensor:
+    """hmatrix_{parent}_{child} ([n_parent, n_child] membership) -> int64 [n_child] on the host: the class of each child's parent, -1
+    for an all-zero column.  This is the convention of lnx_predict_task.parent and lnx_hier_refine_level.parent (one derivation for
+    DevicePredictor and HierarchicalRefinement).  With `strict_name` the matrix must be what the gather assumes -- entries 0 or 1, at
+    most one 1 per column -- and is refused under that name otherwise."""
+    m = m.detach().cpu()
+    if m.dim() != 2:
+        raise LnxError(f"{strict_name or 'hierarchy matrix'} must be [n_parent, n_child], got {tuple(m.shape)}")
+    if strict_name is not None:
+        if not bool(((m == 0) | (m == 1)).all()):
+            raise LnxError(f"{strict_name} holds entries other than 0 and 1: the device refinement reads it as a parent table")
+        if m.shape[0] and int(m.ne(0).sum(0).max()) > 1:
+            raise LnxError(f"{strict_name} has a column with more than one 1 (a class with two parents): the device refinement reads it as a parent table")
+    return torch.where(m.ne(0).any(0), m.argmax(0), torch.full((m.shape[1],), -1, dtype=torch.int64))
+
+
+def children_csr(parent: torch.Tensor, n_parent: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The inverse of a parent table as the CSR pair of lnx_hier_refine_level: child_start int32 [n_parent + 1] and child_idx int32
+    [n_child]; the children of j are child_idx[child_start[j] : child_start[j + 1]] in ascending order, classes without a parent are in
+    no list (the entries past child_start[n_parent] are -1 and never read)."""
+    parent = parent.detach().cpu().to(torch.int64).reshape(-1)
+    if parent.numel() and (int(parent.max()) >= n_parent or int(parent.min()) < -1):
+        raise LnxError(f"parent table entries must lie in [-1, {n_parent})")
+    has = parent.ge(0)
+    counts = torch.bincount(parent[has], minlength=n_parent)
+    start = torch.zeros(n_parent + 1, dtype=torch.int64)
+    start[1:] = torch.cumsum(counts, 0)
+    idx = torch.full((parent.numel(),), -1, dtype=torch.int64)
+    owned = torch.nonzero(has).reshape(-1)
+    order = torch.sort(parent[owned], stable=True).indices
+    idx[: owned.numel()] = owned[order]
+    return start.to(torch.int32), idx.to(torch.int32)
+
+
+class _HierRefineFn(torch.autograd.Function):
+    """All levels in one lnx_hier_refine_fwd launch; the backward is one lnx_hier_refine_bwd launch.  Takes every level's base logits
+    (finest first) and returns the refined tensor of every level but the coarsest, whose tensor the caller hands back as it came."""
+
+    @staticmethod
+    def forward(ctx, tables, modes, temps, noises, *bases):
+        outs, stats = ops.hier_refine_fwd(list(bases), tables, modes, temps, noises)
+        ctx.tables, ctx.modes, ctx.temps = tables, modes, temps
+        ctx.has_noise = [g is not None for g in noises]
+        # (outs[-1] is the coarsest base itself; the others are this function's own outputs)
+        ctx.save_for_backward(stats, *outs, *[g for g in noises if g is not None])
+        ctx.set_materialize_grads(False)
+        return tuple(outs[:-1])
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        stats, *rest = ctx.saved_tensors
+        T = len(ctx.modes)
+        outs, given = rest[:T], iter(rest[T:])
+        noises = [next(given) if has else None for has in ctx.has_noise]
+        douts = [None if g is None else g.to(outs[0].dtype) for g in gouts] + [None]
+        dbases = ops.hier_refine_bwd(outs, stats, douts, ctx.tables, ctx.modes, ctx.temps, noises)
+        return (None, None, None, None, *dbases)
+
+
+class HierarchicalRefinement:
+    """`refine_logits_top_down` on the device: built once per model from its heads, it turns every hmatrix_{parent}_{child} into the
+    int32 parent table and the CSR children table of lnx_hier_refine_fwd / _bwd (uploaded once per device) and refines the logits of all
+    tasks in one launch per direction.  Routing per child task follows the reference's _compute_routing_probabilities
+    (heads/conditional_classifier_head.py:142-160), read from the child task's head at every call: HierarchicalSoftmaxHead routes by
+    softmax(R); ConditionalClassifierHead by the one-hot arg-max in eval with routing_strategy 'hard', by gumbel-softmax in training
+    with 'gumbel', and by softmax(R / temperature) otherwise."""
+
+    def __init__(self, heads: nn.ModuleDict, task_keys: List[str]):
+        self.heads, self.task_keys = heads, list(task_keys)
+        T = len(self.task_keys)
+        if not 1 <= T <= L.METRICS_MAX_TASKS:
+            raise LnxError(f"HierarchicalRefinement: {T} tasks (1..{L.METRICS_MAX_TASKS})")
+        self.host_tables: List[Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]] = [None] * T
+        for i in range(T - 1):
+            child, parent = self.task_keys[i], self.task_keys[i + 1]
+            name = f"hmatrix_{parent}_{child}"
+            head = heads[child] if child in heads else None
+            if head is None or not hasattr(head, name):
+                continue  # no matrix for this pair: the level is passed through, as in refine_logits_top_down
+            m = getattr(head, name)
+            par = parent_index_from_matrix(m, strict_name=name)
+            start, idx = children_csr(par, m.shape[0])
+            self.host_tables[i] = (par.to(torch.int32).contiguous(), start, idx)
+        self._dev_tables: Dict[torch.device, list] = {}
+
+    def _tables_on(self, device):
+        if device not in self._dev_tables:
+            self._dev_tables[device] = [None if t is None else tuple(x.to(device) for x in t) for t in self.host_tables]
+        return self._dev_tables[device]
+
+    def routing(self, i: int) -> Tuple[int, float]:
+        """(LNX_HIER_ROUTE_* mode, temperature) of task i's level right now."""
+        head = self.heads[self.task_keys[i]] if self.task_keys[i] in self.heads else None
+        strategy = getattr(head, "routing_strategy", "soft")
+        temp = float(getattr(head, "temperature", 1.0))
+        if strategy == "hard" and not head.training:
+            return L.HIER_ROUTE_HARD, temp
+        if strategy == "gumbel" and head.training:
+            return L.HIER_ROUTE_GUMBEL, temp
+        return L.HIER_ROUTE_SOFT, temp
+
+    def __call__(self, base: Dict[str, torch.Tensor], noise: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """{task: [B, C] logits} -> the same dict with every task below the coarsest refined; the coarsest task's tensor is returned
+        as it came.  fp32 or bf16 (one dtype for all tasks), on the GPU.  `noise`: {child task: fp32 [B, C_parent]} replays gumbel
+        noise; tasks routed by gumbel and not named there draw theirs from torch's generator as F.gumbel_softmax does."""
+        missing = [t for t in self.task_keys if t not in base]
+        if missing:
+            raise LnxError(f"HierarchicalRefinement: no logits for {missing}")
+        xs = [base[t] for t in self.task_keys]
+        if any(not x.is_cuda for x in xs):
+            raise LnxError("HierarchicalRefinement runs on the HIP kernels only; move the logits to the GPU (or set LNX_HIER_REFINE=0)")
+        T = len(xs)
+        if T == 1:
+            return dict(base)
+        tables = self._tables_on(xs[0].device)
+        modes, temps, noises = [L.HIER_ROUTE_SOFT] * T, [1.0] * T, [None] * T
+        for i in range(T - 1):
+            if tables[i] is None:
+                continue
+            modes[i], temps[i] = self.routing(i)
+            if modes[i] == L.HIER_ROUTE_GUMBEL:
+                g = noise.get(self.task_keys[i]) if noise is not None else None
+                if g is None:  # F.gumbel_softmax: -torch.empty_like(logits).exponential_().log()
+                    g = -torch.empty(xs[i + 1].shape, dtype=torch.float32, device=xs[i + 1].device).exponential_().log()
+                noises[i] = g.float().contiguous()
+        refined = _HierRefineFn.apply(tables, modes, temps, noises, *xs)
+        out = dict(base)
+        for t, r in zip(self.task_keys[:-1], refined):
+            out[t] = r
+        return out
+
+
+def hier_refine_on_device() -> bool:
+    """LNX_HIER_REFINE, read per call: 0 keeps the torch composition (refine_logits_top_down) under
+    MODEL.CLASSIFICATION.HIERARCHICAL_REFINEMENT; anything else takes HierarchicalRefinement."""
+    return os.environ.get("LNX_HIER_REFINE", "1") != "0"

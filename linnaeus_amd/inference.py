@@ -22,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .heads import parent_index_from_matrix
 
 
 def _rank(task_key: str) -> int:
@@ -109,7 +110,7 @@ class DevicePredictor:
                     m = m.detach().cpu()
                     if tuple(m.shape) != (self.num_classes[i + 1], C_):
                         raise L.LnxError(f"DevicePredictor: {name} is {tuple(m.shape)}, expected {(self.num_classes[i + 1], C_)}")
-                    tab = torch.where(m.ne(0).any(0), m.argmax(0), torch.full((C_,), -1, dtype=torch.int64))
+                    tab = parent_index_from_matrix(m)
             if tab is None:
                 continue
             if tab.numel() != C_ or int(tab.max()) >= self.num_classes[i + 1] or int(tab.min()) < -1:

@@ -992,9 +992,14 @@ class mFormerV1(nn.Module):
                 out[t] = out[t].to(acast)  # the reference returns logits in the autocast dtype (SURVEY 8b "Tensor conventions")
         self._last_feats = feats
         if self.hierarchical_refinement:
-            from .heads import refine_logits_top_down
+            from .heads import HierarchicalRefinement, hier_refine_on_device, refine_logits_top_down
 
-            out = refine_logits_top_down(out, self.head, self.task_keys)
+            if hier_refine_on_device():  # one launch per direction (lnx_hier_refine_fwd / _bwd); LNX_HIER_REFINE=0: the torch composition
+                if getattr(self, "_hier_refine", None) is None:
+                    self._hier_refine = HierarchicalRefinement(self.head, self.task_keys)
+                out = self._hier_refine(out)
+            else:
+                out = refine_logits_top_down(out, self.head, self.task_keys)
         return out
 
     def __del__(self):

@@ -664,6 +664,88 @@ def predict_topk(logits, parents, *, K, null_index=0, id_maps=None, k_per_sample
     return tuple(out)
 
 
+def _hier_refine_rows(what, t, x, B, code, like=None):
+    """[B, C] rows of one dtype with unit column stride -> the leading dimension (a padded view's stride(0))"""
+    if x.dim() != 2 or x.shape[0] != B or code_of(x) != code or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise L.LnxError(f"{what}: level {t} must be [B, C] rows of one dtype (fp32 / bf16) with unit column stride, got {tuple(x.shape)} {x.dtype} strides {x.stride()}")
+    if like is not None and x.shape[1] != like.shape[1]:
+        raise L.LnxError(f"{what}: level {t} has {x.shape[1]} columns, expected {like.shape[1]}")
+    return x.stride(0) if B > 1 else x.shape[1]
+
+
+def _hier_refine_levels(what, a, rows, tables, modes, temps, noises):
+    """The per-level fields both directions share: C, the tables, mode, temperature, noise (rows: per level a [B, C] tensor)."""
+    T = len(rows)
+    if not 1 <= T <= L.METRICS_MAX_TASKS or not (len(tables) == len(modes) == len(temps) == len(noises) == T):
+        raise L.LnxError(f"{what}: {T} levels (1..{L.METRICS_MAX_TASKS}) need {T} tables / modes / temperatures / noise entries")
+    a.dtype, a.B, a.n_tasks = code_of(rows[0]), rows[0].shape[0], T
+    for t in range(T):
+        k, Ct = a.level[t], rows[t].shape[1]
+        k.C, k.mode, k.temperature = Ct, int(modes[t]), float(temps[t])
+        if tables[t] is None or t == T - 1:
+            continue
+        Cp = rows[t + 1].shape[1]
+        par, start, idx = tables[t]
+        for name, tab, n in (("parent", par, Ct), ("child_start", start, Cp + 1), ("child_idx", idx, Ct)):
+            if tab is not None and (tab.dtype != torch.int32 or tab.shape != (n,) or not tab.is_contiguous()):
+                raise L.LnxError(f"{what}: level {t} {name} table must be contiguous int32 [{n}]")
+        k.parent, k.child_start, k.child_idx = _p(par), _p(start), _p(idx)
+        g = noises[t]
+        if g is not None:
+            if g.dtype != torch.float32 or g.shape != (a.B, Cp) or not g.is_contiguous():
+                raise L.LnxError(f"{what}: level {t} noise must be contiguous fp32 [{a.B}, {Cp}]")
+            k.noise = _p(g)
+
+
+def hier_refine_fwd(bases, tables, modes, temps, noises, outs=None):
+    """One lnx_hier_refine_fwd launch: out[t] = base[t] + log(prob[parent] + 1e-10) for every level, finest first (include/lnx.h).
+    bases: per level [B, C] rows of one dtype (fp32 / bf16), unit column stride (padded views welcome); tables: per level
+    (parent, child_start, child_idx) int32 device tensors or None (= pass-through; the coarsest level's entry is not read); modes / temps:
+    per level L.HIER_ROUTE_* and the temperature; noises: per level fp32 [B, C_parent] or None.  outs: tensors laid out like the bases to
+    write into (default: new ones; the coarsest level's is its base, which is not copied).  Returns (outs, stats [B, T, 2]); never synchronises."""
+    a = L.HierRefineArgs()
+    _hier_refine_levels("hier_refine_fwd", a, bases, tables, modes, temps, noises)
+    T, B = a.n_tasks, a.B
+    if outs is None:
+        outs = [torch.empty_strided(x.shape, (x.stride(0) if B > 1 else x.shape[1], 1), dtype=x.dtype, device=x.device) for x in bases[:-1]] + [bases[-1]]
+    for t in range(T):
+        k = a.level[t]
+        k.ld = _hier_refine_rows("hier_refine_fwd", t, bases[t], B, a.dtype)
+        if _hier_refine_rows("hier_refine_fwd", t, outs[t], B, a.dtype, like=bases[t]) != k.ld:
+            raise L.LnxError(f"hier_refine_fwd: level {t} out must have the leading dimension of its base ({k.ld})")
+        k.base, k.out = _p(bases[t]), _p(outs[t])
+    stats = torch.empty(B, T, 2, dtype=torch.float32, device=bases[0].device)
+    a.stats = _p(stats)
+    L.check(L.lib().lnx_hier_refine_fwd(C.byref(a), _stream()), "lnx_hier_refine_fwd")
+    return list(outs), stats
+
+
+def hier_refine_bwd(outs, stats, douts, tables, modes, temps, noises, dbases=None):
+    """One lnx_hier_refine_bwd launch: the gradients of every level's base logits from the gradients of the refined ones.  outs / stats /
+    noises: what hier_refine_fwd returned / was given; douts: per level [B, C] of the outs' dtype or None (= zeros); dbases: tensors to
+    write into (default: new contiguous ones).  Returns dbases; never synchronises."""
+    a = L.HierRefineArgs()
+    _hier_refine_levels("hier_refine_bwd", a, outs, tables, modes, temps, noises)
+    T, B = a.n_tasks, a.B
+    if len(douts) != T:
+        raise L.LnxError(f"hier_refine_bwd: {T} levels need {T} dout entries (None = zeros)")
+    if stats.dtype != torch.float32 or stats.shape != (B, T, 2) or not stats.is_contiguous():
+        raise L.LnxError(f"hier_refine_bwd: stats must be contiguous fp32 [{B}, {T}, 2]")
+    if dbases is None:  # contiguous, and so are the douts beside them (one leading dimension per level)
+        douts = [None if g is None else g.contiguous() for g in douts]
+        dbases = [torch.empty(x.shape, dtype=x.dtype, device=x.device) for x in outs]
+    for t in range(T):
+        k = a.level[t]
+        k.ld = _hier_refine_rows("hier_refine_bwd", t, outs[t], B, a.dtype)
+        k.ldd = _hier_refine_rows("hier_refine_bwd", t, dbases[t], B, a.dtype, like=outs[t])
+        if douts[t] is not None and _hier_refine_rows("hier_refine_bwd", t, douts[t], B, a.dtype, like=outs[t]) != k.ldd:
+            raise L.LnxError(f"hier_refine_bwd: level {t} dout and dbase must share one leading dimension")
+        k.out, k.dout, k.dbase = _p(outs[t]), _p(douts[t]), _p(dbases[t])
+    a.stats = _p(stats)
+    L.check(L.lib().lnx_hier_refine_bwd(C.byref(a), _stream()), "lnx_hier_refine_bwd")
+    return list(dbases)
+
+
 def preprocess_images(blob, blob_bytes, images, images_off, n, H, W, filter_code, mean, std, scratch, out):
     """lnx_preprocess on a batch that is already on the device: blob uint8 (descriptor table at images_off, tables, packed [h, w, 3]
     sources: include/lnx.h), images the HOST copy of the descriptor table (a ctypes array of L.PreprocessImage that
