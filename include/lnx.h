@@ -207,6 +207,23 @@ typedef struct lnx_wgrad_args {
 #define LNX_TN_WS_FLOATS (256 * (256 * 128 + 256))
 
 int lnx_gemm_tn(const lnx_wgrad_args* args, void* stream);
+/* What lnx_gemm_tn WOULD launch for these arguments (no launch, no device work, no GPU needed; 0 on success, 1 and lnx_last_error on
+ * arguments lnx_gemm_tn refuses for their sizes): only dtype / M / N / K / leading dimensions / a_mode and its geometry / k_store /
+ * splits / ws_floats, WHICH of ws is non-NULL, the deterministic mode and the LNX_GEMM_V1 / LNX_TN_ORIENT / LNX_TN_ATOMIC switches are
+ * looked at, never the memory behind a pointer.  It is the function lnx_gemm_tn itself takes its launch from; the seam tests use it to
+ * prove which kernel, tile form, split and summation path a case ran on, and DESIGN.md's TN table is checked against it. */
+enum { LNX_TN_KERNEL_V1 = 1 /* gemm_tn_kernel<T>: 128x128 register-staged, fp32 and bf16, atomics only */,
+       LNX_TN_KERNEL_RING = 2 /* gemm_tn_v2_kernel<rw, cw, patch>: LDS-DMA ring of 64-row contraction tiles, bf16 */ };
+typedef struct lnx_tn_launch {
+    int kernel;          /* LNX_TN_KERNEL_* */
+    int rw, cw;          /* output tile: rows (of N) x columns (of K); 128 x 128, 256 x 128 or 128 x 256 */
+    int patch;           /* 1: the 2x2 patch-gather instantiation (ring kernel) / addressing (128x128 kernel) */
+    int tiles_n, tiles_k;
+    int splits;          /* workgroups per output tile as launched ... */
+    int m_per_split;     /* ... and the contraction rows each of them covers (the last one what is left) */
+    int workspace;       /* 1: partial tiles go through ws and the second stage; 0: fp32 atomics on dW / db */
+} lnx_tn_launch;
+int lnx_gemm_tn_query(const lnx_wgrad_args* args, lnx_tn_launch* out);
 /* sums the partial tiles of the products postponed with `defer` into their dW / db (no-op when nothing is pending).  `stream` must be the
  * stream those products were launched on (or NULL = that stream): another stream is an error (the reduces would be ordered behind the wrong work). */
 int lnx_gemm_tn_flush(void* stream);

@@ -67,6 +67,14 @@ class WgradArgs(C.Structure):
     ]
 
 
+class TnLaunch(C.Structure):  # == lnx_tn_launch (lnx_gemm_tn_query)
+    _fields_ = [("kernel", C.c_int), ("rw", C.c_int), ("cw", C.c_int), ("patch", C.c_int), ("tiles_n", C.c_int), ("tiles_k", C.c_int),
+                ("splits", C.c_int), ("m_per_split", C.c_int), ("workspace", C.c_int)]
+
+
+TN_KERNEL_V1, TN_KERNEL_RING = 1, 2  # lnx_tn_launch.kernel (include/lnx.h)
+
+
 class SoftCEArgs(C.Structure):
     _fields_ = [
         ("B", C.c_int), ("C", C.c_int),
@@ -301,6 +309,8 @@ def lib() -> C.CDLL:
             _lib.lnx_plan_unit_name.argtypes = [C.c_void_p, C.c_int]
             _lib.lnx_plan_unit_name.restype = C.c_char_p
             _lib.lnx_plan_set_trainable.argtypes = [C.c_void_p, C.c_char_p]
+        if hasattr(_lib, "lnx_gemm_tn_query"):
+            _lib.lnx_gemm_tn_query.argtypes = [C.POINTER(WgradArgs), C.POINTER(TnLaunch)]
         if hasattr(_lib, "lnx_layernorm_fwd_query"):
             _lib.lnx_layernorm_fwd_query.argtypes = [C.POINTER(LnArgs), C.POINTER(LnLaunch)]
             _lib.lnx_layernorm_bwd_query.argtypes = [C.POINTER(LnBwdArgs), C.POINTER(LnLaunch)]
@@ -344,7 +354,7 @@ ATTN_KERNEL_NONE, ATTN_KERNEL_RES4, ATTN_KERNEL_RES8, ATTN_KERNEL_TILED4, ATTN_K
 # every symbol include/lnx.h declares (kept in sync by tests/test_abi.py)
 EXPORTS = [
     "lnx_last_error", "lnx_version", "lnx_device_cus", "lnx_set_cu_margin", "lnx_set_deterministic", "lnx_get_deterministic", "lnx_tile_sched_static",
-    "lnx_gemm_nt", "lnx_last_nt_kernel", "lnx_nt_kernel_launches", "lnx_nt_dispatch", "lnx_gemm_tn", "lnx_gemm_tn_flush", "lnx_gemm_tn_discard", "lnx_amax", "lnx_quantize_fp8", "lnx_gemm_nt_fp8", "lnx_quantize_mxfp8", "lnx_gemm_nt_mxfp8", "lnx_dropout_mul", "lnx_dropout_residual", "lnx_plan_dropout_bytes", "lnx_plan_set_dropout", "lnx_plan_attn_dropout_bytes", "lnx_plan_set_attn_dropout",
+    "lnx_gemm_nt", "lnx_last_nt_kernel", "lnx_nt_kernel_launches", "lnx_nt_dispatch", "lnx_gemm_tn", "lnx_gemm_tn_query", "lnx_gemm_tn_flush", "lnx_gemm_tn_discard", "lnx_amax", "lnx_quantize_fp8", "lnx_gemm_nt_fp8", "lnx_quantize_mxfp8", "lnx_gemm_nt_mxfp8", "lnx_dropout_mul", "lnx_dropout_residual", "lnx_plan_dropout_bytes", "lnx_plan_set_dropout", "lnx_plan_attn_dropout_bytes", "lnx_plan_set_attn_dropout",
     "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard", "lnx_layernorm_fwd_query", "lnx_layernorm_bwd_query",
     "lnx_dwconv7_fwd", "lnx_dwconv7_fwd_kept", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_kept", "lnx_dwconv7_wgrad_ws_floats",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_fwd_compact", "lnx_attn_bwd_compact", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",

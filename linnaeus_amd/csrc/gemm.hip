@@ -336,6 +336,10 @@ int lnxg::launch_nt_v1(const GemmP& p, int dtype, bool out_f32, hipStream_t st) 
     return launch_nt<float, true>(p, st);  // T == float: both output kinds are fp32
 }
 
+int lnxg::launch_tn_v1(const WgradP& p, int dtype, hipStream_t st) {
+    return dtype == LNX_BF16 ? launch_tn<bf16_t>(p, st) : launch_tn<float>(p, st);
+}
+
 extern "C" int lnx_gemm_nt_group_ok(const lnx_gemm_args* a, int n, int accumulate) {
     if (!a || n < 1 || n > LNX_GEMM_GROUP_MAX) return 0;
     for (int j = 0; j < n; ++j) {
@@ -361,72 +365,6 @@ extern "C" int lnx_gemm_nt_group(const lnx_gemm_args* a, int n, int accumulate, 
     for (int j = 0; j < n; ++j) fill_gemm_p(&a[j], ps[j]);
     note_nt_kernel(LNX_NT_KERNEL_SKINNY);
     launch_nt_skinny_group(ps, n, accumulate != 0, a[0].out_f32 != 0, (hipStream_t)stream);
-    LNX_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int lnx_gemm_tn(const lnx_wgrad_args* a, void* stream) {
-    LNX_CHECK(a != nullptr, "lnx_gemm_tn: null args");
-    LNX_CHECK(a->dtype == LNX_F32 || a->dtype == LNX_BF16, "lnx_gemm_tn: bad dtype %d", a->dtype);
-    const int epv = a->dtype == LNX_F32 ? 4 : 8;
-    LNX_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "lnx_gemm_tn: empty problem");
-    LNX_CHECK(a->dY && a->A && a->dW, "lnx_gemm_tn: null operand");
-    // dY rows are read in 16-byte chunks: a chunk that starts below N may run past it, so the row
-    // must be padded (lddy >= roundup(N, epv)); what the padding holds is never stored
-    LNX_CHECK(a->lddy % epv == 0 && a->lddy >= (int64_t)cdiv(a->N, epv) * epv, "lnx_gemm_tn: lddy=%lld must be a multiple of %d and >= roundup(N)", (long long)a->lddy, epv);
-    LNX_CHECK(a->K % epv == 0, "lnx_gemm_tn: K=%d must be a multiple of %d", a->K, epv);
-    LNX_CHECK((((uintptr_t)a->A) & 15) == 0 && (((uintptr_t)a->dY) & 15) == 0, "lnx_gemm_tn: operands must be 16-byte aligned");
-    if (a->a_mode == LNX_ADDR_PATCH2) {
-        LNX_CHECK(a->Hin % 2 == 0 && a->Win % 2 == 0 && a->Cin % epv == 0 && a->K == 4 * a->Cin, "lnx_gemm_tn: bad PATCH2 geometry");
-    } else {
-        LNX_CHECK(a->lda % epv == 0, "lnx_gemm_tn: lda must be a multiple of %d", epv);
-    }
-    if (a->k_perm_c > 0) LNX_CHECK(a->K % a->k_perm_c == 0, "lnx_gemm_tn: K %% k_perm_c != 0");
-    WgradP p;
-    p.dY = (const unsigned char*)a->dY;
-    p.A = (const unsigned char*)a->A;
-    p.dW = a->dW;
-    p.db = a->db;
-    p.lddy = a->lddy;
-    p.lda = a->lda;
-    p.lddw = a->lddw;
-    p.M = a->M;
-    p.N = a->N;
-    p.K = a->K;
-    p.a_mode = a->a_mode;
-    p.pg = PatchGeom{a->Hin, a->Win, a->Cin};
-    p.k_perm_c = a->k_perm_c;
-    p.ws = a->ws;
-    p.ws_floats = a->ws ? a->ws_floats : 0;
-    p.k_store = (a->k_store > 0 && a->k_store < a->K) ? a->k_store : a->K;
-    p.m_dev = a->m_dev;
-    p.tiles_n = cdiv(a->N, TILE);
-    p.tiles_k = cdiv(a->K, TILE);
-    const int bmc = a->dtype == LNX_BF16 ? 64 : 32;
-    int splits = a->splits;
-    if (splits <= 0) {
-        // aim at ~2 workgroups per CU, but keep >= 4 M-tiles of work per split
-        const int tiles = p.tiles_n * p.tiles_k;
-        splits = cdiv(2 * 256, tiles);
-        const int max_splits = cdiv(a->M, 4 * bmc);
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-    }
-    const bool v2 = tn_v2_ok(p, a->dtype) && !nt_switches().force_v1;
-    // deterministic mode: this kernel has no workspace second stage, its splits meet in float atomics -- one split, one contributor
-    // per element (launch_tn_v2 applies its own rule to the hint)
-    if (!v2 && deterministic()) splits = 1;
-    int mps = cdiv(a->M, splits);
-    mps = cdiv(mps, bmc) * bmc;
-    p.splits = cdiv(a->M, mps);
-    p.m_per_split = mps;
-    hipStream_t st = (hipStream_t)stream;
-    static const bool no_defer = getenv("LNX_TN_NO_DEFER") != nullptr;  // A/B switch: every product reduces its own partial tiles at once
-    int rc;
-    if (v2) rc = launch_tn_v2(p, a->splits, st, a->defer != 0 && !no_defer);
-    else if (a->dtype == LNX_BF16) rc = launch_tn<bf16_t>(p, st);
-    else rc = launch_tn<float>(p, st);
-    if (rc != 0) return rc;
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -666,53 +666,13 @@ int tn_discard() {
     return n;
 }
 
-bool tn_v2_ok(const WgradP& p, int dtype) {
-    return dtype == LNX_BF16 && p.M % TBM == 0 && p.M >= 4096 && p.N >= 8 && p.K >= 8;
-}
-
-int launch_tn_v2(const WgradP& p0, int splits_hint, hipStream_t st, bool defer) {
-    WgradP p = p0;
-    // tile orientation with the least padding waste
-    auto waste = [&](int rw, int cw) { return (double)cdiv(p.N, rw) * rw * cdiv(p.K, cw) * cw; };
-    static const char* force = getenv("LNX_TN_ORIENT");  // A/B switch: "r" = 256x128 tiles, "c" = 128x256
-    const bool wide_r = force ? force[0] == 'r' : waste(256, 128) <= waste(128, 256);
-    const int RW = wide_r ? 256 : 128, CW = wide_r ? 128 : 256;
-    p.tiles_n = cdiv(p.N, RW);
-    p.tiles_k = cdiv(p.K, CW);
+int launch_tn_v2(const WgradP& p, const TnPlan& t, hipStream_t st, bool defer) {
+    static_assert(TBM == TN_RING_ROWS, "tn_plan splits the contraction in this kernel's ring stages");
+    const bool wide_r = t.RW == 256, patch = t.patch;
+    const int RW = t.RW, CW = t.CW;
     const int tiles = p.tiles_n * p.tiles_k;
-    const int mtiles = p.M / TBM;
-    int splits = splits_hint;
-    if (splits <= 0) {
-        splits = 256 / tiles;  // the 144 KiB ring allows one workgroup per CU: at most one full round
-        if (splits < 1) splits = 1;
-        const int max_splits = mtiles / 8 > 0 ? mtiles / 8 : 1;  // ... with >= 8 contraction tiles each
-        if (splits > max_splits) splits = max_splits;
-    }
-    if (splits > mtiles) splits = mtiles;
-    if (splits < 1) splits = 1;
-    const bool det = deterministic();
-    auto ws_need = [&](int sp) { return (size_t)sp * tiles * (256 * 128) + (size_t)sp * p.tiles_n * RW; };
-    if (det) {
-        // deterministic mode: two or more splits always meet in the workspace second stage (fixed order); where the workspace cannot
-        // hold them the contraction is split less, down to one workgroup per output tile (one contributor per element)
-        const size_t have = p.ws ? (size_t)p.ws_floats : 0;
-        while (splits > 1 && ws_need(cdiv(mtiles, cdiv(mtiles, splits))) > have) --splits;
-    }
-    const int per = cdiv(mtiles, splits);
-    p.m_per_split = per * TBM;
-    p.splits = cdiv(mtiles, per);
     const int grid = tiles * p.splits;
     const size_t lds = NarrowRing::NST * (size_t)(TBM * (RW + CW) * 2);
-    static const bool no_ws = getenv("LNX_TN_ATOMIC") != nullptr;  // A/B switch for benchmarking
-    const size_t need = (size_t)p.splits * tiles * (256 * 128) + (size_t)p.splits * p.tiles_n * RW;
-    // padded tiles are stored and re-read whole: with poorly filled tiles (N x K well below tiles x 256 x 128) the atomics move fewer bytes
-    const bool sparse_tiles = (double)p.N * p.k_store < 0.7 * (double)tiles * (256 * 128);
-    if (det) {
-        if (p.splits < 2) p.ws = nullptr;  // (the loop above made the workspace fit otherwise)
-    } else if (no_ws || p.ws == nullptr || (size_t)p.ws_floats < need || p.splits < 2 || sparse_tiles) {
-        p.ws = nullptr;
-    }
-    const bool patch = p.a_mode == LNX_ADDR_PATCH2;
     int rc;
     if (wide_r) rc = patch ? launch_with_lds<gemm_tn_v2_kernel<256, 128, true>>(grid, 512, lds, st, p) : launch_with_lds<gemm_tn_v2_kernel<256, 128, false>>(grid, 512, lds, st, p);
     else rc = patch ? launch_with_lds<gemm_tn_v2_kernel<128, 256, true>>(grid, 512, lds, st, p) : launch_with_lds<gemm_tn_v2_kernel<128, 256, false>>(grid, 512, lds, st, p);

@@ -618,6 +618,7 @@ int with_nt_form(const char* family, bool out_f32, int f, Launch&& launch) {
 
 // gemm.hip: 128x128 register-staged kernels (both storage types)
 int launch_nt_v1(const GemmP& p, int dtype, bool out_f32, hipStream_t st);
+int launch_tn_v1(const WgradP& p, int dtype, hipStream_t st);  // gemm_tn_kernel<T>: fp32, and the bf16 products the ring kernel cannot run
 
 // gemm_skinny.hip: M <= 256 (one wave per 32x32 output tile, operands straight from L2)
 bool nt_skinny_ok(const GemmP& p, int dtype, bool out_f32);
@@ -661,8 +662,21 @@ int launch_nt_v7(const GemmP& p, int f, bool out_f32, hipStream_t st);
 bool nt_v9_ok(const GemmP& p, int f, bool out_f32);
 int launch_nt_v9(const GemmP& p, int f, bool out_f32, hipStream_t st);
 
-// gemm2.hip: weight gradients on the same LDS-DMA ring
-int launch_tn_v2(const WgradP& p, int splits_hint, hipStream_t st, bool defer);
+// What lnx_gemm_tn does with a product (gemm_tn_dispatch.cpp): the kernel, its tile form, the split of the contraction as launched and
+// whether the partial tiles meet in the workspace.  lnx_gemm_tn launches from it, lnx_gemm_tn_query reports it.
+constexpr int TN_RING_ROWS = 64;  // contraction rows per ring stage of gemm_tn_v2_kernel
+struct TnPlan {
+    bool ring;   // gemm_tn_v2_kernel<RW, CW, patch> (gemm2.hip); else gemm_tn_kernel<T> (gemm.hip), RW = CW = 128
+    int RW, CW;
+    bool patch;
+    int tiles_n, tiles_k, splits, m_per_split;
+    bool workspace;  // partial tiles to ws and a second stage; else fp32 atomics
+};
+// p: M / N / K / a_mode / k_store and ws / ws_floats (ws = nullptr: none) are looked at, nothing is dereferenced
+TnPlan tn_plan(const WgradP& p, int dtype, int splits_hint);
+
+// gemm2.hip: weight gradients on the same LDS-DMA ring (p carries the plan: tiles, splits, m_per_split, ws only where t.workspace)
+int launch_tn_v2(const WgradP& p, const TnPlan& t, hipStream_t st, bool defer);
 int tn_flush(hipStream_t st);  // launches the deferred second stages of this thread, if any (st: their stream, or nullptr); 1 = they belong to another stream
 int tn_discard();               // forgets them without launching (error paths / teardown); returns how many
 bool tn_v2_ok(const WgradP& p, int dtype);

@@ -163,10 +163,8 @@ def gemm_nt_mxfp8(A8, a_scales, W8, w_scales, out, *, bias=None, act=L.ACT_NONE,
     return out
 
 
-def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, a_patch=None, k_perm_c=0, k_store=0, splits=0, dtype=None, ws=None,
-            m_dev=None):
-    """m_dev (optional device int32 tensor): the contraction stops at row min(M, m_dev[0]) -- see lnx_wgrad_args.m_dev.  ws (optional fp32 scratch): split-K partial tiles meet there and a second stage sums them in a fixed order; without it (or where
-    it is too small) the splits meet in float atomics -- in deterministic mode the contraction is then split less, down to not at all."""
+def _wgrad_args(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, a_patch=None, k_perm_c=0, k_store=0, splits=0, dtype=None, ws=None,
+                m_dev=None, defer=False) -> L.WgradArgs:
     a = L.WgradArgs()
     a.dtype = dtype if dtype is not None else code_of(dY)
     a.M = M if M is not None else dY.shape[0]
@@ -181,8 +179,47 @@ def gemm_tn(dY, A, dW, *, M=None, N=None, K=None, lda=None, lddw=None, db=None, 
     if ws is not None:
         a.ws, a.ws_floats = _p(ws), ws.numel()
     a.m_dev = _p(m_dev)
+    a.defer = int(bool(defer))
+    return a
+
+
+def gemm_tn(dY, A, dW, **kw):
+    """dW += dY^T . A (and db += colsum(dY)); see lnx_wgrad_args.  Keywords: M, N, K, lda, lddw, db, a_patch = (Hin, Win, Cin), k_perm_c, k_store, splits,
+    dtype, ws, m_dev, defer.
+    m_dev (optional device int32 tensor): the contraction stops at row min(M, m_dev[0]) -- see lnx_wgrad_args.m_dev.  ws (optional fp32 scratch): split-K partial tiles meet there and a second stage sums them in a fixed order; without it (or where
+    it is too small) the splits meet in float atomics -- in deterministic mode the contraction is then split less, down to not at all.
+    defer (with ws): the second stage is postponed to gemm_tn_flush()."""
+    a = _wgrad_args(dY, A, dW, **kw)
     L.check(L.lib().lnx_gemm_tn(C.byref(a), _stream()), "lnx_gemm_tn")
     return dW
+
+
+def gemm_tn_query(dY, A, dW, **kw) -> L.TnLaunch:
+    """What gemm_tn(...) with the same arguments would launch (lnx_gemm_tn_query: kernel, tile form, splits, workspace or atomics); no device work."""
+    a, out = _wgrad_args(dY, A, dW, **kw), L.TnLaunch()
+    L.check(L.lib().lnx_gemm_tn_query(C.byref(a), C.byref(out)), "lnx_gemm_tn_query")
+    return out
+
+
+def gemm_tn_query_shape(*, dtype, M, N, K, lddy=None, lda=None, a_patch=None, k_perm_c=0, k_store=0, splits=0, ws_floats=0) -> L.TnLaunch:
+    """lnx_gemm_tn_query from sizes alone (no tensors, no GPU): ws_floats > 0 stands for a workspace of that many floats."""
+    epv = 4 if dtype == F32 else 8
+    a, out = L.WgradArgs(), L.TnLaunch()
+    a.dtype, a.M, a.N, a.K = dtype, M, N, K
+    a.lddy = lddy if lddy is not None else -(-N // epv) * epv
+    a.lda = lda if lda is not None else (K if a_patch is None else 0)
+    if a_patch is not None:
+        a.a_mode, a.Hin, a.Win, a.Cin = L.ADDR_PATCH2, *a_patch
+    a.k_perm_c, a.splits, a.k_store = k_perm_c, splits, k_store
+    if ws_floats > 0:
+        a.ws, a.ws_floats = C.c_void_p(0x1000), ws_floats  # (never dereferenced: the query looks at "is there one, how large")
+    L.check(L.lib().lnx_gemm_tn_query(C.byref(a), C.byref(out)), "lnx_gemm_tn_query")
+    return out
+
+
+def gemm_tn_flush():
+    """Sums the partial tiles of this thread's deferred gemm_tn products into their dW / db (lnx_gemm_tn_flush)."""
+    L.check(L.lib().lnx_gemm_tn_flush(_stream()), "lnx_gemm_tn_flush")
 
 
 def _ln_args(x, w, b, y, eps, *, M=None, C_=None, ldx=None, ldy=None, x_map=None, y_map=None, add=None, ldadd=None, mean=None, rstd=None, y8=None, y8_scales=None,
