@@ -27,43 +27,35 @@ from . import _lib as L
 from .loss import _cfg_get as _cfg, param_filter
 
 
-def _slot_items(state, items, name):
-    """[(param group, p)] -> ({(group, step): slot}, [(slot, p)]): one hyper-parameter slot per distinct (group, step count)"""
-    slots = {}
-    for gi, p in items:
-        slots.setdefault((gi, int(state[p]["step"])), len(slots))
-    if len(slots) > L.ADAMW_MAX_GROUPS:
-        raise L.LnxError(f"{name}: {len(slots)} distinct (parameter group, step count) combinations, at most {L.ADAMW_MAX_GROUPS} are supported")
-    return slots, [(slots[(gi, int(state[p]["step"]))], p) for gi, p in items]
+def _closure_loss(closure):
+    """the loss of an optimizer's closure, run with gradients enabled; None without a closure"""
+    if closure is None:
+        return None
+    with torch.enable_grad():
+        return closure()
 
 
-def _adamw_descs(state, items):
-    """host lnx_adamw_desc table of [(slot, p)] and its total workgroup count"""
-    lib = L.lib()
-    arr = (L.AdamWDesc * len(items))()
+def _dense_fp32(t, dev, shape=None):
+    """a contiguous fp32 tensor on `dev` (and of `shape`): what the kernels index with flat offsets"""
+    return t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and (shape is None or t.shape == shape)
+
+
+def _desc_table(rows):
+    """host lnx_adamw_desc table of [(slot, p, m, v)] (m, v: state tensors or None) and its total workgroup count"""
+    blocks_of = L.lib().lnx_adamw_blocks
+    arr = (L.AdamWDesc * len(rows))()
     blk = 0
-    for i, (gi, p) in enumerate(items):  # gi: hyper-parameter slot = (param group, step count) combination
-        st = state[p]
-        arr[i].p, arr[i].m, arr[i].v, arr[i].g = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.grad.data_ptr()
-        arr[i].n, arr[i].group, arr[i].block_start = p.numel(), gi, blk
-        blk += lib.lnx_adamw_blocks(C.c_int64(p.numel()))
+    for d, (slot, p, m, v) in zip(arr, rows):  # slot: which entry of the hyper struct the kernel reads for this row
+        d.p, d.m, d.v, d.g = p.data_ptr(), None if m is None else m.data_ptr(), None if v is None else v.data_ptr(), p.grad.data_ptr()
+        d.n, d.group, d.block_start = p.numel(), slot, blk
+        blk += blocks_of(C.c_int64(p.numel()))
     return arr, blk
 
 
-def _grad_table(params, dev):
-    """device lnx_adamw_desc table that carries only the gradients of `params` (all lnx_grad_sumsq reads), its length and workgroups"""
-    lib = L.lib()
-    arr = (L.AdamWDesc * len(params))()
-    blk = 0
-    for i, p in enumerate(params):
-        arr[i].g, arr[i].n, arr[i].block_start = p.grad.data_ptr(), p.numel(), blk
-        blk += lib.lnx_adamw_blocks(C.c_int64(p.numel()))
-    return _upload(arr, dev), len(params), blk
-
-
-def _upload(arr, dev):
-    """a ctypes table on the device, through pinned memory when there is a GPU: the copy does not wait for the device"""
-    host = torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy())
+def _upload(dev, *arrs):
+    """ctypes tables, one behind the other, on the device in one copy: through pinned memory when there is a GPU, so the copy does
+    not wait for the device"""
+    host = torch.from_numpy(np.concatenate([np.frombuffer(a, dtype=np.uint8) for a in arrs]))
     if dev.type != "cuda":
         return host
     host = host.pin_memory()
@@ -72,7 +64,50 @@ def _upload(arr, dev):
     return out
 
 
-class _SharedClip:
+class _NormPass:
+    """The global-norm pass: lnx_grad_sumsq over a device descriptor table (per-workgroup partials + a fixed-order fold) leaves the
+    sum of squares of the table's gradients in the one-element `sumsq`.  An optimizer whose own table lists every gradient calls
+    `run`; `over_grads` keeps a gradient-only table for the others, rebuilt only when a gradient pointer changes."""
+
+    def __init__(self):
+        self.sumsq = None      # the result, a device scalar
+        self._partials = None  # one float per workgroup
+        self._key = None       # what the table of over_grads was built for
+        self._table = None     # (device table, rows, workgroups)
+
+    def reserve(self, dev, blocks):
+        if self.sumsq is None or self.sumsq.device != dev:
+            self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
+        if self._partials is None or self._partials.device != dev or self._partials.numel() < blocks:
+            self._partials = torch.empty(blocks, device=dev, dtype=torch.float32)
+
+    def run(self, table, n, blocks):
+        self.reserve(table.device, blocks)
+        L.check(L.lib().lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self.sumsq.data_ptr()), C.c_void_p(self._partials.data_ptr()),
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_grad_sumsq")
+
+    def over_grads(self, params):
+        key = tuple((p.grad.data_ptr(), p.numel()) for p in params)
+        if key != self._key:
+            arr, blocks = _desc_table([(0, p, None, None) for p in params])
+            self._table = (_upload(params[0].grad.device, arr), len(params), blocks)
+            self._key = key
+        self.run(*self._table)
+
+
+class _Clipped:
+    """What the fused optimizers and the multi-optimizer share: `max_grad_norm`, the norm pass and the norm it leaves"""
+
+    max_grad_norm = None
+
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """total (pre-clip) L2 norm of the gradients seen by the last clipped step (device scalar, no sync); None without clipping"""
+        if self._norm.sumsq is None or self.max_grad_norm is None:
+            return None
+        return self._norm.sumsq.sqrt()[0]
+
+
+class _SharedClip(_Clipped):
     """What the four fused optimizers share: `use_shared_clip(sumsq, max_norm)` hands the optimizer a device scalar with the sum of
     squares of ALL gradients of the run (FusedMultiOptimizer computes it once per step).  The optimizer then makes no norm pass of
     its own and its kernel clips by that scalar; `use_shared_clip(None)` restores its own behaviour."""
@@ -97,85 +132,116 @@ class _SharedClip:
             return self._shared[0].data_ptr(), self._shared[1]
         if self.max_grad_norm is not None and self.max_grad_norm > 0:
             norm_pass()
-            return self._sumsq.data_ptr(), float(self.max_grad_norm)
+            return self._norm.sumsq.data_ptr(), float(self.max_grad_norm)
         return None, 0.0
 
 
-class FusedAdamW(_SharedClip, torch.optim.Optimizer):
+class _ElementwiseOptimizer(_SharedClip, torch.optim.Optimizer):
+    """The step of FusedAdamW, FusedAdEMAMix and FusedSGD: every parameter with a gradient becomes one row of a device descriptor
+    table, every distinct (parameter group, `_state`'s slot key) pair one slot of the hyper struct, and the update is one launch over
+    the table -- after a norm pass over the same table when the optimizer clips by itself.  The table is rebuilt, and the state
+    tensors are validated, only when a slot or a pointer changed.  A subclass gives
+      _STATE, _SLOT, _Hyper                    its state keys (the first two are desc.m and desc.v), what its slot key is, its hyper struct
+      _state(group, p)                         (slot key, state tensors in _STATE order) of p for this step, the state created on first use
+      _fill(h, si, group, slot_key)            slot si of the hyper struct
+      _launch(table, n, blocks, h, sumsq, max_norm, stream)    its lnx_*_step over the table (device address, rows, workgroups)
+    and may give `_check_group` and `_behind`."""
+
+    def _init_step(self, max_grad_norm):
+        self.max_grad_norm = max_grad_norm
+        self._table = None  # (device table, rows, workgroups)
+        self._key = None    # slot and pointers of every row of the table
+        self._norm = _NormPass()
+
+    @staticmethod
+    def _check_group(group):
+        """validation of a group that is repeated at every step: a loaded state dict or a scheduler may have changed it"""
+
+    def _behind(self, items):
+        """further ctypes tables that go behind the descriptors in the same upload"""
+        return ()
+
+    def _build(self, items):
+        dev = items[0][1].device
+        for _, p, tensors in items:  # the kernel indexes every state tensor with the parameter's offsets
+            for k, t in zip(self._STATE, tensors):
+                if not _dense_fp32(t, dev, p.shape):
+                    raise L.LnxError(f"{type(self).__name__}: state '{k}' must be a contiguous fp32 tensor of the parameter's shape on its device")
+        arr, blocks = _desc_table([(si, p, *(tuple(tensors) + (None, None))[:2]) for si, p, tensors in items])
+        self._table = (_upload(dev, arr, *self._behind(items)), len(items), blocks)
+        self._norm.reserve(dev, blocks)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = _closure_loss(closure)
+        name = type(self).__name__
+        slots, items, key = {}, [], []
+        for gi, group in enumerate(self.param_groups):
+            self._check_group(group)
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or g.dtype != torch.float32 or not g.is_contiguous():
+                    raise L.LnxError(f"{name} needs contiguous fp32 parameters and gradients on the GPU")
+                slot_key, tensors = self._state(group, p)
+                si = slots.setdefault((gi, slot_key), len(slots))
+                items.append((si, p, tensors))
+                key.append((si, p.data_ptr(), g.data_ptr(), *[t.data_ptr() for t in tensors]))
+        if not items:
+            return loss
+        if len(slots) > L.ADAMW_MAX_GROUPS:
+            raise L.LnxError(f"{name}: {len(slots)} distinct (parameter group, {self._SLOT}) combinations, at most {L.ADAMW_MAX_GROUPS} are supported")
+        if key != self._key:
+            self._build(items)
+            self._key = key
+        h = self._Hyper()
+        h.ngroups = len(slots)
+        for (gi, slot_key), si in slots.items():
+            self._fill(h, si, self.param_groups[gi], slot_key)
+        table, n, blocks = self._table
+        sumsq, max_norm = self._clip(lambda: self._norm.run(table, n, blocks))
+        self._launch(table.data_ptr(), n, blocks, h, sumsq, max_norm, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        return loss
+
+
+class _AdamFamily(_ElementwiseOptimizer):
+    """State and hyper-parameters that AdamW and AdEMAMix share.  torch.optim.AdamW bias-corrects PER PARAMETER (its own step count).
+    Parameters of one group normally share a step count, but one that was frozen for a while, had no gradient on some steps or came
+    from a checkpoint with mixed steps does not: every distinct (group, step) pair gets its own hyper-parameter slot."""
+
+    _SLOT = "step count"
+
+    def _state(self, group, p):
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = 0
+            for k in self._STATE:
+                st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        t = st["step"] = int(st["step"]) + 1  # int() also accepts the tensor a torch.optim.AdamW state_dict carries
+        return t, [st[k] for k in self._STATE]
+
+    def _fill(self, h, si, group, t):
+        b1, b2 = group["betas"][:2]
+        h.lr[si], h.beta1[si], h.beta2[si], h.eps[si], h.weight_decay[si] = group["lr"], b1, b2, group["eps"], group["weight_decay"]
+        h.bias_c1[si], h.bias_c2[si] = 1.0 - b1 ** float(t), 1.0 - b2 ** float(t)
+        h.omb1[si], h.omb2[si] = 1.0 - b1, 1.0 - b2
+
+
+class FusedAdamW(_AdamFamily):
+    _STATE = ("exp_avg", "exp_avg_sq")
+    _Hyper = L.AdamWHyper
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameters")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) > L.ADAMW_MAX_GROUPS:
             raise ValueError(f"at most {L.ADAMW_MAX_GROUPS} parameter groups")
-        self.max_grad_norm = max_grad_norm
-        self._table = None
-        self._key = None
-        self._sumsq = None
-        self._sumsq_ws = None
+        self._init_step(max_grad_norm)
 
-    # ------------------------------------------------------------------ descriptor table
-    def _build(self, items):
-        dev = items[0][1].device
-        arr, blk = _adamw_descs(self.state, items)
-        host = torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy())
-        self._table = (host.to(dev), len(items), blk)
-        if self._sumsq is None or self._sumsq.device != dev:
-            self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-        if self._sumsq_ws is None or self._sumsq_ws.device != dev or self._sumsq_ws.numel() < blk:
-            self._sumsq_ws = torch.empty(blk, device=dev, dtype=torch.float32)  # one partial per workgroup (lnx_grad_sumsq: fixed-order fold)
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        items = []
-        for gi, group in enumerate(self.param_groups):
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
-                    raise L.LnxError("FusedAdamW needs contiguous fp32 parameters and gradients on the GPU")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] = int(st["step"]) + 1  # int() also accepts the tensor a torch.optim.AdamW state_dict carries
-                items.append((gi, p))
-        if not items:
-            return loss
-        # torch.optim.AdamW bias-corrects PER PARAMETER (its own step count).  Parameters of one group normally share a
-        # step count, but one that was frozen for a while, had no gradient on some steps or came from a checkpoint with
-        # mixed steps does not: every distinct (group, step) pair gets its own hyper-parameter slot.
-        slots, items = _slot_items(self.state, items, "FusedAdamW")
-        key = tuple((si, p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for si, p in items)
-        if key != self._key:
-            self._build(items)
-            self._key = key
-        h = L.AdamWHyper()
-        h.ngroups = len(slots)
-        for (gi, t), si in slots.items():
-            group = self.param_groups[gi]
-            b1, b2 = group["betas"]
-            h.lr[si], h.beta1[si], h.beta2[si], h.eps[si], h.weight_decay[si] = group["lr"], b1, b2, group["eps"], group["weight_decay"]
-            h.bias_c1[si], h.bias_c2[si] = 1.0 - b1 ** float(t), 1.0 - b2 ** float(t)
-            h.omb1[si], h.omb2[si] = 1.0 - b1, 1.0 - b2
-        table, n, blocks = self._table
-        lib = L.lib()
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        sumsq, max_norm = self._clip(lambda: L.check(
-            lib.lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self._sumsq.data_ptr()), C.c_void_p(self._sumsq_ws.data_ptr()), stream), "lnx_grad_sumsq"))
-        L.check(lib.lnx_adamw_step(C.c_void_p(table.data_ptr()), n, blocks, C.byref(h), C.c_void_p(sumsq), C.c_float(max_norm), stream), "lnx_adamw_step")
-        return loss
-
-    def grad_norm(self) -> Optional[torch.Tensor]:
-        """total L2 norm of the gradients seen by the last clipped step (device scalar, no sync); None without clipping"""
-        if self._sumsq is None or self.max_grad_norm is None:
-            return None
-        return self._sumsq.sqrt()[0]
+    def _launch(self, table, n, blocks, h, sumsq, max_norm, stream):
+        L.check(L.lib().lnx_adamw_step(C.c_void_p(table), n, blocks, C.byref(h), C.c_void_p(sumsq), C.c_float(max_norm), stream), "lnx_adamw_step")
 
 
 def ademamix_schedule(step: int, alpha: float, beta1: float, beta3: float, T_alpha_beta3: Optional[float]):
@@ -206,7 +272,7 @@ def _check_ademamix_group(lr, betas, eps, weight_decay, T_alpha_beta3):
             raise ValueError(f"Invalid beta parameters: {betas}: the T_alpha_beta3 schedule needs beta1 > 0 and beta3 > 0")
 
 
-class FusedAdEMAMix(_SharedClip, torch.optim.Optimizer):
+class FusedAdEMAMix(_AdamFamily):
     """AdEMAMix (linnaeus/optimizers/ademamix.py, chosen by OPTIMIZER.NAME = ademamix in optimizers/build.py) as one
     multi-tensor HIP launch per step, three with clipping (lnx_grad_sumsq, then lnx_ademamix_step with the clip folded in),
     instead of the reference's ~13 tensor ops per parameter.
@@ -221,6 +287,9 @@ class FusedAdEMAMix(_SharedClip, torch.optim.Optimizer):
     does that on the device through `use_shared_clip`.  GPU fp32 only.
     """
 
+    _STATE = ("exp_avg", "exp_avg_sq", "exp_avg_slow")
+    _Hyper = L.AdEMAMixHyper
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999, 0.9999), eps: float = 1e-8, weight_decay: float = 0, alpha: float = 5.0,
                  T_alpha_beta3: Optional[float] = None, max_grad_norm: Optional[float] = None):
         _check_ademamix_group(lr, betas, eps, weight_decay, T_alpha_beta3)
@@ -229,82 +298,20 @@ class FusedAdEMAMix(_SharedClip, torch.optim.Optimizer):
             _check_ademamix_group(g["lr"], g["betas"], g["eps"], g["weight_decay"], g["T_alpha_beta3"])
         if len(self.param_groups) > L.ADAMW_MAX_GROUPS:
             raise ValueError(f"at most {L.ADAMW_MAX_GROUPS} parameter groups")
-        self.max_grad_norm = max_grad_norm
-        self._table = None
-        self._key = None
-        self._sumsq = None
-        self._sumsq_ws = None
+        self._init_step(max_grad_norm)
 
-    def _build(self, items):
-        dev = items[0][1].device
-        for _, p in items:  # the kernel indexes every state tensor with the parameter's offsets
-            for k in ("exp_avg", "exp_avg_sq", "exp_avg_slow"):
-                t = self.state[p][k]
-                if t.device != dev or t.dtype != torch.float32 or t.shape != p.shape or not t.is_contiguous():
-                    raise L.LnxError(f"FusedAdEMAMix: state '{k}' must be a contiguous fp32 tensor of the parameter's shape on its device")
-        arr, blk = _adamw_descs(self.state, items)
-        slow = (C.c_uint64 * len(items))(*(self.state[p]["exp_avg_slow"].data_ptr() for _, p in items))
-        descs = np.frombuffer(arr, dtype=np.uint8)
-        host = torch.from_numpy(np.concatenate([descs, np.frombuffer(slow, dtype=np.uint8)]))  # one copy: descriptors, then slow pointers
-        self._table = (host.to(dev), len(descs), len(items), blk)
-        if self._sumsq is None or self._sumsq.device != dev:
-            self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-        if self._sumsq_ws is None or self._sumsq_ws.device != dev or self._sumsq_ws.numel() < blk:
-            self._sumsq_ws = torch.empty(blk, device=dev, dtype=torch.float32)
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        items = []
-        for gi, group in enumerate(self.param_groups):
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
-                    raise L.LnxError("FusedAdEMAMix needs contiguous fp32 parameters and gradients on the GPU")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_slow"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] = int(st["step"]) + 1  # int() also accepts a tensor step
-                items.append((gi, p))
-        if not items:
-            return loss
+    def _fill(self, h, si, group, t):
         # bias corrections, alpha_t and beta3_t all follow each parameter's own step count (as in the reference)
-        slots, items = _slot_items(self.state, items, "FusedAdEMAMix")
-        key = tuple((si, p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
-                     self.state[p]["exp_avg_slow"].data_ptr()) for si, p in items)
-        if key != self._key:
-            self._build(items)
-            self._key = key
-        h = L.AdEMAMixHyper()
-        h.ngroups = len(slots)
-        for (gi, t), si in slots.items():
-            group = self.param_groups[gi]
-            b1, b2, b3 = group["betas"]
-            alpha_t, beta3_t = ademamix_schedule(t, group["alpha"], b1, b3, group["T_alpha_beta3"])
-            h.lr[si], h.beta1[si], h.beta2[si], h.eps[si], h.weight_decay[si] = group["lr"], b1, b2, group["eps"], group["weight_decay"]
-            h.bias_c1[si], h.bias_c2[si] = 1.0 - b1 ** float(t), 1.0 - b2 ** float(t)
-            h.omb1[si], h.omb2[si] = 1.0 - b1, 1.0 - b2
-            h.alpha_t[si], h.beta3_t[si], h.omb3[si] = alpha_t, beta3_t, 1.0 - beta3_t
-        table, nbytes, n, blocks = self._table
-        lib = L.lib()
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        sumsq, max_norm = self._clip(lambda: L.check(
-            lib.lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self._sumsq.data_ptr()), C.c_void_p(self._sumsq_ws.data_ptr()), stream), "lnx_grad_sumsq"))
-        L.check(lib.lnx_ademamix_step(table.data_ptr(), table.data_ptr() + nbytes, n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_ademamix_step")
-        return loss
+        super()._fill(h, si, group, t)
+        b1, _, b3 = group["betas"]
+        alpha_t, beta3_t = ademamix_schedule(t, group["alpha"], b1, b3, group["T_alpha_beta3"])
+        h.alpha_t[si], h.beta3_t[si], h.omb3[si] = alpha_t, beta3_t, 1.0 - beta3_t
 
-    def grad_norm(self) -> Optional[torch.Tensor]:
-        """total L2 norm of the gradients seen by the last clipped step (device scalar, no sync); None without clipping"""
-        if self._sumsq is None or self.max_grad_norm is None:
-            return None
-        return self._sumsq.sqrt()[0]
+    def _behind(self, items):
+        return ((C.c_uint64 * len(items))(*(tensors[2].data_ptr() for _, _, tensors in items)),)  # the slow-EMA pointer of every row
+
+    def _launch(self, table, n, blocks, h, sumsq, max_norm, stream):
+        L.check(L.lib().lnx_ademamix_step(table, table + n * C.sizeof(L.AdamWDesc), n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_ademamix_step")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -459,8 +466,7 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
         self._sent = None     # bytes of the table as last copied to the device
         self._dev = None      # (device table, device tile tables, workspace, partials, MuonInfo)
         self.max_grad_norm = max_grad_norm
-        self._sumsq = None    # own clip: sum of squares of this optimizer's gradients ...
-        self._gtable = None   # ... over a gradient-only descriptor table (key, table, n, blocks, partials)
+        self._norm = _NormPass()  # own clip: over a gradient-only descriptor table
 
     def _build(self, order, dev):
         mats, tiles, info = muon_layout([_muon_shape(p) for _, p in order])
@@ -476,10 +482,7 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = _closure_loss(closure)
         order = [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"]]
         if not order:
             return loss
@@ -492,9 +495,9 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
             return loss
         dev = with_grad[0].device
         for p in with_grad:  # a parameter without a gradient is not touched this step
-            if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+            if not (p.is_cuda and _dense_fp32(p, dev)):
                 raise L.LnxError("FusedMuon needs contiguous fp32 parameters on one GPU")
-            if p.grad.device != dev or p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.shape != p.shape:
+            if not _dense_fp32(p.grad, dev, p.shape):
                 raise L.LnxError("FusedMuon needs contiguous fp32 gradients on the parameters' GPU")
         key = tuple((id(p), tuple(p.shape), int(self.param_groups[gi]["ns_steps"])) for gi, p in order)
         if key != self._key:
@@ -511,7 +514,7 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
                 if "momentum_buffer" not in st:
                     st["momentum_buffer"] = torch.zeros_like(p.grad)
                 buf = st["momentum_buffer"]
-                if buf.device != dev or buf.dtype != torch.float32 or buf.shape != p.shape or not buf.is_contiguous():
+                if not _dense_fp32(buf, dev, p.shape):
                     raise L.LnxError("FusedMuon: state 'momentum_buffer' must be a contiguous fp32 tensor of the parameter's shape on its device")
                 m.g, m.buf = p.grad.data_ptr(), buf.data_ptr()
             rows, cols = _muon_shape(p)
@@ -527,32 +530,15 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
         a = L.MuonStepArgs()
         a.n, a.mats, a.mats_dev, a.tiles_dev = len(order), C.addressof(mats), table.data_ptr(), tiles.data_ptr()
         a.workspace, a.workspace_bytes, a.partials = ws.data_ptr(), ws.numel(), part.data_ptr()
-        a.sumsq, a.max_norm = self._clip(lambda: self._norm_pass(with_grad, dev))
+        a.sumsq, a.max_norm = self._clip(lambda: self._norm.over_grads(with_grad))
         L.check(L.lib().lnx_muon_step(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_muon_step")
         return loss
-
-    def _norm_pass(self, with_grad, dev):
-        key = tuple(p.grad.data_ptr() for p in with_grad)
-        if self._gtable is None or self._gtable[0] != key:
-            table, n, blocks = _grad_table(with_grad, dev)
-            self._gtable = (key, table, n, blocks, torch.empty(blocks, device=dev, dtype=torch.float32))
-        if self._sumsq is None or self._sumsq.device != dev:
-            self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-        _, table, n, blocks, ws = self._gtable
-        L.check(L.lib().lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self._sumsq.data_ptr()), C.c_void_p(ws.data_ptr()),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_grad_sumsq")
-
-    def grad_norm(self) -> Optional[torch.Tensor]:
-        """total L2 norm of the gradients seen by the last clipped step (device scalar, no sync); None without clipping"""
-        if self._sumsq is None or self.max_grad_norm is None:
-            return None
-        return self._sumsq.sqrt()[0]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # SGD (OPTIMIZER.NAME = sgd; optimizers/build.py always builds it with nesterov=True): torch.optim.SGD's update as one launch
 # ----------------------------------------------------------------------------------------------------------------------
-class FusedSGD(_SharedClip, torch.optim.Optimizer):
+class FusedSGD(_ElementwiseOptimizer):
     """`torch.optim.SGD` as one multi-tensor HIP launch per step (lnx_sgd_step), three with clipping, instead of torch's foreach
     passes.  Same `param_groups` keys and per-parameter state (`momentum_buffer`) as `torch.optim.SGD`, so state dicts load both
     ways; a missing or None buffer means "first step for this parameter" (the buffer then starts as the decayed gradient, as in
@@ -560,6 +546,10 @@ class FusedSGD(_SharedClip, torch.optim.Optimizer):
     torch's constructor refuses (Nesterov without momentum or with dampening, negative values).  A parameter without `.grad` is
     skipped.  `max_grad_norm` clips over THIS optimizer's parameters; `use_shared_clip` takes a run's norm instead.  GPU fp32 only.
     """
+
+    _STATE = ("momentum_buffer",)
+    _SLOT = "first step or not"
+    _Hyper = L.SGDHyper
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0, dampening: float = 0, weight_decay: float = 0, nesterov: bool = False,
                  max_grad_norm: Optional[float] = None):
@@ -570,11 +560,7 @@ class FusedSGD(_SharedClip, torch.optim.Optimizer):
             self._check_group(g)
         if len(self.param_groups) > L.ADAMW_MAX_GROUPS // 2:
             raise ValueError(f"at most {L.ADAMW_MAX_GROUPS // 2} parameter groups (two hyper-parameter slots each)")
-        self.max_grad_norm = max_grad_norm
-        self._table = None
-        self._key = None
-        self._sumsq = None
-        self._sumsq_ws = None
+        self._init_step(max_grad_norm)
 
     @staticmethod
     def _check_group(g):
@@ -591,67 +577,22 @@ class FusedSGD(_SharedClip, torch.optim.Optimizer):
         if g["nesterov"] and (g["momentum"] <= 0 or g["dampening"] != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        items, slots = [], {}
-        for gi, group in enumerate(self.param_groups):
-            self._check_group(group)  # a loaded state dict or a scheduler may have changed it
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
-                    raise L.LnxError("FusedSGD needs contiguous fp32 parameters and gradients on the GPU")
-                buf, first = None, False
-                if group["momentum"] != 0:
-                    st = self.state[p]
-                    buf = st.get("momentum_buffer")
-                    first = buf is None
-                    if first:
-                        buf = st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.preserve_format)  # the kernel writes all of it
-                    elif buf.device != p.device or buf.dtype != torch.float32 or buf.shape != p.shape or not buf.is_contiguous():
-                        raise L.LnxError("FusedSGD: state 'momentum_buffer' must be a contiguous fp32 tensor of the parameter's shape on its device")
-                items.append((slots.setdefault((gi, first), len(slots)), p, buf))
-        if not items:
-            return loss
-        key = tuple((si, p.data_ptr(), p.grad.data_ptr(), 0 if buf is None else buf.data_ptr()) for si, p, buf in items)
-        if key != self._key:
-            dev = items[0][1].device
-            lib = L.lib()
-            arr = (L.AdamWDesc * len(items))()
-            blk = 0
-            for i, (si, p, buf) in enumerate(items):
-                arr[i].p, arr[i].m, arr[i].g = p.data_ptr(), None if buf is None else buf.data_ptr(), p.grad.data_ptr()
-                arr[i].n, arr[i].group, arr[i].block_start = p.numel(), si, blk
-                blk += lib.lnx_adamw_blocks(C.c_int64(p.numel()))
-            self._table = (_upload(arr, dev), len(items), blk)
-            if self._sumsq is None or self._sumsq.device != dev:
-                self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-            if self._sumsq_ws is None or self._sumsq_ws.device != dev or self._sumsq_ws.numel() < blk:
-                self._sumsq_ws = torch.empty(blk, device=dev, dtype=torch.float32)
-            self._key = key
-        h = L.SGDHyper()
-        h.ngroups = len(slots)
-        for (gi, first), si in slots.items():
-            g = self.param_groups[gi]
-            h.lr[si], h.momentum[si], h.dampening[si], h.weight_decay[si] = g["lr"], g["momentum"], g["dampening"], g["weight_decay"]
-            h.nesterov[si], h.first[si] = 1 if g["nesterov"] else 0, 1 if first else 0
-        table, n, blocks = self._table
-        lib = L.lib()
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        sumsq, max_norm = self._clip(lambda: L.check(
-            lib.lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self._sumsq.data_ptr()), C.c_void_p(self._sumsq_ws.data_ptr()), stream), "lnx_grad_sumsq"))
-        L.check(lib.lnx_sgd_step(table.data_ptr(), n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_sgd_step")
-        return loss
+    def _state(self, group, p):
+        if group["momentum"] == 0:
+            return False, ()
+        st = self.state[p]
+        buf = st.get("momentum_buffer")
+        first = buf is None
+        if first:
+            buf = st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.preserve_format)  # the kernel writes all of it
+        return first, (buf,)
 
-    def grad_norm(self) -> Optional[torch.Tensor]:
-        """total L2 norm of the gradients seen by the last clipped step (device scalar, no sync); None without clipping"""
-        if self._sumsq is None or self.max_grad_norm is None:
-            return None
-        return self._sumsq.sqrt()[0]
+    def _fill(self, h, si, g, first):
+        h.lr[si], h.momentum[si], h.dampening[si], h.weight_decay[si] = g["lr"], g["momentum"], g["dampening"], g["weight_decay"]
+        h.nesterov[si], h.first[si] = 1 if g["nesterov"] else 0, 1 if first else 0
+
+    def _launch(self, table, n, blocks, h, sumsq, max_norm, stream):
+        L.check(L.lib().lnx_sgd_step(table, n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_sgd_step")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -660,7 +601,7 @@ class FusedSGD(_SharedClip, torch.optim.Optimizer):
 FUSED_OPTIMIZERS = (FusedAdamW, FusedAdEMAMix, FusedSGD, FusedMuon)
 
 
-class FusedMultiOptimizer:
+class FusedMultiOptimizer(_Clipped):
     """The reference's `MultiOptimizer` (same interface: `optimizers`, `param_groups` carrying `optimizer_name` /
     `optimizer_group_idx`, `step`, `zero_grad`, `add_param_group`, `state_dict`, `load_state_dict`) with the gradient clip of
     train.py:279-313 inside `step()`: with `max_grad_norm`, ONE lnx_grad_sumsq pass (two launches, fixed-order fold) over every
@@ -699,8 +640,7 @@ class FusedMultiOptimizer:
                 group["optimizer_name"] = name
                 group["optimizer_group_idx"] = i
                 self.param_groups.append(group)
-        self._sumsq = None
-        self._union = None  # (key, device table, n, blocks, partials)
+        self._norm = _NormPass()  # over the union table
 
     # ------------------------------------------------------------------ step
     def _ordered_params(self):
@@ -709,37 +649,20 @@ class FusedMultiOptimizer:
 
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = _closure_loss(closure)
         if self.max_grad_norm is not None:
             with_grad = [p for p in self._ordered_params() if p.grad is not None]
             if with_grad:
                 dev = with_grad[0].device
                 for p in with_grad:
-                    if not p.grad.is_cuda or p.grad.device != dev or p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
+                    if not (p.grad.is_cuda and _dense_fp32(p.grad, dev)):
                         raise L.LnxError("FusedMultiOptimizer needs contiguous fp32 gradients on one GPU")
-                key = tuple((p.grad.data_ptr(), p.numel()) for p in with_grad)
-                if self._union is None or self._union[0] != key:
-                    table, n, blocks = _grad_table(with_grad, dev)
-                    self._union = (key, table, n, blocks, torch.empty(blocks, device=dev, dtype=torch.float32))
-                if self._sumsq is None or self._sumsq.device != dev:
-                    self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-                _, table, n, blocks, ws = self._union
-                L.check(L.lib().lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self._sumsq.data_ptr()), C.c_void_p(ws.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_grad_sumsq")
+                self._norm.over_grads(with_grad)  # the union table
                 for opt in self.optimizers.values():
-                    opt.use_shared_clip(self._sumsq, self.max_grad_norm)
+                    opt.use_shared_clip(self._norm.sumsq, self.max_grad_norm)
         for opt in self.optimizers.values():
             opt.step()
         return loss
-
-    def grad_norm(self) -> Optional[torch.Tensor]:
-        """pre-clip L2 norm of all gradients of the last step (device scalar, no sync); None without clipping or before a step"""
-        if self._sumsq is None or self.max_grad_norm is None:
-            return None
-        return self._sumsq.sqrt()[0]
 
     def grad_norms(self):
         """(pre-clip norm, post-clip norm, the value clip_grad_norm_ returned) of the last step, the three values train.py:339-348

@@ -114,6 +114,40 @@ def test_fused_adamw_per_parameter_step_counts():
     assert oa.state[pa[1]]["step"] == 3 and oa.state[pa[0]]["step"] == 5
 
 
+@pytest.mark.parametrize("cls, kw, keys", [("FusedAdamW", {}, ("exp_avg", "exp_avg_sq")), ("FusedAdEMAMix", {}, ("exp_avg", "exp_avg_sq", "exp_avg_slow")),
+                                           ("FusedSGD", {"momentum": 0.9}, ("momentum_buffer",))])
+def test_replaced_state_tensors_are_refused_before_any_launch(cls, kw, keys):
+    """The kernels index every state tensor with the parameter's offsets.  One that was replaced (a hand-edited or mismatched
+    checkpoint) by a tensor of another shape, another dtype or by a non-contiguous view makes the step raise, naming the class and
+    the state key, before it launches anything; with the tensor put back the optimizer steps on."""
+    import linnaeus_amd.optim as O
+    from linnaeus_amd import _lib as L
+
+    launches = L.lib().lnx_optim_launches
+    g = torch.Generator().manual_seed(11)
+    params = [torch.nn.Parameter(torch.randn(n, generator=g).cuda()) for n in (8, 4096, 4097)]
+    for p in params:
+        p.grad = torch.randn(p.shape, generator=g).cuda()
+    opt = getattr(O, cls)(params, lr=1e-3, **kw)
+    opt.step()  # creates the state
+    for p in params:
+        n = p.numel()
+        for k in keys:
+            good = opt.state[p][k]
+            for what, bad in (("shape", torch.zeros(n + 1, device="cuda")), ("dtype", torch.zeros(n, device="cuda", dtype=torch.float64)),
+                              ("view", torch.zeros(2 * n, device="cuda")[::2])):
+                assert bad.is_contiguous() == (what != "view") and (bad.shape == p.shape) == (what != "shape")
+                opt.state[p][k] = bad
+                before = launches()
+                with pytest.raises(L.LnxError, match=f"{cls}: state '{k}'"):
+                    opt.step()
+                assert launches() == before, (n, k, what)
+            opt.state[p][k] = good
+    before, old = launches(), [p.detach().clone() for p in params]
+    opt.step()
+    assert launches() == before + 1 and all(not torch.equal(p, o) for p, o in zip(params, old))
+
+
 def test_muon_newton_schulz_and_steps_match_reference(golden_dir):
     """Muon (optimizers/muon.py) on the HIP GEMMs against the reference's own outputs (tests/golden/muon.npz): the
     Newton-Schulz orthogonalisation of wide / tall / non-multiple-of-8 / square matrices, and two optimizer steps on a
