@@ -758,8 +758,18 @@ int lnx_prep_blocks(int rows, int ld, int cols, int ld_t, int has_t);
  *   LNX_CE_FORM_SOFT_ROW   S = soft_target[b, :] (SoftTargetCrossEntropy, loss/basic_loss.py:188-228): sum S is summed, never assumed to be 1, and
  *                          cw = sum_c soft_target[b, c] * class_weight[c].  target is not read; no soft matrix, no ignore_index.  A row whose
  *                          sum is not finite (NaN or infinite entries) gives a NaN loss and a zero gradient row
+ *   LNX_CE_FORM_TAXONOMY   (lnx_version 115) S = row t_b of the taxonomy smoothing matrix, formed per column from two small tables instead of
+ *                          being read from a [C, C] matrix (the table form of TaxonomyAwareLabelSmoothingCE; see lnx_taxonomy_rows below):
+ *                            S[c] = tax_val[t_b, 0] if c == t_b, else tax_val[t_b, k*],  k* = the first k in 1..tax_depth with
+ *                            tax_anc[k-1, c] == tax_anc[k-1, t_b] >= 0, or tax_depth + 1 if there is none
+ *                          soft == NULL, smoothing == 0, target required; sum S is summed like any other row.  Everything else (a target
+ *                          outside [0, C), ignore_index, class_weight, sum_ws) is as in the default form, and with the tables of a matrix
+ *                          (lnx_taxonomy_rows) the same logits give the same bits as with soft = that matrix
+ * sizeof(lnx_softce_args) is 168 bytes with the taxonomy fields (lnx_softce_multi passes 8 of them by value: 1344 bytes of the 4 KB
+ * kernel-argument segment).
  * -----------------------------------------------------------------------------------*/
-enum { LNX_CE_FORM_DEFAULT = 0, LNX_CE_FORM_OFF_TARGET = 1, LNX_CE_FORM_SOFT_ROW = 2 };
+enum { LNX_CE_FORM_DEFAULT = 0, LNX_CE_FORM_OFF_TARGET = 1, LNX_CE_FORM_SOFT_ROW = 2, LNX_CE_FORM_TAXONOMY = 3 };
+#define LNX_TAX_MAX_DEPTH 8 /* levels above the task's own that the taxonomy tables may hold */
 typedef struct lnx_softce_args {
     int B, C;
     const float* logits;       /* [B, ld] fp32 */
@@ -778,6 +788,12 @@ typedef struct lnx_softce_args {
     int form;                  /* LNX_CE_FORM_*; 0 = the two forms above */
     const float* soft_target;  /* LNX_CE_FORM_SOFT_ROW: [B, ldt] per-sample rows; NULL otherwise */
     int64_t ldt;               /* >= C */
+    /* added (lnx_version 115) in front of sum_ws, which stays the last field: the tables of LNX_CE_FORM_TAXONOMY; zero-filled with any
+     * other form: the call as before */
+    const int32_t* tax_anc;    /* [tax_depth, C] level-major: tax_anc[k-1, c] = index at level + k of the k-th ancestor of class c, -1 once the
+                                  chain has ended; may be NULL when tax_depth == 0 */
+    const float* tax_val;      /* [C, tax_depth + 2]: the diagonal value, one value per height 1..tax_depth, one for disconnected classes */
+    int tax_depth;             /* 0..LNX_TAX_MAX_DEPTH */
     float* sum_ws;             /* [B] scratch or NULL.  Deterministic mode with loss_sum: required -- the rows' terms go here and are folded
                                   into loss_sum in row order (otherwise one float atomic per row, in any order); ignored outside the mode */
 } lnx_softce_args;
@@ -786,6 +802,25 @@ int lnx_softce(const lnx_softce_args* args, void* stream);
  * `criteria`, loss/hierarchical_loss.py:130-190) in ONE launch */
 #define LNX_SOFTCE_MAX_TASKS 8
 int lnx_softce_multi(const lnx_softce_args* args, int n, void* stream);
+
+/* Rows of the dense [C, C] matrices that the taxonomy tables stand for (lnx_version 115): the device replacement of
+ * build_taxonomy_smoothing_matrix (loss/taxonomy_label_smoothing.py:30-128) and of TaxonomyTree.build_distance_matrix
+ * (utils/taxonomy/taxonomy_tree.py:364-381) for whoever still wants the matrix, or a few rows of it.  ONE launch, one workgroup per row:
+ *   r = rows ? rows[i] : i;   k(c) = 0 if c == r, else the k* of LNX_CE_FORM_TAXONOMY above (1..depth, or depth + 1 = disconnected)
+ *   what == 0: out[i, c] = val[r, k(c)]                                   (soft labels)
+ *   what == 1: out[i, c] = 0 if c == r, 2 k(c), +inf where disconnected   (distances; val is not read and may be NULL)
+ * for c < C; columns C..ldo-1 of out are not written.  A row index outside [0, C) gives a row of NaN. */
+typedef struct lnx_taxonomy_rows_args {
+    int C, depth;          /* depth in 0..LNX_TAX_MAX_DEPTH */
+    const int32_t* anc;    /* [depth, C] level-major, -1 = the chain has ended; may be NULL when depth == 0 */
+    const float* val;      /* [C, depth + 2] */
+    const int64_t* rows;   /* [n] row indices, or NULL = 0..n-1 */
+    int n;
+    float* out;            /* [n, ldo] fp32 */
+    int64_t ldo;           /* >= C */
+    int what;              /* 0 = soft labels, 1 = distances */
+} lnx_taxonomy_rows_args;
+int lnx_taxonomy_rows(const lnx_taxonomy_rows_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * GPU-side batch mixing of the collate step: selective Mixup / CutMix and the metadata chunk pick.
@@ -1209,7 +1244,8 @@ int lnx_preprocess(const lnx_preprocess_args* args, void* stream);
  * Per task t < n_tasks and row b < B, with the row arithmetic of lnx_softce (same NaN loss / zero gradient for a target outside [0, C)):
  *   class    target[b], or with soft_target the first maximum of soft_target[b, 0..C) (torch.argmax)
  *   raw      = crit_weight[class] * (lse * sum_c S[c] - sum_c S[c] x[c]),  S = soft[class, :] or the smoothed one-hot row; 0 where class == ignore_index
- *              (form LNX_CE_FORM_SOFT_ROW: S = soft_target[b, :] and sum_c soft_target[b, c] * crit_weight[c] in place of crit_weight[class])
+ *              (form LNX_CE_FORM_SOFT_ROW: S = soft_target[b, :] and sum_c soft_target[b, c] * crit_weight[c] in place of crit_weight[class];
+ *               form LNX_CE_FORM_TAXONOMY: S = row `class` of the matrix that tax_anc / tax_val stand for, formed per column, soft == NULL)
  *   null     = target[b] == 0, or soft_target[b, 0] > 0.5
  *   keep     = !null || draws[t * B + b] < prob          (prob >= 1: everything is kept, prob <= 0: no null row; draws is read for 0 < prob < 1 only)
  *   masked   = keep ? raw : 0        (mask_mul != 0, the PHASE1_MASK_NULL_LOSS branch: raw * keep, so that a NaN survives the mask)
@@ -1248,6 +1284,11 @@ typedef struct lnx_hier_loss_task {
     int64_t ldd;
     int form;                   /* LNX_CE_FORM_* of lnx_softce_args; 0 = the forms above.  LNX_CE_FORM_SOFT_ROW needs soft_target, which the
                                    backward reads again; null stays soft_target[b, 0] > 0.5 and the class in the flags the first maximum */
+    /* appended (lnx_version 115): the tables of LNX_CE_FORM_TAXONOMY, as in lnx_softce_args; zero-filled with any other form.  With them
+     * sizeof(lnx_hier_loss_task) is 152 and sizeof(lnx_hier_loss_args) 1280 bytes, passed by value to each kernel (limit: 4 KB) */
+    const int32_t* tax_anc;
+    const float* tax_val;
+    int tax_depth;
 } lnx_hier_loss_task;
 typedef struct lnx_hier_loss_args {
     int dtype;            /* of every task's logits: 0 = fp32, 1 = bf16 */

@@ -87,12 +87,20 @@ class SoftCEArgs(C.Structure):
         ("loss", C.c_void_p), ("loss_sum", C.c_void_p),
         ("dlogits", C.c_void_p), ("ldd", C.c_int64),
         ("form", C.c_int), ("soft_target", C.c_void_p), ("ldt", C.c_int64),
+        ("tax_anc", C.c_void_p), ("tax_val", C.c_void_p), ("tax_depth", C.c_int),
         ("sum_ws", C.c_void_p),
     ]
 
 
 # lnx_softce_args.form / lnx_hier_loss_task.form (the LNX_CE_FORM_* enum of include/lnx.h): how the row S is formed
-CE_FORM_DEFAULT, CE_FORM_OFF_TARGET, CE_FORM_SOFT_ROW = range(3)
+CE_FORM_DEFAULT, CE_FORM_OFF_TARGET, CE_FORM_SOFT_ROW, CE_FORM_TAXONOMY = range(4)
+TAX_MAX_DEPTH = 8  # == LNX_TAX_MAX_DEPTH
+
+
+class TaxonomyRowsArgs(C.Structure):  # == lnx_taxonomy_rows_args
+    _fields_ = [("C", C.c_int), ("depth", C.c_int), ("anc", C.c_void_p), ("val", C.c_void_p), ("rows", C.c_void_p), ("n", C.c_int),
+                ("out", C.c_void_p), ("ldo", C.c_int64), ("what", C.c_int)]
+
 
 ADAMW_MAX_GROUPS = 16
 
@@ -213,7 +221,8 @@ HL_NULL_TOTAL, HL_NULL_INCLUDED, HL_COUNTS = 8, 9, 10
 class HierLossTask(C.Structure):  # == lnx_hier_loss_task
     _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("C", C.c_int), ("target", C.c_void_p), ("soft_target", C.c_void_p), ("ldt", C.c_int64),
                 ("soft", C.c_void_p), ("smoothing", C.c_float), ("crit_weight", C.c_void_p), ("ignore_index", C.c_int64), ("class_weight", C.c_void_p),
-                ("n_cw", C.c_int), ("p_cw", C.c_int), ("p_w", C.c_int), ("dlogits", C.c_void_p), ("ldd", C.c_int64), ("form", C.c_int)]
+                ("n_cw", C.c_int), ("p_cw", C.c_int), ("p_w", C.c_int), ("dlogits", C.c_void_p), ("ldd", C.c_int64), ("form", C.c_int),
+                ("tax_anc", C.c_void_p), ("tax_val", C.c_void_p), ("tax_depth", C.c_int)]
 
 
 class HierLossArgs(C.Structure):  # == lnx_hier_loss_args
@@ -281,6 +290,8 @@ def lib() -> C.CDLL:
         if hasattr(_lib, "lnx_hier_loss_fwd"):
             _lib.lnx_hier_loss_fwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p]
             _lib.lnx_hier_loss_bwd.argtypes = [C.POINTER(HierLossArgs), C.c_void_p, C.c_void_p]
+        if hasattr(_lib, "lnx_taxonomy_rows"):
+            _lib.lnx_taxonomy_rows.argtypes = [C.POINTER(TaxonomyRowsArgs), C.c_void_p]
         if hasattr(_lib, "lnx_hier_refine_fwd"):
             _lib.lnx_hier_refine_fwd.argtypes = [C.POINTER(HierRefineArgs), C.c_void_p]
             _lib.lnx_hier_refine_bwd.argtypes = [C.POINTER(HierRefineArgs), C.c_void_p]
@@ -359,7 +370,7 @@ EXPORTS = [
     "lnx_dwconv7_fwd", "lnx_dwconv7_fwd_kept", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_kept", "lnx_dwconv7_wgrad_ws_floats",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_fwd_compact", "lnx_attn_bwd_compact", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_drop_compact_conv_blocks", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
-    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
+    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_taxonomy_rows", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_hier_refine_fwd", "lnx_hier_refine_bwd", "lnx_hier_refine_launches",
     "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",

@@ -9,6 +9,7 @@
 //   hier_bwd_kernel    grid (B, tasks): dlogits from (lse, sum S, coef) of the forward, the fold's scale and the device scalar `go`
 #include "common.hpp"
 #include "../../include/lnx.h"
+#include "taxonomy.hpp"
 
 namespace {
 
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     __shared__ float red[4];
     __shared__ float best_v[4];
     __shared__ int best_i[4];
+    __shared__ TaxRow trow;
     const lnx_hier_loss_task& k = a.task[blockIdx.y];
     const int b = blockIdx.x, tid = threadIdx.x, Cn = k.C;
     const T* x = static_cast<const T*>(k.logits) + (int64_t)b * k.ld;
@@ -111,6 +113,9 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     bool bad = t < 0 || t >= Cn;
     const bool ignored = k.ignore_index >= 0 && t == k.ignore_index && !soft_row;
     const float* srow = (k.soft != nullptr && !bad && !soft_row) ? k.soft + t * (int64_t)Cn : nullptr;
+    // LNX_CE_FORM_TAXONOMY: row t of the matrix is formed per column from the tables (uniform over the workgroup)
+    const bool tax = k.form == LNX_CE_FORM_TAXONOMY && !bad;
+    if (tax) tax_load(&trow, k.tax_anc, k.tax_val, k.tax_depth, Cn, t);
     float at, off;
     smooth_pair(k, at, off);
     float mx = -INFINITY;
@@ -120,7 +125,7 @@ __global__ __launch_bounds__(HL_T) void hier_rows_kernel(const lnx_hier_loss_arg
     for (int c = tid; c < Cn; c += HL_T) {
         const float v = to_f(x[c]);
         se += __expf(v - mx);
-        const float sv = soft_row ? st[c] : soft_at(srow, c, t, at, off);
+        const float sv = soft_row ? st[c] : (tax ? tax_at(&trow, k.tax_anc, k.tax_depth, Cn, c, t) : soft_at(srow, c, t, at, off));
         sx = fmaf(sv, v, sx);
         ss += sv;
     }
@@ -232,6 +237,15 @@ __global__ __launch_bounds__(HL_T) void hier_bwd_kernel(const lnx_hier_loss_args
         }
         return;
     }
+    if (k.form == LNX_CE_FORM_TAXONOMY) {  // S from the tables, as the forward formed it
+        __shared__ TaxRow trow;
+        tax_load(&trow, k.tax_anc, k.tax_val, k.tax_depth, Cn, t);
+        for (int c = tid; c < Cn; c += HL_T) {
+            const float p = __expf(to_f(x[c]) - lse);
+            d[c] = g * (p * ss - tax_at(&trow, k.tax_anc, k.tax_depth, Cn, c, t));
+        }
+        return;
+    }
     const float* srow = k.soft ? k.soft + t * (int64_t)Cn : nullptr;
     float at, off;
     smooth_pair(k, at, off);
@@ -263,8 +277,8 @@ int hier_check(const lnx_hier_loss_args* a, const char* who) {
                   k.class_weight ? "given" : "NULL", k.n_cw, k.p_w);
         LNX_CHECK(!(k.class_weight && k.soft_target) || k.n_cw >= k.C, "%s: task %d has n_cw=%d < C=%d with soft_target", who, t, k.n_cw, k.C);
         LNX_CHECK(k.dlogits == nullptr || k.ldd >= k.C, "%s: task %d has ldd=%lld < C=%d", who, t, (long long)k.ldd, k.C);
-        LNX_CHECK(k.form == LNX_CE_FORM_DEFAULT || k.form == LNX_CE_FORM_OFF_TARGET || k.form == LNX_CE_FORM_SOFT_ROW,
-                  "%s: task %d has form=%d (0 = default, 1 = off-target smoothing, 2 = soft row)", who, t, k.form);
+        LNX_CHECK(k.form == LNX_CE_FORM_DEFAULT || k.form == LNX_CE_FORM_OFF_TARGET || k.form == LNX_CE_FORM_SOFT_ROW || k.form == LNX_CE_FORM_TAXONOMY,
+                  "%s: task %d has form=%d (0 = default, 1 = off-target smoothing, 2 = soft row, 3 = taxonomy tables)", who, t, k.form);
         if (k.form == LNX_CE_FORM_OFF_TARGET) {
             LNX_CHECK(k.C >= 2, "%s: off-target smoothing needs C >= 2, task %d has C=%d (smoothing / (C - 1))", who, t, k.C);
             LNX_CHECK(k.soft == nullptr, "%s: off-target smoothing excludes a [C, C] soft matrix (task %d)", who, t);
@@ -273,6 +287,14 @@ int hier_check(const lnx_hier_loss_args* a, const char* who) {
             LNX_CHECK(k.soft_target, "%s: the soft-row form needs soft_target (task %d)", who, t);
             LNX_CHECK(k.soft == nullptr, "%s: the soft-row form excludes a [C, C] soft matrix (task %d)", who, t);
             LNX_CHECK(k.ignore_index < 0, "%s: the soft-row form has no ignore_index (task %d has %lld)", who, t, (long long)k.ignore_index);
+        }
+        if (k.form == LNX_CE_FORM_TAXONOMY) {
+            LNX_CHECK(k.soft == nullptr, "%s: form=3 (taxonomy tables) excludes a [C, C] soft matrix (task %d)", who, t);
+            LNX_CHECK(k.smoothing == 0.f, "%s: form=3 (taxonomy tables) has no uniform smoothing (task %d has %g)", who, t, (double)k.smoothing);
+            LNX_CHECK(k.tax_depth >= 0 && k.tax_depth <= LNX_TAX_MAX_DEPTH, "%s: task %d has tax_depth=%d (0..%d)", who, t, k.tax_depth, LNX_TAX_MAX_DEPTH);
+            LNX_CHECK(k.tax_val && (k.tax_anc || k.tax_depth == 0), "%s: form=3 (taxonomy tables) needs tax_val, and tax_anc when tax_depth > 0 (task %d)", who, t);
+        } else {
+            LNX_CHECK(k.tax_anc == nullptr && k.tax_val == nullptr, "%s: task %d has taxonomy tables with form=%d: they belong to form 3", who, t, k.form);
         }
     }
     return 0;

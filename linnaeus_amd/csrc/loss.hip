@@ -6,6 +6,7 @@
 // One 256-thread workgroup per sample row; everything fp32; exp/log only on the row maximum-shifted values.
 #include "common.hpp"
 #include "../../include/lnx.h"
+#include "taxonomy.hpp"
 
 namespace {
 
@@ -23,6 +24,7 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
 
 __device__ __forceinline__ void softce_row(const lnx_softce_args& a, const int b) {
     __shared__ float red[4];
+    __shared__ TaxRow trow;
     const float* x = a.logits + (int64_t)b * a.ld;
     // LNX_CE_FORM_SOFT_ROW: the row S is the sample's own target row (SoftTargetCrossEntropy); target is not read
     const float* st = a.form == LNX_CE_FORM_SOFT_ROW ? a.soft_target + (int64_t)b * a.ldt : nullptr;
@@ -30,6 +32,9 @@ __device__ __forceinline__ void softce_row(const lnx_softce_args& a, const int b
     bool bad = t < 0 || t >= a.C;  // out-of-range targets produce NaN loss and zero gradient (the host checks them when asked to)
     const bool ignored = a.ignore_index >= 0 && t == a.ignore_index && !st;
     const float* srow = (a.soft != nullptr && !bad) ? a.soft + t * (int64_t)a.C : nullptr;
+    // LNX_CE_FORM_TAXONOMY: row t of the matrix is formed per column from the tables (uniform over the workgroup, like every test above)
+    const bool tax = a.form == LNX_CE_FORM_TAXONOMY && !bad;
+    if (tax) tax_load(&trow, a.tax_anc, a.tax_val, a.tax_depth, a.C, t);
     // at the class / elsewhere: torch's uniform smoothing, or LabelSmoothingCrossEntropy's eps / (C - 1) off the target only
     const bool off_target = a.form == LNX_CE_FORM_OFF_TARGET;
     const float on = 1.0f - a.smoothing, off = a.smoothing / (float)(off_target ? a.C - 1 : a.C);
@@ -42,7 +47,7 @@ __device__ __forceinline__ void softce_row(const lnx_softce_args& a, const int b
     for (int c = threadIdx.x; c < a.C; c += 256) {
         const float v = x[c];
         se += __expf(v - mx);
-        const float sv = st ? st[c] : (srow ? srow[c] : (c == t ? at : off));
+        const float sv = st ? st[c] : (srow ? srow[c] : (tax ? tax_at(&trow, a.tax_anc, a.tax_depth, a.C, c, t) : (c == t ? at : off)));
         sx = fmaf(sv, v, sx);
         ss += sv;
         if (st && a.class_weight) sw = fmaf(sv, a.class_weight[c], sw);
@@ -77,7 +82,7 @@ __device__ __forceinline__ void softce_row(const lnx_softce_args& a, const int b
         }
         for (int c = threadIdx.x; c < a.C; c += 256) {
             const float p = __expf(x[c] - mx) * inv;
-            const float sv = st ? st[c] : (srow ? srow[c] : (c == t ? at : off));
+            const float sv = st ? st[c] : (srow ? srow[c] : (tax ? tax_at(&trow, a.tax_anc, a.tax_depth, a.C, c, t) : (c == t ? at : off)));
             d[c] = g * (p * ss - sv);
         }
     }
@@ -94,13 +99,30 @@ __global__ __launch_bounds__(256) void softce_multi_kernel(const SoftceMulti m) 
     if ((int)blockIdx.x < a.B) softce_row(a, blockIdx.x);
 }
 
+// lnx_taxonomy_rows: one workgroup per output row
+__global__ __launch_bounds__(256) void taxonomy_rows_kernel(const lnx_taxonomy_rows_args a) {
+    __shared__ TaxRow trow;
+    const int i = blockIdx.x;
+    const int64_t r = a.rows ? a.rows[i] : (int64_t)i;
+    float* o = a.out + (int64_t)i * a.ldo;
+    if (r < 0 || r >= a.C) {  // (uniform over the workgroup)
+        for (int c = threadIdx.x; c < a.C; c += 256) o[c] = NAN;
+        return;
+    }
+    tax_load(&trow, a.anc, a.what == 0 ? a.val : nullptr, a.depth, a.C, r);
+    for (int c = threadIdx.x; c < a.C; c += 256) {
+        const int k = tax_height(&trow, a.anc, a.depth, a.C, c, r);
+        o[c] = a.what == 0 ? trow.val[k] : (k > a.depth ? INFINITY : 2.0f * (float)k);
+    }
+}
+
 }  // namespace
 
 // the argument checks of both entry points, before any launch
 static int softce_check(const lnx_softce_args* a, const char* who, int i) {
     const bool soft_row = a->form == LNX_CE_FORM_SOFT_ROW;
-    LNX_CHECK(a->form == LNX_CE_FORM_DEFAULT || a->form == LNX_CE_FORM_OFF_TARGET || soft_row, "%s: form=%d in set %d (0 = default, 1 = off-target smoothing, 2 = soft row)", who,
-              a->form, i);
+    LNX_CHECK(a->form == LNX_CE_FORM_DEFAULT || a->form == LNX_CE_FORM_OFF_TARGET || soft_row || a->form == LNX_CE_FORM_TAXONOMY,
+              "%s: form=%d in set %d (0 = default, 1 = off-target smoothing, 2 = soft row, 3 = taxonomy tables)", who, a->form, i);
     LNX_CHECK(a->logits && (a->target || soft_row), "%s: null operand in set %d", who, i);
     LNX_CHECK(a->B > 0 && a->C > 0 && a->ld >= a->C, "%s: bad shape B=%d C=%d ld=%lld in set %d", who, a->B, a->C, (long long)a->ld, i);
     LNX_CHECK(a->dlogits == nullptr || a->ldd >= a->C, "%s: ldd < C in set %d", who, i);
@@ -114,6 +136,14 @@ static int softce_check(const lnx_softce_args* a, const char* who, int i) {
         LNX_CHECK(a->ldt >= a->C, "%s: ldt=%lld < C=%d in set %d", who, (long long)a->ldt, a->C, i);
         LNX_CHECK(a->soft == nullptr, "%s: the soft-row form excludes a [C, C] soft matrix (set %d)", who, i);
         LNX_CHECK(a->ignore_index < 0, "%s: the soft-row form has no ignore_index (set %d has %lld)", who, i, (long long)a->ignore_index);
+    }
+    if (a->form == LNX_CE_FORM_TAXONOMY) {
+        LNX_CHECK(a->soft == nullptr, "%s: form=3 (taxonomy tables) excludes a [C, C] soft matrix (set %d)", who, i);
+        LNX_CHECK(a->smoothing == 0.f, "%s: form=3 (taxonomy tables) has no uniform smoothing (set %d has %g)", who, i, (double)a->smoothing);
+        LNX_CHECK(a->tax_depth >= 0 && a->tax_depth <= LNX_TAX_MAX_DEPTH, "%s: tax_depth=%d in set %d (0..%d)", who, a->tax_depth, i, LNX_TAX_MAX_DEPTH);
+        LNX_CHECK(a->tax_val && (a->tax_anc || a->tax_depth == 0), "%s: form=3 (taxonomy tables) needs tax_val, and tax_anc when tax_depth > 0 (set %d)", who, i);
+    } else {
+        LNX_CHECK(a->tax_anc == nullptr && a->tax_val == nullptr, "%s: taxonomy tables given with form=%d (set %d): they belong to form 3", who, a->form, i);
     }
     // the row sums meet in one float atomic per row unless the rows' terms go through sum_ws (deterministic mode)
     LNX_CHECK(a->loss_sum == nullptr || a->sum_ws != nullptr || !deterministic(),
@@ -151,6 +181,19 @@ extern "C" int lnx_softce(const lnx_softce_args* a, void* stream) {
     softce_route(q);
     hipLaunchKernelGGL(softce_kernel, dim3(q.B), dim3(256), 0, (hipStream_t)stream, q);
     if (q.sum_ws) launch_fold(q.sum_ws, q.B, 1, 1, q.loss_sum, (hipStream_t)stream);
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_taxonomy_rows(const lnx_taxonomy_rows_args* a, void* stream) {
+    LNX_CHECK(a, "lnx_taxonomy_rows: null operand");
+    LNX_CHECK(a->C > 0 && a->n > 0, "lnx_taxonomy_rows: bad shape C=%d n=%d", a->C, a->n);
+    LNX_CHECK(a->depth >= 0 && a->depth <= LNX_TAX_MAX_DEPTH, "lnx_taxonomy_rows: depth=%d (0..%d)", a->depth, LNX_TAX_MAX_DEPTH);
+    LNX_CHECK(a->what == 0 || a->what == 1, "lnx_taxonomy_rows: what=%d (0 = soft labels, 1 = distances)", a->what);
+    LNX_CHECK(a->anc || a->depth == 0, "lnx_taxonomy_rows: null anc with depth=%d", a->depth);
+    LNX_CHECK(a->val || a->what == 1, "lnx_taxonomy_rows: the soft labels need val");
+    LNX_CHECK(a->out && a->ldo >= a->C, "lnx_taxonomy_rows: null out or ldo=%lld < C=%d", (long long)a->ldo, a->C);
+    hipLaunchKernelGGL(taxonomy_rows_kernel, dim3(a->n), dim3(256), 0, (hipStream_t)stream, *a);
     LNX_LAUNCH_CHECK();
     return 0;
 }

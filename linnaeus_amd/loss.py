@@ -2,7 +2,9 @@
 of the train step as single HIP launches (`lnx_softce`, csrc/loss.hip) behind the reference's module interface.
 
   TaxonomyAwareLabelSmoothingCE  <- linnaeus/loss/taxonomy_label_smoothing.py:131-408 (same constructor, same
-                                    [B] per-sample return, same ignore_index / class-weight behaviour, same errors)
+                                    [B] per-sample return, same ignore_index / class-weight behaviour, same errors);
+                                    from_tables / TaxonomySmoothingTables / generate_taxonomy_tables: the same criterion
+                                    without the [C, C] matrix (<- utils/taxonomy/taxonomy_utils.py:24-254, taxonomy_tree.py:364-381)
   CrossEntropyLoss, LabelSmoothingCrossEntropy, SoftTargetCrossEntropy
                                  <- linnaeus/loss/basic_loss.py:15-228, the other three names of LOSS.TASK_SPECIFIC.*.FUNCS
   get_loss_function / prepare_loss_functions <- linnaeus/loss/utils.py:58-294; convert_criteria maps criteria the reference
@@ -29,7 +31,9 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_scale, scale, loss, loss_sum, dlogits, form=0, soft_target=None, sum_ws=None):
+def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_scale, scale, loss, loss_sum, dlogits, form=0, soft_target=None, sum_ws=None,
+          tax=None):
+    """`tax`: (anc, val, depth) of a criterion in table form (form CE_FORM_TAXONOMY), on the logits' device"""
     if not logits.is_cuda:
         raise L.LnxError("linnaeus_amd.loss has no CPU path: logits must be on the GPU")
     a.B, a.C = logits.shape
@@ -43,6 +47,8 @@ def _fill(a, logits, target, soft, smoothing, class_weight, ignore_index, row_sc
     a.dlogits, a.ldd = _ptr(dlogits), (dlogits.stride(0) if dlogits is not None else 0)
     a.form, a.soft_target, a.ldt = int(form), _ptr(soft_target), (soft_target.stride(0) if soft_target is not None else 0)
     a.sum_ws = _ptr(sum_ws)
+    if tax is not None:
+        a.tax_anc, a.tax_val, a.tax_depth = _ptr(tax[0]), _ptr(tax[1]), int(tax[2])
 
 
 def _launch(*args):
@@ -74,25 +80,28 @@ class _SoftCE(torch.autograd.Function):
     """per-sample loss [B]; the unit gradient (d loss[b] / d logits[b, :]) is produced by the same launch"""
 
     @staticmethod
-    def forward(ctx, logits, target, soft, class_weight, ignore_index, smoothing, form=0, soft_target=None):
+    def forward(ctx, logits, target, soft, class_weight, ignore_index, smoothing, form=0, soft_target=None, tax=None):
         x = _as_rows(logits)
         B, Cn = x.shape
         loss = torch.empty(B, device=x.device, dtype=torch.float32)
         need = logits.requires_grad
         unit = torch.empty(B, Cn, device=x.device, dtype=torch.float32) if need else None
-        _launch(x, target, soft, smoothing, class_weight, ignore_index, None, 1.0, loss, None, unit, form, soft_target)
+        _launch(x, target, soft, smoothing, class_weight, ignore_index, None, 1.0, loss, None, unit, form, soft_target, None, tax)
         ctx.unit = unit
         ctx.in_dtype = logits.dtype
         return loss
 
     @staticmethod
     def backward(ctx, go):
-        return (ctx.unit * go.unsqueeze(1)).to(ctx.in_dtype), None, None, None, None, None, None, None
+        return (ctx.unit * go.unsqueeze(1)).to(ctx.in_dtype), None, None, None, None, None, None, None, None
 
 
 class TaxonomyAwareLabelSmoothingCE(nn.Module):
     """Label-smoothing cross entropy whose soft labels come from a precomputed [C, C] distribution matrix
-    (row c = distribution over classes when the true class is c).  Returns per-sample losses [B]."""
+    (row c = distribution over classes when the true class is c).  Returns per-sample losses [B].
+
+    `from_tables` builds the same criterion from TaxonomySmoothingTables instead: no [C, C] matrix exists anywhere, the kernel
+    forms each row from the tables (`soft_labels` is None, the buffers are `tax_anc` / `tax_val`)."""
 
     def __init__(self, soft_label_matrix: torch.Tensor, weight: Optional[torch.Tensor] = None, apply_class_weights: bool = False,
                  ignore_index: Optional[int] = None, config: Optional[Any] = None):
@@ -101,6 +110,10 @@ class TaxonomyAwareLabelSmoothingCE(nn.Module):
             raise ValueError("soft_label_matrix must be square [C, C].")
         self.num_classes = soft_label_matrix.shape[0]
         self.register_buffer("soft_labels", soft_label_matrix.clone().float().contiguous())
+        self.tables = None
+        self._init_common(weight, apply_class_weights, ignore_index, config)
+
+    def _init_common(self, weight, apply_class_weights, ignore_index, config):
         self.apply_class_weights = apply_class_weights
         self.ignore_index = ignore_index
         self.config = config
@@ -111,6 +124,34 @@ class TaxonomyAwareLabelSmoothingCE(nn.Module):
                 weight = torch.tensor(weight, dtype=torch.float32)
             self.register_buffer("class_weight", weight.clone().float().contiguous())
             self.weight = self.class_weight
+
+    @classmethod
+    def from_tables(cls, tables: "TaxonomySmoothingTables", weight: Optional[torch.Tensor] = None, apply_class_weights: bool = False,
+                    ignore_index: Optional[int] = None, config: Optional[Any] = None) -> "TaxonomyAwareLabelSmoothingCE":
+        """The criterion of the matrix `tables` stand for, without the matrix: same forward, same `validate_targets` behaviour, same
+        attributes, `soft_labels = None`, and the int32 [D, C] / fp32 [C, D + 2] buffers `tax_anc` / `tax_val` in its place."""
+        if not isinstance(tables, TaxonomySmoothingTables):
+            raise TypeError(f"from_tables needs TaxonomySmoothingTables, got {type(tables).__name__}")
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.num_classes = tables.num_classes
+        self.register_buffer("soft_labels", None)
+        self.register_buffer("tax_anc", tables.anc.clone())
+        self.register_buffer("tax_val", tables.val.clone())
+        self.tables = tables
+        self._init_common(weight, apply_class_weights, ignore_index, config)
+        return self
+
+    def _row_source(self, dev):
+        """(soft, form, tax) for _fill on `dev`: the [C, C] matrix with the default form, or (anc, val, depth) with CE_FORM_TAXONOMY;
+        the buffers are moved once when they live elsewhere"""
+        if self.soft_labels is not None:
+            if self.soft_labels.device != dev:
+                self.soft_labels = self.soft_labels.to(dev)
+            return self.soft_labels, L.CE_FORM_DEFAULT, None
+        if self.tax_val.device != dev:
+            self.tax_anc, self.tax_val = self.tax_anc.to(dev), self.tax_val.to(dev)
+        return None, L.CE_FORM_TAXONOMY, (self.tax_anc, self.tax_val, self.tables.depth)
 
     def forward(self, logits, target: torch.Tensor) -> torch.Tensor:
         if isinstance(logits, dict):  # output of a ConditionalClassifierHead: first [B, num_classes] tensor
@@ -132,14 +173,13 @@ class TaxonomyAwareLabelSmoothingCE(nn.Module):
         elif target.dim() != 1:
             raise ValueError(f"Target tensor has invalid shape {target.shape}. Expected 1D indices or [B, C] one-hot/soft-representing-one-class.")
         target = target.to(logits.device, torch.long).contiguous()
-        if self.soft_labels.device != logits.device:
-            self.soft_labels = self.soft_labels.to(logits.device)
+        soft, form, tax = self._row_source(logits.device)
         cw = None
         if self.apply_class_weights and self.weight is not None:
             if self.weight.device != logits.device:
                 self.weight = self.class_weight = self.weight.to(logits.device)
             cw = self.weight
-        loss = _SoftCE.apply(logits, target, self.soft_labels, cw, self.ignore_index, 0.0, L.CE_FORM_DEFAULT, None)
+        loss = _SoftCE.apply(logits, target, soft, cw, self.ignore_index, 0.0, form, None, tax)
         # Out-of-range targets surface as NaN rows from the kernel; the reference raises IndexError for them
         # (taxonomy_label_smoothing.py:330-343, itself a host sync).  This check is ONE host<->device sync per call:
         # set `validate_targets = False` on the criterion to keep the launch queue asynchronous (NaN rows then
@@ -273,9 +313,9 @@ LOSS_FUNCTIONS = ("CrossEntropyLoss", "SoftTargetCrossEntropy", "LabelSmoothingC
 
 
 def get_loss_function(loss_type: str, config, class_weights=None, is_train: bool = True, task_key: Optional[str] = None,
-                      taxonomy_matrices: Optional[Dict[str, torch.Tensor]] = None, ignore_index: Optional[int] = None, taxonomy_tree=None) -> nn.Module:
+                      taxonomy_matrices: Optional[Dict[str, Any]] = None, ignore_index: Optional[int] = None, taxonomy_tree=None) -> nn.Module:
     """The criterion `loss_type` names (loss/utils.py:153-294: the same name table, the same LOSS.GRAD_WEIGHTING.CLASS.TRAIN / .VAL
-    switch).  A class-weight dict {class: weight} becomes a [max index + 1] tensor with missing entries 1.0; a tensor is passed on.
+    switch).  `taxonomy_matrices[task]` is a [C, C] tensor or TaxonomySmoothingTables (generate_taxonomy_tables: no matrix is built).  A class-weight dict {class: weight} becomes a [max index + 1] tensor with missing entries 1.0; a tensor is passed on.
     `taxonomy_tree` is accepted and unused, as in the reference."""
     apply_class_weights = config.LOSS.GRAD_WEIGHTING.CLASS.TRAIN if is_train else config.LOSS.GRAD_WEIGHTING.CLASS.VAL
     weight = None
@@ -300,6 +340,9 @@ def get_loss_function(loss_type: str, config, class_weights=None, is_train: bool
             raise ValueError("task_key must be provided for TaxonomyAwareLabelSmoothing")
         if taxonomy_matrices is None or task_key not in taxonomy_matrices:
             raise ValueError(f"No taxonomy smoothing matrix found for task '{task_key}'")
+        if isinstance(taxonomy_matrices[task_key], TaxonomySmoothingTables):
+            return TaxonomyAwareLabelSmoothingCE.from_tables(taxonomy_matrices[task_key], weight=weight, apply_class_weights=apply_class_weights,
+                                                             ignore_index=ignore_index, config=config)
         return TaxonomyAwareLabelSmoothingCE(soft_label_matrix=taxonomy_matrices[task_key], weight=weight, apply_class_weights=apply_class_weights,
                                              ignore_index=ignore_index, config=config)
     raise ValueError(f"Unsupported loss function type: {loss_type}")
@@ -313,7 +356,7 @@ def _per_task(value, task_keys, name: str) -> list:
     return [value for _ in task_keys]
 
 
-def prepare_loss_functions(config, class_weights_train=None, class_weights_val=None, taxonomy_matrices: Optional[Dict[str, torch.Tensor]] = None):
+def prepare_loss_functions(config, class_weights_train=None, class_weights_val=None, taxonomy_matrices: Optional[Dict[str, Any]] = None):
     """(criteria_train, criteria_val), {task: criterion} over config.DATA.TASK_KEYS_H5 from LOSS.TASK_SPECIFIC.TRAIN.FUNCS / VAL.FUNCS
     (loss/utils.py:58-150), with ignore_index = 0 under TRAIN.PHASE1_MASK_NULL_LOSS.  The class weights are {task: {class: weight}}
     (or tensors) per split: computing them from label counts (calculate_class_weights) stays with the caller."""
@@ -340,6 +383,9 @@ def convert_criterion(crit):
         if name == "SoftTargetCrossEntropy":
             return SoftTargetCrossEntropy(weight=crit.weight, apply_class_weights=crit.apply_class_weights)
         if name == "TaxonomyAwareLabelSmoothingCE":
+            if getattr(crit, "soft_labels", None) is None and isinstance(getattr(crit, "tables", None), TaxonomySmoothingTables):  # table form
+                return TaxonomyAwareLabelSmoothingCE.from_tables(crit.tables, weight=crit.weight, apply_class_weights=crit.apply_class_weights,
+                                                                 ignore_index=crit.ignore_index, config=getattr(crit, "config", None))
             return TaxonomyAwareLabelSmoothingCE(crit.soft_labels, weight=crit.weight, apply_class_weights=crit.apply_class_weights,
                                                  ignore_index=crit.ignore_index, config=getattr(crit, "config", None))
     except AttributeError as e:
@@ -450,6 +496,207 @@ def build_taxonomy_smoothing_matrix(num_classes: int, distances: torch.Tensor, a
     probs = probs.masked_fill(eye, 1.0 - alpha)
     tot = probs.sum(1, keepdim=True)
     return torch.where((tot - 1.0).abs() > 1e-6, probs / tot, probs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Taxonomy smoothing without the [C, C] matrix.  Parents always sit at the next task level (utils/taxonomy/taxonomy_tree.py:
+# 165-213), so two classes of one level are at distance 2k, k the first height at which their ancestor chains meet, or inf when
+# they never meet.  Row i of build_taxonomy_smoothing_matrix(build_distance_matrix(...)) therefore holds at most D + 2 distinct
+# values (D = levels above): 1 - alpha on the diagonal, one value per height, one for disconnected classes; and its normaliser
+# follows from per-ancestor descendant counts in O(C * D).  The tables below hold exactly that: O(C * D) memory and build time
+# instead of the reference's O(C^2) Python double loop, nothing to broadcast between ranks (each rank builds them locally).
+#   n_k(i) = classes of the level sharing i's k-th ancestor (n_0 = 1; n_{k-1} where the chain has ended),  m_k = n_k - n_{k-1}
+#   Z_i    = sum_k m_k(i) * exp(-2 beta k)
+#   row i is UNIFORM (every off-diagonal entry alpha / (C - 1), disconnected classes included) when Z_i <= 1e-9, or when class i
+#   has no parent and uniform_roots is set; otherwise val[i, k] = alpha * exp(-2 beta k) / Z_i and disconnected classes get 0.
+# Everything is computed in fp64 and rounded to fp32 once.  Stated difference from the reference: it takes the Z <= 1e-9 decision
+# on an fp32 sum of C terms, here it is taken on the fp64 closed form, so a row within rounding of the threshold can fall on the
+# other side.  (The reference also divides a row by its fp32 sum when that is off 1 by more than 1e-6; the rows here sum to 1.)
+# ----------------------------------------------------------------------------------------------------------------------
+TAX_MAX_DEPTH = L.TAX_MAX_DEPTH
+
+
+class TaxonomySmoothingTables:
+    """The soft-label matrix of one task level as two small tables (host tensors; `to(device)` caches device copies):
+      anc  int32 [D, C]   anc[k-1, c] = index at level + k of the k-th ancestor of class c, -1 once the chain has ended (level-major)
+      val  fp32 [C, D+2]  val[i, 0] = 1 - alpha, val[i, k] = soft label true class i gives a class at distance 2k, val[i, D+1] =
+                          soft label for a disconnected class
+    `dense()` / `distances()` expand rows of the matrices they stand for on the GPU (lnx_taxonomy_rows)."""
+
+    def __init__(self, anc: torch.Tensor, val: torch.Tensor, alpha: float, beta: float, val64=None, counts=None):
+        self.anc, self.val = anc.to(torch.int32).contiguous(), val.to(torch.float32).contiguous()
+        self.num_classes, self.depth = int(self.val.shape[0]), int(self.val.shape[1]) - 2
+        if self.anc.shape != (self.depth, self.num_classes):
+            raise ValueError(f"anc must be [{self.depth}, {self.num_classes}], got {tuple(self.anc.shape)}")
+        self.alpha, self.beta = float(alpha), float(beta)
+        self.val64, self.counts = val64, counts  # keep_fp64=True: the unrounded values and how many classes take each of them
+        self._dev = {}
+
+    @property
+    def nbytes(self) -> int:
+        return self.anc.numel() * 4 + self.val.numel() * 4
+
+    @property
+    def matrix_bytes(self) -> int:
+        """what the fp32 [C, C] matrix these tables replace would take"""
+        return 4 * self.num_classes * self.num_classes
+
+    def to(self, device):
+        """(anc, val) on `device`, uploaded once per device"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._dev:
+            self._dev[device] = (self.anc.to(device), self.val.to(device))
+        return self._dev[device]
+
+    def _rows(self, rows, device, what: int) -> torch.Tensor:
+        anc, val = self.to(device or "cuda")
+        dev = val.device
+        if dev.type != "cuda":
+            raise L.LnxError("TaxonomySmoothingTables.dense / distances run on the GPU (lnx_taxonomy_rows): there is no CPU path")
+        if rows is not None:
+            rows = torch.as_tensor(rows, dtype=torch.long).to(dev).contiguous().view(-1)
+        n = self.num_classes if rows is None else int(rows.numel())
+        out = torch.empty(n, self.num_classes, device=dev, dtype=torch.float32)
+        if n == 0:
+            return out
+        a = L.TaxonomyRowsArgs()
+        a.C, a.depth, a.anc, a.val, a.rows, a.n = self.num_classes, self.depth, _ptr(anc), _ptr(val), _ptr(rows), n
+        a.out, a.ldo, a.what = _ptr(out), out.stride(0), what
+        with torch.cuda.device(dev):
+            L.check(L.lib().lnx_taxonomy_rows(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lnx_taxonomy_rows")
+        return out
+
+    def dense(self, rows=None, device=None) -> torch.Tensor:
+        """rows (all of them with rows=None) of the [C, C] soft-label matrix: build_taxonomy_smoothing_matrix on the device"""
+        return self._rows(rows, device, 0)
+
+    def distances(self, rows=None, device=None) -> torch.Tensor:
+        """rows of the [C, C] distance matrix (2k, inf where disconnected, 0 on the diagonal): build_distance_matrix on the device"""
+        return self._rows(rows, device, 1)
+
+
+def _check_alpha_beta(alpha: float, beta: float) -> None:
+    if not (0.0 <= alpha <= 1.0):
+        raise ValueError(f"alpha must be in [0, 1], got {alpha}")
+    if beta < 0:
+        raise ValueError(f"beta must be non-negative, got {beta}")
+
+
+def build_taxonomy_smoothing_tables(parents, num_classes, level: int, alpha: float = 0.1, beta: float = 1.0, uniform_roots: bool = True,
+                                    keep_fp64: bool = False) -> TaxonomySmoothingTables:
+    """Tables of task level `level` (an index into `num_classes`, the class counts per level from the finest up).  `parents[l]` is an
+    int array [num_classes[l]]: the index at level l + 1 of each class's parent, -1 for none -- the tree's hierarchy map; entries
+    below `level` are not read, and a missing or empty top entry means no parents.  keep_fp64 also keeps `val64` (the unrounded
+    values) and `counts` (int64 [C, D + 2]: how many classes of row i take each value) on the result."""
+    import numpy as np
+
+    _check_alpha_beta(alpha, beta)
+    ncls = [int(c) for c in num_classes]
+    if not 0 <= level < len(ncls):
+        raise ValueError(f"level={level} outside the {len(ncls)} levels")
+    Cn, D = ncls[level], len(ncls) - 1 - level
+    if Cn <= 1:
+        raise ValueError(f"taxonomy smoothing needs at least 2 classes, level {level} has {Cn} (the reference skips such tasks)")
+    if D > TAX_MAX_DEPTH:
+        raise L.LnxError(f"taxonomy tables hold at most {TAX_MAX_DEPTH} levels above the task's own (LNX_TAX_MAX_DEPTH), level {level} has {D}")
+    anc = np.full((D, Cn), -1, np.int64)
+    n = np.ones((D + 1, Cn), np.int64)
+    prev = np.arange(Cn, dtype=np.int64)
+    for k in range(1, D + 1):
+        lv = level + k - 1
+        p = parents[lv] if lv < len(parents) and parents[lv] is not None else None
+        p = np.full(ncls[lv], -1, np.int64) if p is None or len(p) == 0 else np.asarray(p).astype(np.int64).reshape(-1)
+        if p.shape[0] != ncls[lv]:
+            raise ValueError(f"parents[{lv}] has {p.shape[0]} entries, level {lv} has {ncls[lv]} classes")
+        if p.min() < -1 or p.max() >= ncls[lv + 1]:
+            raise ValueError(f"parents[{lv}] holds a parent index outside [-1, {ncls[lv + 1] - 1}]")
+        cur = np.where(prev >= 0, p[np.clip(prev, 0, None)], -1)
+        cnt = np.bincount(cur[cur >= 0], minlength=ncls[lv + 1])
+        n[k] = np.where(cur >= 0, cnt[np.clip(cur, 0, None)], n[k - 1])
+        anc[k - 1] = prev = cur
+    m = (n[1:] - n[:-1]).astype(np.float64)                        # [D, C] classes at distance 2k
+    w = np.exp(-2.0 * float(beta) * np.arange(1, D + 1, dtype=np.float64))
+    Z = (m * w[:, None]).sum(0) if D else np.zeros(Cn)
+    root = anc[0] < 0 if D else np.ones(Cn, bool)
+    uniform = (Z <= 1e-9) | (root & bool(uniform_roots))
+    val = np.empty((Cn, D + 2), np.float64)
+    val[:, 0] = 1.0 - alpha
+    flat = alpha / (Cn - 1)
+    safe = np.where(uniform, 1.0, Z)
+    for k in range(1, D + 1):
+        val[:, k] = np.where(uniform, flat, alpha * w[k - 1] / safe)
+    val[:, D + 1] = np.where(uniform, flat, 0.0)
+    counts = None
+    if keep_fp64:
+        counts = np.empty((Cn, D + 2), np.int64)
+        counts[:, 0] = 1
+        counts[:, 1:D + 1] = (n[1:] - n[:-1]).T
+        counts[:, D + 1] = Cn - n[D]
+    return TaxonomySmoothingTables(torch.from_numpy(anc.astype(np.int32)), torch.from_numpy(val.astype(np.float32)), alpha, beta,
+                                   val64=val if keep_fp64 else None, counts=counts)
+
+
+def _tree_parents(tree, first: int):
+    """per-level parent arrays (None below `first`) of a duck-typed TaxonomyTree: task_keys, num_classes, get_nodes_at_level, get_parent"""
+    import numpy as np
+
+    keys = list(tree.task_keys)
+    parents = [None] * len(keys)
+    for lv in range(first, len(keys) - 1):
+        nodes = tree.get_nodes_at_level(keys[lv])
+        p = np.full(int(tree.num_classes[keys[lv]]), -1, np.int64)
+        for i, node in enumerate(nodes):
+            up = tree.get_parent(node)
+            if up is not None and up[0] == keys[lv + 1]:
+                p[i] = int(up[1])
+        parents[lv] = p
+    return parents
+
+
+def taxonomy_smoothing_tables_from_tree(tree, task_key: str, alpha: float = 0.1, beta: float = 1.0, uniform_roots: bool = True,
+                                        keep_fp64: bool = False) -> TaxonomySmoothingTables:
+    """Tables of `task_key` from a TaxonomyTree-like object, read through `task_keys`, `num_classes`, `get_nodes_at_level` and
+    `get_parent` only (the reference's class is never imported)."""
+    keys = list(tree.task_keys)
+    if task_key not in keys or task_key not in tree.num_classes:
+        raise KeyError(f"Task key '{task_key}' not found in the taxonomy tree.")
+    level = keys.index(task_key)
+    return build_taxonomy_smoothing_tables(_tree_parents(tree, level), [int(tree.num_classes[k]) for k in keys], level, alpha, beta, uniform_roots,
+                                           keep_fp64)
+
+
+def generate_taxonomy_tables(config, taxonomy_tree, num_classes: Dict[str, int]) -> Dict[str, TaxonomySmoothingTables]:
+    """{task: tables} with the per-task decisions of generate_taxonomy_matrices (utils/taxonomy/taxonomy_utils.py:24-254): only tasks
+    whose LOSS.TAXONOMY_SMOOTHING.ENABLED flag is set; a task with unknown or <= 1 classes is skipped; a level none of whose classes
+    has a parent is all-uniform (depth-0 tables) under FALLBACK_TO_UNIFORM and skipped without it; a level with parent links gets
+    the distance-based tables (UNIFORM_ROOTS makes the parentless rows uniform); a task whose tables cannot be built (alpha or beta
+    out of range, a class count that differs from the tree's) is skipped, as the reference skips a task whose matrix raises."""
+    ts = config.LOSS.TAXONOMY_SMOOTHING
+    task_keys, flags = list(config.DATA.TASK_KEYS_H5), list(ts.ENABLED)
+    alpha, beta, uniform_roots, fallback = ts.ALPHA, ts.BETA, bool(ts.UNIFORM_ROOTS), bool(ts.FALLBACK_TO_UNIFORM)
+    out = {}
+    for i, task in enumerate(task_keys):
+        if i >= len(flags) or not flags[i]:
+            continue
+        n = num_classes.get(task)
+        if n is None or n <= 1:
+            continue
+        nodes = taxonomy_tree.get_nodes_at_level(task)
+        has_parents = any(taxonomy_tree.get_parent(node) is not None for node in nodes)
+        if not has_parents and not fallback:
+            continue
+        try:
+            if not has_parents:  # (with parent links some class has a parent, so "all global roots" cannot hold: one uniform case)
+                out[task] = build_taxonomy_smoothing_tables([], [int(n)], 0, alpha, beta, uniform_roots)
+            elif int(taxonomy_tree.num_classes.get(task, -1)) != int(n):
+                continue  # (the reference's distance matrix would not have the shape num_classes asks for: it skips the task)
+            else:
+                out[task] = taxonomy_smoothing_tables_from_tree(taxonomy_tree, task, alpha, beta, uniform_roots)
+        except (ValueError, KeyError):
+            continue
+    return out
 
 
 def _is_null(target: torch.Tensor) -> torch.Tensor:
@@ -763,7 +1010,8 @@ class GradientWeighting(nn.Module):
                         cw = crit.weight.to(dev) if (crit.apply_class_weights and crit.weight is not None) else None
                         rs = valid.float() / cnt.clamp_min(1.0)
                         per = torch.empty(y.shape[0], device=dev, dtype=torch.float32)
-                        _launch(_as_rows(logits_t), tgt, crit.soft_labels.to(dev), 0.0, cw, crit.ignore_index, rs, 1.0, per, None, dl_t)
+                        soft, form, tax = crit._row_source(dev)
+                        _launch(_as_rows(logits_t), tgt, soft, 0.0, cw, crit.ignore_index, rs, 1.0, per, None, dl_t, form, None, None, tax)
                         lsum = torch.where(valid, per, torch.zeros((), device=dev)).sum()
                     else:  # any other criterion: autograd on a detached [B, C] leaf, never on the model
                         leaf = logits_t.detach().clone().requires_grad_(True)
@@ -951,7 +1199,7 @@ class FusedHierarchicalLoss:
     masking, class weighting with finding F13's multiplicities, valid-sample denominators, static or GradNorm task weights, the total,
     every logged component and the null statistics in two launches, the gradients of every task's logits in one more.
 
-    Supported criteria, in any mix over up to 8 tasks: TaxonomyAwareLabelSmoothingCE, this module's CrossEntropyLoss,
+    Supported criteria, in any mix over up to 8 tasks: TaxonomyAwareLabelSmoothingCE (over its matrix, or in table form), this module's CrossEntropyLoss,
     LabelSmoothingCrossEntropy and SoftTargetCrossEntropy (with their class weights, uploaded once, and [B] or [B, C] targets; [B, C] only
     for SoftTargetCrossEntropy), and torch.nn.CrossEntropyLoss(reduction="none", label_smoothing=eps) without a class weight of its own
     and with [B] targets.  Anything else, dict-valued head outputs and CPU tensors are refused by name (LnxError): there is no fall-back
@@ -992,6 +1240,8 @@ class FusedHierarchicalLoss:
         self._draws = {}   # (n_tasks, B) -> [n_tasks, B] buffer of uniform draws
         for crit in criteria.values():  # upload at construction when the criteria already live on a GPU
             sl = getattr(crit, "soft_labels", None)
+            if sl is None:
+                sl = getattr(crit, "tax_val", None)  # (a TaxonomyAwareLabelSmoothingCE in table form)
             if isinstance(sl, torch.Tensor) and sl.is_cuda:
                 self._prepare(sl.device)
                 break
@@ -1008,8 +1258,7 @@ class FusedHierarchicalLoss:
                 w = crit.weight if isinstance(crit.weight, torch.Tensor) else torch.tensor(crit.weight, dtype=torch.float32)
                 self._critw[t] = w.detach().to(dev, torch.float32).contiguous()
             if self._crit[t] == "soft":
-                if crit.soft_labels.device != dev:
-                    crit.soft_labels = crit.soft_labels.to(dev)
+                crit._row_source(dev)
                 if crit.apply_class_weights and crit.weight is not None and crit.weight.device != dev:
                     crit.weight = crit.class_weight = crit.weight.to(dev)
             if tw.class_weights and t in tw.class_weights:
@@ -1088,7 +1337,10 @@ class FusedHierarchicalLoss:
             if self._crit[t] == "soft":
                 if x.shape[1] != crit.num_classes:
                     raise ValueError(f"Logits dimension mismatch. Expected {crit.num_classes} classes, got {x.shape[1]}.")
-                k.soft, k.smoothing = _ptr(crit.soft_labels), 0.0
+                soft, k.form, tax = crit._row_source(dev)
+                k.soft, k.smoothing = _ptr(soft), 0.0
+                if tax is not None:
+                    k.tax_anc, k.tax_val, k.tax_depth = _ptr(tax[0]), _ptr(tax[1]), int(tax[2])
                 k.crit_weight = _ptr(crit.weight) if (crit.apply_class_weights and crit.weight is not None) else None
                 k.ignore_index = -1 if crit.ignore_index is None else int(crit.ignore_index)
             elif self._crit[t] == "basic":
