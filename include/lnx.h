@@ -1356,6 +1356,130 @@ int lnx_hier_refine_bwd(const lnx_hier_refine_args* args, void* stream);
 int64_t lnx_hier_refine_launches(void);
 
 /* ------------------------------------------------------------------------------------
+ * Abstention phase (the reference's phase 2: rl_train_abstention.py, rl_env/): batched rollout, rewards, advantages and the PPO loss
+ * on [B, C] logits.  A decision at rank r depends on the image only, so a whole episode in either mode follows from ONE forward pass.
+ * R ranks in DECISION order (r = 0 is decided first), 1 <= R <= LNX_SOFTCE_MAX_TASKS; logits fp32 or bf16, arithmetic fp32.
+ * Per (b, r), from the row z = logits_r[b, 0..C):
+ *   lse     = max + log(total),  total = the running sum of exp(z - max) below at its last class
+ *   H       = lse - sum_c p[c] z[c]  (entropy; a term with p = 0 contributes 0, never NaN)
+ *   greedy  = the arg-max, the lowest index on a tie
+ *   action  greedy != 0: the arg-max.  Else the smallest j whose running sum of exp(z - max) in class order exceeds u[b, r] * total;
+ *           if rounding leaves no such j, the arg-max.  u in [0, 1) is drawn by the caller.  The running sum is formed in a fixed
+ *           order (256 contiguous chunks, an exclusive scan over the chunk sums, then class by class inside a chunk): the same
+ *           input gives the same action on every run.
+ *   logp    = z[action] - lse
+ *   prediction None iff action == abstain_index (or the rank was not taken); ground truth None iff target[b] == null_index
+ *   outcome = LNX_ABSTAIN_CORRECT (gt class, equal), CORRECT_ABSTAIN (None, None), MISCLASSIFIED (gt class, another class),
+ *             UNNECESSARY_ABSTAIN (gt class, None), PREDICTED_AT_NULL (gt None, class): the argument order of SimpleAbstentionReward
+ * Modes: LNX_ABSTAIN_MULTITASK decides every rank, one transition per sample (length = 1, logp_b = sum_r logp, H_b = sum_r H).
+ *   LNX_ABSTAIN_SEQUENTIAL stops behind the first abstention: length L_b = its rank + 1, else R; ranks r >= L_b are not taken
+ *   (taken = 0, action = abstain_index, logp = H = 0, prediction None, their rows are not read); transitions are (b, t), t < L_b, the
+ *   reward falls on t = L_b - 1.
+ * Reward of the episode over the counted ranks (LNX_ABSTAIN_RANKS_ALL: every rank, LNX_ABSTAIN_RANKS_FIRST: rank 0 only -- what the
+ * reference's environment computes, finding F-a of INTEGRATION.md):
+ *   LNX_ABSTAIN_REWARD_SIMPLE   sum of table[outcome] in rank order (fp32)
+ *   LNX_ABSTAIN_REWARD_OUTCOME  the walk of EpisodeOutcomeReward: outcome_reward[0] if every rank up to and including the first
+ *                               correct abstention is right (or all are, without one), else outcome_reward[1]
+ * counts (NULL = none) is an int64 table of LNX_ABSTAIN_COUNTS entries this batch is ADDED to with integer atomics: per rank r at
+ *   LNX_ABSTAIN_CNT_STRIDE * r the seven counters of the reference's evaluate_policy (every rank of every episode is one decision,
+ *   an untaken one an abstention), then LNX_ABSTAIN_CNT_EPISODES, LNX_ABSTAIN_CNT_LENGTH_SUM and LNX_ABSTAIN_CNT_REWARD_FIX: the
+ *   reward sum in units of 2^-LNX_ABSTAIN_REWARD_FIX_BITS (llrintf(reward * 2^20): exact for dyadic tables, order-free for any).
+ * lnx_abstain_act: ONE launch, one workgroup per sample walking the ranks; three passes over a row (max; sum and sum e z in chunks;
+ * the crossing inside one chunk).  No atomics on floats.
+ * Refused on the host before any launch (all four entry points): R outside 1..8, B <= 0, C <= 0, ld < C, a NULL required pointer,
+ * an abstain_index / null_index outside [0, C), an unknown dtype / mode / reward kind, a missing u without greedy.
+ * -----------------------------------------------------------------------------------*/
+enum { LNX_ABSTAIN_MULTITASK = 0, LNX_ABSTAIN_SEQUENTIAL = 1 };
+enum { LNX_ABSTAIN_REWARD_SIMPLE = 0, LNX_ABSTAIN_REWARD_OUTCOME = 1 };
+enum { LNX_ABSTAIN_RANKS_ALL = 0, LNX_ABSTAIN_RANKS_FIRST = 1 };
+enum { LNX_ABSTAIN_CORRECT = 0, LNX_ABSTAIN_CORRECT_ABSTAIN, LNX_ABSTAIN_MISCLASSIFIED, LNX_ABSTAIN_UNNECESSARY_ABSTAIN, LNX_ABSTAIN_PREDICTED_AT_NULL,
+       LNX_ABSTAIN_OUTCOMES };
+enum { LNX_ABSTAIN_CNT_ABSTAINED = 0, LNX_ABSTAIN_CNT_TOTAL, LNX_ABSTAIN_CNT_CORRECT_ABSTAIN, LNX_ABSTAIN_CNT_UNNECESSARY_ABSTAIN, LNX_ABSTAIN_CNT_MISSED_ABSTAIN,
+       LNX_ABSTAIN_CNT_CORRECT_CLASSIFY, LNX_ABSTAIN_CNT_MISCLASSIFY, LNX_ABSTAIN_CNT_STRIDE = 8, LNX_ABSTAIN_CNT_EPISODES = 64,
+       LNX_ABSTAIN_CNT_LENGTH_SUM = 65, LNX_ABSTAIN_CNT_REWARD_FIX = 66, LNX_ABSTAIN_COUNTS = 72 };
+#define LNX_ABSTAIN_REWARD_FIX_BITS 20
+typedef struct lnx_abstain_rank {
+    const void* logits;     /* [B, ld] of the args' dtype */
+    int64_t ld;             /* >= C */
+    int C;
+    int abstain_index;      /* in [0, C): the class of this head that stands for "abstain" (lnx_abstain_act) */
+    int null_index;         /* in [0, C): target == null_index is the ground truth None (lnx_abstain_act) */
+    const int64_t* target;  /* [B] (lnx_abstain_act); a target outside [0, C) is a class no action equals */
+    float* dlogits;         /* lnx_ppo_loss_bwd: [B, ldd] fp32; columns >= C and the rows of untaken ranks are not written */
+    int64_t ldd;            /* >= C */
+} lnx_abstain_rank;
+typedef struct lnx_abstain_act_args {
+    int dtype;                      /* of every rank's logits: 0 = fp32, 1 = bf16 */
+    int B, R, mode, greedy, reward_kind, reward_ranks;
+    float table[LNX_ABSTAIN_OUTCOMES]; /* LNX_ABSTAIN_REWARD_SIMPLE */
+    float outcome_reward[2];        /* LNX_ABSTAIN_REWARD_OUTCOME: optimal, suboptimal */
+    const float* u;                 /* [B, R] uniforms in [0, 1); may be NULL with greedy != 0 */
+    int32_t* actions;               /* [B, R] */
+    float* logp;                    /* [B, R] */
+    float* entropy;                 /* [B, R] */
+    uint8_t* taken;                 /* [B, R] */
+    int32_t* length;                /* [B]: transitions of the episode (multitask: 1) */
+    float* reward;                  /* [B] */
+    int64_t* counts;                /* [LNX_ABSTAIN_COUNTS] or NULL */
+    lnx_abstain_rank rank[LNX_SOFTCE_MAX_TASKS];
+} lnx_abstain_act_args;
+int lnx_abstain_act(const lnx_abstain_act_args* args, void* stream);
+
+/* Advantages of whole episodes: the recursion of compute_gae_and_returns (rl_train_abstention.py:38-55) per episode, in fp32.  Every
+ * episode of the rollout is complete, so next_non_terminal is 0 at its last step and the reference's last_value never enters.
+ * Sequential: V_b at every step (the same image), reward[b] at t = L_b - 1 and 0 before; multitask: one step, slot [b, 0].
+ *   adv[t] = delta_t + gamma * lambda * adv[t + 1],  delta_t = r_t + gamma * V_b * (t < L_b - 1) - V_b;   ret = adv + V_b
+ * then adv = (adv - mean) / (std + 1e-8) over all N transitions of the rollout (population std).  mean and std are folded in double,
+ * each thread a fixed stride and a fixed LDS tree: the same bits run to run.  Slots that are no transition are written as 0.
+ * ONE launch of one workgroup.  n_trans[0] = N. */
+typedef struct lnx_ppo_adv_args {
+    int B, R, mode;
+    float gamma, gae_lambda;
+    const float* reward;    /* [B] */
+    const float* value;     /* [B] */
+    const int32_t* length;  /* [B], 1..R (multitask: ignored, 1) */
+    float* adv;             /* [B, R] */
+    float* ret;             /* [B, R] */
+    int32_t* n_trans;       /* [1] */
+} lnx_ppo_adv_args;
+int lnx_ppo_advantages(const lnx_ppo_adv_args* args, void* stream);
+
+/* The clipped-surrogate loss of ppo_update (rl_train_abstention.py:109-116) over the N transitions of a minibatch of B samples, each
+ * decision evaluated at its own rank (finding F-d), with the row arithmetic of lnx_abstain_act (the same bits: a first epoch has
+ * ratio = 1 exactly):
+ *   ratio = exp(logp_new - logp_old);  policy = -mean(min(ratio A, clamp(ratio, 1 - eps, 1 + eps) A));  value = mean((V - ret)^2)
+ *   entropy_loss = -mean(H);  total = policy + vf_coef * value + ent_coef * entropy_loss
+ * multitask: logp_new - logp_old and H are summed over the ranks in rank order, A = adv[b, 0]; sequential: per taken (b, t).
+ * lnx_ppo_loss_fwd: a launch of one workgroup per (sample, rank), then ONE workgroup that folds every sum in double in a fixed order.
+ * lnx_ppo_loss_bwd: one launch; the gradients of torch autograd on the expression above (d/dratio = A where ratio A <= the clipped
+ * term, else 0), times the device scalar go_dev[0]: rank[r].dlogits (NULL = none for that rank) and dvalue [B] (NULL = none), which
+ * in sequential mode sums the L_b steps of sample b.
+ *   ws   [R][LNX_PPO_WS_ROWS][B] floats (lse, H, logp_new, the transition's d total / d logp_new times N)
+ *   out  [LNX_PPO_OUT_FLOATS] floats at LNX_PPO_OUT_* */
+enum { LNX_PPO_WS_LSE = 0, LNX_PPO_WS_H, LNX_PPO_WS_LOGP, LNX_PPO_WS_COEF, LNX_PPO_WS_ROWS };
+enum { LNX_PPO_OUT_POLICY = 0, LNX_PPO_OUT_VALUE, LNX_PPO_OUT_ENTROPY, LNX_PPO_OUT_TOTAL, LNX_PPO_OUT_N, LNX_PPO_OUT_RATIO_MEAN, LNX_PPO_OUT_CLIP_FRAC,
+       LNX_PPO_OUT_FLOATS = 8 };
+typedef struct lnx_ppo_loss_args {
+    int dtype, B, R, mode;
+    float clip_eps, vf_coef, ent_coef;
+    const int32_t* actions;  /* [B, R] */
+    const uint8_t* taken;    /* [B, R] */
+    const float* logp_old;   /* [B, R] */
+    const float* adv;        /* [B, R] */
+    const float* ret;        /* [B, R] */
+    const float* value;      /* [B] */
+    float* ws;
+    float* out;
+    float* dvalue;           /* lnx_ppo_loss_bwd: [B] or NULL */
+    lnx_abstain_rank rank[LNX_SOFTCE_MAX_TASKS];
+} lnx_ppo_loss_args;
+int lnx_ppo_loss_fwd(const lnx_ppo_loss_args* args, void* stream);
+int lnx_ppo_loss_bwd(const lnx_ppo_loss_args* args, const float* go_dev, void* stream);
+/* kernel launches made by the four entry points above since the library was loaded (host-side counter): 1 for lnx_abstain_act, 1 for
+ * lnx_ppo_advantages, 2 for lnx_ppo_loss_fwd, 1 for lnx_ppo_loss_bwd */
+int64_t lnx_abstain_launches(void);
+
+/* ------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP branch (bf16 storage, C in {32,64,96,128,192}):
  *   out = x + rowscale * gamma * (GELU(ln . W1^T + b1) . W2^T + b2)
  * = pwconv1 -> GELU -> pwconv2 -> LayerScale -> DropPath -> residual (blocks/convnext.py:79-86)

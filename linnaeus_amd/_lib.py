@@ -248,6 +248,49 @@ class HierRefineArgs(C.Structure):  # == lnx_hier_refine_args
 HIER_REFINE_STRUCTS = {"lnx_hier_refine_level": HierRefineLevel, "lnx_hier_refine_args": HierRefineArgs}
 
 
+# lnx_abstain_act / lnx_ppo_advantages / lnx_ppo_loss_fwd / lnx_ppo_loss_bwd (the LNX_ABSTAIN_* and LNX_PPO_* enums of include/lnx.h)
+ABSTAIN_MULTITASK, ABSTAIN_SEQUENTIAL = range(2)
+ABSTAIN_REWARD_SIMPLE, ABSTAIN_REWARD_OUTCOME = range(2)
+ABSTAIN_RANKS_ALL, ABSTAIN_RANKS_FIRST = range(2)
+ABSTAIN_CORRECT, ABSTAIN_CORRECT_ABSTAIN, ABSTAIN_MISCLASSIFIED, ABSTAIN_UNNECESSARY_ABSTAIN, ABSTAIN_PREDICTED_AT_NULL, ABSTAIN_OUTCOMES = range(6)
+(ABSTAIN_CNT_ABSTAINED, ABSTAIN_CNT_TOTAL, ABSTAIN_CNT_CORRECT_ABSTAIN, ABSTAIN_CNT_UNNECESSARY_ABSTAIN, ABSTAIN_CNT_MISSED_ABSTAIN,
+ ABSTAIN_CNT_CORRECT_CLASSIFY, ABSTAIN_CNT_MISCLASSIFY) = range(7)
+ABSTAIN_CNT_STRIDE, ABSTAIN_CNT_EPISODES, ABSTAIN_CNT_LENGTH_SUM, ABSTAIN_CNT_REWARD_FIX, ABSTAIN_COUNTS = 8, 64, 65, 66, 72
+ABSTAIN_REWARD_FIX_BITS = 20
+PPO_WS_LSE, PPO_WS_H, PPO_WS_LOGP, PPO_WS_COEF, PPO_WS_ROWS = range(5)
+PPO_OUT_POLICY, PPO_OUT_VALUE, PPO_OUT_ENTROPY, PPO_OUT_TOTAL, PPO_OUT_N, PPO_OUT_RATIO_MEAN, PPO_OUT_CLIP_FRAC = range(7)
+PPO_OUT_FLOATS = 8
+
+
+class AbstainRank(C.Structure):  # == lnx_abstain_rank
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("C", C.c_int), ("abstain_index", C.c_int), ("null_index", C.c_int), ("target", C.c_void_p),
+                ("dlogits", C.c_void_p), ("ldd", C.c_int64)]
+
+
+class AbstainActArgs(C.Structure):  # == lnx_abstain_act_args
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("R", C.c_int), ("mode", C.c_int), ("greedy", C.c_int), ("reward_kind", C.c_int),
+                ("reward_ranks", C.c_int), ("table", C.c_float * ABSTAIN_OUTCOMES), ("outcome_reward", C.c_float * 2), ("u", C.c_void_p),
+                ("actions", C.c_void_p), ("logp", C.c_void_p), ("entropy", C.c_void_p), ("taken", C.c_void_p), ("length", C.c_void_p),
+                ("reward", C.c_void_p), ("counts", C.c_void_p), ("rank", AbstainRank * METRICS_MAX_TASKS)]
+
+
+class PpoAdvArgs(C.Structure):  # == lnx_ppo_adv_args
+    _fields_ = [("B", C.c_int), ("R", C.c_int), ("mode", C.c_int), ("gamma", C.c_float), ("gae_lambda", C.c_float), ("reward", C.c_void_p),
+                ("value", C.c_void_p), ("length", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p), ("n_trans", C.c_void_p)]
+
+
+class PpoLossArgs(C.Structure):  # == lnx_ppo_loss_args
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("R", C.c_int), ("mode", C.c_int), ("clip_eps", C.c_float), ("vf_coef", C.c_float),
+                ("ent_coef", C.c_float), ("actions", C.c_void_p), ("taken", C.c_void_p), ("logp_old", C.c_void_p), ("adv", C.c_void_p),
+                ("ret", C.c_void_p), ("value", C.c_void_p), ("ws", C.c_void_p), ("out", C.c_void_p), ("dvalue", C.c_void_p),
+                ("rank", AbstainRank * METRICS_MAX_TASKS)]
+
+
+# the argument structs of the abstention phase by their C names (tests compare sizeof against a compiled probe)
+ABSTENTION_STRUCTS = {"lnx_abstain_rank": AbstainRank, "lnx_abstain_act_args": AbstainActArgs, "lnx_ppo_adv_args": PpoAdvArgs,
+                      "lnx_ppo_loss_args": PpoLossArgs}
+
+
 _lib = None
 
 
@@ -296,6 +339,12 @@ def lib() -> C.CDLL:
             _lib.lnx_hier_refine_fwd.argtypes = [C.POINTER(HierRefineArgs), C.c_void_p]
             _lib.lnx_hier_refine_bwd.argtypes = [C.POINTER(HierRefineArgs), C.c_void_p]
             _lib.lnx_hier_refine_launches.restype = C.c_int64
+        if hasattr(_lib, "lnx_abstain_act"):
+            _lib.lnx_abstain_act.argtypes = [C.POINTER(AbstainActArgs), C.c_void_p]
+            _lib.lnx_ppo_advantages.argtypes = [C.POINTER(PpoAdvArgs), C.c_void_p]
+            _lib.lnx_ppo_loss_fwd.argtypes = [C.POINTER(PpoLossArgs), C.c_void_p]
+            _lib.lnx_ppo_loss_bwd.argtypes = [C.POINTER(PpoLossArgs), C.c_void_p, C.c_void_p]
+            _lib.lnx_abstain_launches.restype = C.c_int64
         if hasattr(_lib, "lnx_preprocess"):
             _lib.lnx_resize_taps.argtypes = [C.c_int, C.c_int, C.c_int]
             _lib.lnx_resize_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -373,6 +422,7 @@ EXPORTS = [
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_taxonomy_rows", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_hier_refine_fwd", "lnx_hier_refine_bwd", "lnx_hier_refine_launches",
+    "lnx_abstain_act", "lnx_ppo_advantages", "lnx_ppo_loss_fwd", "lnx_ppo_loss_bwd", "lnx_abstain_launches",
     "lnx_mix_rows", "lnx_mix_meta", "lnx_meta_mask",
     "lnx_aug_pointwise", "lnx_aug_saturation", "lnx_aug_rowstat", "lnx_aug_rescale", "lnx_aug_affine", "lnx_aug_stencil", "lnx_erase_rects", "lnx_u8hwc_to_f32chw",
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",
