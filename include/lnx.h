@@ -988,9 +988,36 @@ typedef struct lnx_sgd_hyper {
 } lnx_sgd_hyper;
 int lnx_sgd_step(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_sgd_hyper* hyper, const float* sumsq, float max_norm,
                  void* stream);
-/* launches made by lnx_grad_sumsq (2), lnx_adamw_step, lnx_ademamix_step and lnx_sgd_step (1 each) since the library was loaded
- * (host-side counter, the twin of lnx_muon_launches) */
+/* launches made by lnx_grad_sumsq (2), lnx_adamw_step, lnx_ademamix_step and lnx_sgd_step (1 each) and their _guarded forms since the
+ * library was loaded (host-side counter, the twin of lnx_muon_launches) */
 int64_t lnx_optim_launches(void);
+
+/* Non-finite guard (lnx_version 117): the skipped step of torch.amp.GradScaler.step (train.py:279-312 of the reference steps through
+ * scaler.step(optimizer)), decided once per step ON THE DEVICE.  All four fields are device pointers.
+ *   lnx_grad_sumsq_guarded   the norm pass of lnx_grad_sumsq whose fold launch also decides: *flag = 1 when the sum of squares is not
+ *                            finite (an inf or NaN gradient, or a finite one whose square overflows fp32, |g| >~ 1.8e19) or when
+ *                            *found_inf != 0, else 0; then *skipped += *flag (one thread, ordinary stores).  `out` holds TWO floats:
+ *                            out[0] the sum of squares as accumulated (of the scaled gradients when grad_scale is given), out[1] the
+ *                            total norm of the unscaled gradients, sqrt(out[0]) * (1 / *grad_scale).
+ *   lnx_*_step_guarded       every workgroup reads *flag first and returns when it is set: a skipped step writes nothing.  Otherwise,
+ *                            with inv = 1 / *grad_scale (1 when grad_scale is NULL), the total norm is sqrt(*sumsq) * inv, the clip
+ *                            coefficient min(1, max_norm / (norm + 1e-6)) and the gradient the update sees (g * inv) * coef, in that
+ *                            order: a power-of-two scale gives the bits of the unscaled step.
+ * found_inf and grad_scale may be NULL (no outside verdict, no scale); flag must be given; skipped is needed by the norm pass only.
+ * guard == NULL: the entry point without the suffix, launch for launch and bit for bit. */
+typedef struct lnx_step_guard {
+    const float* found_inf;   /* GradScaler's verdict on the gradients, or NULL */
+    const float* grad_scale;  /* the loss scale the gradients still carry, or NULL (already unscaled) */
+    float* flag;              /* 1: this step is skipped; written by the norm pass, read by every step kernel */
+    int64_t* skipped;         /* running count of skipped steps */
+} lnx_step_guard;
+int lnx_grad_sumsq_guarded(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, float* out, float* ws, const lnx_step_guard* guard, void* stream);
+int lnx_adamw_step_guarded(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_adamw_hyper* hyper, const float* sumsq, float max_norm,
+                           const lnx_step_guard* guard, void* stream);
+int lnx_ademamix_step_guarded(const lnx_adamw_desc* descs_dev, float* const* slow_dev, int ndesc, int total_blocks, const lnx_ademamix_hyper* hyper,
+                              const float* sumsq, float max_norm, const lnx_step_guard* guard, void* stream);
+int lnx_sgd_step_guarded(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_sgd_hyper* hyper, const float* sumsq, float max_norm,
+                         const lnx_step_guard* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Muon (linnaeus/optimizers/muon.py:27-65, 126-190, chosen by OPTIMIZER.NAME = muon in optimizers/build.py:130-154): the whole step
@@ -1052,6 +1079,11 @@ typedef struct lnx_muon_step_args {
      * the momentum lerp; g itself is not modified.  sumsq == NULL or max_norm <= 0 (a zero-filled tail): no clip, the step as before. */
     const float* sumsq;
     float max_norm;
+    /* appended (lnx_version 117): the non-finite guard (lnx_step_guard above; a HOST pointer to the struct, its fields device pointers).
+     * All 3 * ns + 3 launches read *guard->flag first and return when it is set: the momentum buffers, the parameters and the workspace
+     * (whose zero padding is relied on for ever) stay as they were.  The momentum kernel reads the gradient as (g / *grad_scale) * coef.
+     * NULL (a zero-filled tail): the step as before. */
+    const lnx_step_guard* guard;
 } lnx_muon_step_args;
 int lnx_muon_step(const lnx_muon_step_args* args, void* stream);
 /* launches made by lnx_muon_step since the library was loaded (host-side counter, as lnx_nt_kernel_launches) */

@@ -8,6 +8,8 @@
 //   muon_apply_kernel      p = p * decay - step * O
 // Operands are zero-padded to tile multiples (lnx_muon_layout), so no kernel has an edge case: a padded row or column of X gives
 // zero rows / columns of A and B and stays zero in X' = B X + a X.  No atomics: the same inputs give the same bits, alone or in a set.
+// With a non-finite guard (lnx_step_guard) EVERY launch reads the guard's flag before it touches a tensor and returns when it is set: products over a NaN
+// operand would turn the workspace's zero padding, written once and relied on for ever, into NaN.
 #include <atomic>
 #include <vector>
 
@@ -44,13 +46,21 @@ __device__ __forceinline__ int64_t x_index(const lnx_muon_mat& d, int r, int c) 
     return d.rows > d.cols ? (int64_t)c * d.np + r : (int64_t)r * d.np + c;
 }
 
-// sumsq / max_norm: the global-norm clip of lnx_adamw_step; every gradient element is scaled as it is read, g itself is not written
+// one 4-byte load, uniform across the workgroup; tested behind the table lookups and ahead of the first access to a matrix, a buffer
+// or the workspace (as a kernel's first statement it would stand in front of the loads of the other kernel arguments)
+__device__ __forceinline__ bool guard_skips(const float* __restrict__ flag) { return flag != nullptr && *flag != 0.f; }
+
+// sumsq / max_norm: the global-norm clip of lnx_adamw_step; every gradient element is scaled as it is read, g itself is not written.
+// grad_scale: the loss scale the gradients still carry (lnx_step_guard); total norm = sqrt(sumsq) * inv, the gradient seen (g * inv) * coef
 __global__ __launch_bounds__(256) void muon_momentum_kernel(const lnx_muon_mat* __restrict__ mats, int n, char* __restrict__ ws, float* __restrict__ part,
-                                                            const float* __restrict__ sumsq, float max_norm) {
+                                                            const float* __restrict__ sumsq, float max_norm, const float* __restrict__ flag,
+                                                            const float* __restrict__ grad_scale) {
     __shared__ float red[4];
+    const float inv = grad_scale != nullptr ? __fdiv_rn(1.0f, *grad_scale) : 1.0f;
     float coef = 1.0f;
-    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) * inv + 1e-6f));
     const lnx_muon_mat& d = mats[find_mat(mats, n, blockIdx.x)];
+    if (guard_skips(flag)) return;
     float s = 0.f;
     if (d.g != nullptr) {
         bf16_t* __restrict__ X = reinterpret_cast<bf16_t*>(ws + d.x_off);
@@ -59,7 +69,7 @@ __global__ __launch_bounds__(256) void muon_momentum_kernel(const lnx_muon_mat* 
         const int64_t end = min(numel, base + ELEMS);
         const float mu = d.momentum, omm = d.omm;
         for (int64_t i = base + threadIdx.x; i < end; i += 256) {
-            const float g = d.g[i] * coef;
+            const float g = (d.g[i] * inv) * coef;
             const float b = lerp_f(d.buf[i], g, omm);
             d.buf[i] = b;
             const float u = d.nesterov ? lerp_f(g, b, mu) : b;
@@ -77,12 +87,12 @@ __global__ __launch_bounds__(256) void muon_momentum_kernel(const lnx_muon_mat* 
 
 // One wave per tile of X (the stage-2 table).  Every wave of a matrix folds the matrix's partials in the same order: same norm bits.
 __global__ __launch_bounds__(256) void muon_normalise_kernel(const lnx_muon_mat* __restrict__ mats, const lnx_muon_tile* __restrict__ tiles, int ntiles,
-                                                             char* __restrict__ ws, const float* __restrict__ part) {
+                                                             char* __restrict__ ws, const float* __restrict__ part, const float* __restrict__ flag) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= ntiles) return;
     const lnx_muon_tile tl = tiles[t];
     const lnx_muon_mat& d = mats[tl.mat];
-    if (d.g == nullptr) return;
+    if (d.g == nullptr || guard_skips(flag)) return;
     const int nblk = (int)(((int64_t)d.rows * d.cols + ELEMS - 1) / ELEMS);
     float s = 0.f;
     for (int i = lane; i < nblk; i += 64) s += part[d.block_start + i];
@@ -111,12 +121,12 @@ __global__ __launch_bounds__(256) void muon_normalise_kernel(const lnx_muon_mat*
 //   STAGE 2: X = B X + a X        P = B [mp, mp], Q = X^T [np, mp] (ping), K = mp; X in place, X^T to pong
 template <int STAGE>
 __global__ __launch_bounds__(256) void muon_ns_kernel(const lnx_muon_mat* __restrict__ mats, const lnx_muon_tile* __restrict__ tiles, int ntiles, int it,
-                                                      char* __restrict__ ws) {
+                                                      char* __restrict__ ws, const float* __restrict__ flag) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= ntiles) return;
     const lnx_muon_tile tl = tiles[t];
     const lnx_muon_mat& d = mats[tl.mat];
-    if (d.g == nullptr || it >= d.ns_steps) return;
+    if (d.g == nullptr || it >= d.ns_steps || guard_skips(flag)) return;
     const int mp = d.mp, np = d.np;
     const bf16_t *P, *Q;
     int K, ldp, ldq;
@@ -190,9 +200,9 @@ __global__ __launch_bounds__(256) void muon_ns_kernel(const lnx_muon_mat* __rest
         }
 }
 
-__global__ __launch_bounds__(256) void muon_apply_kernel(const lnx_muon_mat* __restrict__ mats, int n, const char* __restrict__ ws) {
+__global__ __launch_bounds__(256) void muon_apply_kernel(const lnx_muon_mat* __restrict__ mats, int n, const char* __restrict__ ws, const float* __restrict__ flag) {
     const lnx_muon_mat& d = mats[find_mat(mats, n, blockIdx.x)];
-    if (d.g == nullptr) return;
+    if (d.g == nullptr || guard_skips(flag)) return;
     const bf16_t* __restrict__ X = reinterpret_cast<const bf16_t*>(ws + d.x_off);
     const int64_t numel = (int64_t)d.rows * d.cols;
     const int64_t base = (int64_t)(blockIdx.x - d.block_start) * ELEMS;
@@ -270,6 +280,8 @@ extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
     LNX_CHECK(a != nullptr, "lnx_muon_step: args is NULL");
     LNX_CHECK(a->n > 0 && a->mats && a->mats_dev && a->tiles_dev && a->workspace && a->partials, "lnx_muon_step: bad arguments (n > 0 and no NULL table, workspace or partials)");
     LNX_CHECK((reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0, "lnx_muon_step: the workspace must be 256-byte aligned");
+    LNX_CHECK(a->guard == nullptr || a->guard->flag != nullptr, "lnx_muon_step: the guard has no flag");
+    const float* flag = a->guard != nullptr ? a->guard->flag : nullptr;
     const int n = a->n;
     // the host table must be what lnx_muon_layout gives for its shapes: every offset and tile range the kernels follow is checked here
     std::vector<int> shapes(2 * (size_t)n);
@@ -297,8 +309,9 @@ extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     char* ws = static_cast<char*>(a->workspace);
     const lnx_muon_tile* tb[3] = {a->tiles_dev, a->tiles_dev + info.ntiles[0], a->tiles_dev + info.ntiles[0] + info.ntiles[1]};
-    hipLaunchKernelGGL(muon_momentum_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, ws, a->partials, a->sumsq, a->max_norm);
-    hipLaunchKernelGGL(muon_normalise_kernel, dim3(cdiv(info.ntiles[2], 4)), dim3(256), 0, st, a->mats_dev, tb[2], (int)info.ntiles[2], ws, (const float*)a->partials);
+    hipLaunchKernelGGL(muon_momentum_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, ws, a->partials, a->sumsq, a->max_norm, flag,
+                       a->guard != nullptr ? a->guard->grad_scale : nullptr);
+    hipLaunchKernelGGL(muon_normalise_kernel, dim3(cdiv(info.ntiles[2], 4)), dim3(256), 0, st, a->mats_dev, tb[2], (int)info.ntiles[2], ws, (const float*)a->partials, flag);
     g_launches += 2;
     for (int it = 0; it < max_steps; ++it) {
         // the prefix of each table that still holds a matrix with an iteration left (matrices in descending ns_steps: the others drop out)
@@ -306,12 +319,12 @@ extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
         for (int i = 0; i < n; ++i)
             if (a->mats[i].ns_steps > it)
                 for (int s = 0; s < 3; ++s) nt[s] = a->mats[i].tile_start[s] + a->mats[i].tile_count[s];
-        hipLaunchKernelGGL(muon_ns_kernel<0>, dim3(cdiv(nt[0], 4)), dim3(256), 0, st, a->mats_dev, tb[0], nt[0], it, ws);
-        hipLaunchKernelGGL(muon_ns_kernel<1>, dim3(cdiv(nt[1], 4)), dim3(256), 0, st, a->mats_dev, tb[1], nt[1], it, ws);
-        hipLaunchKernelGGL(muon_ns_kernel<2>, dim3(cdiv(nt[2], 4)), dim3(256), 0, st, a->mats_dev, tb[2], nt[2], it, ws);
+        hipLaunchKernelGGL(muon_ns_kernel<0>, dim3(cdiv(nt[0], 4)), dim3(256), 0, st, a->mats_dev, tb[0], nt[0], it, ws, flag);
+        hipLaunchKernelGGL(muon_ns_kernel<1>, dim3(cdiv(nt[1], 4)), dim3(256), 0, st, a->mats_dev, tb[1], nt[1], it, ws, flag);
+        hipLaunchKernelGGL(muon_ns_kernel<2>, dim3(cdiv(nt[2], 4)), dim3(256), 0, st, a->mats_dev, tb[2], nt[2], it, ws, flag);
         g_launches += 3;
     }
-    hipLaunchKernelGGL(muon_apply_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, (const char*)ws);
+    hipLaunchKernelGGL(muon_apply_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, (const char*)ws, flag);
     g_launches += 1;
     LNX_LAUNCH_CHECK();
     return 0;

@@ -3,8 +3,9 @@
 // by linnaeus/optimizers/build.py, and the gradient-norm / clip passes of train.py:282-308
 // (clip_grad_norm_: coef = min(1, max_norm / (total_norm + 1e-6)), gradients scaled by coef).
 // Launches per step over a device descriptor table (one entry per parameter tensor): sum of squares of all gradients
-// (partials per workgroup + a fixed-order fold; only when clipping), then the update, which reads the clip coefficient
-// from that scalar.
+// (partials per workgroup + a fixed-order fold; only when clipping or guarding), then the update, which reads the clip coefficient
+// from that scalar.  With a non-finite guard (lnx_step_guard) the fold also decides whether the step is skipped, and every update
+// kernel returns at once when it is.
 #include <atomic>
 
 #include "common.hpp"
@@ -29,6 +30,20 @@ __device__ __forceinline__ int find_desc_index(const lnx_adamw_desc* __restrict_
 
 __device__ __forceinline__ const lnx_adamw_desc& find_desc(const lnx_adamw_desc* __restrict__ descs, int ndesc, int block) {
     return descs[find_desc_index(descs, ndesc, block)];
+}
+
+// The non-finite guard (lnx_step_guard): a step kernel reads the flag the fold launch left, one 4-byte load that is uniform across the
+// workgroup, and returns when it is set: a skipped step writes nothing.  The test stands behind the descriptor lookup and ahead of the
+// first access to a parameter, state or gradient tensor: as the first statement of a kernel it put a branch in front of the loads of
+// the other kernel arguments, which cost every launch about a microsecond, guard or no guard.
+__device__ __forceinline__ bool guard_skips(const float* __restrict__ flag) { return flag != nullptr && *flag != 0.f; }
+
+// 1 / loss scale of the step (1 without a scale): the gradient an update sees is (g * inv) * coef
+__device__ __forceinline__ float guard_inv(const float* __restrict__ grad_scale) { return grad_scale != nullptr ? __fdiv_rn(1.0f, *grad_scale) : 1.0f; }
+
+// clip coefficient from the sum of squares of the gradients as they lie in memory: total norm = sqrt(sumsq) * inv
+__device__ __forceinline__ float clip_coef(const float* __restrict__ sumsq, float max_norm, float inv) {
+    return sumsq != nullptr && max_norm > 0.f ? fminf(1.0f, max_norm / (sqrtf(*sumsq) * inv + 1e-6f)) : 1.0f;
 }
 
 // one partial per workgroup, folded in a fixed order by grad_sumsq_fold_kernel: the same gradients give the same bits on every
@@ -59,7 +74,8 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const lnx_adamw_desc* _
     if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(1024) void grad_sumsq_fold_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
+// guard.flag != NULL: the fold also decides the step (out then holds two floats, the second the norm of the unscaled gradients)
+__global__ __launch_bounds__(1024) void grad_sumsq_fold_kernel(const float* __restrict__ part, int n, float* __restrict__ out, const lnx_step_guard guard) {
     __shared__ float red[16];
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;  // four independent chains per thread: loads in flight
     int i = threadIdx.x;
@@ -78,22 +94,28 @@ __global__ __launch_bounds__(1024) void grad_sumsq_fold_kernel(const float* __re
 #pragma unroll
         for (int k = 0; k < 16; ++k) t += red[k];
         *out = t;
+        if (guard.flag != nullptr) {
+            out[1] = sqrtf(t) * guard_inv(guard.grad_scale);
+            const bool skip = !isfinite(t) || (guard.found_inf != nullptr && *guard.found_inf != 0.f);
+            *guard.flag = skip ? 1.0f : 0.0f;
+            *guard.skipped += skip ? 1 : 0;
+        }
     }
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(const lnx_adamw_desc* __restrict__ descs, int ndesc, const lnx_adamw_hyper h, const float* __restrict__ sumsq,
-                                                    float max_norm) {
+                                                    float max_norm, const float* __restrict__ flag, const float* __restrict__ grad_scale) {
     const lnx_adamw_desc& d = find_desc(descs, ndesc, blockIdx.x);
     const int gi = d.group;
     const float lr = h.lr[gi], b1 = h.beta1[gi], b2 = h.beta2[gi], eps = h.eps[gi], wd = h.weight_decay[gi];
     const float omb1 = h.omb1[gi], omb2 = h.omb2[gi];
     const float step_size = lr / h.bias_c1[gi], inv_sqrt_bc2 = 1.0f / sqrtf(h.bias_c2[gi]);
-    float coef = 1.0f;
-    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+    const float inv = guard_inv(grad_scale), coef = clip_coef(sumsq, max_norm, inv);
+    if (guard_skips(flag)) return;
     const int64_t base = (int64_t)(blockIdx.x - d.block_start) * OPT_ELEMS;
     const int64_t end = min(d.n, base + OPT_ELEMS);
     auto upd = [&](float g, float& p, float& m, float& v) __attribute__((always_inline)) {
-        g *= coef;
+        g = (g * inv) * coef;
         p *= 1.0f - lr * wd;
         m = fmaf(b1, m, omb1 * g);
         v = fmaf(b2, v, omb2 * g * g);
@@ -147,7 +169,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const lnx_adamw_desc* __rest
 
 // AdEMAMix (linnaeus/optimizers/ademamix.py:119-175) over the same descriptor table; slow[i] is exp_avg_slow (m3) of
 // descs[i].  Per element, in the reference's order and with its quirks:
-//   g *= coef                                   (clip coefficient, as adamw_kernel)
+//   g = (g * inv) * coef                        (loss scale and clip coefficient, as adamw_kernel)
 //   p *= 1 - lr*wd                              decoupled weight decay; the reference applies it after the moments and
 //                                               before the update, which touches p only, so applying it first is the same
 //   m1 = b1 m1 + (1-b1) g;  v = b2 v + (1-b2) g^2;  m3 = b3_t m3 + (1-b3_t) g
@@ -159,7 +181,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(const lnx_adamw_desc* __rest
 // Weight decay is written p + (-lr*wd) p, one fma, as the reference's p.add_(p, alpha=-wd*lr).
 // 36 bytes per parameter: read p, g, m1, v, m3; write p, m1, v, m3.
 __global__ __launch_bounds__(256) void ademamix_kernel(const lnx_adamw_desc* __restrict__ descs, float* const* __restrict__ slow, int ndesc,
-                                                       const lnx_ademamix_hyper h, const float* __restrict__ sumsq, float max_norm) {
+                                                       const lnx_ademamix_hyper h, const float* __restrict__ sumsq, float max_norm,
+                                                       const float* __restrict__ flag, const float* __restrict__ grad_scale) {
     const int di = find_desc_index(descs, ndesc, blockIdx.x);
     const lnx_adamw_desc& d = descs[di];
     float* const m3p = slow[di];
@@ -167,12 +190,12 @@ __global__ __launch_bounds__(256) void ademamix_kernel(const lnx_adamw_desc* __r
     const float lr = h.lr[gi], b1 = h.beta1[gi], b2 = h.beta2[gi], eps = h.eps[gi], nlrwd = -(lr * h.weight_decay[gi]);
     const float omb1 = h.omb1[gi], omb2 = h.omb2[gi], b3 = h.beta3_t[gi], omb3 = h.omb3[gi], alpha = h.alpha_t[gi];
     const float step_size = lr / h.bias_c1[gi], sqrt_bc2 = sqrtf(h.bias_c2[gi]);
-    float coef = 1.0f;
-    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+    const float inv = guard_inv(grad_scale), coef = clip_coef(sumsq, max_norm, inv);
+    if (guard_skips(flag)) return;
     const int64_t base = (int64_t)(blockIdx.x - d.block_start) * OPT_ELEMS;
     const int64_t end = min(d.n, base + OPT_ELEMS);
     auto upd = [&](float g, float& p, float& m, float& v, float& s) __attribute__((always_inline)) {
-        g *= coef;
+        g = (g * inv) * coef;
         p = fmaf(nlrwd, p, p);
         m = fmaf(b1, m, omb1 * g);
         v = fmaf(b2, v, omb2 * g * g);
@@ -231,7 +254,7 @@ __global__ __launch_bounds__(256) void ademamix_kernel(const lnx_adamw_desc* __r
 
 // torch.optim.SGD (optimizers/build.py:89-96, 542-549, 578-585) over the same descriptor table; d.m is the momentum buffer, d.v is
 // not read.  Per element, in torch's order:
-//   g *= coef                                   (clip coefficient, as adamw_kernel)
+//   g = (g * inv) * coef                        (loss scale and clip coefficient, as adamw_kernel)
 //   g += wd p                                   coupled weight decay
 //   momentum != 0:  buf = first ? g : momentum buf + (1 - dampening) g;   g = nesterov ? g + momentum buf : buf
 //   p -= lr g
@@ -239,18 +262,18 @@ __global__ __launch_bounds__(256) void ademamix_kernel(const lnx_adamw_desc* __r
 // read.  Slots with momentum 0 touch no buffer at all (d.m may be NULL there).  20 bytes per parameter (read p, g, buf; write p,
 // buf), 16 in a first slot, 12 without momentum.  A descriptor with momentum but no buffer is left alone (the host API never builds one).
 __global__ __launch_bounds__(256) void sgd_kernel(const lnx_adamw_desc* __restrict__ descs, int ndesc, const lnx_sgd_hyper h, const float* __restrict__ sumsq,
-                                                  float max_norm) {
+                                                  float max_norm, const float* __restrict__ flag, const float* __restrict__ grad_scale) {
     const lnx_adamw_desc& d = find_desc(descs, ndesc, blockIdx.x);
     const int gi = d.group;
     const float lr = h.lr[gi], mom = h.momentum[gi], omd = 1.0f - h.dampening[gi], wd = h.weight_decay[gi];
     const bool nesterov = h.nesterov[gi] != 0, first = h.first[gi] != 0, has_buf = mom != 0.f, rd_buf = has_buf && !first;
     if (has_buf && d.m == nullptr) return;
-    float coef = 1.0f;
-    if (sumsq != nullptr && max_norm > 0.f) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+    const float inv = guard_inv(grad_scale), coef = clip_coef(sumsq, max_norm, inv);
+    if (guard_skips(flag)) return;
     const int64_t base = (int64_t)(blockIdx.x - d.block_start) * OPT_ELEMS;
     const int64_t end = min(d.n, base + OPT_ELEMS);
     auto upd = [&](float g, float& p, float& m) __attribute__((always_inline)) {
-        g *= coef;
+        g = (g * inv) * coef;
         g = fmaf(wd, p, g);
         if (has_buf) {
             m = first ? g : fmaf(mom, m, omd * g);
@@ -305,23 +328,51 @@ __global__ __launch_bounds__(256) void sgd_kernel(const lnx_adamw_desc* __restri
 
 extern "C" int lnx_adamw_blocks(int64_t numel) { return (int)((numel + OPT_ELEMS - 1) / OPT_ELEMS); }
 
-extern "C" int lnx_grad_sumsq(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, float* out, float* ws, void* stream) {
+// The unsuffixed entry points are the guarded ones with a NULL guard: the same launches with NULL flag and scale pointers.
+extern "C" int lnx_grad_sumsq_guarded(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, float* out, float* ws, const lnx_step_guard* guard,
+                                      void* stream) {
     LNX_CHECK(descs_dev && ndesc > 0 && total_blocks > 0 && out && ws, "lnx_grad_sumsq: bad arguments (ws: total_blocks floats)");
+    LNX_CHECK(guard == nullptr || (guard->flag != nullptr && guard->skipped != nullptr), "lnx_grad_sumsq_guarded: the guard needs its flag and its skipped counter");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(total_blocks), dim3(256), 0, st, descs_dev, ndesc, ws);
-    hipLaunchKernelGGL(grad_sumsq_fold_kernel, dim3(1), dim3(1024), 0, st, ws, total_blocks, out);
+    hipLaunchKernelGGL(grad_sumsq_fold_kernel, dim3(1), dim3(1024), 0, st, ws, total_blocks, out, guard != nullptr ? *guard : lnx_step_guard{});
     g_launches += 2;
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_grad_sumsq(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, float* out, float* ws, void* stream) {
+    return lnx_grad_sumsq_guarded(descs_dev, ndesc, total_blocks, out, ws, nullptr, stream);
+}
+
+extern "C" int lnx_adamw_step_guarded(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_adamw_hyper* hyper, const float* sumsq, float max_norm,
+                                      const lnx_step_guard* guard, void* stream) {
+    LNX_CHECK(descs_dev && ndesc > 0 && total_blocks > 0 && hyper, "lnx_adamw_step: bad arguments");
+    LNX_CHECK(hyper->ngroups > 0 && hyper->ngroups <= LNX_ADAMW_MAX_GROUPS, "lnx_adamw_step: ngroups=%d (max %d)", hyper->ngroups, LNX_ADAMW_MAX_GROUPS);
+    for (int i = 0; i < hyper->ngroups; ++i)
+        LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_adamw_step: bias corrections of group %d must be positive (step >= 1)", i);
+    LNX_CHECK(guard == nullptr || guard->flag != nullptr, "lnx_adamw_step_guarded: the guard has no flag");
+    hipLaunchKernelGGL(adamw_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, ndesc, *hyper, sumsq, max_norm,
+                       guard != nullptr ? (const float*)guard->flag : nullptr, guard != nullptr ? guard->grad_scale : nullptr);
+    g_launches += 1;
     LNX_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int lnx_adamw_step(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_adamw_hyper* hyper, const float* sumsq, float max_norm,
                               void* stream) {
-    LNX_CHECK(descs_dev && ndesc > 0 && total_blocks > 0 && hyper, "lnx_adamw_step: bad arguments");
-    LNX_CHECK(hyper->ngroups > 0 && hyper->ngroups <= LNX_ADAMW_MAX_GROUPS, "lnx_adamw_step: ngroups=%d (max %d)", hyper->ngroups, LNX_ADAMW_MAX_GROUPS);
+    return lnx_adamw_step_guarded(descs_dev, ndesc, total_blocks, hyper, sumsq, max_norm, nullptr, stream);
+}
+
+extern "C" int lnx_ademamix_step_guarded(const lnx_adamw_desc* descs_dev, float* const* slow_dev, int ndesc, int total_blocks, const lnx_ademamix_hyper* hyper,
+                                         const float* sumsq, float max_norm, const lnx_step_guard* guard, void* stream) {
+    LNX_CHECK(descs_dev && slow_dev && ndesc > 0 && total_blocks > 0 && hyper, "lnx_ademamix_step: bad arguments");
+    LNX_CHECK(hyper->ngroups > 0 && hyper->ngroups <= LNX_ADAMW_MAX_GROUPS, "lnx_ademamix_step: ngroups=%d (max %d)", hyper->ngroups, LNX_ADAMW_MAX_GROUPS);
     for (int i = 0; i < hyper->ngroups; ++i)
-        LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_adamw_step: bias corrections of group %d must be positive (step >= 1)", i);
-    hipLaunchKernelGGL(adamw_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, ndesc, *hyper, sumsq, max_norm);
+        LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_ademamix_step: bias corrections of slot %d must be positive (step >= 1)", i);
+    LNX_CHECK(guard == nullptr || guard->flag != nullptr, "lnx_ademamix_step_guarded: the guard has no flag");
+    hipLaunchKernelGGL(ademamix_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, slow_dev, ndesc, *hyper, sumsq, max_norm,
+                       guard != nullptr ? (const float*)guard->flag : nullptr, guard != nullptr ? guard->grad_scale : nullptr);
     g_launches += 1;
     LNX_LAUNCH_CHECK();
     return 0;
@@ -329,18 +380,11 @@ extern "C" int lnx_adamw_step(const lnx_adamw_desc* descs_dev, int ndesc, int to
 
 extern "C" int lnx_ademamix_step(const lnx_adamw_desc* descs_dev, float* const* slow_dev, int ndesc, int total_blocks, const lnx_ademamix_hyper* hyper,
                                  const float* sumsq, float max_norm, void* stream) {
-    LNX_CHECK(descs_dev && slow_dev && ndesc > 0 && total_blocks > 0 && hyper, "lnx_ademamix_step: bad arguments");
-    LNX_CHECK(hyper->ngroups > 0 && hyper->ngroups <= LNX_ADAMW_MAX_GROUPS, "lnx_ademamix_step: ngroups=%d (max %d)", hyper->ngroups, LNX_ADAMW_MAX_GROUPS);
-    for (int i = 0; i < hyper->ngroups; ++i)
-        LNX_CHECK(hyper->bias_c1[i] > 0.f && hyper->bias_c2[i] > 0.f, "lnx_ademamix_step: bias corrections of slot %d must be positive (step >= 1)", i);
-    hipLaunchKernelGGL(ademamix_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, slow_dev, ndesc, *hyper, sumsq, max_norm);
-    g_launches += 1;
-    LNX_LAUNCH_CHECK();
-    return 0;
+    return lnx_ademamix_step_guarded(descs_dev, slow_dev, ndesc, total_blocks, hyper, sumsq, max_norm, nullptr, stream);
 }
 
-extern "C" int lnx_sgd_step(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_sgd_hyper* hyper, const float* sumsq, float max_norm,
-                            void* stream) {
+extern "C" int lnx_sgd_step_guarded(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_sgd_hyper* hyper, const float* sumsq, float max_norm,
+                                    const lnx_step_guard* guard, void* stream) {
     LNX_CHECK(descs_dev != nullptr && hyper != nullptr, "lnx_sgd_step: NULL descriptor table or hyper-parameter table");
     LNX_CHECK(ndesc > 0, "lnx_sgd_step: ndesc=%d (must be positive)", ndesc);
     LNX_CHECK(total_blocks > 0, "lnx_sgd_step: total_blocks=%d (must be positive)", total_blocks);
@@ -352,10 +396,17 @@ extern "C" int lnx_sgd_step(const lnx_adamw_desc* descs_dev, int ndesc, int tota
         LNX_CHECK(!hyper->nesterov[i] || (hyper->momentum[i] > 0.f && hyper->dampening[i] == 0.f),
                   "lnx_sgd_step: nesterov in slot %d needs a momentum above zero and zero dampening", i);
     }
-    hipLaunchKernelGGL(sgd_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, ndesc, *hyper, sumsq, max_norm);
+    LNX_CHECK(guard == nullptr || guard->flag != nullptr, "lnx_sgd_step_guarded: the guard has no flag");
+    hipLaunchKernelGGL(sgd_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, ndesc, *hyper, sumsq, max_norm,
+                       guard != nullptr ? (const float*)guard->flag : nullptr, guard != nullptr ? guard->grad_scale : nullptr);
     g_launches += 1;
     LNX_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int lnx_sgd_step(const lnx_adamw_desc* descs_dev, int ndesc, int total_blocks, const lnx_sgd_hyper* hyper, const float* sumsq, float max_norm,
+                            void* stream) {
+    return lnx_sgd_step_guarded(descs_dev, ndesc, total_blocks, hyper, sumsq, max_norm, nullptr, stream);
 }
 
 extern "C" int64_t lnx_optim_launches(void) { return g_launches.load(); }

@@ -15,6 +15,9 @@ same descriptor table plus a parallel table of slow-EMA pointers, three with the
 `build_optimizer(config, model)` is the reference's optimizers/build.py with these classes, and `FusedMultiOptimizer` its
 MultiOptimizer with the clip block of train.py:279-313 inside `step()`: one norm pass over every gradient of the run, the clip
 coefficient applied by each sub-optimizer's kernel (`use_shared_clip`), nothing read back to the host.
+
+All five take `nonfinite_guard=True`: the skipped step of `torch.amp.GradScaler` (train.py:279-312 steps through `scaler.step`),
+decided on the device by the norm pass, and GradScaler's `found_inf` / `grad_scale` protocol (`_Clipped`).
 """
 import ctypes as C
 import math
@@ -66,55 +69,118 @@ def _upload(dev, *arrs):
 
 class _NormPass:
     """The global-norm pass: lnx_grad_sumsq over a device descriptor table (per-workgroup partials + a fixed-order fold) leaves the
-    sum of squares of the table's gradients in the one-element `sumsq`.  An optimizer whose own table lists every gradient calls
+    sum of squares of the table's gradients in `sumsq[0]` (a guarded pass, lnx_grad_sumsq_guarded, also the norm of the unscaled
+    gradients in `sumsq[1]`).  An optimizer whose own table lists every gradient calls
     `run`; `over_grads` keeps a gradient-only table for the others, rebuilt only when a gradient pointer changes."""
 
     def __init__(self):
-        self.sumsq = None      # the result, a device scalar
+        self.sumsq = None      # the result: [sum of squares, norm of the unscaled gradients (written by a guarded pass only)] on the device
         self._partials = None  # one float per workgroup
         self._key = None       # what the table of over_grads was built for
         self._table = None     # (device table, rows, workgroups)
 
     def reserve(self, dev, blocks):
         if self.sumsq is None or self.sumsq.device != dev:
-            self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
+            self.sumsq = torch.zeros(2, device=dev, dtype=torch.float32)
         if self._partials is None or self._partials.device != dev or self._partials.numel() < blocks:
             self._partials = torch.empty(blocks, device=dev, dtype=torch.float32)
 
-    def run(self, table, n, blocks):
+    def run(self, table, n, blocks, guard=None):
+        """guard: the step's lnx_step_guard; the fold launch then also decides whether the step is skipped"""
         self.reserve(table.device, blocks)
-        L.check(L.lib().lnx_grad_sumsq(C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self.sumsq.data_ptr()), C.c_void_p(self._partials.data_ptr()),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_grad_sumsq")
+        args = (C.c_void_p(table.data_ptr()), n, blocks, C.c_void_p(self.sumsq.data_ptr()), C.c_void_p(self._partials.data_ptr()))
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if guard is None:
+            L.check(L.lib().lnx_grad_sumsq(*args, stream), "lnx_grad_sumsq")
+        else:
+            L.check(L.lib().lnx_grad_sumsq_guarded(*args, C.byref(guard), stream), "lnx_grad_sumsq_guarded")
 
-    def over_grads(self, params):
+    def over_grads(self, params, guard=None):
         key = tuple((p.grad.data_ptr(), p.numel()) for p in params)
         if key != self._key:
             arr, blocks = _desc_table([(0, p, None, None) for p in params])
             self._table = (_upload(params[0].grad.device, arr), len(params), blocks)
             self._key = key
-        self.run(*self._table)
+        self.run(*self._table, guard)
+
+
+class _Guard:
+    """Device side of the non-finite guard: the flag of the last step (1: skipped) and the running count of skipped steps, and the
+    lnx_step_guard of a step, which adds the `found_inf` / `grad_scale` tensors that `torch.amp.GradScaler.step` hangs on the
+    optimizer for the duration of the call."""
+
+    def __init__(self):
+        self.flag = None     # fp32 [1]
+        self.skipped = None  # int64 [1]
+
+    def struct(self, dev, owner):
+        if self.flag is None or self.flag.device != dev:
+            self.flag = torch.zeros(1, device=dev, dtype=torch.float32)
+            self.skipped = torch.zeros(1, device=dev, dtype=torch.int64)
+        g = L.StepGuard()
+        g.flag, g.skipped = self.flag.data_ptr(), self.skipped.data_ptr()
+        for name in ("found_inf", "grad_scale"):
+            t = getattr(owner, name, None)
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != dev:
+                raise L.LnxError(f"{type(owner).__name__}: `{name}` must be a one-element fp32 tensor on the gradients' device (GradScaler on that device)")
+            setattr(g, name, t.data_ptr())
+        return g
 
 
 class _Clipped:
-    """What the fused optimizers and the multi-optimizer share: `max_grad_norm`, the norm pass and the norm it leaves"""
+    """What the fused optimizers and the multi-optimizer share: `max_grad_norm`, the norm pass and the norm it leaves, and the
+    non-finite guard.
+
+    `nonfinite_guard=True` is the skipped step of `torch.amp.GradScaler`, decided on the device: the norm pass runs at every step
+    (also without a clip) and its fold launch raises a flag when the sum of squares is not finite -- an inf or NaN gradient, or a finite
+    one whose square overflows fp32 (|g| above about 1.8e19) -- or when GradScaler's `found_inf` is non-zero.  Every kernel of the step
+    reads the flag first and returns: parameters, state tensors, `.grad` and Muon's workspace stay as they were.  The host never learns
+    of a skip, so `state["step"]` counts ATTEMPTED steps (torch leaves it alone on a skipped step), and a momentum buffer that FusedSGD
+    creates on a skipped step starts at zero (the next step then forms (1 - dampening) g where torch clones g).  The optimizer then
+    speaks GradScaler's protocol (`_step_supports_amp_scaling`): `scaler.step(opt)` hands it `found_inf` and, unless `scaler.unscale_(opt)`
+    ran, `grad_scale`, which the kernels divide out as they read the gradients; no value is read back to the host."""
 
     max_grad_norm = None
+    nonfinite_guard = False
+    _guard = None
+
+    def _init_guard(self, nonfinite_guard):
+        self.nonfinite_guard = bool(nonfinite_guard)
+        self._guard = _Guard() if self.nonfinite_guard else None
+
+    @property
+    def _step_supports_amp_scaling(self) -> bool:
+        """what torch.amp.GradScaler.step looks for: true exactly when the guard is on (an unguarded optimizer takes torch's generic path)"""
+        return self.nonfinite_guard
 
     def grad_norm(self) -> Optional[torch.Tensor]:
-        """total (pre-clip) L2 norm of the gradients seen by the last clipped step (device scalar, no sync); None without clipping"""
-        if self._norm.sumsq is None or self.max_grad_norm is None:
+        """total (pre-clip) L2 norm of the gradients seen by the last clipped or guarded step (device scalar, no sync), with GradScaler's
+        scale divided out; inf or NaN on a skipped step.  None without a clip and without the guard."""
+        if self._norm.sumsq is None or (self.max_grad_norm is None and not self.nonfinite_guard):
             return None
-        return self._norm.sumsq.sqrt()[0]
+        return self._norm.sumsq[1] if self.nonfinite_guard else self._norm.sumsq.sqrt()[0]
+
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """how many steps the guard has skipped (device int64 scalar, no sync); None without the guard or before the first step"""
+        return None if self._guard is None or self._guard.skipped is None else self._guard.skipped[0]
+
+    def last_step_skipped(self) -> Optional[torch.Tensor]:
+        """whether the guard skipped the last step (device bool scalar, no sync); None without the guard or before the first step"""
+        return None if self._guard is None or self._guard.flag is None else self._guard.flag[0] != 0
 
 
 class _SharedClip(_Clipped):
     """What the four fused optimizers share: `use_shared_clip(sumsq, max_norm)` hands the optimizer a device scalar with the sum of
     squares of ALL gradients of the run (FusedMultiOptimizer computes it once per step).  The optimizer then makes no norm pass of
-    its own and its kernel clips by that scalar; `use_shared_clip(None)` restores its own behaviour."""
+    its own and its kernel clips by that scalar; `use_shared_clip(None)` restores its own behaviour.  `guard` is the lnx_step_guard of the pass that
+    wrote the scalar (FusedMultiOptimizer's union pass, which decides for every sub-optimizer): the kernels then obey its flag and divide
+    its `grad_scale` out, and `max_norm` may be None (a guarded run without a clip)."""
 
     _shared = None
 
-    def use_shared_clip(self, sumsq: Optional[torch.Tensor], max_norm: Optional[float] = None):
+    def use_shared_clip(self, sumsq: Optional[torch.Tensor], max_norm: Optional[float] = None, guard=None):
         if sumsq is None:
             self._shared = None
             return
@@ -122,18 +188,23 @@ class _SharedClip(_Clipped):
             raise ValueError(f"{type(self).__name__}: max_grad_norm is set; an optimizer clips either by its own norm or by a shared one")
         if not isinstance(sumsq, torch.Tensor) or sumsq.dtype != torch.float32 or sumsq.numel() != 1:
             raise ValueError("use_shared_clip: sumsq must be a one-element fp32 tensor")
-        if max_norm is None or not max_norm > 0:
+        if guard is not None and self.nonfinite_guard:
+            raise ValueError(f"{type(self).__name__}: nonfinite_guard is set; a step is guarded either by the optimizer's own norm pass or by a shared one")
+        if (max_norm is None and guard is None) or (max_norm is not None and not max_norm > 0):
             raise ValueError(f"use_shared_clip: max_norm must be positive, got {max_norm}")
-        self._shared = (sumsq, float(max_norm))
+        self._shared = (sumsq, 0.0 if max_norm is None else float(max_norm), guard)
 
-    def _clip(self, norm_pass):
-        """(pointer of the sum of squares or None, max_norm) of this step; norm_pass() is run when the optimizer clips by itself"""
+    def _clip(self, dev, norm_pass):
+        """(pointer of the sum of squares or None, max_norm, lnx_step_guard or None) of this step; norm_pass(guard) is run when the
+        optimizer clips or guards by itself"""
         if self._shared is not None:
-            return self._shared[0].data_ptr(), self._shared[1]
-        if self.max_grad_norm is not None and self.max_grad_norm > 0:
-            norm_pass()
-            return self._norm.sumsq.data_ptr(), float(self.max_grad_norm)
-        return None, 0.0
+            return self._shared[0].data_ptr(), self._shared[1], self._shared[2]
+        clip = self.max_grad_norm is not None and self.max_grad_norm > 0
+        if clip or self.nonfinite_guard:
+            guard = self._guard.struct(dev, self) if self.nonfinite_guard else None
+            norm_pass(guard)
+            return self._norm.sumsq.data_ptr(), float(self.max_grad_norm) if clip else 0.0, guard
+        return None, 0.0, None
 
 
 class _ElementwiseOptimizer(_SharedClip, torch.optim.Optimizer):
@@ -144,11 +215,13 @@ class _ElementwiseOptimizer(_SharedClip, torch.optim.Optimizer):
       _STATE, _SLOT, _Hyper                    its state keys (the first two are desc.m and desc.v), what its slot key is, its hyper struct
       _state(group, p)                         (slot key, state tensors in _STATE order) of p for this step, the state created on first use
       _fill(h, si, group, slot_key)            slot si of the hyper struct
-      _launch(table, n, blocks, h, sumsq, max_norm, stream)    its lnx_*_step over the table (device address, rows, workgroups)
+      _launch(table, n, blocks, h, sumsq, max_norm, guard, stream)    its lnx_*_step over the table (device address, rows, workgroups),
+                                               the _guarded entry point when the step carries an lnx_step_guard
     and may give `_check_group` and `_behind`."""
 
-    def _init_step(self, max_grad_norm):
+    def _init_step(self, max_grad_norm, nonfinite_guard=False):
         self.max_grad_norm = max_grad_norm
+        self._init_guard(nonfinite_guard)
         self._table = None  # (device table, rows, workgroups)
         self._key = None    # slot and pointers of every row of the table
         self._norm = _NormPass()
@@ -200,8 +273,8 @@ class _ElementwiseOptimizer(_SharedClip, torch.optim.Optimizer):
         for (gi, slot_key), si in slots.items():
             self._fill(h, si, self.param_groups[gi], slot_key)
         table, n, blocks = self._table
-        sumsq, max_norm = self._clip(lambda: self._norm.run(table, n, blocks))
-        self._launch(table.data_ptr(), n, blocks, h, sumsq, max_norm, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        sumsq, max_norm, guard = self._clip(table.device, lambda guard: self._norm.run(table, n, blocks, guard))
+        self._launch(table.data_ptr(), n, blocks, h, sumsq, max_norm, guard, C.c_void_p(torch.cuda.current_stream().cuda_stream))
         return loss
 
 
@@ -232,16 +305,20 @@ class FusedAdamW(_AdamFamily):
     _STATE = ("exp_avg", "exp_avg_sq")
     _Hyper = L.AdamWHyper
 
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None,
+                 nonfinite_guard: bool = False):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameters")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) > L.ADAMW_MAX_GROUPS:
             raise ValueError(f"at most {L.ADAMW_MAX_GROUPS} parameter groups")
-        self._init_step(max_grad_norm)
+        self._init_step(max_grad_norm, nonfinite_guard)
 
-    def _launch(self, table, n, blocks, h, sumsq, max_norm, stream):
-        L.check(L.lib().lnx_adamw_step(C.c_void_p(table), n, blocks, C.byref(h), C.c_void_p(sumsq), C.c_float(max_norm), stream), "lnx_adamw_step")
+    def _launch(self, table, n, blocks, h, sumsq, max_norm, guard, stream):
+        if guard is None:
+            L.check(L.lib().lnx_adamw_step(C.c_void_p(table), n, blocks, C.byref(h), C.c_void_p(sumsq), C.c_float(max_norm), stream), "lnx_adamw_step")
+        else:
+            L.check(L.lib().lnx_adamw_step_guarded(table, n, blocks, C.byref(h), sumsq, max_norm, C.byref(guard), stream), "lnx_adamw_step_guarded")
 
 
 def ademamix_schedule(step: int, alpha: float, beta1: float, beta3: float, T_alpha_beta3: Optional[float]):
@@ -291,14 +368,14 @@ class FusedAdEMAMix(_AdamFamily):
     _Hyper = L.AdEMAMixHyper
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999, 0.9999), eps: float = 1e-8, weight_decay: float = 0, alpha: float = 5.0,
-                 T_alpha_beta3: Optional[float] = None, max_grad_norm: Optional[float] = None):
+                 T_alpha_beta3: Optional[float] = None, max_grad_norm: Optional[float] = None, nonfinite_guard: bool = False):
         _check_ademamix_group(lr, betas, eps, weight_decay, T_alpha_beta3)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, alpha=alpha, T_alpha_beta3=T_alpha_beta3))
         for g in self.param_groups:  # groups may carry their own values
             _check_ademamix_group(g["lr"], g["betas"], g["eps"], g["weight_decay"], g["T_alpha_beta3"])
         if len(self.param_groups) > L.ADAMW_MAX_GROUPS:
             raise ValueError(f"at most {L.ADAMW_MAX_GROUPS} parameter groups")
-        self._init_step(max_grad_norm)
+        self._init_step(max_grad_norm, nonfinite_guard)
 
     def _fill(self, h, si, group, t):
         # bias corrections, alpha_t and beta3_t all follow each parameter's own step count (as in the reference)
@@ -310,8 +387,12 @@ class FusedAdEMAMix(_AdamFamily):
     def _behind(self, items):
         return ((C.c_uint64 * len(items))(*(tensors[2].data_ptr() for _, _, tensors in items)),)  # the slow-EMA pointer of every row
 
-    def _launch(self, table, n, blocks, h, sumsq, max_norm, stream):
-        L.check(L.lib().lnx_ademamix_step(table, table + n * C.sizeof(L.AdamWDesc), n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_ademamix_step")
+    def _launch(self, table, n, blocks, h, sumsq, max_norm, guard, stream):
+        slow = table + n * C.sizeof(L.AdamWDesc)
+        if guard is None:
+            L.check(L.lib().lnx_ademamix_step(table, slow, n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_ademamix_step")
+        else:
+            L.check(L.lib().lnx_ademamix_step_guarded(table, slow, n, blocks, C.byref(h), sumsq, max_norm, C.byref(guard), stream), "lnx_ademamix_step_guarded")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -446,7 +527,8 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
     parameters whatever else is in the optimizer, so data-parallel replicas that each run the whole step stay equal.
     """
 
-    def __init__(self, params, lr=0.02, weight_decay=0.01, momentum=0.95, nesterov=True, ns_steps=5, strict=False, max_grad_norm: Optional[float] = None):
+    def __init__(self, params, lr=0.02, weight_decay=0.01, momentum=0.95, nesterov=True, ns_steps=5, strict=False, max_grad_norm: Optional[float] = None,
+                 nonfinite_guard: bool = False):
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= momentum < 1.0:
@@ -467,6 +549,7 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
         self._dev = None      # (device table, device tile tables, workspace, partials, MuonInfo)
         self.max_grad_norm = max_grad_norm
         self._norm = _NormPass()  # own clip: over a gradient-only descriptor table
+        self._init_guard(nonfinite_guard)
 
     def _build(self, order, dev):
         mats, tiles, info = muon_layout([_muon_shape(p) for _, p in order])
@@ -530,7 +613,9 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
         a = L.MuonStepArgs()
         a.n, a.mats, a.mats_dev, a.tiles_dev = len(order), C.addressof(mats), table.data_ptr(), tiles.data_ptr()
         a.workspace, a.workspace_bytes, a.partials = ws.data_ptr(), ws.numel(), part.data_ptr()
-        a.sumsq, a.max_norm = self._clip(lambda: self._norm.over_grads(with_grad))
+        a.sumsq, a.max_norm, guard = self._clip(dev, lambda guard: self._norm.over_grads(with_grad, guard))
+        if guard is not None:  # every launch of the step obeys its flag: the workspace's zero padding survives a skipped step
+            a.guard = C.pointer(guard)
         L.check(L.lib().lnx_muon_step(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_muon_step")
         return loss
 
@@ -552,7 +637,7 @@ class FusedSGD(_ElementwiseOptimizer):
     _Hyper = L.SGDHyper
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0, dampening: float = 0, weight_decay: float = 0, nesterov: bool = False,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, nonfinite_guard: bool = False):
         # torch's own constructor checks and its group keys (maximize, foreach, differentiable, fused, ...), whatever the torch version
         defaults = dict(torch.optim.SGD([torch.zeros(1)], lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov).defaults)
         super().__init__(params, defaults)
@@ -560,7 +645,7 @@ class FusedSGD(_ElementwiseOptimizer):
             self._check_group(g)
         if len(self.param_groups) > L.ADAMW_MAX_GROUPS // 2:
             raise ValueError(f"at most {L.ADAMW_MAX_GROUPS // 2} parameter groups (two hyper-parameter slots each)")
-        self._init_step(max_grad_norm)
+        self._init_step(max_grad_norm, nonfinite_guard)
 
     @staticmethod
     def _check_group(g):
@@ -584,15 +669,20 @@ class FusedSGD(_ElementwiseOptimizer):
         buf = st.get("momentum_buffer")
         first = buf is None
         if first:
-            buf = st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.preserve_format)  # the kernel writes all of it
+            # the kernel writes all of it -- unless a guard skips the step: the buffer then has to read as "no momentum yet"
+            guarded = self.nonfinite_guard or (self._shared is not None and self._shared[2] is not None)
+            buf = st["momentum_buffer"] = (torch.zeros_like if guarded else torch.empty_like)(p, memory_format=torch.preserve_format)
         return first, (buf,)
 
     def _fill(self, h, si, g, first):
         h.lr[si], h.momentum[si], h.dampening[si], h.weight_decay[si] = g["lr"], g["momentum"], g["dampening"], g["weight_decay"]
         h.nesterov[si], h.first[si] = 1 if g["nesterov"] else 0, 1 if first else 0
 
-    def _launch(self, table, n, blocks, h, sumsq, max_norm, stream):
-        L.check(L.lib().lnx_sgd_step(table, n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_sgd_step")
+    def _launch(self, table, n, blocks, h, sumsq, max_norm, guard, stream):
+        if guard is None:
+            L.check(L.lib().lnx_sgd_step(table, n, blocks, C.byref(h), sumsq, max_norm, stream), "lnx_sgd_step")
+        else:
+            L.check(L.lib().lnx_sgd_step_guarded(table, n, blocks, C.byref(h), sumsq, max_norm, C.byref(guard), stream), "lnx_sgd_step_guarded")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -612,23 +702,30 @@ class FusedMultiOptimizer(_Clipped):
     stable state-dict indices -- so the norm's bits do not depend on the order the optimizers were inserted in.  It is rebuilt
     only when a gradient pointer changes.  `.grad` is left as it was (clip_grad_norm_ scales it in place).
 
-    Refused: a sub-optimizer with its own `max_grad_norm`; with a clip, a sub-optimizer that is not FusedAdamW, FusedAdEMAMix,
-    FusedSGD or FusedMuon; a parameter held by two sub-optimizers (the reference would step it twice).
+    `nonfinite_guard=True` (see `_Clipped`): the union pass runs at every step, with or without a clip, and decides for all
+    sub-optimizers at once; `scaler.step(multi)` works as on a single fused optimizer, the `found_inf` / `grad_scale` it sets here going
+    to every sub-optimizer's kernels with the pass's flag.
+
+    Refused: a sub-optimizer with its own `max_grad_norm` or `nonfinite_guard`; with a clip or the guard, a sub-optimizer that is not
+    FusedAdamW, FusedAdEMAMix, FusedSGD or FusedMuon; a parameter held by two sub-optimizers (the reference would step it twice).
 
     `state_dict()` writes the layout the reference's code intends but does not produce (its saved per-optimizer "state" is always
     empty): `_version` 2, `_param_shapes`, `optimizers[name] = {"state": {stable index: ...}, "param_groups"}`.
     """
 
-    def __init__(self, optimizers: dict, max_grad_norm: Optional[float] = None):
+    def __init__(self, optimizers: dict, max_grad_norm: Optional[float] = None, nonfinite_guard: bool = False):
         self.optimizers = optimizers
         self.max_grad_norm = None if max_grad_norm is None or not max_grad_norm > 0 else float(max_grad_norm)
+        self._init_guard(nonfinite_guard)
         seen = {}
         for name, opt in optimizers.items():
             if getattr(opt, "max_grad_norm", None) is not None:
                 raise ValueError(f"FusedMultiOptimizer: sub-optimizer '{name}' has its own max_grad_norm; the clip is global, set it on the multi-optimizer")
-            if self.max_grad_norm is not None and not isinstance(opt, FUSED_OPTIMIZERS):
+            if getattr(opt, "nonfinite_guard", False):
+                raise ValueError(f"FusedMultiOptimizer: sub-optimizer '{name}' has its own nonfinite_guard; one pass decides for all, set it on the multi-optimizer")
+            if (self.max_grad_norm is not None or self.nonfinite_guard) and not isinstance(opt, FUSED_OPTIMIZERS):
                 raise ValueError(f"FusedMultiOptimizer: sub-optimizer '{name}' ({type(opt).__name__}) is not a fused optimizer; "
-                                 "the shared clip needs FusedAdamW, FusedAdEMAMix, FusedSGD or FusedMuon")
+                                 "the shared clip and the non-finite guard need FusedAdamW, FusedAdEMAMix, FusedSGD or FusedMuon")
             for group in opt.param_groups:
                 for p in group["params"]:
                     if id(p) in seen:
@@ -650,16 +747,17 @@ class FusedMultiOptimizer(_Clipped):
     @torch.no_grad()
     def step(self, closure=None):
         loss = _closure_loss(closure)
-        if self.max_grad_norm is not None:
+        if self.max_grad_norm is not None or self.nonfinite_guard:
             with_grad = [p for p in self._ordered_params() if p.grad is not None]
             if with_grad:
                 dev = with_grad[0].device
                 for p in with_grad:
                     if not (p.grad.is_cuda and _dense_fp32(p.grad, dev)):
                         raise L.LnxError("FusedMultiOptimizer needs contiguous fp32 gradients on one GPU")
-                self._norm.over_grads(with_grad)  # the union table
+                guard = self._guard.struct(dev, self) if self.nonfinite_guard else None  # with GradScaler's found_inf / grad_scale
+                self._norm.over_grads(with_grad, guard)  # the union table
                 for opt in self.optimizers.values():
-                    opt.use_shared_clip(self._norm.sumsq, self.max_grad_norm)
+                    opt.use_shared_clip(self._norm.sumsq[:1], self.max_grad_norm, guard)
         for opt in self.optimizers.values():
             opt.step()
         return loss
@@ -671,6 +769,8 @@ class FusedMultiOptimizer(_Clipped):
         pre = self.grad_norm()
         if pre is None:
             return None
+        if self.max_grad_norm is None:  # guarded, not clipped
+            return pre, pre, pre
         coef = torch.clamp(self.max_grad_norm / (pre + 1e-6), max=1.0)
         return pre, pre * coef, pre
 
@@ -774,7 +874,7 @@ def set_weight_decay(model, skip_list=(), skip_keywords=()):
     return [{"params": has_decay}, {"params": no_decay, "weight_decay": 0.0}]
 
 
-def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_reference: bool = False):
+def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_reference: bool = False, nonfinite_guard: bool = False):
     """optimizers/build.py's `build_optimizer`, branch for branch, with the fused classes: `OPTIMIZER.NAME` sgd / adamw / ademamix over
     the decay / no-decay split; muon as {"MUON": FusedMuon, "ADAMW": FusedAdamW}; and with `OPTIMIZER.PARAMETER_GROUPS.ENABLED` one
     optimizer per group (filters of `loss.param_filter`, `LR_MULTIPLIER`, `WEIGHT_DECAY`, `{group}_ADAMW` for the non-matrix parameters
@@ -785,6 +885,7 @@ def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_refere
     `max_grad_norm`, several get it through `FusedMultiOptimizer`: either way the clip of train.py:279-313 is inside `step()`.
     4-D parameters selected for Muon are trained.  The reference never updates them (it hands Muon wrappers whose .grad stays None):
     freeze_4d_like_reference=True leaves them out of every optimizer, which is what the reference effectively does.
+    nonfinite_guard: the device-side skipped step of GradScaler (see `_Clipped`), on the single optimizer or on the FusedMultiOptimizer.
     """
     if max_grad_norm == "config":
         max_grad_norm = _cfg(config, "TRAIN.CLIP_GRAD", 5.0)
@@ -797,15 +898,16 @@ def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_refere
     muon_kw = dict(momentum=float(_cfg(O, "MUON.MOMENTUM", 0.95)), nesterov=bool(_cfg(O, "MUON.NESTEROV", True)), ns_steps=int(_cfg(O, "MUON.NS_STEPS", 5)),
                    strict=bool(_cfg(O, "MUON.STRICT", False)))  # MUON.USE_DISTRIBUTED: FusedMuon all the same (sharding is out of scope)
 
-    def make(kind, params, lr, wd, own_clip=None):
+    def make(kind, params, lr, wd, own_clip=None, own_guard=False):
+        own = dict(max_grad_norm=own_clip, nonfinite_guard=own_guard)
         if kind == "sgd":
-            return FusedSGD(params, lr=lr, momentum=momentum, weight_decay=wd, nesterov=True, max_grad_norm=own_clip)
+            return FusedSGD(params, lr=lr, momentum=momentum, weight_decay=wd, nesterov=True, **own)
         if kind == "adamw":
-            return FusedAdamW(params, lr=lr, eps=eps, betas=betas[:2], weight_decay=wd, max_grad_norm=own_clip)
+            return FusedAdamW(params, lr=lr, eps=eps, betas=betas[:2], weight_decay=wd, **own)
         if kind == "ademamix":
-            return FusedAdEMAMix(params, lr=lr, betas=betas, eps=eps, weight_decay=wd, alpha=alpha, T_alpha_beta3=t_ab3, max_grad_norm=own_clip)
+            return FusedAdEMAMix(params, lr=lr, betas=betas, eps=eps, weight_decay=wd, alpha=alpha, T_alpha_beta3=t_ab3, **own)
         if kind == "muon":
-            return FusedMuon(params, lr=lr, weight_decay=wd, max_grad_norm=own_clip, **muon_kw)
+            return FusedMuon(params, lr=lr, weight_decay=wd, **own, **muon_kw)
         raise ValueError(f"Unknown optimizer: {kind}")
 
     def muon_split(params):
@@ -818,7 +920,7 @@ def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_refere
         if name in ("sgd", "adamw", "ademamix"):
             skip = model.no_weight_decay() if hasattr(model, "no_weight_decay") else ()
             skip_kw = model.no_weight_decay_keywords() if hasattr(model, "no_weight_decay_keywords") else ()
-            return make(name, set_weight_decay(model, skip, skip_kw), base_lr, wd_default, clip)
+            return make(name, set_weight_decay(model, skip, skip_kw), base_lr, wd_default, clip, nonfinite_guard)
         if name != "muon":
             raise ValueError(f"Unknown optimizer: {name}")
         cand, rest = [], []
@@ -829,10 +931,11 @@ def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_refere
         mats, other = muon_split(cand)
         adamw = other + rest
         if mats and adamw:
-            return FusedMultiOptimizer({"MUON": make("muon", mats, base_lr, wd_default), "ADAMW": make("adamw", adamw, base_lr, wd_default)}, max_grad_norm=clip)
+            return FusedMultiOptimizer({"MUON": make("muon", mats, base_lr, wd_default), "ADAMW": make("adamw", adamw, base_lr, wd_default)}, max_grad_norm=clip,
+                                       nonfinite_guard=nonfinite_guard)
         if not mats and not adamw:
             raise ValueError("build_optimizer: the model has no trainable parameter")
-        return make("muon", mats, base_lr, wd_default, clip) if mats else make("adamw", adamw, base_lr, wd_default, clip)  # one optimizer: bare
+        return make("muon" if mats else "adamw", mats or adamw, base_lr, wd_default, clip, nonfinite_guard)  # one optimizer: bare
 
     G = _cfg(O, "PARAMETER_GROUPS", None)
     named = [(n, p) for n, p in model.named_parameters()]
@@ -874,4 +977,4 @@ def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_refere
         if default_kind not in ("sgd", "adamw", "ademamix", "muon"):
             raise ValueError(f"Unknown optimizer: {default_kind}")
         add("DEFAULT", default_kind, unmatched, base_lr, default_wd, "DEFAULT_MUON", "DEFAULT_ADAMW")
-    return FusedMultiOptimizer(optimizers, max_grad_norm=clip)
+    return FusedMultiOptimizer(optimizers, max_grad_norm=clip, nonfinite_guard=nonfinite_guard)

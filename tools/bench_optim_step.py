@@ -1,6 +1,7 @@
 """The optimizer step of a configured run, clip included: `build_optimizer`'s fused step against the best the package offered before it.
 
     python tools/bench_optim_step.py [--steps 50] [--warmup 10] [--repeats 7] [--log profiles/optim_build_bench.log]
+                                     [--guard] [--other-lib PATH]
 
 Parameters: mFormerV1_sm with four heads (shapes and names from the model built on the CPU), seeded values and gradients on the device,
 TRAIN.CLIP_GRAD 5.0 with a gradient norm above it.  Two jobs:
@@ -11,11 +12,17 @@ TRAIN.CLIP_GRAD 5.0 with a gradient norm above it.  Two jobs:
          clip_grad_norm_(5.0) and its .item() -- then FusedMuon.step() and FusedAdamW.step().
   sgd    OPTIMIZER.NAME = sgd.  `fused`: FusedSGD.step() with its own clip; `before`: the same two clip passes, then torch.optim.SGD.step().
 
+--guard adds the non-finite guard to both jobs: `guard` is `fused` built with nonfinite_guard=True (the same launches; every workgroup
+reads the skip flag first), `noclip` and `guard-noclip` the step without a clip, guard off and on (the guard forces the norm pass: two
+more launches).  --other-lib PATH adds `other`: `fused` on a second optimizer whose calls go to the library at PATH, e.g. one built from
+the parent commit, so two builds alternate in one process on one device.
+
 The candidates of a job run in this process on the same device and alternate round by round (`--repeats` rounds); a round times
 `--steps` steps between two device events after `--warmup` untimed ones.  Reported: median and range of the rounds in microseconds
 per step, and launches per step where the library counts them.  Last line: one JSON object; the log file gets the same text.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -81,8 +88,32 @@ def window(step, steps):
     return e0.elapsed_time(e1) * 1e3 / steps  # microseconds per step
 
 
+def through(lib, step):
+    """`step` with every library call of linnaeus_amd going to `lib`"""
+
+    def run():
+        mine, L._lib = L._lib, lib
+        try:
+            return step()
+        finally:
+            L._lib = mine
+
+    run.lib = lib
+    return run
+
+
+def load_other(path):
+    """a second build of the library, with the argument types of the entry points an optimizer step calls"""
+    lib, mine = C.CDLL(path), L.lib()
+    for name in ("lnx_sgd_step", "lnx_ademamix_step", "lnx_muon_step", "lnx_muon_layout"):
+        getattr(lib, name).argtypes = getattr(mine, name).argtypes
+    lib.lnx_last_error.restype = C.c_char_p
+    lib.lnx_optim_launches.restype = lib.lnx_muon_launches.restype = C.c_int64
+    return lib
+
+
 def launches(step):
-    lib = L.lib()
+    lib = getattr(step, "lib", None) or L.lib()
     torch.cuda.synchronize()
     o, m = lib.lnx_optim_launches(), lib.lnx_muon_launches()
     step()
@@ -112,6 +143,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--log", default=os.path.join(REPO, "profiles", "optim_build_bench.log"))
+    ap.add_argument("--guard", action="store_true", help="add the rows of the non-finite guard")
+    ap.add_argument("--other-lib", default=None, help="a second build of liblnx_hip.so: adds the row `other`")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_optim_step.py measures on the GPU; there is none here")
@@ -123,6 +156,29 @@ def main():
 
     gen = torch.Generator(device="cuda").manual_seed(0)
     res = {"device": torch.cuda.get_device_name(0), "steps": args.steps, "repeats": args.repeats, "clip": CLIP}
+    other = None
+    if args.other_lib:
+        other = load_other(args.other_lib)
+        res["lnx_version"], res["other_lnx_version"] = L.lib().lnx_version(), other.lnx_version()
+        say(f"library version {res['lnx_version']}; other library {args.other_lib}: version {res['other_lnx_version']}")
+
+    def extra_rows(name):
+        """the rows of --guard and --other-lib for OPTIMIZER.NAME = name, each on parameters of its own"""
+        rows, keep = {}, []
+
+        def row(key, wrap=lambda f: f, **kw):
+            model = fresh()
+            opt = build_optimizer(config(name), model, **kw)
+            keep.append((model, opt))
+            rows[key] = wrap(opt.step)
+
+        if other is not None:
+            row("other", lambda f: through(other, f))
+        if args.guard:
+            row("guard", nonfinite_guard=True)
+            row("noclip", max_grad_norm=None)
+            row("guard-noclip", max_grad_norm=None, nonfinite_guard=True)
+        return rows, keep
 
     def fresh():
         gen.manual_seed(0)
@@ -153,10 +209,11 @@ def main():
         ref.optimizers["ADAMW"].step()
 
     say(f"muon: {len(multi.optimizers['MUON'].param_groups[0]['params'])} matrices to FusedMuon, {len(multi.optimizers['ADAMW'].param_groups[0]['params'])} tensors to FusedAdamW")
-    res["muon"] = run_job({"fused": fused, "fused+read": fused_read, "before": before}, args, say)
+    rows, keep = extra_rows("muon")
+    res["muon"] = run_job({"fused": fused, "fused+read": fused_read, "before": before, **rows}, args, say)
     res["muon"]["speedup"] = round(res["muon"]["before"]["us_median"] / res["muon"]["fused"]["us_median"], 3)
     say(f"  before / fused = {res['muon']['speedup']:.3f}x")
-    del multi, ref, a, b, b_params
+    del multi, ref, a, b, b_params, rows, keep
     torch.cuda.empty_cache()
 
     # ---- sgd
@@ -170,7 +227,10 @@ def main():
         tsgd.step()
 
     say(f"sgd: {n_params * 20 / 1e6:.0f} MB of update traffic and {n_params * 4 / 1e6:.0f} MB of norm pass per fused step")
-    res["sgd"] = run_job({"fused": sgd.step, "before": before_sgd}, args, say)
+    rows, keep = extra_rows("sgd")
+    res["sgd"] = run_job({"fused": sgd.step, "before": before_sgd, **rows}, args, say)
+    if args.guard:
+        say(f"sgd: every guarded step of this run was taken: skipped_steps() = {int(keep[-1][1].skipped_steps())}")
     res["sgd"]["speedup"] = round(res["sgd"]["before"]["us_median"] / res["sgd"]["fused"]["us_median"], 3)
     res["sgd"]["fused_GBps"] = round(n_params * 24 / (res["sgd"]["fused"]["us_median"] * 1e-6) / 1e9, 1)
     say(f"  before / fused = {res['sgd']['speedup']:.3f}x; fused step moves {n_params * 24 / 1e6:.0f} MB: {res['sgd']['fused_GBps']:.0f} GB/s end to end (launch gaps included)")
