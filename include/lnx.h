@@ -1086,8 +1086,44 @@ typedef struct lnx_muon_step_args {
     const lnx_step_guard* guard;
 } lnx_muon_step_args;
 int lnx_muon_step(const lnx_muon_step_args* args, void* stream);
-/* launches made by lnx_muon_step since the library was loaded (host-side counter, as lnx_nt_kernel_launches) */
+/* launches made by lnx_muon_step, lnx_muon_orthogonalize and lnx_muon_apply_packed since the library was loaded (host-side counter, as
+ * lnx_nt_kernel_launches) */
 int64_t lnx_muon_launches(void);
+
+/* Muon sharded over data-parallel ranks (lnx_version 118; the reference's DistributedMuon, muon.py:200-428): every rank holds the same
+ * all-reduced gradients, orthogonalises only the matrices it OWNS, and the ranks all-gather the bf16 updates.  Each matrix gives the same
+ * bits alone or in a set, so the sharded step gives the bits of lnx_muon_step.
+ *   lnx_muon_partition      host only, no GPU, a pure function of its inputs: every rank computes the same table without communication.
+ *                           Cost of matrix i: ns_steps (4 mp^2 np + 2 mp^3), the MFMA FLOPs of its three products with mp, np as
+ *                           lnx_muon_layout pads them; mp np when ns_steps = 0.  Longest-processing-time greedy: the matrices by
+ *                           (cost descending, index ascending), each to the least-loaded rank, the lowest rank on ties.  Inside a rank's
+ *                           segment its matrices lie in table order, each at a multiple of LNX_MUON_SEG_ALIGN elements; *seg_elems is the
+ *                           largest segment rounded up to that multiple (all_gather_into_tensor needs equal parts, so every segment is
+ *                           padded to it).  owner and elem_off hold n entries, rank_cost holds world.
+ *   lnx_muon_orthogonalize  the launches of lnx_muon_step over a table of the OWNED matrices (its layout, and so the workspace, is of
+ *                           those alone) except the last: in place of the update, muon_pack_kernel writes each O as bf16 in logical
+ *                           [rows, cols] row-major order (tall matrices are un-transposed here) at seg + out_off[i] elements.  p is not
+ *                           touched; a matrix with g == NULL writes nothing; a step skipped by the guard writes nothing.
+ *                           3 * max(ns_steps) + 3 launches.  out_off is given twice, as the table is: the host copy is checked (inside
+ *                           seg_elems, multiples of LNX_MUON_SEG_ALIGN, pairwise disjoint), the device copy is what the kernel reads.
+ *   lnx_muon_apply_packed   ONE launch over all matrices of the optimizer: p = p * decay - step * O, the expression of lnx_muon_step's last
+ *                           launch, with O read from the gathered [world * seg_elems] bf16 buffer at `off` elements
+ *                           (owner * seg_elems + elem_off).  An entry with off < 0 is skipped (a parameter without a gradient).  Obeys the
+ *                           guard's flag (guard may be NULL).  block_start counts workgroups of LNX_MUON_ELEMS elements, skipped
+ *                           entries included.  The host table is checked (offsets inside the gathered size, regions pairwise disjoint,
+ *                           block_start) before the launch. */
+#define LNX_MUON_SEG_ALIGN 128 /* elements: 256 bytes */
+int lnx_muon_partition(const int* shapes, const int* ns_steps, int n, int world, int* owner, int64_t* elem_off, int64_t* seg_elems, int64_t* rank_cost);
+int lnx_muon_orthogonalize(const lnx_muon_step_args* args, const int64_t* out_off_host, const int64_t* out_off_dev, void* seg, int64_t seg_elems, void* stream);
+typedef struct lnx_muon_packed {
+    float* p;        /* parameter, fp32 [numel] contiguous */
+    int64_t off;     /* first element of its O in the gathered buffer, or < 0: skipped this step */
+    int64_t numel;
+    float decay, step;
+    int block_start; /* first workgroup of the launch */
+} lnx_muon_packed;
+int lnx_muon_apply_packed(const lnx_muon_packed* table_host, const lnx_muon_packed* table_dev, int n, const void* gathered, int64_t seg_elems, int world,
+                          const lnx_step_guard* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * GradNorm task weighting (LOSS.GRAD_WEIGHTING.TASK.TYPE = gradnorm): loss/gradnorm.py GradNormModule.measure_and_update on the

@@ -16,6 +16,6 @@ from .registry import build_model, create_model, install_into_linnaeus, register
 from .model import mFormerV1  # noqa: F401
 from . import autobatch, inference, loss, metrics, optim, prefetch, rl  # noqa: F401
 from .inference import DevicePredictor, DevicePreprocessor  # noqa: F401
-from .optim import FusedMultiOptimizer, FusedMuon, FusedSGD, build_optimizer  # noqa: F401
+from .optim import FusedMultiOptimizer, FusedMuon, FusedSGD, ShardedFusedMuon, build_optimizer  # noqa: F401
 from .rl import AbstentionPolicy, AbstentionReward, evaluate_policy, ppo_update, rollout  # noqa: F401
 from .collate import GPUMetaMasking, GPUTrainCollate, mask_meta_components  # noqa: F401

@@ -152,6 +152,13 @@ class MuonStepArgs(C.Structure):  # == lnx_muon_step_args
                 ("guard", C.POINTER(StepGuard))]
 
 
+class MuonPacked(C.Structure):  # == lnx_muon_packed
+    _fields_ = [("p", C.c_void_p), ("off", C.c_int64), ("numel", C.c_int64), ("decay", C.c_float), ("step", C.c_float), ("block_start", C.c_int)]
+
+
+MUON_SEG_ALIGN = 128  # == LNX_MUON_SEG_ALIGN
+MUON_SHARDED_STRUCTS = {"lnx_muon_packed": MuonPacked}
+
 # the argument structs of include/lnx.h by their C names (tests compare sizeof against a compiled probe)
 MUON_STRUCTS = {"lnx_muon_mat": MuonMat, "lnx_muon_tile": MuonTile, "lnx_muon_info": MuonInfo, "lnx_muon_step_args": MuonStepArgs}
 GUARD_STRUCTS = {"lnx_step_guard": StepGuard, "lnx_muon_step_args": MuonStepArgs}
@@ -328,6 +335,10 @@ def lib() -> C.CDLL:
             _lib.lnx_muon_layout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MuonInfo)]
             _lib.lnx_muon_step.argtypes = [C.POINTER(MuonStepArgs), C.c_void_p]
             _lib.lnx_muon_launches.restype = C.c_int64
+        if hasattr(_lib, "lnx_muon_partition"):
+            _lib.lnx_muon_partition.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+            _lib.lnx_muon_orthogonalize.argtypes = [C.POINTER(MuonStepArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+            _lib.lnx_muon_apply_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(StepGuard), C.c_void_p]
         if hasattr(_lib, "lnx_grad_sumsq_guarded"):
             guard = C.POINTER(StepGuard)
             _lib.lnx_grad_sumsq_guarded.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, guard, C.c_void_p]
@@ -431,7 +442,7 @@ EXPORTS = [
     "lnx_dwconv7_fwd", "lnx_dwconv7_fwd_kept", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_kept", "lnx_dwconv7_wgrad_ws_floats",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_fwd_compact", "lnx_attn_bwd_compact", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
     "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_drop_compact_conv_blocks", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
-    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_taxonomy_rows", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_grad_sumsq_guarded", "lnx_adamw_step_guarded", "lnx_ademamix_step_guarded", "lnx_sgd_step_guarded", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
+    "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_taxonomy_rows", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_grad_sumsq_guarded", "lnx_adamw_step_guarded", "lnx_ademamix_step_guarded", "lnx_sgd_step_guarded", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_muon_partition", "lnx_muon_orthogonalize", "lnx_muon_apply_packed", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_hier_refine_fwd", "lnx_hier_refine_bwd", "lnx_hier_refine_launches",
     "lnx_abstain_act", "lnx_ppo_advantages", "lnx_ppo_loss_fwd", "lnx_ppo_loss_bwd", "lnx_abstain_launches",

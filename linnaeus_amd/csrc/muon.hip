@@ -6,11 +6,16 @@
 //   muon_ns_kernel<0/1/2>  A = X X^T;  B = c A A + b A;  X = B X + a X (and X^T): grouped NT products, one wave per 32 x 32 output tile,
 //                          fragments straight from L2 (every operand of a step fits there), fp32 accumulate, one rounding
 //   muon_apply_kernel      p = p * decay - step * O
+// Sharded over data-parallel ranks (lnx_muon_partition): lnx_muon_orthogonalize runs all but the last launch over the matrices a rank owns and
+//   muon_pack_kernel          writes each O as bf16 in logical row-major order into the rank's segment of the buffer the ranks all-gather;
+//   muon_apply_packed_kernel  p = p * decay - step * O for ALL matrices out of the gathered buffer (lnx_muon_apply_packed), the same expression
 // Operands are zero-padded to tile multiples (lnx_muon_layout), so no kernel has an edge case: a padded row or column of X gives
 // zero rows / columns of A and B and stays zero in X' = B X + a X.  No atomics: the same inputs give the same bits, alone or in a set.
 // With a non-finite guard (lnx_step_guard) EVERY launch reads the guard's flag before it touches a tensor and returns when it is set: products over a NaN
 // operand would turn the workspace's zero padding, written once and relied on for ever, into NaN.
+#include <algorithm>
 #include <atomic>
+#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -200,6 +205,9 @@ __global__ __launch_bounds__(256) void muon_ns_kernel(const lnx_muon_mat* __rest
         }
 }
 
+// the update, one expression for both apply kernels: the sharded step gives the bits of the unsharded one
+__device__ __forceinline__ float muon_update(float p, float o, float decay, float nstep) { return fmaf(nstep, o, p * decay); }
+
 __global__ __launch_bounds__(256) void muon_apply_kernel(const lnx_muon_mat* __restrict__ mats, int n, const char* __restrict__ ws, const float* __restrict__ flag) {
     const lnx_muon_mat& d = mats[find_mat(mats, n, blockIdx.x)];
     if (d.g == nullptr || guard_skips(flag)) return;
@@ -210,7 +218,80 @@ __global__ __launch_bounds__(256) void muon_apply_kernel(const lnx_muon_mat* __r
     const float decay = d.decay, nstep = -d.step;
     for (int64_t i = base + threadIdx.x; i < end; i += 256) {
         const float o = (float)X[x_index(d, (int)(i / d.cols), (int)(i % d.cols))];
-        d.p[i] = fmaf(nstep, o, d.p[i] * decay);
+        d.p[i] = muon_update(d.p[i], o, decay, nstep);
+    }
+}
+
+// The sharded step's hand-over: O of every owned matrix as bf16 in logical [rows, cols] row-major order at seg + out_off[matrix]
+// (multiples of 128 elements in a 256-byte aligned segment).  A thread takes four consecutive logical elements: one 8-byte store, and
+// one 8-byte load where they are consecutive in X too (a wide matrix whose cols is a multiple of 4); a tall matrix is un-transposed
+// by four strided 2-byte loads.  The last numel % 4 elements of a matrix are stored one by one.
+__global__ __launch_bounds__(256) void muon_pack_kernel(const lnx_muon_mat* __restrict__ mats, int n, const char* __restrict__ ws,
+                                                        const int64_t* __restrict__ out_off, bf16_t* __restrict__ seg, const float* __restrict__ flag) {
+    const int m = find_mat(mats, n, blockIdx.x);
+    const lnx_muon_mat& d = mats[m];
+    if (d.g == nullptr || guard_skips(flag)) return;
+    const bf16_t* __restrict__ X = reinterpret_cast<const bf16_t*>(ws + d.x_off);
+    bf16_t* __restrict__ out = seg + out_off[m];
+    const int64_t numel = (int64_t)d.rows * d.cols;
+    const int64_t base = (int64_t)(blockIdx.x - d.block_start) * ELEMS;
+    const int64_t end = min(numel, base + ELEMS);
+    const bool wide4 = d.rows <= d.cols && (d.cols & 3) == 0;
+    for (int64_t i = base + 4 * (int64_t)threadIdx.x; i < end; i += 1024) {
+        if (i + 4 <= end) {
+            uint2 w;
+            if (wide4) {
+                w = *reinterpret_cast<const uint2*>(X + x_index(d, (int)(i / d.cols), (int)(i % d.cols)));
+            } else {
+                bf16_t* we = reinterpret_cast<bf16_t*>(&w);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) we[j] = X[x_index(d, (int)((i + j) / d.cols), (int)((i + j) % d.cols))];
+            }
+            *reinterpret_cast<uint2*>(out + i) = w;
+        } else {
+            for (int64_t k = i; k < end; ++k) out[k] = X[x_index(d, (int)(k / d.cols), (int)(k % d.cols))];
+        }
+    }
+}
+
+// index of the entry that owns workgroup `block` (block_start ascending)
+__device__ __forceinline__ int find_packed(const lnx_muon_packed* __restrict__ t, int n, int block) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t[mid].block_start <= block) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// p = p * decay - step * O over the gathered buffer: both operands contiguous.  A thread takes four consecutive elements: p as one
+// 16-byte load and store, O as one 8-byte load, when the two addresses allow it (uniform over the workgroup); the last numel % 4
+// elements, and a misaligned entry, go one by one.
+__global__ __launch_bounds__(256) void muon_apply_packed_kernel(const lnx_muon_packed* __restrict__ table, int n, const bf16_t* __restrict__ gathered,
+                                                                const float* __restrict__ flag) {
+    const lnx_muon_packed& d = table[find_packed(table, n, blockIdx.x)];
+    if (d.off < 0 || guard_skips(flag)) return;
+    float* __restrict__ p = d.p;
+    const bf16_t* __restrict__ o = gathered + d.off;
+    const int64_t base = (int64_t)(blockIdx.x - d.block_start) * ELEMS;
+    const int64_t end = min(d.numel, base + ELEMS);
+    const float decay = d.decay, nstep = -d.step;
+    const bool vec = (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (reinterpret_cast<uintptr_t>(o) & 7) == 0;
+    for (int64_t i = base + 4 * (int64_t)threadIdx.x; i < end; i += 1024) {
+        if (vec && i + 4 <= end) {
+            float4 pv = *reinterpret_cast<const float4*>(p + i);
+            const uint2 ow = *reinterpret_cast<const uint2*>(o + i);
+            const bf16_t* oe = reinterpret_cast<const bf16_t*>(&ow);
+            pv.x = muon_update(pv.x, (float)oe[0], decay, nstep);
+            pv.y = muon_update(pv.y, (float)oe[1], decay, nstep);
+            pv.z = muon_update(pv.z, (float)oe[2], decay, nstep);
+            pv.w = muon_update(pv.w, (float)oe[3], decay, nstep);
+            *reinterpret_cast<float4*>(p + i) = pv;
+        } else {
+            const int64_t stop = min(end, i + 4);
+            for (int64_t k = i; k < stop; ++k) p[k] = muon_update(p[k], (float)o[k], decay, nstep);
+        }
     }
 }
 
@@ -276,12 +357,22 @@ extern "C" int lnx_muon_layout(const int* shapes, int n, lnx_muon_mat* mats, lnx
 
 extern "C" int64_t lnx_muon_launches(void) { return g_launches.load(); }
 
-extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
-    LNX_CHECK(a != nullptr, "lnx_muon_step: args is NULL");
-    LNX_CHECK(a->n > 0 && a->mats && a->mats_dev && a->tiles_dev && a->workspace && a->partials, "lnx_muon_step: bad arguments (n > 0 and no NULL table, workspace or partials)");
-    LNX_CHECK((reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0, "lnx_muon_step: the workspace must be 256-byte aligned");
-    LNX_CHECK(a->guard == nullptr || a->guard->flag != nullptr, "lnx_muon_step: the guard has no flag");
-    const float* flag = a->guard != nullptr ? a->guard->flag : nullptr;
+namespace {
+
+// What lnx_muon_step and lnx_muon_orthogonalize share.  check_step: every check of the arguments, nothing launched; launch_front: the
+// momentum, normalise and Newton-Schulz launches (2 + 3 * max_steps).
+struct StepPlan {
+    lnx_muon_info info;
+    int max_steps;
+    const float* flag;
+};
+
+int check_step(const lnx_muon_step_args* a, const char* who, StepPlan* plan) {
+    LNX_CHECK(a != nullptr, "%s: args is NULL", who);
+    LNX_CHECK(a->n > 0 && a->mats && a->mats_dev && a->tiles_dev && a->workspace && a->partials, "%s: bad arguments (n > 0 and no NULL table, workspace or partials)", who);
+    LNX_CHECK((reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+    LNX_CHECK(a->guard == nullptr || a->guard->flag != nullptr, "%s: the guard has no flag", who);
+    plan->flag = a->guard != nullptr ? a->guard->flag : nullptr;
     const int n = a->n;
     // the host table must be what lnx_muon_layout gives for its shapes: every offset and tile range the kernels follow is checked here
     std::vector<int> shapes(2 * (size_t)n);
@@ -290,9 +381,9 @@ extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
         shapes[2 * i + 1] = a->mats[i].cols;
     }
     std::vector<lnx_muon_mat> ref((size_t)n);
-    lnx_muon_info info;
+    lnx_muon_info& info = plan->info;
     if (int rc = layout(shapes.data(), n, ref.data(), nullptr, 0, &info)) return rc;
-    LNX_CHECK(info.workspace_bytes <= a->workspace_bytes, "lnx_muon_step: the layout needs %lld workspace bytes, %lld given", (long long)info.workspace_bytes,
+    LNX_CHECK(info.workspace_bytes <= a->workspace_bytes, "%s: the layout needs %lld workspace bytes, %lld given", who, (long long)info.workspace_bytes,
               (long long)a->workspace_bytes);
     int max_steps = 0;
     for (int i = 0; i < n; ++i) {
@@ -300,20 +391,27 @@ extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
         bool same = m.mp == r.mp && m.np == r.np && m.x_off == r.x_off && m.xt_off[0] == r.xt_off[0] && m.xt_off[1] == r.xt_off[1] && m.a_off == r.a_off &&
                     m.b_off == r.b_off && m.block_start == r.block_start;
         for (int s = 0; s < 3; ++s) same = same && m.tile_start[s] == r.tile_start[s] && m.tile_count[s] == r.tile_count[s];
-        LNX_CHECK(same, "lnx_muon_step: the table entry of matrix %d does not match the layout of its shape [%d, %d]", i, m.rows, m.cols);
-        LNX_CHECK(m.ns_steps >= 0, "lnx_muon_step: ns_steps=%d of matrix %d", m.ns_steps, i);
-        LNX_CHECK(m.p != nullptr, "lnx_muon_step: matrix %d has no parameter pointer", i);
-        LNX_CHECK(m.g == nullptr || m.buf != nullptr, "lnx_muon_step: matrix %d has a gradient but no momentum buffer", i);
+        LNX_CHECK(same, "%s: the table entry of matrix %d does not match the layout of its shape [%d, %d]", who, i, m.rows, m.cols);
+        LNX_CHECK(m.ns_steps >= 0, "%s: ns_steps=%d of matrix %d", who, m.ns_steps, i);
+        LNX_CHECK(m.p != nullptr, "%s: matrix %d has no parameter pointer", who, i);
+        LNX_CHECK(m.g == nullptr || m.buf != nullptr, "%s: matrix %d has a gradient but no momentum buffer", who, i);
         if (m.ns_steps > max_steps) max_steps = m.ns_steps;
     }
-    hipStream_t st = (hipStream_t)stream;
+    plan->max_steps = max_steps;
+    return 0;
+}
+
+void launch_front(const lnx_muon_step_args* a, const StepPlan& plan, hipStream_t st) {
+    const int n = a->n;
+    const lnx_muon_info& info = plan.info;
+    const float* flag = plan.flag;
     char* ws = static_cast<char*>(a->workspace);
     const lnx_muon_tile* tb[3] = {a->tiles_dev, a->tiles_dev + info.ntiles[0], a->tiles_dev + info.ntiles[0] + info.ntiles[1]};
     hipLaunchKernelGGL(muon_momentum_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, ws, a->partials, a->sumsq, a->max_norm, flag,
                        a->guard != nullptr ? a->guard->grad_scale : nullptr);
     hipLaunchKernelGGL(muon_normalise_kernel, dim3(cdiv(info.ntiles[2], 4)), dim3(256), 0, st, a->mats_dev, tb[2], (int)info.ntiles[2], ws, (const float*)a->partials, flag);
     g_launches += 2;
-    for (int it = 0; it < max_steps; ++it) {
+    for (int it = 0; it < plan.max_steps; ++it) {
         // the prefix of each table that still holds a matrix with an iteration left (matrices in descending ns_steps: the others drop out)
         int nt[3] = {0, 0, 0};
         for (int i = 0; i < n; ++i)
@@ -324,7 +422,129 @@ extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
         hipLaunchKernelGGL(muon_ns_kernel<2>, dim3(cdiv(nt[2], 4)), dim3(256), 0, st, a->mats_dev, tb[2], nt[2], it, ws, flag);
         g_launches += 3;
     }
-    hipLaunchKernelGGL(muon_apply_kernel, dim3(info.total_blocks), dim3(256), 0, st, a->mats_dev, n, (const char*)ws, flag);
+}
+
+// [off, off + len) of every region with off >= 0: pairwise disjoint?  On overlap, *a and *b name the two entries.
+bool regions_disjoint(const std::vector<std::pair<int64_t, int64_t>>& regions, const std::vector<int>& ids, int* a, int* b) {
+    std::vector<size_t> idx(regions.size());
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
+    std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return regions[x].first != regions[y].first ? regions[x].first < regions[y].first : x < y; });
+    for (size_t k = 1; k < idx.size(); ++k)
+        if (regions[idx[k - 1]].first + regions[idx[k - 1]].second > regions[idx[k]].first) {
+            *a = ids[idx[k - 1]];
+            *b = ids[idx[k]];
+            return false;
+        }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int lnx_muon_step(const lnx_muon_step_args* a, void* stream) {
+    StepPlan plan;
+    if (int rc = check_step(a, "lnx_muon_step", &plan)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    launch_front(a, plan, st);
+    hipLaunchKernelGGL(muon_apply_kernel, dim3(plan.info.total_blocks), dim3(256), 0, st, a->mats_dev, a->n, (const char*)a->workspace, plan.flag);
+    g_launches += 1;
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_muon_partition(const int* shapes, const int* ns_steps, int n, int world, int* owner, int64_t* elem_off, int64_t* seg_elems, int64_t* rank_cost) {
+    LNX_CHECK(shapes && ns_steps && owner && elem_off && seg_elems && rank_cost && n > 0,
+              "lnx_muon_partition: bad arguments (shapes, ns_steps, owner, elem_off, seg_elems and rank_cost must be given, n > 0)");
+    LNX_CHECK(world >= 1, "lnx_muon_partition: world=%d, at least one rank is needed", world);
+    std::vector<lnx_muon_mat> mats((size_t)n);
+    lnx_muon_info info;
+    if (int rc = layout(shapes, n, mats.data(), nullptr, 0, &info)) return rc;
+    std::vector<int64_t> cost((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        LNX_CHECK(ns_steps[i] >= 0 && ns_steps[i] <= 1024, "lnx_muon_partition: ns_steps=%d of matrix %d", ns_steps[i], i);
+        const int64_t mp = mats[i].mp, np = mats[i].np;  // mp np < 2^31 and mp <= np (lnx_muon_layout): the cost stays far below 2^63
+        cost[i] = ns_steps[i] > 0 ? (int64_t)ns_steps[i] * (4 * mp * mp * np + 2 * mp * mp * mp) : mp * np;
+        LNX_CHECK(cost[i] < ((int64_t)1 << 56), "lnx_muon_partition: matrix %d [%d, %d] is too costly to count", i, shapes[2 * i], shapes[2 * i + 1]);
+    }
+    std::vector<int> by_cost((size_t)n);
+    for (int i = 0; i < n; ++i) by_cost[i] = i;
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](int x, int y) { return cost[x] > cost[y]; });  // stable: equal costs by ascending index
+    for (int r = 0; r < world; ++r) rank_cost[r] = 0;
+    for (int i : by_cost) {
+        int best = 0;
+        for (int r = 1; r < world; ++r)
+            if (rank_cost[r] < rank_cost[best]) best = r;  // strict: the lowest rank on ties
+        owner[i] = best;
+        rank_cost[best] += cost[i];
+    }
+    std::vector<int64_t> fill((size_t)world, 0);
+    int64_t largest = 0;
+    for (int i = 0; i < n; ++i) {  // table order inside a segment
+        int64_t& f = fill[owner[i]];
+        elem_off[i] = f;
+        f += ((int64_t)shapes[2 * i] * shapes[2 * i + 1] + LNX_MUON_SEG_ALIGN - 1) / LNX_MUON_SEG_ALIGN * LNX_MUON_SEG_ALIGN;
+        if (f > largest) largest = f;
+    }
+    *seg_elems = largest;
+    return 0;
+}
+
+extern "C" int lnx_muon_orthogonalize(const lnx_muon_step_args* a, const int64_t* out_off_host, const int64_t* out_off_dev, void* seg, int64_t seg_elems,
+                                      void* stream) {
+    StepPlan plan;
+    if (int rc = check_step(a, "lnx_muon_orthogonalize", &plan)) return rc;
+    LNX_CHECK(out_off_host != nullptr && out_off_dev != nullptr, "lnx_muon_orthogonalize: the offset table is NULL (host and device copies must be given)");
+    LNX_CHECK(seg != nullptr && seg_elems > 0, "lnx_muon_orthogonalize: no segment (seg=%p, seg_elems=%lld)", seg, (long long)seg_elems);
+    LNX_CHECK((reinterpret_cast<uintptr_t>(seg) & 255) == 0, "lnx_muon_orthogonalize: the segment must be 256-byte aligned");
+    std::vector<std::pair<int64_t, int64_t>> regions;
+    std::vector<int> ids;
+    for (int i = 0; i < a->n; ++i) {
+        const int64_t off = out_off_host[i], numel = (int64_t)a->mats[i].rows * a->mats[i].cols;
+        LNX_CHECK(off >= 0 && off <= seg_elems && numel <= seg_elems - off, "lnx_muon_orthogonalize: matrix %d at offset %lld with %lld elements lies outside the segment of %lld",
+                  i, (long long)off, (long long)numel, (long long)seg_elems);
+        LNX_CHECK(off % LNX_MUON_SEG_ALIGN == 0, "lnx_muon_orthogonalize: offset %lld of matrix %d is not a multiple of %d elements", (long long)off, i, LNX_MUON_SEG_ALIGN);
+        regions.emplace_back(off, numel);
+        ids.push_back(i);
+    }
+    int x = 0, y = 0;
+    LNX_CHECK(regions_disjoint(regions, ids, &x, &y), "lnx_muon_orthogonalize: the regions of matrices %d and %d overlap", x, y);
+    hipStream_t st = (hipStream_t)stream;
+    launch_front(a, plan, st);
+    hipLaunchKernelGGL(muon_pack_kernel, dim3(plan.info.total_blocks), dim3(256), 0, st, a->mats_dev, a->n, (const char*)a->workspace, out_off_dev,
+                       static_cast<bf16_t*>(seg), plan.flag);
+    g_launches += 1;
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_muon_apply_packed(const lnx_muon_packed* t, const lnx_muon_packed* table_dev, int n, const void* gathered, int64_t seg_elems, int world,
+                                     const lnx_step_guard* guard, void* stream) {
+    LNX_CHECK(t != nullptr && table_dev != nullptr && n > 0, "lnx_muon_apply_packed: the table is NULL or empty (host and device copies must be given, n > 0)");
+    LNX_CHECK(world >= 1, "lnx_muon_apply_packed: world=%d, at least one rank is needed", world);
+    LNX_CHECK(gathered != nullptr && seg_elems > 0 && seg_elems % LNX_MUON_SEG_ALIGN == 0 && seg_elems <= (((int64_t)1 << 56) / world),
+              "lnx_muon_apply_packed: no gathered buffer, or seg_elems=%lld is not a positive multiple of %d", (long long)seg_elems, LNX_MUON_SEG_ALIGN);
+    LNX_CHECK((reinterpret_cast<uintptr_t>(gathered) & 255) == 0, "lnx_muon_apply_packed: the gathered buffer must be 256-byte aligned");
+    LNX_CHECK(guard == nullptr || guard->flag != nullptr, "lnx_muon_apply_packed: the guard has no flag");
+    const int64_t total = seg_elems * world;
+    std::vector<std::pair<int64_t, int64_t>> regions;
+    std::vector<int> ids;
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const lnx_muon_packed& d = t[i];
+        LNX_CHECK(d.numel > 0, "lnx_muon_apply_packed: entry %d has %lld elements", i, (long long)d.numel);
+        LNX_CHECK(d.block_start == blocks, "lnx_muon_apply_packed: block_start=%d of entry %d, %lld workgroups lie in front of it", d.block_start, i, (long long)blocks);
+        blocks += (d.numel + ELEMS - 1) / ELEMS;
+        LNX_CHECK(blocks < ((int64_t)1 << 30), "lnx_muon_apply_packed: too many workgroups at entry %d", i);
+        if (d.off < 0) continue;
+        LNX_CHECK(d.p != nullptr, "lnx_muon_apply_packed: entry %d has no parameter pointer", i);
+        LNX_CHECK(d.off <= total && d.numel <= total - d.off, "lnx_muon_apply_packed: entry %d at offset %lld with %lld elements lies outside the gathered buffer of %lld",
+                  i, (long long)d.off, (long long)d.numel, (long long)total);
+        regions.emplace_back(d.off, d.numel);
+        ids.push_back(i);
+    }
+    int x = 0, y = 0;
+    LNX_CHECK(regions_disjoint(regions, ids, &x, &y), "lnx_muon_apply_packed: the regions of entries %d and %d overlap", x, y);
+    hipLaunchKernelGGL(muon_apply_packed_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, table_dev, n, static_cast<const bf16_t*>(gathered),
+                       guard != nullptr ? guard->flag : nullptr);
     g_launches += 1;
     LNX_LAUNCH_CHECK();
     return 0;

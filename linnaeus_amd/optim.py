@@ -10,7 +10,8 @@ builder (optimizers/build.py) work unchanged.  GPU fp32 parameters only.
 
 `FusedAdEMAMix` is the same machinery for the reference's AdEMAMix (optimizers/ademamix.py): one launch per step over the
 same descriptor table plus a parallel table of slow-EMA pointers, three with the clip.  `FusedSGD` is torch.optim.SGD the same way,
-`FusedMuon` the reference's Muon in a fixed number of launches.
+`FusedMuon` the reference's Muon in a fixed number of launches, `ShardedFusedMuon` the same step with the matrices shared out over the
+data-parallel ranks and the bf16 updates all-gathered (the reference's DistributedMuon), bit for bit.
 
 `build_optimizer(config, model)` is the reference's optimizers/build.py with these classes, and `FusedMultiOptimizer` its
 MultiOptimizer with the clip block of train.py:279-313 inside `step()`: one norm pass over every gradient of the run, the clip
@@ -563,26 +564,39 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
         """bytes of the bf16 workspace of the last step's layout (0 before the first step)"""
         return 0 if self._dev is None else int(self._dev[4].workspace_bytes)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = _closure_loss(closure)
+    def _launch_order(self):
+        """[(group index, p)] of every parameter by descending ns_steps (stable: ties keep the parameter order), and those with a gradient,
+        validated; ([], []) when no parameter has a gradient: nothing to do this step"""
         order = [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"]]
-        if not order:
-            return loss
-        for gi, g in enumerate(self.param_groups):
+        for g in self.param_groups:
             if int(g["ns_steps"]) != g["ns_steps"] or g["ns_steps"] < 0:
                 raise ValueError(f"Invalid ns_steps value: {g['ns_steps']}")
-        order.sort(key=lambda it: -int(self.param_groups[it[0]]["ns_steps"]))  # stable: ties keep the parameter order
+        order.sort(key=lambda it: -int(self.param_groups[it[0]]["ns_steps"]))
         with_grad = [p for _, p in order if p.grad is not None]
         if not with_grad:
-            return loss
+            return [], []
         dev = with_grad[0].device
         for p in with_grad:  # a parameter without a gradient is not touched this step
             if not (p.is_cuda and _dense_fp32(p, dev)):
                 raise L.LnxError("FusedMuon needs contiguous fp32 parameters on one GPU")
             if not _dense_fp32(p.grad, dev, p.shape):
                 raise L.LnxError("FusedMuon needs contiguous fp32 gradients on the parameters' GPU")
-        key = tuple((id(p), tuple(p.shape), int(self.param_groups[gi]["ns_steps"])) for gi, p in order)
+        return order, with_grad
+
+    def _order_key(self, order):
+        return tuple((id(p), tuple(p.shape), int(self.param_groups[gi]["ns_steps"])) for gi, p in order)
+
+    def _step_scalars(self, gi, p):
+        """(decay, step) of lnx_muon_mat for parameter p of group gi: double on the host, rounded once by the struct"""
+        g = self.param_groups[gi]
+        rows, cols = _muon_shape(p)
+        lr = float(g["lr"])
+        return 1 - lr * float(g["weight_decay"]), lr * max(1, rows / cols) ** 0.5
+
+    def _step_args(self, order, dev):
+        """lnx_muon_step_args (without the clip and the guard) over `order`, matrices by descending ns_steps: the layout rebuilt when a
+        shape or ns_steps changed, the table refilled and copied to the device when its bytes changed, momentum buffers created on first use"""
+        key = self._order_key(order)
         if key != self._key:
             self._build(order, dev)
             self._key, self._order = key, order
@@ -600,11 +614,10 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
                 if not _dense_fp32(buf, dev, p.shape):
                     raise L.LnxError("FusedMuon: state 'momentum_buffer' must be a contiguous fp32 tensor of the parameter's shape on its device")
                 m.g, m.buf = p.grad.data_ptr(), buf.data_ptr()
-            rows, cols = _muon_shape(p)
-            lr, mom = float(g["lr"]), float(g["momentum"])
+            mom = float(g["momentum"])
             m.ns_steps, m.nesterov = int(g["ns_steps"]), 1 if g["nesterov"] else 0
             m.momentum, m.omm = mom, 1 - mom
-            m.decay, m.step = 1 - lr * float(g["weight_decay"]), lr * max(1, rows / cols) ** 0.5
+            m.decay, m.step = self._step_scalars(gi, p)
         table, tiles, ws, part, info = self._dev
         raw = bytes(mats)
         if raw != self._sent:  # gradient pointers and learning rates usually move between steps; the layout does not
@@ -613,11 +626,246 @@ class FusedMuon(_SharedClip, torch.optim.Optimizer):
         a = L.MuonStepArgs()
         a.n, a.mats, a.mats_dev, a.tiles_dev = len(order), C.addressof(mats), table.data_ptr(), tiles.data_ptr()
         a.workspace, a.workspace_bytes, a.partials = ws.data_ptr(), ws.numel(), part.data_ptr()
+        return a
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = _closure_loss(closure)
+        order, with_grad = self._launch_order()
+        if not with_grad:
+            return loss
+        dev = with_grad[0].device
+        a = self._step_args(order, dev)
         a.sumsq, a.max_norm, guard = self._clip(dev, lambda guard: self._norm.over_grads(with_grad, guard))
         if guard is not None:  # every launch of the step obeys its flag: the workspace's zero padding survives a skipped step
             a.guard = C.pointer(guard)
         L.check(L.lib().lnx_muon_step(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_muon_step")
         return loss
+
+
+def muon_partition(shapes, ns_steps, world):
+    """lnx_muon_partition (host only, no GPU) of n logical [rows, cols] shapes with their ns_steps over `world` ranks: (owner per matrix,
+    offset per matrix in bf16 elements inside its owner's segment, seg_elems, cost per rank).  Longest-processing-time greedy over the
+    MFMA FLOPs of the Newton-Schulz products; a pure function of its inputs, so every rank computes the same table."""
+    n = len(shapes)
+    flat = (C.c_int * (2 * max(n, 1)))(*(int(v) for s in shapes for v in s))
+    ns = (C.c_int * max(n, 1))(*(int(v) for v in ns_steps))
+    owner, off = (C.c_int * max(n, 1))(), (C.c_int64 * max(n, 1))()
+    cost, seg = (C.c_int64 * max(int(world), 1))(), C.c_int64()
+    L.check(L.lib().lnx_muon_partition(flat, ns, n, int(world), owner, off, C.byref(seg), cost), "lnx_muon_partition")
+    return list(owner[:n]), list(off[:n]), int(seg.value), list(cost[:int(world)])
+
+
+class _Done:
+    """the work handle of a collective that has nothing to wait for"""
+
+    def wait(self):
+        return True
+
+
+class ShardedFusedMuon(FusedMuon):
+    """`FusedMuon` with the step split over data-parallel ranks (the reference's DistributedMuon, muon.py:200-428): every rank holds the same
+    all-reduced gradients, runs momentum and Newton-Schulz only for the matrices it owns, and the ranks all-gather the bf16 updates.
+    Each matrix gives the same bits alone or in a set, so the parameters are those of `FusedMuon`, bit for bit, on every rank.
+
+      begin_step()   the owned table (`muon_partition` over the shapes and ns_steps of ALL parameters of ALL groups, with or without a
+                     gradient, by descending ns_steps), lnx_muon_orthogonalize into this rank's segment of a persistent
+                     [world * seg_elems] bf16 buffer (3 * max(ns_steps) + 3 launches; none on a rank that owns nothing), then the gather
+      finish_step()  waits for the gather; lnx_muon_apply_packed updates ALL matrices from the gathered buffer in one launch
+      step()         both in turn.  `FusedMultiOptimizer.step` puts the other sub-optimizers' launches between the two.
+
+    process_group / rank / world_size: rank and world size default to the process group's (the default group when None).
+    gather(out, seg): a seam that replaces the collective (tests, the benchmark): `seg` is this rank's part of `out`, a view into it; it
+    returns a work handle (`.wait()`) or None.  The default is `dist.all_gather_into_tensor(out, seg, group, async_op=True)`, or
+    `dist.all_gather` over `world` views of `out` where the backend refuses that call; at world size 1 nothing is gathered.
+
+    `max_grad_norm`, `use_shared_clip` and `nonfinite_guard` work as on `FusedMuon`: the norm pass runs over the gradients of ALL
+    parameters, in FusedMuon's order, so every rank forms the same coefficient and the same flag.
+    `momentum_buffer` exists only for owned parameters: `state_dict()` is the local shard, `full_state_dict()` a collective that
+    returns what `FusedMuon.state_dict()` would, and `load_state_dict` takes either and keeps the owned part.  The bf16 workspace
+    and the fp32 momentum are this rank's share."""
+
+    def __init__(self, params, lr=0.02, weight_decay=0.01, momentum=0.95, nesterov=True, ns_steps=5, strict=False, max_grad_norm: Optional[float] = None,
+                 nonfinite_guard: bool = False, process_group=None, rank=None, world_size=None, gather=None):
+        super().__init__(params, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, ns_steps=ns_steps, strict=strict,
+                         max_grad_norm=max_grad_norm, nonfinite_guard=nonfinite_guard)
+        if rank is None or world_size is None:
+            import torch.distributed as dist
+
+            if not (dist.is_available() and dist.is_initialized()):
+                raise ValueError("ShardedFusedMuon: torch.distributed is not initialised; give rank and world_size (and a gather seam) or a process group")
+            rank = dist.get_rank(process_group) if rank is None else rank
+            world_size = dist.get_world_size(process_group) if world_size is None else world_size
+        if int(world_size) < 1 or not 0 <= int(rank) < int(world_size):
+            raise ValueError(f"ShardedFusedMuon: rank {rank} of world size {world_size}")
+        self.process_group, self.rank, self.world_size, self._gather_seam = process_group, int(rank), int(world_size), gather
+        self._part_key = None  # what the partition was computed for
+        self._part = None      # (owner, elem_off, seg_elems, cost) in launch order
+        self._gathered = None  # bf16 [world * seg_elems]: the ranks' segments, persistent
+        self._out_off = None   # (host int64 array, device tensor) of the owned matrices' offsets in this rank's segment
+        self._packed = None    # (host lnx_muon_packed table, device copy, bytes last sent)
+        self._pending = None   # between begin_step and finish_step: (launch order, device, guard, work handle)
+        self.collective = None  # which torch.distributed call the last default gather made
+
+    # ------------------------------------------------------------------ partition
+    def _all_order(self):
+        order = [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"]]
+        order.sort(key=lambda it: -int(self.param_groups[it[0]]["ns_steps"]))
+        return order
+
+    def _partition(self, order=None):
+        order = self._all_order() if order is None else order
+        key = self._order_key(order)
+        if key != self._part_key:
+            self._part = muon_partition([_muon_shape(p) for _, p in order], [int(self.param_groups[gi]["ns_steps"]) for gi, _ in order], self.world_size)
+            self._part_key = key
+            self._gathered = self._out_off = self._packed = None
+        return self._part
+
+    def owns(self, p) -> bool:
+        order = self._all_order()
+        owner = self._partition(order)[0]
+        return any(q is p and owner[i] == self.rank for i, (_, q) in enumerate(order))
+
+    def partition_report(self) -> dict:
+        """host only: owner of every parameter (param_groups order), cost per rank (Newton-Schulz MFMA FLOPs), their max / mean, seg_elems, and
+        the bytes of this rank's workspace and of the gathered buffer"""
+        order = self._all_order()
+        owner, _, seg, cost = self._partition(order)
+        by_id = {id(p): owner[i] for i, (_, p) in enumerate(order)}
+        mine = [_muon_shape(p) for i, (_, p) in enumerate(order) if owner[i] == self.rank]
+        mean = sum(cost) / len(cost)
+        return {"rank": self.rank, "world_size": self.world_size, "owner": [by_id[id(p)] for g in self.param_groups for p in g["params"]], "cost": cost,
+                "max_over_mean": max(cost) / mean if mean > 0 else 1.0, "seg_elems": seg,
+                "workspace_bytes": int(muon_layout(mine)[2].workspace_bytes) if mine else 0, "gathered_bytes": 2 * seg * self.world_size}
+
+    # ------------------------------------------------------------------ step
+    def _gather(self, out, seg):
+        if self._gather_seam is not None:
+            return self._gather_seam(out, seg)
+        if self.world_size == 1:
+            return None  # the segment is the buffer
+        import torch.distributed as dist
+
+        try:
+            work = dist.all_gather_into_tensor(out, seg, group=self.process_group, async_op=True)
+            self.collective = "all_gather_into_tensor"
+        except (RuntimeError, NotImplementedError):  # a backend without that call for these tensors: the list form over views of `out`
+            work = dist.all_gather(list(out.view(self.world_size, -1).unbind(0)), seg, group=self.process_group, async_op=True)
+            self.collective = "all_gather"
+        return work
+
+    @torch.no_grad()
+    def begin_step(self):
+        if self._pending is not None:
+            raise L.LnxError("ShardedFusedMuon: begin_step twice without finish_step")
+        order, with_grad = self._launch_order()
+        if not with_grad:
+            return
+        dev = with_grad[0].device
+        owner, elem_off, seg_elems, _ = self._partition(order)
+        if self._gathered is None or self._gathered.device != dev:
+            self._gathered = torch.zeros(self.world_size * seg_elems, device=dev, dtype=torch.bfloat16)
+        mine = [i for i in range(len(order)) if owner[i] == self.rank]
+        sumsq, max_norm, guard = self._clip(dev, lambda guard: self._norm.over_grads(with_grad, guard))  # over ALL gradients: the same on every rank
+        seg = self._gathered[self.rank * seg_elems:(self.rank + 1) * seg_elems]
+        if mine:
+            a = self._step_args([order[i] for i in mine], dev)
+            a.sumsq, a.max_norm = sumsq, max_norm
+            if guard is not None:
+                a.guard = C.pointer(guard)
+            off = np.asarray([elem_off[i] for i in mine], dtype=np.int64)
+            if self._out_off is None or not np.array_equal(self._out_off[0], off) or self._out_off[1].device != dev:
+                self._out_off = (off, torch.from_numpy(off).to(dev))
+            L.check(L.lib().lnx_muon_orthogonalize(C.byref(a), C.c_void_p(self._out_off[0].ctypes.data), C.c_void_p(self._out_off[1].data_ptr()),
+                                                   C.c_void_p(seg.data_ptr()), seg_elems, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                    "lnx_muon_orthogonalize")
+        self._pending = (order, dev, guard, self._gather(self._gathered, seg))
+
+    @torch.no_grad()
+    def finish_step(self):
+        if self._pending is None:
+            return  # begin_step found no gradient
+        order, dev, guard, work = self._pending
+        self._pending = None
+        if work is not None:
+            work.wait()
+        owner, elem_off, seg_elems, _ = self._part
+        n = len(order)
+        if self._packed is None or len(self._packed[0]) != n or self._packed[1].device != dev:
+            table = (L.MuonPacked * n)()
+            self._packed = [table, torch.empty(C.sizeof(table), device=dev, dtype=torch.uint8), None]
+        table = self._packed[0]
+        blk = 0
+        for i, (gi, p) in enumerate(order):
+            d = table[i]
+            d.p, d.numel, d.block_start = p.data_ptr(), p.numel(), blk
+            d.off = -1 if p.grad is None else owner[i] * seg_elems + elem_off[i]
+            d.decay, d.step = self._step_scalars(gi, p)
+            blk += -(-p.numel() // L.MUON_ELEMS)
+        raw = bytes(table)
+        if raw != self._packed[2]:
+            self._packed[1].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+            self._packed[2] = raw
+        L.check(L.lib().lnx_muon_apply_packed(C.addressof(table), C.c_void_p(self._packed[1].data_ptr()), n, C.c_void_p(self._gathered.data_ptr()), seg_elems,
+                                              self.world_size, None if guard is None else C.pointer(guard), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                "lnx_muon_apply_packed")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = _closure_loss(closure)
+        self.begin_step()
+        self.finish_step()
+        return loss
+
+    # ------------------------------------------------------------------ state
+    def _state_segment(self):
+        """this rank's part of the buffer `full_state_dict` gathers, fp32 [n + seg_elems]: one flag per matrix in launch order (1: owned here
+        and holding a momentum buffer), then the owned momentum buffers at their segment offsets"""
+        order = self._all_order()
+        owner, elem_off, seg_elems, _ = self._partition(order)
+        dev = next((self.state[p]["momentum_buffer"].device for _, p in order if "momentum_buffer" in self.state.get(p, {})), order[0][1].device)
+        seg = torch.zeros(len(order) + seg_elems, device=dev, dtype=torch.float32)
+        for i, (_, p) in enumerate(order):
+            buf = self.state.get(p, {}).get("momentum_buffer") if owner[i] == self.rank else None
+            if buf is not None:
+                seg[i] = 1.0
+                seg[len(order) + elem_off[i]:len(order) + elem_off[i] + p.numel()].copy_(buf.reshape(-1))
+        return seg
+
+    @torch.no_grad()
+    def full_state_dict(self) -> dict:
+        """A COLLECTIVE (every rank calls it): the state dict `FusedMuon` would write, with every momentum buffer, on every rank."""
+        order = self._all_order()
+        owner, elem_off, seg_elems, _ = self._partition(order)
+        n, width = len(order), len(order) + seg_elems
+        mine = self._state_segment()
+        out = torch.empty(self.world_size * width, device=mine.device, dtype=torch.float32)
+        seg = out[self.rank * width:(self.rank + 1) * width]
+        seg.copy_(mine)
+        work = self._gather(out, seg)
+        if work is not None:
+            work.wait()
+        rows = out.view(self.world_size, width)
+        flags = rows[:, :n].cpu()
+        sd = super().state_dict()
+        index = {id(p): k for k, p in enumerate(p for g in self.param_groups for p in g["params"])}  # torch packs the parameters 0, 1, ... in group order
+        state = {}
+        for i, (_, p) in enumerate(order):
+            if flags[owner[i], i] != 0:
+                lo = n + elem_off[i]
+                state[index[id(p)]] = {"momentum_buffer": rows[owner[i], lo:lo + p.numel()].reshape(p.shape).clone()}
+        sd["state"] = {k: state[k] for k in sorted(state)}
+        return sd
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        """takes the local shard or a full state dict (FusedMuon's, Muon's, the reference's) and keeps the owned part"""
+        super().load_state_dict(state_dict)
+        order = self._all_order()
+        owner = self._partition(order)[0]
+        for i, (_, p) in enumerate(order):
+            if owner[i] != self.rank:
+                self.state.pop(p, None)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -688,7 +936,7 @@ class FusedSGD(_ElementwiseOptimizer):
 # ----------------------------------------------------------------------------------------------------------------------
 # The configured optimizer (optimizers/build.py + optimizers/multi_optimizer.py + the clip block of train.py:279-313)
 # ----------------------------------------------------------------------------------------------------------------------
-FUSED_OPTIMIZERS = (FusedAdamW, FusedAdEMAMix, FusedSGD, FusedMuon)
+FUSED_OPTIMIZERS = (FusedAdamW, FusedAdEMAMix, FusedSGD, FusedMuon)  # (ShardedFusedMuon is a FusedMuon)
 
 
 class FusedMultiOptimizer(_Clipped):
@@ -758,8 +1006,15 @@ class FusedMultiOptimizer(_Clipped):
                 self._norm.over_grads(with_grad, guard)  # the union table
                 for opt in self.optimizers.values():
                     opt.use_shared_clip(self._norm.sumsq[:1], self.max_grad_norm, guard)
+        # a sharded sub-optimizer's gather runs under the other sub-optimizers' launches: begin (orthogonalise, issue the gather), the others, finish
+        sharded = [opt for opt in self.optimizers.values() if isinstance(opt, ShardedFusedMuon)]
+        for opt in sharded:
+            opt.begin_step()
         for opt in self.optimizers.values():
-            opt.step()
+            if not isinstance(opt, ShardedFusedMuon):
+                opt.step()
+        for opt in sharded:
+            opt.finish_step()
         return loss
 
     def grad_norms(self):
@@ -896,7 +1151,11 @@ def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_refere
     momentum, wd_default = float(_cfg(O, "MOMENTUM", 0.9)), float(_cfg(O, "WEIGHT_DECAY", 0.05))
     alpha, t_ab3 = float(_cfg(O, "ALPHA", 5.0)), _cfg(O, "T_ALPHA_BETA3", None)
     muon_kw = dict(momentum=float(_cfg(O, "MUON.MOMENTUM", 0.95)), nesterov=bool(_cfg(O, "MUON.NESTEROV", True)), ns_steps=int(_cfg(O, "MUON.NS_STEPS", 5)),
-                   strict=bool(_cfg(O, "MUON.STRICT", False)))  # MUON.USE_DISTRIBUTED: FusedMuon all the same (sharding is out of scope)
+                   strict=bool(_cfg(O, "MUON.STRICT", False)))
+    # MUON.USE_DISTRIBUTED (the reference's DistributedMuon): the sharded step, but only where there is something to share the work with
+    import torch.distributed as dist
+
+    shard_muon = bool(_cfg(O, "MUON.USE_DISTRIBUTED", False)) and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 
     def make(kind, params, lr, wd, own_clip=None, own_guard=False):
         own = dict(max_grad_norm=own_clip, nonfinite_guard=own_guard)
@@ -907,7 +1166,7 @@ def build_optimizer(config, model, max_grad_norm="config", freeze_4d_like_refere
         if kind == "ademamix":
             return FusedAdEMAMix(params, lr=lr, betas=betas, eps=eps, weight_decay=wd, alpha=alpha, T_alpha_beta3=t_ab3, **own)
         if kind == "muon":
-            return FusedMuon(params, lr=lr, weight_decay=wd, **own, **muon_kw)
+            return (ShardedFusedMuon if shard_muon else FusedMuon)(params, lr=lr, weight_decay=wd, **own, **muon_kw)
         raise ValueError(f"Unknown optimizer: {kind}")
 
     def muon_split(params):
