@@ -615,6 +615,16 @@ int64_t lnx_drop_compact_branches(void);
  * RoPE blocks compact (read by every lnx_plan_forward).  lnx_drop_compact_conv_blocks(): conv blocks that ran a forward on compact
  * rows since the library was loaded; lnx_drop_compact_branches() keeps counting RoPE branches only. */
 int64_t lnx_drop_compact_conv_blocks(void);
+/* A/B switch of the CLS-only last RoPE block inside lnx_plan_forward / lnx_plan_backward, process-wide: on = 0 / 1, or -1 = back to the
+ * environment (LNX_LAST_CLS, on unless it is 0).  Returns the previous setting (-1, 0 or 1).  norm_2 reads only the CLS row of the
+ * stage-4 output (mFormerV1.py:509-527), so the last stage-4 block runs LayerNorm 1, qkv and attention on all rows and proj, LayerNorm 2,
+ * fc1 and fc2 -- forward, data and weight gradients -- on the batch's CLS rows alone; the other rows of that block's xmid and output are
+ * never written.  Same arithmetic on fewer rows: logits, loss and gradients are what the full block gives up to summation order and the
+ * kernel family a product of M = batch rows dispatches to.  Read by every lnx_plan_forward; a backward follows its forward's choice.
+ * fp8 plans and plans with dropout masks keep the full block.  lnx_last_cls_blocks(): block forwards that took the path since the
+ * library was loaded. */
+int lnx_set_last_cls(int on);
+int64_t lnx_last_cls_blocks(void);
 
 /* LayerScale+DropPath backward of a ConvNeXt block branch (blocks/convnext.py:82-86):
  * dz = rowscale * gamma * g  (T),  dgamma[c] += sum_m rowscale * g * z */

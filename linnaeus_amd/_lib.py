@@ -388,6 +388,9 @@ def lib() -> C.CDLL:
                 _lib.lnx_dwconv7_wgrad_kept.argtypes = [C.POINTER(DwconvWgradArgs), C.c_void_p, C.c_void_p, C.c_void_p]
             _lib.lnx_scale_cast_compact.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                                     C.c_void_p]
+        if hasattr(_lib, "lnx_last_cls_blocks"):
+            _lib.lnx_set_last_cls.argtypes = [C.c_int]
+            _lib.lnx_last_cls_blocks.restype = C.c_int64
         if hasattr(_lib, "lnx_plan_set_trainable"):
             _lib.lnx_plan_unit_name.argtypes = [C.c_void_p, C.c_int]
             _lib.lnx_plan_unit_name.restype = C.c_char_p
@@ -441,7 +444,7 @@ EXPORTS = [
     "lnx_layernorm_fwd", "lnx_layernorm_bwd", "lnx_layernorm_bwd_flush", "lnx_layernorm_bwd_discard", "lnx_layernorm_fwd_query", "lnx_layernorm_bwd_query",
     "lnx_dwconv7_fwd", "lnx_dwconv7_fwd_kept", "lnx_dwconv7_wgrad", "lnx_dwconv7_wgrad_kept", "lnx_dwconv7_wgrad_ws_floats",
     "lnx_gemm_nt_group_ok", "lnx_gemm_nt_group", "lnx_rope_cos_table", "lnx_rope_cos_table_hd", "lnx_rope_cossin_table_hd", "lnx_rope_cos_tables", "lnx_attn_bwd_ws_floats", "lnx_attn_bwd_ws_floats_hd", "lnx_attn_fwd", "lnx_attn_bwd", "lnx_attn_bwd_sized", "lnx_attn_fwd_compact", "lnx_attn_bwd_compact", "lnx_attn_bwd_flush", "lnx_attn_bwd_discard", "lnx_attn_dispatch", "lnx_last_attn_kernel", "lnx_last_attn_bwd_launches",
-    "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_drop_compact_conv_blocks", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
+    "lnx_im2col_stem", "lnx_scale_cast", "lnx_scale_cast_compact", "lnx_drop_partition", "lnx_copy_dropped_rows", "lnx_set_drop_compact", "lnx_drop_compact_branches", "lnx_drop_compact_conv_blocks", "lnx_set_last_cls", "lnx_last_cls_blocks", "lnx_layerscale_bwd", "lnx_layerscale_bwd_ws", "lnx_layerscale_bwd_ws_floats", "lnx_layerscale_apply_wgrad", "lnx_fill_rows", "lnx_colsum_rows",
     "lnx_agg2_fwd", "lnx_agg2_bwd", "lnx_pack_meta", "lnx_meta_heads_supported", "lnx_meta_heads_fwd", "lnx_meta_heads_bwd", "lnx_meta_heads_bwd_part_floats", "lnx_prep_weights", "lnx_prep_blocks", "lnx_softce", "lnx_softce_multi", "lnx_taxonomy_rows", "lnx_stem_fwd", "lnx_stem_fwd_ok", "lnx_adamw_blocks", "lnx_grad_sumsq", "lnx_adamw_step", "lnx_ademamix_step", "lnx_sgd_step", "lnx_optim_launches", "lnx_grad_sumsq_guarded", "lnx_adamw_step_guarded", "lnx_ademamix_step_guarded", "lnx_sgd_step_guarded", "lnx_muon_layout", "lnx_muon_step", "lnx_muon_launches", "lnx_muon_partition", "lnx_muon_orthogonalize", "lnx_muon_apply_packed", "lnx_gradnorm_sumsq", "lnx_gradnorm_update",
     "lnx_metrics_table_sizes", "lnx_metrics_update", "lnx_predict", "lnx_resize_taps", "lnx_resize_coeffs", "lnx_preprocess_scratch_bytes", "lnx_preprocess", "lnx_hier_loss_fwd", "lnx_hier_loss_bwd",
     "lnx_hier_refine_fwd", "lnx_hier_refine_bwd", "lnx_hier_refine_launches",

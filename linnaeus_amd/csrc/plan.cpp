@@ -212,6 +212,10 @@ struct lnx_plan {
     int* droplists = nullptr;
     bool compact_now = false;
     bool compact_conv_now = false;  // ... and the conv blocks' calls are among them (LNX_DROP_COMPACT_CONV)
+    // CLS-only last block: the last forward ran the last stage-4 block's proj / norm2 / MLP on the B CLS rows only (norm_2 reads
+    // nothing else of the stage output); the backward and a recompute plan's re-forward follow that forward's choice
+    bool last_cls_now = false;
+    bool last_cls(int s, int i) const { return last_cls_now && s == 1 && i + 1 == (int)rope[1].size(); }
     const int* drop_list(int call) const {
         if (!compact_now || droplists == nullptr || drop_ptr(call) == nullptr) return nullptr;
         return droplists + (int64_t)call * LNX_DROP_LIST_INTS(c.batch);
@@ -228,6 +232,11 @@ extern "C" int lnx_set_drop_compact(int on) {
 extern "C" int64_t lnx_drop_compact_branches(void) { return (int64_t)g_compact_branches.load(std::memory_order_relaxed); }
 static std::atomic<long long> g_compact_conv_blocks{0};
 extern "C" int64_t lnx_drop_compact_conv_blocks(void) { return (int64_t)g_compact_conv_blocks.load(std::memory_order_relaxed); }
+// A/B switch of the CLS-only last RoPE block, process-wide: -1 = LNX_LAST_CLS (on unless set to 0), else what lnx_set_last_cls said
+static std::atomic<int> g_last_cls{-1};
+static std::atomic<long long> g_last_cls_blocks{0};
+extern "C" int lnx_set_last_cls(int on) { return g_last_cls.exchange(on < 0 ? -1 : (on ? 1 : 0)); }
+extern "C" int64_t lnx_last_cls_blocks(void) { return (int64_t)g_last_cls_blocks.load(std::memory_order_relaxed); }
 
 namespace {
 
@@ -1513,10 +1522,14 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     const float* xin = c.at<float>(k.xin);
     // DropPath compaction: a branch whose call has a list runs on the kept samples' rows only (compact rows: n1 / qkvbuf / o / lse,
     // n2 / act / hpre and the LayerNorm statistics); the fp32 stream keeps its layout, the dropped samples' rows of xmid / xout are copies
-    const Compact ca = compact_of(p, p->drop_attn[s][i], M, C, N), cm = compact_of(p, p->drop_mlp[s][i], M, C, N);
+    // CLS-only (the last stage-4 block, lnx_plan::last_cls): LayerNorm 1, qkv and attention on all rows (compact under the attention
+    // call's list like any block's); everything behind the attention on the B CLS rows (the MLP call stays off the lists: its M = B
+    // products take the multiplier of the row's own sample)
+    const bool lc = p->last_cls(s, i);
+    const Compact ca = compact_of(p, p->drop_attn[s][i], M, C, N), cm = lc ? Compact() : compact_of(p, p->drop_mlp[s][i], M, C, N);
     g_compact_branches.fetch_add((ca ? 1 : 0) + (cm ? 1 : 0), std::memory_order_relaxed);
     p->resident[2 + s] = i;
-    Timed span(c, 8, rope_block_flops(B, N, C, hid));
+    Timed span(c, 8, rope_block_flops(B, N, C, hid));  // (the nominal count, CLS-only or not: DESIGN 5)
     const bool f8 = fp8_rows(p, M, C);
     void* a8 = f8 ? c.at<void>(p->o_a8) : nullptr;
     void* a8s = f8 ? c.at<void>(p->o_a8s) : nullptr;
@@ -1537,6 +1550,33 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     {
         Timed t(c, 2, 4.0 * B * (double)N * N * C);
         RUN(lnx_attn_fwd_compact(&a, ca.nkeep, c.st));
+    }
+    if (lc) {
+        // Row b of every operand below is the CLS row of sample b: row b N of o / xin / xmid / xout through a leading dimension of N C (no
+        // gather), row b of n2 / act / hpre / mean2 / rstd2.  The other rows of xmid and xout are never written: nobody reads them.
+        // DropPath: the multiplier of the sample itself (rows_per_sample = 1).  With a list for the attention call, o holds compact rows:
+        // row j N is the CLS row of sample perm[j], the product covers the kept samples (the list's nkeep as its row count) and writes
+        // xmid through perm; the dropped samples' CLS rows of xmid are copies of xin's.  The MLP branch has no list: a dropped sample
+        // gets res + 0 . z.
+        const int64_t ldt = (int64_t)N * C;
+        const lnx_rowmap clsrow = {1, N - 1, 0};
+        g_last_cls_blocks.fetch_add(1, std::memory_order_relaxed);
+        g = gemm_base(c, B, C, C, c.at<void>(k.o), ldt, c.wptr(k.proj), k.proj.ld, c.at<float>(k.xmid), ldt, true);
+        g.bias = p->P[k.projb]; g.rowscale = p->drop_ptr(p->drop_attn[s][i]); g.rows_per_sample = 1; g.res = xin; g.ldres = ldt;
+        g.m_dev = ca.nkeep; g.perm = ca.perm;
+        RUN(gemm_nt_t(c, &g));
+        if (ca) RUN(lnx_copy_dropped_rows(xin, c.at<float>(k.xmid), ldt, ca.perm, ca.nkeep, B, 1, C, c.st));
+        RUN(ln_fwd(c, B, C, 1e-5f, c.at<float>(k.xmid), LNX_F32, C, clsrow, k.n2w, k.n2b, c.at<void>(k.n2), c.dt, C, IDM, nullptr, 0, c.at<float>(k.mean2), c.at<float>(k.rstd2)));
+        g = gemm_base(c, B, hid, C, c.at<void>(k.n2), C, c.wptr(k.fc1), k.fc1.ld, c.at<void>(k.act), hid, false);
+        g.bias = p->P[k.fc1b]; g.act = LNX_ACT_GELU_D; g.c2 = c.at<void>(k.hpre); g.ldc2 = hid;
+        if (p->c.inference) {
+            g.act = LNX_ACT_GELU; g.c2 = nullptr; g.ldc2 = 0;
+        }
+        RUN(gemm_nt_t(c, &g));
+        g = gemm_base(c, B, C, hid, c.at<void>(k.act), hid, c.wptr(k.fc2), k.fc2.ld, xout, ldt, true);
+        g.bias = p->P[k.fc2b]; g.rowscale = p->drop_ptr(p->drop_mlp[s][i]); g.rows_per_sample = 1; g.res = c.at<float>(k.xmid); g.ldres = ldt;
+        RUN(gemm_nt_t(c, &g));
+        return 0;
     }
     if (p->dmask) {
         // proj_drop (rope_2d_mhsa.py:503): the product with its bias goes to scratch, dropout + DropPath + residual in one pass
@@ -1614,6 +1654,14 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
     // DropPath compaction lists of the RoPE blocks' and the fused conv blocks' drop calls of this forward, one launch (the multipliers are
     // drawn on the device: no host synchronisation).  LNX_DROP_COMPACT=0 / lnx_set_drop_compact(0): every branch on full rows, as before;
     // LNX_DROP_COMPACT_CONV=0: the conv blocks alone.
+    // CLS-only last block, decided per forward.  LNX_LAST_CLS=0 / lnx_set_last_cls(0): the full block.  Plans the path does not
+    // cover keep the full block as well: fp8 plans (their LayerNorm / fc1 epilogues hand MXFP8 copies on by full rows) and plans with
+    // dropout masks (DROP_RATE / ATTN_DROP_RATE > 0: the masks are laid out by full rows).
+    {
+        const int sw = g_last_cls.load(std::memory_order_relaxed);
+        const bool on = sw < 0 ? !env_off("LNX_LAST_CLS") : sw != 0;
+        p->last_cls_now = on && cf.rope_depths[1] > 0 && cf.fp8 == 0 && !p->dmask && !p->amask;
+    }
     p->compact_now = false;
     p->compact_conv_now = false;
     {
@@ -1636,7 +1684,8 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
             for (int s = 0; s < 2; ++s)
                 for (size_t i = 0; i < p->rope[s].size(); ++i)
                     for (const int call : {p->drop_attn[s][i], p->drop_mlp[s][i]})
-                        if (p->mask_host[call] && !fp8_rows(p, B * p->Ntok[s], D[2 + s])) {
+                        // (the CLS-only block's MLP call stays off the lists: its M = B products take the multiplier of the row's own sample)
+                        if (p->mask_host[call] && !fp8_rows(p, B * p->Ntok[s], D[2 + s]) && !(p->last_cls((int)s, (int)i) && call == p->drop_mlp[s][i])) {
                             want[call] = 1;
                             rps[call] = p->Ntok[s];
                             any = true;
@@ -1823,19 +1872,29 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     auto wdone = [&](int j) { return wg_done(c, j); };
     auto wjoin = [&](int j) { return wg_join(c, j); };
     // DropPath compaction (the forward's decision, from the same lists): sC / sA / sD hold compact rows inside a branch, g keeps its layout
-    const Compact ca = compact_of(p, p->drop_attn[s][i], M, C, N), cm = compact_of(p, p->drop_mlp[s][i], M, C, N);
+    // CLS-only (the forward's decision, lnx_plan::last_cls): g is zero outside the CLS rows and this block's MLP branch and proj pair saved
+    // B rows, so both run on Mb = B rows -- row b is row b N of g / xmid / o (row map, leading dimension), row b of everything else
+    const bool lc = p->last_cls(s, i);
+    if (lc && have_dy) FAIL("rope_block_bwd: the CLS-only block takes its dY from g, not from a LayerNorm backward above it");
+    // The attention call's list holds as for any block (o, sC and sD are compact under it: sample perm[j]'s CLS row is row j N of o and
+    // sD, row j of sC, and the proj pair covers nkeep rows); the MLP call has none.
+    const int Mb = lc ? B : M, rps = lc ? 1 : N;
+    const lnx_rowmap tm = lc ? lnx_rowmap{1, N - 1, 0} : IDM;
+    const int64_t ldo = lc ? (int64_t)N * C : C;
+    const Compact ca = compact_of(p, p->drop_attn[s][i], M, C, N), cm = lc ? Compact() : compact_of(p, p->drop_mlp[s][i], M, C, N);
+    const int* pj_mdev = lc ? ca.nkeep : ca.m_dev;  // effective rows of the proj pair
     const bool prev_runs = i > 0 && p->runs(p->u_rope[s] + i - 1);  // block i - 1 is not behind the cut: it takes its dY from this block's norm1 backward
     const Compact cprev = prev_runs ? compact_of(p, p->drop_mlp[s][i - 1], M, C, N) : Compact();
     // ---- MLP branch ----
     if (!have_dy) {
         if (cm) RUN(lnx_scale_cast_compact(g, C, p->drop_ptr(p->drop_mlp[s][i]), N, cm.perm, cm.m_dev, sC, c.dt, C, M, C, c.st));
-        else RUN(lnx_scale_cast(g, C, IDM, p->drop_ptr(p->drop_mlp[s][i]), N, sC, c.dt, C, M, C, c.st));
+        else RUN(lnx_scale_cast(g, C, tm, p->drop_ptr(p->drop_mlp[s][i]), rps, sC, c.dt, C, Mb, C, c.st));
     }
     if (p->dmask) RUN(lnx_dropout_mul(sC, c.dt, p->dmask + k.dm_fc2, p->inv_keep, M, C, c.st));  // through the dropout after fc2
     RUN(wfork(0));
-    RUN(wgrad(cw, M, C, hid, sC, C, c.at<void>(k.act), hid, k.fc2.param, k.fc2b, hid, 0, 0, cm.m_dev));
+    RUN(wgrad(cw, Mb, C, hid, sC, C, c.at<void>(k.act), hid, k.fc2.param, k.fc2b, hid, 0, 0, cm.m_dev));
     RUN(wdone(0));
-    lnx_gemm_args a = gemm_base(c, M, hid, C, sC, C, c.wtptr(k.fc2), k.fc2.ld_t, sA, hid, false);
+    lnx_gemm_args a = gemm_base(c, Mb, hid, C, sC, C, c.wtptr(k.fc2), k.fc2.ld_t, sA, hid, false);
     a.m_dev = cm.m_dev;
     a.act = fp8_rows(p, M, C) ? LNX_ACT_GELU_BWD : LNX_ACT_MUL_AUX; a.aux = c.at<void>(k.hpre); a.ldaux = hid;  // what the forward left in hpre
     // fp8 plans: dY comes in MXFP8 from the LayerNorm backward that wrote it (the block above's norm1 backward; quantised here when
@@ -1846,26 +1905,30 @@ int rope_block_bwd(const Ctx& c, int s, int i, float* g, bool have_dy) {
     p->dy8_ready = false;
     if (p->dmask) RUN(lnx_dropout_mul(sA, c.dt, p->dmask + k.dm_hid, p->inv_keep, M, hid, c.st));  // through the dropout after the activation
     RUN(wfork(1));
-    RUN(wgrad(cw, M, hid, C, sA, hid, c.at<void>(k.n2), C, k.fc1.param, k.fc1b, C, 0, 1, cm.m_dev));
+    RUN(wgrad(cw, Mb, hid, C, sA, hid, c.at<void>(k.n2), C, k.fc1.param, k.fc1b, C, 0, 1, cm.m_dev));
     RUN(wdone(1));
-    a = gemm_base(c, M, C, hid, sA, hid, c.wtptr(k.fc1), k.fc1.ld_t, sD, C, false);
+    a = gemm_base(c, Mb, C, hid, sA, hid, c.wtptr(k.fc1), k.fc1.ld_t, sD, C, false);
     a.m_dev = cm.m_dev;
     RUN(linear_dgrad(c, a, k.fc1, false, p->o_h8, p->o_h8s));
     RUN(wjoin(0));  // norm2 backward overwrites sC
     // norm2 backward adds into g and, in the same pass, writes the attention branch's dY (DropPath-scaled g in storage type)
     Dx2 d2;
-    d2.p = sC; d2.rowscale = p->drop_ptr(p->drop_attn[s][i]); d2.rps = N; d2.inv = ca.inv; d2.nkeep = ca.nkeep;
+    d2.p = sC; d2.rowscale = p->drop_ptr(p->drop_attn[s][i]); d2.rps = rps; d2.inv = ca.inv; d2.nkeep = ca.nkeep;
     if (mx_dgrad) {
         d2.p8 = c.at<void>(p->o_a8); d2.p8s = c.at<void>(p->o_a8s);
     }
-    RUN(ln_bwd(c, M, C, sD, c.dt, C, IDM, c.at<float>(k.xmid), LNX_F32, C, IDM, k.n2w, k.n2b, c.at<float>(k.mean2), c.at<float>(k.rstd2), g, g, LNX_F32, C, false, d2, cm));
+    // (CLS-only: the CLS rows of xmid / g by leading dimension, not by row map -- the second output's translation wants identity maps)
+    RUN(ln_bwd(c, Mb, C, sD, c.dt, C, IDM, c.at<float>(k.xmid), LNX_F32, ldo, IDM, k.n2w, k.n2b, c.at<float>(k.mean2), c.at<float>(k.rstd2), g, g, LNX_F32, ldo, false, d2, cm));
     // ---- attention branch ----
     if (p->dmask) RUN(lnx_dropout_mul(sC, c.dt, p->dmask + k.dm_proj, p->inv_keep, M, C, c.st));  // through proj_drop
     RUN(wfork(2));
-    RUN(wgrad(cw, M, C, C, sC, C, c.at<void>(k.o), C, k.proj.param, k.projb, C, 0, 2, ca.m_dev));
+    RUN(wgrad(cw, Mb, C, C, sC, C, c.at<void>(k.o), ldo, k.proj.param, k.projb, C, 0, 2, pj_mdev));
     RUN(wdone(2));
-    a = gemm_base(c, M, C, C, sC, C, c.wtptr(k.proj), k.proj.ld_t, sD, C, false);
-    a.m_dev = ca.m_dev;
+    // CLS-only: the attention backward keeps its kernel and gets a dO that is zero outside the CLS rows (exact: a query with dO = 0 has
+    // delta = 0 and dS = 0) -- one memset, and the B rows the product writes through its leading dimension
+    if (lc) HIPRUN(hipMemsetAsync(sD, 0, (size_t)M * C * p->esz, (hipStream_t)c.st));
+    a = gemm_base(c, Mb, C, C, sC, C, c.wtptr(k.proj), k.proj.ld_t, sD, ldo, false);
+    a.m_dev = pj_mdev;
     RUN(linear_dgrad(c, a, k.proj, !mx_dgrad, p->o_a8, p->o_a8s));
     RUN(wjoin(1));  // the attention backward overwrites sA
     lnx_attn_bwd_args ab;

@@ -365,6 +365,18 @@ class mFormerV1(nn.Module):
         """Conv blocks whose forward ran on compact rows since the library was loaded (lnx_drop_compact_conv_blocks)."""
         return int(L.lib().lnx_drop_compact_conv_blocks())
 
+    @staticmethod
+    def set_last_cls(on: Optional[bool]) -> int:
+        """A/B switch of the CLS-only last RoPE block (process-wide, include/lnx.h lnx_set_last_cls): True / False, or None = back to the
+        environment (LNX_LAST_CLS, on unless 0).  Read by every forward; a backward follows its forward.  Logits and gradients differ by
+        summation order and the kernel family of the M = batch products only.  Returns the previous setting (-1, 0 or 1)."""
+        return int(L.lib().lnx_set_last_cls(-1 if on is None else int(bool(on))))
+
+    @staticmethod
+    def last_cls_blocks() -> int:
+        """Forwards of the last stage-4 block that ran CLS-only since the library was loaded (lnx_last_cls_blocks)."""
+        return int(L.lib().lnx_last_cls_blocks())
+
     def set_wgrad_stream(self, on: bool) -> None:
         """Backward scheduling of this model's native plans, present and future (include/lnx.h lnx_plan_set_wgrad_stream): True (the
         default) runs the weight-gradient products on a second HIP stream beside the data-gradient chain, False keeps everything on the
