@@ -1718,6 +1718,25 @@ int lnx_plan_bind(lnx_plan* p, const float* const* params, float* const* grads, 
  * which calls use their row.  Outputs: feats [B, dims[3]] fp32, logits (layout above). */
 int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, const float* drop_scales, const unsigned char* drop_mask,
                      float* feats, float* logits, void* stream);
+/* Metadata variants from one trunk pass (lnx_version 120).
+ * Re-run an inference plan from the token boundary with other metadata: the metadata heads, both RoPE stages,
+ * norm_1 / cl_1_fc / downsample 2 (model index; plan.cpp calls it downsample 3), the tail and the heads.
+ * Needs a completed lnx_plan_forward on this plan whose stem / ConvNeXt / downsample-1 results are still in place.
+ * feats / logits as in lnx_plan_forward; they receive what lnx_plan_forward(p, x, meta, NULL, NULL, ...) with that forward's x would
+ * write, bit for bit (the same kernels on the same operands: the metadata enters only as the extra token rows of the two RoPE stages).
+ * The metadata heads run on `stream` itself (no side stream, no events).  No workspace beyond the plan's, no copy: the stage-3 token
+ * buffer is read-only to the RoPE blocks, so the forward's patch rows are still there.
+ * Rules for the caller:
+ *  - the tail must be ordered after the forward on the same stream (or by the caller's own events); so must successive tails, and
+ *    whoever reads feats / logits of one call before the next call on this plan overwrites the workspace (not those buffers);
+ *  - the tail sees the weights as of that forward (the operand arena is refreshed by lnx_plan_forward only) and follows that forward's
+ *    CLS-only decision (lnx_set_last_cls);
+ *  - any later lnx_plan_forward starts a new trunk; lnx_plan_bind and any failed lnx_plan_forward / lnx_plan_forward_tail discard it.
+ * Refused before any launch (nonzero, lnx_last_error): a NULL or unbound plan, a training or recompute plan, a plan without
+ * metadata components, NULL meta, NULL logits with tasks configured, no valid trunk.
+ * lnx_plan_trunk_valid: 1 if lnx_plan_forward_tail may be called, else 0. */
+int lnx_plan_forward_tail(lnx_plan* p, const float* meta, float* feats, float* logits, void* stream);
+int lnx_plan_trunk_valid(const lnx_plan* p);   /* 1: lnx_plan_forward_tail may be called */
 /* Training-time dropout of the RoPE blocks (MODEL.DROP_RATE): keep masks for the next forward and its backward, one byte per
  * element, per RoPE block (stage 3 blocks first) [proj output M x C][MLP hidden M x hidden][fc2 output M x C] -- the caller
  * draws them (Bernoulli(1 - drop_rate)) and keeps the buffer alive until the backward has run.  masks = NULL or

@@ -18,4 +18,4 @@ from . import autobatch, inference, loss, metrics, optim, prefetch, rl  # noqa: 
 from .inference import DevicePredictor, DevicePreprocessor  # noqa: F401
 from .optim import FusedMultiOptimizer, FusedMuon, FusedSGD, ShardedFusedMuon, build_optimizer  # noqa: F401
 from .rl import AbstentionPolicy, AbstentionReward, evaluate_policy, ppo_update, rollout  # noqa: F401
-from .collate import GPUMetaMasking, GPUTrainCollate, mask_meta_components  # noqa: F401
+from .collate import GPUMetaMasking, GPUTrainCollate, mask_meta_components, meta_variants, variant_phase_names  # noqa: F401

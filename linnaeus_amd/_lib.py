@@ -391,6 +391,9 @@ def lib() -> C.CDLL:
         if hasattr(_lib, "lnx_last_cls_blocks"):
             _lib.lnx_set_last_cls.argtypes = [C.c_int]
             _lib.lnx_last_cls_blocks.restype = C.c_int64
+        if hasattr(_lib, "lnx_plan_forward_tail"):
+            _lib.lnx_plan_forward_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            _lib.lnx_plan_trunk_valid.argtypes = [C.c_void_p]
         if hasattr(_lib, "lnx_plan_set_trainable"):
             _lib.lnx_plan_unit_name.argtypes = [C.c_void_p, C.c_int]
             _lib.lnx_plan_unit_name.restype = C.c_char_p
@@ -454,7 +457,7 @@ EXPORTS = [
     "lnx_convmlp_supported", "lnx_convmlp_fwd", "lnx_convmlp_bwd", "lnx_convmlp_bwd_ws_floats",
     "lnx_plan_create", "lnx_plan_destroy", "lnx_plan_workspace_bytes", "lnx_plan_num_params", "lnx_plan_param_name",
     "lnx_plan_param_numel", "lnx_plan_num_drop_calls", "lnx_plan_logits_numel", "lnx_plan_logits_offset", "lnx_plan_logits_ld",
-    "lnx_plan_bind", "lnx_plan_forward", "lnx_plan_backward", "lnx_plan_backward_into", "lnx_plan_segment_params", "lnx_plan_profile_begin", "lnx_plan_profile_end", "lnx_plan_profile_begin_spans", "lnx_plan_profile_end_ex", "lnx_plan_set_wgrad_stream", "lnx_plan_set_meta_stream",
+    "lnx_plan_bind", "lnx_plan_forward", "lnx_plan_forward_tail", "lnx_plan_trunk_valid", "lnx_plan_backward", "lnx_plan_backward_into", "lnx_plan_segment_params", "lnx_plan_profile_begin", "lnx_plan_profile_end", "lnx_plan_profile_begin_spans", "lnx_plan_profile_end_ex", "lnx_plan_set_wgrad_stream", "lnx_plan_set_meta_stream",
     "lnx_plan_num_units", "lnx_plan_unit_name", "lnx_plan_param_unit", "lnx_plan_set_trainable", "lnx_plan_first_trained_unit", "lnx_plan_last_backward_units",
 ]
 

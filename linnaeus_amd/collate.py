@@ -387,6 +387,52 @@ def mask_meta_components(aux, bounds_map, components=None):
     return out.to(aux.dtype)
 
 
+def _check_combos(combos, names=None) -> list:
+    """A list of variants: () = aux_info as it is, None = all of it zeroed, else the component names whose columns are zeroed."""
+    if isinstance(combos, str) or combos is None:
+        raise TypeError("combos must be a sequence of variants: (), None or a list of component names each")
+    out = []
+    for c in combos:
+        if c is None:
+            out.append(None)
+            continue
+        if isinstance(c, str):
+            raise TypeError(f"a combo is a list of component names, not the string {c!r}")
+        c = tuple(c)
+        for n in c:
+            if not isinstance(n, str):
+                raise TypeError(f"component names are strings, got {n!r}")
+            if names is not None and n not in names:
+                raise KeyError(f"unknown metadata component {n!r} (known: {list(names)})")
+        out.append(c)
+    if not out:
+        raise ValueError("no metadata variants given")
+    return out
+
+
+def variant_phase_names(combos) -> List[str]:
+    """The reference's phase name of each variant: `val` for () (validation.py:84), `val_mask_meta` for None (all of aux_info
+    zeroed, :84,174-175), `val_mask_<A_B>` for the components A, B (main.py:2207)."""
+    names = ["val_mask_meta" if c is None else ("val_mask_" + "_".join(c) if c else "val") for c in _check_combos(combos)]
+    if len(set(names)) != len(names):
+        raise ValueError(f"metadata variants repeat a phase: {names}")
+    return names
+
+
+def meta_variants(aux, bounds_map, combos):
+    """[K, B, W]: aux_info as each of the K validation passes of the reference sees it (validate_one_pass, validation.py:174-175;
+    validate_with_partial_mask, :428-489), for `mFormerV1.forward_meta_variants`.  A combo is a list of component names; () means
+    unmasked and None all of aux_info zeroed.  One mask_meta_components launch per masked variant; `aux` is not modified."""
+    combos = _check_combos(combos, list(bounds_map.keys()))
+    if aux.dim() != 2:
+        raise ValueError(f"aux must be [B, W], got {tuple(aux.shape)}")
+    _need_gpu(aux)
+    out = torch.empty((len(combos),) + tuple(aux.shape), dtype=aux.dtype, device=aux.device)
+    for k, c in enumerate(combos):
+        out[k].copy_(aux if c == () else mask_meta_components(aux, bounds_map, None if c is None else list(c)))
+    return out
+
+
 class GPUTrainCollate:
     """The training half of H5DataLoader.collate_fn (h5data/h5dataloader.py:642-1801) on a device batch
     `(images, targets, aux, masks, group_ids)`, in the reference's order: metadata masking, the mixing decision against

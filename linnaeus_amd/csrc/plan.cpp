@@ -215,6 +215,10 @@ struct lnx_plan {
     // CLS-only last block: the last forward ran the last stage-4 block's proj / norm2 / MLP on the B CLS rows only (norm_2 reads
     // nothing else of the stage output); the backward and a recompute plan's re-forward follow that forward's choice
     bool last_cls_now = false;
+    // Metadata variants: the last lnx_plan_forward of this inference plan completed and nothing has touched what it left in front
+    // of the token boundary (the stage-3 patch and CLS rows in o_tok[0], the operand arena, the cos / sin tables): lnx_plan_forward_tail may
+    // re-run the token stages with other metadata.  Cleared on entry to lnx_plan_forward, by lnx_plan_bind and by any failed call.
+    bool trunk_valid = false;
     bool last_cls(int s, int i) const { return last_cls_now && s == 1 && i + 1 == (int)rope[1].size(); }
     const int* drop_list(int call) const {
         if (!compact_now || droplists == nullptr || drop_ptr(call) == nullptr) return nullptr;
@@ -952,6 +956,7 @@ extern "C" int64_t lnx_plan_logits_offset(const lnx_plan* p, int t) { return (p 
 extern "C" int lnx_plan_logits_ld(const lnx_plan* p, int t) { return (p && t >= 0 && t < p->c.n_tasks) ? p->logit_ld[t] : -1; }
 
 extern "C" int lnx_plan_bind(lnx_plan* p, const float* const* params, float* const* grads, void* workspace) {
+    if (p) p->trunk_valid = false;  // (a new workspace or new parameters: whatever a forward left is not this binding's)
     if (!p || !params || !workspace) FAIL("lnx_plan_bind: null argument");
     {
         // One device per process (one process per GPU): the cached CU count, the per-kernel dynamic-LDS attributes (set once per process) and the
@@ -1049,6 +1054,7 @@ extern "C" int lnx_plan_bind(lnx_plan* p, const float* const* params, float* con
     p->fwd_done = false;
     return 0;
 }
+extern "C" int lnx_plan_trunk_valid(const lnx_plan* p) { return p && p->bound && p->trunk_valid ? 1 : 0; }
 
 // ------------------------------------------------------------------------------------
 // launch helpers
@@ -1619,10 +1625,11 @@ int rope_block_fwd(const Ctx& c, int s, int i, float* xout) {
     return 0;
 }
 
-}  // namespace
+int tokens_to_heads(const Ctx& c, const float* meta, int mw_all, hipStream_t mst, float* feats, float* logits);
 
-extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, const float* drop_scales, const unsigned char* drop_mask, float* feats,
-                                float* logits, void* stream) {
+// lnx_plan_forward without the trunk-validity bookkeeping of its caller below
+int plan_forward(lnx_plan* p, const float* x, const float* meta, const float* drop_scales, const unsigned char* drop_mask, float* feats, float* logits,
+                 void* stream) {
     if (!p || !p->bound) FAIL("lnx_plan_forward: plan is not bound");
     if (!x) FAIL("lnx_plan_forward: null input");
     const lnx_mformer_cfg& cf = p->c;
@@ -1764,13 +1771,31 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
         }
     }
 
+    // 3. RoPE stages, 4. tail and heads
+    RUN(tokens_to_heads(c, meta, mw_all, mst, feats, logits));
+    p->fwd_done = true;
+    return 0;
+}
+
+// Sections 3 and 4 of the forward: everything behind the token boundary.  Reads the patch rows of o_tok[0] (downsample 2 wrote them: section 2)
+// and the metadata rows of both token buffers; writes the CLS rows, o_tok[1]'s patch rows and every buffer behind them.  The metadata
+// rows: with a side stream (mst) the heads were forked there and are joined here; without one they run here, stage by stage; meta == NULL
+// (lnx_plan_forward_tail): the caller has already written them on this stream, nothing to run or to join.
+int tokens_to_heads(const Ctx& c, const float* meta, int mw_all, hipStream_t mst, float* feats, float* logits) {
+    lnx_plan* p = c.p;
+    const lnx_mformer_cfg& cf = p->c;
+    void* const stream = c.st;
+    const int B = cf.batch;
+    const int* D = cf.dims;
     // 3. RoPE stages (mFormerV1.py:445-510)
     for (int s = 0; s < 2; ++s) {
         const int N = p->Ntok[s], C = D[2 + s];
         float* tok = c.at<float>(p->o_tok[s]);
         const lnx_rowmap clsmap = {1, N - 1, 0};
         RUN(lnx_fill_rows(p->P[p->cls[s]], tok, C, clsmap, B, C, stream));
-        if (mst) {
+        if (meta == nullptr) {
+            // (the tail entry point: both stages' metadata rows are already written, in stream order; or a plan without metadata components)
+        } else if (mst) {
             if (s == 0) HIPRUN(hipStreamWaitEvent((hipStream_t)stream, p->ev_meta, 0));  // join: all meta tokens written
         } else {
             RUN(meta_fwd(c, s, s + 1, meta, mw_all));
@@ -1825,7 +1850,39 @@ extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, 
             RUN(heads_nt(c, hg, cf.n_tasks, false));  // every head in one launch where the grouped kernel takes them
         }
     }
-    p->fwd_done = true;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int lnx_plan_forward(lnx_plan* p, const float* x, const float* meta, const float* drop_scales, const unsigned char* drop_mask, float* feats,
+                                float* logits, void* stream) {
+    if (p) p->trunk_valid = false;  // a new trunk starts here; it counts once every launch of this call is enqueued
+    RUN(plan_forward(p, x, meta, drop_scales, drop_mask, feats, logits, stream));
+    p->trunk_valid = p->c.inference != 0;
+    return 0;
+}
+
+// Metadata variants: the forward again from the token boundary.  The metadata heads of both stages on the caller's stream (no fork, no
+// events: there is no trunk to run beside), then sections 3 and 4 as the forward ran them, with the forward's CLS-only decision.
+extern "C" int lnx_plan_forward_tail(lnx_plan* p, const float* meta, float* feats, float* logits, void* stream) {
+    if (!p) FAIL("lnx_plan_forward_tail: plan is NULL (nothing bound)");
+    const bool had_trunk = p->bound && p->trunk_valid;
+    p->trunk_valid = false;  // (set again below: every refusal and every failed launch leaves the plan without a trunk)
+    const lnx_mformer_cfg& cf = p->c;
+    if (!cf.inference) FAIL("lnx_plan_forward_tail: inference plans only: a training plan keeps one set of activations for its backward");
+    if (cf.n_meta <= 0) FAIL("lnx_plan_forward_tail: the plan has no metadata components: nothing to vary");
+    if (!meta) FAIL("lnx_plan_forward_tail: meta is NULL");
+    if (cf.n_tasks > 0 && !logits) FAIL("lnx_plan_forward_tail: logits buffer is NULL");
+    if (!p->bound) FAIL("lnx_plan_forward_tail: plan is not bound: no trunk to continue from");
+    if (!had_trunk) FAIL("lnx_plan_forward_tail: no valid trunk: call lnx_plan_forward on this plan first (lnx_plan_bind and a failed call discard it)");
+    Ctx c{p, stream, cf.dtype};
+    int mw_all = 0;
+    for (int m = 0; m < cf.n_meta; ++m) mw_all += cf.meta_dims[m];
+    p->last_meta = meta;
+    RUN(meta_fwd(c, 0, 2, meta, mw_all));
+    RUN(tokens_to_heads(c, nullptr, mw_all, nullptr, feats, logits));
+    p->trunk_valid = true;
     return 0;
 }
 

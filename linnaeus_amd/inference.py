@@ -183,6 +183,18 @@ class DevicePredictor:
             model.train(was_training)
         return self.predict_logits(outputs, top_k)
 
+    def predict_variants(self, model, images, metas, top_k=None) -> List[Dict[str, torch.Tensor]]:
+        """`[predict(model, images, m, top_k) for m in metas]` for the price of one trunk pass: the model's eval / no_grad
+        `forward_meta_variants` (the image alone against the image with its metadata, say), then one predict_logits per variant."""
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                outputs = model.forward_meta_variants(images, metas)
+        finally:
+            model.train(was_training)
+        return [self.predict_logits(o, top_k) for o in outputs]
+
     def to_results(self, pred) -> list:
         """ONE device-to-host copy of the four tensors -> per sample a list, coarsest task first (the reference's order), of
         (task_key, [(id, probability), ...]) with `count` entries each.  Plain Python types."""

@@ -178,3 +178,52 @@ class DeviceMetrics:
                     s_tab[phase][t]["loss"] += d[f"{kind}_loss_sum"]
                     c_tab[phase][t]["loss"] += d[f"{kind}_n"]
         self.reset()
+
+
+class MetaVariantEvaluator:
+    """The reference's validation passes over the same images with different metadata (`val`, `val_mask_meta`, `val_mask_<A_B>`:
+    validation.py:84,174-175,341-617, main.py:2207) from ONE pass over the data: per batch one `forward_meta_variants` (one trunk, K
+    token-stage passes) and one DeviceMetrics.update per variant."""
+
+    def __init__(self, model, bounds_map, combos, task_keys: Sequence[str], num_classes, null_tracking_tasks: Sequence[str] = (),
+                 subset_bins: Optional[Dict[str, int]] = None, per_sample_loss=None):
+        """combos: the variants (`collate.meta_variants`: () unmasked, None all of aux_info zeroed, else component names);
+        per_sample_loss: callable (outputs, targets) -> {task: [B]}, called once per variant.  The other arguments are DeviceMetrics'."""
+        from .collate import _check_combos, variant_phase_names
+
+        self.model = model
+        self.bounds_map = dict(bounds_map)
+        self.combos = _check_combos(combos, list(self.bounds_map.keys()))
+        self.phases = variant_phase_names(self.combos)
+        self.per_sample_loss = per_sample_loss
+        self.metrics = {ph: DeviceMetrics(task_keys, num_classes, null_tracking_tasks, subset_bins) for ph in self.phases}
+
+    def reset(self) -> None:
+        for m in self.metrics.values():
+            m.reset()
+
+    def update(self, images, aux, targets, subset_ids=None) -> None:
+        """Enqueues the masking launches, the forward and its K - 1 tails, and per variant the loss (if any) and one metrics launch;
+        never synchronises."""
+        from .collate import meta_variants
+
+        module = getattr(self.model, "module", self.model)  # (ddp.DataParallel: the wrapped model)
+        was_training = module.training
+        module.eval()
+        try:
+            with torch.no_grad():
+                outs = module.forward_meta_variants(images, meta_variants(aux, self.bounds_map, self.combos))
+                for ph, out in zip(self.phases, outs):
+                    losses = self.per_sample_loss(out, targets) if self.per_sample_loss is not None else None
+                    self.metrics[ph].update(out, targets, per_sample_losses=losses, subset_ids=subset_ids)
+        finally:
+            module.train(was_training)
+
+    def compute(self) -> dict:
+        """{phase: DeviceMetrics.compute()}"""
+        return {ph: m.compute() for ph, m in self.metrics.items()}
+
+    def flush_into(self, tracker) -> None:
+        """DeviceMetrics.flush_into for every phase, under the reference's phase names."""
+        for ph, m in self.metrics.items():
+            m.flush_into(tracker, ph)

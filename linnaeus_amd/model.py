@@ -996,6 +996,10 @@ class mFormerV1(nn.Module):
 
     def forward(self, x: torch.Tensor, meta: Optional[torch.Tensor] = None, force_checkpointing: Optional[bool] = None) -> Dict[str, torch.Tensor]:
         st, feats, views = self._run(x, meta, force_checkpointing)
+        return self._finish_outputs(st, feats, views)
+
+    def _finish_outputs(self, st, feats: torch.Tensor, views: List[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """What `forward` does behind the plan call: {task: logits} in the autocast dtype, the hierarchical refinement on top."""
         acast = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
         out = {}
         for t, v in zip(st["tasks"], views):
@@ -1013,6 +1017,65 @@ class mFormerV1(nn.Module):
             else:
                 out = refine_logits_top_down(out, self.head, self.task_keys)
         return out
+
+    # ------------------------------------------------------------------ metadata variants from one trunk pass
+    def _plan_forward_tail(self, st, meta: torch.Tensor):
+        """lnx_plan_forward_tail on the plan of the forward that just ran: the token stages again with `meta`, into fresh outputs."""
+        B = st["B"]
+        feats = torch.empty(B, self._dims[3], device=meta.device, dtype=torch.float32)
+        logits = torch.empty(max(st["logits_numel"], 1), device=meta.device, dtype=torch.float32)
+        L.check(L.lib().lnx_plan_forward_tail(
+            st["handle"], C.c_void_p(meta.data_ptr()), C.c_void_p(feats.data_ptr()), C.c_void_p(logits.data_ptr()),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "lnx_plan_forward_tail")
+        return feats, logits
+
+    def _run_meta_variants(self, x: torch.Tensor, metas):
+        if not (self.use_meta and self.meta_dims):
+            raise ValueError("forward_meta_variants: the model has no metadata components, there is nothing to vary")
+        if isinstance(metas, torch.Tensor):
+            if metas.dim() != 3:
+                raise ValueError(f"metas must be a sequence of [B, {sum(self.meta_dims)}] tensors or one [K, B, {sum(self.meta_dims)}] tensor, "
+                                 f"got {tuple(metas.shape)}")
+            metas = list(metas.unbind(0))
+        else:
+            metas = list(metas)
+        if not metas:
+            raise ValueError("forward_meta_variants: no metadata variants given")
+        if torch.is_grad_enabled() and any(p_.requires_grad for p_ in self.parameters()):
+            # a training plan keeps ONE set of activations for its backward: a second pass through the token stages would overwrite them
+            raise RuntimeError("forward_meta_variants runs on an inference plan: call it under torch.no_grad() (or on a model whose "
+                               "parameters are all frozen)")
+        for k, m in enumerate(metas):
+            if m is None:
+                raise AssertionError(f"metadata components are configured but metas[{k}] is None")
+            if m.dim() != 2 or m.shape[0] != x.shape[0] or m.shape[1] != sum(self.meta_dims):
+                raise ValueError(f"metas[{k}] must be [{x.shape[0]}, {sum(self.meta_dims)}] (components in IDX order), got {tuple(m.shape)}")
+            if not m.is_cuda:
+                raise L.LnxError("mFormerV1 (linnaeus_amd) has no CPU path: inputs must be on the GPU")
+        st, feats, views = self._run(x, metas[0])
+        B = x.shape[0]
+        results = [(feats, views)]
+        kept = [m.float().contiguous() for m in metas[1:]]
+        for m in kept:
+            f_k, logits_k = self._plan_forward_tail(st, m)
+            results.append((f_k, self._task_views(st, logits_k, B)))
+        st["saved_inputs"] = st["saved_inputs"] + (kept,)
+        return st, results
+
+    def forward_features_meta_variants(self, x: torch.Tensor, metas) -> List[torch.Tensor]:
+        """K [B, D3] feature tensors, `forward_features(x, metas[k])` each, from one pass over the stem and the ConvNeXt stages."""
+        return [f for f, _ in self._run_meta_variants(x, metas)[1]]
+
+    def forward_meta_variants(self, x: torch.Tensor, metas) -> List[Dict[str, torch.Tensor]]:
+        """`[model(x, m) for m in metas]`, bit for bit, for the price of one trunk: the metadata enters mFormerV1 only as the extra
+        tokens of the two RoPE stages (mFormerV1.py:448-465, 487-504), so variant 0 is the plan's forward and every other variant
+        re-runs the plan from the token boundary (`lnx_plan_forward_tail`: the metadata heads, the RoPE stages, the tail, the heads) on
+        the stage-3 patch tokens that forward left in the workspace.  `metas`: a sequence of K [B, sum(meta_dims)] tensors or one
+        [K, B, W] tensor (`collate.meta_variants` builds the validation passes of the reference).  Every variant owns its feats /
+        logits storage.  Eval / no_grad only (where `forward` takes an inference plan), else RuntimeError; a model without metadata
+        components raises ValueError.  In training mode under no_grad the variants share variant 0's DropPath draw."""
+        st, results = self._run_meta_variants(x, metas)
+        return [self._finish_outputs(st, f, v) for f, v in results]
 
     def __del__(self):
         try:
