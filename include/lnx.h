@@ -573,6 +573,32 @@ typedef struct lnx_stem_args {
 int lnx_stem_fwd_ok(int dtype, int Cin, int H, int W, int Cout);
 int lnx_stem_fwd(const lnx_stem_args* args, void* stream);
 
+/* Input gradient of the stem convolution (lnx_version 121; csrc/stem.hip): the transpose of nn.Conv2d(Cin, Cout, 4, 4),
+ *     dx[b, c, 4i + kh, 4j + kw] = sum over o of dy[m, o] * w[o, c*16 + kh*4 + kw],   m = (b * H/4 + i) * W/4 + j,
+ * what F.conv_transpose2d(dy as NCHW, weight, stride = 4) gives.  dy is the gradient at the convolution's output (the stem LayerNorm
+ * backward's dx), rows of ldy elements of which the first Cout count (whatever the padding holds is never read); w is the operand
+ * arena's [Cout, 64] copy the forward reads (columns >= Cin * 16 are never read).  EVERY element of dx is written exactly once (one
+ * contributor per element, no atomics, nothing to pre-zero), as 16-byte stores: in the MFMA result layout a lane holds the four kw of
+ * one (patch, c, kh), and the sixteen patches of a tile are neighbours along W, so a store instruction writes 256 contiguous bytes per
+ * (c, kh) row without a pass through LDS.
+ *   LNX_BF16: v_mfma_f32_16x16x32_bf16, fp32 accumulation.   LNX_F32: v_mfma_f32_16x16x4_f32, an exact fp32 FMA chain (strict parity).
+ * lnx_stem_dgrad_ok mirrors lnx_stem_fwd_ok (Cin <= 4, H and W multiples of 4, Cout in {96, 128, 192, 256}) for both dtypes;
+ * LNX_NO_FUSED_STEM_DGRAD in the environment makes it answer 0 (A/B against the fallback).  Every other geometry:
+ * lnx_gemm_nt(dy, transposed weight copy [Cin * 16, Cout]) -> fp32 [M, Cin * 16], then lnx_col2im_stem. */
+typedef struct lnx_stem_dgrad_args {
+    int dtype;           /* LNX_BF16 or LNX_F32: the type of dy and w */
+    int B, Cin, H, W, Cout;
+    const void* dy;      /* T [M, ldy], M = B * H/4 * W/4; 16-byte aligned rows */
+    int64_t ldy;
+    const void* w;       /* T [Cout, 64], column k = c*16 + kh*4 + kw */
+    float* dx;           /* fp32 [B, Cin, H, W], 16-byte aligned */
+} lnx_stem_dgrad_args;
+int lnx_stem_dgrad_ok(int dtype, int Cin, int H, int W, int Cout);
+int lnx_stem_dgrad(const lnx_stem_dgrad_args* args, void* stream);
+/* The inverse of lnx_im2col_stem: patches [B*(H/4)*(W/4), ldp] of T, column k = c*16 + kh*4 + kw  ->  dx fp32 NCHW [B, Cin, H, W],
+ * every element written once (columns >= Cin * 16 of a patch row are not read). */
+int lnx_col2im_stem(const void* patches, int dtype, int ldp, int B, int Cin, int H, int W, float* dx, void* stream);
+
 /* out[m, :] = rowscale[m / rows_per_sample] * in[map(m), :]   (fp32 in, T or fp32 out) */
 int lnx_scale_cast(const float* in, int64_t ldin, lnx_rowmap in_map, const float* rowscale, int rows_per_sample, void* out,
                    int out_dtype, int64_t ldout, int M, int C, void* stream);
@@ -733,6 +759,25 @@ typedef struct lnx_meta_head_bwd_args {
 int64_t lnx_meta_heads_bwd_part_floats(int B, int C);
 /* two launches per (up to four) heads: the data-gradient chain, then every weight / bias / LayerNorm gradient of those heads */
 int lnx_meta_heads_bwd(const lnx_meta_head_bwd_args* heads, int n_heads, void* stream);
+
+/* Gradient with respect to the metadata itself (lnx_version 121): for every head of the call
+ *     dmeta[b, off + j]  (+)=  sum over o of dp0[b, o] * w0[o, j],     j < dim,
+ * dp0 = the gradient at the first Linear's output, before the ReLU mask is needed again (lnx_meta_head_bwd_args.dp0 of the one-launch
+ * chain, or the launch-by-launch path's last LayerNorm-backward output), w0 = the operand arena's copy of `.0.weight`.  One launch for up
+ * to LNX_MAX_META heads; fp32 throughout; one wave per (row, head) sums over o in a fixed order (each lane its stride-64 share in
+ * ascending order, then a fixed butterfly), so the result is the same bits run to run with or without the deterministic mode.  No atomics:
+ * the heads of ONE call must cover disjoint column ranges (the components of one RoPE stage do); a component's two contributions -- one
+ * per RoPE stage -- come from two calls on one stream, the first with accumulate = 0 (write), the second with accumulate = 1 (add).
+ * Any width C >= 1 (the one-launch chain's widths and the wider ones of the launch-by-launch path alike). */
+typedef struct lnx_meta_input_grad_args {
+    int B, C;            /* batch rows; width of the head (columns of dp0, rows of w0) */
+    int dim, off;        /* the component's input width (1..16) and its first column in dmeta */
+    const float* dp0;    /* [B, lddp0] */
+    int64_t lddp0;
+    const float* w0;     /* [C, ldw0], ldw0 >= dim */
+    int ldw0;
+} lnx_meta_input_grad_args;
+int lnx_meta_input_grad(const lnx_meta_input_grad_args* heads, int n_heads, float* dmeta, int meta_width, int accumulate, void* stream);
 
 /* Per-step parameter preparation: cast fp32 master parameters into the T-typed operand
  * arena the GEMMs read (plus transposed copies for the data-gradient GEMMs and the
@@ -1757,7 +1802,8 @@ int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float* dfeats, in
  * instead of the bound ones, which stay untouched and are bound again when the call returns, whatever it returns.  No rebind:
  * the forward stays valid, and any number of these (and lnx_plan_backward) may follow one forward, each giving what a fresh
  * forward + backward would (recompute plans re-run every block, the last ones included).  GradNorm runs one forward and one
- * of these per task, seeded by that task's dlogits alone, into scratch gradient arenas. */
+ * of these per task, seeded by that task's dlogits alone, into scratch gradient arenas.  It never writes input gradients
+ * (lnx_plan_bind_input_grads): dx / dmeta stay as they are. */
 int lnx_plan_backward_into(lnx_plan* p, const float* dlogits, const float* dfeats, float* const* grads, void* stream);
 /* Live per-kernel-class timing with HIP events on the launch stream (used by bench.py for the
  * roofline line; adds event records around the timed launches, so never leave it on in a timed
@@ -1831,6 +1877,34 @@ int lnx_plan_param_unit(const lnx_plan* p, int i);
 int lnx_plan_set_trainable(lnx_plan* p, const unsigned char* mask /* [lnx_plan_num_params] */);
 int lnx_plan_first_trained_unit(const lnx_plan* p);
 int lnx_plan_last_backward_units(const lnx_plan* p);
+
+/* Input gradients (lnx_version 121): the backward continued through the stem to the image and through the metadata heads to the
+ * metadata, what autograd gives the reference for `images.requires_grad_(True)` / `meta.requires_grad_(True)`.
+ *   lnx_plan_set_input_grads(p, want_x, want_meta)   legal only between lnx_plan_create and lnx_plan_bind, in either order with
+ *       lnx_plan_set_trainable (it may change lnx_plan_workspace_bytes); refused by name on an inference plan, after the bind, and
+ *       want_meta on a plan without metadata components.  With a flag set the data path of the backward runs down to that source
+ *       whatever the trainable mask: want_x moves the cut (lnx_plan_first_trained_unit) to the stem, want_meta to tokens_1 at the latest
+ *       (the first unit that holds a metadata head; the RoPE stages, mid and everything behind them then run).  The units from the cut
+ *       on run the launches they always run, so a frozen parameter behind the cut is treated as the fine-tuning contract above treats
+ *       it: its gradient slice is unspecified and the caller hands no gradient out for it.  With a flag set lnx_plan_set_trainable
+ *       accepts an all-zero mask (nothing trains, only the inputs are differentiated).  Both flags zero = the plan as created: the
+ *       same workspace bytes, the same launches, the same bits.
+ *   lnx_plan_input_grads(p)   bit 0: want_x, bit 1: want_meta (negative: NULL plan)
+ *   lnx_plan_bind_input_grads(p, dx, dmeta)   where the NEXT lnx_plan_backward writes them; callable any time after the flags are set,
+ *       before any backward; the pointers stay until the next call.  dx fp32 [B, Cin, H, W], 16-byte aligned, every element written
+ *       (no pre-zeroing) in segment 3 behind the stem's weight gradient.  dmeta fp32 [B, sum(meta_dims)], every element written: the
+ *       stage-4 heads write it and the stage-3 heads add to it (a fixed order: the heads of both stages run on one stream, the
+ *       stage-4 heads first), and it is final after SEGMENT 2, where the stage-3 heads' backward is joined (as their parameter
+ *       gradients are: lnx_plan_segment_params).  NULL skips that output for the backwards that follow; a pointer for an output whose
+ *       flag is not set is refused.
+ * lnx_plan_backward_into (GradNorm) never writes input gradients: its per-task backwards leave dx / dmeta untouched.
+ * Recompute, fp8, DropPath-compacted, deterministic and fine-tuning plans take the same kernels: lnx_stem_dgrad where
+ * lnx_stem_dgrad_ok, else lnx_gemm_nt on a transposed copy of the stem weight (kept in the operand arena of want_x plans only) +
+ * lnx_col2im_stem; lnx_meta_input_grad for the metadata, one launch per stage with the one-launch chain and one per head on the
+ * launch-by-launch path.  Second-order gradients (a graph through the backward) are out of scope. */
+int lnx_plan_set_input_grads(lnx_plan* p, int want_x, int want_meta);
+int lnx_plan_input_grads(const lnx_plan* p);
+int lnx_plan_bind_input_grads(lnx_plan* p, float* dx, float* dmeta);
 
 #ifdef __cplusplus
 }

@@ -398,6 +398,13 @@ def lib() -> C.CDLL:
             _lib.lnx_plan_unit_name.argtypes = [C.c_void_p, C.c_int]
             _lib.lnx_plan_unit_name.restype = C.c_char_p
             _lib.lnx_plan_set_trainable.argtypes = [C.c_void_p, C.c_char_p]
+        if hasattr(_lib, "lnx_plan_set_input_grads"):
+            _lib.lnx_plan_set_input_grads.argtypes = [C.c_void_p, C.c_int, C.c_int]
+            _lib.lnx_plan_input_grads.argtypes = [C.c_void_p]
+            _lib.lnx_plan_bind_input_grads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            _lib.lnx_stem_dgrad.argtypes = [C.POINTER(StemDgradArgs), C.c_void_p]
+            _lib.lnx_col2im_stem.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            _lib.lnx_meta_input_grad.argtypes = [C.POINTER(MetaInputGradArgs), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         if hasattr(_lib, "lnx_gemm_tn_query"):
             _lib.lnx_gemm_tn_query.argtypes = [C.POINTER(WgradArgs), C.POINTER(TnLaunch)]
         if hasattr(_lib, "lnx_layernorm_fwd_query"):
@@ -459,6 +466,7 @@ EXPORTS = [
     "lnx_plan_param_numel", "lnx_plan_num_drop_calls", "lnx_plan_logits_numel", "lnx_plan_logits_offset", "lnx_plan_logits_ld",
     "lnx_plan_bind", "lnx_plan_forward", "lnx_plan_forward_tail", "lnx_plan_trunk_valid", "lnx_plan_backward", "lnx_plan_backward_into", "lnx_plan_segment_params", "lnx_plan_profile_begin", "lnx_plan_profile_end", "lnx_plan_profile_begin_spans", "lnx_plan_profile_end_ex", "lnx_plan_set_wgrad_stream", "lnx_plan_set_meta_stream",
     "lnx_plan_num_units", "lnx_plan_unit_name", "lnx_plan_param_unit", "lnx_plan_set_trainable", "lnx_plan_first_trained_unit", "lnx_plan_last_backward_units",
+    "lnx_stem_dgrad_ok", "lnx_stem_dgrad", "lnx_col2im_stem", "lnx_meta_input_grad", "lnx_plan_set_input_grads", "lnx_plan_input_grads", "lnx_plan_bind_input_grads",
 ]
 
 
@@ -613,6 +621,15 @@ class StemArgs(C.Structure):  # == lnx_stem_args
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("patches", C.c_void_p),
                 ("pre", C.c_void_p), ("y", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("B", C.c_int), ("Cin", C.c_int), ("H", C.c_int),
                 ("W", C.c_int), ("Cout", C.c_int), ("eps", C.c_float)]
+
+
+class StemDgradArgs(C.Structure):  # == lnx_stem_dgrad_args
+    _fields_ = [("dtype", C.c_int), ("B", C.c_int), ("Cin", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cout", C.c_int),
+                ("dy", C.c_void_p), ("ldy", C.c_int64), ("w", C.c_void_p), ("dx", C.c_void_p)]
+
+
+class MetaInputGradArgs(C.Structure):  # == lnx_meta_input_grad_args
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("dim", C.c_int), ("off", C.c_int), ("dp0", C.c_void_p), ("lddp0", C.c_int64), ("w0", C.c_void_p), ("ldw0", C.c_int)]
 
 
 class MixArgs(C.Structure):

@@ -20,7 +20,7 @@ void lnx_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* lnx_last_error(void) { return g_err; }
-extern "C" int lnx_version(void) { return 120; }
+extern "C" int lnx_version(void) { return 121; }
 extern "C" int lnx_device_cus(void) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;

@@ -41,6 +41,27 @@ __global__ __launch_bounds__(256) void im2col_stem_kernel(const float* __restric
     }
 }
 
+// the inverse (lnx_col2im_stem): one thread per (patch row, channel, kh) reads 4 T and writes 4 contiguous floats of the image; the
+// patches of a row are neighbouring threads' units only every Cin * 4, so the unit index runs fastest over the PATCH: neighbouring
+// threads write neighbouring float4 of one image row
+template <typename T>
+__global__ __launch_bounds__(256) void col2im_stem_kernel(const T* __restrict__ in, float* __restrict__ x, int B, int Cin, int H, int W, int ldp) {
+    const int Ho = H >> 2, Wo = W >> 2;
+    const int64_t rows = (int64_t)B * Ho * Wo, total = rows * Cin * 4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int wo = (int)(i % Wo);
+        int64_t t = i / Wo;
+        const int kh = (int)(t & 3);
+        t >>= 2;
+        const int c = (int)(t % Cin);
+        t /= Cin;
+        const int ho = (int)(t % Ho);
+        const int b = (int)(t / Ho);
+        const T* src = in + (((int64_t)b * Ho + ho) * Wo + wo) * ldp + 16 * c + 4 * kh;
+        *reinterpret_cast<float4*>(x + (((int64_t)b * Cin + c) * H + 4 * ho + kh) * W + 4 * wo) = make_float4(to_f(src[0]), to_f(src[1]), to_f(src[2]), to_f(src[3]));
+    }
+}
+
 // out[m, c] = rowscale[m / rps] * in[map(m), c]
 template <typename T>
 __global__ __launch_bounds__(256) void scale_cast_kernel(const float* __restrict__ in, int64_t ldin, RowMap map, const float* __restrict__ rowscale,
@@ -372,6 +393,19 @@ extern "C" int lnx_im2col_stem(const float* x, int B, int Cin, int H, int W, voi
     const int64_t total = (int64_t)B * (H / 4) * (W / 4) * (ldp / 4);
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, hipLaunchKernelGGL((im2col_stem_kernel<T>), dim3(ew_grid(total, 256)), dim3(256), 0, st, x, (T*)patches, B, Cin, H, W, ldp));
+    LNX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lnx_col2im_stem(const void* patches, int dtype, int ldp, int B, int Cin, int H, int W, float* dx, void* stream) {
+    LNX_CHECK(patches && dx, "lnx_col2im_stem: null operand");
+    LNX_CHECK(dtype == LNX_BF16 || dtype == LNX_F32, "lnx_col2im_stem: unsupported dtype %d (LNX_BF16 or LNX_F32)", dtype);
+    LNX_CHECK(B > 0 && Cin >= 1 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0 && ldp >= Cin * 16, "lnx_col2im_stem: bad geometry B=%d Cin=%d H=%d W=%d ldp=%d (H and W multiples of 4, ldp >= Cin * 16)",
+              B, Cin, H, W, ldp);
+    LNX_CHECK((((uintptr_t)dx) & 15) == 0, "lnx_col2im_stem: dx must be 16-byte aligned");
+    const int64_t total = (int64_t)B * (H / 4) * (W / 4) * Cin * 4;
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_T(dtype, hipLaunchKernelGGL((col2im_stem_kernel<T>), dim3(ew_grid(total, 256)), dim3(256), 0, st, (const T*)patches, dx, B, Cin, H, W, ldp));
     LNX_LAUNCH_CHECK();
     return 0;
 }

@@ -590,3 +590,65 @@ extern "C" int lnx_meta_heads_bwd(const lnx_meta_head_bwd_args* heads, int n_hea
     }
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// lnx_meta_input_grad: the gradient with respect to the metadata, dmeta[b, off + j] (+)= sum_o dp0[b, o] w0[o, j].  B x dim outputs of
+// C products each: nothing to tile.  One wave per (row b, head); lane l walks o = l, l + 64, ... in ascending order with one fp32 FMA
+// chain per column j, then a fixed butterfly over the 64 lanes: the summation order depends on nothing but the shapes.
+// ------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct MigBatch {
+    lnx_meta_input_grad_args h[LNX_MAX_META];
+    float* dmeta;
+    int meta_width, accumulate;
+};
+
+__global__ __launch_bounds__(256) void meta_input_grad_kernel(const MigBatch bt) {
+    const lnx_meta_input_grad_args& a = bt.h[blockIdx.y];
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;  // wave-uniform
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    const float* dp = a.dp0 + (int64_t)b * a.lddp0;
+    for (int o = lane; o < a.C; o += 64) {
+        const float d = dp[o];
+        const float* wr = a.w0 + (int64_t)o * a.ldw0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (j < a.dim) acc[j] = fmaf(d, wr[j], acc[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = wave_sum(acc[j]);
+    float* out = bt.dmeta + (int64_t)b * bt.meta_width + a.off;
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (lane == j && j < a.dim) out[j] = bt.accumulate ? out[j] + acc[j] : acc[j];
+}
+
+}  // namespace
+
+extern "C" int lnx_meta_input_grad(const lnx_meta_input_grad_args* heads, int n_heads, float* dmeta, int meta_width, int accumulate, void* stream) {
+    LNX_CHECK(heads != nullptr && n_heads > 0, "lnx_meta_input_grad: no heads");
+    LNX_CHECK(n_heads <= LNX_MAX_META, "lnx_meta_input_grad: %d heads in one call (at most LNX_MAX_META = %d)", n_heads, LNX_MAX_META);
+    LNX_CHECK(dmeta != nullptr, "lnx_meta_input_grad: dmeta is NULL");
+    LNX_CHECK(meta_width > 0, "lnx_meta_input_grad: meta_width=%d", meta_width);
+    MigBatch bt = {};
+    int maxB = 0;
+    for (int i = 0; i < n_heads; ++i) {
+        const lnx_meta_input_grad_args& a = heads[i];
+        LNX_CHECK(a.dp0 && a.w0, "lnx_meta_input_grad: null operand (head %d)", i);
+        LNX_CHECK(a.B > 0 && a.C > 0 && a.dim >= 1 && a.dim <= 16, "lnx_meta_input_grad: B=%d C=%d dim=%d (head %d; dim 1..16)", a.B, a.C, a.dim, i);
+        LNX_CHECK(a.lddp0 >= a.C && a.ldw0 >= a.dim && a.off >= 0 && a.off + a.dim <= meta_width, "lnx_meta_input_grad: bad leading dimension / metadata slice (head %d)", i);
+        for (int k = 0; k < i; ++k)  // no atomics: two heads of one launch must not write the same column
+            LNX_CHECK(a.off + a.dim <= heads[k].off || heads[k].off + heads[k].dim <= a.off,
+                      "lnx_meta_input_grad: heads %d and %d overlap in dmeta (a component's second contribution takes a second call with accumulate = 1)", k, i);
+        bt.h[i] = a;
+        if (a.B > maxB) maxB = a.B;
+    }
+    bt.dmeta = dmeta; bt.meta_width = meta_width; bt.accumulate = accumulate ? 1 : 0;
+    hipLaunchKernelGGL(meta_input_grad_kernel, dim3((maxB + 3) / 4, n_heads), dim3(256), 0, (hipStream_t)stream, bt);
+    LNX_LAUNCH_CHECK();
+    return 0;
+}

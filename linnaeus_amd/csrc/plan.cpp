@@ -111,6 +111,15 @@ struct lnx_plan {
     bool frozen_prefix = true;  // LNX_FROZEN_PREFIX=0 (read at creation): lnx_plan_set_trainable accepts and ignores its mask (A/B switch)
     int bwd_units = 0;          // units the last backward ran (lnx_plan_last_backward_units)
     bool runs(int unit) const { return unit >= cut; }  // the backward runs this unit
+    // Input gradients (lnx_plan_set_input_grads): the backward's data path continues to the image (want_x: the cut is the stem) / to the
+    // metadata (want_meta: the cut is tokens_1 at the latest) whatever the mask says; mask_cut keeps what lnx_plan_set_trainable asked for
+    // (the number of units: an all-zero mask, legal only with a flag set).  dx_out / dmeta_out: where the next backward writes them
+    // (lnx_plan_bind_input_grads; NULL = not this time); hold_input_grads: lnx_plan_backward_into is running, which never writes them.
+    int mask_cut = 0;
+    bool want_x = false, want_meta = false, hold_input_grads = false;
+    float *dx_out = nullptr, *dmeta_out = nullptr;
+    int64_t o_dcol = 0;  // want_x without lnx_stem_dgrad: the [M0, in_chans * 16] product between lnx_gemm_nt and lnx_col2im_stem
+    float* dmeta_dst() const { return want_meta && !hold_input_grads ? dmeta_out : nullptr; }
     std::vector<const float*> P;
     std::vector<float*> G;
     bool bound = false, has_grads = false, fwd_done = false;
@@ -462,6 +471,7 @@ struct Carver {
 }  // namespace
 
 static void layout_workspace(lnx_plan* p);
+static void apply_cut(lnx_plan* p);
 
 extern "C" int lnx_plan_create(const lnx_mformer_cfg* cfg, lnx_plan** out) {
     if (!cfg || !out) FAIL("lnx_plan_create: null argument");
@@ -840,6 +850,9 @@ static void layout_workspace(lnx_plan* p) {
             p->amask_bytes += (int64_t)B * c.rope_heads[s] * N * ((N + 63) / 64 * 64);
         }
     }
+    // the image gradient without the fused kernel: dY . W lands here as fp32 [M0, in_chans * 16] before lnx_col2im_stem (stem_w.ld_t != 0: the
+    // plan keeps a transposed copy of the stem weight for that product -- apply_cut)
+    p->o_dcol = p->want_x && p->stem_w.ld_t ? cv.take((int64_t)B * p->HW[0] * c.in_chans * 16 * 4) : 0;
     p->ws_bytes = cv.cur;
 }
 
@@ -859,12 +872,56 @@ extern "C" int lnx_plan_set_trainable(lnx_plan* p, const unsigned char* mask) {
     int cut = -1;
     for (size_t i = 0; i < p->unit_of.size(); ++i)
         if (mask[i] && (cut < 0 || p->unit_of[i] < cut)) cut = p->unit_of[i];
-    if (cut < 0) FAIL("lnx_plan_set_trainable: the mask is all zero: nothing trains; use an inference plan (cfg.inference = 1) for that");
-    if (!p->frozen_prefix) return 0;  // LNX_FROZEN_PREFIX=0: the full plan, whatever the mask says
-    if (cut != p->cut) {
+    if (cut < 0) {
+        if (!p->want_x && !p->want_meta)
+            FAIL("lnx_plan_set_trainable: the mask is all zero: nothing trains; use an inference plan (cfg.inference = 1) for that, or ask for input gradients first "
+                 "(lnx_plan_set_input_grads)");
+        cut = (int)p->unit_names.size();  // nothing trains: only the inputs are differentiated
+    }
+    p->mask_cut = cut;
+    apply_cut(p);
+    return 0;
+}
+
+// The cut the backward stops behind, from the trainable mask and the input-gradient flags, and what depends on it: the transposed copy
+// of the stem weight (the image gradient's lnx_gemm_nt, only where lnx_stem_dgrad does not carry the geometry) and the workspace layout.
+static void apply_cut(lnx_plan* p) {
+    const lnx_mformer_cfg& c = p->c;
+    int cut = p->frozen_prefix ? p->mask_cut : 0;  // LNX_FROZEN_PREFIX=0: the full plan, whatever the mask says
+    if (p->want_meta && cut > p->u_tok[0]) cut = p->u_tok[0];
+    if (p->want_x) cut = 0;
+    if (cut >= (int)p->unit_names.size()) cut = p->u_heads;  // (LNX_FROZEN_PREFIX=0 cannot get here; an all-zero mask needs a flag)
+    const int ld_t = p->want_x && !lnx_stem_dgrad_ok(c.dtype, c.in_chans, c.img_h, c.img_w, c.dims[0]) ? c.dims[0] : 0;
+    if (cut != p->cut || ld_t != p->stem_w.ld_t) {
         p->cut = cut;
+        p->stem_w.ld_t = ld_t;
         layout_workspace(p);
     }
+}
+
+extern "C" int lnx_plan_set_input_grads(lnx_plan* p, int want_x, int want_meta) {
+    if (!p) FAIL("lnx_plan_set_input_grads: null plan");
+    if (p->c.inference) FAIL("lnx_plan_set_input_grads: this is an inference plan (cfg.inference = 1): it has no backward");
+    if (p->bound) FAIL("lnx_plan_set_input_grads: the plan is already bound (lnx_plan_bind); the flags change lnx_plan_workspace_bytes, so set them between create and bind");
+    if (want_meta && p->c.n_meta <= 0) FAIL("lnx_plan_set_input_grads: want_meta on a plan without metadata components (cfg.n_meta = 0)");
+    if (!want_x && !want_meta && p->mask_cut >= (int)p->unit_names.size())
+        FAIL("lnx_plan_set_input_grads: the trainable mask is all zero, so at least one input gradient must stay wanted");
+    p->want_x = want_x != 0;
+    p->want_meta = want_meta != 0;
+    if (!p->want_x) p->dx_out = nullptr;
+    if (!p->want_meta) p->dmeta_out = nullptr;
+    apply_cut(p);
+    return 0;
+}
+extern "C" int lnx_plan_input_grads(const lnx_plan* p) { return p ? (p->want_x ? 1 : 0) | (p->want_meta ? 2 : 0) : -1; }
+extern "C" int lnx_plan_bind_input_grads(lnx_plan* p, float* dx, float* dmeta) {
+    if (!p) FAIL("lnx_plan_bind_input_grads: null plan");
+    if (p->c.inference) FAIL("lnx_plan_bind_input_grads: this is an inference plan (cfg.inference = 1): it has no backward");
+    if (dx && !p->want_x) FAIL("lnx_plan_bind_input_grads: dx given, but the plan was not asked for the image gradient (lnx_plan_set_input_grads want_x)");
+    if (dmeta && !p->want_meta) FAIL("lnx_plan_bind_input_grads: dmeta given, but the plan was not asked for the metadata gradient (lnx_plan_set_input_grads want_meta)");
+    if ((((uintptr_t)dx) & 15) != 0 || (((uintptr_t)dmeta) & 3) != 0) FAIL("lnx_plan_bind_input_grads: dx must be 16-byte aligned, dmeta 4-byte aligned");
+    p->dx_out = dx;
+    p->dmeta_out = dmeta;
     return 0;
 }
 
@@ -1456,6 +1513,26 @@ int meta_chain_fwd(const Ctx& c, int s_lo, int s_hi, const float* meta, int meta
     return n ? lnx_meta_heads_fwd(a, n, c.st) : 0;
 }
 
+// The metadata gradient (want_meta plans, lnx_meta_input_grad): head m of stage s contributes dp0 . w0 to its component's columns.  A
+// component has two heads, one per RoPE stage, and both stages' head backwards run on one stream (meta_stream, or the launch stream) in
+// the order stage 4, stage 3: the stage-4 heads WRITE dmeta (every column belongs to a component), the stage-3 heads ADD to it -- a fixed
+// order with no atomics and nothing to pre-zero.  Final once the stage-3 heads are joined (the end of segment 2).
+int meta_width_of(const lnx_plan* p) {
+    int w = 0;
+    for (int m = 0; m < p->c.n_meta; ++m) w += p->c.meta_dims[m];
+    return w;
+}
+int meta_accumulates(int s) { return s == 0 ? 1 : 0; }
+lnx_meta_input_grad_args meta_input_grad_of(const Ctx& c, int s, int m, const float* dp0) {
+    const MetaHead& k = c.p->meta[s][m];
+    lnx_meta_input_grad_args a;
+    memset(&a, 0, sizeof a);
+    a.B = c.p->c.batch; a.C = c.p->c.dims[2 + s]; a.dim = k.dim; a.off = k.off;
+    a.dp0 = dp0; a.lddp0 = a.C;
+    a.w0 = (const float*)c.wptr(k.w0); a.ldw0 = k.w0.ld;
+    return a;
+}
+
 // ... and their backward for one stage: g = gradient of the stage's token matrix [B N, C]
 int meta_chain_bwd(const Ctx& c, int s, const float* g) {
     lnx_plan* p = c.p;
@@ -1476,7 +1553,14 @@ int meta_chain_bwd(const Ctx& c, int s, const float* g) {
         h.d_w1 = p->G[k.w1.param]; h.d_b1 = p->G[k.b1]; h.d_ln1_w = p->G[k.nf1w]; h.d_ln1_b = p->G[k.nf1b];
         h.d_w2 = p->G[k.w2.param]; h.d_b2 = p->G[k.b2]; h.d_ln2_w = p->G[k.nf2w]; h.d_ln2_b = p->G[k.nf2b];
     }
-    return p->c.n_meta ? lnx_meta_heads_bwd(a, p->c.n_meta, c.st) : 0;
+    if (p->c.n_meta == 0) return 0;
+    RUN(lnx_meta_heads_bwd(a, p->c.n_meta, c.st));
+    if (float* dmeta = p->dmeta_dst()) {  // every head of the stage from the dp0 the chain just left, one launch
+        lnx_meta_input_grad_args ig[LNX_MAX_META];
+        for (int m = 0; m < p->c.n_meta; ++m) ig[m] = meta_input_grad_of(c, s, m, a[m].dp0);
+        RUN(lnx_meta_input_grad(ig, p->c.n_meta, dmeta, meta_width_of(p), meta_accumulates(s), c.st));
+    }
+    return 0;
 }
 
 // The metadata heads of stages [s_lo, s_hi), forward: the one-launch chain where it carries the stage's width (chain_ok), else head by head
@@ -2183,6 +2267,10 @@ int meta_head_bwd(const Ctx& cc, int s, int m, const float* g) {
     RUN(gemm_nt_t(c, &a));
     RUN(ln_bwd(c, B, C, dxf, LNX_F32, C, IDM, c.at<void>(k.h0), c.dt, C, IDM, k.lnw0, k.lnb0, c.at<float>(k.m0), c.at<float>(k.r0), nullptr, t1, c.dt, C, true));
     RUN(wgrad(c, B, C, 16, t1, C, c.at<void>(k.t0), 16, k.w0.param, k.b0, k.dim, k.dim));
+    if (float* dmeta = p->dmeta_dst()) {  // t1 = this path's dp0 (fp32), overwritten by the next head: one launch per head
+        const lnx_meta_input_grad_args ig = meta_input_grad_of(c, s, m, (const float*)t1);
+        RUN(lnx_meta_input_grad(&ig, 1, dmeta, meta_width_of(p), meta_accumulates(s), c.st));
+    }
     return 0;
 }
 
@@ -2442,6 +2530,22 @@ extern "C" int lnx_plan_backward(lnx_plan* p, const float* dlogits, const float*
                        c.at<float>(p->o_stem_rstd), nullptr, sC, cf.dtype, D[0], false));
             const int kst = cf.in_chans * 16;
             RUN(wgrad(c, M0, D[0], 64, sC, D[0], c.at<void>(p->o_patches), 64, p->stem_w.param, p->stem_b, kst, kst));
+            if (p->want_x && p->dx_out && !p->hold_input_grads) {
+                // the image gradient: dx = unpatchify(dY . W) from the same dY, in one kernel where it carries the geometry
+                if (p->stem_w.ld_t == 0) {
+                    lnx_stem_dgrad_args a;
+                    memset(&a, 0, sizeof a);
+                    a.dtype = cf.dtype; a.B = B; a.Cin = cf.in_chans; a.H = cf.img_h; a.W = cf.img_w; a.Cout = D[0];
+                    a.dy = sC; a.ldy = D[0]; a.w = c.wptr(p->stem_w); a.dx = p->dx_out;
+                    RUN(lnx_stem_dgrad(&a, stream));
+                } else {
+                    void* dcol = c.at<void>(p->o_dcol);
+                    // (the product leaves the GEMM in fp32: dx is an fp32 tensor, and a bf16 round trip in between would be its only rounding)
+                    const lnx_gemm_args a = gemm_base(c, M0, kst, D[0], sC, D[0], c.wtptr(p->stem_w), p->stem_w.ld_t, dcol, kst, true);
+                    RUN(gemm_nt_t(c, &a));
+                    RUN(lnx_col2im_stem(dcol, LNX_F32, kst, B, cf.in_chans, cf.img_h, cf.img_w, p->dx_out, stream));
+                }
+            }
             ran();
         }
         RUN(ln_flush(c));
@@ -2462,8 +2566,14 @@ extern "C" int lnx_plan_backward_into(lnx_plan* p, const float* dlogits, const f
     struct Swap {
         lnx_plan* p;
         std::vector<float*>& v;
-        Swap(lnx_plan* p_, std::vector<float*>& v_) : p(p_), v(v_) { p->G.swap(v); }
-        ~Swap() { p->G.swap(v); }  // the bound set is back on every exit path
+        Swap(lnx_plan* p_, std::vector<float*>& v_) : p(p_), v(v_) {
+            p->G.swap(v);
+            p->hold_input_grads = true;  // a per-task backward never writes the input gradients (include/lnx.h)
+        }
+        ~Swap() {  // the bound set is back on every exit path
+            p->G.swap(v);
+            p->hold_input_grads = false;
+        }
     } swap{p, into};
     return lnx_plan_backward(p, dlogits, dfeats, -1, stream);
 }

@@ -237,3 +237,156 @@ extern "C" int lnx_stem_fwd(const lnx_stem_args* a, void* stream) {
     LNX_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Input gradient of the patchify convolution (lnx_stem_dgrad): dx = unpatchify(dY . W), the transpose of Conv2d(Cin, Cout, 4, 4).
+// Per 16-patch tile a wave computes the TRANSPOSED product, first operand = 16 columns k of W (one channel c: k = 16 c + 4 kh + kw),
+// second = the 16 dY rows, contraction over the Cout output channels.  In the result layout lane (s, g) holds rows 4 g .. 4 g + 3 of
+// column s: the four kw of (patch s, channel c, kh = g) -- exactly one float4 of the image, x[b, c, 4 i + g, 4 j .. 4 j + 3].  The sixteen
+// patches of a tile are neighbours along W (until a row of patches ends), so every store instruction writes four runs of up to 256
+// contiguous bytes, straight from the accumulators: the result never needs a pass through LDS to become whole runs.  One contributor per
+// element, every element written.  The kernel reads 2 Cout (bf16) bytes and writes 64 Cin bytes per patch: bound by its stores.
+//   bf16: the W fragments (Cout / 32 k steps x Cin channels, 4 registers each) stay in registers for the whole kernel.
+//   fp32: W lives in LDS ([Cout][64] floats, at most 64 KiB) and v_mfma_f32_16x16x4_f32 walks Cout four channels at a time in a permuted
+//         order -- step ks takes o = g Cout / 4 + ks from both operands -- so that a lane's dY values are one contiguous run of its row.
+// ------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct StemDgP {
+    const void* dy;
+    int64_t ldy;
+    const void* w;
+    float* dx;
+    int B, Cin, H, W, Ho, Wo, M;
+};
+
+// where lane (s, g) of a tile stores channel 0 (add c planes for channel c); m is clamped to a live patch by the caller
+__device__ __forceinline__ float* dgrad_dst(const StemDgP& p, int m, int g) {
+    const int wo = m % p.Wo, t2 = m / p.Wo;
+    const int ho = t2 % p.Ho, b = t2 / p.Ho;
+    return p.dx + ((int64_t)b * p.Cin * p.H + 4 * ho + g) * p.W + 4 * wo;
+}
+
+template <int NK>  // Cout = 32 NK
+__global__ __launch_bounds__(256) void stem_dgrad_bf16_kernel(const StemDgP p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = lane & 15, g = lane >> 4;
+    const bf16_t* w = (const bf16_t*)p.w;
+    // first operand: row s of channel c's tile is column 16 c + s of W, element j of k step ks is output channel 32 ks + 8 g + j
+    uint4 wf[4][NK];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int ks = 0; ks < NK; ++ks) {
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (c < p.Cin) {  // (columns beyond Cin * 16 are padding: never read)
+                bf16_t* e = reinterpret_cast<bf16_t*>(&v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) e[j] = w[(int64_t)(32 * ks + 8 * g + j) * 64 + 16 * c + s];
+            }
+            wf[c][ks] = v;
+        }
+    const int64_t plane = (int64_t)p.H * p.W;
+    const int ntiles = (p.M + 15) / 16;
+    for (int t = blockIdx.x * 4 + wave; t < ntiles; t += gridDim.x * 4) {
+        const int m = t * 16 + s, mc = min(m, p.M - 1);  // a lane beyond M (last tile) computes patch M - 1 again and stores nothing
+        const bf16_t* dyr = (const bf16_t*)p.dy + (int64_t)mc * p.ldy + 8 * g;
+        uint4 dv[NK];
+#pragma unroll
+        for (int ks = 0; ks < NK; ++ks) dv[ks] = ld16(dyr + 32 * ks);
+        float* px = dgrad_dst(p, mc, g);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c < p.Cin) {  // wave-uniform
+                f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < NK; ++ks)
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8v, wf[c][ks]), __builtin_bit_cast(bf16x8v, dv[ks]), acc, 0, 0, 0);
+                if (m < p.M) *reinterpret_cast<float4*>(px + (int64_t)c * plane) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            }
+        }
+    }
+}
+
+template <int NK>  // Cout = 32 NK
+__global__ __launch_bounds__(256) void stem_dgrad_f32_kernel(const StemDgP p) {
+    constexpr int Cout = 32 * NK, Q = Cout / 4;
+    __shared__ __attribute__((aligned(16))) float wl[Cout * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = lane & 15, g = lane >> 4;
+    {
+        const float4* src = reinterpret_cast<const float4*>(p.w);
+        float4* dst = reinterpret_cast<float4*>(wl);
+        for (int i = threadIdx.x; i < Cout * 16; i += 256) dst[i] = src[i];
+    }
+    __syncthreads();
+    const int64_t plane = (int64_t)p.H * p.W;
+    const int ntiles = (p.M + 15) / 16;
+    for (int t = blockIdx.x * 4 + wave; t < ntiles; t += gridDim.x * 4) {
+        const int m = t * 16 + s, mc = min(m, p.M - 1);
+        const float* dyr = (const float*)p.dy + (int64_t)mc * p.ldy + g * Q;
+        f32x4_t acc[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int k4 = 0; k4 < Q / 4; ++k4) {
+            const float4 d = *reinterpret_cast<const float4*>(dyr + 4 * k4);
+            const float dd[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float* wr = wl + (g * Q + 4 * k4 + i) * 64 + s;
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (c < p.Cin) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * c], dd[i], acc[c], 0, 0, 0);
+            }
+        }
+        float* px = dgrad_dst(p, mc, g);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < p.Cin && m < p.M) *reinterpret_cast<float4*>(px + (int64_t)c * plane) = make_float4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]);
+    }
+}
+
+}  // namespace
+
+extern "C" int lnx_stem_dgrad_ok(int dtype, int Cin, int H, int W, int Cout) {
+    static const bool off = getenv("LNX_NO_FUSED_STEM_DGRAD") != nullptr;
+    return !off && (dtype == LNX_BF16 || dtype == LNX_F32) && Cin >= 1 && Cin <= 4 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0 &&
+           (Cout == 96 || Cout == 128 || Cout == 192 || Cout == 256);
+}
+
+extern "C" int lnx_stem_dgrad(const lnx_stem_dgrad_args* a, void* stream) {
+    LNX_CHECK(a && a->dy && a->w && a->dx, "lnx_stem_dgrad: null operand");
+    LNX_CHECK(a->dtype == LNX_BF16 || a->dtype == LNX_F32, "lnx_stem_dgrad: unsupported dtype %d (LNX_BF16 or LNX_F32)", a->dtype);
+    LNX_CHECK(a->H > 0 && a->W > 0 && a->H % 4 == 0 && a->W % 4 == 0, "lnx_stem_dgrad: H=%d W=%d must be positive multiples of 4", a->H, a->W);
+    LNX_CHECK(a->B > 0 && a->Cin >= 1 && a->Cin <= 4 && (a->Cout == 96 || a->Cout == 128 || a->Cout == 192 || a->Cout == 256),
+              "lnx_stem_dgrad: unsupported geometry B=%d Cin=%d Cout=%d (Cin 1..4, Cout in {96, 128, 192, 256}; otherwise lnx_gemm_nt + lnx_col2im_stem)", a->B, a->Cin,
+              a->Cout);
+    const int epv = a->dtype == LNX_BF16 ? 8 : 4;
+    LNX_CHECK(a->ldy >= a->Cout && a->ldy % epv == 0, "lnx_stem_dgrad: ldy=%lld must be >= Cout and a multiple of %d", (long long)a->ldy, epv);
+    LNX_CHECK((((uintptr_t)a->dy) & 15) == 0 && (((uintptr_t)a->w) & 15) == 0 && (((uintptr_t)a->dx) & 15) == 0, "lnx_stem_dgrad: operands must be 16-byte aligned");
+    const int64_t M64 = (int64_t)a->B * (a->H / 4) * (a->W / 4);
+    LNX_CHECK(M64 < (int64_t)0x7fffffff - 16, "lnx_stem_dgrad: too many patches (%lld)", (long long)M64);
+    StemDgP p;
+    p.dy = a->dy; p.ldy = a->ldy; p.w = a->w; p.dx = a->dx;
+    p.B = a->B; p.Cin = a->Cin; p.H = a->H; p.W = a->W; p.Ho = a->H / 4; p.Wo = a->W / 4; p.M = (int)M64;
+    const int tiles = cdiv(p.M, 16);
+    int grid = cdiv(tiles, 4);
+    const int cap = a->dtype == LNX_BF16 ? 1024 : 512;  // a few resident workgroups per CU: the W fragments / the LDS image are loaded once per workgroup
+    if (grid > cap) grid = cap;
+    hipStream_t st = (hipStream_t)stream;
+#define DGRAD_(NKV)                                                                                                   \
+    do {                                                                                                              \
+        if (a->dtype == LNX_BF16) hipLaunchKernelGGL((stem_dgrad_bf16_kernel<NKV>), dim3(grid), dim3(256), 0, st, p); \
+        else hipLaunchKernelGGL((stem_dgrad_f32_kernel<NKV>), dim3(grid), dim3(256), 0, st, p);                       \
+    } while (0)
+    switch (a->Cout) {
+        case 96: DGRAD_(3); break;
+        case 128: DGRAD_(4); break;
+        case 192: DGRAD_(6); break;
+        default: DGRAD_(8); break;
+    }
+#undef DGRAD_
+    LNX_LAUNCH_CHECK();
+    return 0;
+}

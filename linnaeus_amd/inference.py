@@ -375,3 +375,46 @@ class DevicePreprocessor:
             self._done.record(stream)
         del descs
         return out
+
+
+def input_attribution(model, images, aux=None, task=None, class_index=None, kind: str = "grad"):
+    """Which pixels and which metadata components a class logit depends on: one eval-mode forward and one backward of the HIP plan with
+    the inputs as the differentiated leaves (the plan's backward then runs down to the image and to the metadata, whatever is frozen:
+    `lnx_plan_set_input_grads`), seeded with the chosen logit of every sample.
+
+    task: a key of the model's output dict (default: the first task); class_index: an int, a [B] integer tensor, or None = each
+    sample's predicted (argmax) class of `task`.  kind = "grad": `image` is the channel-max of |d logit / d image|; "grad_x_input": the
+    channel-sum of gradient * image.  Returns {"image": [B, H, W], "meta": {component: [B]}}; `meta` holds the L2 norm of each metadata
+    component's slice of d logit / d aux (empty for a model without metadata components).  First-order only."""
+    if kind not in ("grad", "grad_x_input"):
+        raise ValueError(f"kind must be 'grad' or 'grad_x_input', got {kind!r}")
+    has_meta = bool(getattr(model, "use_meta", False) and getattr(model, "meta_dims", None))
+    x = images.detach().float().contiguous().requires_grad_(True)
+    m = aux.detach().float().contiguous().requires_grad_(True) if (has_meta and aux is not None) else aux
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.enable_grad():
+            out = model(x, m)
+            key = task if task is not None else next(iter(out))
+            if key not in out:
+                raise KeyError(f"unknown task {key!r}; the model's tasks are {list(out)}")
+            logits = out[key].float()
+            if class_index is None:
+                idx = logits.detach().argmax(-1)
+            elif isinstance(class_index, int):
+                idx = torch.full((logits.shape[0],), class_index, device=logits.device, dtype=torch.long)
+            else:
+                idx = torch.as_tensor(class_index, device=logits.device).long().reshape(-1)
+            seed = logits.gather(1, idx.unsqueeze(1)).sum()
+            leaves = [x] + ([m] if (has_meta and m is not None) else [])
+            grads = torch.autograd.grad(seed, leaves)
+    finally:
+        model.train(was_training)
+    dx = grads[0]
+    image = dx.abs().amax(1) if kind == "grad" else (dx * x.detach()).sum(1)
+    meta = {}
+    if len(grads) > 1:
+        for name, info in model.meta_components.items():
+            meta[name] = grads[1][:, info["offset"]: info["offset"] + info["dim"]].norm(dim=1)
+    return {"image": image, "meta": meta}

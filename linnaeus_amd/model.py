@@ -158,8 +158,17 @@ class _PlanFn(torch.autograd.Function):
                     v.zero_()
                 else:
                     v.copy_(d)
+        # input gradients (a plan made for them: _run saw x / meta requiring grad): fresh tensors the plan writes in full, never views
+        # of the workspace, so autograd may keep or accumulate them as it does any other gradient
+        x, meta, _ = st["saved_inputs"][:3]
+        want_x, want_meta = st["want"]
+        dx = torch.empty_like(x) if (want_x and ctx.needs_input_grad[1]) else None
+        dmeta = torch.empty_like(meta) if (want_meta and meta is not None and ctx.needs_input_grad[2]) else None
+        if want_x or want_meta:
+            L.check(L.lib().lnx_plan_bind_input_grads(st["handle"], C.c_void_p(dx.data_ptr()) if dx is not None else None,
+                                                      C.c_void_p(dmeta.data_ptr()) if dmeta is not None else None), "lnx_plan_bind_input_grads")
         grads = ctx.model._plan_backward(st, dfeats, dlogits)
-        return (None, None, None, None, *grads)
+        return (None, dx, dmeta, None, *grads)
 
 
 @register_model("mFormerV1")
@@ -603,11 +612,12 @@ class mFormerV1(nn.Module):
         finally:
             lib.lnx_plan_destroy(handle)
 
-    def _get_plan(self, B: int, H: int, W: int, train: bool = True, recompute: bool = False) -> Dict[str, Any]:
+    def _get_plan(self, B: int, H: int, W: int, train: bool = True, recompute: bool = False, want=(False, False)) -> Dict[str, Any]:
         """Native plan for one (batch, image size, dtype, train/inference, recompute) combination.  Inference plans (no_grad /
         frozen model) carry no backward scratch and share activation buffers between blocks; recompute plans (gradient
         checkpointing) keep block inputs only.  The cache is a small LRU: an evicted plan is destroyed and its workspace freed."""
         recompute = bool(train and recompute)
+        want = (bool(train and want[0]), bool(train and want[1]))  # (image, metadata) gradients: lnx_plan_set_input_grads
         # the freeze state at forward time: frozen parameters select (or create) a plan of their own, whose backward stops at the
         # first unit that trains; with everything trainable the key and the plan are those of a model that never froze anything
         def lookup():
@@ -615,6 +625,8 @@ class mFormerV1(nn.Module):
             key = (B, H, W, self._dtype_code, self._fp8, bool(train), recompute)
             if mask is not None:
                 key = key[:-1] + (mask, recompute)
+            if any(want):  # (without input gradients the key, and the plan, are those of a model that never asked for any)
+                key = key + (want,)
             return mask, key, self._plans.get(key)
 
         mask, key, st = lookup()
@@ -637,12 +649,14 @@ class mFormerV1(nn.Module):
             tasks = self._task_list()
             handle = C.c_void_p()
             L.check(lib.lnx_plan_create(C.byref(cfg), C.byref(handle)), "lnx_plan_create")
-            if mask is not None:
-                try:
+            try:
+                if any(want):  # first: with a flag set the mask may say that nothing trains
+                    L.check(lib.lnx_plan_set_input_grads(handle, int(want[0]), int(want[1])), "lnx_plan_set_input_grads")
+                if mask is not None:
                     L.check(lib.lnx_plan_set_trainable(handle, mask), "lnx_plan_set_trainable")
-                except L.LnxError:
-                    lib.lnx_plan_destroy(handle)
-                    raise
+            except L.LnxError:
+                lib.lnx_plan_destroy(handle)
+                raise
             if not getattr(self, "_wgrad_stream", True) and lib.lnx_plan_set_wgrad_stream(handle, 0) < 0:
                 L.check(1, "lnx_plan_set_wgrad_stream")
             if getattr(self, "_meta_stream", None) is not None and lib.lnx_plan_set_meta_stream(handle, self._meta_stream) < 0:
@@ -671,7 +685,7 @@ class mFormerV1(nn.Module):
                       ndrop=lib.lnx_plan_num_drop_calls(handle), logits_numel=lib.lnx_plan_logits_numel(handle),
                       logit_off=[lib.lnx_plan_logits_offset(handle, i) for i in range(len(tasks))],
                       logit_ld=[lib.lnx_plan_logits_ld(handle, i) for i in range(len(tasks))], tasks=tasks, B=B, fwd_id=0, train=bool(train),
-                      trains=[True] * n if mask is None else [bool(m) for m in mask])
+                      trains=[True] * n if mask is None else [bool(m) for m in mask], want=want)
             self._plans[key] = st
         self._ensure_bound(st)
         return st
@@ -977,8 +991,12 @@ class mFormerV1(nn.Module):
             meta = meta.float().contiguous()
         else:
             meta = None
-        train = torch.is_grad_enabled() and any(p_.requires_grad for p_ in self.parameters())
-        st = self._get_plan(B, H, W, train, self._wants_recompute(force_checkpointing))
+        # a training plan also when only an INPUT is differentiated (saliency, metadata sensitivity, adversarial examples): its backward
+        # then runs down to that input whatever is frozen; in eval mode such a plan runs without DropPath and dropout
+        grad_on = torch.is_grad_enabled()
+        want = (grad_on and x.requires_grad, grad_on and meta is not None and meta.requires_grad)
+        train = grad_on and (any(want) or any(p_.requires_grad for p_ in self.parameters()))
+        st = self._get_plan(B, H, W, train, self._wants_recompute(force_checkpointing), want)
         self._active = st
         drop = self._draw_drop_scales(st, B, x.device)
         self._set_dropout(st, train, x.device)

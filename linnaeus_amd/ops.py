@@ -436,6 +436,38 @@ def stem_fwd(x, w, bias, ln_w, ln_b, y, *, patches=None, pre=None, mean=None, rs
     L.check(L.lib().lnx_stem_fwd(C.byref(a), _stream()), "lnx_stem_fwd")
 
 
+def stem_dgrad_ok(dtype_code: int, Cin: int, H: int, W: int, Cout: int) -> bool:
+    return bool(L.lib().lnx_stem_dgrad_ok(dtype_code, Cin, H, W, Cout))
+
+
+def stem_dgrad(dy, w, dx, *, Cout=None):
+    """dx fp32 [B, Cin, H, W] = unpatchify(dy . w): the transpose of Conv2d(Cin, Cout, 4, 4).  dy [M, ldy] (bf16 or fp32, the first Cout
+    columns count; ldy = dy.stride(0)), w [Cout, 64] of dy's dtype.  Every element of dx is written."""
+    a = L.StemDgradArgs()
+    a.dtype = code_of(dy)
+    a.B, a.Cin, a.H, a.W = dx.shape
+    a.Cout = Cout if Cout is not None else w.shape[0]
+    a.dy, a.ldy, a.w, a.dx = _p(dy), dy.stride(0), _p(w), _p(dx)
+    L.check(L.lib().lnx_stem_dgrad(C.byref(a), _stream()), "lnx_stem_dgrad")
+
+
+def col2im_stem(patches, dx):
+    """The inverse of im2col_stem: patches [M, ldp] (column k = c*16 + kh*4 + kw) -> dx fp32 [B, Cin, H, W], every element written."""
+    B, Cin, H, W = dx.shape
+    L.check(L.lib().lnx_col2im_stem(_p(patches), code_of(patches), patches.stride(0), B, Cin, H, W, _p(dx), _stream()), "lnx_col2im_stem")
+
+
+def meta_input_grad(heads, dmeta, *, accumulate=False):
+    """dmeta[b, off + j] (+)= sum_o dp0[b, o] w0[o, j] for every (dp0 [B, C], w0 [C, ldw0 >= dim], dim, off) of `heads` (at most
+    LNX_MAX_META, disjoint column ranges), fp32, one launch, a fixed summation order."""
+    arr = (L.MetaInputGradArgs * max(len(heads), 1))()
+    for a, (dp0, w0, dim, off) in zip(arr, heads):
+        a.B, a.C = dp0.shape
+        a.dim, a.off = dim, off
+        a.dp0, a.lddp0, a.w0, a.ldw0 = _p(dp0), dp0.stride(0), _p(w0), w0.stride(0)
+    L.check(L.lib().lnx_meta_input_grad(arr, len(heads), _p(dmeta), dmeta.stride(0), int(bool(accumulate)), _stream()), "lnx_meta_input_grad")
+
+
 def scale_cast(inp, out, M, Cc, *, ldin=None, in_map=None, rowscale=None, rows_per_sample=0, ldout=None):
     L.check(L.lib().lnx_scale_cast(_p(inp), C.c_int64(ldin if ldin is not None else inp.stride(-2)), _map(in_map), _p(rowscale), rows_per_sample,
                                    _p(out), code_of(out), C.c_int64(ldout if ldout is not None else out.stride(-2)), M, Cc, _stream()), "lnx_scale_cast")
